@@ -10,6 +10,12 @@ Positions are generated on device from the lattice, so there is no host input to
   python bench.py --gpus N --steps K --warmup W            (N>1: launched by torch.distributed.run)
 
 Prints ONE JSON line (rank 0). value = total SDF evaluations of all ranks / max-over-ranks time.
+
+A plain run sets up, warms up, times the K steps and prints the line. --full adds every measurement beside the headline,
+each after the timed loop: the roofline objects (blocking meshes with the device to itself, the live copy-kernel yardstick),
+the distinct-rows / distinct-points meshes, the other gather modes (N > 1), the host-inclusive, drop-in and one-shot
+timings and the CPU baseline. --dump-outputs DIR writes what the timed loop's last step computed to DIR/<name>.npy
+(dump_outputs below).
 """
 import argparse
 import json
@@ -21,6 +27,51 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
+DUMP_BYTES = 48 << 20  # what --dump-outputs writes at most (under the 64 MB a dump may take)
+
+
+def triangle_sample(tris, budget=DUMP_BYTES):
+    """A fixed sample of a triangle set that does not depend on the order the device emitted it in: the triangles whose 32-bit
+    hash of their nine coordinates' bits falls in one of 2^k buckets (k the smallest that fits `budget`), sorted bitwise.
+    Two builds that make the same triangle set give the same array; one triangle more or less changes one row. (m, 9) float32."""
+    import numpy as np
+    t = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 9)
+    k = 0
+    while (t.shape[0] * 36) >> k > budget:
+        k += 1
+    if k:
+        u = t.view(np.uint32)
+        h = np.full(t.shape[0], 2166136261, np.uint32)  # FNV-1a over the nine words, then a final mix
+        for c in range(9):
+            h ^= u[:, c]
+            h *= np.uint32(16777619)
+        h ^= h >> np.uint32(15)
+        h *= np.uint32(0x2C1B3C6D)
+        h ^= h >> np.uint32(12)
+        t = t[(h & np.uint32((1 << k) - 1)) == 0]
+    t = t[np.lexsort(t.view(np.uint32).T[::-1])]
+    return t[:budget // 36]
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: every array as d/<name>.npy (float32 / float64)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
+def mesh_outputs(mesh, evals):
+    """What a caller of a mesh receives: its triangles (triangle_sample of them) and counts = [triangles, evaluations]."""
+    import numpy as np
+    if hasattr(mesh, "RenderAll"):
+        tris = mesh.RenderAll()
+    else:  # the torch.distributed gather's result: a device tensor of triangles
+        tris = mesh.detach().cpu().numpy()
+    tris = tris.reshape(-1, 9)
+    return {"triangles": triangle_sample(tris), "counts": np.array([tris.shape[0], evals], np.float64)}
 
 
 def cpu_baseline(shader, scene, resdiv, threads):
@@ -361,6 +412,9 @@ def eval_mode(args, torch, np, hip, shader, sdf, res, dev):
     dt = time.perf_counter() - t0
     k_ms = ev0.elapsed_time(ev1) / args.steps
     achieved = n * 16.0 / (k_ms * 1e-3) / 1e9
+    if args.dump_outputs:  # the distances of the last launch, every step-th one if all of them exceed the budget
+        stride = -(-n * 4 // DUMP_BYTES)
+        dump_outputs(args.dump_outputs, {"distances": dist[::stride].cpu().numpy()})
     print(json.dumps({
         "metric": "sdf_evals_per_s", "value": n * args.steps / dt, "unit": "evals/s", "n_gpus": 1, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
@@ -390,6 +444,8 @@ def flat_mode(args, torch, np, hip, shader, sdf, res, spec_note):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     ev, nt = int(f.stats.evals), int(f.stats.n_tris)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, mesh_outputs(f, ev))
     g_ms /= args.steps
     m_ms /= args.steps
     alg_gb = (4.0 * ev + 36.0 * nt) / 1e9
@@ -486,8 +542,17 @@ def main():
                     help="0: every corner of every leaf, as the reference (headline); 1: each bitwise-distinct lattice corner of a brick once (older fused kernel); "
                          "2: the bitwise-distinct z rows of a brick once each (same kernels, same triangles, a quarter fewer evaluations)")
     ap.add_argument("--no-gather-modes", action="store_true",
-                    help="N > 1: skip the two extra timed loops (the gather modes other than --gather) that follow the headline loop")
+                    help="N > 1, --full: skip the two extra timed loops (the gather modes other than --gather) that follow the headline loop")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed loop, also run every measurement beside the headline: roofline objects (blocking meshes, copy-kernel "
+                         "yardstick), distinct rows / points, the other gather modes, host-inclusive, drop-in and one-shot timings, CPU baseline "
+                         "(the --no-* options above skip single ones of them)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy: mesh modes triangles.npy (a fixed, "
+                         "order-independent sample of at most 48 MB, sorted) and counts.npy ([triangles, evaluations]); eval mode distances.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` as the driver starts the N = 1 line: become the launcher -- one rank per GPU under
@@ -799,13 +864,19 @@ def main():
 
     run_meshes(args.preheat)
     H = timed_loop()  # the headline: the gather mode --gather names (default all)
+    if args.dump_outputs:
+        if rank == 0:  # what rank 0's caller holds after the last step: the gathered mesh, or its own (gather none, N = 1)
+            lo, lg = H["last"]
+            dump_outputs(args.dump_outputs, mesh_outputs(lg if lg is not None else lo, lo.stats.evals))
+        if dist is not None:
+            barrier()
     gather_modes = None
     if comm is not None:
         # Beside the headline, after it: the SAME loop with the other two gather modes, so that one N > 1 run separates what the
         # compute scales to (none: every rank keeps its shard) from what the wire allows (root, all) -- xGMI is one ~60 GB/s link per
         # peer, one GPU emits triangles at 400 GB/s
         gather_modes = {args.gather: gather_report(H)}
-        if not args.no_gather_modes:
+        if args.full and not args.no_gather_modes:
             for mode in ("all", "root", "none"):
                 if mode != args.gather:
                     use_gather(mode)
@@ -816,15 +887,16 @@ def main():
     records = H["records"]
 
     # The dominant kernel ALONE, after the timed loops: blocking meshes of rank 0's shard with the device to itself (the other
-    # ranks wait at the barrier -- they may share rank 0's device), no gather. Every line takes its roofline from these.
-    barrier()
+    # ranks wait at the barrier -- they may share rank 0's device), no gather. Every --full line takes its roofline from these.
     alone = None
-    if rank == 0 and not dc:
-        alone = [hip.OctreeHIP(sdf, res, shard_rank=rank, shard_count=world, share_corners=args.share_corners).stats for _ in range(8)][2:]
-    elif rank == 0:
-        alone = [hip.DualContourHIP(sdf, res, shard_rank=rank, shard_count=world) for _ in range(4)][1:]
-        alone_stage_ms = [a.stage_ms() for a in alone]
-    barrier()
+    if args.full:
+        barrier()
+        if rank == 0 and not dc:
+            alone = [hip.OctreeHIP(sdf, res, shard_rank=rank, shard_count=world, share_corners=args.share_corners).stats for _ in range(8)][2:]
+        elif rank == 0:
+            alone = [hip.DualContourHIP(sdf, res, shard_rank=rank, shard_count=world) for _ in range(4)][1:]
+            alone_stage_ms = [a.stage_ms() for a in alone]
+        barrier()
 
     if rank == 0:
         oc, g = last
@@ -834,9 +906,11 @@ def main():
                     + f"(res {float(res):.7f}, {st.levels} levels)")
         kern = sdf.info()["kernels"]
         code = kern.get("code")
-        dc_stages = None
+        dc_stages = rf = None
         two_kernel = emit_ms > 0 or (alone is not None and not dc and alone[0].ms_emit > 0)  # leaf phase = leaf_eval_kernel (dominant) + march_records_kernel
-        if dc:
+        if alone is None:
+            pass  # (plain run: the roofline objects take runs of their own, --full)
+        elif dc:
             # five stages, timed apart by HIP events (gsdf_hip_mesh_stage_ms): the roofline is the longest one's
             sm = {k: sum(a[k] for a in alone_stage_ms) / len(alone_stage_ms) for k in alone_stage_ms[0]}
             nc, ne, nq, no = float(st.leaf_cubes), float(st.active_leaves), float(st.n_tris) / 2, float(st.evals_prune)
@@ -911,13 +985,15 @@ def main():
                                 else "one blocking mesh call per step"},
             "triangles_per_s": tris_all / dt,
             "triangles_per_step": tris_all / args.steps, "evals_per_step": evals_all / args.steps,
-            "roofline": rf,
-            "stages": dc_stages,
             "phase_ms_rank0": {"prune": st.ms_prune, "leaf": st.ms_leaf, "eval_kernel": st.ms_march, "march_kernel": st.ms_emit, "total_device": st.ms_total},
             "phase_note": ("event-to-event spans of the timed loop's LAST mesh" + (": it shares the device with the other mesh in flight, so the spans overlap the other chain's kernels "
-                           "(a mesh with the device to itself: roofline.ms_per_mesh_device_alone)" if mesh_pipeline else "")),
+                           "(a mesh with the device to itself: roofline.ms_per_mesh_device_alone, --full)" if mesh_pipeline else "")),
+            "full": args.full,
         }
-        if not dc and two_kernel:
+        if args.full:
+            out["roofline"] = rf
+            out["stages"] = dc_stages
+        if args.full and not dc and two_kernel:
             # march_records_kernel alone (the same blocking meshes): its two streams against the HBM peak and against what a plain
             # HIP copy kernel of as many bytes reaches on this part (tools/ubench/copy_rate.hip; profiles/r6m_copy_rate.txt)
             m_ms = sum(a.ms_emit for a in alone) / len(alone)
@@ -934,7 +1010,7 @@ def main():
         if shared_device:
             out["config"]["devices"] = (f"{world} ranks on {ndev} GPU(s): ranks share a device over the library's inter-process transport (GSDF_HIP_COMM=ipc) -- "
                                         "the N > 1 code path end to end, not a scaling measurement")
-        if mesh_pipeline and not dc and args.share_corners == 0 and not args.no_distinct_rows:
+        if args.full and mesh_pipeline and not dc and args.share_corners == 0 and not args.no_distinct_rows:
             # Beside the headline, not in it: the same mesh with the evaluations the reference repeats left out (gsdf_mesh_opts.share_corners;
             # the triangle set is bit-identical, tests/test_gpu_mesh.py) -- time to mesh for a caller who does not need the reference's
             # evaluation count. Same pipelined loop, after the timed region. 2: every bitwise-distinct z row of a brick once (the
@@ -967,16 +1043,17 @@ def main():
             out["phase_ms_rank0"]["gather"] = gh["ms_payload"]
             out["phase_ms_rank0"]["gather_march"] = gh["ms_march_after_gather"]
             out["gather"] = dict(gh, note="rank 0, HIP events on the communicator's stream; a step = one mesh + its gather")
+        if gather_modes and args.full:
             out["gather_modes"] = dict(gather_modes, note="the same K-step loop once per mode, one after the other in this run; the headline (`value`, `ms_per_step`) is mode "
                                        + args.gather + "; `none` is what the compute scales to, `root` / `all` add the wire")
-        if world == 1 and comm is None and not dc:
+        if args.full and world == 1 and comm is None and not dc:
             out["host_inclusive"] = guarded(host_inclusive, hip, sdf, res)
-        if world == 1 and comm is None and not dc and not args.no_evaluate_dropin and args.scene != "text-plate":
+        if args.full and world == 1 and comm is None and not dc and not args.no_evaluate_dropin and args.scene != "text-plate":
             out["evaluate_dropin"] = guarded(evaluate_dropin, hip, sdf, shader)
-        if world == 1 and comm is None and not dc and not args.no_one_shot and not args.interpreter:
+        if args.full and world == 1 and comm is None and not dc and not args.no_one_shot and not args.interpreter:
             out["one_shot"] = guarded(one_shot, hip, shader, res)
         # (last: its 255 host threads leave the host's clocks and caches in a state the host-side measurements above should not see)
-        if world == 1 and not args.no_cpu_baseline and not dc:
+        if args.full and world == 1 and not args.no_cpu_baseline and not dc:
             threads = max(1, (os.cpu_count() or 2) - 1)  # GOMAXPROCS-1 (gsdfaux/gsdfaux.go:162-164)
             # bounded sample of the SAME workload: full resdiv 1600 lattice (420 M evals) on big hosts, coarser on small ones
             cpu_rd = args.cpu_resdiv or (args.resdiv if threads >= 64 else (1000 if threads >= 16 else 600))

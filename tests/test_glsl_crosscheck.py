@@ -5,17 +5,15 @@ bodies (translated statement by statement, strings verbatim) and interprets it. 
 parity corpus -- every node type, the forge/threads parts and the four BASELINE scenes (npt-flange, bolt, knurled-cylinder, glyph
 plate), three of which have no reference-held triangle count to pin them. Supplementary evidence: it shows restatement == the
 reference's formulas where no answer is held; it does not replace a Go run (evaluation order, float32 rounding and math32's own
-routines are not exercised by it). Build container only: it reads /root/reference (skipped where that does not exist)."""
+routines are not exercised by it). What the interpreted GLSL returns at the compared points is stored in
+tests/golden/glsl_reference_distances.npz (tests/golden/make_glsl_golden.py renders it from a checkout of the reference), so the
+comparison needs no reference tree."""
 import os
 import sys
 
 import numpy as np
-import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import corpus  # noqa: E402
-
-pytestmark = pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="needs the reference tree (build container)")
 
 REF_TOL = 5e-3    # the reference's own CPU <-> GPU tolerance (gsdf_test.go:529)
 TIGHT_TOL = 1e-4  # what the two statements actually agree to on these parts (float32 noise of trees a few units across)
@@ -40,29 +38,24 @@ def _reachable(tree):
 
 
 def test_reference_glsl_agrees_with_the_oracle_on_the_corpus():
-    from glslref.glsl import Interp
-    from glslref.goshader import Reference, STRUCT
+    from glslref.goshader import STRUCT
     from gsdf_amd._ctypes_common import OPS
     from oracle.oracle import OracleSDF
-    ref = Reference()
-    assert len(ref.body) == 55                      # every shader node struct of the reference has a body to render
-    _, s3 = corpus.shapes3d()
-    _, s2 = corpus.shapes2d()
-    _, sz = corpus.bezier2d()
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+    import make_glsl_golden
+    gold = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "glsl_reference_distances.npz"))
+    assert int(gold["n_bodies"]) == 55              # every shader node struct of the reference had a body to render
+    shapes = make_glsl_golden.shapes()
+    assert sorted("pos_" + n for n, _, _ in shapes) == sorted(f for f in gold.files if f.startswith("pos_"))
     rng = np.random.default_rng(11)
     covered, rows = set(), []
-    for name, s, dim in [(n, s, 3) for n, s in s3] + [(n, s, 2) for n, s in s2 + sz]:
+    for name, s, dim in shapes:
         tree = s.tree()
         covered |= {STRUCT[OPS[tree.nodes[i].op]] for i in _reachable(tree)}
-        src, root, _ = ref.program(tree)
-        prog = Interp(src)
-        bb = s.Bounds().astype(np.float64)
-        lo, hi = (bb[:3], bb[3:]) if dim == 3 else (bb[[0, 1]], bb[[3, 4]])
-        c, h = (lo + hi) / 2, (hi - lo) / 2 * 1.25 + 1e-3
-        n = 60 if tree.n_nodes and name == "scene_glyph_plate" else 120
-        pos = (c + (rng.random((n, dim)) * 2 - 1) * h).astype(np.float32)
+        pos = gold["pos_" + name]
+        assert (pos.view(np.uint32) == make_glsl_golden.points(rng, name, s, dim).view(np.uint32)).all(), name  # the corpus is the fixture's
         want = OracleSDF(tree).Evaluate(pos)
-        got = np.array([prog.call(root, [p.astype(np.float64)]) for p in pos])
+        got = gold["glsl_" + name]
         ok = np.isfinite(got)
         assert ok.mean() > 0.98, (name, int((~ok).sum()))   # (a degenerate branch of a GLSL body may be undefined at a point: pow of a negative, 0/0)
         err = float(np.abs(got[ok] - want[ok]).max())

@@ -361,7 +361,7 @@ def test_bench_self_launches_two_ranks_on_one_gpu(gpu):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(GSDF_HIP_COMM="ipc", HSA_ENABLE_IPC_MODE_LEGACY="0", GSDF_HIP_IPC_TIMEOUT_S="120")
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--preheat", "3", "--resdiv", "400"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--preheat", "3", "--resdiv", "400", "--full"]
     pr = subprocess.run(cmd, env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert pr.returncode == 0, pr.stderr.decode(errors="replace")[-3000:]
     lines = [l for l in pr.stdout.decode().splitlines() if l.startswith("{")]

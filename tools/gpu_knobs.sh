@@ -1,7 +1,7 @@
 #!/bin/bash
 # round 6: the grid-size knobs again, now that three meshes are in flight and the marching kernel is a different one
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp
-run() { python bench.py --steps 30 --no-cpu-baseline --no-evaluate-dropin --no-distinct-rows --no-one-shot 2>/dev/null | python -c "
+run() { python bench.py --full --steps 30 --no-cpu-baseline --no-evaluate-dropin --no-distinct-rows --no-one-shot 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']; m=d['roofline_march']
 print('$1', 'ms/step', round(d['ms_per_step'],4), 'eval alone', round(r['kernel_ms'],4), 'march', round(m['kernel_ms'],4), 'device alone', round(r['ms_per_mesh_device_alone'],4))"; }

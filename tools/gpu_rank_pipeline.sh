@@ -9,7 +9,7 @@ d=json.loads(l[-1]); print(d["n_gpus"], d["steps"], round(d["ms_per_step"],4), {
 for n in 2 3; do for a in "" "--no-mesh-pipeline" "--payload triangles" "POOL4"; do
   echo "== $n ranks $a"
   if [ "$a" = "POOL4" ]; then export GSDF_HIP_POOL_MAX=4; a=""; else unset GSDF_HIP_POOL_MAX; fi
-  GSDF_HIP_COMM=ipc HSA_ENABLE_IPC_MODE_LEGACY=0 timeout 600 python bench.py --gpus $n --steps 200 --no-cpu-baseline $a 2>gpurun_out/rt.err | python -c "$P" || grep -i "fault\|error" gpurun_out/rt.err | head -3
+  GSDF_HIP_COMM=ipc HSA_ENABLE_IPC_MODE_LEGACY=0 timeout 600 python bench.py --full --gpus $n --steps 200 --no-cpu-baseline $a 2>$TMPDIR/rt.err | python -c "$P" || grep -i "fault\|error" $TMPDIR/rt.err | head -3
 done; done
 unset GSDF_HIP_POOL_MAX
 bash tools/gpu_dist1.sh 2>&1 | cut -c1-200 | tail -16
