@@ -1,6 +1,7 @@
 // abi_eval.hip -- C ABI (include/gsdf_hip.h), evaluator side: program handles and their run-time specialisation, the
 // gleval.SDF3 / SDF2 Evaluate drop-ins (host buffers, pipelined tickets, registered memory, device-resident), central-difference
-// normals, the 2-D image renderer, the block cache. Kernels: kernels_eval.h over the interpreter of interp.h.
+// normals, the 2-D image renderer, the UI's view of a 3-D part, the block cache. Kernels: kernels_eval.h and kernels_view.h over
+// the interpreter of interp.h.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -13,6 +14,7 @@
 
 #include "kernels_common.h"
 #include "kernels_eval.h"
+#include "kernels_view.h"
 #include "abi_program.h"
 
 extern "C" int gsdf_hip_init(int device) {
@@ -300,6 +302,23 @@ void spec_leaf_dense(gsdf_program* p) {
     const bool ok = fn_scratch_bytes(f[i]) == 0;
     spec_report("specialised", names[i], f[i], ok && !p->f_leaf_dense);
     if (ok && !p->f_leaf_dense) { p->f_leaf_dense = f[i]; p->spec_leaf_dense_w = ws[i]; }
+  }
+}
+
+// view_kernel, both forms (kernels_view.h), for a specialised handle: built at its first frame, in a module of its own that includes
+// kernels_common.h and kernels_view.h only (specialize.cpp: spec_includes). A form that fails to build or needs scratch stays on the
+// interpreter kernel.
+void spec_view(gsdf_program* p) {
+  if (!p->spec_mod || p->spec_view_tried || p->prog.is2d) return;
+  p->spec_view_tried = true;
+  const std::vector<std::string> names = {"view_kernel<true>", "view_kernel<false>"};
+  std::vector<hipFunction_t> f;
+  if (spec_build(p, names, &p->spec_mod_view, f, &p->spec_compile_s) != GSDF_OK) return;
+  hipFunction_t* dst[2] = {&p->f_view, &p->f_view_plain};
+  for (int i = 0; i < 2; i++) {
+    const bool ok = fn_scratch_bytes(f[(size_t)i]) == 0;
+    spec_report("specialised", names[(size_t)i], f[(size_t)i], ok);
+    *dst[i] = ok ? f[(size_t)i] : nullptr;
   }
 }
 
@@ -602,6 +621,7 @@ extern "C" void gsdf_hip_program_destroy(gsdf_program* p) {
   if (p->spec_mod_dz) (void)hipModuleUnload(p->spec_mod_dz);
   if (p->spec_mod_k1) (void)hipModuleUnload(p->spec_mod_k1);
   if (p->spec_mod_dense) (void)hipModuleUnload(p->spec_mod_dense);
+  if (p->spec_mod_view) (void)hipModuleUnload(p->spec_mod_view);
   p->q0.release(); p->q1.release(); p->ctr.release();
   p->rec.release(); p->hdr.release(); p->grp.release();
   p->b_q0.release(); p->b_q1.release(); p->b_ctr.release(); p->b_spec_pass.release(); p->b_rec.release(); p->b_hdr.release(); p->b_grp.release();
@@ -948,6 +968,131 @@ extern "C" int gsdf_hip_image2(gsdf_program* p, int w, int h, float* dist_out, u
   if (rgba_out) HIP_TRY(hipMemcpyAsync(rgba_out, dc.p, n * 4, hipMemcpyDeviceToHost, p->stream));
   HIP_TRY(hipStreamSynchronize(p->stream));
   p->evals += n;
+  return GSDF_OK;
+}
+
+// ---- the UI's view of a 3-D part (gsdfaux.UI, gsdfaux/ui.go:247-355): camera helper and frame --------------------------------
+namespace {
+// math32.Hypot (scaffold/ms.hpp: hypotf32): the bounds' Diagonal() = Norm(Size()) by nested hypot
+float hypot32(float p, float q) {
+  if (std::isinf(p) || std::isinf(q)) return INFINITY;
+  if (p != p || q != q) return NAN;
+  p = std::fabs(p); q = std::fabs(q);
+  if (p < q) std::swap(p, q);
+  if (p == 0) return 0;
+  q = q / p;
+  return p * std::sqrt(1 + q * q);
+}
+void normalize3(const float a[3], float out[3]) {
+  const float len = std::sqrt((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]);
+  out[0] = a[0] / len; out[1] = a[1] / len; out[2] = a[2] / len;
+}
+void cross3(const float a[3], const float b[3], float out[3]) {
+  out[0] = a[1] * b[2] - a[2] * b[1];
+  out[1] = a[2] * b[0] - a[0] * b[2];
+  out[2] = a[0] * b[1] - a[1] * b[0];
+}
+bool finite_all(const float* v, int n) {
+  for (int i = 0; i < n; i++) if (!std::isfinite(v[i])) return false;
+  return true;
+}
+}  // namespace
+
+// ui.go:18 (diag), 123 (camDist = diag), 220 (charDist = camDist + diag), 276-297 (orbit camera). Host only.
+extern "C" int gsdf_hip_view_orbit(const float bb[6], float yaw, float pitch, float cam_dist, const float target[3], gsdf_view* view) {
+  if (!bb || !view) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  if (!finite_all(bb, 6) || !std::isfinite(yaw) || !std::isfinite(pitch) || !std::isfinite(cam_dist) || (target && !finite_all(target, 3)))
+    return fail(GSDF_ERR_BAD_ARGUMENT, "non-finite bounds, angle, distance or target");
+  const float diag = hypot32(bb[3] - bb[0], hypot32(bb[4] - bb[1], bb[5] - bb[2]));
+  const float cd = cam_dist > 0.f ? cam_dist : diag;
+  if (!(cd > 0.f) || !std::isfinite(cd + diag)) return fail(GSDF_ERR_BAD_ARGUMENT, "empty bounds and no camera distance");
+  const float kPi = 3.14159265359f;  // ui.go:269
+  const float lim_lo = -kPi / 2.0f + 0.01f, lim_hi = kPi / 2.0f - 0.01f;
+  const float pc = std::fmin(std::fmax(pitch, lim_lo), lim_hi);
+  const float cp = (float)std::cos((double)pc), sp = (float)std::sin((double)pc);
+  const float cy = (float)std::cos((double)yaw), sy = (float)std::sin((double)yaw);
+  const float dir[3] = {cp * sy, sp, cp * cy};
+  const float ta[3] = {target ? target[0] : 0.f, target ? target[1] : 0.f, target ? target[2] : 0.f};
+  gsdf_view v;
+  std::memset(&v, 0, sizeof v);
+  float fwd[3], right[3];
+  for (int a = 0; a < 3; a++) v.ro[a] = ta[a] - dir[a] * cd;
+  for (int a = 0; a < 3; a++) fwd[a] = ta[a] - v.ro[a];
+  normalize3(fwd, v.ww);
+  const float up[3] = {0.f, 1.f, 0.f};
+  cross3(v.ww, up, right);
+  normalize3(right, v.uu);
+  cross3(v.uu, v.ww, v.vv);
+  v.char_dist = cd + diag;
+  v.aa = 1;
+  v.max_steps = 256;
+  if (!finite_all(v.ro, 3) || !finite_all(v.uu, 3) || !finite_all(v.vv, 3) || !finite_all(v.ww, 3))
+    return fail(GSDF_ERR_BAD_ARGUMENT, "degenerate camera (the camera distance vanishes next to the target)");
+  *view = v;
+  return GSDF_OK;
+}
+
+// One UI frame (ui.go:247-355) of a 3-D program: view_kernel over the interpreter, or the handle's specialised build of it.
+// The plain form runs by default: measured against the refilling one (tools/view_bench.py, profiles/view_*), it is 1.3-2x faster on
+// every frame tried. GSDF_HIP_VIEW_REFILL=1 (read at every call; developer knob for the A/B and its parity
+// test) runs the refilling form.
+extern "C" int gsdf_hip_render3(gsdf_program* p, const gsdf_view* view, int w, int h, uint8_t* rgba_out, float* depth_out, uint32_t* evals_out) {
+  if (!p || !view) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  if (p->prog.is2d) return fail(GSDF_ERR_DIMENSION, "program is 2D, render3 called");
+  if (w <= 0 || h <= 0 || w > 16384 || h > 16384) return fail(GSDF_ERR_BAD_ARGUMENT, "bad image size (1 .. 16384 pixels per side)");
+  if (view->aa < 1 || view->aa > 8) return fail(GSDF_ERR_BAD_ARGUMENT, "aa must be 1 .. 8");
+  if (view->max_steps < 0 || view->max_steps > 4096) return fail(GSDF_ERR_BAD_ARGUMENT, "max_steps must be 0 .. 4096");
+  if (!finite_all(view->ro, 3) || !finite_all(view->uu, 3) || !finite_all(view->vv, 3) || !finite_all(view->ww, 3) || !std::isfinite(view->char_dist))
+    return fail(GSDF_ERR_BAD_ARGUMENT, "non-finite camera");
+  const size_t n = (size_t)w * (size_t)h;
+  if (view->max_steps == 0) {  // no sample marches: nothing hits, nothing is evaluated
+    for (size_t i = 0; i < n; i++) {
+      if (rgba_out) { rgba_out[4 * i] = rgba_out[4 * i + 1] = rgba_out[4 * i + 2] = 0; rgba_out[4 * i + 3] = 255; }
+      if (depth_out) depth_out[i] = INFINITY;
+      if (evals_out) evals_out[i] = 0;
+    }
+    return GSDF_OK;
+  }
+  HIP_TRY(hipSetDevice(p->device));
+  spec_adopt(p);  // (a background build that has finished: its kernels from here on)
+  spec_view(p);
+  ViewCam cam;
+  for (int a = 0; a < 3; a++) { cam.ro[a] = view->ro[a]; cam.uu[a] = view->uu[a]; cam.vv[a] = view->vv[a]; cam.ww[a] = view->ww[a]; }
+  cam.tmax = 1.3f * view->char_dist;
+  cam.aa = view->aa; cam.max_steps = view->max_steps; cam.w = w; cam.h = h;
+  cam.tiles_x = (unsigned)((w + VIEW_TILE - 1) / VIEW_TILE);
+  cam.n_claims = cam.tiles_x * (unsigned)((h + VIEW_TILE - 1) / VIEW_TILE) * VIEW_TILE * VIEW_TILE;
+  DevBuf d_rgba, d_depth, d_evals, d_ctr;
+  HIP_TRY(d_rgba.alloc(n * 4));
+  HIP_TRY(d_depth.alloc(n * 4));
+  HIP_TRY(d_evals.alloc(n * 4));
+  HIP_TRY(d_ctr.alloc(16));
+  HIP_TRY(hipMemsetAsync(d_ctr.p, 0, 16, p->stream));
+  const char* e = getenv("GSDF_HIP_VIEW_REFILL");
+  const bool plain = !(e && atoi(e) != 0);
+  const size_t lds = p->lds_bytes(1);
+  // plain: one lane per claim; refilling: persistent, as many workgroups as the CUs hold at once (4 per CU: the launch bounds)
+  unsigned grid = (cam.n_claims + BLOCK - 1) / BLOCK;
+  if (!plain) {
+    const unsigned per_cu = std::max(1u, std::min(4u, (unsigned)((size_t)160 * 1024 / (lds + 64))));
+    grid = std::min(grid, (unsigned)p->num_cu * per_cu);
+  }
+  uint32_t* o_rgba = (uint32_t*)d_rgba.p;
+  float* o_depth = (float*)d_depth.p;
+  uint32_t* o_evals = (uint32_t*)d_evals.p;
+  unsigned long long* o_ctr = (unsigned long long*)d_ctr.p;
+  const hipFunction_t fs = plain ? p->f_view_plain : p->f_view;
+  if (fs) HIP_TRY(launch_fn(fs, grid, BLOCK, lds, p->stream, (const uint32_t*)p->d_code, cam, o_rgba, o_depth, o_evals, o_ctr));
+  else if (plain) hipLaunchKernelGGL((view_kernel<false>), dim3(grid), dim3(BLOCK), lds, p->stream, p->d_code, cam, o_rgba, o_depth, o_evals, o_ctr);
+  else hipLaunchKernelGGL((view_kernel<true>), dim3(grid), dim3(BLOCK), lds, p->stream, p->d_code, cam, o_rgba, o_depth, o_evals, o_ctr);
+  HIP_TRY(hipGetLastError());
+  unsigned long long h_ctr[2] = {0, 0};
+  if (rgba_out) HIP_TRY(hipMemcpyAsync(rgba_out, d_rgba.p, n * 4, hipMemcpyDeviceToHost, p->stream));
+  if (depth_out) HIP_TRY(hipMemcpyAsync(depth_out, d_depth.p, n * 4, hipMemcpyDeviceToHost, p->stream));
+  if (evals_out) HIP_TRY(hipMemcpyAsync(evals_out, d_evals.p, n * 4, hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipMemcpyAsync(h_ctr, d_ctr.p, 16, hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  p->evals += h_ctr[1];
   return GSDF_OK;
 }
 

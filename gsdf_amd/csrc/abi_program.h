@@ -89,6 +89,10 @@ struct gsdf_program {
   bool spec_dense_tried = false;
   int spec_leaf_dense_w = 0;
   size_t lds_dense() const { return (size_t)(prog.nslots * 4 > 8 ? prog.nslots * 4 : 8) * BLOCK * sizeof(float) + 256 + 4 * 512 * sizeof(float) + 4 * 24 * sizeof(float) + 16; }
+  // the UI's view (kernels_view.h: view_kernel<REFILL>, <plain>) for a specialised handle: built on its first frame (spec_view)
+  hipModule_t spec_mod_view = nullptr;
+  hipFunction_t f_view = nullptr, f_view_plain = nullptr;
+  bool spec_view_tried = false;
   double spec_compile_s = 0;
   // Specialisation in the background (gsdf_hip_program_specialize_async): a thread builds and loads the kernels on a shadow handle
   // (this program, this device, nothing else) while the interpreter kernels serve; the entry points adopt the result at their
@@ -184,6 +188,8 @@ inline void spec_adopt(gsdf_program* p) { if (p->spec_async.load(std::memory_ord
 // The evaluating kernel with distinct z rows for a specialised handle, built on first use: abi_eval.hip.
 void spec_leaf_dz(gsdf_program* p);
 void spec_leaf_dense(gsdf_program* p);
+// The view kernels for a specialised handle, built on its first gsdf_hip_render3: abi_eval.hip.
+void spec_view(gsdf_program* p);
 
 namespace {
 // ms3.Box.ScaleCentered(1.01) = NewCenteredBox(Center(), MulElem(scale, Size())) [external]; float32, unfused.

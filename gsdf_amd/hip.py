@@ -22,7 +22,7 @@ ErrMismatchBufferLength = "position and distance buffer length mismatch"
 # every symbol include/gsdf_hip.h declares
 SYMBOLS = ["gsdf_hip_last_error", "gsdf_hip_init", "gsdf_hip_program_create", "gsdf_hip_program_destroy",
            "gsdf_hip_program_bounds", "gsdf_hip_program_is2d", "gsdf_hip_program_info", "gsdf_hip_evaluations", "gsdf_hip_lower", "gsdf_hip_lower_region", "gsdf_hip_eval3_submit", "gsdf_hip_eval_wait", "gsdf_hip_host_alloc", "gsdf_hip_host_register", "gsdf_hip_host_release", "gsdf_hip_comm_unique_id", "gsdf_hip_comm_create", "gsdf_hip_comm_rank", "gsdf_hip_comm_world", "gsdf_hip_comm_allreduce_sum_u64", "gsdf_hip_mesh_gatherv", "gsdf_hip_mesh_gatherv_start", "gsdf_hip_mesh_gatherv_wait", "gsdf_hip_comm_destroy", "gsdf_hip_selftest_div", "gsdf_hip_selftest_sqrt", "gsdf_hip_selftest_circ", "gsdf_hip_selftest_atan2", "gsdf_hip_selftest_cossin", "gsdf_hip_mesh_minecraft", "gsdf_hip_blockcache_create", "gsdf_hip_blockcache_reset", "gsdf_hip_blockcache_eval3", "gsdf_hip_blockcache_hits", "gsdf_hip_blockcache_evaluations", "gsdf_hip_blockcache_destroy", "gsdf_hip_program_specialize", "gsdf_hip_program_specialize_async", "gsdf_hip_program_specialize_poll", "gsdf_hip_program_is_specialized", "gsdf_hip_program_kernels", "gsdf_hip_specialize_source", "gsdf_hip_specialize_check",
-           "gsdf_hip_eval3", "gsdf_hip_eval2", "gsdf_hip_eval3_dev", "gsdf_hip_eval2_dev", "gsdf_hip_normals3", "gsdf_hip_image2",
+           "gsdf_hip_eval3", "gsdf_hip_eval2", "gsdf_hip_eval3_dev", "gsdf_hip_eval2_dev", "gsdf_hip_normals3", "gsdf_hip_image2", "gsdf_hip_view_orbit", "gsdf_hip_render3",
            "gsdf_hip_mesh_octree", "gsdf_hip_mesh_dualcontour", "gsdf_hip_mesh_flat", "gsdf_hip_mesh_stats_get", "gsdf_hip_mesh_read", "gsdf_hip_mesh_dev_tris",
            "gsdf_hip_mesh_stl", "gsdf_hip_mesh_host_tris", "gsdf_hip_mesh_host_stl", "gsdf_hip_mesh_destroy", "gsdf_hip_brick_owner", "gsdf_hip_slab_range",
            "gsdf_hip_mesh_payload", "gsdf_hip_mesh_march", "gsdf_hip_mesh_stage_ms", "gsdf_hip_mesh_octree_start", "gsdf_hip_mesh_octree_wait", "gsdf_hip_comm_transport", "gsdf_hip_gather_plan"]
@@ -48,6 +48,12 @@ class GatherStats(C.Structure):
 class MeshOpts(C.Structure):
     _fields_ = [("prune", C.c_int), ("shard_rank", C.c_int), ("shard_count", C.c_int), ("max_tris", C.c_uint64),
                 ("stream", C.c_void_p), ("share_corners", C.c_int), ("host_output", C.c_int), ("payload", C.c_int), ("reserved", C.c_int)]
+
+
+class GsdfView(C.Structure):
+    """gsdf_view (gsdf_hip.h): the camera of one UI frame (gsdfaux/ui.go:276-297) and its sampling."""
+    _fields_ = [("ro", C.c_float * 3), ("uu", C.c_float * 3), ("vv", C.c_float * 3), ("ww", C.c_float * 3), ("char_dist", C.c_float),
+                ("aa", C.c_int32), ("max_steps", C.c_int32), ("reserved", C.c_int32)]
 
 
 class MeshStats(C.Structure):
@@ -133,6 +139,8 @@ def lib():
             f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
         L.gsdf_hip_normals3.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float]
         L.gsdf_hip_image2.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.gsdf_hip_view_orbit.argtypes = [C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float, C.POINTER(C.c_float), C.POINTER(GsdfView)]
+        L.gsdf_hip_render3.argtypes = [C.c_void_p, C.POINTER(GsdfView), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.gsdf_hip_mesh_octree.argtypes = [C.c_void_p, C.c_float, C.POINTER(MeshOpts), C.POINTER(C.c_void_p)]
         L.gsdf_hip_mesh_octree_start.argtypes = [C.c_void_p, C.c_float, C.POINTER(MeshOpts), C.POINTER(C.c_void_p)]
         L.gsdf_hip_mesh_octree_wait.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
@@ -169,6 +177,17 @@ def lower(shader_or_tree):
     code = np.zeros(n.value, np.uint32)
     _check(lib().gsdf_hip_lower(C.byref(tree), code.ctypes.data, n.value, C.byref(n), C.byref(sl)))
     return code, sl.value
+
+
+def view_orbit(bounds, yaw=0.0, pitch=0.0, cam_dist=None, target=None, aa=1, max_steps=256):
+    """The UI's orbit camera (gsdf_hip_view_orbit; host only, no device needed): a GsdfView looking at `target` (None = the
+    origin, as gsdfaux/ui.go) from yaw / pitch (radians) at cam_dist (None = the bounds' diagonal, the UI's default)."""
+    bb = (C.c_float * 6)(*[float(v) for v in np.asarray(bounds, np.float32).reshape(6)])
+    ta = None if target is None else (C.c_float * 3)(*[float(v) for v in np.asarray(target, np.float32).reshape(3)])
+    v = GsdfView()
+    _check(lib().gsdf_hip_view_orbit(bb, np.float32(yaw), np.float32(pitch), np.float32(0.0 if cam_dist is None else cam_dist), ta, C.byref(v)))
+    v.aa, v.max_steps = int(aa), int(max_steps)
+    return v
 
 
 def init(device=-1):
@@ -276,6 +295,20 @@ class SDFHIP:
         rgba = np.empty((h, w, 4), np.uint8)
         _check(lib().gsdf_hip_image2(self._h, w, h, dist.ctypes.data, rgba.ctypes.data))
         return dist, rgba
+
+    def render3(self, view, w, h):
+        """One UI frame through the camera `view` (a GsdfView; gsdf_hip_render3): (rgba (h,w,4) uint8, depth (h,w) float32, evals
+        (h,w) uint32), row 0 at the top."""
+        hh, ww = max(int(h), 0), max(int(w), 0)  # (the library refuses bad sizes with GSDF_ERR_BAD_ARGUMENT)
+        rgba = np.empty((hh, ww, 4), np.uint8)
+        depth = np.empty((hh, ww), np.float32)
+        evals = np.empty((hh, ww), np.uint32)
+        _check(lib().gsdf_hip_render3(self._h, C.byref(view), int(w), int(h), rgba.ctypes.data, depth.ctypes.data, evals.ctypes.data))
+        return rgba, depth, evals
+
+    def render_view(self, w, h, yaw=0.0, pitch=0.0, cam_dist=None, aa=1, target=None, max_steps=256):
+        """gsdfaux.UI's view of the part, headless: the orbit camera of view_orbit over this handle's bounds, then render3."""
+        return self.render3(view_orbit(self.Bounds(), yaw, pitch, cam_dist, target, aa, max_steps), w, h)
 
     def normals(self, pos, step):
         pos = np.ascontiguousarray(pos, np.float32)

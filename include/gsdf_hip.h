@@ -15,6 +15,9 @@
  *                              equivalent: the GL path re-uploads every call, gpu_cgo.go:238-257)
  *   gsdf_hip_normals3          gleval.NormalsCentralDiff              gleval/gleval.go:53-108
  *   gsdf_hip_image2            glrender.ImageRendererSDF2.Render (default conversion)  glrender/image.go:46-118
+ *   gsdf_hip_view_orbit        the camera of gsdfaux.UI's fragment shader (orbit about a target)  gsdfaux/ui.go:18,123,220,276-297
+ *   gsdf_hip_render3           one gsdfaux.UI frame, headless: ray march + normal + two-light shading, uAA x uAA
+ *                              supersampling                                                      gsdfaux/ui.go:247-355
  *   gsdf_hip_mesh_octree       glrender.NewOctreeRenderer + RenderAll glrender/octreerenderer.go:43-178,
  *                              (octree prune + marching cubes on device) glrender/marchcubes.go:14-98
  *   gsdf_hip_mesh_dualcontour  glrender.DualContourRenderer.Reset/RenderAll + DualContourLeastSquares
@@ -165,6 +168,52 @@ int gsdf_hip_normals3(gsdf_program* p, const float* pos, float* normals, size_t 
 /* ImageRendererSDF2.Render of a 2D program over its Bounds(): dist_out (w*h floats, row 0 = top) and/or rgba_out
  * (w*h*4 bytes: black inside, white outside, red for NaN/Inf -- the renderer's default conversion). */
 int gsdf_hip_image2(gsdf_program* p, int w, int h, float* dist_out, uint8_t* rgba_out);
+
+/* ---- the UI's ray-marched view of a 3-D part (gsdfaux.UI, gsdfaux/ui.go:247-355), headless ------------------------------------
+ *
+ * The GLSL leaves rounding to the driver; here the frame is exact float32 arithmetic, which the device kernel
+ * (gsdf_amd/csrc/kernels_view.h) and the CPU twin of the tests (tests/viewref.py) follow to the bit. Every operation is ONE
+ * IEEE float32 operation, rounded to nearest, never contracted; sqrt and division correctly rounded; sums left to right as the
+ * shader writes them. normalize(v) = v / sqrt((x*x + y*y) + z*z), one division per component; clamp(x, a, b) = fmin(fmax(x, a), b),
+ * so a NaN clamps to a.
+ *
+ * Pixels and samples. Output row r is GL row j = h - 1 - r (row 0 is the top, as gsdf_hip_image2); fragCoord = (i + 0.5, j + 0.5),
+ * exact. For m, n in 0 .. aa-1 (m outer): o = (float(m), float(n)) / float(aa) - 0.5; p = (2 (fragCoord + o) - (w, h)) / float(h);
+ * rd = normalize((p.x uu + p.y vv) + 1.5 ww).
+ * Marching. tol = 1e-4f, tmax = 1.3f * char_dist, t = 0; for i < max_steps: pos = ro + t rd, d = sdf(pos); if d < tol || t > tmax
+ * { hit = d < tol; stop } else t += d. A NaN distance is never a hit and marching runs on to max_steps; a field that is not
+ * 1-Lipschitz overshoots as the UI's does (a view, not a guarantee).
+ * Normal and colour (hit samples only). k = 0.5773f * 1e-4f; d0..d3 = sdf(pos + (k,-k,-k)), sdf(pos + (-k,-k,k)), sdf(pos + (-k,k,-k)),
+ * sdf(pos + (k,k,k)); with e = (0.5773, -0.5773): nor = normalize(((e.xyy d0 + e.yyx d1) + e.yxy d2) + e.xxx d3);
+ * dif = clamp((nor.x 0.57703 + nor.y 0.57703) + nor.z 0.57703, 0, 1); amb = 0.5 + 0.5 nor.y;
+ * col = sqrt((0.2, 0.3, 0.4) amb + (0.8, 0.7, 0.5) dif); tot += col. After the samples tot /= float(aa * aa).
+ * Outputs per pixel (each optional): RGBA8 = (uint8)(clamp(tot, 0, 1) * 255 + 0.5f), alpha 255; depth = the smallest t among the
+ * pixel's hitting samples, +Inf if none hit; evals = SDF evaluations the pixel cost (march steps + 4 per hit). The program's
+ * gsdf_hip_evaluations grows by the sum of evals. */
+typedef struct gsdf_view {
+  float ro[3];        /* camera position */
+  float uu[3];        /* right */
+  float vv[3];        /* up */
+  float ww[3];        /* forward (unit) */
+  float char_dist;    /* characteristic distance: marching gives up beyond t = 1.3 char_dist */
+  int32_t aa;         /* aa x aa samples per pixel, 1 .. 8 (the UI: 1 while the mouse moves, 3 at rest) */
+  int32_t max_steps;  /* march steps per sample, 0 .. 4096 (the UI: 256) */
+  int32_t reserved;   /* 0 */
+} gsdf_view;
+GSDF_ABI_ASSERT(sizeof(gsdf_view) == 64, "gsdf_view is 64 bytes");
+GSDF_ABI_ASSERT(offsetof(gsdf_view, ro) == 0 && offsetof(gsdf_view, uu) == 12 && offsetof(gsdf_view, vv) == 24 && offsetof(gsdf_view, ww) == 36, "gsdf_view basis");
+GSDF_ABI_ASSERT(offsetof(gsdf_view, char_dist) == 48 && offsetof(gsdf_view, aa) == 52 && offsetof(gsdf_view, max_steps) == 56, "gsdf_view tail");
+
+/* The UI's orbit camera (host only, needs no device): bb = gsdf_hip_program_bounds of the part; yaw, pitch in radians (pitch is
+ * clamped to +-(pi/2 - 0.01)); cam_dist <= 0: the UI's default camDist = diag, the bounds' Diagonal() (Norm of the size vector by
+ * nested hypot); char_dist = camDist + diag; target NULL = the origin, as ui.go. dir = (cos p sin y, sin p, cos p cos y) (trig in
+ * float64, rounded once), ro = ta - dir camDist, ww = normalize(ta - ro), uu = normalize(cross(ww, (0,1,0))), vv = cross(uu, ww).
+ * Sets aa = 1, max_steps = 256. GSDF_ERR_BAD_ARGUMENT for non-finite inputs or an empty camera distance. */
+int gsdf_hip_view_orbit(const float bb[6], float yaw, float pitch, float cam_dist, const float target[3], gsdf_view* view);
+/* One frame of a 3-D program through `view` (see gsdf_view): host outputs, each may be NULL -- rgba_out w*h*4 bytes, depth_out
+ * w*h floats, evals_out w*h uint32, row 0 = top. Blocking, like gsdf_hip_image2. GSDF_ERR_DIMENSION for a 2-D program;
+ * GSDF_ERR_BAD_ARGUMENT for w or h outside 1 .. 16384, aa outside 1 .. 8, max_steps outside 0 .. 4096 or a non-finite camera. */
+int gsdf_hip_render3(gsdf_program* p, const gsdf_view* view, int w, int h, uint8_t* rgba_out, float* depth_out, uint32_t* evals_out);
 
 /* gsdf_mesh_opts.prune flag: apply the reference's centre test verbatim, |d(centre)| >= size * sqrt3/2
  * (octreerenderer.go:270-273), at the tested levels, as if the field were a true distance field. */
