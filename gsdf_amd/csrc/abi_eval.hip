@@ -1,7 +1,7 @@
 // abi_eval.hip -- C ABI (include/gsdf_hip.h), evaluator side: program handles and their run-time specialisation, the
 // gleval.SDF3 / SDF2 Evaluate drop-ins (host buffers, pipelined tickets, registered memory, device-resident), central-difference
-// normals, the 2-D image renderer, the UI's view of a 3-D part, the block cache. Kernels: kernels_eval.h and kernels_view.h over
-// the interpreter of interp.h.
+// normals, the 2-D image renderer and its colour conversions, the UI's view of a 3-D part, the block cache. Kernels: kernels_eval.h,
+// kernels_image.h and kernels_view.h over the interpreter of interp.h.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -15,6 +15,7 @@
 #include "kernels_common.h"
 #include "kernels_eval.h"
 #include "kernels_view.h"
+#include "kernels_image.h"
 #include "abi_program.h"
 
 extern "C" int gsdf_hip_init(int device) {
@@ -322,6 +323,23 @@ void spec_view(gsdf_program* p) {
   }
 }
 
+// image2_color_kernel<k, kind> for every conversion kind (kernels_image.h), for a specialised 2-D handle: built at its first picture,
+// in a module of its own (specialize.cpp: spec_includes). A kernel that fails to build or needs scratch stays on the interpreter kernel.
+void spec_image_color(gsdf_program* p) {
+  if (!p->spec_mod || p->spec_imgc_tried || !p->prog.is2d) return;
+  p->spec_imgc_tried = true;
+  const std::string k = std::to_string(p->batch_k());
+  std::vector<std::string> names;
+  for (int kind = 0; kind < 4; kind++) names.push_back("image2_color_kernel<" + k + ", " + std::to_string(kind) + ">");
+  std::vector<hipFunction_t> f;
+  if (spec_build(p, names, &p->spec_mod_imgc, f, &p->spec_compile_s) != GSDF_OK) return;
+  for (int i = 0; i < 4; i++) {
+    const bool ok = fn_scratch_bytes(f[(size_t)i]) == 0;
+    spec_report("specialised", names[(size_t)i], f[(size_t)i], ok);
+    p->f_imgc[i] = ok ? f[(size_t)i] : nullptr;
+  }
+}
+
 // Compile and load kernels specialised for this handle's program (specialize.cpp): eval, prune and leaf kernels of
 // the configuration the mesher would pick. Afterwards gsdf_hip_eval*/gsdf_hip_mesh_octree launch them instead of the
 // interpreter kernels; results are bit-identical (same statements, same compiler flags). Idempotent.
@@ -528,6 +546,12 @@ extern "C" int gsdf_hip_program_kernels(const gsdf_program* p, char* dst, size_t
     snprintf(buf + strlen(buf), sizeof buf - strlen(buf), " leaf_dense=leaf_dense_kernel<%d>:specialised", p->spec_leaf_dense_w);
   if (p->f_leaf_dz && strlen(buf) + 64 < sizeof buf)  // the evaluating kernel of share_corners = 2, once it has been built
     snprintf(buf + strlen(buf), sizeof buf - strlen(buf), " leaf_rows=leaf_eval_kernel<4,%d%s,rows>:specialised", p->spec_leaf_dz_w, p->spec_leaf_dz_both ? ",both" : "");
+  if (p->prog.is2d && strlen(buf) + 64 < sizeof buf) {  // the picture kernels (a specialised handle builds its own at its first picture)
+    std::string kinds;
+    for (int i = 0; i < 4; i++) if (p->f_imgc[i]) kinds += std::to_string(i);
+    snprintf(buf + strlen(buf), sizeof buf - strlen(buf), " picture=image2_color_kernel<%d,kind>:%s", ek,
+             kinds.empty() ? "interpreter" : ("specialised/" + kinds).c_str());
+  }
   if (p->spec_mod && strlen(buf) + 32 < sizeof buf) { strcat(buf, " compiler="); strcat(buf, p->spec_compiler.c_str()); }
   {  // identity of the code that runs: a stored profile describes this handle's kernels only if it carries the same key
     const std::string key = p->spec_mod ? p->spec_key : gsdf_dev::spec_library_key();
@@ -622,6 +646,7 @@ extern "C" void gsdf_hip_program_destroy(gsdf_program* p) {
   if (p->spec_mod_k1) (void)hipModuleUnload(p->spec_mod_k1);
   if (p->spec_mod_dense) (void)hipModuleUnload(p->spec_mod_dense);
   if (p->spec_mod_view) (void)hipModuleUnload(p->spec_mod_view);
+  if (p->spec_mod_imgc) (void)hipModuleUnload(p->spec_mod_imgc);
   p->q0.release(); p->q1.release(); p->ctr.release();
   p->rec.release(); p->hdr.release(); p->grp.release();
   p->b_q0.release(); p->b_q1.release(); p->b_ctr.release(); p->b_spec_pass.release(); p->b_rec.release(); p->b_hdr.release(); p->b_grp.release();
@@ -1093,6 +1118,100 @@ extern "C" int gsdf_hip_render3(gsdf_program* p, const gsdf_view* view, int w, i
   HIP_TRY(hipMemcpyAsync(h_ctr, d_ctr.p, 16, hipMemcpyDeviceToHost, p->stream));
   HIP_TRY(hipStreamSynchronize(p->stream));
   p->evals += h_ctr[1];
+  return GSDF_OK;
+}
+
+// ---- a 2-D part's picture with gsdfaux's colour conversions (gsdfaux.RenderPNGFile, gsdfaux/gsdfaux.go:264-296; color.go) --------
+// RenderPNGFile's picture size (gsdfaux.go:271-274). Host only.
+extern "C" int gsdf_hip_picture_size(const float bb[6], int pic_height, int* w) {
+  if (!bb || !w) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  if (!finite_all(bb, 6)) return fail(GSDF_ERR_BAD_ARGUMENT, "non-finite bounds");
+  if (pic_height < 1 || pic_height > 16384) return fail(GSDF_ERR_BAD_ARGUMENT, "picture height must be 1 .. 16384");
+  const float szx = bb[3] - bb[0], szy = bb[4] - bb[1];
+  if (!(szy > 0.f) || !std::isfinite(szx) || !std::isfinite(szy)) return fail(GSDF_ERR_BAD_ARGUMENT, "empty or non-finite bounds");
+  const double pix_per_unit = (double)pic_height / (double)szy;
+  const double wd = pix_per_unit * (double)szx;
+  if (!(wd >= 1.0 && wd < 16385.0)) return fail(GSDF_ERR_BAD_ARGUMENT, "picture width comes out outside 1 .. 16384");
+  *w = (int)wd;
+  return GSDF_OK;
+}
+
+// ColorConversionInigoQuilez with RenderPNGFile's default, ms2.Box.Diagonal() / 3 (gsdfaux.go:268). Host only.
+extern "C" int gsdf_hip_color_iq(const float bb[6], float char_dist, gsdf_color2* out) {
+  if (!out || (!bb && !(char_dist > 0.f))) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  float cd = char_dist;
+  if (!std::isfinite(cd)) return fail(GSDF_ERR_BAD_ARGUMENT, "non-finite characteristic distance");
+  if (!(cd > 0.f)) {
+    if (!finite_all(bb, 6)) return fail(GSDF_ERR_BAD_ARGUMENT, "non-finite bounds");
+    cd = hypot32(bb[3] - bb[0], bb[4] - bb[1]) / 3.f;
+    if (!(cd > 0.f) || !std::isfinite(cd)) return fail(GSDF_ERR_BAD_ARGUMENT, "empty bounds and no characteristic distance");
+  }
+  gsdf_color2 c;
+  std::memset(&c, 0, sizeof c);
+  c.kind = GSDF_COLOR_IQ;
+  c.length = cd;
+  *out = c;
+  return GSDF_OK;
+}
+
+// ColorConversionLinearGradient (color.go:50-71): Go's `c0 == color.Black && c1 == color.White` selects the black-and-white closure.
+extern "C" int gsdf_hip_color_gradient(float length, const uint8_t c0[4], const uint8_t c1[4], gsdf_color2* out) {
+  if (!c0 || !c1 || !out) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  if (!std::isfinite(length) || length < 0.f) return fail(GSDF_ERR_BAD_ARGUMENT, "gradient length must be finite and >= 0");
+  gsdf_color2 c;
+  std::memset(&c, 0, sizeof c);
+  const bool black = c0[0] == 0 && c0[1] == 0 && c0[2] == 0 && c0[3] == 255;
+  const bool white = c1[0] == 255 && c1[1] == 255 && c1[2] == 255 && c1[3] == 255;
+  c.kind = black && white ? GSDF_COLOR_BW_SMOOTH : GSDF_COLOR_GRADIENT;
+  c.length = length;
+  std::memcpy(c.c0, c0, 4);
+  std::memcpy(c.c1, c1, 4);
+  *out = c;
+  return GSDF_OK;
+}
+
+// ImageRendererSDF2.Render (image.go:76-118) with a conversion of gsdfaux: image2_color_kernel over the interpreter (the kind a
+// kernel argument), or the handle's specialised build of it (one kernel per kind).
+extern "C" int gsdf_hip_image2_color(gsdf_program* p, const gsdf_color2* conv, int w, int h, uint8_t* rgba_out, float* dist_out) {
+  if (!p || !conv) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  if (!p->prog.is2d) return fail(GSDF_ERR_DIMENSION, "program is 3D, image2_color called");
+  if (w <= 0 || h <= 0 || w > 16384 || h > 16384) return fail(GSDF_ERR_BAD_ARGUMENT, "bad image size (1 .. 16384 pixels per side)");
+  if (conv->kind < GSDF_COLOR_DEFAULT || conv->kind > GSDF_COLOR_BW_SMOOTH) return fail(GSDF_ERR_BAD_ARGUMENT, "unknown colour conversion");
+  if (conv->reserved[0] || conv->reserved[1] || conv->reserved[2] || conv->reserved[3]) return fail(GSDF_ERR_BAD_ARGUMENT, "reserved words must be 0");
+  if (!std::isfinite(conv->length)) return fail(GSDF_ERR_BAD_ARGUMENT, "non-finite conversion length");
+  if (conv->kind == GSDF_COLOR_IQ && !(conv->length > 0.f)) return fail(GSDF_ERR_BAD_ARGUMENT, "IQ characteristic distance must be > 0");
+  if ((conv->kind == GSDF_COLOR_GRADIENT || conv->kind == GSDF_COLOR_BW_SMOOTH) && conv->length < 0.f)
+    return fail(GSDF_ERR_BAD_ARGUMENT, "gradient length must be >= 0");
+  HIP_TRY(hipSetDevice(p->device));
+  spec_adopt(p);  // (a background build that has finished: its kernels from here on)
+  spec_image_color(p);
+  const size_t n = (size_t)w * (size_t)h;
+  // gsdf_hip_image2's lattice, statement for statement
+  const float szx = p->prog.bb[3] - p->prog.bb[0], szy = p->prog.bb[4] - p->prog.bb[1];
+  const float dx = szx / (float)w, dy = szy / (float)h;
+  const float xmin = p->prog.bb[0] + dx / 2, ymax = p->prog.bb[4];
+  ColorConv cv;
+  cv.kind = conv->kind;
+  cv.length = conv->length;
+  cv.c0 = (uint32_t)conv->c0[0] | ((uint32_t)conv->c0[1] << 8) | ((uint32_t)conv->c0[2] << 16) | ((uint32_t)conv->c0[3] << 24);
+  cv.c1 = (uint32_t)conv->c1[0] | ((uint32_t)conv->c1[1] << 8) | ((uint32_t)conv->c1[2] << 16) | ((uint32_t)conv->c1[3] << 24);
+  DevBuf dd, dc;  // (an output not asked for is neither allocated nor written)
+  if (dist_out) HIP_TRY(dd.alloc(n * 4));
+  if (rgba_out) HIP_TRY(dc.alloc(n * 4));
+  float* o_dist = dist_out ? (float*)dd.p : nullptr;
+  uint32_t* o_rgba = rgba_out ? (uint32_t*)dc.p : nullptr;
+  const int k = p->batch_k();
+  const unsigned grid = grid_for((n + k - 1) / k, p->num_cu, 8);
+  const hipFunction_t fs = p->f_imgc[conv->kind];
+  if (fs) HIP_TRY(launch_fn(fs, grid, BLOCK, p->lds_bytes(k), p->stream, (const uint32_t*)p->d_code, (int)w, (int)h, xmin, ymax, dx, dy, cv, o_dist, o_rgba));
+  else if (k == 4) hipLaunchKernelGGL((image2_color_kernel<4, -1>), dim3(grid), dim3(BLOCK), p->lds_bytes(4), p->stream, p->d_code, w, h, xmin, ymax, dx, dy, cv, o_dist, o_rgba);
+  else if (k == 2) hipLaunchKernelGGL((image2_color_kernel<2, -1>), dim3(grid), dim3(BLOCK), p->lds_bytes(2), p->stream, p->d_code, w, h, xmin, ymax, dx, dy, cv, o_dist, o_rgba);
+  else hipLaunchKernelGGL((image2_color_kernel<1, -1>), dim3(grid), dim3(BLOCK), p->lds_bytes(1), p->stream, p->d_code, w, h, xmin, ymax, dx, dy, cv, o_dist, o_rgba);
+  HIP_TRY(hipGetLastError());
+  if (dist_out) HIP_TRY(hipMemcpyAsync(dist_out, dd.p, n * 4, hipMemcpyDeviceToHost, p->stream));
+  if (rgba_out) HIP_TRY(hipMemcpyAsync(rgba_out, dc.p, n * 4, hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  p->evals += n;
   return GSDF_OK;
 }
 

@@ -93,6 +93,11 @@ struct gsdf_program {
   hipModule_t spec_mod_view = nullptr;
   hipFunction_t f_view = nullptr, f_view_plain = nullptr;
   bool spec_view_tried = false;
+  // the 2-D picture (kernels_image.h: image2_color_kernel<K, kind> per conversion kind) for a specialised handle: built on its first
+  // gsdf_hip_image2_color (spec_image_color)
+  hipModule_t spec_mod_imgc = nullptr;
+  hipFunction_t f_imgc[4] = {nullptr, nullptr, nullptr, nullptr};
+  bool spec_imgc_tried = false;
   double spec_compile_s = 0;
   // Specialisation in the background (gsdf_hip_program_specialize_async): a thread builds and loads the kernels on a shadow handle
   // (this program, this device, nothing else) while the interpreter kernels serve; the entry points adopt the result at their
@@ -190,6 +195,8 @@ void spec_leaf_dz(gsdf_program* p);
 void spec_leaf_dense(gsdf_program* p);
 // The view kernels for a specialised handle, built on its first gsdf_hip_render3: abi_eval.hip.
 void spec_view(gsdf_program* p);
+// The picture kernels for a specialised 2-D handle, built on its first gsdf_hip_image2_color: abi_eval.hip.
+void spec_image_color(gsdf_program* p);
 
 namespace {
 // ms3.Box.ScaleCentered(1.01) = NewCenteredBox(Center(), MulElem(scale, Size())) [external]; float32, unfused.

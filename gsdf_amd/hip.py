@@ -22,7 +22,7 @@ ErrMismatchBufferLength = "position and distance buffer length mismatch"
 # every symbol include/gsdf_hip.h declares
 SYMBOLS = ["gsdf_hip_last_error", "gsdf_hip_init", "gsdf_hip_program_create", "gsdf_hip_program_destroy",
            "gsdf_hip_program_bounds", "gsdf_hip_program_is2d", "gsdf_hip_program_info", "gsdf_hip_evaluations", "gsdf_hip_lower", "gsdf_hip_lower_region", "gsdf_hip_eval3_submit", "gsdf_hip_eval_wait", "gsdf_hip_host_alloc", "gsdf_hip_host_register", "gsdf_hip_host_release", "gsdf_hip_comm_unique_id", "gsdf_hip_comm_create", "gsdf_hip_comm_rank", "gsdf_hip_comm_world", "gsdf_hip_comm_allreduce_sum_u64", "gsdf_hip_mesh_gatherv", "gsdf_hip_mesh_gatherv_start", "gsdf_hip_mesh_gatherv_wait", "gsdf_hip_comm_destroy", "gsdf_hip_selftest_div", "gsdf_hip_selftest_sqrt", "gsdf_hip_selftest_circ", "gsdf_hip_selftest_atan2", "gsdf_hip_selftest_cossin", "gsdf_hip_mesh_minecraft", "gsdf_hip_blockcache_create", "gsdf_hip_blockcache_reset", "gsdf_hip_blockcache_eval3", "gsdf_hip_blockcache_hits", "gsdf_hip_blockcache_evaluations", "gsdf_hip_blockcache_destroy", "gsdf_hip_program_specialize", "gsdf_hip_program_specialize_async", "gsdf_hip_program_specialize_poll", "gsdf_hip_program_is_specialized", "gsdf_hip_program_kernels", "gsdf_hip_specialize_source", "gsdf_hip_specialize_check",
-           "gsdf_hip_eval3", "gsdf_hip_eval2", "gsdf_hip_eval3_dev", "gsdf_hip_eval2_dev", "gsdf_hip_normals3", "gsdf_hip_image2", "gsdf_hip_view_orbit", "gsdf_hip_render3",
+           "gsdf_hip_eval3", "gsdf_hip_eval2", "gsdf_hip_eval3_dev", "gsdf_hip_eval2_dev", "gsdf_hip_normals3", "gsdf_hip_image2", "gsdf_hip_image2_color", "gsdf_hip_picture_size", "gsdf_hip_color_iq", "gsdf_hip_color_gradient", "gsdf_hip_view_orbit", "gsdf_hip_render3",
            "gsdf_hip_mesh_octree", "gsdf_hip_mesh_dualcontour", "gsdf_hip_mesh_flat", "gsdf_hip_mesh_stats_get", "gsdf_hip_mesh_read", "gsdf_hip_mesh_dev_tris",
            "gsdf_hip_mesh_stl", "gsdf_hip_mesh_host_tris", "gsdf_hip_mesh_host_stl", "gsdf_hip_mesh_destroy", "gsdf_hip_brick_owner", "gsdf_hip_slab_range",
            "gsdf_hip_mesh_payload", "gsdf_hip_mesh_march", "gsdf_hip_mesh_stage_ms", "gsdf_hip_mesh_octree_start", "gsdf_hip_mesh_octree_wait", "gsdf_hip_comm_transport", "gsdf_hip_gather_plan"]
@@ -54,6 +54,14 @@ class GsdfView(C.Structure):
     """gsdf_view (gsdf_hip.h): the camera of one UI frame (gsdfaux/ui.go:276-297) and its sampling."""
     _fields_ = [("ro", C.c_float * 3), ("uu", C.c_float * 3), ("vv", C.c_float * 3), ("ww", C.c_float * 3), ("char_dist", C.c_float),
                 ("aa", C.c_int32), ("max_steps", C.c_int32), ("reserved", C.c_int32)]
+
+
+class GsdfColor2(C.Structure):
+    """gsdf_color2 (gsdf_hip.h): one of gsdfaux's colour conversions of a distance (gsdfaux/color.go)."""
+    _fields_ = [("kind", C.c_int32), ("length", C.c_float), ("c0", C.c_uint8 * 4), ("c1", C.c_uint8 * 4), ("reserved", C.c_int32 * 4)]
+
+
+COLOR_DEFAULT, COLOR_IQ, COLOR_GRADIENT, COLOR_BW_SMOOTH = 0, 1, 2, 3
 
 
 class MeshStats(C.Structure):
@@ -139,6 +147,10 @@ def lib():
             f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
         L.gsdf_hip_normals3.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float]
         L.gsdf_hip_image2.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.gsdf_hip_image2_color.argtypes = [C.c_void_p, C.POINTER(GsdfColor2), C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.gsdf_hip_picture_size.argtypes = [C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int)]
+        L.gsdf_hip_color_iq.argtypes = [C.POINTER(C.c_float), C.c_float, C.POINTER(GsdfColor2)]
+        L.gsdf_hip_color_gradient.argtypes = [C.c_float, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(GsdfColor2)]
         L.gsdf_hip_view_orbit.argtypes = [C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float, C.POINTER(C.c_float), C.POINTER(GsdfView)]
         L.gsdf_hip_render3.argtypes = [C.c_void_p, C.POINTER(GsdfView), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.gsdf_hip_mesh_octree.argtypes = [C.c_void_p, C.c_float, C.POINTER(MeshOpts), C.POINTER(C.c_void_p)]
@@ -188,6 +200,43 @@ def view_orbit(bounds, yaw=0.0, pitch=0.0, cam_dist=None, target=None, aa=1, max
     _check(lib().gsdf_hip_view_orbit(bb, np.float32(yaw), np.float32(pitch), np.float32(0.0 if cam_dist is None else cam_dist), ta, C.byref(v)))
     v.aa, v.max_steps = int(aa), int(max_steps)
     return v
+
+
+def _bounds6(bounds):
+    return (C.c_float * 6)(*[float(v) for v in np.asarray(bounds, np.float32).reshape(6)])
+
+
+def picture_size(bounds, pic_height):
+    """gsdfaux.RenderPNGFile's picture width for pic_height rows (gsdf_hip_picture_size; host only): the bounds' aspect ratio."""
+    w = C.c_int()
+    _check(lib().gsdf_hip_picture_size(_bounds6(bounds), int(pic_height), C.byref(w)))
+    return w.value
+
+
+def color_iq(bounds, char_dist=None):
+    """ColorConversionInigoQuilez(char_dist) as a GsdfColor2 (gsdf_hip_color_iq; host only); None = RenderPNGFile's default,
+    the bounds' Diagonal() / 3."""
+    c = GsdfColor2()
+    _check(lib().gsdf_hip_color_iq(_bounds6(bounds), np.float32(0.0 if char_dist is None else char_dist), C.byref(c)))
+    return c
+
+
+def color_gradient(length, c0=(0, 0, 0, 255), c1=(255, 255, 255, 255)):
+    """ColorConversionLinearGradient(length, c0, c1) as a GsdfColor2 (gsdf_hip_color_gradient; host only): c0 / c1 are 8-bit RGBA as
+    image.RGBA stores them; the bytes of black -> white select the black-and-white conversion, as color.Black, color.White do in Go
+    (Go's test is an interface comparison: an RGBA black -> white takes the HSV path there, which differs only at length 0, where d
+    is 0 or NaN -- gsdf_hip.h). kind=COLOR_GRADIENT afterwards selects that path."""
+    a, b = (C.c_uint8 * 4)(*[int(v) for v in c0]), (C.c_uint8 * 4)(*[int(v) for v in c1])
+    c = GsdfColor2()
+    _check(lib().gsdf_hip_color_gradient(np.float32(length), a, b, C.byref(c)))
+    return c
+
+
+def color_default():
+    """ImageRendererSDF2's own default conversion (black, white, red for NaN / Inf) as a GsdfColor2."""
+    c = GsdfColor2()
+    c.kind = COLOR_DEFAULT
+    return c
 
 
 def init(device=-1):
@@ -295,6 +344,25 @@ class SDFHIP:
         rgba = np.empty((h, w, 4), np.uint8)
         _check(lib().gsdf_hip_image2(self._h, w, h, dist.ctypes.data, rgba.ctypes.data))
         return dist, rgba
+
+    def render_picture(self, w, h, color=None):
+        """The picture of a 2-D part with one of gsdfaux's conversions (a GsdfColor2; None = RenderPNGFile's default, color_iq of
+        the bounds; gsdf_hip_image2_color): (rgba (h,w,4) uint8, dist (h,w) float32), row 0 at the top."""
+        conv = color_iq(self.Bounds()) if color is None else color
+        hh, ww = max(int(h), 0), max(int(w), 0)  # (the library refuses bad sizes with GSDF_ERR_BAD_ARGUMENT)
+        rgba = np.empty((hh, ww, 4), np.uint8)
+        dist = np.empty((hh, ww), np.float32)
+        _check(lib().gsdf_hip_image2_color(self._h, C.byref(conv), int(w), int(h), rgba.ctypes.data, dist.ctypes.data))
+        return rgba, dist
+
+    def render_png(self, path, pic_height, color=None):
+        """gsdfaux.RenderPNGFile: width from the bounds' aspect ratio, the IQ conversion of Diagonal() / 3 unless `color` is given,
+        written as an 8-bit RGBA PNG. Returns the (h, w, 4) pixels."""
+        from . import png
+        w = picture_size(self.Bounds(), pic_height)
+        rgba, _ = self.render_picture(w, pic_height, color)
+        png.write_png(path, rgba)
+        return rgba
 
     def render3(self, view, w, h):
         """One UI frame through the camera `view` (a GsdfView; gsdf_hip_render3): (rgba (h,w,4) uint8, depth (h,w) float32, evals

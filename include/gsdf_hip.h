@@ -15,6 +15,10 @@
  *                              equivalent: the GL path re-uploads every call, gpu_cgo.go:238-257)
  *   gsdf_hip_normals3          gleval.NormalsCentralDiff              gleval/gleval.go:53-108
  *   gsdf_hip_image2            glrender.ImageRendererSDF2.Render (default conversion)  glrender/image.go:46-118
+ *   gsdf_hip_image2_color      ImageRendererSDF2.Render with gsdfaux's colour conversions (IQ, linear gradient, black and
+ *                              white)                              gsdfaux/color.go, glrender/image.go:46-118
+ *   gsdf_hip_picture_size,     RenderPNGFile's picture width and its default conversion
+ *   gsdf_hip_color_iq / _gradient                                   gsdfaux/gsdfaux.go:264-296
  *   gsdf_hip_view_orbit        the camera of gsdfaux.UI's fragment shader (orbit about a target)  gsdfaux/ui.go:18,123,220,276-297
  *   gsdf_hip_render3           one gsdfaux.UI frame, headless: ray march + normal + two-light shading, uAA x uAA
  *                              supersampling                                                      gsdfaux/ui.go:247-355
@@ -168,6 +172,89 @@ int gsdf_hip_normals3(gsdf_program* p, const float* pos, float* normals, size_t 
 /* ImageRendererSDF2.Render of a 2D program over its Bounds(): dist_out (w*h floats, row 0 = top) and/or rgba_out
  * (w*h*4 bytes: black inside, white outside, red for NaN/Inf -- the renderer's default conversion). */
 int gsdf_hip_image2(gsdf_program* p, int w, int h, float* dist_out, uint8_t* rgba_out);
+
+/* ---- a 2-D part's picture with the reference's colour conversions (gsdfaux.RenderPNGFile, gsdfaux/gsdfaux.go:264-296;
+ *      gsdfaux/color.go) ---------------------------------------------------------------------------------------------------------
+ *
+ * gsdf_hip_image2_color samples the pixel lattice of gsdf_hip_image2 (the same statements, so the same distances, bit for bit)
+ * and converts each distance d to RGBA8 by the conversion `conv`. The conversions are exact float32 arithmetic, which the device
+ * kernel (gsdf_amd/csrc/kernels_image.h) and the CPU twin of the tests (tests/colorref.py) follow to the bit: every step ONE IEEE
+ * operation rounded to nearest, never contracted, division correctly rounded, sums left to right as color.go writes them; the
+ * constants are the float32 values nearest to the exact numbers Go's untyped constants denote (1.0/6 -> float32(1/6), not the
+ * float32 of the float64 1/6). Helpers (u8 and friends are stated at the end):
+ *   Clamp(v, lo, hi) = v < lo ? lo : (v > hi ? hi : v)  (a NaN stays NaN)        Interp(x, y, a) = x + a * (y - x)
+ *   SmoothStep(e0, e1, x) = (t * t) * (3 - 2 * t), t = Clamp((x - e0) / (e1 - e0), 0, 1)
+ *
+ * GSDF_COLOR_DEFAULT    gsdf_hip_image2's bytes: (255,0,0,255) for NaN / +-Inf, white for d > 0, black otherwise (image.go:51-61).
+ * GSDF_COLOR_IQ         ColorConversionInigoQuilez(length) (color.go:21-46). NaN -> (255,0,0,255). Otherwise inv = 1 / length;
+ *                       d = d * inv; c = d > 0 ? (0.9, 0.6, 0.3) : (0.65, 0.85, 1.0); a = |d|; c *= 1 - Exp(-6 * a);
+ *                       c *= 0.8 + 0.2 * Cos(150 * d); mx = 1 - SmoothStep(0, 0.01, a); c = Interp(c, 1, mx) per channel;
+ *                       (u8(c.x * 255), u8(c.y * 255), u8(c.z * 255), 255). An infinite distance gives Cos(Inf) = NaN, hence
+ *                       (0, 0, 0, 255).
+ * GSDF_COLOR_GRADIENT   ColorConversionLinearGradient(length, c0, c1) (color.go:50-71, 104-200) for any pair but black -> white.
+ *                       blend = d / length + 0.5; blend <= 0 -> c0 as stored; blend >= 1 -> c1 as stored. Otherwise (a NaN
+ *                       included) (h, s, v) = hsvToRGB's inverse rgbToHSV of each end colour's r / 255, g / 255, b / 255
+ *                       (colorToHSV; the >> 8 of the 16-bit values gives the stored bytes back), interpHSV (h0 += 1 if h1 - h0 >
+ *                       0.5, else h1 += 1 if h1 - h0 < -0.5; then Interp of h, s, v by blend), hsvToRGB (c = s * v, x = c * (1 -
+ *                       |Mod(h * 6, 2) - 1|), m = v - c; the six cases h in [0, 1/6], (1/6, 2/6], ... (5/6, 1] give (c,x,0),
+ *                       (x,c,0), (0,c,x), (0,x,c), (x,0,c), (c,0,x); an h outside [0, 1], NaN included, gives (0,0,0); then + m
+ *                       per channel), rgbToC (u32(Clamp(ch, 0, 1) * 255) per channel); alpha 255. rgbToHSV(r, g, b): xmax / xmin
+ *                       of the three, c = xmax - xmin, v = xmax; h = 0 if c == 0, else (g - b) / (c * 6) if v == r, else 1/3 +
+ *                       (b - r) / (c * 6) if v == g, else 2/3 + (r - g) / (c * 6); h += 1 if h < 0; s = xmax > 0 ? c / xmax : 0.
+ *                       Mod(x, 2) is the exact remainder with the sign of x (math32.Mod).
+ * GSDF_COLOR_BW_SMOOTH  ColorConversionLinearGradient(length, color.Black, color.White) (color.go:73-99). length == 0: d < 0 ->
+ *                       black, anything else (NaN included) -> white. Otherwise blend = d / length + 0.5; blend <= 0 -> black;
+ *                       blend >= 1 -> white; else y = u8(Clamp(blend, 0, 1) * 255) -> (y, y, y, 255) (a NaN gives y = 0).
+ *
+ * Pinned by this contract, not by the reference (the reference leaves them to the platform or to code outside it):
+ *   Exp(x)  = float32(exp64(float64(x))), exp64 Go's portable math.Exp (exp.go: FreeBSD e_exp.c reduction k = int(Log2e x -+ 0.5),
+ *             hi = x - k Ln2Hi, lo = k Ln2Lo, then expmulti and an exact Ldexp) with its special cases (NaN, +-Inf, x > 709.78...
+ *             -> +Inf, x < -745.13... -> 0, |x| < 2^-28 -> 1 + x). math32.Exp has amd64 assembly of its own.
+ *   Cos(x)  = float32(cos64(float64(x))), cos64 Go's math.Cos with Cody-Waite reduction (cos.go, as oracle/orc_math.h states it)
+ *             at every finite argument: Go switches to Payne-Hanek at |x| >= 2^29, which this contract does not follow (at such
+ *             arguments the results differ from Go's; IQ reaches them only at distances above 3.5e6 characteristic lengths).
+ *             Where x (4/pi) >= 2^64 the integer part is taken as 0, as amd64's float64 -> uint64 conversion gives it.
+ *   u8(v), u32(v): Go's float -> integer conversion of a value outside the target's range is implementation-specific. Stated
+ *             here as amd64's truncating conversion to int64, low bits kept: NaN and |v| >= 2^63 give 0, other values
+ *             trunc(v) mod 256 (u8) / mod 2^32 (u32). (Not checked against a Go toolchain.)
+ *   Clamp, SmoothStep, Interp and the bounds' Diagonal (below) restate helpers of soypat/geometry (ms1, ms3, ms2), a module
+ *   this project does not carry. */
+enum {
+  GSDF_COLOR_DEFAULT = 0,
+  GSDF_COLOR_IQ = 1,
+  GSDF_COLOR_GRADIENT = 2,
+  GSDF_COLOR_BW_SMOOTH = 3
+};
+typedef struct gsdf_color2 {
+  int32_t kind;        /* GSDF_COLOR_* */
+  float length;        /* IQ: characteristic distance (finite, > 0); GRADIENT / BW_SMOOTH: gradient length (finite, >= 0) */
+  uint8_t c0[4];       /* GRADIENT end colours, 8-bit RGBA as image.RGBA stores them (alpha-premultiplied) */
+  uint8_t c1[4];
+  int32_t reserved[4]; /* 0 */
+} gsdf_color2;
+GSDF_ABI_ASSERT(sizeof(gsdf_color2) == 32, "gsdf_color2 is 32 bytes");
+GSDF_ABI_ASSERT(offsetof(gsdf_color2, kind) == 0 && offsetof(gsdf_color2, length) == 4 && offsetof(gsdf_color2, c0) == 8, "gsdf_color2 head");
+GSDF_ABI_ASSERT(offsetof(gsdf_color2, c1) == 12 && offsetof(gsdf_color2, reserved) == 16, "gsdf_color2 tail");
+
+/* RenderPNGFile's picture size (gsdfaux.go:271-274; host only, needs no device): bb = gsdf_hip_program_bounds of the part;
+ * sz = (bb[3] - bb[0], bb[4] - bb[1]) in float32, pixPerUnit = float64(pic_height) / float64(sz.y), *w = int(pixPerUnit *
+ * float64(sz.x)) (truncated). GSDF_ERR_BAD_ARGUMENT for non-finite bounds, sz.y <= 0, or pic_height or *w outside 1 .. 16384. */
+int gsdf_hip_picture_size(const float bb[6], int pic_height, int* w);
+/* ColorConversionInigoQuilez (host only): char_dist > 0 is used as given; char_dist <= 0 selects RenderPNGFile's default,
+ * Diagonal() / 3 of the x, y extents (math32.Hypot in float32, then one float32 division). GSDF_ERR_BAD_ARGUMENT for non-finite
+ * input or a default that comes out 0. */
+int gsdf_hip_color_iq(const float bb[6], float char_dist, gsdf_color2* out);
+/* ColorConversionLinearGradient(length, c0, c1) (host only): BW_SMOOTH when c0 is (0,0,0,255) and c1 (255,255,255,255), GRADIENT
+ * otherwise. A byte test, not Go's: `c0 == color.Black` is an interface comparison that holds for color.Black / color.White only
+ * (dynamic type Gray16), so Go sends color.RGBA{0,0,0,255} -> {255,255,255,255} down the HSV path. The two paths give the same
+ * bytes for length > 0; at length 0 they differ where d == 0 or d is NaN (BW_SMOOTH: white; the HSV path: black). A caller that
+ * holds Go values decides the kind by Go's own comparison (integration/go/gsdfaux/png_hip.go). GSDF_ERR_BAD_ARGUMENT for a
+ * non-finite or negative length. */
+int gsdf_hip_color_gradient(float length, const uint8_t c0[4], const uint8_t c1[4], gsdf_color2* out);
+/* The picture of a 2-D program: rgba_out w*h*4 bytes converted by `conv`, dist_out w*h floats (gsdf_hip_image2's), row 0 = top;
+ * either may be NULL. Blocking; gsdf_hip_evaluations grows by w*h. GSDF_ERR_DIMENSION for a 3-D program; GSDF_ERR_BAD_ARGUMENT
+ * for a NULL or unknown conversion, a length out of its kind's range, non-zero reserved words, or w or h outside 1 .. 16384. */
+int gsdf_hip_image2_color(gsdf_program* p, const gsdf_color2* conv, int w, int h, uint8_t* rgba_out, float* dist_out);
 
 /* ---- the UI's ray-marched view of a 3-D part (gsdfaux.UI, gsdfaux/ui.go:247-355), headless ------------------------------------
  *
