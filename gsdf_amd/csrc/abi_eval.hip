@@ -965,6 +965,28 @@ extern "C" int gsdf_hip_normals3(gsdf_program* p, const float* pos, float* norma
   return rc;
 }
 
+// The same on device-resident points (gsdf_hip_indexed_normals: the welded vertices of a mesh): d_pos, d_nrm 12-byte xyz on the
+// program's device; blocking. The launch is gsdf_hip_normals3's, so the values are.
+int normals3_dev(gsdf_program* p, const float* d_pos, float* d_nrm, size_t n, float step) {
+  step *= 0.5f;
+  if (!(step > 0)) return fail(GSDF_ERR_BAD_ARGUMENT, "invalid step");
+  if (n == 0) return fail(GSDF_ERR_EMPTY_BUFFERS, "empty buffers");
+  if (p->prog.is2d) return fail(GSDF_ERR_DIMENSION, "program is 2D");
+  HIP_TRY(hipSetDevice(p->device));
+  spec_adopt(p);
+  spec_aux(p);
+  if (p->f_normals) {
+    HIP_TRY(launch_fn(p->f_normals, grid_for(n, p->num_cu, 8), BLOCK, p->lds_bytes(2), p->stream, (const uint32_t*)p->d_code, (const float*)d_pos, (float*)d_nrm,
+                      (uint64_t)n, (float)step));
+  } else {
+    hipLaunchKernelGGL(normals_kernel, dim3(grid_for(n, p->num_cu, 8)), dim3(BLOCK), p->lds_bytes(2), p->stream, p->d_code, d_pos, d_nrm, (uint64_t)n, step);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  p->evals += 6 * n;
+  return GSDF_OK;
+}
+
 // glrender.ImageRendererSDF2.Render for a 2D program: w x h pixels over Bounds(); host outputs (either may be NULL).
 extern "C" int gsdf_hip_image2(gsdf_program* p, int w, int h, float* dist_out, uint8_t* rgba_out) {
   if (!p) return fail(GSDF_ERR_BAD_ARGUMENT, "null program");

@@ -44,6 +44,12 @@ struct gsdf_mesh {
   uint8_t* d_recs = nullptr;
   uint64_t recs_cap36 = 0;
   uint64_t n_recs = 0;
+  // A records mesh of the whole model (octree mesher, shard_count == 1) can be welded (gsdf_hip_mesh_weld), before or after
+  // gsdf_hip_mesh_march: the march then parks the records here instead of releasing them, until the mesh is destroyed.
+  bool weldable = false;
+  uint8_t* d_wrecs = nullptr;
+  uint64_t wrecs_cap36 = 0;
+  uint64_t n_wrecs = 0;
   int num_cu = 256;
   // device time per stage, where a mesher records it (dual contouring: five stages; gsdf_hip_mesh_stage_ms)
   int n_stages = 0;

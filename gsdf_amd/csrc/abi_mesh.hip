@@ -1,6 +1,6 @@
 // abi_mesh.hip -- C ABI (include/gsdf_hip.h), mesher side: glrender.Octree + marchCubes, FlatRenderer and
 // DualContourRenderer on device, and the accessors of the resulting mesh (ReadTriangles drain, STL, pinned host views).
-// Kernels: kernels_octree.h, kernels_flat.h, kernels_dc.h, kernels_stl.h.
+// Kernels: kernels_octree.h, kernels_flat.h, kernels_dc.h, kernels_stl.h, kernels_weld.h (indexed meshes, binary PLY).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -14,6 +14,7 @@
 #include "kernels_dc.h"
 #include "kernels_stl.h"
 #include "kernels_minecraft.h"
+#include "kernels_weld.h"
 #include "abi_program.h"
 #include "host_math.h"
 
@@ -414,7 +415,7 @@ int gsdf_mesh_job::stats() {
   m->st.ms_total = (double)ms01 + (double)ms12;
   p->evals += m->st.evals;
   p->last_tris = hc.n_tris;
-  if (want_recs) { m->payload = GSDF_PAYLOAD_RECORDS; m->n_recs = hc.n_cut; p->last_recs = hc.n_cut; }
+  if (want_recs) { m->payload = GSDF_PAYLOAD_RECORDS; m->n_recs = hc.n_cut; p->last_recs = hc.n_cut; m->weldable = opts.shard_count == 1; }
   return GSDF_OK;
 }
 #undef HIP_TRYM
@@ -601,6 +602,21 @@ extern "C" int gsdf_hip_mesh_payload(const gsdf_mesh* m, uint64_t* n_records, ui
   return m->payload;
 }
 
+extern "C" int gsdf_hip_mesh_read_records(const gsdf_mesh* m, uint32_t* dst, uint64_t dst_records, uint64_t* n_records) {
+  if (!m) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  const bool r = m->payload == GSDF_PAYLOAD_RECORDS;
+  const uint8_t* d = r ? m->d_recs : m->d_wrecs;
+  const uint64_t n = r ? m->n_recs : m->n_wrecs;
+  if (!r && !m->weldable) return fail(GSDF_ERR_BAD_ARGUMENT, "the mesh holds no cut-leaf records (payload = GSDF_PAYLOAD_RECORDS keeps them)");
+  if (n_records) *n_records = n;
+  if (!dst) return GSDF_OK;
+  if (dst_records < n) return fail(GSDF_ERR_SHORT_BUFFER, "short buffer");
+  if (n == 0) return GSDF_OK;
+  HIP_TRY(hipSetDevice(m->device));
+  HIP_TRY(hipMemcpy(dst, d, n * 40ull, hipMemcpyDeviceToHost));
+  return GSDF_OK;
+}
+
 extern "C" int gsdf_hip_mesh_march(gsdf_mesh* m) {
   if (!m) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
   if (m->payload != GSDF_PAYLOAD_RECORDS) return GSDF_OK;
@@ -622,7 +638,8 @@ extern "C" int gsdf_hip_mesh_march(gsdf_mesh* m) {
     hipError_t e = hipStreamSynchronize(rs);
     if (e != hipSuccess) { release_tris(m); return fail(GSDF_ERR_HIP, std::string("march over the records: ") + hipGetErrorString(e)); }
   }
-  pool_give(m->device, (float*)m->d_recs, m->recs_cap36);
+  if (m->weldable) { m->d_wrecs = m->d_recs; m->wrecs_cap36 = m->recs_cap36; m->n_wrecs = m->n_recs; }  // kept for gsdf_hip_mesh_weld
+  else pool_give(m->device, (float*)m->d_recs, m->recs_cap36);
   m->d_recs = nullptr; m->recs_cap36 = 0; m->n_recs = 0;
   m->payload = GSDF_PAYLOAD_TRIANGLES;
   return GSDF_OK;
@@ -1220,6 +1237,7 @@ extern "C" int gsdf_hip_mesh_host_stl(gsdf_mesh* m, const uint8_t** stl, size_t*
 static void mesh_free(gsdf_mesh* m) {
   release_tris(m);
   pool_give(m->device, (float*)m->d_recs, m->recs_cap36);
+  pool_give(m->device, (float*)m->d_wrecs, m->wrecs_cap36);
   hpool_give(m->h_tris, m->h_tris_cap);
   hpool_give(m->h_stl, m->h_stl_cap);
   if (m->rstream) (void)hipStreamDestroy(m->rstream);
@@ -1233,4 +1251,288 @@ extern "C" void gsdf_hip_mesh_destroy(gsdf_mesh* m) {
 void mesh_inflight_done(gsdf_mesh* m) {
   m->inflight.fetch_sub(1);
   if (m->refs.fetch_sub(1, std::memory_order_acq_rel) == 1) mesh_free(m);
+}
+
+// ---- indexed meshes (kernels_weld.h; the contract is in include/gsdf_hip.h) ----------------------------------------------------
+namespace {
+// a device buffer from the triangle pool (sized in 36-byte units), handed back when it goes out of scope
+struct PoolBuf {
+  int device = 0;
+  float* p = nullptr;
+  uint64_t cap = 0;
+  PoolBuf() = default;
+  PoolBuf(const PoolBuf&) = delete;
+  PoolBuf& operator=(const PoolBuf&) = delete;
+  ~PoolBuf() { give(); }
+  void give() { pool_give(device, p, cap); p = nullptr; cap = 0; }
+  bool take(int dev, size_t bytes) {
+    give();
+    device = dev;
+    const uint64_t units = (bytes + 35) / 36 + 1;
+    p = pool_take(dev, units, &cap);
+    if (!p) {
+      if (hipMalloc((void**)&p, units * 36) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return false; }
+      cap = units;
+    }
+    return true;
+  }
+  template <typename T> T* as() const { return (T*)p; }
+};
+struct EventPair {
+  hipEvent_t a = nullptr, b = nullptr;
+  ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+  bool make() { return hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess; }
+  double ms() const { float t = 0; return hipEventElapsedTime(&t, a, b) == hipSuccess ? (double)t : 0.0; }
+};
+}  // namespace
+
+struct gsdf_indexed {
+  int device = 0;
+  int num_cu = 256;
+  hipStream_t stream = nullptr;
+  uint64_t n_verts = 0, n_tris = 0;
+  PoolBuf verts, idx, vkeys, normals;
+  bool has_normals = false;
+  double ms_device = 0;
+  gsdf_indexed_stats st{};
+  void* h_ply = nullptr;
+  size_t h_ply_cap = 0, ply_len = 0;
+  bool ply_valid = false;
+};
+
+extern "C" void gsdf_hip_indexed_destroy(gsdf_indexed* ix) {
+  if (!ix) return;
+  (void)hipSetDevice(ix->device);
+  if (ix->stream) { (void)hipStreamSynchronize(ix->stream); (void)hipStreamDestroy(ix->stream); }
+  hpool_give(ix->h_ply, ix->h_ply_cap);
+  delete ix;
+}
+
+extern "C" int gsdf_hip_mesh_weld(const gsdf_mesh* m, gsdf_indexed** out) {
+  if (!m || !out) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  *out = nullptr;
+  const bool marched = m->payload != GSDF_PAYLOAD_RECORDS;
+  const uint8_t* d_recs = marched ? m->d_wrecs : m->d_recs;
+  const uint64_t n_recs = marched ? m->n_wrecs : m->n_recs;
+  if (!m->weldable || (!d_recs && m->st.n_tris))
+    return fail(GSDF_ERR_BAD_ARGUMENT, "weld needs a mesh of the octree mesher made with payload = GSDF_PAYLOAD_RECORDS and shard_count == 1 (marched in place or "
+                                       "not): triangle-payload, flat, dual-contouring, minecraft, gathered and sharded meshes carry no lattice coordinates");
+  if (m->inflight.load() > 0) return fail(GSDF_ERR_BAD_ARGUMENT, "the mesh is being gathered: wait for the gather first");
+  const uint64_t F = m->st.n_tris;
+  if (F == 0) return fail(GSDF_ERR_EMPTY_BUFFERS, "empty triangle slice");
+  if (3 * F >= ((uint64_t)1 << 32)) return fail(GSDF_ERR_CAPACITY, "weld: 3 x triangles must stay below 2^32 (32-bit vertex numbers)");
+  HIP_TRY(hipSetDevice(m->device));
+  gsdf_indexed* ix = new (std::nothrow) gsdf_indexed();
+  if (!ix) return fail(GSDF_ERR_BAD_ARGUMENT, "out of memory");
+  ix->device = m->device;
+  ix->num_cu = m->num_cu;
+  auto bail = [&](int code) { gsdf_hip_indexed_destroy(ix); return code; };
+#define HIP_TRYW(expr)                                                                                          \
+  do {                                                                                                          \
+    hipError_t _e = (expr);                                                                                     \
+    if (_e != hipSuccess) return bail(fail(GSDF_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e))); \
+  } while (0)
+  HIP_TRYW(hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking));
+  hipStream_t s = ix->stream;
+  const int dev = m->device;
+  const uint64_t S = 3 * F;  // soup slots
+  const uint64_t n_chunks = (n_recs + DENSE_CHUNK - 1) / DENSE_CHUNK;
+  const uint64_t n_blocks = (S + BLOCK - 1) / BLOCK;
+  const char* nomem = "weld: no device memory for the workspace";
+  // the soup: the mesh's own triangles if it was marched, else a marching pass over its records into scratch
+  PoolBuf soup_tmp;
+  const float* soup = m->d_tris;
+  if (!marched) {
+    if (!soup_tmp.take(dev, (size_t)F * 36 + dense_parts_bytes() + 36)) return bail(fail(GSDF_ERR_HIP, nomem));
+    const gsdf_dense_part part{0, n_recs, 0};
+    if (int rc = mesh_march_dense(d_recs, &part, 1, dense_parts_at(soup_tmp.p, F), m->st.origin[0], m->st.origin[1], m->st.origin[2], m->st.res, soup_tmp.p,
+                                  m->num_cu, s))
+      return bail(rc);
+    soup = soup_tmp.p;
+  }
+  PoolBuf keys, vnum, chunk_base, blk_cnt, blk_base, ctr, table;
+  if (!keys.take(dev, S * 8) || !ix->idx.take(dev, S * 4) || !vnum.take(dev, S * 4) || !chunk_base.take(dev, n_chunks * 4 + 4) ||
+      !blk_cnt.take(dev, n_blocks * 4) || !blk_base.take(dev, n_blocks * 4) || !ctr.take(dev, sizeof(WeldCounters)))
+    return bail(fail(GSDF_ERR_HIP, nomem));
+  EventPair ev_k, ev_i, ev_n;
+  if (!ev_k.make() || !ev_i.make() || !ev_n.make()) return bail(fail(GSDF_ERR_HIP, "hipEventCreate failed"));
+  // 1. keys
+  HIP_TRYW(hipEventRecord(ev_k.a, s));
+  hipLaunchKernelGGL(weld_chunk_scan_kernel, dim3(1), dim3(1024), 0, s, (const uint32_t*)(d_recs + n_recs * 40ull), (unsigned long long)n_chunks,
+                     chunk_base.as<uint32_t>());
+  HIP_TRYW(hipGetLastError());
+  hipLaunchKernelGGL(weld_keys_kernel, dim3(grid_for(n_chunks * BLOCK, m->num_cu, 16)), dim3(BLOCK), 0, s, d_recs, (unsigned long long)n_recs,
+                     (const uint32_t*)chunk_base.as<uint32_t>(), (unsigned long long)S, keys.as<unsigned long long>());
+  HIP_TRYW(hipGetLastError());
+  HIP_TRYW(hipEventRecord(ev_k.b, s));
+  // 2. the table: cells from F (V is about F / 2: load factor <= 0.5); a pass that ends fuller than that, or that gave up on a key,
+  // is repeated with twice the cells -- no key is ever dropped. GSDF_HIP_WELD_CELLS_MIN lowers the first size so that tests can drive
+  // the grow-and-rerun path.
+  uint64_t cells = 1024;
+  {
+    const char* e = getenv("GSDF_HIP_WELD_CELLS_MIN");
+    const uint64_t want = e ? (uint64_t)strtoull(e, nullptr, 10) : F;
+    while (cells < want) cells <<= 1;
+  }
+  WeldCounters hc{};
+  int attempts = 0;
+  HIP_TRYW(hipEventRecord(ev_i.a, s));
+  for (;;) {
+    if (cells > ((uint64_t)1 << 32)) return bail(fail(GSDF_ERR_CAPACITY, "weld: hash table capacity exceeded"));
+    if (!table.take(dev, cells * 12)) return bail(fail(GSDF_ERR_HIP, nomem));
+    attempts++;
+    HIP_TRYW(hipMemsetAsync(table.p, 0xff, cells * 12, s));
+    HIP_TRYW(hipMemsetAsync(ctr.p, 0, sizeof(WeldCounters), s));
+    hipLaunchKernelGGL(weld_insert_kernel, dim3(grid_for(S, m->num_cu, 16)), dim3(BLOCK), 0, s, (const unsigned long long*)keys.as<unsigned long long>(),
+                       (unsigned long long)S, table.as<unsigned long long>(), (unsigned*)(table.as<unsigned long long>() + cells), (unsigned)(cells - 1),
+                       ctr.as<WeldCounters>());
+    HIP_TRYW(hipGetLastError());
+    HIP_TRYW(hipMemcpyAsync(&hc, ctr.p, sizeof hc, hipMemcpyDeviceToHost, s));
+    HIP_TRYW(hipStreamSynchronize(s));
+    if (!hc.overflow && hc.distinct * 2 <= cells) break;
+    cells <<= 1;
+  }
+  HIP_TRYW(hipEventRecord(ev_i.b, s));
+  // 3. owners, numbers, positions, indices
+  HIP_TRYW(hipEventRecord(ev_n.a, s));
+  hipLaunchKernelGGL(weld_owner_kernel, dim3((unsigned)n_blocks), dim3(BLOCK), 0, s, (const unsigned long long*)keys.as<unsigned long long>(), (unsigned long long)S,
+                     (const unsigned long long*)table.as<unsigned long long>(), (const unsigned*)(table.as<unsigned long long>() + cells), (unsigned)(cells - 1),
+                     ix->idx.as<unsigned>(), blk_cnt.as<unsigned>());
+  HIP_TRYW(hipGetLastError());
+  hipLaunchKernelGGL(weld_block_scan_kernel, dim3(1), dim3(1024), 0, s, (const unsigned*)blk_cnt.as<unsigned>(), (unsigned)n_blocks, blk_base.as<unsigned>(),
+                     ctr.as<WeldCounters>());
+  HIP_TRYW(hipGetLastError());
+  WeldCounters hv{};
+  HIP_TRYW(hipMemcpyAsync(&hv, ctr.p, sizeof hv, hipMemcpyDeviceToHost, s));
+  HIP_TRYW(hipStreamSynchronize(s));
+  const uint64_t V = hv.n_verts;
+  if (V == 0 || V > S || V != hc.distinct) return bail(fail(GSDF_ERR_HIP, "weld: internal error (owners and distinct keys disagree)"));
+  if (!ix->verts.take(dev, V * 12) || !ix->vkeys.take(dev, V * 8)) return bail(fail(GSDF_ERR_HIP, nomem));
+  hipLaunchKernelGGL(weld_number_kernel, dim3((unsigned)n_blocks), dim3(BLOCK), 0, s, (const unsigned*)ix->idx.as<unsigned>(), (unsigned long long)S,
+                     (const unsigned*)blk_base.as<unsigned>(), soup, (const unsigned long long*)keys.as<unsigned long long>(), vnum.as<unsigned>(), ix->verts.p,
+                     ix->vkeys.as<unsigned long long>());
+  HIP_TRYW(hipGetLastError());
+  hipLaunchKernelGGL(weld_index_kernel, dim3((unsigned)n_blocks), dim3(BLOCK), 0, s, ix->idx.as<unsigned>(), (unsigned long long)S, (const unsigned*)vnum.as<unsigned>());
+  HIP_TRYW(hipGetLastError());
+  HIP_TRYW(hipEventRecord(ev_n.b, s));
+  HIP_TRYW(hipStreamSynchronize(s));
+#undef HIP_TRYW
+  ix->n_verts = V;
+  ix->n_tris = F;
+  ix->st.ms_keys = ev_k.ms();
+  ix->st.ms_insert = ev_i.ms();
+  ix->st.ms_number = ev_n.ms();
+  ix->st.probes = hc.probes;
+  ix->st.table_cells = cells;
+  ix->st.attempts = attempts;
+  ix->ms_device = ix->st.ms_keys + ix->st.ms_insert + ix->st.ms_number;
+  *out = ix;
+  return GSDF_OK;
+}
+
+extern "C" int gsdf_hip_indexed_counts(const gsdf_indexed* ix, uint64_t* n_verts, uint64_t* n_tris, double* ms_device) {
+  if (!ix) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  if (n_verts) *n_verts = ix->n_verts;
+  if (n_tris) *n_tris = ix->n_tris;
+  if (ms_device) *ms_device = ix->ms_device;
+  return GSDF_OK;
+}
+
+extern "C" int gsdf_hip_indexed_stats_get(const gsdf_indexed* ix, gsdf_indexed_stats* st) {
+  if (!ix || !st) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  *st = ix->st;
+  st->has_normals = ix->has_normals ? 1 : 0;
+  return GSDF_OK;
+}
+
+extern "C" int gsdf_hip_indexed_read(const gsdf_indexed* ix, float* verts, uint32_t* idx, uint64_t* keys) {
+  if (!ix) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  HIP_TRY(hipSetDevice(ix->device));
+  if (verts) HIP_TRY(hipMemcpy(verts, ix->verts.p, ix->n_verts * 12, hipMemcpyDeviceToHost));
+  if (idx) HIP_TRY(hipMemcpy(idx, ix->idx.p, ix->n_tris * 12, hipMemcpyDeviceToHost));
+  if (keys) HIP_TRY(hipMemcpy(keys, ix->vkeys.p, ix->n_verts * 8, hipMemcpyDeviceToHost));
+  return GSDF_OK;
+}
+
+extern "C" int gsdf_hip_indexed_normals(gsdf_indexed* ix, gsdf_program* p, float step) {
+  if (!ix || !p) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  if (p->device != ix->device) return fail(GSDF_ERR_BAD_ARGUMENT, "the program and the indexed mesh live on different devices");
+  HIP_TRY(hipSetDevice(ix->device));
+  if (!ix->normals.p && !ix->normals.take(ix->device, ix->n_verts * 12)) return fail(GSDF_ERR_HIP, "no device memory for the normals");
+  ix->has_normals = false;
+  ix->ply_valid = false;
+  if (int rc = normals3_dev(p, ix->verts.p, ix->normals.p, (size_t)ix->n_verts, step)) return rc;
+  ix->has_normals = true;
+  return GSDF_OK;
+}
+
+extern "C" int gsdf_hip_indexed_read_normals(const gsdf_indexed* ix, float* normals) {
+  if (!ix || !normals) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  if (!ix->has_normals) return fail(GSDF_ERR_BAD_ARGUMENT, "no normals yet: gsdf_hip_indexed_normals first");
+  HIP_TRY(hipSetDevice(ix->device));
+  HIP_TRY(hipMemcpy(normals, ix->normals.p, ix->n_verts * 12, hipMemcpyDeviceToHost));
+  return GSDF_OK;
+}
+
+// The PLY header (gsdf_hip.h; gsdf_amd/ply.py writes the same bytes): its comment line is padded to a length that is a multiple of 4.
+static std::string ply_header(uint64_t V, uint64_t F, bool normals) {
+  std::string a = "ply\nformat binary_little_endian 1.0\ncomment gsdf";
+  std::string b = "\nelement vertex " + std::to_string(V) + "\nproperty float x\nproperty float y\nproperty float z\n";
+  if (normals) b += "property float nx\nproperty float ny\nproperty float nz\n";
+  b += "element face " + std::to_string(F) + "\nproperty list uchar int vertex_indices\nend_header\n";
+  a.append((4 - (a.size() + b.size()) % 4) % 4, ' ');
+  return a + b;
+}
+
+extern "C" int gsdf_hip_indexed_host_ply(gsdf_indexed* ix, const uint8_t** ply, size_t* len) {
+  if (!ix || !ply || !len) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  *ply = nullptr; *len = 0;
+  HIP_TRY(hipSetDevice(ix->device));
+  if (!ix->ply_valid) {
+    const std::string hdr = ply_header(ix->n_verts, ix->n_tris, ix->has_normals);
+    const size_t vbytes = (size_t)ix->n_verts * (ix->has_normals ? 24 : 12), fbytes = (size_t)ix->n_tris * 13;
+    const size_t bytes = hdr.size() + vbytes + fbytes;
+    if (int rc = host_buf(&ix->h_ply, &ix->h_ply_cap, bytes + 4)) return rc;
+    PoolBuf d_out;  // device scratch from the triangle pool (the last face dword may reach past the file's end)
+    if (!d_out.take(ix->device, bytes + 4)) return fail(GSDF_ERR_HIP, "hipMalloc of the PLY scratch failed");
+    EventPair ev;
+    if (!ev.make()) return fail(GSDF_ERR_HIP, "hipEventCreate failed");
+    std::memcpy(ix->h_ply, hdr.data(), hdr.size());  // pinned: a valid source for the async header upload
+    hipStream_t s = ix->stream;
+    uint8_t* o = (uint8_t*)d_out.p;
+    hipError_t e = hipEventRecord(ev.a, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(o, ix->h_ply, hdr.size(), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(ply_verts_kernel, dim3(grid_for(vbytes / 4, ix->num_cu, 8)), dim3(BLOCK), 0, s, (const float*)ix->verts.p,
+                         (const float*)(ix->has_normals ? ix->normals.p : nullptr), (unsigned long long)ix->n_verts, (uint32_t*)(o + hdr.size()));
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(ply_faces_kernel, dim3(grid_for((fbytes + 3) / 4, ix->num_cu, 8)), dim3(BLOCK), 0, s, (const unsigned*)ix->idx.as<unsigned>(),
+                         (unsigned long long)ix->n_tris, (uint32_t*)(o + hdr.size() + vbytes));
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(ix->h_ply, o, bytes, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipEventRecord(ev.b, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    else (void)hipStreamSynchronize(s);
+    if (e != hipSuccess) return fail(GSDF_ERR_HIP, std::string("PLY build/transfer: ") + hipGetErrorString(e));
+    ix->st.ms_ply = ev.ms();
+    ix->ply_len = bytes;
+    ix->ply_valid = true;
+  }
+  *ply = (const uint8_t*)ix->h_ply;
+  *len = ix->ply_len;
+  return GSDF_OK;
+}
+
+extern "C" int gsdf_hip_indexed_ply(gsdf_indexed* ix, uint8_t* dst, size_t cap, size_t* len) {
+  if (!ix || !len) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  *len = ply_header(ix->n_verts, ix->n_tris, ix->has_normals).size() + (size_t)ix->n_verts * (ix->has_normals ? 24 : 12) + (size_t)ix->n_tris * 13;
+  if (!dst || cap < *len) return fail(GSDF_ERR_SHORT_BUFFER, "short buffer");
+  const uint8_t* h = nullptr;
+  size_t n = 0;
+  if (int rc = gsdf_hip_indexed_host_ply(ix, &h, &n)) return rc;
+  big_memcpy(dst, h, n);
+  return GSDF_OK;
 }

@@ -193,6 +193,8 @@ inline void spec_adopt(gsdf_program* p) { if (p->spec_async.load(std::memory_ord
 // The evaluating kernel with distinct z rows for a specialised handle, built on first use: abi_eval.hip.
 void spec_leaf_dz(gsdf_program* p);
 void spec_leaf_dense(gsdf_program* p);
+// gleval.NormalsCentralDiff on device-resident points (abi_eval.hip; what gsdf_hip_normals3 launches): blocking.
+int normals3_dev(gsdf_program* p, const float* d_pos, float* d_nrm, size_t n, float step);
 // The view kernels for a specialised handle, built on its first gsdf_hip_render3: abi_eval.hip.
 void spec_view(gsdf_program* p);
 // The picture kernels for a specialised 2-D handle, built on its first gsdf_hip_image2_color: abi_eval.hip.

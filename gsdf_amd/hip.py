@@ -25,7 +25,9 @@ SYMBOLS = ["gsdf_hip_last_error", "gsdf_hip_init", "gsdf_hip_program_create", "g
            "gsdf_hip_eval3", "gsdf_hip_eval2", "gsdf_hip_eval3_dev", "gsdf_hip_eval2_dev", "gsdf_hip_normals3", "gsdf_hip_image2", "gsdf_hip_image2_color", "gsdf_hip_picture_size", "gsdf_hip_color_iq", "gsdf_hip_color_gradient", "gsdf_hip_view_orbit", "gsdf_hip_render3",
            "gsdf_hip_mesh_octree", "gsdf_hip_mesh_dualcontour", "gsdf_hip_mesh_flat", "gsdf_hip_mesh_stats_get", "gsdf_hip_mesh_read", "gsdf_hip_mesh_dev_tris",
            "gsdf_hip_mesh_stl", "gsdf_hip_mesh_host_tris", "gsdf_hip_mesh_host_stl", "gsdf_hip_mesh_destroy", "gsdf_hip_brick_owner", "gsdf_hip_slab_range",
-           "gsdf_hip_mesh_payload", "gsdf_hip_mesh_march", "gsdf_hip_mesh_stage_ms", "gsdf_hip_mesh_octree_start", "gsdf_hip_mesh_octree_wait", "gsdf_hip_comm_transport", "gsdf_hip_gather_plan"]
+           "gsdf_hip_mesh_payload", "gsdf_hip_mesh_march", "gsdf_hip_mesh_stage_ms", "gsdf_hip_mesh_octree_start", "gsdf_hip_mesh_octree_wait", "gsdf_hip_comm_transport", "gsdf_hip_gather_plan",
+           "gsdf_hip_mesh_read_records", "gsdf_hip_mesh_weld", "gsdf_hip_indexed_counts", "gsdf_hip_indexed_stats_get", "gsdf_hip_indexed_read",
+           "gsdf_hip_indexed_normals", "gsdf_hip_indexed_read_normals", "gsdf_hip_indexed_ply", "gsdf_hip_indexed_host_ply", "gsdf_hip_indexed_destroy"]
 
 
 PRUNE_ASSUME_SDF = 1 << 30  # gsdf_hip.h: GSDF_PRUNE_ASSUME_SDF
@@ -69,6 +71,12 @@ class MeshStats(C.Structure):
                 ("active_leaves", C.c_uint64), ("levels", C.c_int), ("origin", C.c_float * 3), ("res", C.c_float),
                 ("ms_total", C.c_double), ("ms_prune", C.c_double), ("ms_leaf", C.c_double), ("ms_march", C.c_double),
                 ("evals_prune", C.c_uint64), ("evals_leaf", C.c_uint64), ("ms_emit", C.c_double), ("cut_leaves", C.c_uint64)]
+
+
+class IndexedStats(C.Structure):
+    """gsdf_indexed_stats (gsdf_hip.h): device times of a weld's stages and its hash table's figures."""
+    _fields_ = [("ms_keys", C.c_double), ("ms_insert", C.c_double), ("ms_number", C.c_double), ("ms_ply", C.c_double),
+                ("probes", C.c_uint64), ("table_cells", C.c_uint64), ("attempts", C.c_int32), ("has_normals", C.c_int32)]
 
 
 class HipError(RuntimeError):
@@ -168,6 +176,17 @@ def lib():
         L.gsdf_hip_mesh_host_stl.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
         L.gsdf_hip_mesh_destroy.argtypes = [C.c_void_p]
         L.gsdf_hip_mesh_destroy.restype = None
+        L.gsdf_hip_mesh_read_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.gsdf_hip_mesh_weld.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+        L.gsdf_hip_indexed_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+        L.gsdf_hip_indexed_stats_get.argtypes = [C.c_void_p, C.POINTER(IndexedStats)]
+        L.gsdf_hip_indexed_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.gsdf_hip_indexed_normals.argtypes = [C.c_void_p, C.c_void_p, C.c_float]
+        L.gsdf_hip_indexed_read_normals.argtypes = [C.c_void_p, C.c_void_p]
+        L.gsdf_hip_indexed_ply.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.gsdf_hip_indexed_host_ply.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+        L.gsdf_hip_indexed_destroy.argtypes = [C.c_void_p]
+        L.gsdf_hip_indexed_destroy.restype = None
         L.gsdf_hip_brick_owner.restype = C.c_uint32
         L.gsdf_hip_brick_owner.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         L.gsdf_hip_slab_range.restype = None
@@ -525,6 +544,24 @@ class OctreeHIP:
         _check(lib().gsdf_hip_mesh_march(self._mesh))
         return self
 
+    def records(self):
+        """The cut-leaf records of a records mesh, in the order marching cubes takes them (gsdf_hip_mesh_read_records):
+        (dist (n, 8) float32, leaf (n, 3) integer coordinates, case (n,))."""
+        n = C.c_uint64()
+        _check(lib().gsdf_hip_mesh_read_records(self._mesh, None, 0, C.byref(n)))
+        raw = np.zeros((n.value, 10), np.uint32)
+        if n.value:
+            _check(lib().gsdf_hip_mesh_read_records(self._mesh, raw.ctypes.data, n.value, None))
+        leaf = np.stack([raw[:, 8] & 0xffff, raw[:, 8] >> 16, raw[:, 9] & 0xffff], axis=1).astype(np.int64)
+        return raw[:, :8].copy().view(np.float32), leaf, (raw[:, 9] >> 16).astype(np.int64)
+
+    def weld(self):
+        """The mesh with its marching-cubes vertices welded by lattice edge (gsdf_hip_mesh_weld): an IndexedHIP. For a mesh made
+        with payload=PAYLOAD_RECORDS and shard_count 1, marched or not."""
+        h = C.c_void_p()
+        _check(lib().gsdf_hip_mesh_weld(self._mesh, C.byref(h)))
+        return IndexedHIP(h)
+
     def n_tris(self):
         return int(self.stats.n_tris)
 
@@ -578,6 +615,70 @@ class OctreeHIP:
         p, ln = C.c_void_p(), C.c_size_t()
         _check(lib().gsdf_hip_mesh_host_stl(self._mesh, C.byref(p), C.byref(ln)))
         return self._view(p.value, ln.value, np.uint8)
+
+
+class IndexedHIP:
+    """An indexed triangle mesh resident on the device (gsdf_indexed): vertices, faces, the vertices' lattice keys, optional
+    normals, and its binary PLY. Independent of the mesh it was welded from."""
+
+    def __init__(self, handle):
+        self._h = handle
+        nv, nf, ms = C.c_uint64(), C.c_uint64(), C.c_double()
+        _check(lib().gsdf_hip_indexed_counts(handle, C.byref(nv), C.byref(nf), C.byref(ms)))
+        self.n_verts, self.n_tris, self.ms_device = int(nv.value), int(nf.value), float(ms.value)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().gsdf_hip_indexed_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def stats(self):
+        st = IndexedStats()
+        _check(lib().gsdf_hip_indexed_stats_get(self._h, C.byref(st)))
+        return st
+
+    def read(self):
+        """(verts (V, 3) float32, idx (F, 3) uint32, keys (V,) uint64)."""
+        v, i, k = np.empty((self.n_verts, 3), np.float32), np.empty((self.n_tris, 3), np.uint32), np.empty(self.n_verts, np.uint64)
+        _check(lib().gsdf_hip_indexed_read(self._h, v.ctypes.data, i.ctypes.data, k.ctypes.data))
+        return v, i, k
+
+    def normals(self, sdf, step):
+        """gleval.NormalsCentralDiff of `sdf` at the vertices, computed and kept on the device; returns them (V, 3) float32."""
+        _check(lib().gsdf_hip_indexed_normals(self._h, sdf._h, np.float32(step)))
+        n = np.empty((self.n_verts, 3), np.float32)
+        _check(lib().gsdf_hip_indexed_read_normals(self._h, n.ctypes.data))
+        return n
+
+    def ply_size(self):
+        ln = C.c_size_t()
+        lib().gsdf_hip_indexed_ply(self._h, None, 0, C.byref(ln))
+        return int(ln.value)
+
+    def ply(self):
+        """The binary PLY file as bytes (gsdf_hip_indexed_ply: packed on the device, copied into a buffer of the caller's)."""
+        buf = np.empty(self.ply_size(), np.uint8)
+        ln = C.c_size_t()
+        _check(lib().gsdf_hip_indexed_ply(self._h, buf.ctypes.data, buf.size, C.byref(ln)))
+        return buf[:ln.value].tobytes()
+
+    def ply_view(self):
+        """The same file as a read-only uint8 array over pinned host memory the handle owns (one DMA, no copy): valid until
+        normals() is called or the handle is freed."""
+        p, ln = C.c_void_p(), C.c_size_t()
+        _check(lib().gsdf_hip_indexed_host_ply(self._h, C.byref(p), C.byref(ln)))
+        raw = (C.c_ubyte * ln.value).from_address(p.value)
+        raw._owner = self
+        a = np.frombuffer(raw, dtype=np.uint8)
+        a.flags.writeable = False
+        return a
 
 
 class PendingMesh:

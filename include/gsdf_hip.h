@@ -421,6 +421,11 @@ int gsdf_hip_mesh_stage_ms(const gsdf_mesh* m, double* ms, const char** names, i
 /* What the mesh holds: GSDF_PAYLOAD_TRIANGLES or GSDF_PAYLOAD_RECORDS (gsdf_mesh_opts.payload); *n_records / *payload_bytes
  * (optional) = its cut-leaf records and the size of their packed form (0 for a mesh of triangles). */
 int gsdf_hip_mesh_payload(const gsdf_mesh* m, uint64_t* n_records, uint64_t* payload_bytes);
+/* Host copy of a records mesh's cut-leaf records, in the order marching cubes takes them: 10 words each -- the 8 corner distances
+ * (float32 bits, Box.Vertices order), lx | ly << 16, lz | case << 16 (the leaf's integer coordinates and its marching-cubes case).
+ * Works while the mesh holds records, and after gsdf_hip_mesh_march on a mesh gsdf_hip_mesh_weld accepts. *n_records optional;
+ * dst NULL to query it. */
+int gsdf_hip_mesh_read_records(const gsdf_mesh* m, uint32_t* dst, uint64_t dst_records, uint64_t* n_records);
 /* Marching cubes over a mesh's packed records, in place: afterwards it holds triangles (stats.n_tris was known before) and
  * every accessor below works. No-op on a mesh of triangles. glrender/marchcubes.go:14-98. */
 int gsdf_hip_mesh_march(gsdf_mesh* m);
@@ -440,6 +445,66 @@ int gsdf_hip_mesh_host_stl(gsdf_mesh* m, const uint8_t** stl, size_t* len);
 /* Releases the mesh. Its device buffers go to a per-process pool that the next meshes (and gathers) draw from -- up to 16 idle
  * buffers are kept (environment: GSDF_HIP_POOL_MAX), beyond that the smallest is freed. */
 void gsdf_hip_mesh_destroy(gsdf_mesh* m);
+
+/* ---- indexed meshes: the marching-cubes vertices welded on device (no reference counterpart: the reference's mesh is a triangle
+ *      list, SURVEY.md "no vertex welding") ---------------------------------------------------------------------------------------
+ *
+ * The two to four copies of a vertex that neighbouring cubes emit differ in their last bits (a leaf's corner is (O + res (i-1)) + res
+ * seen from one leaf and O + res i from the next; half the marching-cubes edge pairs run against their axis), so they cannot be
+ * merged by comparing floats. The cut-leaf records carry the leaves' integer coordinates: vertices are welded by the LATTICE EDGE
+ * (or lattice point) they sit on, which is exact.
+ *
+ * Soup slot. Slot s = 3 t + c is corner c of triangle t, in the order gsdf_hip_mesh_march produces for the same mesh.
+ * Key. One uint64 per slot: ix | iy << 20 | iz << 40 | kind << 60. Let v1, v2 be the corner distances at the two ends p1, p2 of the
+ *   cube edge mcInterpolate (marchcubes.go:76-98) is called on for that slot. If it returns p1 or p2 unchanged -- exactly one of
+ *   |v1|, |v2| is below 1e-12 -- the key names that LATTICE POINT: kind 3, (ix, iy, iz) = the leaf's integer coordinates + that
+ *   corner's offset (0 or 1 per axis). Otherwise (both or neither below 1e-12, a NaN included: the comparison is false) it names the
+ *   LATTICE EDGE: kind = the axis the edge runs along (0 x, 1 y, 2 z), (ix, iy, iz) = the leaf's coordinates + the offset of the
+ *   edge's lower end. The leaf's coordinates are those of its cut-leaf record (0 .. 2^(levels-1) - 1).
+ * Vertices. A vertex is the set of slots with one key. Vertices are numbered by the smallest slot they contain, in increasing order;
+ *   a vertex's position is the position that smallest slot has in the marched soup, bit for bit. (The other slots of the vertex
+ *   lie within a few ulp of it: far below res / 64 per coordinate at the 17 levels the mesher allows.)
+ * Faces. idx[s] is the number of slot s's vertex. All F triangles are kept, degenerate ones included: F == stats.n_tris.
+ * Determinism. The result is a function of the records alone, not of the order in which threads arrive.
+ *
+ * gsdf_hip_mesh_weld takes a mesh of the octree mesher made with payload = GSDF_PAYLOAD_RECORDS and shard_count == 1, marched
+ * in place already (gsdf_hip_mesh_march: the mesh keeps its records for this) or not (the mesh stays as it is). Every other mesh
+ * -- triangle payload, flat, dual contouring, minecraft, gathered, sharded -- is refused with GSDF_ERR_BAD_ARGUMENT and a text that
+ * says what is required; a mesh with 3 F >= 2^32 with GSDF_ERR_CAPACITY; an empty one with GSDF_ERR_EMPTY_BUFFERS. The result is
+ * independent of the mesh afterwards. Kernels: gsdf_amd/csrc/kernels_weld.h. */
+typedef struct gsdf_indexed gsdf_indexed; /* welded mesh, resident in HBM */
+typedef struct gsdf_indexed_stats {
+  double ms_keys;        /* device time, HIP events: the slots' keys from the records */
+  double ms_insert;      /* the hash table (all attempts) */
+  double ms_number;      /* owner lookup, vertex numbering, position gather, index write */
+  double ms_ply;         /* the last PLY pack (0 before gsdf_hip_indexed_ply / _host_ply) */
+  uint64_t probes;       /* table cells inspected by the inserting pass that succeeded */
+  uint64_t table_cells;  /* its capacity (a power of two, >= 2 V) */
+  int32_t attempts;      /* inserting passes run: 1 unless the table had to grow */
+  int32_t has_normals;
+} gsdf_indexed_stats;
+GSDF_ABI_ASSERT(sizeof(gsdf_indexed_stats) == 56, "gsdf_indexed_stats is 56 bytes");
+int gsdf_hip_mesh_weld(const gsdf_mesh* m, gsdf_indexed** out);
+/* Each output optional. ms_device: device time of the whole weld (keys + table + numbering), HIP events. */
+int gsdf_hip_indexed_counts(const gsdf_indexed* ix, uint64_t* n_verts, uint64_t* n_tris, double* ms_device);
+int gsdf_hip_indexed_stats_get(const gsdf_indexed* ix, gsdf_indexed_stats* st);
+/* Host copies, each optional: verts 3 V floats, idx 3 F vertex numbers, keys V (the key of each vertex: what a later weld across
+ * shards would match on). */
+int gsdf_hip_indexed_read(const gsdf_indexed* ix, float* verts, uint32_t* idx, uint64_t* keys);
+/* gleval.NormalsCentralDiff (gleval/gleval.go:53-108; not normalised) of program p at the welded vertices, kept on device: the
+ * values gsdf_hip_normals3 gives at the same points with the same step. The PLY carries them from then on; _read_normals copies
+ * them out (3 V floats). */
+int gsdf_hip_indexed_normals(gsdf_indexed* ix, gsdf_program* p, float step);
+int gsdf_hip_indexed_read_normals(const gsdf_indexed* ix, float* normals);
+/* Binary PLY, packed on device and moved by one DMA. The file: the header lines "ply", "format binary_little_endian 1.0", one
+ * "comment gsdf" line padded with spaces so that the header's length is a multiple of 4, "element vertex V", "property float x" /
+ * y / z (and nx / ny / nz once normals were asked for), "element face F", "property list uchar int vertex_indices", "end_header",
+ * each ended by '\n'; then V records of 3 (6) little-endian floats; then F records of one byte 3 and three little-endian int32.
+ * _ply copies it into dst (*len = its size; dst NULL or cap short: GSDF_ERR_SHORT_BUFFER with *len set); _host_ply returns a view
+ * of pinned host memory the handle owns, valid until the next gsdf_hip_indexed_normals or gsdf_hip_indexed_destroy. */
+int gsdf_hip_indexed_ply(gsdf_indexed* ix, uint8_t* dst, size_t cap, size_t* len);
+int gsdf_hip_indexed_host_ply(gsdf_indexed* ix, const uint8_t** ply, size_t* len);
+void gsdf_hip_indexed_destroy(gsdf_indexed* ix);
 
 /* ---- multi-GPU (one process per GPU). The meshers shard with NO data-path collective (shard_rank / shard_count above); the
  * one exchange is the final variable-length gather of the ranks' results, over xGMI, inside this library: a Go caller needs no
