@@ -6,7 +6,12 @@
 The octree mesher leaves the cut-leaf records on the device (payload = records); gsdf_hip_mesh_weld turns them into vertices and
 faces by lattice edge -- exact, where a float comparison of the triangle list's corners leaves cracks -- and the file is packed on
 the device and arrives in pinned host memory by one DMA (gsdf_hip_indexed_host_ply). Prints V, F, the file's bytes against the
-binary STL's of the same mesh, and the weld's device time."""
+binary STL's of the same mesh, and the weld's device time.
+
+    --report             also print what gsdf_hip_indexed_report says of the mesh (watertight and oriented? shells, volume, area,
+                         centre of mass; its device time per stage) and the shell table
+    --min-shell-tris N   write the mesh without the shells of fewer than N faces (specks)
+    --drop-cavities      ... and without the shells of negative volume (enclosed cavities)"""
 import argparse
 import os
 import sys
@@ -17,6 +22,19 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 SCENES = ["npt-flange", "bolt", "knurled-cylinder", "glyph-plate", "fibonacci-showerhead"]
 
 
+def print_report(name, ix):
+    r = ix.report()
+    print(f"{name} report: {'closed and oriented' if r.closed_oriented else 'NOT closed and oriented'}; V {r.n_verts} (used {r.used_verts}) "
+          f"E {r.edges} F {r.n_tris}, Euler {r.euler}; degenerate {r.degenerate}, non-finite {r.nonfinite}, boundary {r.boundary_edges}, "
+          f"non-manifold {r.nonmanifold_edges}, misoriented {r.misoriented_edges}; {r.n_shells} shells; volume {r.volume:.9g}, area {r.area:.9g}, "
+          f"centroid ({r.centroid[0]:.6g}, {r.centroid[1]:.6g}, {r.centroid[2]:.6g}); device {r.ms_edges + r.ms_shells + r.ms_measure:.3f} ms "
+          f"(edges {r.ms_edges:.3f}, shells {r.ms_shells:.3f}, measures {r.ms_measure:.3f}; {r.probes} probes of {r.table_cells} cells, {r.attempts} pass)")
+    for k, s in enumerate(ix.shells()):
+        print(f"  shell {k}: label {s['label']}, V {s['n_verts']} E {s['edges']} F {s['n_tris']}, Euler {s['euler']}, volume {s['volume']:.9g}"
+              f"{' (cavity)' if s['volume'] < 0 else ''}, area {s['area']:.9g}, boundary {s['boundary_edges']}, non-manifold {s['nonmanifold_edges']}, "
+              f"misoriented {s['misoriented_edges']}")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("scene", choices=SCENES)
@@ -24,6 +42,9 @@ def main(argv=None):
     ap.add_argument("--normals", action="store_true", help="central-difference normals at the vertices (nx ny nz in the file)")
     ap.add_argument("-o", "--output", default=None)
     ap.add_argument("--interpreter", action="store_true", help="skip the per-tree kernel build")
+    ap.add_argument("--report", action="store_true", help="print the mesh's report and its shell table")
+    ap.add_argument("--min-shell-tris", type=int, default=0, help="drop the shells with fewer faces than this")
+    ap.add_argument("--drop-cavities", action="store_true", help="drop the shells of negative volume")
     args = ap.parse_args(argv)
 
     import numpy as np
@@ -43,6 +64,14 @@ def main(argv=None):
     t2 = time.perf_counter()
     if args.normals:
         ix.normals(sdf, np.float32(float(res) * 1e-3))
+    if args.report:
+        print_report(args.scene, ix)
+    if args.min_shell_tris > 0 or args.drop_cavities:
+        keep = ix.select_shells(args.min_shell_tris, args.drop_cavities)
+        whole = ix
+        ix = whole.extract(keep)
+        print(f"kept {int(keep.sum())} of {len(keep)} shells: V {whole.n_verts} -> {ix.n_verts}, F {whole.n_tris} -> {ix.n_tris} "
+              f"(extract {ix.ms_device:.3f} ms device)")
     out = args.output or f"{args.scene}.ply"
     data = ix.ply_view()
     with open(out, "wb") as f:

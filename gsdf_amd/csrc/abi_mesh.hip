@@ -1,12 +1,14 @@
 // abi_mesh.hip -- C ABI (include/gsdf_hip.h), mesher side: glrender.Octree + marchCubes, FlatRenderer and
 // DualContourRenderer on device, and the accessors of the resulting mesh (ReadTriangles drain, STL, pinned host views).
-// Kernels: kernels_octree.h, kernels_flat.h, kernels_dc.h, kernels_stl.h, kernels_weld.h (indexed meshes, binary PLY).
+// Kernels: kernels_octree.h, kernels_flat.h, kernels_dc.h, kernels_stl.h, kernels_weld.h (indexed meshes, binary PLY), kernels_topo.h
+// (their report: edge classes, shells, measures; extract).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <vector>
 
 #include "kernels_common.h"
 #include "kernels_octree.h"
@@ -15,6 +17,7 @@
 #include "kernels_stl.h"
 #include "kernels_minecraft.h"
 #include "kernels_weld.h"
+#include "kernels_topo.h"
 #include "abi_program.h"
 #include "host_math.h"
 
@@ -1298,6 +1301,11 @@ struct gsdf_indexed {
   void* h_ply = nullptr;
   size_t h_ply_cap = 0, ply_len = 0;
   bool ply_valid = false;
+  // gsdf_hip_indexed_report's result, computed once: the report, the shell table, the shell numbers of vertices and faces (device)
+  bool topo_valid = false;
+  gsdf_indexed_report rep{};
+  std::vector<gsdf_shell> shells;
+  PoolBuf shell_of_vertex, shell_of_face;
 };
 
 extern "C" void gsdf_hip_indexed_destroy(gsdf_indexed* ix) {
@@ -1534,5 +1542,312 @@ extern "C" int gsdf_hip_indexed_ply(gsdf_indexed* ix, uint8_t* dst, size_t cap, 
   size_t n = 0;
   if (int rc = gsdf_hip_indexed_host_ply(ix, &h, &n)) return rc;
   big_memcpy(dst, h, n);
+  return GSDF_OK;
+}
+
+// ---- indexed meshes: report and extract (kernels_topo.h; the contract is in include/gsdf_hip.h) ---------------------------------
+namespace {
+// an empty handle on the calling thread's device, with its own stream
+int indexed_new(int device, int num_cu, gsdf_indexed** out) {
+  gsdf_indexed* ix = new (std::nothrow) gsdf_indexed();
+  if (!ix) return fail(GSDF_ERR_BAD_ARGUMENT, "out of memory");
+  ix->device = device;
+  ix->num_cu = num_cu;
+  if (hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking) != hipSuccess) {
+    (void)hipGetLastError();
+    ix->stream = nullptr;
+    gsdf_hip_indexed_destroy(ix);
+    return fail(GSDF_ERR_HIP, "hipStreamCreate failed");
+  }
+  *out = ix;
+  return GSDF_OK;
+}
+unsigned blocks_of(uint64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
+float topo_unordered(unsigned o) {
+  const uint32_t bits = (o & 0x80000000u) ? (o ^ 0x80000000u) : ~o;
+  float f;
+  std::memcpy(&f, &bits, 4);
+  return f;
+}
+// low-word sum and (signed) rest sum of the quantised terms -> the integer they stand for
+__int128 topo_int(const unsigned long long* s) { return (__int128)(long long)s[1] * ((__int128)1 << 32) + (__int128)s[0]; }
+// that integer as float64 (one rounding) times 2^-shift (exact)
+double topo_value(__int128 t, int shift) { return std::ldexp((double)t, -shift); }
+double topo_quotient(double m, double v) {
+  if (v == 0.0) {
+    const uint64_t q = 0x7ff8000000000000ull;
+    double d;
+    std::memcpy(&d, &q, 8);
+    return d;
+  }
+  return m / v;
+}
+}  // namespace
+
+extern "C" int gsdf_hip_indexed_create(const float* verts, uint64_t n_verts, const uint32_t* idx, uint64_t n_tris, const uint64_t* keys, gsdf_indexed** out) {
+  if (!out) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  *out = nullptr;
+  if (n_verts == 0 || n_tris == 0) return fail(GSDF_ERR_EMPTY_BUFFERS, "empty buffers");
+  if (!verts || !idx) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  if (3 * n_tris >= ((uint64_t)1 << 32) || n_verts >= ((uint64_t)1 << 32))
+    return fail(GSDF_ERR_CAPACITY, "indexed mesh: vertices and 3 x triangles must stay below 2^32 (32-bit vertex numbers)");
+  for (uint64_t s = 0; s < 3 * n_tris; s++)
+    if (idx[s] >= n_verts)
+      return fail(GSDF_ERR_BAD_ARGUMENT, "indexed mesh: face " + std::to_string(s / 3) + " names vertex index " + std::to_string(idx[s]) + ", the mesh has " +
+                                             std::to_string(n_verts) + " vertices");
+  int device = 0, num_cu = 256;
+  HIP_TRY(hipGetDevice(&device));
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, device) == hipSuccess) num_cu = prop.multiProcessorCount;
+  gsdf_indexed* ix = nullptr;
+  if (int rc = indexed_new(device, num_cu, &ix)) return rc;
+  auto bail = [&](int code) { gsdf_hip_indexed_destroy(ix); return code; };
+  if (!ix->verts.take(device, n_verts * 12) || !ix->idx.take(device, n_tris * 12) || !ix->vkeys.take(device, n_verts * 8))
+    return bail(fail(GSDF_ERR_HIP, "indexed mesh: no device memory"));
+  hipError_t e = hipMemcpy(ix->verts.p, verts, n_verts * 12, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(ix->idx.p, idx, n_tris * 12, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = keys ? hipMemcpy(ix->vkeys.p, keys, n_verts * 8, hipMemcpyHostToDevice) : hipMemset(ix->vkeys.p, 0, n_verts * 8);
+  if (e != hipSuccess) return bail(fail(GSDF_ERR_HIP, std::string("indexed mesh upload: ") + hipGetErrorString(e)));
+  ix->n_verts = n_verts;
+  ix->n_tris = n_tris;
+  *out = ix;
+  return GSDF_OK;
+}
+
+// The report, the shell table and the shell numbers, once per handle.
+static int topo_ensure(gsdf_indexed* ix) {
+  if (ix->topo_valid) return GSDF_OK;
+  HIP_TRY(hipSetDevice(ix->device));
+  const int dev = ix->device;
+  hipStream_t s = ix->stream;
+  const uint64_t V = ix->n_verts, F = ix->n_tris;
+  const unsigned nb_v = blocks_of(V), nb_f = blocks_of(F);
+  const char* nomem = "report: no device memory for the workspace";
+  PoolBuf ctr, wctr, parent, used, root_of, shell_num, blk_cnt, blk_base, table, acc;
+  if (!ctr.take(dev, sizeof(TopoCounters)) || !wctr.take(dev, sizeof(WeldCounters)) || !parent.take(dev, V * 4) || !used.take(dev, V * 4) ||
+      !root_of.take(dev, V * 4) || !shell_num.take(dev, V * 4) || !blk_cnt.take(dev, (size_t)nb_v * 4) || !blk_base.take(dev, (size_t)nb_v * 4) ||
+      !ix->shell_of_vertex.take(dev, V * 4) || !ix->shell_of_face.take(dev, F * 4))
+    return fail(GSDF_ERR_HIP, nomem);
+  EventPair ev_e, ev_s, ev_m;
+  if (!ev_e.make() || !ev_s.make() || !ev_m.make()) return fail(GSDF_ERR_HIP, "hipEventCreate failed");
+  // 1. the edge table: about 3 F / 2 pairs at load <= 0.5; a pass that ends fuller, or that gave up on a pair, is repeated with
+  // twice the cells (GSDF_HIP_TOPO_CELLS_MIN lowers the first size: the tests' way into that path). Then the exponent.
+  uint64_t cells = 1024;
+  {
+    const char* e = getenv("GSDF_HIP_TOPO_CELLS_MIN");
+    const uint64_t want = e ? (uint64_t)strtoull(e, nullptr, 10) : 3 * F;
+    while (cells < want) cells <<= 1;
+  }
+  TopoCounters hc{};
+  int attempts = 0;
+  HIP_TRY(hipEventRecord(ev_e.a, s));
+  for (;;) {
+    if (cells > ((uint64_t)1 << 32)) return fail(GSDF_ERR_CAPACITY, "report: hash table capacity exceeded");
+    if (!table.take(dev, cells * 16)) return fail(GSDF_ERR_HIP, nomem);
+    attempts++;
+    HIP_TRY(hipMemsetAsync(table.p, 0xff, cells * 8, s));
+    HIP_TRY(hipMemsetAsync((uint8_t*)table.p + cells * 8, 0, cells * 8, s));
+    HIP_TRY(hipMemsetAsync(ctr.p, 0, sizeof(TopoCounters), s));
+    hipLaunchKernelGGL(topo_edge_insert_kernel, dim3(nb_f), dim3(BLOCK), 0, s, (const unsigned*)ix->idx.as<unsigned>(), (unsigned long long)F,
+                       table.as<unsigned long long>(), (unsigned*)(table.as<unsigned long long>() + cells), (unsigned)(cells - 1), ctr.as<TopoCounters>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&hc, ctr.p, sizeof hc, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (!hc.overflow && hc.distinct * 2 <= cells) break;
+    cells <<= 1;
+  }
+  hipLaunchKernelGGL(topo_maxbits_kernel, dim3(grid_for(3 * V, ix->num_cu, 8)), dim3(BLOCK), 0, s, (const float*)ix->verts.p, (unsigned long long)(3 * V),
+                     ctr.as<TopoCounters>());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(ev_e.b, s));
+  // 2. shells
+  HIP_TRY(hipEventRecord(ev_s.a, s));
+  hipLaunchKernelGGL(topo_parent_init_kernel, dim3(nb_v), dim3(BLOCK), 0, s, parent.as<unsigned>(), used.as<unsigned>(), (unsigned long long)V);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(topo_union_kernel, dim3(nb_f), dim3(BLOCK), 0, s, (const unsigned*)ix->idx.as<unsigned>(), (unsigned long long)F, parent.as<unsigned>(),
+                     used.as<unsigned>());
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(topo_root_kernel, dim3(nb_v), dim3(BLOCK), 0, s, (const unsigned*)parent.as<unsigned>(), (const unsigned*)used.as<unsigned>(),
+                     (unsigned long long)V, root_of.as<unsigned>(), blk_cnt.as<unsigned>(), ctr.as<TopoCounters>());
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(weld_block_scan_kernel, dim3(1), dim3(1024), 0, s, (const unsigned*)blk_cnt.as<unsigned>(), nb_v, blk_base.as<unsigned>(), wctr.as<WeldCounters>());
+  HIP_TRY(hipGetLastError());
+  WeldCounters hw{};
+  HIP_TRY(hipMemcpyAsync(&hw, wctr.p, sizeof hw, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(&hc, ctr.p, sizeof hc, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  const uint64_t n_shells = hw.n_verts;
+  if (n_shells > V) return fail(GSDF_ERR_HIP, "report: internal error (more shells than vertices)");
+  if (!acc.take(dev, (n_shells + 1) * sizeof(TopoShellAcc))) return fail(GSDF_ERR_HIP, nomem);
+  HIP_TRY(hipMemsetAsync(acc.p, 0, (n_shells + 1) * sizeof(TopoShellAcc), s));
+  hipLaunchKernelGGL(topo_number_kernel, dim3(nb_v), dim3(BLOCK), 0, s, (const unsigned*)root_of.as<unsigned>(), (const unsigned*)used.as<unsigned>(),
+                     (unsigned long long)V, (const unsigned*)blk_base.as<unsigned>(), shell_num.as<unsigned>(), acc.as<TopoShellAcc>());
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(topo_vertex_shell_kernel, dim3(nb_v), dim3(BLOCK), 0, s, (const unsigned*)root_of.as<unsigned>(), (const unsigned*)used.as<unsigned>(),
+                     (unsigned long long)V, (const unsigned*)shell_num.as<unsigned>(), ix->shell_of_vertex.as<unsigned>(), acc.as<TopoShellAcc>());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(ev_s.b, s));
+  // 3. measures and pair classes
+  const int biased = (int)(hc.maxbits >> 23);
+  const int e = (biased > 1 ? biased : 1) - 126;
+  const int sh_area = 59 - 2 * e, sh_vol = 62 - 3 * e, sh_mom = 62 - 4 * e;
+  HIP_TRY(hipEventRecord(ev_m.a, s));
+  hipLaunchKernelGGL(topo_measure_kernel, dim3(nb_f), dim3(BLOCK), 0, s, (const float*)ix->verts.p, (const unsigned*)ix->idx.as<unsigned>(), (unsigned long long)F,
+                     (const unsigned*)ix->shell_of_vertex.as<unsigned>(), ix->shell_of_face.as<unsigned>(), acc.as<TopoShellAcc>(), std::ldexp(1.0, sh_area),
+                     std::ldexp(1.0, sh_vol), std::ldexp(1.0, sh_mom));
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(topo_classify_kernel, dim3(blocks_of(cells)), dim3(BLOCK), 0, s, (const unsigned long long*)table.as<unsigned long long>(),
+                     (const unsigned*)(table.as<unsigned long long>() + cells), (unsigned long long)cells, (const unsigned*)ix->shell_of_vertex.as<unsigned>(),
+                     acc.as<TopoShellAcc>());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(ev_m.b, s));
+  std::vector<TopoShellAcc> ha(n_shells);
+  if (n_shells) HIP_TRY(hipMemcpyAsync(ha.data(), acc.p, n_shells * sizeof(TopoShellAcc), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  // the shells' records; the mesh's sums are the sums of the shells' integers
+  gsdf_indexed_report r{};
+  std::vector<gsdf_shell> shells(n_shells);
+  __int128 tot[5] = {0, 0, 0, 0, 0};
+  unsigned bb[6] = {TOPO_BB_MIN_INIT, TOPO_BB_MIN_INIT, TOPO_BB_MIN_INIT, TOPO_BB_MAX_INIT, TOPO_BB_MAX_INIT, TOPO_BB_MAX_INIT};
+  const int shift[5] = {sh_area, sh_vol, sh_mom, sh_mom, sh_mom};
+  uint64_t tris = 0, edges_by_shell = 0;
+  for (uint64_t k = 0; k < n_shells; k++) {
+    const TopoShellAcc& a = ha[k];
+    gsdf_shell& o = shells[k];
+    o.n_verts = a.n_verts; o.n_tris = a.n_tris; o.nonfinite = a.nonfinite;
+    o.edges = a.edges; o.boundary_edges = a.boundary; o.nonmanifold_edges = a.nonmanifold; o.misoriented_edges = a.misoriented;
+    o.euler = (int64_t)a.n_verts - (int64_t)a.edges + (int64_t)a.n_tris;
+    double val[5];
+    for (int q = 0; q < 5; q++) {
+      const __int128 t = topo_int(a.sum + 2 * q);
+      tot[q] += t;
+      val[q] = topo_value(t, shift[q]);
+    }
+    o.area = val[0]; o.volume = val[1];
+    for (int q = 0; q < 3; q++) o.centroid[q] = topo_quotient(val[2 + q], val[1]);
+    for (int q = 0; q < 6; q++) o.bbox[q] = topo_unordered(a.bb[q]);
+    for (int q = 0; q < 3; q++) { bb[q] = std::min(bb[q], a.bb[q]); bb[3 + q] = std::max(bb[3 + q], a.bb[3 + q]); }
+    o.label = a.label;
+    r.nonfinite += a.nonfinite; r.boundary_edges += a.boundary; r.nonmanifold_edges += a.nonmanifold; r.misoriented_edges += a.misoriented;
+    tris += a.n_tris; edges_by_shell += a.edges;
+  }
+  if (tris != F - hc.degenerate || edges_by_shell != hc.distinct) return fail(GSDF_ERR_HIP, "report: internal error (the shells' counts do not add up)");
+  r.n_verts = V; r.n_tris = F; r.degenerate = hc.degenerate; r.used_verts = hc.used_verts; r.edges = hc.distinct; r.n_shells = n_shells;
+  r.euler = (int64_t)r.used_verts - (int64_t)r.edges + (int64_t)(F - r.degenerate);
+  r.area = topo_value(tot[0], shift[0]);
+  r.volume = topo_value(tot[1], shift[1]);
+  for (int q = 0; q < 3; q++) r.centroid[q] = topo_quotient(topo_value(tot[2 + q], shift[2 + q]), r.volume);
+  for (int q = 0; q < 6; q++) r.bbox[q] = topo_unordered(bb[q]);
+  r.closed_oriented = (r.degenerate == 0 && r.boundary_edges == 0 && r.nonmanifold_edges == 0 && r.misoriented_edges == 0) ? 1 : 0;
+  r.exponent = e;
+  r.ms_edges = ev_e.ms(); r.ms_shells = ev_s.ms(); r.ms_measure = ev_m.ms();
+  r.probes = hc.probes; r.table_cells = cells; r.attempts = attempts;
+  ix->rep = r;
+  ix->shells.swap(shells);
+  ix->topo_valid = true;
+  return GSDF_OK;
+}
+
+extern "C" int gsdf_hip_indexed_report(gsdf_indexed* ix, gsdf_indexed_report* rep) {
+  if (!ix || !rep) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  if (int rc = topo_ensure(ix)) return rc;
+  *rep = ix->rep;
+  return GSDF_OK;
+}
+
+extern "C" int gsdf_hip_indexed_shells(gsdf_indexed* ix, gsdf_shell* dst, uint64_t cap, uint64_t* n) {
+  if (!ix || !n) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  if (int rc = topo_ensure(ix)) return rc;
+  *n = ix->shells.size();
+  if (!dst) return GSDF_OK;
+  if (cap < *n) return fail(GSDF_ERR_SHORT_BUFFER, "short buffer");
+  if (*n) std::memcpy(dst, ix->shells.data(), *n * sizeof(gsdf_shell));
+  return GSDF_OK;
+}
+
+extern "C" int gsdf_hip_indexed_read_shell_of(gsdf_indexed* ix, uint32_t* shell_of_vertex, uint32_t* shell_of_face) {
+  if (!ix) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  if (int rc = topo_ensure(ix)) return rc;
+  HIP_TRY(hipSetDevice(ix->device));
+  if (shell_of_vertex) HIP_TRY(hipMemcpy(shell_of_vertex, ix->shell_of_vertex.p, ix->n_verts * 4, hipMemcpyDeviceToHost));
+  if (shell_of_face) HIP_TRY(hipMemcpy(shell_of_face, ix->shell_of_face.p, ix->n_tris * 4, hipMemcpyDeviceToHost));
+  return GSDF_OK;
+}
+
+extern "C" int gsdf_hip_indexed_extract(gsdf_indexed* ix, const uint8_t* keep_shell, int drop_degenerate, gsdf_indexed** out) {
+  if (!ix || !out) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  *out = nullptr;
+  if (int rc = topo_ensure(ix)) return rc;
+  HIP_TRY(hipSetDevice(ix->device));
+  const int dev = ix->device;
+  hipStream_t s = ix->stream;
+  const uint64_t V = ix->n_verts, F = ix->n_tris, n_shells = ix->shells.size();
+  const unsigned nb_f = blocks_of(F);
+  const char* nomem = "extract: no device memory for the workspace";
+  PoolBuf d_keep, keep, blk_cnt, blk_base, wctr, first, vnum;
+  if (!keep.take(dev, F) || !blk_cnt.take(dev, (size_t)blocks_of(3 * F) * 4) || !blk_base.take(dev, (size_t)blocks_of(3 * F) * 4) ||
+      !wctr.take(dev, sizeof(WeldCounters)) || !first.take(dev, V * 4) || !vnum.take(dev, V * 4))
+    return fail(GSDF_ERR_HIP, nomem);
+  if (keep_shell && n_shells) {
+    if (!d_keep.take(dev, n_shells)) return fail(GSDF_ERR_HIP, nomem);
+    HIP_TRY(hipMemcpyAsync(d_keep.p, keep_shell, n_shells, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));  // (the caller's bytes are pageable: they were read by now)
+  }
+  EventPair ev;
+  if (!ev.make()) return fail(GSDF_ERR_HIP, "hipEventCreate failed");
+  HIP_TRY(hipEventRecord(ev.a, s));
+  // kept faces, in order
+  hipLaunchKernelGGL(topo_keep_kernel, dim3(nb_f), dim3(BLOCK), 0, s, (const unsigned*)ix->shell_of_face.as<unsigned>(), (unsigned long long)F,
+                     (const unsigned char*)(keep_shell ? d_keep.p : nullptr), (!drop_degenerate && !keep_shell) ? 1 : 0, keep.as<unsigned char>(), blk_cnt.as<unsigned>());
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(weld_block_scan_kernel, dim3(1), dim3(1024), 0, s, (const unsigned*)blk_cnt.as<unsigned>(), nb_f, blk_base.as<unsigned>(), wctr.as<WeldCounters>());
+  HIP_TRY(hipGetLastError());
+  WeldCounters hw{};
+  HIP_TRY(hipMemcpyAsync(&hw, wctr.p, sizeof hw, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  const uint64_t F2 = hw.n_verts;
+  if (F2 == 0) return fail(GSDF_ERR_EMPTY_BUFFERS, "extract: nothing kept");
+  if (F2 > F) return fail(GSDF_ERR_HIP, "extract: internal error (more faces kept than there are)");
+  gsdf_indexed* nx = nullptr;
+  if (int rc = indexed_new(dev, ix->num_cu, &nx)) return rc;
+  auto bail = [&](int code) { gsdf_hip_indexed_destroy(nx); return code; };
+#define HIP_TRYX(expr)                                                                                          \
+  do {                                                                                                          \
+    hipError_t _e = (expr);                                                                                     \
+    if (_e != hipSuccess) return bail(fail(GSDF_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e))); \
+  } while (0)
+  const uint64_t S2 = 3 * F2;
+  const unsigned nb_s = blocks_of(S2);
+  if (!nx->idx.take(dev, S2 * 4)) return bail(fail(GSDF_ERR_HIP, nomem));
+  HIP_TRYX(hipMemsetAsync(first.p, 0xff, V * 4, s));
+  hipLaunchKernelGGL(topo_compact_kernel, dim3(nb_f), dim3(BLOCK), 0, s, (const unsigned*)ix->idx.as<unsigned>(), (const unsigned char*)keep.as<unsigned char>(),
+                     (unsigned long long)F, (const unsigned*)blk_base.as<unsigned>(), nx->idx.as<unsigned>(), first.as<unsigned>());
+  HIP_TRYX(hipGetLastError());
+  // vertices by their smallest kept slot
+  hipLaunchKernelGGL(topo_owner_kernel, dim3(nb_s), dim3(BLOCK), 0, s, (const unsigned*)nx->idx.as<unsigned>(), (unsigned long long)S2,
+                     (const unsigned*)first.as<unsigned>(), blk_cnt.as<unsigned>());
+  HIP_TRYX(hipGetLastError());
+  hipLaunchKernelGGL(weld_block_scan_kernel, dim3(1), dim3(1024), 0, s, (const unsigned*)blk_cnt.as<unsigned>(), nb_s, blk_base.as<unsigned>(), wctr.as<WeldCounters>());
+  HIP_TRYX(hipGetLastError());
+  HIP_TRYX(hipMemcpyAsync(&hw, wctr.p, sizeof hw, hipMemcpyDeviceToHost, s));
+  HIP_TRYX(hipStreamSynchronize(s));
+  const uint64_t V2 = hw.n_verts;
+  if (V2 == 0 || V2 > V) return bail(fail(GSDF_ERR_HIP, "extract: internal error (kept vertices)"));
+  if (!nx->verts.take(dev, V2 * 12) || !nx->vkeys.take(dev, V2 * 8) || (ix->has_normals && !nx->normals.take(dev, V2 * 12))) return bail(fail(GSDF_ERR_HIP, nomem));
+  hipLaunchKernelGGL(topo_renumber_kernel, dim3(nb_s), dim3(BLOCK), 0, s, (const unsigned*)nx->idx.as<unsigned>(), (unsigned long long)S2,
+                     (const unsigned*)first.as<unsigned>(), (const unsigned*)blk_base.as<unsigned>(), vnum.as<unsigned>(), (const unsigned*)ix->verts.as<unsigned>(),
+                     (const unsigned long long*)ix->vkeys.as<unsigned long long>(), (const unsigned*)(ix->has_normals ? ix->normals.p : nullptr),
+                     nx->verts.as<unsigned>(), nx->vkeys.as<unsigned long long>(), (unsigned*)(ix->has_normals ? nx->normals.p : nullptr));
+  HIP_TRYX(hipGetLastError());
+  hipLaunchKernelGGL(topo_reindex_kernel, dim3(nb_s), dim3(BLOCK), 0, s, nx->idx.as<unsigned>(), (unsigned long long)S2, (const unsigned*)vnum.as<unsigned>());
+  HIP_TRYX(hipGetLastError());
+  HIP_TRYX(hipEventRecord(ev.b, s));
+  HIP_TRYX(hipStreamSynchronize(s));
+#undef HIP_TRYX
+  nx->n_verts = V2;
+  nx->n_tris = F2;
+  nx->has_normals = ix->has_normals;
+  nx->ms_device = ev.ms();
+  *out = nx;
   return GSDF_OK;
 }

@@ -27,7 +27,8 @@ SYMBOLS = ["gsdf_hip_last_error", "gsdf_hip_init", "gsdf_hip_program_create", "g
            "gsdf_hip_mesh_stl", "gsdf_hip_mesh_host_tris", "gsdf_hip_mesh_host_stl", "gsdf_hip_mesh_destroy", "gsdf_hip_brick_owner", "gsdf_hip_slab_range",
            "gsdf_hip_mesh_payload", "gsdf_hip_mesh_march", "gsdf_hip_mesh_stage_ms", "gsdf_hip_mesh_octree_start", "gsdf_hip_mesh_octree_wait", "gsdf_hip_comm_transport", "gsdf_hip_gather_plan",
            "gsdf_hip_mesh_read_records", "gsdf_hip_mesh_weld", "gsdf_hip_indexed_counts", "gsdf_hip_indexed_stats_get", "gsdf_hip_indexed_read",
-           "gsdf_hip_indexed_normals", "gsdf_hip_indexed_read_normals", "gsdf_hip_indexed_ply", "gsdf_hip_indexed_host_ply", "gsdf_hip_indexed_destroy"]
+           "gsdf_hip_indexed_normals", "gsdf_hip_indexed_read_normals", "gsdf_hip_indexed_ply", "gsdf_hip_indexed_host_ply", "gsdf_hip_indexed_destroy",
+           "gsdf_hip_indexed_create", "gsdf_hip_indexed_report", "gsdf_hip_indexed_shells", "gsdf_hip_indexed_read_shell_of", "gsdf_hip_indexed_extract"]
 
 
 PRUNE_ASSUME_SDF = 1 << 30  # gsdf_hip.h: GSDF_PRUNE_ASSUME_SDF
@@ -77,6 +78,28 @@ class IndexedStats(C.Structure):
     """gsdf_indexed_stats (gsdf_hip.h): device times of a weld's stages and its hash table's figures."""
     _fields_ = [("ms_keys", C.c_double), ("ms_insert", C.c_double), ("ms_number", C.c_double), ("ms_ply", C.c_double),
                 ("probes", C.c_uint64), ("table_cells", C.c_uint64), ("attempts", C.c_int32), ("has_normals", C.c_int32)]
+
+
+class IndexedReport(C.Structure):
+    """gsdf_indexed_report (gsdf_hip.h): counts, edge classes, shells and measures of an indexed mesh; bytes 0 .. 159 (RESULT_BYTES)
+    are a function of the mesh alone, the rest says what the run cost."""
+    _fields_ = [("n_verts", C.c_uint64), ("n_tris", C.c_uint64), ("degenerate", C.c_uint64), ("nonfinite", C.c_uint64), ("used_verts", C.c_uint64),
+                ("edges", C.c_uint64), ("boundary_edges", C.c_uint64), ("nonmanifold_edges", C.c_uint64), ("misoriented_edges", C.c_uint64),
+                ("n_shells", C.c_uint64), ("euler", C.c_int64), ("area", C.c_double), ("volume", C.c_double), ("centroid", C.c_double * 3),
+                ("bbox", C.c_float * 6), ("closed_oriented", C.c_int32), ("exponent", C.c_int32),
+                ("ms_edges", C.c_double), ("ms_shells", C.c_double), ("ms_measure", C.c_double), ("probes", C.c_uint64), ("table_cells", C.c_uint64),
+                ("attempts", C.c_int32), ("reserved", C.c_int32)]
+    RESULT_BYTES = 160
+
+    def result_bytes(self):
+        return bytes(self)[:self.RESULT_BYTES]
+
+
+# gsdf_shell (gsdf_hip.h) as a numpy record: one per shell, in increasing order of the label (the shell's smallest vertex number)
+SHELL_DTYPE = np.dtype([("n_verts", "<u8"), ("n_tris", "<u8"), ("nonfinite", "<u8"), ("edges", "<u8"), ("boundary_edges", "<u8"),
+                        ("nonmanifold_edges", "<u8"), ("misoriented_edges", "<u8"), ("euler", "<i8"), ("area", "<f8"), ("volume", "<f8"),
+                        ("centroid", "<f8", (3,)), ("bbox", "<f4", (6,)), ("label", "<u4"), ("reserved", "<u4")])
+SHELL_NONE = 0xffffffff  # shell_of(): a vertex no non-degenerate face names / a degenerate face
 
 
 class HipError(RuntimeError):
@@ -187,6 +210,11 @@ def lib():
         L.gsdf_hip_indexed_host_ply.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
         L.gsdf_hip_indexed_destroy.argtypes = [C.c_void_p]
         L.gsdf_hip_indexed_destroy.restype = None
+        L.gsdf_hip_indexed_create.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_void_p)]
+        L.gsdf_hip_indexed_report.argtypes = [C.c_void_p, C.POINTER(IndexedReport)]
+        L.gsdf_hip_indexed_shells.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.gsdf_hip_indexed_read_shell_of.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.gsdf_hip_indexed_extract.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
         L.gsdf_hip_brick_owner.restype = C.c_uint32
         L.gsdf_hip_brick_owner.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         L.gsdf_hip_slab_range.restype = None
@@ -656,6 +684,64 @@ class IndexedHIP:
         n = np.empty((self.n_verts, 3), np.float32)
         _check(lib().gsdf_hip_indexed_read_normals(self._h, n.ctypes.data))
         return n
+
+    @classmethod
+    def from_arrays(cls, verts, idx, keys=None):
+        """A host mesh on the device (gsdf_hip_indexed_create): verts (V, 3) float32, idx (F, 3) vertex numbers, keys (V,) uint64 or
+        None (they then read back as 0). An index >= V raises HipError (GSDF_ERR_BAD_ARGUMENT) with the face and the index."""
+        v = np.ascontiguousarray(verts, np.float32).reshape(-1, 3)
+        i = np.asarray(idx)
+        if i.size and (i.min() < 0 or i.max() > 0xffffffff):
+            raise ValueError("vertex numbers must fit 32 unsigned bits")
+        i = np.ascontiguousarray(i, np.uint32).reshape(-1, 3)
+        k = None if keys is None else np.ascontiguousarray(keys, np.uint64).reshape(-1)
+        if k is not None and len(k) != len(v):
+            raise ValueError("one key per vertex")
+        h = C.c_void_p()
+        _check(lib().gsdf_hip_indexed_create(v.ctypes.data, len(v), i.ctypes.data, len(i), None if k is None else k.ctypes.data, C.byref(h)))
+        return cls(h)
+
+    def report(self):
+        """gsdf_hip_indexed_report: an IndexedReport (computed on the device once per handle)."""
+        rep = IndexedReport()
+        _check(lib().gsdf_hip_indexed_report(self._h, C.byref(rep)))
+        return rep
+
+    def shells(self):
+        """gsdf_hip_indexed_shells: a structured array (SHELL_DTYPE), one record per shell in increasing order of its label."""
+        n = C.c_uint64()
+        _check(lib().gsdf_hip_indexed_shells(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, SHELL_DTYPE)
+        if n.value:
+            _check(lib().gsdf_hip_indexed_shells(self._h, out.ctypes.data, n.value, C.byref(n)))
+        return out
+
+    def shell_of(self):
+        """(shell number of every vertex (V,), of every face (F,)) uint32; SHELL_NONE for an unused vertex / a degenerate face."""
+        sv, sf = np.empty(self.n_verts, np.uint32), np.empty(self.n_tris, np.uint32)
+        _check(lib().gsdf_hip_indexed_read_shell_of(self._h, sv.ctypes.data, sf.ctypes.data))
+        return sv, sf
+
+    def extract(self, keep=None, drop_degenerate=True):
+        """gsdf_hip_indexed_extract: a new IndexedHIP with the faces of the kept shells (keep: one truth value per shell, None = all)
+        in their order, vertices renumbered by first appearance; degenerate faces stay only with keep=None, drop_degenerate=False."""
+        k = None
+        if keep is not None:
+            k = np.ascontiguousarray(np.asarray(keep) != 0, np.uint8).reshape(-1)
+            if len(k) != int(self.report().n_shells):
+                raise ValueError("keep: one entry per shell")
+        h = C.c_void_p()
+        _check(lib().gsdf_hip_indexed_extract(self._h, None if k is None else k.ctypes.data, 1 if drop_degenerate else 0, C.byref(h)))
+        return IndexedHIP(h)
+
+    def select_shells(self, min_tris=0, drop_cavities=False):
+        """A keep mask for extract() from the shell table: shells with at least min_tris faces and, with drop_cavities, a volume
+        that is not negative (an enclosed cavity is a shell wound inside out)."""
+        sh = self.shells()
+        keep = sh["n_tris"] >= min_tris
+        if drop_cavities:
+            keep &= ~(sh["volume"] < 0)
+        return keep
 
     def ply_size(self):
         ln = C.c_size_t()

@@ -506,6 +506,103 @@ int gsdf_hip_indexed_ply(gsdf_indexed* ix, uint8_t* dst, size_t cap, size_t* len
 int gsdf_hip_indexed_host_ply(gsdf_indexed* ix, const uint8_t** ply, size_t* len);
 void gsdf_hip_indexed_destroy(gsdf_indexed* ix);
 
+/* ---- indexed meshes: report and extract (no reference counterpart) --------------------------------------------------------------
+ *
+ * What one asks of a mesh before it goes to a slicer: is it watertight and consistently oriented, how many shells has it, what are
+ * their volume, area and centre of mass, and the mesh without some of them. All of it is computed on the device from the handle's
+ * vertices and faces; the counts are functions of the faces alone, the measures of faces and positions, NONE of the order in which
+ * threads arrive or of the order of the faces (Determinism below). Kernels: gsdf_amd/csrc/kernels_topo.h; a numpy restatement:
+ * tests/toporef.py.
+ *
+ * Faces. A face with two equal indices is DEGENERATE: counted, and otherwise absent from everything below. A non-degenerate face
+ *   with a NaN or infinite coordinate is NONFINITE: it takes part in the topology (pairs, shells, counts) and not in the measures
+ *   (area, volume, centroid, bbox). A vertex is USED if a non-degenerate face names it.
+ * Pairs. Over the non-degenerate faces (a, b, c), the directed edges (a, b), (b, c), (c, a); per UNORDERED pair {p, q}, p < q,
+ *   f = its uses as (p, q) and r = its uses as (q, p). edges = distinct pairs; a pair is a BOUNDARY edge if f + r == 1, NON-MANIFOLD
+ *   if f + r > 2, MISORIENTED if f + r == 2 and f != 1. euler = used_verts - edges + (n_tris - degenerate).
+ *   closed_oriented = degenerate == 0 and no boundary, non-manifold or misoriented edge: every directed edge used once each way.
+ * Shells. The connected components of the graph whose nodes are the used vertices and whose edges are the pairs. A shell's LABEL is
+ *   its smallest vertex number; shells are numbered 0 .. n_shells - 1 in increasing order of their labels. A face belongs to the
+ *   shell of its vertices, a pair to the shell of its vertices. Per shell: the same counts, euler = n_verts - edges + n_tris
+ *   (n_tris: its non-degenerate faces), and the same measures.
+ * Measures, per FINITE non-degenerate face with corner positions a, b, c, each coordinate taken as (double)float32 (exact); every
+ *   operation below is one IEEE float64 operation, in this order, none contracted (the library is built with -ffp-contract=off and
+ *   these kernels are never part of a per-tree fast-math build):
+ *     u = b - a, w = c - a;  n = (u.y w.z - u.z w.y, u.z w.x - u.x w.z, u.x w.y - u.y w.x)
+ *     area term   = 0.5 * sqrt((n.x n.x + n.y n.y) + n.z n.z)                       (correctly rounded square root)
+ *     m = (b.y c.z - b.z c.y, b.z c.x - b.x c.z, b.x c.y - b.y c.x);  det = (a.x m.x + a.y m.y) + a.z m.z
+ *     volume term = det / 6;   moment term k = (det * ((a_k + b_k) + c_k)) / 24     (k = x, y, z)
+ *   bbox = min / max of the corner coordinates, compared as order-preserving float32 bits (-0 below +0); with no finite face
+ *   min = +inf, max = -inf.
+ * Determinism. Let e (`exponent`) be the smallest integer >= -125 with |x| < 2^e for every FINITE coordinate x of the handle's V
+ *   vertices (from the largest |bits|: e = max(biased exponent, 1) - 126; -125 for a mesh of zeros). Then area term < 2^(2e+3),
+ *   |volume term| < 2^(3e), |moment term| < 2^(4e). Each term is multiplied by the power of two 2^(59-2e), 2^(62-3e), 2^(62-4e)
+ *   (exact), rounded to the nearest integer, ties to even: |q| <= 2^62. The q are summed as INTEGERS (on the device: q's low 32 bits
+ *   and its arithmetic-shifted rest in separate 64-bit words, which the 2^31 faces a handle can hold cannot overflow; sum = rest
+ *   sum * 2^32 + low sum), so any reduction tree and any order of atomics give the same sum. The result is that integer, converted to
+ *   float64 with ONE rounding (to nearest even), times the inverse power of two (exact: never subnormal). A mesh's sums are the sums
+ *   of its shells' integers. centroid_k = moment_k / volume, one float64 division; the quiet NaN 0x7ff8000000000000 where volume == 0.
+ *   Error of the quantisation: at most n_tris / 2 units of 2^(3e-62) for the volume, i.e. n_tris * 2^-66 of the volume of the cube
+ *   [-2^e, 2^e]^3 that holds the mesh (< 2^-35 of it at 2^31 faces); likewise n_tris / 2 units of 2^(2e-59) for the area, i.e. n_tris * 2^-62 of that cube's face 2^(2e+2): both far
+ *   below what float32 positions carry (2^-24 relative per coordinate). Derived, not measured.
+ *
+ * gsdf_hip_indexed_create uploads a host mesh (a PLY read back, or any mesh): verts 3 V floats, idx 3 F vertex numbers, keys V or
+ *   NULL (then they read back as 0). The device of the calling thread (gsdf_hip_init). An index >= n_verts: GSDF_ERR_BAD_ARGUMENT,
+ *   the text names the face and the index; n_tris == 0 or n_verts == 0: GSDF_ERR_EMPTY_BUFFERS; 3 F >= 2^32 or V >= 2^32:
+ *   GSDF_ERR_CAPACITY. Every accessor above works on the result (its gsdf_indexed_stats times are 0).
+ * gsdf_hip_indexed_report computes the report once per handle (later calls return the same bytes). Bytes 0 .. 159 of the struct
+ *   (n_verts .. exponent) are a function of the mesh alone; the rest says what this run cost. GSDF_HIP_TOPO_CELLS_MIN (environment)
+ *   lowers the edge table's first size so that tests can drive the grow-and-repeat path, as GSDF_HIP_WELD_CELLS_MIN does.
+ * gsdf_hip_indexed_shells: one record per shell, in shell order. dst NULL: *n = n_shells; cap < n_shells: GSDF_ERR_SHORT_BUFFER with
+ *   *n set.
+ * gsdf_hip_indexed_read_shell_of: each optional; the shell NUMBER of every vertex (V) and face (F), 0xffffffff for a vertex that is
+ *   not used / a degenerate face.
+ * gsdf_hip_indexed_extract: a new, independent handle with the faces of the kept shells (keep_shell: n_shells bytes, non-zero =
+ *   keep; NULL = all) in their original order; degenerate faces are kept only if drop_degenerate == 0 and keep_shell == NULL.
+ *   Vertices are renumbered by the smallest slot 3 g + c (g: position among the kept faces) that names them, in increasing order --
+ *   the weld's own rule; positions, keys and, if present, normals are carried bit for bit. Nothing kept: GSDF_ERR_EMPTY_BUFFERS. */
+typedef struct gsdf_indexed_report {
+  uint64_t n_verts, n_tris;
+  uint64_t degenerate, nonfinite, used_verts;
+  uint64_t edges, boundary_edges, nonmanifold_edges, misoriented_edges;
+  uint64_t n_shells;
+  int64_t euler;
+  double area, volume, centroid[3];
+  float bbox[6];            /* min x y z, max x y z */
+  int32_t closed_oriented;  /* 0 / 1 */
+  int32_t exponent;         /* e of the contract */
+  double ms_edges;          /* device time, HIP events: exponent scan + edge table (all attempts) */
+  double ms_shells;         /* union-find, roots, numbering */
+  double ms_measure;        /* face measures + pair classes */
+  uint64_t probes;          /* table cells inspected by the inserting pass that succeeded */
+  uint64_t table_cells;     /* its capacity (a power of two, >= 2 edges) */
+  int32_t attempts;         /* inserting passes run */
+  int32_t reserved;
+} gsdf_indexed_report;
+GSDF_ABI_ASSERT(sizeof(gsdf_indexed_report) == 208, "gsdf_indexed_report is 208 bytes");
+GSDF_ABI_ASSERT(offsetof(gsdf_indexed_report, degenerate) == 16 && offsetof(gsdf_indexed_report, edges) == 40 && offsetof(gsdf_indexed_report, n_shells) == 72, "gsdf_indexed_report counts");
+GSDF_ABI_ASSERT(offsetof(gsdf_indexed_report, euler) == 80 && offsetof(gsdf_indexed_report, area) == 88 && offsetof(gsdf_indexed_report, centroid) == 104, "gsdf_indexed_report measures");
+GSDF_ABI_ASSERT(offsetof(gsdf_indexed_report, bbox) == 128 && offsetof(gsdf_indexed_report, closed_oriented) == 152 && offsetof(gsdf_indexed_report, exponent) == 156, "gsdf_indexed_report box");
+GSDF_ABI_ASSERT(offsetof(gsdf_indexed_report, ms_edges) == 160 && offsetof(gsdf_indexed_report, probes) == 184 && offsetof(gsdf_indexed_report, attempts) == 200, "gsdf_indexed_report cost");
+typedef struct gsdf_shell {
+  uint64_t n_verts, n_tris; /* n_tris: non-degenerate faces, nonfinite ones included */
+  uint64_t nonfinite;
+  uint64_t edges, boundary_edges, nonmanifold_edges, misoriented_edges;
+  int64_t euler;
+  double area, volume, centroid[3];
+  float bbox[6];
+  uint32_t label;           /* the shell's smallest vertex number */
+  uint32_t reserved;
+} gsdf_shell;
+GSDF_ABI_ASSERT(sizeof(gsdf_shell) == 136, "gsdf_shell is 136 bytes");
+GSDF_ABI_ASSERT(offsetof(gsdf_shell, nonfinite) == 16 && offsetof(gsdf_shell, edges) == 24 && offsetof(gsdf_shell, euler) == 56, "gsdf_shell counts");
+GSDF_ABI_ASSERT(offsetof(gsdf_shell, area) == 64 && offsetof(gsdf_shell, centroid) == 80 && offsetof(gsdf_shell, bbox) == 104 && offsetof(gsdf_shell, label) == 128, "gsdf_shell measures");
+int gsdf_hip_indexed_create(const float* verts, uint64_t n_verts, const uint32_t* idx, uint64_t n_tris, const uint64_t* keys, gsdf_indexed** out);
+int gsdf_hip_indexed_report(gsdf_indexed* ix, gsdf_indexed_report* rep);
+int gsdf_hip_indexed_shells(gsdf_indexed* ix, gsdf_shell* dst, uint64_t cap, uint64_t* n);
+int gsdf_hip_indexed_read_shell_of(gsdf_indexed* ix, uint32_t* shell_of_vertex, uint32_t* shell_of_face);
+int gsdf_hip_indexed_extract(gsdf_indexed* ix, const uint8_t* keep_shell, int drop_degenerate, gsdf_indexed** out);
+
 /* ---- multi-GPU (one process per GPU). The meshers shard with NO data-path collective (shard_rank / shard_count above); the
  * one exchange is the final variable-length gather of the ranks' results, over xGMI, inside this library: a Go caller needs no
  * Python for it. Replaces nothing in the reference (single device; its analogue of the split is the goroutine split of

@@ -80,6 +80,104 @@ func (ix *IndexedHIP) WriteBinaryPLY(w io.Writer) (int, error) {
 	return w.Write(unsafe.Slice((*byte)(unsafe.Pointer(p)), int(n)))
 }
 
+// IndexedReport is gsdf_indexed_report: counts, edge classes, shells and measures of the mesh (gsdf_hip.h states every term).
+type IndexedReport struct {
+	V, F, Degenerate, NonFinite, UsedV            uint64
+	Edges, Boundary, NonManifold, Misoriented     uint64
+	Shells                                        uint64
+	Euler                                         int64
+	Area, Volume                                  float64
+	Centroid                                      ms3.Vec
+	Min, Max                                      ms3.Vec
+	ClosedOriented                                bool
+	EdgesMillis, ShellsMillis, MeasureMillis      float64
+}
+
+// Shell is gsdf_shell: one connected component of the mesh. Label is its smallest vertex number; a negative Volume is a cavity.
+type Shell struct {
+	Label                                     uint32
+	V, F, NonFinite                           uint64
+	Edges, Boundary, NonManifold, Misoriented uint64
+	Euler                                     int64
+	Area, Volume                              float64
+	Centroid, Min, Max                        ms3.Vec
+}
+
+// Report computes (once per handle) whether the mesh is closed and oriented, its shells and its measures, on the device.
+func (ix *IndexedHIP) Report() (IndexedReport, error) {
+	var rep C.gsdf_indexed_report
+	if rc := C.gsdf_hip_indexed_report(ix.h, &rep); rc != 0 {
+		return IndexedReport{}, hipErr(rc)
+	}
+	return IndexedReport{
+		V: uint64(rep.n_verts), F: uint64(rep.n_tris), Degenerate: uint64(rep.degenerate), NonFinite: uint64(rep.nonfinite), UsedV: uint64(rep.used_verts),
+		Edges: uint64(rep.edges), Boundary: uint64(rep.boundary_edges), NonManifold: uint64(rep.nonmanifold_edges), Misoriented: uint64(rep.misoriented_edges),
+		Shells: uint64(rep.n_shells), Euler: int64(rep.euler), Area: float64(rep.area), Volume: float64(rep.volume),
+		Centroid:       ms3.Vec{X: float32(rep.centroid[0]), Y: float32(rep.centroid[1]), Z: float32(rep.centroid[2])},
+		Min:            ms3.Vec{X: float32(rep.bbox[0]), Y: float32(rep.bbox[1]), Z: float32(rep.bbox[2])},
+		Max:            ms3.Vec{X: float32(rep.bbox[3]), Y: float32(rep.bbox[4]), Z: float32(rep.bbox[5])},
+		ClosedOriented: rep.closed_oriented != 0,
+		EdgesMillis:    float64(rep.ms_edges), ShellsMillis: float64(rep.ms_shells), MeasureMillis: float64(rep.ms_measure),
+	}, nil
+}
+
+// Shells returns the shell table, in increasing order of the shells' labels.
+func (ix *IndexedHIP) Shells() ([]Shell, error) {
+	var n C.uint64_t
+	if rc := C.gsdf_hip_indexed_shells(ix.h, nil, 0, &n); rc != 0 {
+		return nil, hipErr(rc)
+	}
+	if n == 0 {
+		return nil, nil
+	}
+	raw := make([]C.gsdf_shell, int(n))
+	if rc := C.gsdf_hip_indexed_shells(ix.h, &raw[0], n, &n); rc != 0 {
+		return nil, hipErr(rc)
+	}
+	out := make([]Shell, len(raw))
+	for i := range raw {
+		var sh C.gsdf_shell = raw[i]
+		out[i] = Shell{
+			Label: uint32(sh.label), V: uint64(sh.n_verts), F: uint64(sh.n_tris), NonFinite: uint64(sh.nonfinite),
+			Edges: uint64(sh.edges), Boundary: uint64(sh.boundary_edges), NonManifold: uint64(sh.nonmanifold_edges), Misoriented: uint64(sh.misoriented_edges),
+			Euler: int64(sh.euler), Area: float64(sh.area), Volume: float64(sh.volume),
+			Centroid: ms3.Vec{X: float32(sh.centroid[0]), Y: float32(sh.centroid[1]), Z: float32(sh.centroid[2])},
+			Min:      ms3.Vec{X: float32(sh.bbox[0]), Y: float32(sh.bbox[1]), Z: float32(sh.bbox[2])},
+			Max:      ms3.Vec{X: float32(sh.bbox[3]), Y: float32(sh.bbox[4]), Z: float32(sh.bbox[5])},
+		}
+	}
+	return out, nil
+}
+
+// Extract returns a new, independent mesh with the faces of the kept shells (keep: one entry per shell of Shells(); nil keeps
+// all), vertices renumbered by first appearance. Degenerate faces stay only with keep == nil and dropDegenerate == false.
+func (ix *IndexedHIP) Extract(keep []bool, dropDegenerate bool) (*IndexedHIP, error) {
+	var kp *C.uint8_t
+	if keep != nil {
+		bytes := make([]byte, len(keep)+1)
+		for i, k := range keep {
+			if k {
+				bytes[i] = 1
+			}
+		}
+		kp = (*C.uint8_t)(unsafe.Pointer(&bytes[0]))
+	}
+	drop := C.int(0)
+	if dropDegenerate {
+		drop = 1
+	}
+	var h *C.gsdf_indexed
+	if rc := C.gsdf_hip_indexed_extract(ix.h, kp, drop, &h); rc != 0 {
+		return nil, hipErr(rc)
+	}
+	nx := &IndexedHIP{h: h}
+	var nv, nf C.uint64_t
+	var ms C.double
+	C.gsdf_hip_indexed_counts(h, &nv, &nf, &ms)
+	nx.V, nx.F, nx.WeldMillis = uint64(nv), uint64(nf), float64(ms)
+	return nx, nil
+}
+
 // Close frees the device and pinned host buffers of the mesh.
 func (ix *IndexedHIP) Close() {
 	if ix.h != nil {
