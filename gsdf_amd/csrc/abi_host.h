@@ -3,6 +3,7 @@
 //   abi_host.cpp  error text, triangle / pinned-buffer pools, result copies
 //   abi_eval.hip  programs, specialisation, gleval.SDF3 / SDF2 Evaluate, normals, image renderer, block cache
 //   abi_mesh.hip  octree / flat / dual-contouring meshers and the mesh accessors
+//   abi_indexed.hip  indexed meshes: the gsdf_indexed handle, weld, PLY, report and extract
 //   abi_comm.cpp  multi-GPU: communicator (RCCL or the in-process loopback transport), gather plan, gatherv
 #pragma once
 #include <hip/hip_runtime.h>

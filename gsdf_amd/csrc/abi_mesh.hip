@@ -1,7 +1,7 @@
 // abi_mesh.hip -- C ABI (include/gsdf_hip.h), mesher side: glrender.Octree + marchCubes, FlatRenderer and
 // DualContourRenderer on device, and the accessors of the resulting mesh (ReadTriangles drain, STL, pinned host views).
-// Kernels: kernels_octree.h, kernels_flat.h, kernels_dc.h, kernels_stl.h, kernels_weld.h (indexed meshes, binary PLY), kernels_topo.h
-// (their report: edge classes, shells, measures; extract).
+// Kernels: kernels_octree.h, kernels_flat.h, kernels_dc.h, kernels_stl.h, kernels_minecraft.h. Indexed meshes (weld, PLY, report,
+// extract) are abi_indexed.hip's; what it takes from here is mesh_march_dense.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -16,8 +16,6 @@
 #include "kernels_dc.h"
 #include "kernels_stl.h"
 #include "kernels_minecraft.h"
-#include "kernels_weld.h"
-#include "kernels_topo.h"
 #include "abi_program.h"
 #include "host_math.h"
 
@@ -1254,600 +1252,4 @@ extern "C" void gsdf_hip_mesh_destroy(gsdf_mesh* m) {
 void mesh_inflight_done(gsdf_mesh* m) {
   m->inflight.fetch_sub(1);
   if (m->refs.fetch_sub(1, std::memory_order_acq_rel) == 1) mesh_free(m);
-}
-
-// ---- indexed meshes (kernels_weld.h; the contract is in include/gsdf_hip.h) ----------------------------------------------------
-namespace {
-// a device buffer from the triangle pool (sized in 36-byte units), handed back when it goes out of scope
-struct PoolBuf {
-  int device = 0;
-  float* p = nullptr;
-  uint64_t cap = 0;
-  PoolBuf() = default;
-  PoolBuf(const PoolBuf&) = delete;
-  PoolBuf& operator=(const PoolBuf&) = delete;
-  ~PoolBuf() { give(); }
-  void give() { pool_give(device, p, cap); p = nullptr; cap = 0; }
-  bool take(int dev, size_t bytes) {
-    give();
-    device = dev;
-    const uint64_t units = (bytes + 35) / 36 + 1;
-    p = pool_take(dev, units, &cap);
-    if (!p) {
-      if (hipMalloc((void**)&p, units * 36) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return false; }
-      cap = units;
-    }
-    return true;
-  }
-  template <typename T> T* as() const { return (T*)p; }
-};
-struct EventPair {
-  hipEvent_t a = nullptr, b = nullptr;
-  ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-  bool make() { return hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess; }
-  double ms() const { float t = 0; return hipEventElapsedTime(&t, a, b) == hipSuccess ? (double)t : 0.0; }
-};
-}  // namespace
-
-struct gsdf_indexed {
-  int device = 0;
-  int num_cu = 256;
-  hipStream_t stream = nullptr;
-  uint64_t n_verts = 0, n_tris = 0;
-  PoolBuf verts, idx, vkeys, normals;
-  bool has_normals = false;
-  double ms_device = 0;
-  gsdf_indexed_stats st{};
-  void* h_ply = nullptr;
-  size_t h_ply_cap = 0, ply_len = 0;
-  bool ply_valid = false;
-  // gsdf_hip_indexed_report's result, computed once: the report, the shell table, the shell numbers of vertices and faces (device)
-  bool topo_valid = false;
-  gsdf_indexed_report rep{};
-  std::vector<gsdf_shell> shells;
-  PoolBuf shell_of_vertex, shell_of_face;
-};
-
-extern "C" void gsdf_hip_indexed_destroy(gsdf_indexed* ix) {
-  if (!ix) return;
-  (void)hipSetDevice(ix->device);
-  if (ix->stream) { (void)hipStreamSynchronize(ix->stream); (void)hipStreamDestroy(ix->stream); }
-  hpool_give(ix->h_ply, ix->h_ply_cap);
-  delete ix;
-}
-
-extern "C" int gsdf_hip_mesh_weld(const gsdf_mesh* m, gsdf_indexed** out) {
-  if (!m || !out) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
-  *out = nullptr;
-  const bool marched = m->payload != GSDF_PAYLOAD_RECORDS;
-  const uint8_t* d_recs = marched ? m->d_wrecs : m->d_recs;
-  const uint64_t n_recs = marched ? m->n_wrecs : m->n_recs;
-  if (!m->weldable || (!d_recs && m->st.n_tris))
-    return fail(GSDF_ERR_BAD_ARGUMENT, "weld needs a mesh of the octree mesher made with payload = GSDF_PAYLOAD_RECORDS and shard_count == 1 (marched in place or "
-                                       "not): triangle-payload, flat, dual-contouring, minecraft, gathered and sharded meshes carry no lattice coordinates");
-  if (m->inflight.load() > 0) return fail(GSDF_ERR_BAD_ARGUMENT, "the mesh is being gathered: wait for the gather first");
-  const uint64_t F = m->st.n_tris;
-  if (F == 0) return fail(GSDF_ERR_EMPTY_BUFFERS, "empty triangle slice");
-  if (3 * F >= ((uint64_t)1 << 32)) return fail(GSDF_ERR_CAPACITY, "weld: 3 x triangles must stay below 2^32 (32-bit vertex numbers)");
-  HIP_TRY(hipSetDevice(m->device));
-  gsdf_indexed* ix = new (std::nothrow) gsdf_indexed();
-  if (!ix) return fail(GSDF_ERR_BAD_ARGUMENT, "out of memory");
-  ix->device = m->device;
-  ix->num_cu = m->num_cu;
-  auto bail = [&](int code) { gsdf_hip_indexed_destroy(ix); return code; };
-#define HIP_TRYW(expr)                                                                                          \
-  do {                                                                                                          \
-    hipError_t _e = (expr);                                                                                     \
-    if (_e != hipSuccess) return bail(fail(GSDF_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e))); \
-  } while (0)
-  HIP_TRYW(hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking));
-  hipStream_t s = ix->stream;
-  const int dev = m->device;
-  const uint64_t S = 3 * F;  // soup slots
-  const uint64_t n_chunks = (n_recs + DENSE_CHUNK - 1) / DENSE_CHUNK;
-  const uint64_t n_blocks = (S + BLOCK - 1) / BLOCK;
-  const char* nomem = "weld: no device memory for the workspace";
-  // the soup: the mesh's own triangles if it was marched, else a marching pass over its records into scratch
-  PoolBuf soup_tmp;
-  const float* soup = m->d_tris;
-  if (!marched) {
-    if (!soup_tmp.take(dev, (size_t)F * 36 + dense_parts_bytes() + 36)) return bail(fail(GSDF_ERR_HIP, nomem));
-    const gsdf_dense_part part{0, n_recs, 0};
-    if (int rc = mesh_march_dense(d_recs, &part, 1, dense_parts_at(soup_tmp.p, F), m->st.origin[0], m->st.origin[1], m->st.origin[2], m->st.res, soup_tmp.p,
-                                  m->num_cu, s))
-      return bail(rc);
-    soup = soup_tmp.p;
-  }
-  PoolBuf keys, vnum, chunk_base, blk_cnt, blk_base, ctr, table;
-  if (!keys.take(dev, S * 8) || !ix->idx.take(dev, S * 4) || !vnum.take(dev, S * 4) || !chunk_base.take(dev, n_chunks * 4 + 4) ||
-      !blk_cnt.take(dev, n_blocks * 4) || !blk_base.take(dev, n_blocks * 4) || !ctr.take(dev, sizeof(WeldCounters)))
-    return bail(fail(GSDF_ERR_HIP, nomem));
-  EventPair ev_k, ev_i, ev_n;
-  if (!ev_k.make() || !ev_i.make() || !ev_n.make()) return bail(fail(GSDF_ERR_HIP, "hipEventCreate failed"));
-  // 1. keys
-  HIP_TRYW(hipEventRecord(ev_k.a, s));
-  hipLaunchKernelGGL(weld_chunk_scan_kernel, dim3(1), dim3(1024), 0, s, (const uint32_t*)(d_recs + n_recs * 40ull), (unsigned long long)n_chunks,
-                     chunk_base.as<uint32_t>());
-  HIP_TRYW(hipGetLastError());
-  hipLaunchKernelGGL(weld_keys_kernel, dim3(grid_for(n_chunks * BLOCK, m->num_cu, 16)), dim3(BLOCK), 0, s, d_recs, (unsigned long long)n_recs,
-                     (const uint32_t*)chunk_base.as<uint32_t>(), (unsigned long long)S, keys.as<unsigned long long>());
-  HIP_TRYW(hipGetLastError());
-  HIP_TRYW(hipEventRecord(ev_k.b, s));
-  // 2. the table: cells from F (V is about F / 2: load factor <= 0.5); a pass that ends fuller than that, or that gave up on a key,
-  // is repeated with twice the cells -- no key is ever dropped. GSDF_HIP_WELD_CELLS_MIN lowers the first size so that tests can drive
-  // the grow-and-rerun path.
-  uint64_t cells = 1024;
-  {
-    const char* e = getenv("GSDF_HIP_WELD_CELLS_MIN");
-    const uint64_t want = e ? (uint64_t)strtoull(e, nullptr, 10) : F;
-    while (cells < want) cells <<= 1;
-  }
-  WeldCounters hc{};
-  int attempts = 0;
-  HIP_TRYW(hipEventRecord(ev_i.a, s));
-  for (;;) {
-    if (cells > ((uint64_t)1 << 32)) return bail(fail(GSDF_ERR_CAPACITY, "weld: hash table capacity exceeded"));
-    if (!table.take(dev, cells * 12)) return bail(fail(GSDF_ERR_HIP, nomem));
-    attempts++;
-    HIP_TRYW(hipMemsetAsync(table.p, 0xff, cells * 12, s));
-    HIP_TRYW(hipMemsetAsync(ctr.p, 0, sizeof(WeldCounters), s));
-    hipLaunchKernelGGL(weld_insert_kernel, dim3(grid_for(S, m->num_cu, 16)), dim3(BLOCK), 0, s, (const unsigned long long*)keys.as<unsigned long long>(),
-                       (unsigned long long)S, table.as<unsigned long long>(), (unsigned*)(table.as<unsigned long long>() + cells), (unsigned)(cells - 1),
-                       ctr.as<WeldCounters>());
-    HIP_TRYW(hipGetLastError());
-    HIP_TRYW(hipMemcpyAsync(&hc, ctr.p, sizeof hc, hipMemcpyDeviceToHost, s));
-    HIP_TRYW(hipStreamSynchronize(s));
-    if (!hc.overflow && hc.distinct * 2 <= cells) break;
-    cells <<= 1;
-  }
-  HIP_TRYW(hipEventRecord(ev_i.b, s));
-  // 3. owners, numbers, positions, indices
-  HIP_TRYW(hipEventRecord(ev_n.a, s));
-  hipLaunchKernelGGL(weld_owner_kernel, dim3((unsigned)n_blocks), dim3(BLOCK), 0, s, (const unsigned long long*)keys.as<unsigned long long>(), (unsigned long long)S,
-                     (const unsigned long long*)table.as<unsigned long long>(), (const unsigned*)(table.as<unsigned long long>() + cells), (unsigned)(cells - 1),
-                     ix->idx.as<unsigned>(), blk_cnt.as<unsigned>());
-  HIP_TRYW(hipGetLastError());
-  hipLaunchKernelGGL(weld_block_scan_kernel, dim3(1), dim3(1024), 0, s, (const unsigned*)blk_cnt.as<unsigned>(), (unsigned)n_blocks, blk_base.as<unsigned>(),
-                     ctr.as<WeldCounters>());
-  HIP_TRYW(hipGetLastError());
-  WeldCounters hv{};
-  HIP_TRYW(hipMemcpyAsync(&hv, ctr.p, sizeof hv, hipMemcpyDeviceToHost, s));
-  HIP_TRYW(hipStreamSynchronize(s));
-  const uint64_t V = hv.n_verts;
-  if (V == 0 || V > S || V != hc.distinct) return bail(fail(GSDF_ERR_HIP, "weld: internal error (owners and distinct keys disagree)"));
-  if (!ix->verts.take(dev, V * 12) || !ix->vkeys.take(dev, V * 8)) return bail(fail(GSDF_ERR_HIP, nomem));
-  hipLaunchKernelGGL(weld_number_kernel, dim3((unsigned)n_blocks), dim3(BLOCK), 0, s, (const unsigned*)ix->idx.as<unsigned>(), (unsigned long long)S,
-                     (const unsigned*)blk_base.as<unsigned>(), soup, (const unsigned long long*)keys.as<unsigned long long>(), vnum.as<unsigned>(), ix->verts.p,
-                     ix->vkeys.as<unsigned long long>());
-  HIP_TRYW(hipGetLastError());
-  hipLaunchKernelGGL(weld_index_kernel, dim3((unsigned)n_blocks), dim3(BLOCK), 0, s, ix->idx.as<unsigned>(), (unsigned long long)S, (const unsigned*)vnum.as<unsigned>());
-  HIP_TRYW(hipGetLastError());
-  HIP_TRYW(hipEventRecord(ev_n.b, s));
-  HIP_TRYW(hipStreamSynchronize(s));
-#undef HIP_TRYW
-  ix->n_verts = V;
-  ix->n_tris = F;
-  ix->st.ms_keys = ev_k.ms();
-  ix->st.ms_insert = ev_i.ms();
-  ix->st.ms_number = ev_n.ms();
-  ix->st.probes = hc.probes;
-  ix->st.table_cells = cells;
-  ix->st.attempts = attempts;
-  ix->ms_device = ix->st.ms_keys + ix->st.ms_insert + ix->st.ms_number;
-  *out = ix;
-  return GSDF_OK;
-}
-
-extern "C" int gsdf_hip_indexed_counts(const gsdf_indexed* ix, uint64_t* n_verts, uint64_t* n_tris, double* ms_device) {
-  if (!ix) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
-  if (n_verts) *n_verts = ix->n_verts;
-  if (n_tris) *n_tris = ix->n_tris;
-  if (ms_device) *ms_device = ix->ms_device;
-  return GSDF_OK;
-}
-
-extern "C" int gsdf_hip_indexed_stats_get(const gsdf_indexed* ix, gsdf_indexed_stats* st) {
-  if (!ix || !st) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
-  *st = ix->st;
-  st->has_normals = ix->has_normals ? 1 : 0;
-  return GSDF_OK;
-}
-
-extern "C" int gsdf_hip_indexed_read(const gsdf_indexed* ix, float* verts, uint32_t* idx, uint64_t* keys) {
-  if (!ix) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
-  HIP_TRY(hipSetDevice(ix->device));
-  if (verts) HIP_TRY(hipMemcpy(verts, ix->verts.p, ix->n_verts * 12, hipMemcpyDeviceToHost));
-  if (idx) HIP_TRY(hipMemcpy(idx, ix->idx.p, ix->n_tris * 12, hipMemcpyDeviceToHost));
-  if (keys) HIP_TRY(hipMemcpy(keys, ix->vkeys.p, ix->n_verts * 8, hipMemcpyDeviceToHost));
-  return GSDF_OK;
-}
-
-extern "C" int gsdf_hip_indexed_normals(gsdf_indexed* ix, gsdf_program* p, float step) {
-  if (!ix || !p) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
-  if (p->device != ix->device) return fail(GSDF_ERR_BAD_ARGUMENT, "the program and the indexed mesh live on different devices");
-  HIP_TRY(hipSetDevice(ix->device));
-  if (!ix->normals.p && !ix->normals.take(ix->device, ix->n_verts * 12)) return fail(GSDF_ERR_HIP, "no device memory for the normals");
-  ix->has_normals = false;
-  ix->ply_valid = false;
-  if (int rc = normals3_dev(p, ix->verts.p, ix->normals.p, (size_t)ix->n_verts, step)) return rc;
-  ix->has_normals = true;
-  return GSDF_OK;
-}
-
-extern "C" int gsdf_hip_indexed_read_normals(const gsdf_indexed* ix, float* normals) {
-  if (!ix || !normals) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
-  if (!ix->has_normals) return fail(GSDF_ERR_BAD_ARGUMENT, "no normals yet: gsdf_hip_indexed_normals first");
-  HIP_TRY(hipSetDevice(ix->device));
-  HIP_TRY(hipMemcpy(normals, ix->normals.p, ix->n_verts * 12, hipMemcpyDeviceToHost));
-  return GSDF_OK;
-}
-
-// The PLY header (gsdf_hip.h; gsdf_amd/ply.py writes the same bytes): its comment line is padded to a length that is a multiple of 4.
-static std::string ply_header(uint64_t V, uint64_t F, bool normals) {
-  std::string a = "ply\nformat binary_little_endian 1.0\ncomment gsdf";
-  std::string b = "\nelement vertex " + std::to_string(V) + "\nproperty float x\nproperty float y\nproperty float z\n";
-  if (normals) b += "property float nx\nproperty float ny\nproperty float nz\n";
-  b += "element face " + std::to_string(F) + "\nproperty list uchar int vertex_indices\nend_header\n";
-  a.append((4 - (a.size() + b.size()) % 4) % 4, ' ');
-  return a + b;
-}
-
-extern "C" int gsdf_hip_indexed_host_ply(gsdf_indexed* ix, const uint8_t** ply, size_t* len) {
-  if (!ix || !ply || !len) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
-  *ply = nullptr; *len = 0;
-  HIP_TRY(hipSetDevice(ix->device));
-  if (!ix->ply_valid) {
-    const std::string hdr = ply_header(ix->n_verts, ix->n_tris, ix->has_normals);
-    const size_t vbytes = (size_t)ix->n_verts * (ix->has_normals ? 24 : 12), fbytes = (size_t)ix->n_tris * 13;
-    const size_t bytes = hdr.size() + vbytes + fbytes;
-    if (int rc = host_buf(&ix->h_ply, &ix->h_ply_cap, bytes + 4)) return rc;
-    PoolBuf d_out;  // device scratch from the triangle pool (the last face dword may reach past the file's end)
-    if (!d_out.take(ix->device, bytes + 4)) return fail(GSDF_ERR_HIP, "hipMalloc of the PLY scratch failed");
-    EventPair ev;
-    if (!ev.make()) return fail(GSDF_ERR_HIP, "hipEventCreate failed");
-    std::memcpy(ix->h_ply, hdr.data(), hdr.size());  // pinned: a valid source for the async header upload
-    hipStream_t s = ix->stream;
-    uint8_t* o = (uint8_t*)d_out.p;
-    hipError_t e = hipEventRecord(ev.a, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(o, ix->h_ply, hdr.size(), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(ply_verts_kernel, dim3(grid_for(vbytes / 4, ix->num_cu, 8)), dim3(BLOCK), 0, s, (const float*)ix->verts.p,
-                         (const float*)(ix->has_normals ? ix->normals.p : nullptr), (unsigned long long)ix->n_verts, (uint32_t*)(o + hdr.size()));
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(ply_faces_kernel, dim3(grid_for((fbytes + 3) / 4, ix->num_cu, 8)), dim3(BLOCK), 0, s, (const unsigned*)ix->idx.as<unsigned>(),
-                         (unsigned long long)ix->n_tris, (uint32_t*)(o + hdr.size() + vbytes));
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(ix->h_ply, o, bytes, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipEventRecord(ev.b, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    else (void)hipStreamSynchronize(s);
-    if (e != hipSuccess) return fail(GSDF_ERR_HIP, std::string("PLY build/transfer: ") + hipGetErrorString(e));
-    ix->st.ms_ply = ev.ms();
-    ix->ply_len = bytes;
-    ix->ply_valid = true;
-  }
-  *ply = (const uint8_t*)ix->h_ply;
-  *len = ix->ply_len;
-  return GSDF_OK;
-}
-
-extern "C" int gsdf_hip_indexed_ply(gsdf_indexed* ix, uint8_t* dst, size_t cap, size_t* len) {
-  if (!ix || !len) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
-  *len = ply_header(ix->n_verts, ix->n_tris, ix->has_normals).size() + (size_t)ix->n_verts * (ix->has_normals ? 24 : 12) + (size_t)ix->n_tris * 13;
-  if (!dst || cap < *len) return fail(GSDF_ERR_SHORT_BUFFER, "short buffer");
-  const uint8_t* h = nullptr;
-  size_t n = 0;
-  if (int rc = gsdf_hip_indexed_host_ply(ix, &h, &n)) return rc;
-  big_memcpy(dst, h, n);
-  return GSDF_OK;
-}
-
-// ---- indexed meshes: report and extract (kernels_topo.h; the contract is in include/gsdf_hip.h) ---------------------------------
-namespace {
-// an empty handle on the calling thread's device, with its own stream
-int indexed_new(int device, int num_cu, gsdf_indexed** out) {
-  gsdf_indexed* ix = new (std::nothrow) gsdf_indexed();
-  if (!ix) return fail(GSDF_ERR_BAD_ARGUMENT, "out of memory");
-  ix->device = device;
-  ix->num_cu = num_cu;
-  if (hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking) != hipSuccess) {
-    (void)hipGetLastError();
-    ix->stream = nullptr;
-    gsdf_hip_indexed_destroy(ix);
-    return fail(GSDF_ERR_HIP, "hipStreamCreate failed");
-  }
-  *out = ix;
-  return GSDF_OK;
-}
-unsigned blocks_of(uint64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
-float topo_unordered(unsigned o) {
-  const uint32_t bits = (o & 0x80000000u) ? (o ^ 0x80000000u) : ~o;
-  float f;
-  std::memcpy(&f, &bits, 4);
-  return f;
-}
-// low-word sum and (signed) rest sum of the quantised terms -> the integer they stand for
-__int128 topo_int(const unsigned long long* s) { return (__int128)(long long)s[1] * ((__int128)1 << 32) + (__int128)s[0]; }
-// that integer as float64 (one rounding) times 2^-shift (exact)
-double topo_value(__int128 t, int shift) { return std::ldexp((double)t, -shift); }
-double topo_quotient(double m, double v) {
-  if (v == 0.0) {
-    const uint64_t q = 0x7ff8000000000000ull;
-    double d;
-    std::memcpy(&d, &q, 8);
-    return d;
-  }
-  return m / v;
-}
-}  // namespace
-
-extern "C" int gsdf_hip_indexed_create(const float* verts, uint64_t n_verts, const uint32_t* idx, uint64_t n_tris, const uint64_t* keys, gsdf_indexed** out) {
-  if (!out) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
-  *out = nullptr;
-  if (n_verts == 0 || n_tris == 0) return fail(GSDF_ERR_EMPTY_BUFFERS, "empty buffers");
-  if (!verts || !idx) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
-  if (3 * n_tris >= ((uint64_t)1 << 32) || n_verts >= ((uint64_t)1 << 32))
-    return fail(GSDF_ERR_CAPACITY, "indexed mesh: vertices and 3 x triangles must stay below 2^32 (32-bit vertex numbers)");
-  for (uint64_t s = 0; s < 3 * n_tris; s++)
-    if (idx[s] >= n_verts)
-      return fail(GSDF_ERR_BAD_ARGUMENT, "indexed mesh: face " + std::to_string(s / 3) + " names vertex index " + std::to_string(idx[s]) + ", the mesh has " +
-                                             std::to_string(n_verts) + " vertices");
-  int device = 0, num_cu = 256;
-  HIP_TRY(hipGetDevice(&device));
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device) == hipSuccess) num_cu = prop.multiProcessorCount;
-  gsdf_indexed* ix = nullptr;
-  if (int rc = indexed_new(device, num_cu, &ix)) return rc;
-  auto bail = [&](int code) { gsdf_hip_indexed_destroy(ix); return code; };
-  if (!ix->verts.take(device, n_verts * 12) || !ix->idx.take(device, n_tris * 12) || !ix->vkeys.take(device, n_verts * 8))
-    return bail(fail(GSDF_ERR_HIP, "indexed mesh: no device memory"));
-  hipError_t e = hipMemcpy(ix->verts.p, verts, n_verts * 12, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(ix->idx.p, idx, n_tris * 12, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = keys ? hipMemcpy(ix->vkeys.p, keys, n_verts * 8, hipMemcpyHostToDevice) : hipMemset(ix->vkeys.p, 0, n_verts * 8);
-  if (e != hipSuccess) return bail(fail(GSDF_ERR_HIP, std::string("indexed mesh upload: ") + hipGetErrorString(e)));
-  ix->n_verts = n_verts;
-  ix->n_tris = n_tris;
-  *out = ix;
-  return GSDF_OK;
-}
-
-// The report, the shell table and the shell numbers, once per handle.
-static int topo_ensure(gsdf_indexed* ix) {
-  if (ix->topo_valid) return GSDF_OK;
-  HIP_TRY(hipSetDevice(ix->device));
-  const int dev = ix->device;
-  hipStream_t s = ix->stream;
-  const uint64_t V = ix->n_verts, F = ix->n_tris;
-  const unsigned nb_v = blocks_of(V), nb_f = blocks_of(F);
-  const char* nomem = "report: no device memory for the workspace";
-  PoolBuf ctr, wctr, parent, used, root_of, shell_num, blk_cnt, blk_base, table, acc;
-  if (!ctr.take(dev, sizeof(TopoCounters)) || !wctr.take(dev, sizeof(WeldCounters)) || !parent.take(dev, V * 4) || !used.take(dev, V * 4) ||
-      !root_of.take(dev, V * 4) || !shell_num.take(dev, V * 4) || !blk_cnt.take(dev, (size_t)nb_v * 4) || !blk_base.take(dev, (size_t)nb_v * 4) ||
-      !ix->shell_of_vertex.take(dev, V * 4) || !ix->shell_of_face.take(dev, F * 4))
-    return fail(GSDF_ERR_HIP, nomem);
-  EventPair ev_e, ev_s, ev_m;
-  if (!ev_e.make() || !ev_s.make() || !ev_m.make()) return fail(GSDF_ERR_HIP, "hipEventCreate failed");
-  // 1. the edge table: about 3 F / 2 pairs at load <= 0.5; a pass that ends fuller, or that gave up on a pair, is repeated with
-  // twice the cells (GSDF_HIP_TOPO_CELLS_MIN lowers the first size: the tests' way into that path). Then the exponent.
-  uint64_t cells = 1024;
-  {
-    const char* e = getenv("GSDF_HIP_TOPO_CELLS_MIN");
-    const uint64_t want = e ? (uint64_t)strtoull(e, nullptr, 10) : 3 * F;
-    while (cells < want) cells <<= 1;
-  }
-  TopoCounters hc{};
-  int attempts = 0;
-  HIP_TRY(hipEventRecord(ev_e.a, s));
-  for (;;) {
-    if (cells > ((uint64_t)1 << 32)) return fail(GSDF_ERR_CAPACITY, "report: hash table capacity exceeded");
-    if (!table.take(dev, cells * 16)) return fail(GSDF_ERR_HIP, nomem);
-    attempts++;
-    HIP_TRY(hipMemsetAsync(table.p, 0xff, cells * 8, s));
-    HIP_TRY(hipMemsetAsync((uint8_t*)table.p + cells * 8, 0, cells * 8, s));
-    HIP_TRY(hipMemsetAsync(ctr.p, 0, sizeof(TopoCounters), s));
-    hipLaunchKernelGGL(topo_edge_insert_kernel, dim3(nb_f), dim3(BLOCK), 0, s, (const unsigned*)ix->idx.as<unsigned>(), (unsigned long long)F,
-                       table.as<unsigned long long>(), (unsigned*)(table.as<unsigned long long>() + cells), (unsigned)(cells - 1), ctr.as<TopoCounters>());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(&hc, ctr.p, sizeof hc, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (!hc.overflow && hc.distinct * 2 <= cells) break;
-    cells <<= 1;
-  }
-  hipLaunchKernelGGL(topo_maxbits_kernel, dim3(grid_for(3 * V, ix->num_cu, 8)), dim3(BLOCK), 0, s, (const float*)ix->verts.p, (unsigned long long)(3 * V),
-                     ctr.as<TopoCounters>());
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(ev_e.b, s));
-  // 2. shells
-  HIP_TRY(hipEventRecord(ev_s.a, s));
-  hipLaunchKernelGGL(topo_parent_init_kernel, dim3(nb_v), dim3(BLOCK), 0, s, parent.as<unsigned>(), used.as<unsigned>(), (unsigned long long)V);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(topo_union_kernel, dim3(nb_f), dim3(BLOCK), 0, s, (const unsigned*)ix->idx.as<unsigned>(), (unsigned long long)F, parent.as<unsigned>(),
-                     used.as<unsigned>());
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(topo_root_kernel, dim3(nb_v), dim3(BLOCK), 0, s, (const unsigned*)parent.as<unsigned>(), (const unsigned*)used.as<unsigned>(),
-                     (unsigned long long)V, root_of.as<unsigned>(), blk_cnt.as<unsigned>(), ctr.as<TopoCounters>());
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(weld_block_scan_kernel, dim3(1), dim3(1024), 0, s, (const unsigned*)blk_cnt.as<unsigned>(), nb_v, blk_base.as<unsigned>(), wctr.as<WeldCounters>());
-  HIP_TRY(hipGetLastError());
-  WeldCounters hw{};
-  HIP_TRY(hipMemcpyAsync(&hw, wctr.p, sizeof hw, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(&hc, ctr.p, sizeof hc, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  const uint64_t n_shells = hw.n_verts;
-  if (n_shells > V) return fail(GSDF_ERR_HIP, "report: internal error (more shells than vertices)");
-  if (!acc.take(dev, (n_shells + 1) * sizeof(TopoShellAcc))) return fail(GSDF_ERR_HIP, nomem);
-  HIP_TRY(hipMemsetAsync(acc.p, 0, (n_shells + 1) * sizeof(TopoShellAcc), s));
-  hipLaunchKernelGGL(topo_number_kernel, dim3(nb_v), dim3(BLOCK), 0, s, (const unsigned*)root_of.as<unsigned>(), (const unsigned*)used.as<unsigned>(),
-                     (unsigned long long)V, (const unsigned*)blk_base.as<unsigned>(), shell_num.as<unsigned>(), acc.as<TopoShellAcc>());
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(topo_vertex_shell_kernel, dim3(nb_v), dim3(BLOCK), 0, s, (const unsigned*)root_of.as<unsigned>(), (const unsigned*)used.as<unsigned>(),
-                     (unsigned long long)V, (const unsigned*)shell_num.as<unsigned>(), ix->shell_of_vertex.as<unsigned>(), acc.as<TopoShellAcc>());
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(ev_s.b, s));
-  // 3. measures and pair classes
-  const int biased = (int)(hc.maxbits >> 23);
-  const int e = (biased > 1 ? biased : 1) - 126;
-  const int sh_area = 59 - 2 * e, sh_vol = 62 - 3 * e, sh_mom = 62 - 4 * e;
-  HIP_TRY(hipEventRecord(ev_m.a, s));
-  hipLaunchKernelGGL(topo_measure_kernel, dim3(nb_f), dim3(BLOCK), 0, s, (const float*)ix->verts.p, (const unsigned*)ix->idx.as<unsigned>(), (unsigned long long)F,
-                     (const unsigned*)ix->shell_of_vertex.as<unsigned>(), ix->shell_of_face.as<unsigned>(), acc.as<TopoShellAcc>(), std::ldexp(1.0, sh_area),
-                     std::ldexp(1.0, sh_vol), std::ldexp(1.0, sh_mom));
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(topo_classify_kernel, dim3(blocks_of(cells)), dim3(BLOCK), 0, s, (const unsigned long long*)table.as<unsigned long long>(),
-                     (const unsigned*)(table.as<unsigned long long>() + cells), (unsigned long long)cells, (const unsigned*)ix->shell_of_vertex.as<unsigned>(),
-                     acc.as<TopoShellAcc>());
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(ev_m.b, s));
-  std::vector<TopoShellAcc> ha(n_shells);
-  if (n_shells) HIP_TRY(hipMemcpyAsync(ha.data(), acc.p, n_shells * sizeof(TopoShellAcc), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  // the shells' records; the mesh's sums are the sums of the shells' integers
-  gsdf_indexed_report r{};
-  std::vector<gsdf_shell> shells(n_shells);
-  __int128 tot[5] = {0, 0, 0, 0, 0};
-  unsigned bb[6] = {TOPO_BB_MIN_INIT, TOPO_BB_MIN_INIT, TOPO_BB_MIN_INIT, TOPO_BB_MAX_INIT, TOPO_BB_MAX_INIT, TOPO_BB_MAX_INIT};
-  const int shift[5] = {sh_area, sh_vol, sh_mom, sh_mom, sh_mom};
-  uint64_t tris = 0, edges_by_shell = 0;
-  for (uint64_t k = 0; k < n_shells; k++) {
-    const TopoShellAcc& a = ha[k];
-    gsdf_shell& o = shells[k];
-    o.n_verts = a.n_verts; o.n_tris = a.n_tris; o.nonfinite = a.nonfinite;
-    o.edges = a.edges; o.boundary_edges = a.boundary; o.nonmanifold_edges = a.nonmanifold; o.misoriented_edges = a.misoriented;
-    o.euler = (int64_t)a.n_verts - (int64_t)a.edges + (int64_t)a.n_tris;
-    double val[5];
-    for (int q = 0; q < 5; q++) {
-      const __int128 t = topo_int(a.sum + 2 * q);
-      tot[q] += t;
-      val[q] = topo_value(t, shift[q]);
-    }
-    o.area = val[0]; o.volume = val[1];
-    for (int q = 0; q < 3; q++) o.centroid[q] = topo_quotient(val[2 + q], val[1]);
-    for (int q = 0; q < 6; q++) o.bbox[q] = topo_unordered(a.bb[q]);
-    for (int q = 0; q < 3; q++) { bb[q] = std::min(bb[q], a.bb[q]); bb[3 + q] = std::max(bb[3 + q], a.bb[3 + q]); }
-    o.label = a.label;
-    r.nonfinite += a.nonfinite; r.boundary_edges += a.boundary; r.nonmanifold_edges += a.nonmanifold; r.misoriented_edges += a.misoriented;
-    tris += a.n_tris; edges_by_shell += a.edges;
-  }
-  if (tris != F - hc.degenerate || edges_by_shell != hc.distinct) return fail(GSDF_ERR_HIP, "report: internal error (the shells' counts do not add up)");
-  r.n_verts = V; r.n_tris = F; r.degenerate = hc.degenerate; r.used_verts = hc.used_verts; r.edges = hc.distinct; r.n_shells = n_shells;
-  r.euler = (int64_t)r.used_verts - (int64_t)r.edges + (int64_t)(F - r.degenerate);
-  r.area = topo_value(tot[0], shift[0]);
-  r.volume = topo_value(tot[1], shift[1]);
-  for (int q = 0; q < 3; q++) r.centroid[q] = topo_quotient(topo_value(tot[2 + q], shift[2 + q]), r.volume);
-  for (int q = 0; q < 6; q++) r.bbox[q] = topo_unordered(bb[q]);
-  r.closed_oriented = (r.degenerate == 0 && r.boundary_edges == 0 && r.nonmanifold_edges == 0 && r.misoriented_edges == 0) ? 1 : 0;
-  r.exponent = e;
-  r.ms_edges = ev_e.ms(); r.ms_shells = ev_s.ms(); r.ms_measure = ev_m.ms();
-  r.probes = hc.probes; r.table_cells = cells; r.attempts = attempts;
-  ix->rep = r;
-  ix->shells.swap(shells);
-  ix->topo_valid = true;
-  return GSDF_OK;
-}
-
-extern "C" int gsdf_hip_indexed_report(gsdf_indexed* ix, gsdf_indexed_report* rep) {
-  if (!ix || !rep) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
-  if (int rc = topo_ensure(ix)) return rc;
-  *rep = ix->rep;
-  return GSDF_OK;
-}
-
-extern "C" int gsdf_hip_indexed_shells(gsdf_indexed* ix, gsdf_shell* dst, uint64_t cap, uint64_t* n) {
-  if (!ix || !n) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
-  if (int rc = topo_ensure(ix)) return rc;
-  *n = ix->shells.size();
-  if (!dst) return GSDF_OK;
-  if (cap < *n) return fail(GSDF_ERR_SHORT_BUFFER, "short buffer");
-  if (*n) std::memcpy(dst, ix->shells.data(), *n * sizeof(gsdf_shell));
-  return GSDF_OK;
-}
-
-extern "C" int gsdf_hip_indexed_read_shell_of(gsdf_indexed* ix, uint32_t* shell_of_vertex, uint32_t* shell_of_face) {
-  if (!ix) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
-  if (int rc = topo_ensure(ix)) return rc;
-  HIP_TRY(hipSetDevice(ix->device));
-  if (shell_of_vertex) HIP_TRY(hipMemcpy(shell_of_vertex, ix->shell_of_vertex.p, ix->n_verts * 4, hipMemcpyDeviceToHost));
-  if (shell_of_face) HIP_TRY(hipMemcpy(shell_of_face, ix->shell_of_face.p, ix->n_tris * 4, hipMemcpyDeviceToHost));
-  return GSDF_OK;
-}
-
-extern "C" int gsdf_hip_indexed_extract(gsdf_indexed* ix, const uint8_t* keep_shell, int drop_degenerate, gsdf_indexed** out) {
-  if (!ix || !out) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
-  *out = nullptr;
-  if (int rc = topo_ensure(ix)) return rc;
-  HIP_TRY(hipSetDevice(ix->device));
-  const int dev = ix->device;
-  hipStream_t s = ix->stream;
-  const uint64_t V = ix->n_verts, F = ix->n_tris, n_shells = ix->shells.size();
-  const unsigned nb_f = blocks_of(F);
-  const char* nomem = "extract: no device memory for the workspace";
-  PoolBuf d_keep, keep, blk_cnt, blk_base, wctr, first, vnum;
-  if (!keep.take(dev, F) || !blk_cnt.take(dev, (size_t)blocks_of(3 * F) * 4) || !blk_base.take(dev, (size_t)blocks_of(3 * F) * 4) ||
-      !wctr.take(dev, sizeof(WeldCounters)) || !first.take(dev, V * 4) || !vnum.take(dev, V * 4))
-    return fail(GSDF_ERR_HIP, nomem);
-  if (keep_shell && n_shells) {
-    if (!d_keep.take(dev, n_shells)) return fail(GSDF_ERR_HIP, nomem);
-    HIP_TRY(hipMemcpyAsync(d_keep.p, keep_shell, n_shells, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));  // (the caller's bytes are pageable: they were read by now)
-  }
-  EventPair ev;
-  if (!ev.make()) return fail(GSDF_ERR_HIP, "hipEventCreate failed");
-  HIP_TRY(hipEventRecord(ev.a, s));
-  // kept faces, in order
-  hipLaunchKernelGGL(topo_keep_kernel, dim3(nb_f), dim3(BLOCK), 0, s, (const unsigned*)ix->shell_of_face.as<unsigned>(), (unsigned long long)F,
-                     (const unsigned char*)(keep_shell ? d_keep.p : nullptr), (!drop_degenerate && !keep_shell) ? 1 : 0, keep.as<unsigned char>(), blk_cnt.as<unsigned>());
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(weld_block_scan_kernel, dim3(1), dim3(1024), 0, s, (const unsigned*)blk_cnt.as<unsigned>(), nb_f, blk_base.as<unsigned>(), wctr.as<WeldCounters>());
-  HIP_TRY(hipGetLastError());
-  WeldCounters hw{};
-  HIP_TRY(hipMemcpyAsync(&hw, wctr.p, sizeof hw, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  const uint64_t F2 = hw.n_verts;
-  if (F2 == 0) return fail(GSDF_ERR_EMPTY_BUFFERS, "extract: nothing kept");
-  if (F2 > F) return fail(GSDF_ERR_HIP, "extract: internal error (more faces kept than there are)");
-  gsdf_indexed* nx = nullptr;
-  if (int rc = indexed_new(dev, ix->num_cu, &nx)) return rc;
-  auto bail = [&](int code) { gsdf_hip_indexed_destroy(nx); return code; };
-#define HIP_TRYX(expr)                                                                                          \
-  do {                                                                                                          \
-    hipError_t _e = (expr);                                                                                     \
-    if (_e != hipSuccess) return bail(fail(GSDF_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e))); \
-  } while (0)
-  const uint64_t S2 = 3 * F2;
-  const unsigned nb_s = blocks_of(S2);
-  if (!nx->idx.take(dev, S2 * 4)) return bail(fail(GSDF_ERR_HIP, nomem));
-  HIP_TRYX(hipMemsetAsync(first.p, 0xff, V * 4, s));
-  hipLaunchKernelGGL(topo_compact_kernel, dim3(nb_f), dim3(BLOCK), 0, s, (const unsigned*)ix->idx.as<unsigned>(), (const unsigned char*)keep.as<unsigned char>(),
-                     (unsigned long long)F, (const unsigned*)blk_base.as<unsigned>(), nx->idx.as<unsigned>(), first.as<unsigned>());
-  HIP_TRYX(hipGetLastError());
-  // vertices by their smallest kept slot
-  hipLaunchKernelGGL(topo_owner_kernel, dim3(nb_s), dim3(BLOCK), 0, s, (const unsigned*)nx->idx.as<unsigned>(), (unsigned long long)S2,
-                     (const unsigned*)first.as<unsigned>(), blk_cnt.as<unsigned>());
-  HIP_TRYX(hipGetLastError());
-  hipLaunchKernelGGL(weld_block_scan_kernel, dim3(1), dim3(1024), 0, s, (const unsigned*)blk_cnt.as<unsigned>(), nb_s, blk_base.as<unsigned>(), wctr.as<WeldCounters>());
-  HIP_TRYX(hipGetLastError());
-  HIP_TRYX(hipMemcpyAsync(&hw, wctr.p, sizeof hw, hipMemcpyDeviceToHost, s));
-  HIP_TRYX(hipStreamSynchronize(s));
-  const uint64_t V2 = hw.n_verts;
-  if (V2 == 0 || V2 > V) return bail(fail(GSDF_ERR_HIP, "extract: internal error (kept vertices)"));
-  if (!nx->verts.take(dev, V2 * 12) || !nx->vkeys.take(dev, V2 * 8) || (ix->has_normals && !nx->normals.take(dev, V2 * 12))) return bail(fail(GSDF_ERR_HIP, nomem));
-  hipLaunchKernelGGL(topo_renumber_kernel, dim3(nb_s), dim3(BLOCK), 0, s, (const unsigned*)nx->idx.as<unsigned>(), (unsigned long long)S2,
-                     (const unsigned*)first.as<unsigned>(), (const unsigned*)blk_base.as<unsigned>(), vnum.as<unsigned>(), (const unsigned*)ix->verts.as<unsigned>(),
-                     (const unsigned long long*)ix->vkeys.as<unsigned long long>(), (const unsigned*)(ix->has_normals ? ix->normals.p : nullptr),
-                     nx->verts.as<unsigned>(), nx->vkeys.as<unsigned long long>(), (unsigned*)(ix->has_normals ? nx->normals.p : nullptr));
-  HIP_TRYX(hipGetLastError());
-  hipLaunchKernelGGL(topo_reindex_kernel, dim3(nb_s), dim3(BLOCK), 0, s, nx->idx.as<unsigned>(), (unsigned long long)S2, (const unsigned*)vnum.as<unsigned>());
-  HIP_TRYX(hipGetLastError());
-  HIP_TRYX(hipEventRecord(ev.b, s));
-  HIP_TRYX(hipStreamSynchronize(s));
-#undef HIP_TRYX
-  nx->n_verts = V2;
-  nx->n_tris = F2;
-  nx->has_normals = ix->has_normals;
-  nx->ms_device = ev.ms();
-  *out = nx;
-  return GSDF_OK;
 }

@@ -1,5 +1,5 @@
 // abi_program.h -- the program handle and the launch helpers of the translation units that own kernels (abi_eval.hip,
-// abi_mesh.hip). Include after the kernel headers: the handle's LDS arithmetic uses their constants (BLOCK, TRI_STAGE, ...).
+// abi_mesh.hip, abi_indexed.hip). Include after the kernel headers: the handle's LDS arithmetic uses their constants (BLOCK, TRI_STAGE, ...).
 #pragma once
 #include <condition_variable>
 #include <mutex>

@@ -112,3 +112,30 @@ __host__ __device__ __forceinline__ unsigned brick_owner(unsigned x, unsigned y,
   h ^= h >> 12;
   return h % count;
 }
+
+// ---- shared by the marching kernels (kernels_octree.h) and the indexed-mesh kernels (kernels_weld.h) --------------------------
+// The packed cut-leaf records (kernels_octree.h: leaf_eval_kernel writes them, pack_records_kernel lays them out as a payload).
+#define REC_WORDS 10     // dwords per record
+#define DENSE_CHUNK 256  // records per chunk of a payload: one triangle count each behind the records (dense_payload_bytes)
+
+// Inclusive prefix sum over the 64 lanes of a wave by DPP row shifts and row broadcasts: six v_add_u32 with a DPP operand (the
+// compiler folds the move into the integer add) -- __shfl_up goes through ds_bpermute, an LDS round trip per step.
+__device__ __forceinline__ unsigned wave_incl_scan_u32(unsigned v) {
+  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);  // row_shr:1
+  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);  // row_shr:2
+  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);  // row_shr:4
+  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);  // row_shr:8
+  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);  // row_bcast:15 into rows 1 and 3
+  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);  // row_bcast:31 into rows 2 and 3
+  return v;
+}
+
+// The edge word of marching-cubes edge e (kernels_octree.h: "the marching kernels' vertex" says what the fields are for).
+constexpr __host__ __device__ __forceinline__ uint32_t march_edge_word(unsigned e) {
+  const unsigned ca = GSDF_MC_PAIR_A(e), cb = GSDF_MC_PAIR_B(e);
+  const unsigned pa = ((ca ^ (ca >> 1)) & 1u) | (((ca >> 1) & 1u) << 1) | (((ca >> 2) & 1u) << 2);
+  const unsigned pb = ((cb ^ (cb >> 1)) & 1u) | (((cb >> 1) & 1u) << 1) | (((cb >> 2) & 1u) << 2);
+  const unsigned d = pa ^ pb;  // exactly one bit
+  const unsigned axis = d == 1u ? 0u : (d == 2u ? 1u : 2u);
+  return ca | (cb << 3) | (axis << 6) | (pa << 8);
+}

@@ -649,7 +649,6 @@ __global__ void __launch_bounds__(BLOCK, WAVES) leaf_kernel(const uint32_t* __re
 // Same float operations on the same values as the fused kernel: the leaf origin is recomputed from the stored leaf
 // coordinates by the expression the evaluation used.
 // ---------------------------------------------------------------------------------------------------------------------
-#define REC_WORDS 10            // dwords per record
 #define REC_BLOCK (64 * REC_WORDS)  // dwords per 64-leaf block
 #define MARCH_GROUP 64              // blocks per entry of the group sums (records, triangles, active leaves) the evaluating kernel accumulates
 // One 64-bit word per group: records in bits 0..19 (<= 64 blocks x 64 = 4096), triangles in bits 20..35 (<= 5 per record: 20 480),
@@ -1112,18 +1111,6 @@ __global__ void __launch_bounds__(BLOCK, WAVES) leaf_dense_kernel(const uint32_t
   }
 }
 
-// Inclusive prefix sum over the 64 lanes of a wave by DPP row shifts and row broadcasts: six v_add_u32 with a DPP operand (the
-// compiler folds the move into the integer add) -- __shfl_up goes through ds_bpermute, an LDS round trip per step.
-__device__ __forceinline__ unsigned wave_incl_scan_u32(unsigned v) {
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);  // row_shr:1
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);  // row_shr:2
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);  // row_shr:4
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);  // row_shr:8
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);  // row_bcast:15 into rows 1 and 3
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);  // row_bcast:31 into rows 2 and 3
-  return v;
-}
-
 // Inclusive prefix sum over the workgroup (thread order) of a 64-bit value; *total = the workgroup's sum. s_w: 4 words of LDS.
 __device__ __forceinline__ unsigned long long block_scan_u64(unsigned long long v, unsigned long long* s_w, unsigned long long* total) {
   const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1148,14 +1135,6 @@ __device__ __forceinline__ unsigned long long block_scan_u64(unsigned long long 
 // also for a NaN or infinite t, which reaches the unchanged coordinates through t * 0 -- at a third of the arithmetic.
 // Edge word (the kernels' LDS table: one 16-bit entry per triangle corner): ca | cb << 3 | axis << 6 | pa << 8, pa bit 0 / 1 / 2 =
 // corner a sits at the max of the leaf's box in x / y / z (Box{origin, origin + size}: max = min + res).
-constexpr __host__ __device__ __forceinline__ uint32_t march_edge_word(unsigned e) {
-  const unsigned ca = GSDF_MC_PAIR_A(e), cb = GSDF_MC_PAIR_B(e);
-  const unsigned pa = ((ca ^ (ca >> 1)) & 1u) | (((ca >> 1) & 1u) << 1) | (((ca >> 2) & 1u) << 2);
-  const unsigned pb = ((cb ^ (cb >> 1)) & 1u) | (((cb >> 1) & 1u) << 1) | (((cb >> 2) & 1u) << 2);
-  const unsigned d = pa ^ pb;  // exactly one bit
-  const unsigned axis = d == 1u ? 0u : (d == 2u ? 1u : 2u);
-  return ca | (cb << 3) | (axis << 6) | (pa << 8);
-}
 // col: the record's 8 corner distances + leaf origin (11 floats)
 __device__ __forceinline__ void march_vertex(uint32_t ed, const float* col, float res, float& rx, float& ry, float& rz) {
   const float x0 = col[8], y0 = col[9], z0 = col[10];
@@ -1549,7 +1528,6 @@ __global__ void __launch_bounds__(BLOCK, 4) march_records_kernel(const uint32_t*
 //   pack_records_kernel  the sparse record slots of leaf_eval_kernel -> the payload; chunk triangle counts by wave-level atomics
 //   march_dense_kernel   marching cubes over a buffer holding the payloads of several ranks side by side (or of one)
 // ---------------------------------------------------------------------------------------------------------------------
-#define DENSE_CHUNK 256
 #define DENSE_MAX_PARTS 64
 __host__ __device__ __forceinline__ unsigned long long dense_payload_bytes(unsigned long long n) {
   return n * 40ull + ((((n + DENSE_CHUNK - 1ull) / DENSE_CHUNK) * 4ull + 7ull) & ~7ull);

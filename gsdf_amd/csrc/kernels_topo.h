@@ -1,19 +1,19 @@
 // kernels_topo.h -- what an indexed mesh is, topologically and in measure: edge classes, shells, area / volume / moments, and the
-// extraction of shells into a new mesh (include/gsdf_hip.h: "indexed meshes: report and extract" states the contract; abi_mesh.hip
+// extraction of shells into a new mesh (include/gsdf_hip.h: "indexed meshes: report and extract" states the contract; abi_indexed.hip
 // launches these). Independent of any SDF tree: these kernels live in the shipped code object only.
 //
 //   topo_maxbits_kernel      integer max over the finite coordinates' |bits|: the exponent e of the contract
-//   topo_edge_insert_kernel  a face per lane -> its three unordered pairs into an open-addressing table (64-bit compare-and-swap on
-//                            the key, as weld_insert_kernel) and +1 on the pair's forward or reverse counter
+//   topo_edge_insert_kernel  a face per lane -> its three unordered pairs into the open-addressing table (kernels_weld.h:
+//                            table_claim) and +1 on the pair's forward or reverse counter
 //   topo_union_kernel        a face per lane -> union (a, b), (b, c): lock-free union-find, every write an atomicMin, so that
 //                            parent[x] <= x always and a component's root is its smallest vertex whatever the order of arrival
 //   topo_root_kernel         vertex -> root (read-only chase); roots of used vertices counted per block of 256
-//   weld_block_scan_kernel   (kernels_weld.h) the carry across blocks
-//   topo_number_kernel       ballot + mbcnt + the block's carry: root -> shell number, in increasing order of the root
+//   block_scan_kernel        (kernels_weld.h) the carry across blocks
+//   topo_number_kernel       block_rank + the block's carry: root -> shell number, in increasing order of the root
 //   topo_vertex_shell_kernel vertex -> shell number; the shells' vertex counts
 //   topo_measure_kernel      a face per lane: shell of the face, the contract's float64 terms quantised to integers, summed as integers
 //   topo_classify_kernel     a CELL per lane: the pair's class, counted on its shell (the shell of its smaller vertex)
-//   topo_keep_kernel .. topo_reindex_kernel   extract: kept faces compacted in order, vertices renumbered by their smallest kept slot
+//   topo_keep_kernel .. topo_renumber_kernel, remap_kernel   extract: kept faces compacted in order, vertices renumbered by their smallest kept slot
 //
 // Sums. A wave whose lanes all belong to one shell (the common case: a shell's faces are runs in mesher order) reduces across the
 // wave and issues ONE atomic per quantity; a mixed wave issues per-lane atomics on each lane's shell. Every quantity is an integer
@@ -28,11 +28,10 @@
 #define TOPO_BB_MAX_INIT 0x007fffffu  // ... of -inf
 
 struct TopoCounters {
-  unsigned long long overflow;    // topo_edge_insert_kernel: a pair found no cell within WELD_MAX_PROBES
-  unsigned long long probes;      // cells it inspected
-  unsigned long long distinct;    // pairs that claimed a cell
+  TableCounters tab;              // topo_edge_insert_kernel: the pairs' table (the host reads this head as it reads the weld's)
   unsigned long long degenerate;  // faces with two equal indices
   unsigned long long used_verts;  // topo_root_kernel
+  unsigned long long n_shells;    // block_scan_kernel over topo_root_kernel's counts
   unsigned long long maxbits;     // topo_maxbits_kernel
 };
 
@@ -122,22 +121,6 @@ __device__ __forceinline__ void topo_minmax(const TopoWave& w, unsigned shell, u
   }
 }
 
-// flags of one workgroup: how many are set (valid in thread 0 after the call) / the rank of this thread's among them
-__device__ __forceinline__ unsigned topo_block_count(bool flag, unsigned* s_w) {
-  const unsigned cnt = (unsigned)__builtin_popcountll(__ballot(flag));
-  if ((threadIdx.x & 63u) == 0u) s_w[threadIdx.x >> 6] = cnt;
-  __syncthreads();
-  return s_w[0] + s_w[1] + s_w[2] + s_w[3];
-}
-__device__ __forceinline__ unsigned topo_block_rank(bool flag, unsigned* s_w) {
-  const unsigned long long m = __ballot(flag);
-  const unsigned wave = threadIdx.x >> 6;
-  const unsigned before = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-  if ((threadIdx.x & 63u) == 0u) s_w[wave] = (unsigned)__builtin_popcountll(m);
-  __syncthreads();
-  return (wave > 0 ? s_w[0] : 0u) + (wave > 1 ? s_w[1] : 0u) + (wave > 2 ? s_w[2] : 0u) + before;
-}
-
 // ---- the exponent ----------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(BLOCK) topo_maxbits_kernel(const float* __restrict__ verts, unsigned long long n, TopoCounters* __restrict__ ctr) {
   unsigned m = 0;
@@ -172,37 +155,15 @@ __global__ void __launch_bounds__(BLOCK) topo_edge_insert_kernel(const unsigned*
         const unsigned p = v[j], q = v[j == 2 ? 0 : j + 1];
         const bool fwd = p < q;
         const unsigned long long key = fwd ? (((unsigned long long)p << 32) | q) : (((unsigned long long)q << 32) | p);
-        unsigned h = weld_hash(key) & mask;
-        bool placed = false;
-        for (unsigned n = 0; n < WELD_MAX_PROBES && n <= mask; n++) {
-          my_probes++;
-          unsigned long long seen = tab_key[h];
-          if (seen == WELD_EMPTY_KEY) {
-            seen = atomicCAS(&tab_key[h], WELD_EMPTY_KEY, key);
-            if (seen == WELD_EMPTY_KEY) { my_new++; seen = key; }
-          }
-          if (seen == key) {
-            atomicAdd(&tab_cnt[2ull * h + (fwd ? 0u : 1u)], 1u);
-            placed = true;
-            break;
-          }
-          h = (h + 1u) & mask;
-        }
-        if (!placed) lost = true;
+        const unsigned long long cell = table_claim(tab_key, mask, key, &my_probes, &my_new);
+        if (cell != TABLE_NONE) atomicAdd(&tab_cnt[2ull * cell + (fwd ? 0u : 1u)], 1u);
+        else lost = true;
       }
     }
   }
-  unsigned p = my_probes, d = my_new;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) { p += __shfl_down(p, off, 64); d += __shfl_down(d, off, 64); }
-  const bool any_lost = __ballot(lost) != 0ull;
+  table_stats(my_probes, my_new, lost, &ctr->tab);
   const unsigned n_deg = (unsigned)__builtin_popcountll(__ballot(deg));
-  if ((threadIdx.x & 63u) == 0u) {
-    if (p) atomicAdd(&ctr->probes, (unsigned long long)p);
-    if (d) atomicAdd(&ctr->distinct, (unsigned long long)d);
-    if (n_deg) atomicAdd(&ctr->degenerate, (unsigned long long)n_deg);
-    if (any_lost) atomicMax(&ctr->overflow, 1ull);
-  }
+  if ((threadIdx.x & 63u) == 0u && n_deg) atomicAdd(&ctr->degenerate, (unsigned long long)n_deg);
 }
 
 // ---- shells ------------------------------------------------------------------------------------------------------------------------
@@ -267,7 +228,7 @@ __global__ void __launch_bounds__(BLOCK) topo_root_kernel(const unsigned* __rest
   }
   const unsigned n_used = (unsigned)__builtin_popcountll(__ballot(is_used));
   if ((threadIdx.x & 63u) == 0u && n_used) atomicAdd(&ctr->used_verts, (unsigned long long)n_used);
-  const unsigned total = topo_block_count(is_root, s_w);
+  const unsigned total = block_count(is_root, s_w);
   if (threadIdx.x == 0) blk_cnt[blockIdx.x] = total;
 }
 
@@ -277,7 +238,7 @@ __global__ void __launch_bounds__(BLOCK) topo_number_kernel(const unsigned* __re
   __shared__ unsigned s_w[4];
   const unsigned long long v = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x;
   const bool is_root = v < n_verts && used[v] != 0u && root_of[v] == (unsigned)v;
-  const unsigned rank = topo_block_rank(is_root, s_w);
+  const unsigned rank = block_rank(is_root, s_w);
   if (is_root) {
     const unsigned s = blk_base[blockIdx.x] + rank;
     shell_num[v] = s;
@@ -401,7 +362,7 @@ __global__ void __launch_bounds__(BLOCK) topo_keep_kernel(const unsigned* __rest
     k = s == TOPO_NONE ? keep_degenerate != 0 : (keep_shell ? keep_shell[s] != 0 : true);
     keep[f] = k ? 1 : 0;
   }
-  const unsigned total = topo_block_count(k, s_w);
+  const unsigned total = block_count(k, s_w);
   if (threadIdx.x == 0) blk_cnt[blockIdx.x] = total;
 }
 
@@ -411,7 +372,7 @@ __global__ void __launch_bounds__(BLOCK) topo_compact_kernel(const unsigned* __r
   __shared__ unsigned s_w[4];
   const unsigned long long f = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x;
   const bool k = f < n_tris && keep[f] != 0;
-  const unsigned rank = topo_block_rank(k, s_w);
+  const unsigned rank = block_rank(k, s_w);
   if (k) {
     const unsigned long long g = (unsigned long long)blk_base[blockIdx.x] + rank;
 #pragma unroll
@@ -428,7 +389,7 @@ __global__ void __launch_bounds__(BLOCK) topo_owner_kernel(const unsigned* __res
   __shared__ unsigned s_w[4];
   const unsigned long long s = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x;
   const bool owner = s < n_slots && first[out[s]] == (unsigned)s;
-  const unsigned total = topo_block_count(owner, s_w);
+  const unsigned total = block_count(owner, s_w);
   if (threadIdx.x == 0) blk_cnt[blockIdx.x] = total;
 }
 
@@ -442,7 +403,7 @@ __global__ void __launch_bounds__(BLOCK) topo_renumber_kernel(const unsigned* __
   const unsigned long long s = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x;
   const unsigned old = s < n_slots ? out[s] : 0u;
   const bool owner = s < n_slots && first[old] == (unsigned)s;
-  const unsigned rank = topo_block_rank(owner, s_w);
+  const unsigned rank = block_rank(owner, s_w);
   if (owner) {
     const unsigned v = blk_base[blockIdx.x] + rank;
     vnum[old] = v;
@@ -453,9 +414,4 @@ __global__ void __launch_bounds__(BLOCK) topo_renumber_kernel(const unsigned* __
     }
     nkeys[v] = vkeys[old];
   }
-}
-
-__global__ void __launch_bounds__(BLOCK) topo_reindex_kernel(unsigned* __restrict__ out, unsigned long long n_slots, const unsigned* __restrict__ vnum) {
-  const unsigned long long s = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x;
-  if (s < n_slots) out[s] = vnum[out[s]];
 }

@@ -1,31 +1,32 @@
 // kernels_weld.h -- indexed meshes: the marching-cubes vertices of a records mesh welded by lattice edge, and the binary PLY of
-// the result (include/gsdf_hip.h: "indexed meshes" states the contract; abi_mesh.hip launches these).
+// the result (include/gsdf_hip.h: "indexed meshes" states the contract; abi_indexed.hip launches these). Also what the weld shares
+// with the report (kernels_topo.h): the open-addressing table, a workgroup's flag count / rank, the scan across blocks, the remap.
 //
 // The soup of gsdf_hip_mesh_march (march_dense_kernel) is a function of the packed records: chunk c of DENSE_CHUNK records starts
 // at triangle sum(chunk_tri[< c]), a record's triangles follow those of the records before it in its chunk, in table order, each
 // with its corners reversed. So every slot's key can be written without looking at a float coordinate:
 //   weld_chunk_scan_kernel   exclusive prefix of the chunks' triangle counts (one workgroup)
 //   weld_keys_kernel         one record per lane -> the keys of its slots
-//   weld_insert_kernel       key -> open-addressing table: 64-bit compare-and-swap on the key, 32-bit atomicMin on the slot
-//   weld_owner_kernel        slot -> the smallest slot with its key; owners counted per block of 256 slots
-//   weld_block_scan_kernel   exclusive prefix of the blocks' owner counts (one workgroup): the carry across blocks
-//   weld_number_kernel       ballot + mbcnt inside a wave, the four waves' sums, the block's carry: owner -> vertex number; gathers
-//                            the owner's position out of the soup, and its key
-//   weld_index_kernel        idx[s] = number of slot s's owner
+//   weld_insert_kernel       key -> its cell of the table (table_claim), 32-bit atomicMin on the cell's slot
+//   weld_owner_kernel        slot -> the smallest slot with its key (table_find); owners counted per block of 256 slots
+//   block_scan_kernel        exclusive prefix of the blocks' owner counts (one workgroup): the carry across blocks
+//   weld_number_kernel       the owner's rank in its block (block_rank) + the block's carry: owner -> vertex number; gathers the
+//                            owner's position out of the soup, and its key
+//   remap_kernel             idx[s] = number of slot s's owner
 // The table's content after weld_insert_kernel does not depend on the order of arrival: a cell's key is set once, its slot is a
 // minimum. Which CELL a key lands in does depend on it, and nothing reads that.
 #pragma once
 #include "kernels_common.h"
-#include "kernels_octree.h"
 
 #define WELD_EMPTY_KEY 0xffffffffffffffffull
 #define WELD_MAX_PROBES 4096u  // a probe sequence this long means a table far too full: the pass gives up and the host grows it
 
-struct WeldCounters {
+#define TABLE_NONE 0xffffffffffffffffull  // no cell (a cell index is below 2^32)
+
+struct TableCounters {
   unsigned long long overflow;  // a key found no cell within WELD_MAX_PROBES
-  unsigned long long probes;    // cells inspected by weld_insert_kernel
+  unsigned long long probes;    // cells inspected by the inserting pass
   unsigned long long distinct;  // keys that claimed a cell
-  unsigned long long n_verts;   // weld_block_scan_kernel: owners in all
 };
 
 __device__ __forceinline__ unsigned weld_hash(unsigned long long k) {
@@ -35,6 +36,64 @@ __device__ __forceinline__ unsigned weld_hash(unsigned long long k) {
   k *= 0xc4ceb9fe1a85ec53ull;
   k ^= k >> 33;
   return (unsigned)k;
+}
+
+// ---- the open-addressing table: tab_key[mask + 1], every cell WELD_EMPTY_KEY before the pass (a memset of 0xff) ----------------
+// The cell of `key`, claimed by a 64-bit compare-and-swap on the empty key if no thread had it yet (*is_new += 1 then); linear
+// probing, *probes += the cells inspected. TABLE_NONE after WELD_MAX_PROBES cells: the host grows the table and runs the pass again.
+__device__ __forceinline__ unsigned long long table_claim(unsigned long long* tab_key, unsigned mask, unsigned long long key, unsigned* probes,
+                                                          unsigned* is_new) {
+  unsigned h = weld_hash(key) & mask;
+  for (unsigned n = 0; n < WELD_MAX_PROBES && n <= mask; n++) {
+    (*probes)++;
+    unsigned long long seen = tab_key[h];
+    if (seen == WELD_EMPTY_KEY) {
+      seen = atomicCAS(&tab_key[h], WELD_EMPTY_KEY, key);
+      if (seen == WELD_EMPTY_KEY) { (*is_new)++; seen = key; }
+    }
+    if (seen == key) return h;
+    h = (h + 1u) & mask;
+  }
+  return TABLE_NONE;
+}
+// Read-only: the cell that holds `key`, TABLE_NONE if the table does not (the probe met an empty cell, or every cell).
+__device__ __forceinline__ unsigned long long table_find(const unsigned long long* tab_key, unsigned mask, unsigned long long key) {
+  unsigned h = weld_hash(key) & mask;
+  for (unsigned n = 0; n <= mask; n++) {
+    const unsigned long long seen = tab_key[h];
+    if (seen == key) return h;
+    if (seen == WELD_EMPTY_KEY) break;
+    h = (h + 1u) & mask;
+  }
+  return TABLE_NONE;
+}
+// An inserting pass's statistics, one atomic per wave and counter. Every lane of the wave calls it (it shuffles).
+__device__ __forceinline__ void table_stats(unsigned probes, unsigned is_new, bool lost, TableCounters* ctr) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) { probes += __shfl_down(probes, off, 64); is_new += __shfl_down(is_new, off, 64); }
+  const bool any_lost = __ballot(lost) != 0ull;
+  if ((threadIdx.x & 63u) == 0u) {
+    if (probes) atomicAdd(&ctr->probes, (unsigned long long)probes);
+    if (is_new) atomicAdd(&ctr->distinct, (unsigned long long)is_new);
+    if (any_lost) atomicMax(&ctr->overflow, 1ull);
+  }
+}
+
+// ---- flags of one workgroup: how many are set (valid in thread 0 after the call) / the rank of this thread's among them ---------
+// s_w: 4 words of LDS. Every thread of the workgroup calls them (they synchronise).
+__device__ __forceinline__ unsigned block_count(bool flag, unsigned* s_w) {
+  const unsigned cnt = (unsigned)__builtin_popcountll(__ballot(flag));
+  if ((threadIdx.x & 63u) == 0u) s_w[threadIdx.x >> 6] = cnt;
+  __syncthreads();
+  return s_w[0] + s_w[1] + s_w[2] + s_w[3];
+}
+__device__ __forceinline__ unsigned block_rank(bool flag, unsigned* s_w) {
+  const unsigned long long m = __ballot(flag);
+  const unsigned wave = threadIdx.x >> 6;
+  const unsigned before = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));  // exclusive, inside the wave
+  if ((threadIdx.x & 63u) == 0u) s_w[wave] = (unsigned)__builtin_popcountll(m);
+  __syncthreads();
+  return (wave > 0 ? s_w[0] : 0u) + (wave > 1 ? s_w[1] : 0u) + (wave > 2 ? s_w[2] : 0u) + before;
 }
 
 // |v| < 1e-12f as mcInterpolate asks it (marchcubes.go:84-90: abs(0 - v) < 1e-12), on the bits: false for a NaN in every build
@@ -116,43 +175,19 @@ __global__ void __launch_bounds__(BLOCK) weld_keys_kernel(const uint8_t* __restr
   }
 }
 
-// tab_key[cells] = WELD_EMPTY_KEY, tab_slot[cells] = 0xffffffff before the pass (a memset of 0xff); mask = cells - 1.
+// tab_slot[cells] = 0xffffffff before the pass (the table's memset of 0xff covers it); mask = cells - 1.
 __global__ void __launch_bounds__(BLOCK) weld_insert_kernel(const unsigned long long* __restrict__ keys, unsigned long long n_slots,
                                                             unsigned long long* __restrict__ tab_key, unsigned* __restrict__ tab_slot,
-                                                            unsigned mask, WeldCounters* __restrict__ ctr) {
+                                                            unsigned mask, TableCounters* __restrict__ ctr) {
   unsigned my_probes = 0, my_new = 0;
   bool lost = false;
   const unsigned long long step = (unsigned long long)gridDim.x * BLOCK;
   for (unsigned long long s = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x; s < n_slots; s += step) {
-    const unsigned long long key = keys[s];
-    unsigned h = weld_hash(key) & mask;
-    bool placed = false;
-    for (unsigned n = 0; n < WELD_MAX_PROBES && n <= mask; n++) {
-      my_probes++;
-      unsigned long long seen = tab_key[h];
-      if (seen == WELD_EMPTY_KEY) {
-        seen = atomicCAS(&tab_key[h], WELD_EMPTY_KEY, key);
-        if (seen == WELD_EMPTY_KEY) { my_new++; seen = key; }
-      }
-      if (seen == key) {
-        atomicMin(&tab_slot[h], (unsigned)s);
-        placed = true;
-        break;
-      }
-      h = (h + 1u) & mask;
-    }
-    if (!placed) lost = true;
+    const unsigned long long cell = table_claim(tab_key, mask, keys[s], &my_probes, &my_new);
+    if (cell != TABLE_NONE) atomicMin(&tab_slot[cell], (unsigned)s);
+    else lost = true;
   }
-  // statistics: one atomic per wave and counter
-  unsigned p = my_probes, d = my_new;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) { p += __shfl_down(p, off, 64); d += __shfl_down(d, off, 64); }
-  const bool any_lost = __ballot(lost) != 0ull;
-  if ((threadIdx.x & 63u) == 0u) {
-    if (p) atomicAdd(&ctr->probes, (unsigned long long)p);
-    if (d) atomicAdd(&ctr->distinct, (unsigned long long)d);
-    if (any_lost) atomicMax(&ctr->overflow, 1ull);
-  }
+  table_stats(my_probes, my_new, lost, ctr);
 }
 
 // idx[s] = the smallest slot with slot s's key; blk_cnt[b] = owners (idx[s] == s) among slots [256 b, 256 b + 256).
@@ -163,26 +198,18 @@ __global__ void __launch_bounds__(BLOCK) weld_owner_kernel(const unsigned long l
   const unsigned long long s = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x;
   bool owner = false;
   if (s < n_slots) {
-    const unsigned long long key = keys[s];
-    unsigned h = weld_hash(key) & mask, own = (unsigned)s;
-    for (unsigned n = 0; n <= mask; n++) {  // every key is in the table: ends at its cell
-      const unsigned long long seen = tab_key[h];
-      if (seen == key) { own = tab_slot[h]; break; }
-      if (seen == WELD_EMPTY_KEY) break;
-      h = (h + 1u) & mask;
-    }
+    const unsigned long long cell = table_find(tab_key, mask, keys[s]);  // every key is in the table
+    const unsigned own = cell != TABLE_NONE ? tab_slot[cell] : (unsigned)s;
     idx[s] = own;
     owner = own == (unsigned)s;
   }
-  const unsigned cnt = (unsigned)__builtin_popcountll(__ballot(owner));
-  if ((threadIdx.x & 63u) == 0u) s_w[threadIdx.x >> 6] = cnt;
-  __syncthreads();
-  if (threadIdx.x == 0) blk_cnt[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+  const unsigned total = block_count(owner, s_w);
+  if (threadIdx.x == 0) blk_cnt[blockIdx.x] = total;
 }
 
-// blk_cnt[n_blocks] -> blk_base[n_blocks], exclusive; the total -> ctr->n_verts. One workgroup of 1024 threads.
-__global__ void __launch_bounds__(1024) weld_block_scan_kernel(const unsigned* __restrict__ blk_cnt, unsigned n_blocks, unsigned* __restrict__ blk_base,
-                                                               WeldCounters* __restrict__ ctr) {
+// blk_cnt[n_blocks] -> blk_base[n_blocks], exclusive; their sum -> *total. One workgroup of 1024 threads.
+__global__ void __launch_bounds__(1024) block_scan_kernel(const unsigned* __restrict__ blk_cnt, unsigned n_blocks, unsigned* __restrict__ blk_base,
+                                                          unsigned long long* __restrict__ total) {
   __shared__ unsigned s_w[16];
   const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   const unsigned per = (n_blocks + 1023u) / 1024u;
@@ -194,17 +221,17 @@ __global__ void __launch_bounds__(1024) weld_block_scan_kernel(const unsigned* _
   const unsigned incl = wave_incl_scan_u32(mine);
   if (lane == 63u) s_w[wave] = incl;
   __syncthreads();
-  unsigned before = 0, total = 0;
+  unsigned before = 0, sum = 0;
   for (unsigned w = 0; w < 16u; w++) {
     if (w < wave) before += s_w[w];
-    total += s_w[w];
+    sum += s_w[w];
   }
   unsigned acc = before + incl - mine;
   for (unsigned e = e0; e < e1; e++) {
     blk_base[e] = acc;
     acc += blk_cnt[e];
   }
-  if (tid == 0) ctr->n_verts = total;
+  if (tid == 0) *total = sum;
 }
 
 // Owners -> vertex numbers, in slot order; the owner's position (soup: 3 floats per slot) and key go to the vertex arrays.
@@ -213,14 +240,10 @@ __global__ void __launch_bounds__(BLOCK) weld_number_kernel(const unsigned* __re
                                                             unsigned* __restrict__ vnum, float* __restrict__ verts, unsigned long long* __restrict__ vkeys) {
   __shared__ unsigned s_w[4];
   const unsigned long long s = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x;
-  const unsigned wave = threadIdx.x >> 6;
   const bool owner = s < n_slots && idx[s] == (unsigned)s;
-  const unsigned long long m = __ballot(owner);
-  const unsigned before = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));  // exclusive, inside the wave
-  if ((threadIdx.x & 63u) == 0u) s_w[wave] = (unsigned)__builtin_popcountll(m);
-  __syncthreads();
+  const unsigned rank = block_rank(owner, s_w);
   if (owner) {
-    const unsigned v = blk_base[blockIdx.x] + (wave > 0 ? s_w[0] : 0u) + (wave > 1 ? s_w[1] : 0u) + (wave > 2 ? s_w[2] : 0u) + before;
+    const unsigned v = blk_base[blockIdx.x] + rank;
     vnum[s] = v;
     const float* src = soup + 3ull * s;
     float* dst = verts + 3ull * v;
@@ -229,7 +252,8 @@ __global__ void __launch_bounds__(BLOCK) weld_number_kernel(const unsigned* __re
   }
 }
 
-__global__ void __launch_bounds__(BLOCK) weld_index_kernel(unsigned* __restrict__ idx, unsigned long long n_slots, const unsigned* __restrict__ vnum) {
+// idx[s] = vnum[idx[s]]: slots that name an owner / an old vertex -> slots that name its new number
+__global__ void __launch_bounds__(BLOCK) remap_kernel(unsigned* __restrict__ idx, unsigned long long n_slots, const unsigned* __restrict__ vnum) {
   const unsigned long long s = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x;
   if (s < n_slots) idx[s] = vnum[idx[s]];
 }

@@ -471,7 +471,7 @@ void gsdf_hip_mesh_destroy(gsdf_mesh* m);
  * in place already (gsdf_hip_mesh_march: the mesh keeps its records for this) or not (the mesh stays as it is). Every other mesh
  * -- triangle payload, flat, dual contouring, minecraft, gathered, sharded -- is refused with GSDF_ERR_BAD_ARGUMENT and a text that
  * says what is required; a mesh with 3 F >= 2^32 with GSDF_ERR_CAPACITY; an empty one with GSDF_ERR_EMPTY_BUFFERS. The result is
- * independent of the mesh afterwards. Kernels: gsdf_amd/csrc/kernels_weld.h. */
+ * independent of the mesh afterwards. Kernels: gsdf_amd/csrc/kernels_weld.h, launched by abi_indexed.hip. */
 typedef struct gsdf_indexed gsdf_indexed; /* welded mesh, resident in HBM */
 typedef struct gsdf_indexed_stats {
   double ms_keys;        /* device time, HIP events: the slots' keys from the records */
@@ -511,7 +511,7 @@ void gsdf_hip_indexed_destroy(gsdf_indexed* ix);
  * What one asks of a mesh before it goes to a slicer: is it watertight and consistently oriented, how many shells has it, what are
  * their volume, area and centre of mass, and the mesh without some of them. All of it is computed on the device from the handle's
  * vertices and faces; the counts are functions of the faces alone, the measures of faces and positions, NONE of the order in which
- * threads arrive or of the order of the faces (Determinism below). Kernels: gsdf_amd/csrc/kernels_topo.h; a numpy restatement:
+ * threads arrive or of the order of the faces (Determinism below). Kernels: gsdf_amd/csrc/kernels_topo.h (abi_indexed.hip); a numpy restatement:
  * tests/toporef.py.
  *
  * Faces. A face with two equal indices is DEGENERATE: counted, and otherwise absent from everything below. A non-degenerate face

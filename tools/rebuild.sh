@@ -9,4 +9,4 @@ for a in "$@"; do case "$a" in -D*) DEFS+=("$a");; *) UNITS+=("$a");; esac; done
 pids=()
 for u in "${UNITS[@]}"; do /opt/rocm/bin/hipcc --offload-arch=gfx950 $FLAGS "${DEFS[@]}" -c "$u" -o "${u%.*}.o" & pids+=($!); done
 for p in "${pids[@]}"; do wait $p || exit 1; done
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC abi_eval.o abi_mesh.o abi_comm.o abi_host.o compile.o specialize.o -lhiprtc -ldl -o ${OUT:-libgsdfhip.so} && echo "linked ${OUT:-libgsdfhip.so}"
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC abi_eval.o abi_mesh.o abi_indexed.o abi_comm.o abi_host.o compile.o specialize.o -lhiprtc -ldl -o ${OUT:-libgsdfhip.so} && echo "linked ${OUT:-libgsdfhip.so}"
