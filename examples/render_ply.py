@@ -11,7 +11,14 @@ binary STL's of the same mesh, and the weld's device time.
     --report             also print what gsdf_hip_indexed_report says of the mesh (watertight and oriented? shells, volume, area,
                          centre of mass; its device time per stage) and the shell table
     --min-shell-tris N   write the mesh without the shells of fewer than N faces (specks)
-    --drop-cavities      ... and without the shells of negative volume (enclosed cavities)"""
+    --drop-cavities      ... and without the shells of negative volume (enclosed cavities)
+    --simplify K         then merge the vertices of every cell of K x res into one at their mean and drop the faces that collapse
+                         (gsdf_hip_indexed_simplify: vertex clustering, on device)
+    --max-tris N         ... with the first cell of 2 res, 4 res, 8 res, ... that leaves at most N faces (dry runs find it)
+With --simplify / --max-tris, --normals are those of the simplified mesh and --report prints a second report for it. The grid starts
+HALF A RES BELOW the mesh's lattice origin: two of a marching-cubes vertex's three coordinates lie on lattice planes, in floats whose
+last bits depend on which leaf emitted the copy the weld kept (the mesher's order, which varies from run to run); cell faces on
+those planes would let these bits decide the cell, cell faces half-way between them make every run cluster alike."""
 import argparse
 import os
 import sys
@@ -45,6 +52,8 @@ def main(argv=None):
     ap.add_argument("--report", action="store_true", help="print the mesh's report and its shell table")
     ap.add_argument("--min-shell-tris", type=int, default=0, help="drop the shells with fewer faces than this")
     ap.add_argument("--drop-cavities", action="store_true", help="drop the shells of negative volume")
+    ap.add_argument("--simplify", type=float, default=0.0, metavar="K", help="cluster the vertices in cells of K x res")
+    ap.add_argument("--max-tris", type=int, default=0, metavar="N", help="cluster in cells of 2 res, 4 res, ... until at most N faces are left")
     args = ap.parse_args(argv)
 
     import numpy as np
@@ -62,7 +71,8 @@ def main(argv=None):
     t1 = time.perf_counter()
     ix = mesh.weld()
     t2 = time.perf_counter()
-    if args.normals:
+    simplify = args.simplify > 0 or args.max_tris > 0
+    if args.normals and not simplify:
         ix.normals(sdf, np.float32(float(res) * 1e-3))
     if args.report:
         print_report(args.scene, ix)
@@ -72,6 +82,21 @@ def main(argv=None):
         ix = whole.extract(keep)
         print(f"kept {int(keep.sum())} of {len(keep)} shells: V {whole.n_verts} -> {ix.n_verts}, F {whole.n_tris} -> {ix.n_tris} "
               f"(extract {ix.ms_device:.3f} ms device)")
+    if simplify:
+        whole, origin = ix, tuple(np.float32(o) - np.float32(0.5) * res for o in mesh.stats.origin[:])
+        if args.max_tris > 0:
+            ix, ss, cell = whole.simplify_to(args.max_tris, np.float32(2) * res, origin)
+        else:
+            cell = np.float32(args.simplify) * res
+            ix, ss = whole.simplify(cell, origin)
+        print(f"simplified in cells of {float(cell) / float(res):g} res: V {whole.n_verts} -> {ix.n_verts}, F {whole.n_tris} -> {ix.n_tris} "
+              f"({ss.cells} clusters, the largest of {ss.largest_cell} vertices; {ss.collapsed} faces collapsed, {ss.degenerate_in} were degenerate; "
+              f"device {ss.ms_cells + ss.ms_faces:.3f} ms: clusters {ss.ms_cells:.3f}, faces {ss.ms_faces:.3f}; {ss.probes} probes of {ss.table_cells} cells, "
+              f"{ss.attempts} pass)")
+        if args.normals:
+            ix.normals(sdf, np.float32(float(res) * 1e-3))
+        if args.report:
+            print_report(args.scene + " simplified", ix)
     out = args.output or f"{args.scene}.ply"
     data = ix.ply_view()
     with open(out, "wb") as f:

@@ -1,6 +1,7 @@
 // abi_indexed.hip -- C ABI (include/gsdf_hip.h), indexed meshes: the gsdf_indexed handle, the weld of a records mesh, counts /
 // stats / reads, normals, the binary PLY, and the report (edge classes, shells, measures) with the extraction of shells.
-// Kernels: kernels_weld.h (weld, PLY, and the table / scan / remap both passes share), kernels_topo.h (report, extract). No
+// Kernels: kernels_weld.h (weld, PLY, and the table / scan / remap every pass shares), kernels_topo.h (report, extract),
+// kernels_simplify.h (simplify). No
 // interpreter kernel is compiled here: of the meshers this unit needs mesh_march_dense alone, and abi_mesh.hip owns that.
 #include <algorithm>
 #include <cmath>
@@ -8,11 +9,13 @@
 #include <cstring>
 #include <memory>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "kernels_common.h"
 #include "kernels_weld.h"
 #include "kernels_topo.h"
+#include "kernels_simplify.h"
 #include "abi_program.h"
 
 namespace {
@@ -116,15 +119,18 @@ int scan_blocks(hipStream_t s, const PoolBuf& blk_cnt, unsigned n_blocks, const 
 // An inserting pass over an open-addressing table (kernels_weld.h: table_claim) at load <= 0.5: a pass that ends fuller than that, or
 // that gave up on a key, is repeated with twice the cells -- no key is ever dropped. The first size is the power of two >= `want`
 // cells, or >= the value of floor_env where that is set: the tests' way into the growth path. pass(cells) memsets the table and the
-// counters and launches the pass on s; d_head is where that pass's TableCounters are on the device.
-struct TableRun {
+// counters and launches the pass on s; d_head is where that pass's Head is on the device: its TableCounters, or a record that
+// begins with them and goes on with whatever else the host wants to know after the same round trip.
+template <typename Head>
+struct TableRunOf {
   uint64_t cells = 0;
   int attempts = 0;
-  TableCounters head{};
+  Head head{};
 };
-template <typename Pass>
+using TableRun = TableRunOf<TableCounters>;
+template <typename Head, typename Pass>
 int table_build(const char* what, const char* floor_env, uint64_t want, size_t cell_bytes, int dev, hipStream_t s, PoolBuf& table, const void* d_head,
-                Pass pass, TableRun* run) {
+                Pass pass, TableRunOf<Head>* run) {
   if (const char* e = getenv(floor_env)) want = (uint64_t)strtoull(e, nullptr, 10);
   for (uint64_t cells = 1024;; cells <<= 1) {
     if (cells < want) continue;
@@ -134,7 +140,10 @@ int table_build(const char* what, const char* floor_env, uint64_t want, size_t c
     if (int rc = pass(cells)) return rc;
     HIP_TRY(hipMemcpyAsync(&run->head, d_head, sizeof run->head, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    if (!run->head.overflow && run->head.distinct * 2 <= cells) {
+    static_assert(std::is_standard_layout<Head>::value && sizeof(Head) >= sizeof(TableCounters), "a head record begins with its TableCounters");
+    TableCounters tc;
+    std::memcpy(&tc, &run->head, sizeof tc);
+    if (!tc.overflow && tc.distinct * 2 <= cells) {
       run->cells = cells;
       return GSDF_OK;
     }
@@ -417,7 +426,7 @@ static int topo_ensure(gsdf_indexed* ix) {
       }, &run))
     return rc;
   const uint64_t cells = run.cells;
-  LAUNCH(topo_maxbits_kernel, grid_for(3 * V, ix->num_cu, 8), BLOCK, s, ix->verts.p, (unsigned long long)(3 * V), d_ctr);
+  LAUNCH(topo_maxbits_kernel, grid_for(3 * V, ix->num_cu, 8), BLOCK, s, ix->verts.p, (unsigned long long)(3 * V), &d_ctr->maxbits);
   HIP_TRY(hipEventRecord(ev_e.b, s));
   // 2. shells
   HIP_TRY(hipEventRecord(ev_s.a, s));
@@ -574,5 +583,116 @@ extern "C" int gsdf_hip_indexed_extract(gsdf_indexed* ix, const uint8_t* keep_sh
   nx->has_normals = ix->has_normals;
   nx->ms_device = ev.ms();
   *out = nx.release();
+  return GSDF_OK;
+}
+
+// ---- simplify (kernels_simplify.h) -----------------------------------------------------------------------------------------------
+extern "C" int gsdf_hip_indexed_simplify(gsdf_indexed* ix, const gsdf_simplify_opts* o, gsdf_indexed** out, gsdf_simplify_stats* st) {
+  if (out) *out = nullptr;
+  if (!o) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  if (!(o->cell > 0.0f) || !std::isfinite(o->cell)) return fail(GSDF_ERR_BAD_ARGUMENT, "simplify: the cell edge must be positive and finite");
+  if (!std::isfinite(o->origin[0]) || !std::isfinite(o->origin[1]) || !std::isfinite(o->origin[2]))
+    return fail(GSDF_ERR_BAD_ARGUMENT, "simplify: the origin must be finite");
+  if (o->flags != 0) return fail(GSDF_ERR_BAD_ARGUMENT, "simplify: unknown flags " + std::to_string(o->flags));
+  if (!ix || (!out && !st)) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  HIP_TRY(hipSetDevice(ix->device));
+  const int dev = ix->device;
+  hipStream_t s = ix->stream;
+  const bool dry = out == nullptr;
+  const uint64_t V = ix->n_verts, F = ix->n_tris;
+  const unsigned nb_v = blocks_of(V), nb_f = blocks_of(F);
+  const char* nomem = "simplify: no device memory for the workspace";
+  PoolBuf ctr, used, vcell, table, keep, fcell, blk_cnt, blk_base, total, cpos, first, vnum;
+  if (!ctr.take(dev, sizeof(SimplifyCounters)) || !used.take(dev, V * 4) || !vcell.take(dev, V * 4)) return fail(GSDF_ERR_HIP, nomem);
+  SimplifyCounters* d_ctr = ctr.as<SimplifyCounters>();
+  EventPair ev_c, ev_f;
+  if (!ev_c.make() || !ev_f.make()) return fail(GSDF_ERR_HIP, "hipEventCreate failed");
+  // 1. used vertices, the exponent, and the cluster table: per cell the key (8 bytes), the label (4), the record (32), the flag (4);
+  // cells from 2 V: the number of used vertices is known on the device only at this point, V bounds it (and so the clusters) from
+  // above, and asking for 2 V instead of 2 x used saves the round trip that would fetch it
+  HIP_TRY(hipEventRecord(ev_c.a, s));
+  HIP_TRY(hipMemsetAsync(d_ctr, 0, sizeof(SimplifyCounters), s));
+  HIP_TRY(hipMemsetAsync(used.p, 0, V * 4, s));
+  LAUNCH(simplify_mark_kernel, nb_f, BLOCK, s, ix->idx.as<unsigned>(), (unsigned long long)F, used.as<unsigned>(), &d_ctr->head);
+  LAUNCH(topo_maxbits_kernel, grid_for(3 * V, ix->num_cu, 8), BLOCK, s, ix->verts.p, (unsigned long long)(3 * V), &d_ctr->head.maxbits);
+  TableRunOf<SimplifyHead> run;
+  auto tab_key = [&](uint64_t cells) { (void)cells; return table.as<unsigned long long>(); };
+  auto tab_label = [&](uint64_t cells) { return (unsigned*)((uint8_t*)table.p + cells * 8); };
+  auto tab_acc = [&](uint64_t cells) { return (SimplifyCell*)((uint8_t*)table.p + cells * 12); };
+  auto tab_flag = [&](uint64_t cells) { return (unsigned*)((uint8_t*)table.p + cells * 44); };
+  if (int rc = table_build("simplify", "GSDF_HIP_SIMPLIFY_CELLS_MIN", 2 * V, 48, dev, s, table, &d_ctr->head, [&](uint64_t cells) -> int {
+        HIP_TRY(hipMemsetAsync(table.p, 0xff, cells * 12, s));
+        HIP_TRY(hipMemsetAsync((uint8_t*)table.p + cells * 12, 0, cells * 36, s));
+        HIP_TRY(hipMemsetAsync(&d_ctr->head, 0, SIMPLIFY_HEAD_RESET_BYTES, s));
+        LAUNCH(simplify_insert_kernel, grid_for(V, ix->num_cu, 16), BLOCK, s, ix->verts.p, used.as<unsigned>(), (unsigned long long)V, (double)o->origin[0],
+               (double)o->origin[1], (double)o->origin[2], (double)o->cell, tab_key(cells), tab_label(cells), (unsigned)(cells - 1), vcell.as<unsigned>(),
+               &d_ctr->head);
+        return GSDF_OK;
+      }, &run))
+    return rc;
+  const SimplifyHead& hd = run.head;
+  if (hd.nonfinite)
+    return fail(GSDF_ERR_BAD_ARGUMENT, "simplify: " + std::to_string(hd.nonfinite) + " used vertices have a NaN or infinite coordinate");
+  if (hd.out_of_range)
+    return fail(GSDF_ERR_RESOLUTION, "simplify: the cell is too small for this mesh: vertex " + std::to_string(0xffffffffull - hd.first_bad) + " (and " +
+                                         std::to_string(hd.out_of_range - 1) + " more) lies 2^19 cells or more from the origin");
+  const uint64_t cells = run.cells;
+  if (cells > ((uint64_t)1 << 31)) return fail(GSDF_ERR_CAPACITY, "simplify: hash table capacity exceeded");  // (a cell number is 32 bits, all ones = none)
+  const int biased = (int)(hd.maxbits >> 23);
+  const int e = (biased > 1 ? biased : 1) - 126;
+  LAUNCH(simplify_sum_kernel, nb_v, BLOCK, s, ix->verts.p, vcell.as<unsigned>(), (unsigned long long)V, std::ldexp(1.0, 30 - e), tab_acc(cells));
+  HIP_TRY(hipEventRecord(ev_c.b, s));
+  // 2. faces; the cells' positions. (The new handle's stream is made before the events: it is host work.)
+  IndexedPtr nx;
+  if (!dry)
+    if (int rc = indexed_new(dev, ix->num_cu, &nx)) return rc;
+  if (!blk_cnt.take(dev, (size_t)blocks_of(3 * F) * 4) || !blk_base.take(dev, (size_t)blocks_of(3 * F) * 4) ||
+      (!dry && (!keep.take(dev, F) || !fcell.take(dev, 3 * F * 4) || !total.take(dev, 8) || !cpos.take(dev, cells * 12) || !first.take(dev, cells * 4) ||
+                !vnum.take(dev, cells * 4))))
+    return fail(GSDF_ERR_HIP, nomem);
+  HIP_TRY(hipEventRecord(ev_f.a, s));
+  LAUNCH(simplify_faces_kernel, nb_f, BLOCK, s, ix->idx.as<unsigned>(), (unsigned long long)F, vcell.as<unsigned>(), tab_flag(cells),
+         dry ? nullptr : keep.as<unsigned char>(), dry ? nullptr : fcell.as<unsigned>(), blk_cnt.as<unsigned>());
+  LAUNCH(block_scan_kernel, 1, 1024, s, blk_cnt.as<unsigned>(), nb_f, blk_base.as<unsigned>(), &d_ctr->tail.kept);
+  LAUNCH(simplify_place_kernel, grid_for(cells, ix->num_cu, 8), BLOCK, s, tab_key(cells), tab_label(cells), tab_acc(cells), tab_flag(cells),
+         (unsigned long long)cells, ix->verts.p, std::ldexp(1.0, e - 30), dry ? nullptr : cpos.p, &d_ctr->tail);
+  SimplifyTail tl{};
+  HIP_TRY(hipMemcpyAsync(&tl, &d_ctr->tail, sizeof tl, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  const uint64_t F2 = tl.kept;
+  if (hd.degenerate + F2 > F) return fail(GSDF_ERR_HIP, "simplify: internal error (the face counts do not add up)");
+  uint64_t V2 = 0;
+  if (!dry) {
+    if (F2 == 0) return fail(GSDF_ERR_EMPTY_BUFFERS, "simplify: nothing kept (every face collapsed: the cell is too large for this mesh)");
+    const uint64_t S2 = 3 * F2;
+    const unsigned nb_s = blocks_of(S2);
+    if (!nx->idx.take(dev, S2 * 4)) return fail(GSDF_ERR_HIP, nomem);
+    // extract's kernels, the table's cell standing for the old vertex: kept faces in order, clusters by their smallest kept slot
+    HIP_TRY(hipMemsetAsync(first.p, 0xff, cells * 4, s));
+    LAUNCH(topo_compact_kernel, nb_f, BLOCK, s, fcell.as<unsigned>(), keep.as<unsigned char>(), (unsigned long long)F, blk_base.as<unsigned>(),
+           nx->idx.as<unsigned>(), first.as<unsigned>());
+    LAUNCH(topo_owner_kernel, nb_s, BLOCK, s, nx->idx.as<unsigned>(), (unsigned long long)S2, first.as<unsigned>(), blk_cnt.as<unsigned>());
+    if (int rc = scan_blocks(s, blk_cnt, nb_s, blk_base, total, &V2)) return rc;
+    if (V2 != tl.named) return fail(GSDF_ERR_HIP, "simplify: internal error (kept clusters)");
+    if (!nx->verts.take(dev, V2 * 12) || !nx->vkeys.take(dev, V2 * 8)) return fail(GSDF_ERR_HIP, nomem);
+    LAUNCH(topo_renumber_kernel, nb_s, BLOCK, s, nx->idx.as<unsigned>(), (unsigned long long)S2, first.as<unsigned>(), blk_base.as<unsigned>(), vnum.as<unsigned>(),
+           cpos.as<unsigned>(), tab_key(cells), (const unsigned*)nullptr, nx->verts.as<unsigned>(), nx->vkeys.as<unsigned long long>(), (unsigned*)nullptr);
+    LAUNCH(remap_kernel, nb_s, BLOCK, s, nx->idx.as<unsigned>(), (unsigned long long)S2, vnum.as<unsigned>());
+  }
+  HIP_TRY(hipEventRecord(ev_f.b, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  const uint64_t n_collapsed = F - hd.degenerate - F2;
+  gsdf_simplify_stats r{};
+  r.n_verts_in = V; r.n_tris_in = F; r.used_verts_in = hd.used; r.degenerate_in = hd.degenerate; r.cells = hd.tab.distinct; r.collapsed = n_collapsed;
+  r.n_verts = tl.named; r.n_tris = F2; r.largest_cell = tl.largest; r.exponent = e;
+  r.ms_cells = ev_c.ms(); r.ms_faces = ev_f.ms();
+  r.probes = hd.tab.probes; r.table_cells = cells; r.attempts = run.attempts;
+  if (st) *st = r;
+  if (!dry) {
+    nx->n_verts = V2;
+    nx->n_tris = F2;
+    nx->ms_device = r.ms_cells + r.ms_faces;
+    *out = nx.release();
+  }
   return GSDF_OK;
 }

@@ -71,8 +71,10 @@ __device__ __forceinline__ TopoWave topo_wave(unsigned shell) {
   }
   return w;
 }
-// Every lane of the wave calls these (they shuffle).
-__device__ __forceinline__ void topo_count(const TopoWave& w, unsigned shell, bool flag, TopoShellAcc* acc, unsigned field) {
+// Every lane of the wave calls these (they shuffle). Acc: a record of 64-bit words (TopoShellAcc; kernels_simplify.h: SimplifyCell, with the
+// table's cell where the report has the shell), `field` the word's index in it.
+template <typename Acc>
+__device__ __forceinline__ void topo_count(const TopoWave& w, unsigned shell, bool flag, Acc* acc, unsigned field) {
   if (w.s0 == TOPO_NONE) return;
   flag = flag && shell != TOPO_NONE;
   if (w.uniform) {
@@ -82,7 +84,8 @@ __device__ __forceinline__ void topo_count(const TopoWave& w, unsigned shell, bo
     atomicAdd((unsigned long long*)&acc[shell] + field, 1ull);
   }
 }
-__device__ __forceinline__ void topo_add(const TopoWave& w, unsigned shell, unsigned long long v, TopoShellAcc* acc, unsigned field) {
+template <typename Acc>
+__device__ __forceinline__ void topo_add(const TopoWave& w, unsigned shell, unsigned long long v, Acc* acc, unsigned field) {
   if (w.s0 == TOPO_NONE) return;
   if (shell == TOPO_NONE) v = 0ull;
   if (w.uniform) {
@@ -122,7 +125,7 @@ __device__ __forceinline__ void topo_minmax(const TopoWave& w, unsigned shell, u
 }
 
 // ---- the exponent ----------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(BLOCK) topo_maxbits_kernel(const float* __restrict__ verts, unsigned long long n, TopoCounters* __restrict__ ctr) {
+__global__ void __launch_bounds__(BLOCK) topo_maxbits_kernel(const float* __restrict__ verts, unsigned long long n, unsigned long long* __restrict__ maxbits) {
   unsigned m = 0;
   const unsigned long long step = (unsigned long long)gridDim.x * BLOCK;
   for (unsigned long long i = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x; i < n; i += step) {
@@ -134,7 +137,7 @@ __global__ void __launch_bounds__(BLOCK) topo_maxbits_kernel(const float* __rest
     const unsigned o = __shfl_down(m, off, 64);
     m = o > m ? o : m;
   }
-  if ((threadIdx.x & 63u) == 0u && m) atomicMax(&ctr->maxbits, (unsigned long long)m);
+  if ((threadIdx.x & 63u) == 0u && m) atomicMax(maxbits, (unsigned long long)m);
 }
 
 // ---- the edge table ----------------------------------------------------------------------------------------------------------------

@@ -28,7 +28,8 @@ SYMBOLS = ["gsdf_hip_last_error", "gsdf_hip_init", "gsdf_hip_program_create", "g
            "gsdf_hip_mesh_payload", "gsdf_hip_mesh_march", "gsdf_hip_mesh_stage_ms", "gsdf_hip_mesh_octree_start", "gsdf_hip_mesh_octree_wait", "gsdf_hip_comm_transport", "gsdf_hip_gather_plan",
            "gsdf_hip_mesh_read_records", "gsdf_hip_mesh_weld", "gsdf_hip_indexed_counts", "gsdf_hip_indexed_stats_get", "gsdf_hip_indexed_read",
            "gsdf_hip_indexed_normals", "gsdf_hip_indexed_read_normals", "gsdf_hip_indexed_ply", "gsdf_hip_indexed_host_ply", "gsdf_hip_indexed_destroy",
-           "gsdf_hip_indexed_create", "gsdf_hip_indexed_report", "gsdf_hip_indexed_shells", "gsdf_hip_indexed_read_shell_of", "gsdf_hip_indexed_extract"]
+           "gsdf_hip_indexed_create", "gsdf_hip_indexed_report", "gsdf_hip_indexed_shells", "gsdf_hip_indexed_read_shell_of", "gsdf_hip_indexed_extract",
+           "gsdf_hip_indexed_simplify"]
 
 
 PRUNE_ASSUME_SDF = 1 << 30  # gsdf_hip.h: GSDF_PRUNE_ASSUME_SDF
@@ -90,6 +91,25 @@ class IndexedReport(C.Structure):
                 ("ms_edges", C.c_double), ("ms_shells", C.c_double), ("ms_measure", C.c_double), ("probes", C.c_uint64), ("table_cells", C.c_uint64),
                 ("attempts", C.c_int32), ("reserved", C.c_int32)]
     RESULT_BYTES = 160
+
+    def result_bytes(self):
+        return bytes(self)[:self.RESULT_BYTES]
+
+
+class SimplifyOpts(C.Structure):
+    """gsdf_simplify_opts (gsdf_hip.h): the clustering grid's cell edge and origin."""
+    _fields_ = [("cell", C.c_float), ("origin", C.c_float * 3), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class SimplifyStats(C.Structure):
+    """gsdf_simplify_stats (gsdf_hip.h): what a simplification by vertex clustering did; bytes 0 .. 79 (RESULT_BYTES) are a function of
+    the mesh and the options alone, the rest says what the run cost."""
+    _fields_ = [("n_verts_in", C.c_uint64), ("n_tris_in", C.c_uint64), ("used_verts_in", C.c_uint64), ("degenerate_in", C.c_uint64),
+                ("cells", C.c_uint64), ("collapsed", C.c_uint64), ("n_verts", C.c_uint64), ("n_tris", C.c_uint64), ("largest_cell", C.c_uint64),
+                ("exponent", C.c_int32), ("reserved", C.c_int32),
+                ("ms_cells", C.c_double), ("ms_faces", C.c_double), ("probes", C.c_uint64), ("table_cells", C.c_uint64),
+                ("attempts", C.c_int32), ("reserved2", C.c_int32)]
+    RESULT_BYTES = 80
 
     def result_bytes(self):
         return bytes(self)[:self.RESULT_BYTES]
@@ -215,6 +235,7 @@ def lib():
         L.gsdf_hip_indexed_shells.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         L.gsdf_hip_indexed_read_shell_of.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.gsdf_hip_indexed_extract.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+        L.gsdf_hip_indexed_simplify.argtypes = [C.c_void_p, C.POINTER(SimplifyOpts), C.POINTER(C.c_void_p), C.POINTER(SimplifyStats)]
         L.gsdf_hip_brick_owner.restype = C.c_uint32
         L.gsdf_hip_brick_owner.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         L.gsdf_hip_slab_range.restype = None
@@ -733,6 +754,29 @@ class IndexedHIP:
         h = C.c_void_p()
         _check(lib().gsdf_hip_indexed_extract(self._h, None if k is None else k.ctypes.data, 1 if drop_degenerate else 0, C.byref(h)))
         return IndexedHIP(h)
+
+    def simplify(self, cell, origin=(0, 0, 0), dry=False):
+        """gsdf_hip_indexed_simplify: the mesh with the used vertices of every grid cell (edge `cell`, cell (0, 0, 0) starting at
+        `origin`) merged into one vertex at their mean and the collapsed faces dropped: (a new IndexedHIP, SimplifyStats). dry: the
+        stats alone, (None, SimplifyStats), at the cost of the clustering and one pass over the faces."""
+        o = SimplifyOpts(cell=np.float32(cell), origin=(C.c_float * 3)(*[np.float32(x) for x in origin]))
+        st, h = SimplifyStats(), C.c_void_p()
+        _check(lib().gsdf_hip_indexed_simplify(self._h, C.byref(o), None if dry else C.byref(h), C.byref(st)))
+        return (None if dry else IndexedHIP(h)), st
+
+    def simplify_to(self, max_tris, cell0, origin=(0, 0, 0)):
+        """The first of cell0, 2 cell0, 4 cell0, ... (float32 doubling: exact) whose simplification has at most max_tris faces, found by
+        dry runs; then that mesh: (IndexedHIP, SimplifyStats, cell). ValueError after 24 doublings, or once nothing would be kept."""
+        cell = np.float32(cell0)
+        for _ in range(25):
+            _, st = self.simplify(cell, origin, dry=True)
+            if st.n_tris == 0:
+                raise ValueError(f"simplify_to: nothing is kept at cell {float(cell)!r}, and every smaller cell tried keeps more than {max_tris} faces")
+            if st.n_tris <= max_tris:
+                ix, st = self.simplify(cell, origin)
+                return ix, st, cell
+            cell = np.float32(cell * np.float32(2))
+        raise ValueError(f"simplify_to: more than {max_tris} faces after 24 doublings of the cell {float(np.float32(cell0))!r}")
 
     def select_shells(self, min_tris=0, drop_cavities=False):
         """A keep mask for extract() from the shell table: shells with at least min_tris faces and, with drop_cavities, a volume

@@ -603,6 +603,86 @@ int gsdf_hip_indexed_shells(gsdf_indexed* ix, gsdf_shell* dst, uint64_t cap, uin
 int gsdf_hip_indexed_read_shell_of(gsdf_indexed* ix, uint32_t* shell_of_vertex, uint32_t* shell_of_face);
 int gsdf_hip_indexed_extract(gsdf_indexed* ix, const uint8_t* keep_shell, int drop_degenerate, gsdf_indexed** out);
 
+/* ---- indexed meshes: simplify (no reference counterpart) --------------------------------------------------------------------------
+ *
+ * A smaller mesh by VERTEX CLUSTERING: the used vertices fall into the cells of a cubic grid, the vertices of one cell become one
+ * vertex at their mean, and the faces that still have three distinct corners are kept. Marching cubes tessellates a flat face as
+ * finely as a thread flank and its vertices sit on lattice edges (features are bevelled at the scale of res already), so cells of
+ * a few res are the natural first simplifier for these meshes. The result is a function of the mesh and the options alone, to the
+ * bit: not of the order in which threads arrive, and (as a set of keyed vertices and of faces over keys) not of the order of the
+ * faces or the numbering of the vertices. Kernels: gsdf_amd/csrc/kernels_simplify.h (abi_indexed.hip); a numpy restatement:
+ * tests/simplifyref.py.
+ *
+ * Input. Any gsdf_indexed handle (welded, extracted, or uploaded with gsdf_hip_indexed_create) and gsdf_simplify_opts: cell > 0 and
+ *   finite, origin finite, flags == 0 -- anything else is GSDF_ERR_BAD_ARGUMENT, checked before the handle is looked at.
+ *   For a WELDED mesh choose an origin off the lattice planes, such as the lattice origin minus res / 2 with a cell of K res
+ *   (examples/render_ply.py does): two of a marching-cubes vertex's three coordinates lie on lattice planes, in floats whose last bits
+ *   depend on which leaf's copy the weld kept, i.e. on the mesher's record order, which differs from run to run. With cell faces on
+ *   those planes these bits would decide the cell -- exactly as the contract says, and differently for the next run's mesh.
+ * Used vertices. A vertex is USED if a non-degenerate face names it; a face is DEGENERATE if two of its indices are equal (the
+ *   report's definitions). Only used vertices take part.
+ * Non-finite coordinates. A used vertex with a NaN or infinite coordinate: GSDF_ERR_BAD_ARGUMENT, the text gives the number of such
+ *   vertices. (A non-finite vertex that no non-degenerate face names is ignored.)
+ * Cell of a vertex. Per coordinate k, c_k = floor(((double)x_k - (double)origin_k) / (double)cell): two IEEE float64 operations and
+ *   a floor, nothing contracted. Some |c_k| >= 2^19: GSDF_ERR_RESOLUTION, the text names the smallest such vertex.
+ * Key. (c_x + 2^19) | (c_y + 2^19) << 20 | (c_z + 2^19) << 40 | 4 << 60: kind 4, after the weld's kinds 0 .. 3. Its top four bits
+ *   are 0100, so it is never the hash table's empty value (all ones).
+ * Clusters. A cluster is the set of used vertices with one key; n its size. n == 1: the cluster's position is that vertex's, bit for
+ *   bit. n > 1: with e the report's `exponent` (over ALL finite coordinates of the handle's V vertices, used or not),
+ *     q_k = rint((double)x_k * 2^(30-e))                 exact scaling, ties to even; |q_k| <= 2^30
+ *     S_k = the INTEGER sum of q_k over the cluster      |S_k| <= 2^62 for V < 2^32: an int64
+ *     position_k = (float)(((double)S_k / (double)n) * 2^(e-30))
+ *   -- one conversion of S_k to float64, one division, an exact scaling, one rounding to float32. The sums being integer sums, any
+ *   order of atomics and any reduction tree give the same bytes. Error of the quantisation: |q_k 2^(e-30) - x_k| <= 2^(e-31) per
+ *   member, hence at most 2^(e-31) for the mean per coordinate: 1/128 of a float32 ulp at magnitude 2^e (ulp 2^(e-24) in
+ *   [2^(e-1), 2^e)). Derived, not measured.
+ * Faces. Degenerate input faces are dropped. A non-degenerate face whose three vertices fall into fewer than three distinct clusters
+ *   is COLLAPSED and dropped. Every other face is kept, in the original order, each corner replaced by its cluster. Clustering can
+ *   make two kept faces equal or opposite (a thin wall inside one layer of cells): such faces are KEPT, nothing is deduplicated,
+ *   and gsdf_hip_indexed_report on the result tells the truth about them (non-manifold / misoriented edges).
+ * Vertices of the result. The clusters a kept face names, numbered by the smallest slot 3 g + c (g: the face's position among the
+ *   kept faces) that names them, in increasing order -- the weld's and extract's rule. A vertex's key is its cluster's key. Normals
+ *   are not carried (has_normals == 0): ask for them again on the result. Unlike extract, positions are new, so the result's own
+ *   exponent may be smaller than the input's.
+ * Nothing kept: GSDF_ERR_EMPTY_BUFFERS.
+ *
+ * gsdf_hip_indexed_simplify(ix, o, out, st): *out = a new, independent handle; st (optional) = the stats. out == NULL with st != NULL
+ *   is a DRY RUN: the same stats, no handle built, GSDF_OK with n_tris == 0 where nothing would be kept; it costs the clustering and
+ *   one counting pass over the faces. Both NULL: GSDF_ERR_BAD_ARGUMENT. On an error *out is NULL and *st is not written.
+ * gsdf_simplify_stats. Bytes 0 .. 79 (n_verts_in .. reserved) are a function of the mesh and the options alone; the rest says what
+ *   this run cost. GSDF_HIP_SIMPLIFY_CELLS_MIN (environment) lowers the cluster table's first size so that tests can drive the
+ *   grow-and-repeat path, as GSDF_HIP_TOPO_CELLS_MIN does.
+ * Not done here: adaptive (quadric edge-collapse) simplification, QEF placement of the representative, projecting it back onto the
+ *   field, removing duplicate or opposite faces. */
+typedef struct gsdf_simplify_opts {
+  float cell;        /* cell edge, > 0 and finite */
+  float origin[3];   /* where cell (0, 0, 0) starts; finite */
+  uint32_t flags;    /* 0; others refused */
+  uint32_t reserved[3];
+} gsdf_simplify_opts;
+GSDF_ABI_ASSERT(sizeof(gsdf_simplify_opts) == 32, "gsdf_simplify_opts is 32 bytes");
+GSDF_ABI_ASSERT(offsetof(gsdf_simplify_opts, origin) == 4 && offsetof(gsdf_simplify_opts, flags) == 16, "gsdf_simplify_opts fields");
+typedef struct gsdf_simplify_stats {
+  uint64_t n_verts_in, n_tris_in;
+  uint64_t used_verts_in, degenerate_in;
+  uint64_t cells;          /* clusters: distinct keys of the used vertices */
+  uint64_t collapsed;      /* non-degenerate faces with fewer than three distinct clusters */
+  uint64_t n_verts, n_tris; /* of the result: clusters a kept face names; n_tris_in - degenerate_in - collapsed */
+  uint64_t largest_cell;   /* the largest n */
+  int32_t exponent;        /* e of the contract */
+  int32_t reserved;
+  double ms_cells;         /* device time, HIP events: used marks, exponent, cluster table (all attempts), sums */
+  double ms_faces;         /* face pass, positions; compaction, numbering, remap (not in a dry run) */
+  uint64_t probes;         /* table cells inspected by the inserting pass that succeeded */
+  uint64_t table_cells;    /* its capacity (a power of two, >= 2 cells) */
+  int32_t attempts;        /* inserting passes run */
+  int32_t reserved2;
+} gsdf_simplify_stats;
+GSDF_ABI_ASSERT(sizeof(gsdf_simplify_stats) == 120, "gsdf_simplify_stats is 120 bytes");
+GSDF_ABI_ASSERT(offsetof(gsdf_simplify_stats, cells) == 32 && offsetof(gsdf_simplify_stats, n_verts) == 48, "gsdf_simplify_stats counts");
+GSDF_ABI_ASSERT(offsetof(gsdf_simplify_stats, exponent) == 72 && offsetof(gsdf_simplify_stats, ms_cells) == 80, "gsdf_simplify_stats cost");
+int gsdf_hip_indexed_simplify(gsdf_indexed* ix, const gsdf_simplify_opts* o, gsdf_indexed** out, gsdf_simplify_stats* st);
+
 /* ---- multi-GPU (one process per GPU). The meshers shard with NO data-path collective (shard_rank / shard_count above); the
  * one exchange is the final variable-length gather of the ranks' results, over xGMI, inside this library: a Go caller needs no
  * Python for it. Replaces nothing in the reference (single device; its analogue of the split is the goroutine split of

@@ -178,6 +178,46 @@ func (ix *IndexedHIP) Extract(keep []bool, dropDegenerate bool) (*IndexedHIP, er
 	return nx, nil
 }
 
+// SimplifyStats is gsdf_simplify_stats: what a simplification by vertex clustering did, and its device time.
+type SimplifyStats struct {
+	VIn, FIn, UsedVIn, DegenerateIn uint64
+	Clusters, Collapsed, V, F       uint64
+	LargestCluster                  uint64
+	ClustersMillis, FacesMillis     float64
+}
+
+// Simplify returns a new, independent mesh in which the used vertices of every cell of a cubic grid (edge cell, cell (0, 0, 0)
+// starting at origin) are merged into one vertex at their mean and the faces that collapse are dropped (gsdf_hip.h states every
+// term). With dry set nothing is built: the mesh returned is nil and the stats say what the result would be.
+func (ix *IndexedHIP) Simplify(cell float32, origin ms3.Vec, dry bool) (*IndexedHIP, SimplifyStats, error) {
+	opts := C.gsdf_simplify_opts{cell: C.float(cell)}
+	opts.origin[0], opts.origin[1], opts.origin[2] = C.float(origin.X), C.float(origin.Y), C.float(origin.Z)
+	var st C.gsdf_simplify_stats
+	var h *C.gsdf_indexed
+	out := &h
+	if dry {
+		out = nil
+	}
+	if rc := C.gsdf_hip_indexed_simplify(ix.h, &opts, out, &st); rc != 0 {
+		return nil, SimplifyStats{}, hipErr(rc)
+	}
+	stats := SimplifyStats{
+		VIn: uint64(st.n_verts_in), FIn: uint64(st.n_tris_in), UsedVIn: uint64(st.used_verts_in), DegenerateIn: uint64(st.degenerate_in),
+		Clusters: uint64(st.cells), Collapsed: uint64(st.collapsed), V: uint64(st.n_verts), F: uint64(st.n_tris),
+		LargestCluster: uint64(st.largest_cell),
+		ClustersMillis: float64(st.ms_cells), FacesMillis: float64(st.ms_faces),
+	}
+	if dry {
+		return nil, stats, nil
+	}
+	nx := &IndexedHIP{h: h}
+	var nv, nf C.uint64_t
+	var ms C.double
+	C.gsdf_hip_indexed_counts(h, &nv, &nf, &ms)
+	nx.V, nx.F, nx.WeldMillis = uint64(nv), uint64(nf), float64(ms)
+	return nx, stats, nil
+}
+
 // Close frees the device and pinned host buffers of the mesh.
 func (ix *IndexedHIP) Close() {
 	if ix.h != nil {
