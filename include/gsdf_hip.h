@@ -433,7 +433,9 @@ int gsdf_hip_mesh_march(gsdf_mesh* m);
 int gsdf_hip_mesh_read(const gsdf_mesh* m, uint64_t first, uint64_t count, float* dst);
 /* Device pointer to the triangle array (for RCCL gathers / further device work). */
 const float* gsdf_hip_mesh_dev_tris(const gsdf_mesh* m);
-/* Binary STL (84 + 50*n bytes) built on device into dst (host). dst_cap must be >= that size. */
+/* Binary STL (84 + 50*n bytes) built on device into dst (host). dst_cap must be >= that size. A zero-area triangle's normal is
+ * NaN in all three components (Inf * 0, as glrender/stl.go computes it), with unspecified sign and payload: the reference's own
+ * differ between amd64 and arm64. Vertex bytes and the attribute word are the reference's for every triangle. */
 int gsdf_hip_mesh_stl(const gsdf_mesh* m, uint8_t* dst, size_t dst_cap);
 /* Zero-copy result views (no reference counterpart: the reference drains a renderer through ReadTriangles into a
  * 4096-triangle buffer and appends, glrender/glrender.go:20-36, and WriteBinarySTL issues one Write per triangle,
