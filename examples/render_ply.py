@@ -15,7 +15,13 @@ binary STL's of the same mesh, and the weld's device time.
     --simplify K         then merge the vertices of every cell of K x res into one at their mean and drop the faces that collapse
                          (gsdf_hip_indexed_simplify: vertex clustering, on device)
     --max-tris N         ... with the first cell of 2 res, 4 res, 8 res, ... that leaves at most N faces (dry runs find it)
-With --simplify / --max-tris, --normals are those of the simplified mesh and --report prints a second report for it. The grid starts
+    --project [ITERS]    then move every vertex onto the part's surface by up to ITERS (8) Newton steps along the field's gradient
+                         (gsdf_hip_indexed_project, on device: step res / 4, on the surface within res / 1024, never further than the
+                         simplify cell -- or res -- from where it was): clustering pulls the surface inwards on every convex part
+    --before-project F   with --project: also write the mesh as it was before the projection to F (the same faces, byte for byte)
+With --simplify / --max-tris, --normals are those of the simplified mesh and --report prints a second report for it; with --project
+they are those of the projected mesh, and --report also prints how far the vertices were from the surface before and after, and
+the projected mesh's report: its volume is the point of the exercise. The grid starts
 HALF A RES BELOW the mesh's lattice origin: two of a marching-cubes vertex's three coordinates lie on lattice planes, in floats whose
 last bits depend on which leaf emitted the copy the weld kept (the mesher's order, which varies from run to run); cell faces on
 those planes would let these bits decide the cell, cell faces half-way between them make every run cluster alike."""
@@ -54,7 +60,11 @@ def main(argv=None):
     ap.add_argument("--drop-cavities", action="store_true", help="drop the shells of negative volume")
     ap.add_argument("--simplify", type=float, default=0.0, metavar="K", help="cluster the vertices in cells of K x res")
     ap.add_argument("--max-tris", type=int, default=0, metavar="N", help="cluster in cells of 2 res, 4 res, ... until at most N faces are left")
+    ap.add_argument("--project", type=int, nargs="?", const=8, default=None, metavar="ITERS", help="move the vertices onto the surface by up to ITERS (8) Newton steps")
+    ap.add_argument("--before-project", default=None, metavar="F", help="with --project: also write the mesh before the projection to F")
     args = ap.parse_args(argv)
+    if args.before_project and args.project is None:
+        ap.error("--before-project needs --project")
 
     import numpy as np
     from gsdf_amd import hip
@@ -72,7 +82,8 @@ def main(argv=None):
     ix = mesh.weld()
     t2 = time.perf_counter()
     simplify = args.simplify > 0 or args.max_tris > 0
-    if args.normals and not simplify:
+    project = args.project is not None
+    if args.normals and not simplify and not project:
         ix.normals(sdf, np.float32(float(res) * 1e-3))
     if args.report:
         print_report(args.scene, ix)
@@ -93,10 +104,26 @@ def main(argv=None):
               f"({ss.cells} clusters, the largest of {ss.largest_cell} vertices; {ss.collapsed} faces collapsed, {ss.degenerate_in} were degenerate; "
               f"device {ss.ms_cells + ss.ms_faces:.3f} ms: clusters {ss.ms_cells:.3f}, faces {ss.ms_faces:.3f}; {ss.probes} probes of {ss.table_cells} cells, "
               f"{ss.attempts} pass)")
-        if args.normals:
+        if args.normals and not project:
             ix.normals(sdf, np.float32(float(res) * 1e-3))
         if args.report:
             print_report(args.scene + " simplified", ix)
+    if project:
+        before = ix
+        if args.before_project:
+            with open(args.before_project, "wb") as f:
+                f.write(before.ply_view())
+        ix, ps = before.project(sdf, res / np.float32(4), res / np.float32(1024), cell if simplify else res, args.project)
+        counts = ", ".join(f"{n.lower()} {ps.count[k]}" for k, n in enumerate(hip.PROJECT_STATUS) if ps.count[k])
+        print(f"projected onto the field in up to {args.project} steps: {counts}; {ps.evals} evaluations, at most {ps.steps_max} steps per vertex, "
+              f"device {ps.ms_device:.3f} ms")
+        if args.normals:
+            ix.normals(sdf, np.float32(float(res) * 1e-3))
+        if args.report:
+            print(f"{args.scene} deviation: max |d| {ps.max_abs_before:.6g} -> {ps.max_abs_after:.6g} ({ps.max_abs_before / float(res):.4g} -> "
+                  f"{ps.max_abs_after / float(res):.4g} res); vertices further than res / 1024 from the surface {ps.over_tol_before} -> {ps.over_tol_after} "
+                  f"of {ps.n_verts}")
+            print_report(args.scene + " projected", ix)
     out = args.output or f"{args.scene}.ply"
     data = ix.ply_view()
     with open(out, "wb") as f:

@@ -1,7 +1,7 @@
 // abi_eval.hip -- C ABI (include/gsdf_hip.h), evaluator side: program handles and their run-time specialisation, the
 // gleval.SDF3 / SDF2 Evaluate drop-ins (host buffers, pipelined tickets, registered memory, device-resident), central-difference
 // normals, the 2-D image renderer and its colour conversions, the UI's view of a 3-D part, the block cache. Kernels: kernels_eval.h,
-// kernels_image.h and kernels_view.h over the interpreter of interp.h.
+// kernels_image.h, kernels_view.h and kernels_project.h over the interpreter of interp.h.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -15,6 +15,7 @@
 #include "kernels_common.h"
 #include "kernels_eval.h"
 #include "kernels_view.h"
+#include "kernels_project.h"
 #include "kernels_image.h"
 #include "abi_program.h"
 
@@ -323,6 +324,19 @@ void spec_view(gsdf_program* p) {
   }
 }
 
+// project_kernel (kernels_project.h) for a specialised handle: built at its first projection, in a module of its own that includes
+// kernels_common.h and kernels_project.h only (specialize.cpp: spec_includes). If it fails to build or needs scratch the interpreter
+// kernel stays in use.
+void spec_project(gsdf_program* p) {
+  if (!p->spec_mod || p->spec_project_tried || p->prog.is2d) return;
+  p->spec_project_tried = true;
+  std::vector<hipFunction_t> f;
+  if (spec_build(p, {"project_kernel"}, &p->spec_mod_project, f, &p->spec_compile_s) != GSDF_OK) return;
+  const bool ok = fn_scratch_bytes(f[0]) == 0;
+  spec_report("specialised", "project_kernel", f[0], ok);
+  p->f_project = ok ? f[0] : nullptr;
+}
+
 // image2_color_kernel<k, kind> for every conversion kind (kernels_image.h), for a specialised 2-D handle: built at its first picture,
 // in a module of its own (specialize.cpp: spec_includes). A kernel that fails to build or needs scratch stays on the interpreter kernel.
 void spec_image_color(gsdf_program* p) {
@@ -552,6 +566,8 @@ extern "C" int gsdf_hip_program_kernels(const gsdf_program* p, char* dst, size_t
     snprintf(buf + strlen(buf), sizeof buf - strlen(buf), " picture=image2_color_kernel<%d,kind>:%s", ek,
              kinds.empty() ? "interpreter" : ("specialised/" + kinds).c_str());
   }
+  if (!p->prog.is2d && strlen(buf) + 48 < sizeof buf)  // the projection of mesh vertices (a specialised handle builds its own at its first projection)
+    snprintf(buf + strlen(buf), sizeof buf - strlen(buf), " project=project_kernel:%s", p->f_project ? "specialised" : "interpreter");
   if (p->spec_mod && strlen(buf) + 32 < sizeof buf) { strcat(buf, " compiler="); strcat(buf, p->spec_compiler.c_str()); }
   {  // identity of the code that runs: a stored profile describes this handle's kernels only if it carries the same key
     const std::string key = p->spec_mod ? p->spec_key : gsdf_dev::spec_library_key();
@@ -646,6 +662,9 @@ extern "C" void gsdf_hip_program_destroy(gsdf_program* p) {
   if (p->spec_mod_k1) (void)hipModuleUnload(p->spec_mod_k1);
   if (p->spec_mod_dense) (void)hipModuleUnload(p->spec_mod_dense);
   if (p->spec_mod_view) (void)hipModuleUnload(p->spec_mod_view);
+  if (p->spec_mod_project) (void)hipModuleUnload(p->spec_mod_project);
+  if (p->proj_ctr) (void)hipFree(p->proj_ctr);
+  for (auto ev1 : p->ev_proj) if (ev1) (void)hipEventDestroy(ev1);
   if (p->spec_mod_imgc) (void)hipModuleUnload(p->spec_mod_imgc);
   p->q0.release(); p->q1.release(); p->ctr.release();
   p->rec.release(); p->hdr.release(); p->grp.release();
@@ -984,6 +1003,57 @@ int normals3_dev(gsdf_program* p, const float* d_pos, float* d_nrm, size_t n, fl
   }
   HIP_TRY(hipStreamSynchronize(p->stream));
   p->evals += 6 * n;
+  return GSDF_OK;
+}
+
+// gsdf_hip_indexed_project's kernel on device-resident points (abi_program.h): project_kernel over the interpreter, or the handle's
+// specialised build of it. One launch: the counters (the handle's, made at its first projection, as are the two events) are cleared on
+// the stream in front of it and read behind it. One projection per program at a time, like every call on the handle's stream.
+int project_dev(gsdf_program* p, const float* d_pos, size_t n, const gsdf_project_opts* o, float* d_out_pos, float* d_before, float* d_after,
+                uint8_t* d_status, gsdf_project_stats* st) {
+  if (n == 0) return fail(GSDF_ERR_EMPTY_BUFFERS, "empty buffers");
+  if (n >= ((size_t)1 << 32)) return fail(GSDF_ERR_CAPACITY, "project: vertices must stay below 2^32");
+  if (p->prog.is2d) return fail(GSDF_ERR_DIMENSION, "program is 2D");
+  HIP_TRY(hipSetDevice(p->device));
+  spec_adopt(p);
+  spec_project(p);
+  if (!p->proj_ctr) HIP_TRY(hipMalloc(&p->proj_ctr, sizeof(ProjectCounters)));
+  for (hipEvent_t& ev1 : p->ev_proj)
+    if (!ev1) HIP_TRY(hipEventCreate(&ev1));
+  hipEvent_t* ev = p->ev_proj;
+  ProjectCounters* d_ctr = (ProjectCounters*)p->proj_ctr;
+  ProjectCounters hc{};
+  float ms = 0.f;
+  const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
+  const float h = o->step * 0.5f;
+  hipError_t e = hipMemsetAsync(d_ctr, 0, sizeof(ProjectCounters), p->stream);
+  if (e == hipSuccess) e = hipEventRecord(ev[0], p->stream);
+  if (e == hipSuccess) {
+    if (p->f_project)
+      e = launch_fn(p->f_project, grid, BLOCK, p->lds_bytes(2), p->stream, (const uint32_t*)p->d_code, (const unsigned*)d_pos, (uint64_t)n, h, (float)o->tol,
+                    (float)o->max_move, (int)o->max_iters, (unsigned*)d_out_pos, d_before, d_after, (unsigned char*)d_status, d_ctr);
+    else {
+      hipLaunchKernelGGL(project_kernel, dim3(grid), dim3(BLOCK), p->lds_bytes(2), p->stream, p->d_code, (const unsigned*)d_pos, (uint64_t)n, h, o->tol, o->max_move,
+                         (int)o->max_iters, (unsigned*)d_out_pos, d_before, d_after, (unsigned char*)d_status, d_ctr);
+      e = hipGetLastError();
+    }
+  }
+  if (e == hipSuccess) e = hipEventRecord(ev[1], p->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(&hc, d_ctr, sizeof hc, hipMemcpyDeviceToHost, p->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
+  else (void)hipStreamSynchronize(p->stream);
+  if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+  if (e != hipSuccess) return fail(GSDF_ERR_HIP, std::string("project: ") + hipGetErrorString(e));
+  p->evals += hc.evals;
+  gsdf_project_stats r{};
+  r.n_verts = n;
+  for (int k = 0; k < 8; k++) r.count[k] = hc.count[k];
+  r.evals = hc.evals; r.over_tol_before = hc.over_before; r.over_tol_after = hc.over_after;
+  std::memcpy(&r.max_abs_before, &hc.max_before, 4);
+  std::memcpy(&r.max_abs_after, &hc.max_after, 4);
+  r.steps_max = hc.steps_max;
+  r.ms_device = (double)ms;
+  *st = r;
   return GSDF_OK;
 }
 

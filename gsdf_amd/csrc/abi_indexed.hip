@@ -1,5 +1,6 @@
 // abi_indexed.hip -- C ABI (include/gsdf_hip.h), indexed meshes: the gsdf_indexed handle, the weld of a records mesh, counts /
-// stats / reads, normals, the binary PLY, and the report (edge classes, shells, measures) with the extraction of shells.
+// stats / reads, normals, the binary PLY, the report (edge classes, shells, measures) with the extraction of shells, and the
+// projection of the vertices onto a program's field (its kernel is abi_eval.hip's: project_dev).
 // Kernels: kernels_weld.h (weld, PLY, and the table / scan / remap every pass shares), kernels_topo.h (report, extract),
 // kernels_simplify.h (simplify). No
 // interpreter kernel is compiled here: of the meshers this unit needs mesh_march_dense alone, and abi_mesh.hip owns that.
@@ -67,6 +68,9 @@ struct gsdf_indexed {
   gsdf_indexed_report rep{};
   std::vector<gsdf_shell> shells;
   PoolBuf shell_of_vertex, shell_of_face;
+  // gsdf_hip_indexed_project's per-vertex record of the handle it made: d_before, d_after (V floats each), status (V bytes)
+  bool has_fit = false;
+  PoolBuf fit_before, fit_after, fit_status;
 };
 
 extern "C" void gsdf_hip_indexed_destroy(gsdf_indexed* ix) {
@@ -694,5 +698,54 @@ extern "C" int gsdf_hip_indexed_simplify(gsdf_indexed* ix, const gsdf_simplify_o
     nx->ms_device = r.ms_cells + r.ms_faces;
     *out = nx.release();
   }
+  return GSDF_OK;
+}
+
+// ---- project onto the field (kernels_project.h; the launch is abi_eval.hip's project_dev) -----------------------------------------
+extern "C" int gsdf_hip_indexed_project(gsdf_indexed* ix, gsdf_program* p, const gsdf_project_opts* o, gsdf_indexed** out, gsdf_project_stats* st) {
+  if (out) *out = nullptr;
+  if (!o) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  if (!std::isfinite(o->step) || !(o->step > 0.0f)) return fail(GSDF_ERR_BAD_ARGUMENT, "project: the step must be positive and finite");
+  if (!std::isfinite(o->tol) || !(o->tol >= 0.0f)) return fail(GSDF_ERR_BAD_ARGUMENT, "project: tol must be finite and not negative");
+  if (!std::isfinite(o->max_move) || !(o->max_move >= 0.0f)) return fail(GSDF_ERR_BAD_ARGUMENT, "project: max_move must be finite and not negative");
+  if (o->max_iters < 0 || o->max_iters > 64) return fail(GSDF_ERR_BAD_ARGUMENT, "project: max_iters must be 0 .. 64");
+  if (o->flags != 0) return fail(GSDF_ERR_BAD_ARGUMENT, "project: unknown flags " + std::to_string(o->flags));
+  if (!ix || !p || (!out && !st)) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  if (p->prog.is2d) return fail(GSDF_ERR_DIMENSION, "project: the program is 2D");
+  if (p->device != ix->device) return fail(GSDF_ERR_BAD_ARGUMENT, "the program and the indexed mesh live on different devices");
+  HIP_TRY(hipSetDevice(ix->device));
+  const int dev = ix->device;
+  const uint64_t V = ix->n_verts, F = ix->n_tris;
+  gsdf_project_stats r{};
+  if (!out) {  // the dry run: the stats alone
+    if (int rc = project_dev(p, ix->verts.p, (size_t)V, o, nullptr, nullptr, nullptr, nullptr, &r)) return rc;
+    *st = r;
+    return GSDF_OK;
+  }
+  IndexedPtr nx;
+  if (int rc = indexed_new(dev, ix->num_cu, &nx)) return rc;
+  if (!nx->verts.take(dev, V * 12) || !nx->idx.take(dev, F * 12) || !nx->vkeys.take(dev, V * 8) || !nx->fit_before.take(dev, V * 4) ||
+      !nx->fit_after.take(dev, V * 4) || !nx->fit_status.take(dev, V))
+    return fail(GSDF_ERR_HIP, "project: no device memory for the result");
+  HIP_TRY(hipMemcpyAsync(nx->idx.p, ix->idx.p, F * 12, hipMemcpyDeviceToDevice, nx->stream));
+  HIP_TRY(hipMemcpyAsync(nx->vkeys.p, ix->vkeys.p, V * 8, hipMemcpyDeviceToDevice, nx->stream));
+  if (int rc = project_dev(p, ix->verts.p, (size_t)V, o, nx->verts.p, nx->fit_before.p, nx->fit_after.p, nx->fit_status.as<uint8_t>(), &r)) return rc;
+  HIP_TRY(hipStreamSynchronize(nx->stream));
+  nx->n_verts = V;
+  nx->n_tris = F;
+  nx->has_fit = true;
+  nx->ms_device = r.ms_device;
+  if (st) *st = r;
+  *out = nx.release();
+  return GSDF_OK;
+}
+
+extern "C" int gsdf_hip_indexed_read_fit(const gsdf_indexed* ix, float* dist_before, float* dist_after, uint8_t* status) {
+  if (!ix) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  if (!ix->has_fit) return fail(GSDF_ERR_BAD_ARGUMENT, "no fit: the handle was not made by gsdf_hip_indexed_project");
+  HIP_TRY(hipSetDevice(ix->device));
+  if (dist_before) HIP_TRY(hipMemcpy(dist_before, ix->fit_before.p, ix->n_verts * 4, hipMemcpyDeviceToHost));
+  if (dist_after) HIP_TRY(hipMemcpy(dist_after, ix->fit_after.p, ix->n_verts * 4, hipMemcpyDeviceToHost));
+  if (status) HIP_TRY(hipMemcpy(status, ix->fit_status.p, ix->n_verts, hipMemcpyDeviceToHost));
   return GSDF_OK;
 }

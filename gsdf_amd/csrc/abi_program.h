@@ -93,6 +93,13 @@ struct gsdf_program {
   hipModule_t spec_mod_view = nullptr;
   hipFunction_t f_view = nullptr, f_view_plain = nullptr;
   bool spec_view_tried = false;
+  // the projection of mesh vertices onto the field (kernels_project.h: project_kernel) for a specialised handle: built on its first
+  // projection (spec_project)
+  hipModule_t spec_mod_project = nullptr;
+  hipFunction_t f_project = nullptr;
+  bool spec_project_tried = false;
+  void* proj_ctr = nullptr;                          // its counters on the device and the two events around its launch: made at the
+  hipEvent_t ev_proj[2] = {nullptr, nullptr};        // first projection, kept for the next (project_dev)
   // the 2-D picture (kernels_image.h: image2_color_kernel<K, kind> per conversion kind) for a specialised handle: built on its first
   // gsdf_hip_image2_color (spec_image_color)
   hipModule_t spec_mod_imgc = nullptr;
@@ -195,6 +202,13 @@ void spec_leaf_dz(gsdf_program* p);
 void spec_leaf_dense(gsdf_program* p);
 // gleval.NormalsCentralDiff on device-resident points (abi_eval.hip; what gsdf_hip_normals3 launches): blocking.
 int normals3_dev(gsdf_program* p, const float* d_pos, float* d_nrm, size_t n, float step);
+// The projection of device-resident points onto the field (abi_eval.hip; what gsdf_hip_indexed_project launches; gsdf_hip.h states
+// the arithmetic): d_pos 12-byte xyz on the program's device; d_out_pos (3 n floats), d_before, d_after (n floats), d_status (n bytes)
+// each optional; st->n_verts .. steps_max and ms_device are filled. Blocking. The options are the caller's to check.
+int project_dev(gsdf_program* p, const float* d_pos, size_t n, const gsdf_project_opts* o, float* d_out_pos, float* d_before, float* d_after,
+                uint8_t* d_status, gsdf_project_stats* st);
+// project_kernel for a specialised handle, built at its first projection: abi_eval.hip.
+void spec_project(gsdf_program* p);
 // The view kernels for a specialised handle, built on its first gsdf_hip_render3: abi_eval.hip.
 void spec_view(gsdf_program* p);
 // The picture kernels for a specialised 2-D handle, built on its first gsdf_hip_image2_color: abi_eval.hip.

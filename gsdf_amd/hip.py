@@ -29,7 +29,7 @@ SYMBOLS = ["gsdf_hip_last_error", "gsdf_hip_init", "gsdf_hip_program_create", "g
            "gsdf_hip_mesh_read_records", "gsdf_hip_mesh_weld", "gsdf_hip_indexed_counts", "gsdf_hip_indexed_stats_get", "gsdf_hip_indexed_read",
            "gsdf_hip_indexed_normals", "gsdf_hip_indexed_read_normals", "gsdf_hip_indexed_ply", "gsdf_hip_indexed_host_ply", "gsdf_hip_indexed_destroy",
            "gsdf_hip_indexed_create", "gsdf_hip_indexed_report", "gsdf_hip_indexed_shells", "gsdf_hip_indexed_read_shell_of", "gsdf_hip_indexed_extract",
-           "gsdf_hip_indexed_simplify"]
+           "gsdf_hip_indexed_simplify", "gsdf_hip_indexed_project", "gsdf_hip_indexed_read_fit"]
 
 
 PRUNE_ASSUME_SDF = 1 << 30  # gsdf_hip.h: GSDF_PRUNE_ASSUME_SDF
@@ -110,6 +110,27 @@ class SimplifyStats(C.Structure):
                 ("ms_cells", C.c_double), ("ms_faces", C.c_double), ("probes", C.c_uint64), ("table_cells", C.c_uint64),
                 ("attempts", C.c_int32), ("reserved2", C.c_int32)]
     RESULT_BYTES = 80
+
+    def result_bytes(self):
+        return bytes(self)[:self.RESULT_BYTES]
+
+
+class ProjectOpts(C.Structure):
+    """gsdf_project_opts (gsdf_hip.h): the central-difference step, the on-surface tolerance, the ball no vertex leaves, the trips."""
+    _fields_ = [("step", C.c_float), ("tol", C.c_float), ("max_move", C.c_float), ("max_iters", C.c_int32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32 * 3)]
+
+
+PROJECT_STATUS = ["SKIPPED", "ON", "CONVERGED", "ITERS", "FLAT", "CLAMPED", "NONFINITE", "REVERTED"]  # gsdf_hip.h: GSDF_PROJECT_*
+
+
+class ProjectStats(C.Structure):
+    """gsdf_project_stats (gsdf_hip.h): what a projection of a mesh's vertices onto a program's field did; bytes 0 .. 111 (RESULT_BYTES)
+    are a function of the mesh, the program and the options alone, ms_device says what the run cost."""
+    _fields_ = [("n_verts", C.c_uint64), ("count", C.c_uint64 * 8), ("evals", C.c_uint64), ("over_tol_before", C.c_uint64),
+                ("over_tol_after", C.c_uint64), ("max_abs_before", C.c_float), ("max_abs_after", C.c_float), ("steps_max", C.c_uint32),
+                ("reserved", C.c_uint32), ("ms_device", C.c_double)]
+    RESULT_BYTES = 112
 
     def result_bytes(self):
         return bytes(self)[:self.RESULT_BYTES]
@@ -236,6 +257,8 @@ def lib():
         L.gsdf_hip_indexed_read_shell_of.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.gsdf_hip_indexed_extract.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
         L.gsdf_hip_indexed_simplify.argtypes = [C.c_void_p, C.POINTER(SimplifyOpts), C.POINTER(C.c_void_p), C.POINTER(SimplifyStats)]
+        L.gsdf_hip_indexed_project.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(ProjectOpts), C.POINTER(C.c_void_p), C.POINTER(ProjectStats)]
+        L.gsdf_hip_indexed_read_fit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.gsdf_hip_brick_owner.restype = C.c_uint32
         L.gsdf_hip_brick_owner.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         L.gsdf_hip_slab_range.restype = None
@@ -777,6 +800,26 @@ class IndexedHIP:
                 return ix, st, cell
             cell = np.float32(cell * np.float32(2))
         raise ValueError(f"simplify_to: more than {max_tris} faces after 24 doublings of the cell {float(np.float32(cell0))!r}")
+
+    def project(self, sdf, step, tol, max_move, max_iters=8, dry=False):
+        """gsdf_hip_indexed_project: the mesh with every vertex moved onto the zero set of `sdf` (an SDF3HIP) by up to max_iters Newton
+        steps along its central-difference gradient (step: as normals()), never further than max_move from where it started and never
+        further from the surface than it was: (a new IndexedHIP with the same faces and keys, ProjectStats). dry: (None, ProjectStats)."""
+        o = ProjectOpts(step=np.float32(step), tol=np.float32(tol), max_move=np.float32(max_move), max_iters=int(max_iters))
+        st, h = ProjectStats(), C.c_void_p()
+        _check(lib().gsdf_hip_indexed_project(self._h, sdf._h, C.byref(o), None if dry else C.byref(h), C.byref(st)))
+        return (None if dry else IndexedHIP(h)), st
+
+    def deviation(self, sdf, tol):
+        """How far the vertices are from the surface of `sdf`: the dry run of project() with no step, one evaluation per vertex
+        (ProjectStats: max_abs_before, over_tol_before, count[ON])."""
+        return self.project(sdf, 1.0, tol, 0.0, max_iters=0, dry=True)[1]
+
+    def fit(self):
+        """Of a handle project() made: (d_before (V,) float32, d_after (V,) float32, status (V,) uint8, see PROJECT_STATUS)."""
+        a, b, s = np.empty(self.n_verts, np.float32), np.empty(self.n_verts, np.float32), np.empty(self.n_verts, np.uint8)
+        _check(lib().gsdf_hip_indexed_read_fit(self._h, a.ctypes.data, b.ctypes.data, s.ctypes.data))
+        return a, b, s
 
     def select_shells(self, min_tris=0, drop_cavities=False):
         """A keep mask for extract() from the shell table: shells with at least min_tris faces and, with drop_cavities, a volume

@@ -654,8 +654,8 @@ int gsdf_hip_indexed_extract(gsdf_indexed* ix, const uint8_t* keep_shell, int dr
  * gsdf_simplify_stats. Bytes 0 .. 79 (n_verts_in .. reserved) are a function of the mesh and the options alone; the rest says what
  *   this run cost. GSDF_HIP_SIMPLIFY_CELLS_MIN (environment) lowers the cluster table's first size so that tests can drive the
  *   grow-and-repeat path, as GSDF_HIP_TOPO_CELLS_MIN does.
- * Not done here: adaptive (quadric edge-collapse) simplification, QEF placement of the representative, projecting it back onto the
- *   field, removing duplicate or opposite faces. */
+ * Not done here: adaptive (quadric edge-collapse) simplification, QEF placement of the representative, removing duplicate or opposite
+ *   faces. (Projecting the representatives back onto the field: gsdf_hip_indexed_project, below.) */
 typedef struct gsdf_simplify_opts {
   float cell;        /* cell edge, > 0 and finite */
   float origin[3];   /* where cell (0, 0, 0) starts; finite */
@@ -684,6 +684,81 @@ GSDF_ABI_ASSERT(sizeof(gsdf_simplify_stats) == 120, "gsdf_simplify_stats is 120 
 GSDF_ABI_ASSERT(offsetof(gsdf_simplify_stats, cells) == 32 && offsetof(gsdf_simplify_stats, n_verts) == 48, "gsdf_simplify_stats counts");
 GSDF_ABI_ASSERT(offsetof(gsdf_simplify_stats, exponent) == 72 && offsetof(gsdf_simplify_stats, ms_cells) == 80, "gsdf_simplify_stats cost");
 int gsdf_hip_indexed_simplify(gsdf_indexed* ix, const gsdf_simplify_opts* o, gsdf_indexed** out, gsdf_simplify_stats* st);
+
+/* ---- indexed meshes: project onto the field (no reference counterpart) -------------------------------------------------------------
+ *
+ * The vertices of an indexed mesh moved onto the zero set of a 3-D program by Newton steps along its central-difference gradient,
+ * and, as the dry run with no step, the DEVIATION of a mesh from the part: how far its vertices are from the surface. A cluster's
+ * mean (simplify) lies inside every convex part and outside every concave one, by up to about cell^2 / (8 radius of curvature); a
+ * marching-cubes vertex is itself only the linear interpolate along a lattice edge. The result is a function of the mesh, the
+ * program and the options alone, to the bit. Kernel: gsdf_amd/csrc/kernels_project.h (abi_eval.hip: project_dev); a numpy
+ * restatement: tests/projectref.py.
+ *
+ * Options. step, tol, max_move finite, step > 0, tol >= 0, max_move >= 0, 0 <= max_iters <= 64, flags == 0 -- anything else is
+ *   GSDF_ERR_BAD_ARGUMENT, checked before the handle is looked at. A 2-D program: GSDF_ERR_DIMENSION. A program on another device
+ *   than the handle's: GSDF_ERR_BAD_ARGUMENT. h = step * 0.5f, as gsdf_hip_normals3.
+ * Arithmetic. Every operation below is ONE IEEE float32 operation, never contracted; the division is correctly rounded; comparisons
+ *   are IEEE (false on a NaN operand). sdf() is the program's distance, gsdf_hip_eval3's.
+ * Who takes part. All V vertices, used by a face or not. A vertex with a NaN or infinite coordinate is SKIPPED: not evaluated, its
+ *   position carried bit for bit, d_before and d_after the quiet NaN 0x7fc00000.
+ * Per vertex. x = x0, the vertex; then for it = 0 .. max_iters:
+ *   1. d = sdf(x)  (one evaluation). On it == 0, d_before = d. If d is NaN on it == 0: status NONFINITE, stop. If NOT (|d| > tol):
+ *      stop, status ON when it == 0, else CONVERGED. If it == max_iters: stop, status ITERS.
+ *   2. g_k = sdf(x + h e_k) - sdf(x - h e_k), k = x, y, z  (six evaluations; gsdf_hip_normals3's points and subtraction).
+ *   3. s = (g.x g.x + g.y g.y) + g.z g.z. If NOT (s > 0): stop, status FLAT.
+ *   4. t = (d * (h + h)) / s;  x'_k = x_k - t * g_k: the Newton step along the central-difference gradient g / 2h.
+ *   5. u = x' - x0;  r = (u.x u.x + u.y u.y) + u.z u.z. If NOT (r <= max_move * max_move): stop, status CLAMPED, x stays.
+ *      Otherwise x = x' (an ACCEPTED step).
+ * The end. d_after is the last d of step 1: it was evaluated at the final x (a vertex that stopped at 3 or 5 evaluated d at its x
+ *   in step 1 of that trip). For every vertex that is neither SKIPPED nor NONFINITE: if d_after is NaN or |d_after| > |d_before|,
+ *   the status becomes REVERTED, the position is x0 bit for bit and d_after = d_before; otherwise the position is x. (A NONFINITE
+ *   vertex keeps its status, its position and d_after = d_before.) So no vertex is further from the surface than it was, and none
+ *   leaves the ball of radius max_move about where it started.
+ * Status. One byte per vertex: GSDF_PROJECT_SKIPPED 0, _ON 1, _CONVERGED 2, _ITERS 3, _FLAT 4, _CLAMPED 5, _NONFINITE 6, _REVERTED 7.
+ * Evaluations. One per step 1 reached plus six per step 2 reached; their sum is st->evals, and gsdf_hip_evaluations(p) grows by
+ *   exactly that (padding lanes and finished lanes do not count, as in gsdf_hip_render3).
+ *
+ * gsdf_hip_indexed_project(ix, p, o, out, st): *out = a new, independent handle with the faces and the keys of ix byte for byte and
+ *   the new positions; normals are not carried (has_normals == 0), the report is computed afresh on demand. The handle keeps
+ *   d_before, d_after and the status per vertex for gsdf_hip_indexed_read_fit (each output optional; a handle not made by
+ *   gsdf_hip_indexed_project: GSDF_ERR_BAD_ARGUMENT); extract and simplify of the result do not carry them. out == NULL with
+ *   st != NULL is a DRY RUN: the same stats, no handle built; with max_iters == 0 it costs one evaluation per vertex and is the
+ *   deviation report. Both NULL: GSDF_ERR_BAD_ARGUMENT. On an error *out is NULL and *st is not written. (A handle always has
+ *   vertices: every call that makes one refuses an empty mesh with GSDF_ERR_EMPTY_BUFFERS.)
+ * gsdf_project_stats. Bytes 0 .. 111 (n_verts .. reserved) are a function of the mesh, the program and the options alone; ms_device
+ *   says what this run cost. count[k]: vertices of status k. over_tol_before / _after: vertices that took part with |d| > tol or a
+ *   NaN d. max_abs_before / _after: the largest non-NaN |d| of a vertex that took part, 0 if none. steps_max: the most accepted steps
+ *   of any vertex (a REVERTED vertex's count too). Every one is an integer sum or an integer maximum (|d|'s bits order as unsigned
+ *   integers), so any order of atomics gives the same bytes.
+ * Not done here: re-meshing, feature-preserving (QEF) placement, un-flipping faces a projection folds over (the report of the result
+ *   counts misoriented edges), 2-D. */
+enum { GSDF_PROJECT_SKIPPED = 0, GSDF_PROJECT_ON = 1, GSDF_PROJECT_CONVERGED = 2, GSDF_PROJECT_ITERS = 3, GSDF_PROJECT_FLAT = 4,
+       GSDF_PROJECT_CLAMPED = 5, GSDF_PROJECT_NONFINITE = 6, GSDF_PROJECT_REVERTED = 7 };
+typedef struct gsdf_project_opts {
+  float step;         /* central-difference step, > 0 and finite: h = step / 2 */
+  float tol;          /* a vertex is on the surface when NOT (|d| > tol); >= 0 and finite */
+  float max_move;     /* no vertex ends further than this from where it started; >= 0 and finite */
+  int32_t max_iters;  /* 0 .. 64 */
+  uint32_t flags;     /* 0; others refused */
+  uint32_t reserved[3];
+} gsdf_project_opts;
+GSDF_ABI_ASSERT(sizeof(gsdf_project_opts) == 32, "gsdf_project_opts is 32 bytes");
+GSDF_ABI_ASSERT(offsetof(gsdf_project_opts, tol) == 4 && offsetof(gsdf_project_opts, max_move) == 8 && offsetof(gsdf_project_opts, max_iters) == 12 && offsetof(gsdf_project_opts, flags) == 16, "gsdf_project_opts fields");
+typedef struct gsdf_project_stats {
+  uint64_t n_verts;
+  uint64_t count[8];        /* vertices per status */
+  uint64_t evals;
+  uint64_t over_tol_before, over_tol_after;
+  float max_abs_before, max_abs_after;
+  uint32_t steps_max;
+  uint32_t reserved;
+  double ms_device;         /* device time of the kernel, HIP events */
+} gsdf_project_stats;
+GSDF_ABI_ASSERT(sizeof(gsdf_project_stats) == 120, "gsdf_project_stats is 120 bytes");
+GSDF_ABI_ASSERT(offsetof(gsdf_project_stats, count) == 8 && offsetof(gsdf_project_stats, evals) == 72 && offsetof(gsdf_project_stats, over_tol_before) == 80, "gsdf_project_stats counts");
+GSDF_ABI_ASSERT(offsetof(gsdf_project_stats, max_abs_before) == 96 && offsetof(gsdf_project_stats, steps_max) == 104 && offsetof(gsdf_project_stats, ms_device) == 112, "gsdf_project_stats maxima and cost");
+int gsdf_hip_indexed_project(gsdf_indexed* ix, gsdf_program* p, const gsdf_project_opts* o, gsdf_indexed** out, gsdf_project_stats* st);
+int gsdf_hip_indexed_read_fit(const gsdf_indexed* ix, float* dist_before, float* dist_after, uint8_t* status);
 
 /* ---- multi-GPU (one process per GPU). The meshers shard with NO data-path collective (shard_rank / shard_count above); the
  * one exchange is the final variable-length gather of the ranks' results, over xGMI, inside this library: a Go caller needs no

@@ -218,6 +218,69 @@ func (ix *IndexedHIP) Simplify(cell float32, origin ms3.Vec, dry bool) (*Indexed
 	return nx, stats, nil
 }
 
+// ProjectStats is gsdf_project_stats: what a projection of the vertices onto a field did, and its device time. Count is indexed by
+// the status byte: skipped, on, converged, iters, flat, clamped, nonfinite, reverted.
+type ProjectStats struct {
+	V                          uint64
+	Count                      [8]uint64
+	Evaluations                uint64
+	OverTolBefore, OverTolAfter uint64
+	MaxAbsBefore, MaxAbsAfter  float32
+	StepsMax                   uint32
+	Millis                     float64
+}
+
+// Project returns a new, independent mesh with the faces of this one and every vertex moved onto the zero set of s by up to maxIters
+// Newton steps along its central-difference gradient (step as Normals), never further than maxMove from where it started and never
+// further from the surface than it was (gsdf_hip.h states every term). With dry set nothing is built: the mesh returned is nil
+// and the stats say what the result would be.
+func (ix *IndexedHIP) Project(s *gleval.SDF3HIP, step, tol, maxMove float32, maxIters int, dry bool) (*IndexedHIP, ProjectStats, error) {
+	po := C.gsdf_project_opts{step: C.float(step), tol: C.float(tol), max_move: C.float(maxMove), max_iters: C.int32_t(maxIters)}
+	var ps C.gsdf_project_stats
+	var h *C.gsdf_indexed
+	out := &h
+	if dry {
+		out = nil
+	}
+	if rc := C.gsdf_hip_indexed_project(ix.h, hipProgram(s), &po, out, &ps); rc != 0 {
+		return nil, ProjectStats{}, hipErr(rc)
+	}
+	stats := ProjectStats{
+		V: uint64(ps.n_verts), Evaluations: uint64(ps.evals), OverTolBefore: uint64(ps.over_tol_before), OverTolAfter: uint64(ps.over_tol_after),
+		MaxAbsBefore: float32(ps.max_abs_before), MaxAbsAfter: float32(ps.max_abs_after), StepsMax: uint32(ps.steps_max), Millis: float64(ps.ms_device),
+	}
+	for k := range stats.Count {
+		stats.Count[k] = uint64(ps.count[k])
+	}
+	if dry {
+		return nil, stats, nil
+	}
+	nx := &IndexedHIP{h: h}
+	var nv, nf C.uint64_t
+	var ms C.double
+	C.gsdf_hip_indexed_counts(h, &nv, &nf, &ms)
+	nx.V, nx.F, nx.WeldMillis = uint64(nv), uint64(nf), float64(ms)
+	return nx, stats, nil
+}
+
+// Deviation says how far the vertices are from the surface of s: the dry run of Project with no step, one evaluation per vertex.
+func (ix *IndexedHIP) Deviation(s *gleval.SDF3HIP, tol float32) (ProjectStats, error) {
+	_, stats, err := ix.Project(s, 1, tol, 0, 0, true)
+	return stats, err
+}
+
+// Fit returns, of a mesh Project made, the distance of every vertex before and after and its status byte.
+func (ix *IndexedHIP) Fit() (before, after []float32, status []uint8, err error) {
+	before, after, status = make([]float32, ix.V), make([]float32, ix.V), make([]uint8, ix.V)
+	if ix.V == 0 {
+		return before, after, status, nil
+	}
+	if rc := C.gsdf_hip_indexed_read_fit(ix.h, (*C.float)(unsafe.Pointer(&before[0])), (*C.float)(unsafe.Pointer(&after[0])), (*C.uint8_t)(unsafe.Pointer(&status[0]))); rc != 0 {
+		return nil, nil, nil, hipErr(rc)
+	}
+	return before, after, status, nil
+}
+
 // Close frees the device and pinned host buffers of the mesh.
 func (ix *IndexedHIP) Close() {
 	if ix.h != nil {
