@@ -19,6 +19,10 @@ binary STL's of the same mesh, and the weld's device time.
                          (gsdf_hip_indexed_project, on device: step res / 4, on the surface within res / 1024, never further than the
                          simplify cell -- or res -- from where it was): clustering pulls the surface inwards on every convex part
     --before-project F   with --project: also write the mesh as it was before the projection to F (the same faces, byte for byte)
+    --renderer R         octree (the default: marching cubes, welded by lattice edge) or dualcontour: the reference's sharp-feature
+                         mesher straight to an indexed mesh (gsdf_hip_mesh_dualcontour_indexed: one vertex per kept cube, faces in
+                         lattice order, the same file byte for byte on every run); every option above works after it
+    --chiseled           with --renderer dualcontour: DualContourLeastSquares.Chiseled
 With --simplify / --max-tris, --normals are those of the simplified mesh and --report prints a second report for it; with --project
 they are those of the projected mesh, and --report also prints how far the vertices were from the surface before and after, and
 the projected mesh's report: its volume is the point of the exercise. The grid starts
@@ -62,9 +66,13 @@ def main(argv=None):
     ap.add_argument("--max-tris", type=int, default=0, metavar="N", help="cluster in cells of 2 res, 4 res, ... until at most N faces are left")
     ap.add_argument("--project", type=int, nargs="?", const=8, default=None, metavar="ITERS", help="move the vertices onto the surface by up to ITERS (8) Newton steps")
     ap.add_argument("--before-project", default=None, metavar="F", help="with --project: also write the mesh before the projection to F")
+    ap.add_argument("--renderer", choices=["octree", "dualcontour"], default="octree", help="the mesher: octree + weld, or dual contouring straight to an indexed mesh")
+    ap.add_argument("--chiseled", action="store_true", help="with --renderer dualcontour: the chiseled vertex placement")
     args = ap.parse_args(argv)
     if args.before_project and args.project is None:
         ap.error("--before-project needs --project")
+    if args.chiseled and args.renderer != "dualcontour":
+        ap.error("--chiseled needs --renderer dualcontour")
 
     import numpy as np
     from gsdf_amd import hip
@@ -77,10 +85,16 @@ def main(argv=None):
         sdf.specialize()
     res = np.float32(float(shape.Diagonal()) / args.resdiv)
     t0 = time.perf_counter()
-    mesh = hip.OctreeHIP(sdf, res, payload=hip.PAYLOAD_RECORDS)
-    t1 = time.perf_counter()
-    ix = mesh.weld()
-    t2 = time.perf_counter()
+    if args.renderer == "dualcontour":
+        ix = hip.IndexedHIP.dual_contour(sdf, res, chiseled=args.chiseled)
+        t1 = t2 = time.perf_counter()
+        mesh_stats = ix.mesh_stats
+    else:
+        mesh = hip.OctreeHIP(sdf, res, payload=hip.PAYLOAD_RECORDS)
+        t1 = time.perf_counter()
+        ix = mesh.weld()
+        t2 = time.perf_counter()
+        mesh_stats = mesh.stats
     simplify = args.simplify > 0 or args.max_tris > 0
     project = args.project is not None
     if args.normals and not simplify and not project:
@@ -94,7 +108,7 @@ def main(argv=None):
         print(f"kept {int(keep.sum())} of {len(keep)} shells: V {whole.n_verts} -> {ix.n_verts}, F {whole.n_tris} -> {ix.n_tris} "
               f"(extract {ix.ms_device:.3f} ms device)")
     if simplify:
-        whole, origin = ix, tuple(np.float32(o) - np.float32(0.5) * res for o in mesh.stats.origin[:])
+        whole, origin = ix, tuple(np.float32(o) - np.float32(0.5) * res for o in mesh_stats.origin[:])
         if args.max_tris > 0:
             ix, ss, cell = whole.simplify_to(args.max_tris, np.float32(2) * res, origin)
         else:
@@ -132,10 +146,11 @@ def main(argv=None):
     st = ix.stats
     stl_bytes = 84 + 50 * ix.n_tris
     print(f"{args.scene} resdiv {args.resdiv}: V {ix.n_verts} F {ix.n_tris}; PLY {len(data)} bytes ({len(data) / ix.n_tris:.1f} per triangle) "
-          f"against STL {stl_bytes} bytes; mesh {(t1 - t0) * 1e3:.2f} ms (device {mesh.stats.ms_total:.2f} ms), weld {(t2 - t1) * 1e3:.2f} ms "
-          f"(device {ix.ms_device:.3f} ms: keys {st.ms_keys:.3f}, table {st.ms_insert:.3f}, numbering {st.ms_number:.3f}; "
-          f"{st.probes} probes of {st.table_cells} cells, {st.attempts} pass), PLY pack + transfer {st.ms_ply:.3f} ms device; "
-          f"written to {out} in {(t3 - t2) * 1e3:.1f} ms")
+          f"against STL {stl_bytes} bytes; mesh {(t1 - t0) * 1e3:.2f} ms (device {mesh_stats.ms_total:.2f} ms), "
+          + (f"of which quads in lattice order {st.ms_keys:.3f} ms and numbering {st.ms_number:.3f} ms device, " if args.renderer == "dualcontour" else
+             f"weld {(t2 - t1) * 1e3:.2f} ms (device {ix.ms_device:.3f} ms: keys {st.ms_keys:.3f}, table {st.ms_insert:.3f}, numbering {st.ms_number:.3f}; "
+             f"{st.probes} probes of {st.table_cells} cells, {st.attempts} pass), ")
+          + f"PLY pack + transfer {st.ms_ply:.3f} ms device; written to {out} in {(t3 - t2) * 1e3:.1f} ms")
     return 0
 
 

@@ -77,6 +77,17 @@ void* dense_parts_at(float* d_tris, uint64_t n_tris);  // where the table goes b
 int mesh_march_dense(const uint8_t* d_buf, const gsdf_dense_part* parts, int nparts, void* d_parts, float ox, float oy, float oz, float res,
                      float* d_tris, int num_cu, hipStream_t s);
 
+// The other direction (abi_indexed.hip, for gsdf_hip_mesh_dualcontour_indexed in abi_mesh.hip): dual contouring's quads in lattice
+// order -> a finished gsdf_indexed handle. d_slot_cube: S = 3 F slots, each the index (< cube_cap: the CALLER has made sure) of the kept cube whose placed
+// vertex d_fv[3 cube ..] that corner is; a buffer from the triangle pool of slot_cap36 36-byte units that the handle TAKES OVER as
+// its index array (on an error it goes back to the pool). d_cubes: the kept cubes (device `Cube`, kernels_common.h), the vertices'
+// keys. Runs on s and waits for it: d_fv and d_cubes may be overwritten afterwards. key_ev: two pairs of events
+// recorded on s around the caller's ordering pass, whose device time becomes the handle's gsdf_indexed_stats.ms_keys.
+int indexed_from_cube_slots(int device, int num_cu, hipStream_t s, float* d_slot_cube, uint64_t slot_cap36, uint64_t S, uint64_t cube_cap, const float* d_fv,
+                            const void* d_cubes, const hipEvent_t key_ev[4], gsdf_indexed** out);
+// kernels_weld.h's block_scan_kernel on s: cnt[n] -> base[n], exclusive; *d_total = their sum. (The kernel is abi_indexed.hip's.)
+int launch_block_scan(const unsigned* d_cnt, unsigned n, unsigned* d_base, unsigned long long* d_total, hipStream_t s);
+
 // Triangle buffers and pinned host buffers are recycled through small per-process pools (abi_host.cpp).
 float* pool_take(int device, uint64_t need, uint64_t* cap_out);
 void pool_give(int device, float* p, uint64_t cap);

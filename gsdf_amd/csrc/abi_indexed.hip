@@ -1,6 +1,7 @@
 // abi_indexed.hip -- C ABI (include/gsdf_hip.h), indexed meshes: the gsdf_indexed handle, the weld of a records mesh, counts /
 // stats / reads, normals, the binary PLY, the report (edge classes, shells, measures) with the extraction of shells, and the
-// projection of the vertices onto a program's field (its kernel is abi_eval.hip's: project_dev).
+// projection of the vertices onto a program's field (its kernel is abi_eval.hip's: project_dev), and the numbering of dual
+// contouring's quads into a handle (indexed_from_cube_slots: abi_mesh.hip orders them and owns the evaluating stages).
 // Kernels: kernels_weld.h (weld, PLY, and the table / scan / remap every pass shares), kernels_topo.h (report, extract),
 // kernels_simplify.h (simplify). No
 // interpreter kernel is compiled here: of the meshers this unit needs mesh_march_dense alone, and abi_mesh.hip owns that.
@@ -235,6 +236,67 @@ extern "C" int gsdf_hip_mesh_weld(const gsdf_mesh* m, gsdf_indexed** out) {
   ix->st.table_cells = cells;
   ix->st.attempts = run.attempts;
   ix->ms_device = ix->st.ms_keys + ix->st.ms_insert + ix->st.ms_number;
+  *out = ix.release();
+  return GSDF_OK;
+}
+
+// ---- dual contouring's indexed mesh: the numbering (abi_mesh.hip orders the quads; kernels_topo.h: cube_first_kernel) -------------
+int launch_block_scan(const unsigned* d_cnt, unsigned n, unsigned* d_base, unsigned long long* d_total, hipStream_t s) {
+  LAUNCH(block_scan_kernel, 1, 1024, s, d_cnt, n, d_base, d_total);
+  return GSDF_OK;
+}
+
+namespace {
+struct CubeSlotsWs { PoolBuf first, vnum, blk_cnt, blk_base, total; };  // (the caller's: it outlives the work on s on every way out)
+int cube_slots_number(gsdf_indexed* ix, CubeSlotsWs& w, hipStream_t s, uint64_t S, uint64_t cube_cap, const float* d_fv, const Cube* d_cubes) {
+  const int dev = ix->device;
+  const unsigned n_blocks = blocks_of(S);
+  const char* nomem = "dual contouring, indexed: no device memory for the workspace";
+  PoolBuf &first = w.first, &vnum = w.vnum, &blk_cnt = w.blk_cnt, &blk_base = w.blk_base, &total = w.total;
+  if (!first.take(dev, cube_cap * 4) || !vnum.take(dev, cube_cap * 4) || !blk_cnt.take(dev, (size_t)n_blocks * 4) || !blk_base.take(dev, (size_t)n_blocks * 4) ||
+      !total.take(dev, 8))
+    return fail(GSDF_ERR_HIP, nomem);
+  EventPair ev;
+  if (!ev.make()) return fail(GSDF_ERR_HIP, "hipEventCreate failed");
+  HIP_TRY(hipEventRecord(ev.a, s));
+  HIP_TRY(hipMemsetAsync(first.p, 0xff, cube_cap * 4, s));
+  LAUNCH(cube_first_kernel, n_blocks, BLOCK, s, ix->idx.as<unsigned>(), (unsigned long long)S, first.as<unsigned>());
+  LAUNCH(topo_owner_kernel, n_blocks, BLOCK, s, ix->idx.as<unsigned>(), (unsigned long long)S, first.as<unsigned>(), blk_cnt.as<unsigned>());
+  uint64_t V = 0;
+  if (int rc = scan_blocks(s, blk_cnt, n_blocks, blk_base, total, &V)) return rc;
+  if (V == 0 || V > S || V > cube_cap) return fail(GSDF_ERR_HIP, "dual contouring, indexed: internal error (owners)");
+  if (!ix->verts.take(dev, V * 12) || !ix->vkeys.take(dev, V * 8)) return fail(GSDF_ERR_HIP, nomem);
+  LAUNCH(cube_number_kernel, n_blocks, BLOCK, s, ix->idx.as<unsigned>(), (unsigned long long)S, first.as<unsigned>(), blk_base.as<unsigned>(), vnum.as<unsigned>(),
+         (const unsigned*)d_fv, d_cubes, ix->verts.as<unsigned>(), ix->vkeys.as<unsigned long long>());
+  LAUNCH(remap_kernel, n_blocks, BLOCK, s, ix->idx.as<unsigned>(), (unsigned long long)S, vnum.as<unsigned>());
+  HIP_TRY(hipEventRecord(ev.b, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  ix->n_verts = V;
+  ix->n_tris = S / 3;
+  ix->st.ms_number = ev.ms();
+  return GSDF_OK;
+}
+}  // namespace
+
+int indexed_from_cube_slots(int device, int num_cu, hipStream_t s, float* d_slot_cube, uint64_t slot_cap36, uint64_t S, uint64_t cube_cap, const float* d_fv,
+                            const void* d_cubes, const hipEvent_t key_ev[4], gsdf_indexed** out) {
+  *out = nullptr;
+  IndexedPtr ix;
+  if (int rc = indexed_new(device, num_cu, &ix)) {
+    (void)hipStreamSynchronize(s);  // (the ordering pass may still be writing the slots)
+    pool_give(device, d_slot_cube, slot_cap36);
+    return rc;
+  }
+  ix->idx.device = device; ix->idx.p = d_slot_cube; ix->idx.cap = slot_cap36;
+  CubeSlotsWs w;
+  if (int rc = cube_slots_number(ix.get(), w, s, S, cube_cap, d_fv, (const Cube*)d_cubes)) {
+    (void)hipStreamSynchronize(s);  // the buffers go back to the pool: nothing may be running on them
+    return rc;
+  }
+  float ta = 0, tb = 0;  // (s has been waited for)
+  if (hipEventElapsedTime(&ta, key_ev[0], key_ev[1]) != hipSuccess || hipEventElapsedTime(&tb, key_ev[2], key_ev[3]) != hipSuccess) { (void)hipGetLastError(); ta = tb = 0; }
+  ix->st.ms_keys = (double)ta + (double)tb;  // (no hash table: ms_insert, probes, table_cells, attempts stay 0)
+  ix->ms_device = ix->st.ms_keys + ix->st.ms_number;
   *out = ix.release();
   return GSDF_OK;
 }

@@ -1,7 +1,8 @@
 // abi_mesh.hip -- C ABI (include/gsdf_hip.h), mesher side: glrender.Octree + marchCubes, FlatRenderer and
 // DualContourRenderer on device, and the accessors of the resulting mesh (ReadTriangles drain, STL, pinned host views).
-// Kernels: kernels_octree.h, kernels_flat.h, kernels_dc.h, kernels_stl.h, kernels_minecraft.h. Indexed meshes (weld, PLY, report,
-// extract) are abi_indexed.hip's; what it takes from here is mesh_march_dense.
+// Kernels: kernels_octree.h, kernels_flat.h, kernels_dc.h, kernels_dc_indexed.h, kernels_stl.h, kernels_minecraft.h. Indexed meshes
+// (weld, PLY, report, extract) are abi_indexed.hip's; what it takes from here is mesh_march_dense, and what dual contouring's indexed
+// entry takes from there is indexed_from_cube_slots.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -14,6 +15,7 @@
 #include "kernels_octree.h"
 #include "kernels_flat.h"
 #include "kernels_dc.h"
+#include "kernels_dc_indexed.h"
 #include "kernels_stl.h"
 #include "kernels_minecraft.h"
 #include "abi_program.h"
@@ -646,9 +648,34 @@ extern "C" int gsdf_hip_mesh_march(gsdf_mesh* m) {
   return GSDF_OK;
 }
 
+// Workspace of dual contouring's indexed quad stage (kernels_dc_indexed.h) in one arena: byte offsets.
+namespace {
+struct DcIndexedWs {
+  uint64_t n_rows = 0;  // lattice rows (z, y): n^2
+  unsigned n_row_blocks = 0;
+  size_t quad = 0, place = 0, row_cnt = 0, row_base = 0, blk_cnt = 0, blk_base = 0, total = 0, bad = 0, bytes = 0;
+  static DcIndexedWs of(uint64_t ecap, int nshift) {
+    DcIndexedWs w;
+    w.n_rows = (uint64_t)1 << (2 * nshift);
+    w.n_row_blocks = (unsigned)((w.n_rows + BLOCK - 1) / BLOCK);
+    w.quad = 0;                                    // uint4 per edge: first, 16-byte aligned
+    w.place = w.quad + (size_t)ecap * 16;
+    w.row_cnt = w.place + (size_t)ecap * 4;
+    w.row_base = w.row_cnt + (size_t)w.n_rows * 4;
+    w.blk_cnt = w.row_base + (size_t)w.n_rows * 4;
+    w.blk_base = w.blk_cnt + (size_t)w.n_row_blocks * 4;
+    w.total = (w.blk_base + (size_t)w.n_row_blocks * 4 + 7) & ~(size_t)7;
+    w.bad = w.total + 8;  // violations counted by passes C and D (none, by construction)
+    w.bytes = w.bad + 8;
+    return w;
+  }
+};
+}  // namespace
+
 // glrender.DualContourRenderer.Reset + RenderAll with DualContourLeastSquares on device.
-extern "C" int gsdf_hip_mesh_dualcontour(gsdf_program* p, float res, int chiseled, int shard_rank, int shard_count, void* stream,
-                                         gsdf_mesh** out) {
+// out_ix == nullptr: the triangle soup (dc_quads_kernel). Else the quads in lattice order as an indexed mesh (kernels_dc_indexed.h
+// in the place of dc_quads_kernel; *out then carries the statistics alone).
+static int dc_mesh(gsdf_program* p, float res, int chiseled, int shard_rank, int shard_count, void* stream, gsdf_mesh** out, gsdf_indexed** out_ix) {
   if (!p || !out) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
   *out = nullptr;
   spec_adopt(p);  // (a background build that has finished: its kernels from here on)
@@ -685,7 +712,11 @@ extern "C" int gsdf_hip_mesh_dualcontour(gsdf_program* p, float res, int chisele
   m->device = p->device; m->stream = s;
   m->st.levels = levels; m->st.res = res;
   m->st.origin[0] = ox; m->st.origin[1] = oy; m->st.origin[2] = oz;
-  auto bail = [&](int code) { gsdf_hip_mesh_destroy(m); return code; };
+  auto bail = [&](int code) {
+    if (out_ix && *out_ix) { gsdf_hip_indexed_destroy(*out_ix); *out_ix = nullptr; }
+    gsdf_hip_mesh_destroy(m);
+    return code;
+  };
 #define HIP_TRYM(expr)                                                                                          \
   do {                                                                                                          \
     hipError_t _e = (expr);                                                                                     \
@@ -707,7 +738,9 @@ extern "C" int gsdf_hip_mesh_dualcontour(gsdf_program* p, float res, int chisele
   uint64_t ccap = p->last_dc_cubes ? p->last_dc_cubes + p->last_dc_cubes / 8 + 4096 : (uint64_t)12 << (2 * nshift);
   if (ccap < (1u << 20)) ccap = 1u << 20;
   DCCounters hc{};
-  uint64_t n_cubes = 0, n_edges = 0, n_cube_runs = 0, n_edge_runs = 0, last_cap = 0;
+  uint64_t n_cubes = 0, n_edges = 0, n_cube_runs = 0, n_edge_runs = 0, last_cap = 0, final_ccap = 0;
+  unsigned long long n_quads = 0;  // (indexed: pass B's total)
+  DcIndexedWs ixw{};
   const float h = (chiseled ? (float)1e-4 : (float)2e-8) * 0.5f;  // NormalsCentralDiff: step *= 0.5
   const float sqrtLambda = chiseled ? (float)(std::sqrt(1e-5) * 1e-4) : (float)std::sqrt(1e-5);
   spec_aux(p);
@@ -747,7 +780,7 @@ extern "C" int gsdf_hip_mesh_dualcontour(gsdf_program* p, float res, int chisele
     HIP_TRYM(f2.ensure(ccap * 12));
     HIP_TRYM(n2.ensure(ccap * 36));
     HIP_TRYM(e2.ensure(ecap * sizeof(unsigned)));
-    if (!m->d_tris || m->cap < tcap) {
+    if (!out_ix && (!m->d_tris || m->cap < tcap)) {
       pool_give(p->device, m->d_tris, m->cap);
       m->d_tris = pool_take(p->device, tcap, &m->cap);
       if (!m->d_tris) { HIP_TRYM(hipMalloc((void**)&m->d_tris, tcap * 36)); m->cap = tcap; }
@@ -815,11 +848,33 @@ extern "C" int gsdf_hip_mesh_dualcontour(gsdf_program* p, float res, int chisele
                        sqrtLambda, (float*)f2.p, zown_hi, (const unsigned char*)p->dc_flag.p, d_ctr);
     HIP_TRYM(hipGetLastError());
     HIP_TRYM(hipEventRecord(p->ev_b[3], s));  // placement done
+    if (out_ix) {
+      // the quads counted row by row and the rows scanned (kernels_dc_indexed.h, passes A and B); their number comes back with the
+      // counters, and the rest of the stage runs once the lists are known to have held
+      ixw = DcIndexedWs::of(ecap, nshift);
+      HIP_TRYM(p->dc_ix.ensure(ixw.bytes));
+      uint8_t* w = (uint8_t*)p->dc_ix.p;
+      HIP_TRYM(hipMemsetAsync(w + ixw.row_cnt, 0, ixw.n_rows * 4, s));
+      hipLaunchKernelGGL(dci_count_kernel, dim3(grid_for(ecap, p->num_cu, 8)), dim3(BLOCK), 0, s, (const Cube*)p->q0.p, (const float4*)d2.p, (const unsigned*)e2.p,
+                         (unsigned long long)ecap, (const int*)grid.p, nshift, (unsigned*)(w + ixw.row_cnt), (unsigned*)(w + ixw.place), (uint4*)(w + ixw.quad), d_ctr);
+      HIP_TRYM(hipGetLastError());
+      hipLaunchKernelGGL(dci_row_sum_kernel, dim3(ixw.n_row_blocks), dim3(BLOCK), 0, s, (const unsigned*)(w + ixw.row_cnt), (unsigned)ixw.n_rows,
+                         (unsigned*)(w + ixw.blk_cnt));
+      HIP_TRYM(hipGetLastError());
+      if (int rc = launch_block_scan((const unsigned*)(w + ixw.blk_cnt), ixw.n_row_blocks, (unsigned*)(w + ixw.blk_base), (unsigned long long*)(w + ixw.total), s))
+        return bail(rc);
+      hipLaunchKernelGGL(dci_row_base_kernel, dim3(ixw.n_row_blocks), dim3(BLOCK), 0, s, (const unsigned*)(w + ixw.row_cnt), (unsigned)ixw.n_rows,
+                         (const unsigned*)(w + ixw.blk_base), (unsigned*)(w + ixw.row_base));
+      HIP_TRYM(hipGetLastError());
+      HIP_TRYM(hipEventRecord(p->ev[2], s));
+      HIP_TRYM(hipMemcpyAsync(&n_quads, w + ixw.total, sizeof n_quads, hipMemcpyDeviceToHost, s));
+    } else {
     hipLaunchKernelGGL(dc_quads_kernel, dim3(grid_for(ecap, p->num_cu, 8)), dim3(BLOCK), 0, s, (const Cube*)p->q0.p, (const float4*)d2.p,
                        (const unsigned*)e2.p, (unsigned long long)ecap, (const int*)grid.p, (const float*)f2.p, nshift, zown_lo, zown_hi,
                        m->d_tris, (unsigned long long)m->cap, d_ctr);
     HIP_TRYM(hipGetLastError());
     HIP_TRYM(hipEventRecord(p->ev[1], s));
+    }
     HIP_TRYM(hipMemcpyAsync(&hc, d_ctr, sizeof(hc), hipMemcpyDeviceToHost, s));
     HIP_TRYM(hipStreamSynchronize(s));
     n_cubes = n_edges = n_cube_runs = n_edge_runs = 0;
@@ -837,7 +892,50 @@ extern "C" int gsdf_hip_mesh_dualcontour(gsdf_program* p, float res, int chisele
       continue;
     }
     last_cap = DC_PARTS * max_part;
+    final_ccap = ccap;
     break;
+  }
+  if (out_ix) {
+    // passes C and D, then the numbering (abi_indexed.hip) -- all of it before the next mesh of this handle overwrites the arenas
+    const uint64_t Q = n_quads, ecap = 3 * final_ccap;
+    if (Q > n_edges) return bail(fail(GSDF_ERR_HIP, "dual contouring, indexed: internal error (more quads than active edges)"));
+    if (Q == 0) return bail(fail(GSDF_ERR_EMPTY_BUFFERS, "empty triangle slice"));
+    if (6 * Q >= ((uint64_t)1 << 32)) return bail(fail(GSDF_ERR_CAPACITY, "dual contouring, indexed: 3 x triangles must stay below 2^32 (32-bit vertex numbers)"));
+    HIP_TRYM(p->dc_ix_sort.ensure(Q * 8));
+    unsigned *xa = (unsigned*)p->dc_ix_sort.p, *src = xa + Q;
+    const uint64_t units = (6 * Q * 4 + 35) / 36 + 1;
+    uint64_t slot_cap = 0;
+    float* slots = pool_take(p->device, units, &slot_cap);
+    if (!slots) { HIP_TRYM(hipMalloc((void**)&slots, units * 36)); slot_cap = units; }
+    const uint8_t* w = (const uint8_t*)p->dc_ix.p;
+    unsigned long long* d_bad = (unsigned long long*)((uint8_t*)p->dc_ix.p + ixw.bad);
+    unsigned long long n_bad = 0;
+    hipError_t e = hipEventRecord(p->ev[3], s);
+    if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0, 8, s);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(dci_scatter_kernel, dim3(grid_for(ecap, p->num_cu, 8)), dim3(BLOCK), 0, s, (const Cube*)p->q0.p, (const unsigned*)e2.p, (unsigned long long)ecap,
+                         nshift, (const unsigned*)(w + ixw.row_base), (const unsigned*)(w + ixw.place), (unsigned long long)Q, xa, src, d_bad, d_ctr);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(dci_rank_kernel, dim3((unsigned)((Q + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, (const Cube*)p->q0.p, (const unsigned*)e2.p, (unsigned long long)ecap,
+                         nshift, (const unsigned*)(w + ixw.row_base), (const unsigned*)(w + ixw.row_cnt), (const unsigned*)xa, (const unsigned*)src,
+                         (const uint4*)(w + ixw.quad), (unsigned long long)Q, (unsigned long long)final_ccap, (unsigned*)slots, d_bad);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(p->ev[1], s);
+    // every slot written, every index in range? (kernels_dc_indexed.h: *bad) -- known before anything reads the slots
+    if (e == hipSuccess) e = hipMemcpyAsync(&n_bad, d_bad, sizeof n_bad, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess || n_bad != 0) {
+      (void)hipStreamSynchronize(s);
+      pool_give(p->device, slots, slot_cap);
+      if (e == hipSuccess) return bail(fail(GSDF_ERR_HIP, "dual contouring, indexed: internal error (" + std::to_string(n_bad) + " quads out of place in the ordering pass)"));
+      return bail(fail(GSDF_ERR_HIP, std::string("dual contouring, indexed: the ordering pass: ") + hipGetErrorString(e)));
+    }
+    const hipEvent_t key_ev[4] = {p->ev_b[3], p->ev[2], p->ev[3], p->ev[1]};  // passes A + B, passes C + D
+    if (int rc = indexed_from_cube_slots(p->device, p->num_cu, s, slots, slot_cap, 6 * Q, final_ccap, (const float*)f2.p, p->q0.p, key_ev, out_ix)) return bail(rc);
+    hc.n_tris = Q;
   }
   float ms = 0;
   HIP_TRYM(hipEventElapsedTime(&ms, p->ev[0], p->ev[1]));
@@ -871,6 +969,23 @@ extern "C" int gsdf_hip_mesh_dualcontour(gsdf_program* p, float res, int chisele
   *out = m;
   return GSDF_OK;
 #undef HIP_TRYM
+}
+
+extern "C" int gsdf_hip_mesh_dualcontour(gsdf_program* p, float res, int chiseled, int shard_rank, int shard_count, void* stream,
+                                         gsdf_mesh** out) {
+  return dc_mesh(p, res, chiseled, shard_rank, shard_count, stream, out, nullptr);
+}
+
+extern "C" int gsdf_hip_mesh_dualcontour_indexed(gsdf_program* p, float res, int chiseled, void* stream, gsdf_indexed** out, gsdf_mesh_stats* st) {
+  if (out) *out = nullptr;
+  if (!p || !out) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  gsdf_mesh* m = nullptr;
+  gsdf_indexed* ix = nullptr;
+  if (int rc = dc_mesh(p, res, chiseled, 0, 1, stream, &m, &ix)) return rc;
+  if (st) *st = m->st;
+  gsdf_hip_mesh_destroy(m);  // (it held the statistics; there are no triangles in it)
+  *out = ix;
+  return GSDF_OK;
 }
 
 // glrender.FlatRenderer (flatrenderer.go:36-256) on device: Reset's lattice, evalGrid into a dense grid in HBM,

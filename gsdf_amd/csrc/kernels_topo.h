@@ -14,6 +14,7 @@
 //   topo_measure_kernel      a face per lane: shell of the face, the contract's float64 terms quantised to integers, summed as integers
 //   topo_classify_kernel     a CELL per lane: the pair's class, counted on its shell (the shell of its smaller vertex)
 //   topo_keep_kernel .. topo_renumber_kernel, remap_kernel   extract: kept faces compacted in order, vertices renumbered by their smallest kept slot
+//   cube_first_kernel, cube_number_kernel                     dual contouring's indexed mesh: extract's owner / number steps over kept cubes
 //
 // Sums. A wave whose lanes all belong to one shell (the common case: a shell's faces are runs in mesher order) reduces across the
 // wave and issues ONE atomic per quantity; a mixed wave issues per-lane atomics on each lane's shell. Every quantity is an integer
@@ -416,5 +417,35 @@ __global__ void __launch_bounds__(BLOCK) topo_renumber_kernel(const unsigned* __
       if (normals) nnormals[3ull * v + k] = normals[3ull * old + k];
     }
     nkeys[v] = vkeys[old];
+  }
+}
+
+// ---- dual contouring's indexed mesh (gsdf_hip_mesh_dualcontour_indexed): extract's shape, a kept CUBE where extract has an old vertex --
+// out[s] = the cube of slot s (kernels_dc_indexed.h: dci_rank_kernel). first[cube] = the smallest slot that names it (memset 0xff
+// before); topo_owner_kernel counts the owners; then owners -> vertex numbers in slot order, the position = the cube's placed vertex
+// (fv, bit for bit, as integers), the key = the cube's lattice coordinates, kind 5; remap_kernel writes the faces.
+// Every out[s] is below the cubes' capacity: dci_rank_kernel tests the four indices of a quad before it writes them, and the host
+// does not come here unless every slot was written (its *bad is 0). So neither this kernel, nor topo_owner_kernel, nor
+// cube_number_kernel tests them again.
+__global__ void __launch_bounds__(BLOCK) cube_first_kernel(const unsigned* __restrict__ out, unsigned long long n_slots, unsigned* __restrict__ first) {
+  const unsigned long long s = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x;
+  if (s < n_slots) atomicMin(first + out[s], (unsigned)s);
+}
+
+__global__ void __launch_bounds__(BLOCK) cube_number_kernel(const unsigned* __restrict__ out, unsigned long long n_slots, const unsigned* __restrict__ first,
+                                                            const unsigned* __restrict__ blk_base, unsigned* __restrict__ vnum, const unsigned* __restrict__ fv,
+                                                            const Cube* __restrict__ cubes, unsigned* __restrict__ nverts, unsigned long long* __restrict__ nkeys) {
+  __shared__ unsigned s_w[4];
+  const unsigned long long s = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x;
+  const unsigned old = s < n_slots ? out[s] : 0u;
+  const bool owner = s < n_slots && first[old] == (unsigned)s;
+  const unsigned rank = block_rank(owner, s_w);
+  if (owner) {
+    const unsigned v = blk_base[blockIdx.x] + rank;
+    vnum[old] = v;
+#pragma unroll
+    for (unsigned k = 0; k < 3u; k++) nverts[3ull * v + k] = fv[3ull * old + k];
+    const Cube c = cubes[old];
+    nkeys[v] = (unsigned long long)c.x | ((unsigned long long)c.y << 20) | ((unsigned long long)c.z << 40) | (5ull << 60);
   }
 }

@@ -29,7 +29,7 @@ SYMBOLS = ["gsdf_hip_last_error", "gsdf_hip_init", "gsdf_hip_program_create", "g
            "gsdf_hip_mesh_read_records", "gsdf_hip_mesh_weld", "gsdf_hip_indexed_counts", "gsdf_hip_indexed_stats_get", "gsdf_hip_indexed_read",
            "gsdf_hip_indexed_normals", "gsdf_hip_indexed_read_normals", "gsdf_hip_indexed_ply", "gsdf_hip_indexed_host_ply", "gsdf_hip_indexed_destroy",
            "gsdf_hip_indexed_create", "gsdf_hip_indexed_report", "gsdf_hip_indexed_shells", "gsdf_hip_indexed_read_shell_of", "gsdf_hip_indexed_extract",
-           "gsdf_hip_indexed_simplify", "gsdf_hip_indexed_project", "gsdf_hip_indexed_read_fit"]
+           "gsdf_hip_indexed_simplify", "gsdf_hip_indexed_project", "gsdf_hip_indexed_read_fit", "gsdf_hip_mesh_dualcontour_indexed"]
 
 
 PRUNE_ASSUME_SDF = 1 << 30  # gsdf_hip.h: GSDF_PRUNE_ASSUME_SDF
@@ -259,6 +259,7 @@ def lib():
         L.gsdf_hip_indexed_simplify.argtypes = [C.c_void_p, C.POINTER(SimplifyOpts), C.POINTER(C.c_void_p), C.POINTER(SimplifyStats)]
         L.gsdf_hip_indexed_project.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(ProjectOpts), C.POINTER(C.c_void_p), C.POINTER(ProjectStats)]
         L.gsdf_hip_indexed_read_fit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.gsdf_hip_mesh_dualcontour_indexed.argtypes = [C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(MeshStats)]
         L.gsdf_hip_brick_owner.restype = C.c_uint32
         L.gsdf_hip_brick_owner.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         L.gsdf_hip_slab_range.restype = None
@@ -744,6 +745,17 @@ class IndexedHIP:
         h = C.c_void_p()
         _check(lib().gsdf_hip_indexed_create(v.ctypes.data, len(v), i.ctypes.data, len(i), None if k is None else k.ctypes.data, C.byref(h)))
         return cls(h)
+
+    @classmethod
+    def dual_contour(cls, sdf, res, chiseled=False, stream=None):
+        """gsdf_hip_mesh_dualcontour_indexed: the dual-contouring mesh of `sdf` (an SDF3HIP) at cube size `res` as an indexed mesh, one
+        vertex per kept cube that a quad names, the faces in lattice order (z, y, x, axis) -- byte for byte the same on every run.
+        .mesh_stats: the MeshStats gsdf_hip_mesh_dualcontour reports for the same call."""
+        h, st = C.c_void_p(), MeshStats()
+        _check(lib().gsdf_hip_mesh_dualcontour_indexed(sdf._h, np.float32(res), int(bool(chiseled)), stream, C.byref(h), C.byref(st)))
+        ix = cls(h)
+        ix.mesh_stats = st
+        return ix
 
     def report(self):
         """gsdf_hip_indexed_report: an IndexedReport (computed on the device once per handle)."""

@@ -760,6 +760,49 @@ GSDF_ABI_ASSERT(offsetof(gsdf_project_stats, max_abs_before) == 96 && offsetof(g
 int gsdf_hip_indexed_project(gsdf_indexed* ix, gsdf_program* p, const gsdf_project_opts* o, gsdf_indexed** out, gsdf_project_stats* st);
 int gsdf_hip_indexed_read_fit(const gsdf_indexed* ix, float* dist_before, float* dist_after, uint8_t* status);
 
+/* ---- indexed meshes: dual contouring (no reference counterpart: the reference's dual-contouring mesh is a triangle list too) -------
+ *
+ * Dual contouring is the one mesher here whose native output IS an indexed mesh: one vertex per kept cube, one quad per active
+ * lattice edge. gsdf_hip_mesh_dualcontour_indexed runs the stages of gsdf_hip_mesh_dualcontour up to the vertex placement and then,
+ * instead of copying the quads' corners into a soup, hands out the cubes' indices as an ordinary gsdf_indexed handle: every accessor
+ * and pass above works on it unchanged (counts, read, normals, PLY, report, shells, extract, simplify, project). Same arguments
+ * and the same checks as gsdf_hip_mesh_dualcontour (2-D program: GSDF_ERR_DIMENSION; bad res or more than 12 levels:
+ * GSDF_ERR_RESOLUTION; an octree mesh of the program in flight: GSDF_ERR_BAD_ARGUMENT); unsharded only.
+ *
+ * Quads. Those of glrender/dual_contour.go:143-219 (oracle/orc_render.c: orc_render_dualcontour restates them): a kept cube
+ *   (x, y, z) whose edge from its origin along axis a (0 x, 1 y, 2 z) is ACTIVE -- the sign bit of the distance at the edge's end
+ *   differs from that of the distance at the origin -- yields a quad if the four cubes of EdgeNeighborsX/Y/Z (:271-287) around that
+ *   edge are all kept: q0 .. q3 in that order, reversed (q3, q2, q1, q0) when d_end - d_origin < 0.
+ * Order. Quads are ordered by (z, y, x, a), increasing: the order the reference emits them in. Quad g is the faces
+ *   2 g = (q0, q1, q2) and 2 g + 1 = (q2, q3, q0). Slot s = 3 t + c is corner c of face t, as in the weld. The order is part of the
+ *   contract, not an accident of scheduling.
+ * Key. The key of a slot is its cube: ix | iy << 20 | iz << 40 | 5 << 60, the cube's lattice coordinates (0 .. 2^(levels-1) - 1).
+ *   Kind 5, after the weld's 0 .. 3 and the simplifier's 4; its top bits are 0101, so it is never the tables' empty value.
+ * Vertices. A vertex is the set of slots with one key. Vertices are numbered by the smallest slot that names them, in increasing
+ *   order (the weld's and extract's rule); a vertex's position is the cube's placed vertex, bit for bit -- the value every copy of it
+ *   has in gsdf_hip_mesh_dualcontour's soup -- and keys[v] is the cube's key. has_normals == 0. A kept cube that no quad names is
+ *   not a vertex.
+ * Faces. F = 2 x quads; idx[s] is the number of slot s's vertex. All faces are kept, degenerate ones included. verts[idx] is the
+ *   reference's triangle list in the reference's order.
+ * Determinism. The result is a function of the program, res and chiseled alone, to the byte: it does not depend on the order in
+ *   which threads arrive, on the capacity-retry loop, or on whether the interpreter or the per-tree kernels evaluated.
+ * Errors. 3 F >= 2^32: GSDF_ERR_CAPACITY. No quad: GSDF_ERR_EMPTY_BUFFERS.
+ * st (optional): what gsdf_hip_mesh_dualcontour reports for the same call -- n_tris, evals, leaf_cubes, active_leaves, levels,
+ *   origin, res, ms_total. Here ms_total runs from the first stage to the end of the ordering of the quads and is NOT pure device time,
+ *   unlike gsdf_hip_mesh_dualcontour's: the ordering waits once for the host in its middle (the quad count comes back with the
+ *   counters and sizes the index array), and that wait is inside the interval. The numbering follows it and is the handle's
+ *   ms_number; ms_keys and ms_number are device time alone. The handle's gsdf_indexed_stats: ms_keys = the ordering of the
+ *   quads, ms_number = owners, numbering, position gather and index write; ms_insert = 0, probes = table_cells = 0, attempts = 0
+ *   (there is no hash table: a cube's index is its vertex's identity).
+ * Workspace. Beside dual contouring's own, the program handle keeps (grow-only, like the rest) 60 bytes per cube of LIST CAPACITY
+ *   (20 per possible edge: a quad's four cubes and its place) + 8 bytes per lattice row (n^2) + 8 per quad of the last mesh: 63 MB at
+ *   the smallest capacity (2^20 cubes), 0.76 GB for a first mesh at 11 levels (12 n^2 cubes), 3 GB at 12. The soup's triangle
+ *   buffer (216 bytes per cube of capacity) is not allocated by this entry.
+ * The result is finished inside the call (the cubes and their vertices live in the program handle's workspace, which the next mesh
+ * overwrites) and independent of the program afterwards. Kernels: gsdf_amd/csrc/kernels_dc_indexed.h (abi_mesh.hip) and
+ * kernels_topo.h: cube_first_kernel, cube_number_kernel (abi_indexed.hip); a numpy restatement: tests/dcref.py. */
+int gsdf_hip_mesh_dualcontour_indexed(gsdf_program* p, float res, int chiseled, void* stream, gsdf_indexed** out, gsdf_mesh_stats* st /* optional */);
+
 /* ---- multi-GPU (one process per GPU). The meshers shard with NO data-path collective (shard_rank / shard_count above); the
  * one exchange is the final variable-length gather of the ranks' results, over xGMI, inside this library: a Go caller needs no
  * Python for it. Replaces nothing in the reference (single device; its analogue of the split is the goroutine split of

@@ -51,6 +51,27 @@ func RenderIndexedHIP(s *gleval.SDF3HIP, cubeResolution float32) (*IndexedHIP, e
 	return ix, nil
 }
 
+// RenderIndexedDualContourHIP meshes s with dual contouring (least-squares vertex placement; chiseled as
+// DualContourLeastSquares.Chiseled) at cubeResolution straight to an indexed mesh (gsdf_hip_mesh_dualcontour_indexed): one vertex
+// per kept cube, the faces in lattice order -- the same bytes on every run. WeldMillis is the device time of the ordering and the
+// numbering. Report, Extract and the rest work on the result as on a welded mesh.
+func RenderIndexedDualContourHIP(s *gleval.SDF3HIP, cubeResolution float32, chiseled bool) (*IndexedHIP, error) {
+	var h *C.gsdf_indexed
+	ch := C.int(0)
+	if chiseled {
+		ch = 1
+	}
+	if rc := C.gsdf_hip_mesh_dualcontour_indexed(hipProgram(s), C.float(cubeResolution), ch, nil, &h, nil); rc != 0 {
+		return nil, hipErr(rc)
+	}
+	ix := &IndexedHIP{h: h}
+	var nv, nf C.uint64_t
+	var ms C.double
+	C.gsdf_hip_indexed_counts(h, &nv, &nf, &ms)
+	ix.V, ix.F, ix.WeldMillis = uint64(nv), uint64(nf), float64(ms)
+	return ix, nil
+}
+
 // Read copies the vertices and the faces' vertex numbers to the host.
 func (ix *IndexedHIP) Read() ([]ms3.Vec, [][3]uint32, error) {
 	verts := make([]ms3.Vec, ix.V)
