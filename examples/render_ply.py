@@ -15,6 +15,11 @@ binary STL's of the same mesh, and the weld's device time.
     --simplify K         then merge the vertices of every cell of K x res into one at their mean and drop the faces that collapse
                          (gsdf_hip_indexed_simplify: vertex clustering, on device)
     --max-tris N         ... with the first cell of 2 res, 4 res, 8 res, ... that leaves at most N faces (dry runs find it)
+    --adaptive TOL       cluster ADAPTIVELY instead (gsdf_hip_indexed_simplify_adaptive, on device): a vertex goes to the coarsest of
+                         --levels nested cells -- the finest of K x res (--simplify K, default 1) -- whose mean stays within TOL x res
+                         of the plane of every face touching the cell: flat faces collapse into large cells, thread flanks keep theirs.
+                         With --max-tris N: the first tolerance of TOL, 2 TOL, 4 TOL, ... x res that leaves at most N faces
+    --levels N           with --adaptive: the number of nested grids (8: cells of up to 128 finest cells)
     --project [ITERS]    then move every vertex onto the part's surface by up to ITERS (8) Newton steps along the field's gradient
                          (gsdf_hip_indexed_project, on device: step res / 4, on the surface within res / 1024, never further than the
                          simplify cell -- or res -- from where it was): clustering pulls the surface inwards on every convex part
@@ -64,6 +69,8 @@ def main(argv=None):
     ap.add_argument("--drop-cavities", action="store_true", help="drop the shells of negative volume")
     ap.add_argument("--simplify", type=float, default=0.0, metavar="K", help="cluster the vertices in cells of K x res")
     ap.add_argument("--max-tris", type=int, default=0, metavar="N", help="cluster in cells of 2 res, 4 res, ... until at most N faces are left")
+    ap.add_argument("--adaptive", type=float, default=None, metavar="TOL", help="cluster adaptively: a cell's mean stays within TOL x res of its faces' planes")
+    ap.add_argument("--levels", type=int, default=8, metavar="N", help="with --adaptive: nested grids, 1 .. 16")
     ap.add_argument("--project", type=int, nargs="?", const=8, default=None, metavar="ITERS", help="move the vertices onto the surface by up to ITERS (8) Newton steps")
     ap.add_argument("--before-project", default=None, metavar="F", help="with --project: also write the mesh before the projection to F")
     ap.add_argument("--renderer", choices=["octree", "dualcontour"], default="octree", help="the mesher: octree + weld, or dual contouring straight to an indexed mesh")
@@ -73,6 +80,10 @@ def main(argv=None):
         ap.error("--before-project needs --project")
     if args.chiseled and args.renderer != "dualcontour":
         ap.error("--chiseled needs --renderer dualcontour")
+    if args.adaptive is not None and not (args.adaptive >= 0 and 1 <= args.levels <= 16):
+        ap.error("--adaptive needs a tolerance >= 0 and --levels 1 .. 16")
+    if args.adaptive is not None and args.max_tris > 0 and not args.adaptive > 0:
+        ap.error("--adaptive with --max-tris needs a tolerance > 0 to double")
 
     import numpy as np
     from gsdf_amd import hip
@@ -95,7 +106,8 @@ def main(argv=None):
         ix = mesh.weld()
         t2 = time.perf_counter()
         mesh_stats = mesh.stats
-    simplify = args.simplify > 0 or args.max_tris > 0
+    adaptive = args.adaptive is not None
+    simplify = args.simplify > 0 or args.max_tris > 0 or adaptive
     project = args.project is not None
     if args.normals and not simplify and not project:
         ix.normals(sdf, np.float32(float(res) * 1e-3))
@@ -109,15 +121,30 @@ def main(argv=None):
               f"(extract {ix.ms_device:.3f} ms device)")
     if simplify:
         whole, origin = ix, tuple(np.float32(o) - np.float32(0.5) * res for o in mesh_stats.origin[:])
-        if args.max_tris > 0:
+        if adaptive:
+            fine = np.float32(args.simplify if args.simplify > 0 else 1) * res
+            tol = np.float32(args.adaptive) * res
+            if args.max_tris > 0:
+                ix, ss, tol = whole.simplify_adaptive_to(args.max_tris, fine, tol, args.levels, origin)
+            else:
+                ix, ss = whole.simplify_adaptive(fine, tol, args.levels, origin)
+            cell = fine * np.float32(1 << (args.levels - 1))      # the largest cell: what --project may move a vertex by
+            per_level = ", ".join(f"{int(n)} of level {l}" for l, n in enumerate(ss.chosen) if n)
+            print(f"simplified adaptively within {float(tol) / float(res):g} res, cells of {float(fine) / float(res):g} res x 1 .. {1 << (args.levels - 1)}: "
+                  f"V {whole.n_verts} -> {ix.n_verts}, F {whole.n_tris} -> {ix.n_tris} (clusters: {per_level or 'none'}; {ss.singles} vertices alone, the largest "
+                  f"cluster of {ss.largest_cluster} vertices, error at most {ss.max_err / float(res):.4g} res; {ss.cells} cells over all levels, "
+                  f"{ss.collapsed} faces collapsed, {ss.degenerate_in} were degenerate; device {ss.ms_cells + ss.ms_error + ss.ms_faces:.3f} ms: cells "
+                  f"{ss.ms_cells:.3f}, errors {ss.ms_error:.3f}, faces {ss.ms_faces:.3f}; {ss.probes} probes of {ss.table_cells} cells, {ss.attempts} pass)")
+        elif args.max_tris > 0:
             ix, ss, cell = whole.simplify_to(args.max_tris, np.float32(2) * res, origin)
         else:
             cell = np.float32(args.simplify) * res
             ix, ss = whole.simplify(cell, origin)
-        print(f"simplified in cells of {float(cell) / float(res):g} res: V {whole.n_verts} -> {ix.n_verts}, F {whole.n_tris} -> {ix.n_tris} "
-              f"({ss.cells} clusters, the largest of {ss.largest_cell} vertices; {ss.collapsed} faces collapsed, {ss.degenerate_in} were degenerate; "
-              f"device {ss.ms_cells + ss.ms_faces:.3f} ms: clusters {ss.ms_cells:.3f}, faces {ss.ms_faces:.3f}; {ss.probes} probes of {ss.table_cells} cells, "
-              f"{ss.attempts} pass)")
+        if not adaptive:
+            print(f"simplified in cells of {float(cell) / float(res):g} res: V {whole.n_verts} -> {ix.n_verts}, F {whole.n_tris} -> {ix.n_tris} "
+                  f"({ss.cells} clusters, the largest of {ss.largest_cell} vertices; {ss.collapsed} faces collapsed, {ss.degenerate_in} were degenerate; "
+                  f"device {ss.ms_cells + ss.ms_faces:.3f} ms: clusters {ss.ms_cells:.3f}, faces {ss.ms_faces:.3f}; {ss.probes} probes of {ss.table_cells} cells, "
+                  f"{ss.attempts} pass)")
         if args.normals and not project:
             ix.normals(sdf, np.float32(float(res) * 1e-3))
         if args.report:

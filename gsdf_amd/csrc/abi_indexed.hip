@@ -3,7 +3,7 @@
 // projection of the vertices onto a program's field (its kernel is abi_eval.hip's: project_dev), and the numbering of dual
 // contouring's quads into a handle (indexed_from_cube_slots: abi_mesh.hip orders them and owns the evaluating stages).
 // Kernels: kernels_weld.h (weld, PLY, and the table / scan / remap every pass shares), kernels_topo.h (report, extract),
-// kernels_simplify.h (simplify). No
+// kernels_simplify.h (simplify), kernels_simplify_adaptive.h (adaptive simplify). No
 // interpreter kernel is compiled here: of the meshers this unit needs mesh_march_dense alone, and abi_mesh.hip owns that.
 #include <algorithm>
 #include <cmath>
@@ -18,6 +18,7 @@
 #include "kernels_weld.h"
 #include "kernels_topo.h"
 #include "kernels_simplify.h"
+#include "kernels_simplify_adaptive.h"
 #include "abi_program.h"
 
 namespace {
@@ -758,6 +759,140 @@ extern "C" int gsdf_hip_indexed_simplify(gsdf_indexed* ix, const gsdf_simplify_o
     nx->n_verts = V2;
     nx->n_tris = F2;
     nx->ms_device = r.ms_cells + r.ms_faces;
+    *out = nx.release();
+  }
+  return GSDF_OK;
+}
+
+// ---- adaptive simplify (kernels_simplify_adaptive.h) ---------------------------------------------------------------------------------
+extern "C" int gsdf_hip_indexed_simplify_adaptive(gsdf_indexed* ix, const gsdf_adaptive_opts* o, gsdf_indexed** out, gsdf_adaptive_stats* st) {
+  if (out) *out = nullptr;
+  if (!o) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  if (!(o->cell > 0.0f) || !std::isfinite(o->cell)) return fail(GSDF_ERR_BAD_ARGUMENT, "adaptive simplify: the cell edge must be positive and finite");
+  if (!std::isfinite(o->origin[0]) || !std::isfinite(o->origin[1]) || !std::isfinite(o->origin[2]))
+    return fail(GSDF_ERR_BAD_ARGUMENT, "adaptive simplify: the origin must be finite");
+  if (!(o->tol >= 0.0f) || !std::isfinite(o->tol)) return fail(GSDF_ERR_BAD_ARGUMENT, "adaptive simplify: tol must be finite and not negative");
+  if (o->levels < 1 || o->levels > ADAPTIVE_MAX_LEVELS) return fail(GSDF_ERR_BAD_ARGUMENT, "adaptive simplify: levels must be 1 .. 16");
+  if (o->flags != 0) return fail(GSDF_ERR_BAD_ARGUMENT, "adaptive simplify: unknown flags " + std::to_string(o->flags));
+  if (!ix || (!out && !st)) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  HIP_TRY(hipSetDevice(ix->device));
+  const int dev = ix->device;
+  hipStream_t s = ix->stream;
+  const bool dry = out == nullptr;
+  const uint64_t V = ix->n_verts, F = ix->n_tris;
+  const unsigned levels = o->levels;
+  const double tol = (double)o->tol;
+  const unsigned nb_v = blocks_of(V), nb_f = blocks_of(F);
+  const char* nomem = "adaptive simplify: no device memory for the workspace";
+  PoolBuf ctr, used, vcell, vchoice, table, cpos, flag, keep, fcell, blk_cnt, blk_base, total, ukeys, first, vnum;
+  if (!ctr.take(dev, sizeof(AdaptiveCounters)) || !used.take(dev, V * 4) || !vcell.take(dev, (size_t)levels * V * 4) || !vchoice.take(dev, V * 4))
+    return fail(GSDF_ERR_HIP, nomem);
+  AdaptiveCounters* d_ctr = ctr.as<AdaptiveCounters>();
+  EventPair ev_c, ev_e, ev_f;
+  if (!ev_c.make() || !ev_e.make() || !ev_f.make()) return fail(GSDF_ERR_HIP, "hipEventCreate failed");
+  // 1. used vertices, the exponent, and ONE table for the cells of all levels: per cell the key (8 bytes), the label (4), the record
+  // (32), the error (8). A surface has about a quarter of a level's cells at the next one, so 3 V cells ask for a load below 0.5
+  // in nearly every case; where they do not, the table grows as every table here does.
+  HIP_TRY(hipEventRecord(ev_c.a, s));
+  HIP_TRY(hipMemsetAsync(d_ctr, 0, sizeof(AdaptiveCounters), s));
+  HIP_TRY(hipMemsetAsync(used.p, 0, V * 4, s));
+  LAUNCH(simplify_mark_kernel, nb_f, BLOCK, s, ix->idx.as<unsigned>(), (unsigned long long)F, used.as<unsigned>(), &d_ctr->head);
+  LAUNCH(topo_maxbits_kernel, grid_for(3 * V, ix->num_cu, 8), BLOCK, s, ix->verts.p, (unsigned long long)(3 * V), &d_ctr->head.maxbits);
+  TableRunOf<SimplifyHead> run;
+  auto tab_key = [&](uint64_t cells) { (void)cells; return table.as<unsigned long long>(); };
+  auto tab_label = [&](uint64_t cells) { return (unsigned*)((uint8_t*)table.p + cells * 8); };
+  auto tab_acc = [&](uint64_t cells) { return (SimplifyCell*)((uint8_t*)table.p + cells * 12); };
+  auto tab_err = [&](uint64_t cells) { return (unsigned long long*)((uint8_t*)table.p + cells * 44); };
+  if (int rc = table_build("adaptive simplify", "GSDF_HIP_SIMPLIFY_CELLS_MIN", (levels > 1 ? 3 : 2) * V, 52, dev, s, table, &d_ctr->head, [&](uint64_t cells) -> int {
+        HIP_TRY(hipMemsetAsync(table.p, 0xff, cells * 12, s));
+        HIP_TRY(hipMemsetAsync((uint8_t*)table.p + cells * 12, 0, cells * 40, s));
+        HIP_TRY(hipMemsetAsync(&d_ctr->head, 0, SIMPLIFY_HEAD_RESET_BYTES, s));
+        LAUNCH(adaptive_insert_kernel, grid_for(V, ix->num_cu, 16), BLOCK, s, ix->verts.p, used.as<unsigned>(), (unsigned long long)V, (double)o->origin[0],
+               (double)o->origin[1], (double)o->origin[2], (double)o->cell, levels, tab_key(cells), tab_label(cells), (unsigned)(cells - 1),
+               vcell.as<unsigned>(), &d_ctr->head);
+        return GSDF_OK;
+      }, &run))
+    return rc;
+  const SimplifyHead& hd = run.head;
+  if (hd.nonfinite)
+    return fail(GSDF_ERR_BAD_ARGUMENT, "adaptive simplify: " + std::to_string(hd.nonfinite) + " used vertices have a NaN or infinite coordinate");
+  if (hd.out_of_range)
+    return fail(GSDF_ERR_RESOLUTION, "adaptive simplify: the cell is too small for this mesh: vertex " + std::to_string(0xffffffffull - hd.first_bad) + " (and " +
+                                         std::to_string(hd.out_of_range - 1) + " more) lies 2^17 cells or more from the origin");
+  const uint64_t cells = run.cells;
+  const uint64_t ids = cells + V;  // cluster numbers: a table cell, or cells + v for a vertex that stays alone
+  if (cells > ((uint64_t)1 << 31) || ids >= 0xffffffffull) return fail(GSDF_ERR_CAPACITY, "adaptive simplify: hash table capacity exceeded");
+  const int biased = (int)(hd.maxbits >> 23);
+  const int e = (biased > 1 ? biased : 1) - 126;
+  if (!cpos.take(dev, ids * 12) || !flag.take(dev, ids * 4)) return fail(GSDF_ERR_HIP, nomem);
+  LAUNCH(adaptive_sum_kernel, nb_v, BLOCK, s, ix->verts.p, vcell.as<unsigned>(), (unsigned long long)V, levels, std::ldexp(1.0, 30 - e), tab_acc(cells));
+  LAUNCH(adaptive_place_kernel, grid_for(cells, ix->num_cu, 8), BLOCK, s, tab_key(cells), tab_label(cells), tab_acc(cells), (unsigned long long)cells, ix->verts.p,
+         std::ldexp(1.0, e - 30), cpos.p);
+  HIP_TRY(hipEventRecord(ev_c.b, s));
+  // 2. the cells' errors, and every vertex's choice
+  HIP_TRY(hipEventRecord(ev_e.a, s));
+  LAUNCH(adaptive_error_kernel, nb_f, BLOCK, s, ix->verts.p, ix->idx.as<unsigned>(), (unsigned long long)F, vcell.as<unsigned>(), (unsigned long long)V, levels,
+         cpos.p, tab_err(cells), tol);
+  LAUNCH(adaptive_choose_kernel, nb_v, BLOCK, s, vcell.as<unsigned>(), (unsigned long long)V, levels, tab_label(cells), tab_acc(cells), tab_err(cells), tol,
+         (unsigned)cells, vchoice.as<unsigned>(), &d_ctr->tail);
+  HIP_TRY(hipEventRecord(ev_e.b, s));
+  // 3. faces, as the uniform simplifier's with the choice where it has the cell. (The new handle's stream is made before the events.)
+  IndexedPtr nx;
+  if (!dry)
+    if (int rc = indexed_new(dev, ix->num_cu, &nx)) return rc;
+  if (!blk_cnt.take(dev, (size_t)blocks_of(3 * F) * 4) || !blk_base.take(dev, (size_t)blocks_of(3 * F) * 4) ||
+      (!dry && (!keep.take(dev, F) || !fcell.take(dev, 3 * F * 4) || !total.take(dev, 8) || !ukeys.take(dev, ids * 8) || !first.take(dev, ids * 4) ||
+                !vnum.take(dev, ids * 4))))
+    return fail(GSDF_ERR_HIP, nomem);
+  HIP_TRY(hipEventRecord(ev_f.a, s));
+  HIP_TRY(hipMemsetAsync(flag.p, 0, ids * 4, s));
+  LAUNCH(simplify_faces_kernel, nb_f, BLOCK, s, ix->idx.as<unsigned>(), (unsigned long long)F, vchoice.as<unsigned>(), flag.as<unsigned>(),
+         dry ? nullptr : keep.as<unsigned char>(), dry ? nullptr : fcell.as<unsigned>(), blk_cnt.as<unsigned>());
+  LAUNCH(block_scan_kernel, 1, 1024, s, blk_cnt.as<unsigned>(), nb_f, blk_base.as<unsigned>(), &d_ctr->tail.kept);
+  LAUNCH(adaptive_named_kernel, grid_for(ids, ix->num_cu, 8), BLOCK, s, flag.as<unsigned>(), (unsigned long long)ids, &d_ctr->tail);
+  AdaptiveTail tl{};
+  HIP_TRY(hipMemcpyAsync(&tl, &d_ctr->tail, sizeof tl, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  const uint64_t F2 = tl.kept;
+  if (hd.degenerate + F2 > F) return fail(GSDF_ERR_HIP, "adaptive simplify: internal error (the face counts do not add up)");
+  uint64_t V2 = 0;
+  if (!dry) {
+    if (F2 == 0) return fail(GSDF_ERR_EMPTY_BUFFERS, "adaptive simplify: nothing kept (every face collapsed: cell, tol and levels are too large for this mesh)");
+    const uint64_t S2 = 3 * F2;
+    const unsigned nb_s = blocks_of(S2);
+    if (!nx->idx.take(dev, S2 * 4)) return fail(GSDF_ERR_HIP, nomem);
+    // positions and keys by cluster number: the cells', then the input's own for the vertices that stay alone
+    HIP_TRY(hipMemcpyAsync(cpos.p + 3 * cells, ix->verts.p, V * 12, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(ukeys.p, tab_key(cells), cells * 8, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(ukeys.as<unsigned long long>() + cells, ix->vkeys.p, V * 8, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemsetAsync(first.p, 0xff, ids * 4, s));
+    LAUNCH(topo_compact_kernel, nb_f, BLOCK, s, fcell.as<unsigned>(), keep.as<unsigned char>(), (unsigned long long)F, blk_base.as<unsigned>(),
+           nx->idx.as<unsigned>(), first.as<unsigned>());
+    LAUNCH(topo_owner_kernel, nb_s, BLOCK, s, nx->idx.as<unsigned>(), (unsigned long long)S2, first.as<unsigned>(), blk_cnt.as<unsigned>());
+    if (int rc = scan_blocks(s, blk_cnt, nb_s, blk_base, total, &V2)) return rc;
+    if (V2 != tl.named) return fail(GSDF_ERR_HIP, "adaptive simplify: internal error (kept clusters)");
+    if (!nx->verts.take(dev, V2 * 12) || !nx->vkeys.take(dev, V2 * 8)) return fail(GSDF_ERR_HIP, nomem);
+    LAUNCH(topo_renumber_kernel, nb_s, BLOCK, s, nx->idx.as<unsigned>(), (unsigned long long)S2, first.as<unsigned>(), blk_base.as<unsigned>(), vnum.as<unsigned>(),
+           cpos.as<unsigned>(), ukeys.as<unsigned long long>(), (const unsigned*)nullptr, nx->verts.as<unsigned>(), nx->vkeys.as<unsigned long long>(),
+           (unsigned*)nullptr);
+    LAUNCH(remap_kernel, nb_s, BLOCK, s, nx->idx.as<unsigned>(), (unsigned long long)S2, vnum.as<unsigned>());
+  }
+  HIP_TRY(hipEventRecord(ev_f.b, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  gsdf_adaptive_stats r{};
+  r.n_verts_in = V; r.n_tris_in = F; r.used_verts_in = hd.used; r.degenerate_in = hd.degenerate; r.cells = hd.tab.distinct;
+  for (int l = 0; l < ADAPTIVE_MAX_LEVELS; l++) r.chosen[l] = tl.chosen[l];
+  r.singles = tl.singles; r.collapsed = F - hd.degenerate - F2;
+  r.n_verts = tl.named; r.n_tris = F2; r.largest_cluster = tl.largest;
+  std::memcpy(&r.max_err, &tl.max_err, 8);
+  r.exponent = e;
+  r.ms_cells = ev_c.ms(); r.ms_error = ev_e.ms(); r.ms_faces = ev_f.ms();
+  r.probes = hd.tab.probes; r.table_cells = cells; r.attempts = run.attempts;
+  if (st) *st = r;
+  if (!dry) {
+    nx->n_verts = V2;
+    nx->n_tris = F2;
+    nx->ms_device = r.ms_cells + r.ms_error + r.ms_faces;
     *out = nx.release();
   }
   return GSDF_OK;

@@ -29,7 +29,7 @@ SYMBOLS = ["gsdf_hip_last_error", "gsdf_hip_init", "gsdf_hip_program_create", "g
            "gsdf_hip_mesh_read_records", "gsdf_hip_mesh_weld", "gsdf_hip_indexed_counts", "gsdf_hip_indexed_stats_get", "gsdf_hip_indexed_read",
            "gsdf_hip_indexed_normals", "gsdf_hip_indexed_read_normals", "gsdf_hip_indexed_ply", "gsdf_hip_indexed_host_ply", "gsdf_hip_indexed_destroy",
            "gsdf_hip_indexed_create", "gsdf_hip_indexed_report", "gsdf_hip_indexed_shells", "gsdf_hip_indexed_read_shell_of", "gsdf_hip_indexed_extract",
-           "gsdf_hip_indexed_simplify", "gsdf_hip_indexed_project", "gsdf_hip_indexed_read_fit", "gsdf_hip_mesh_dualcontour_indexed"]
+           "gsdf_hip_indexed_simplify", "gsdf_hip_indexed_simplify_adaptive", "gsdf_hip_indexed_project", "gsdf_hip_indexed_read_fit", "gsdf_hip_mesh_dualcontour_indexed"]
 
 
 PRUNE_ASSUME_SDF = 1 << 30  # gsdf_hip.h: GSDF_PRUNE_ASSUME_SDF
@@ -110,6 +110,27 @@ class SimplifyStats(C.Structure):
                 ("ms_cells", C.c_double), ("ms_faces", C.c_double), ("probes", C.c_uint64), ("table_cells", C.c_uint64),
                 ("attempts", C.c_int32), ("reserved2", C.c_int32)]
     RESULT_BYTES = 80
+
+    def result_bytes(self):
+        return bytes(self)[:self.RESULT_BYTES]
+
+
+class AdaptiveOpts(C.Structure):
+    """gsdf_adaptive_opts (gsdf_hip.h): the finest cell's edge, the grids' origin, the error a cluster may have, the number of nested grids."""
+    _fields_ = [("cell", C.c_float), ("origin", C.c_float * 3), ("tol", C.c_float), ("levels", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class AdaptiveStats(C.Structure):
+    """gsdf_adaptive_stats (gsdf_hip.h): what an error-bounded clustering did; bytes 0 .. 223 (RESULT_BYTES) are a function of the mesh
+    and the options alone, the rest says what the run cost."""
+    _fields_ = [("n_verts_in", C.c_uint64), ("n_tris_in", C.c_uint64), ("used_verts_in", C.c_uint64), ("degenerate_in", C.c_uint64),
+                ("cells", C.c_uint64), ("chosen", C.c_uint64 * 16), ("singles", C.c_uint64), ("collapsed", C.c_uint64),
+                ("n_verts", C.c_uint64), ("n_tris", C.c_uint64), ("largest_cluster", C.c_uint64), ("max_err", C.c_double),
+                ("exponent", C.c_int32), ("reserved", C.c_int32),
+                ("ms_cells", C.c_double), ("ms_error", C.c_double), ("ms_faces", C.c_double), ("probes", C.c_uint64), ("table_cells", C.c_uint64),
+                ("attempts", C.c_int32), ("reserved2", C.c_int32)]
+    RESULT_BYTES = 224
 
     def result_bytes(self):
         return bytes(self)[:self.RESULT_BYTES]
@@ -257,6 +278,7 @@ def lib():
         L.gsdf_hip_indexed_read_shell_of.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.gsdf_hip_indexed_extract.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
         L.gsdf_hip_indexed_simplify.argtypes = [C.c_void_p, C.POINTER(SimplifyOpts), C.POINTER(C.c_void_p), C.POINTER(SimplifyStats)]
+        L.gsdf_hip_indexed_simplify_adaptive.argtypes = [C.c_void_p, C.POINTER(AdaptiveOpts), C.POINTER(C.c_void_p), C.POINTER(AdaptiveStats)]
         L.gsdf_hip_indexed_project.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(ProjectOpts), C.POINTER(C.c_void_p), C.POINTER(ProjectStats)]
         L.gsdf_hip_indexed_read_fit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.gsdf_hip_mesh_dualcontour_indexed.argtypes = [C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(MeshStats)]
@@ -812,6 +834,33 @@ class IndexedHIP:
                 return ix, st, cell
             cell = np.float32(cell * np.float32(2))
         raise ValueError(f"simplify_to: more than {max_tris} faces after 24 doublings of the cell {float(np.float32(cell0))!r}")
+
+    def simplify_adaptive(self, cell, tol, levels=8, origin=(0, 0, 0), dry=False):
+        """gsdf_hip_indexed_simplify_adaptive: the mesh with the used vertices of every chosen cell merged into one vertex at their mean,
+        a vertex's cell being the coarsest of its `levels` nested ones (edges cell, 2 cell, ..) whose mean stays within `tol` of the plane
+        of every face touching it: (a new IndexedHIP, AdaptiveStats). dry: the stats alone, (None, AdaptiveStats)."""
+        o = AdaptiveOpts(cell=np.float32(cell), origin=(C.c_float * 3)(*[np.float32(x) for x in origin]), tol=np.float32(tol), levels=int(levels))
+        st, h = AdaptiveStats(), C.c_void_p()
+        _check(lib().gsdf_hip_indexed_simplify_adaptive(self._h, C.byref(o), None if dry else C.byref(h), C.byref(st)))
+        return (None if dry else IndexedHIP(h)), st
+
+    def simplify_adaptive_to(self, max_tris, cell, tol0, levels=8, origin=(0, 0, 0)):
+        """The first of tol0, 2 tol0, 4 tol0, ... (float32 doubling: exact) whose adaptive simplification has at most max_tris faces, found
+        by dry runs (the count does not increase with tol); then that mesh: (IndexedHIP, AdaptiveStats, tol). ValueError for tol0 <= 0,
+        after 24 doublings, or once nothing would be kept."""
+        tol = np.float32(tol0)
+        if not tol > 0:
+            raise ValueError(f"simplify_adaptive_to: tol0 must be positive to be doubled, not {float(tol)!r}")
+        for _ in range(25):
+            _, st = self.simplify_adaptive(cell, tol, levels, origin, dry=True)
+            if st.n_tris == 0:
+                raise ValueError(f"simplify_adaptive_to: nothing is kept at tol {float(tol)!r}, and every smaller tol tried keeps more than {max_tris} faces")
+            if st.n_tris <= max_tris:
+                ix, st = self.simplify_adaptive(cell, tol, levels, origin)
+                return ix, st, tol
+            tol = np.float32(tol * np.float32(2))
+        raise ValueError(f"simplify_adaptive_to: more than {max_tris} faces after 24 doublings of tol {float(np.float32(tol0))!r} "
+                         f"(cells of at most {1 << (int(levels) - 1)} x {float(np.float32(cell))!r}: raise levels or the cell)")
 
     def project(self, sdf, step, tol, max_move, max_iters=8, dry=False):
         """gsdf_hip_indexed_project: the mesh with every vertex moved onto the zero set of `sdf` (an SDF3HIP) by up to max_iters Newton

@@ -654,8 +654,9 @@ int gsdf_hip_indexed_extract(gsdf_indexed* ix, const uint8_t* keep_shell, int dr
  * gsdf_simplify_stats. Bytes 0 .. 79 (n_verts_in .. reserved) are a function of the mesh and the options alone; the rest says what
  *   this run cost. GSDF_HIP_SIMPLIFY_CELLS_MIN (environment) lowers the cluster table's first size so that tests can drive the
  *   grow-and-repeat path, as GSDF_HIP_TOPO_CELLS_MIN does.
- * Not done here: adaptive (quadric edge-collapse) simplification, QEF placement of the representative, removing duplicate or opposite
- *   faces. (Projecting the representatives back onto the field: gsdf_hip_indexed_project, below.) */
+ * Not done here: quadric edge-collapse, QEF placement of the representative, removing duplicate or opposite faces. (Adaptive
+ *   simplification, by error-bounded clustering over nested cells: "indexed meshes: adaptive simplify", below. Projecting the
+ *   representatives back onto the field: gsdf_hip_indexed_project, below.) */
 typedef struct gsdf_simplify_opts {
   float cell;        /* cell edge, > 0 and finite */
   float origin[3];   /* where cell (0, 0, 0) starts; finite */
@@ -684,6 +685,101 @@ GSDF_ABI_ASSERT(sizeof(gsdf_simplify_stats) == 120, "gsdf_simplify_stats is 120 
 GSDF_ABI_ASSERT(offsetof(gsdf_simplify_stats, cells) == 32 && offsetof(gsdf_simplify_stats, n_verts) == 48, "gsdf_simplify_stats counts");
 GSDF_ABI_ASSERT(offsetof(gsdf_simplify_stats, exponent) == 72 && offsetof(gsdf_simplify_stats, ms_cells) == 80, "gsdf_simplify_stats cost");
 int gsdf_hip_indexed_simplify(gsdf_indexed* ix, const gsdf_simplify_opts* o, gsdf_indexed** out, gsdf_simplify_stats* st);
+
+/* ---- indexed meshes: adaptive simplify (no reference counterpart) -----------------------------------------------------------------
+ *
+ * A smaller mesh by ERROR-BOUNDED CLUSTERING over nested grids: where the uniform simplifier above has one cell size for the whole
+ * part, this one merges the vertices of the COARSEST cell, out of `levels` nested ones, whose mean stays within `tol` of the plane
+ * of every face that touches the cell. A flat face collapses into cells of 2^(levels-1) finest cells; a thread flank keeps the
+ * finest cells, or its vertices. Like every stage here, and unlike edge-collapse, the result is a function of the mesh and the
+ * options alone, to the bit: integer sums, minima and maxima only. Kernels: gsdf_amd/csrc/kernels_simplify_adaptive.h
+ * (abi_indexed.hip); a numpy restatement: tests/adaptiveref.py.
+ *
+ * Input. Any gsdf_indexed handle and gsdf_adaptive_opts: cell (the FINEST cell's edge) > 0 and finite, origin finite, tol >= 0 and
+ *   finite, levels 1 .. 16, flags == 0 -- anything else is GSDF_ERR_BAD_ARGUMENT, checked before the handle is looked at. Used
+ *   vertices, degenerate faces and non-finite used vertices (GSDF_ERR_BAD_ARGUMENT): as in "simplify". The advice on the origin for a
+ *   welded mesh holds here too.
+ * Nested cells. The level-0 cell of a vertex is c_k of "simplify", computed exactly so (two float64 operations and a floor). Some
+ *   |c_k| >= 2^17: GSDF_ERR_RESOLUTION, the text names the smallest such vertex. Its level-l cell is c_k >> l, an ARITHMETIC shift
+ *   (floor of c_k / 2^l), l = 0 .. levels-1: a level-(l+1) cell is the union of 8 level-l cells, exactly.
+ * Key of a cell. ((c_x >> l) + 2^17) | ((c_y >> l) + 2^17) << 18 | ((c_z >> l) + 2^17) << 36 | l << 54 | 6 << 60: kind 6, after the
+ *   weld's kinds 0 .. 3, the simplifier's 4 and dual contouring's 5. Its top four bits are 0110: never the hash table's empty value.
+ * Position of a cell, at every level: the "simplify" formula over the used vertices in the cell, verbatim. n == 1: that vertex's
+ *   bits. n > 1: q_k = rint((double)x_k * 2^(30-e)), S_k their integer sum, position_k = (float)(((double)S_k / (double)n) * 2^(e-30)),
+ *   e the report's exponent of the input.
+ * Error of a cell. The largest distance from the cell's position r (float32, widened) to the plane of a NON-DEGENERATE face that has
+ *   a corner in the cell -- in float64, nothing contracted, from the float32 vertices pa, pb, pc of the face widened:
+ *     u = pb - pa, w = pc - pa                                     (one float64 subtraction per coordinate)
+ *     n = (u_y w_z - u_z w_y, u_z w_x - u_x w_z, u_x w_y - u_y w_x)
+ *     L = sqrt((n_x n_x + n_y n_y) + n_z n_z)                      a face with !(L > 0) has no plane and contributes nothing
+ *     g = r - pa
+ *     t = |(n_x g_x + n_y g_y) + n_z g_z| / L
+ *     err(cell) = max t over the (face, corner) pairs whose corner's vertex is in the cell; 0 where there is none
+ *   No intermediate overflows: |x| < 2^128 for a finite float32, so |u_k|, |w_k|, |g_k| < 2^129, a product < 2^258, |n_k| < 2^259,
+ *   n_k n_k < 2^518, their sum < 2^520, L < 2^260, |n . g| < 3 * 2^388 < 2^390 -- all far below 2^1024. Squares may UNDERFLOW:
+ *   a sliver's L is then 0 (the face has no plane) or, if positive, at least 2^-537 (the root of the smallest subnormal), so the
+ *   quotient t stays below 2^390 * 2^537 = 2^927: finite.
+ *   The maximum is order-independent: non-negative float64 order as their bit patterns, so a 64-bit unsigned maximum gives the same
+ *   bytes in any order of arrival.
+ * Choice. A cell is ACCEPTED iff err <= (double)tol. A vertex's cluster is its ancestor cell (its own cells at levels 0 .. levels-1)
+ *   at the LARGEST accepted level; the cells below it need not be accepted. A vertex with no accepted ancestor, or whose cluster has
+ *   n == 1, is SINGLE: it keeps its position bits and its INPUT key (the handle's key of that vertex). The grids nest, so all
+ *   vertices of a chosen cell choose it: the clusters and the singles are a partition of the used vertices. Raising tol or levels
+ *   only coarsens the partition (every cluster of the finer one lies inside one cluster of the coarser one): an accepted cell stays
+ *   accepted under a larger tol, and a new level only adds candidates above the old ones. Hence n_verts and n_tris do not increase
+ *   along either.
+ * Faces, vertices of the result, nothing kept: as in "simplify", with the cluster or the single where it has the cluster. Degenerate
+ *   and collapsed faces are dropped, the rest stay in order; result vertices are numbered by the smallest kept slot; nothing is
+ *   deduplicated and the report of the result tells the truth; has_normals == 0. Nothing kept: GSDF_ERR_EMPTY_BUFFERS.
+ * With levels == 1 and a tol no error exceeds, positions, faces and numbering are those of "simplify" with the same cell and origin.
+ * An accepted cell that spans a wall thinner than 2 tol collapses the wall, as a uniform cell does.
+ *
+ * gsdf_hip_indexed_simplify_adaptive(ix, o, out, st): as gsdf_hip_indexed_simplify; out == NULL with st != NULL is a DRY RUN with the
+ *   same leading stats, GSDF_OK with n_tris == 0 where nothing would be kept. Both NULL: GSDF_ERR_BAD_ARGUMENT.
+ * gsdf_adaptive_stats. Bytes 0 .. 223 (n_verts_in .. reserved) are a function of the mesh and the options alone; the rest says what
+ *   this run cost. Only an accepted cell's error is complete (the kernel stops raising a cell's word once it is beyond tol), and
+ *   only those reach max_err. GSDF_HIP_SIMPLIFY_CELLS_MIN lowers this table's first size too.
+ * Run to run. A welded mesh's last bits vary with the mesher's record order (see "simplify"), and here they can also flip an
+ *   err <= tol decision, so two welds of one part may differ in a few clusters. A handle from gsdf_hip_mesh_dualcontour_indexed
+ *   does not vary, so its adaptive result is reproducible byte for byte.
+ * Not done here: edge-collapse, QEF placement, removing duplicate or opposite faces, un-flipping folded faces. */
+typedef struct gsdf_adaptive_opts {
+  float cell;        /* the finest cell's edge, > 0 and finite */
+  float origin[3];   /* where cell (0, 0, 0) of every level starts; finite */
+  float tol;         /* the largest accepted error, >= 0 and finite */
+  uint32_t levels;   /* 1 .. 16 nested grids: cells of 1, 2, .. 2^(levels-1) finest cells */
+  uint32_t flags;    /* 0; others refused */
+  uint32_t reserved;
+} gsdf_adaptive_opts;
+GSDF_ABI_ASSERT(sizeof(gsdf_adaptive_opts) == 32, "gsdf_adaptive_opts is 32 bytes");
+GSDF_ABI_ASSERT(offsetof(gsdf_adaptive_opts, origin) == 4 && offsetof(gsdf_adaptive_opts, tol) == 16 && offsetof(gsdf_adaptive_opts, levels) == 20 &&
+                offsetof(gsdf_adaptive_opts, flags) == 24, "gsdf_adaptive_opts fields");
+typedef struct gsdf_adaptive_stats {
+  uint64_t n_verts_in, n_tris_in;
+  uint64_t used_verts_in, degenerate_in;
+  uint64_t cells;            /* distinct cells of the used vertices, over all levels */
+  uint64_t chosen[16];       /* chosen clusters of more than one vertex, per level */
+  uint64_t singles;          /* used vertices that stay alone */
+  uint64_t collapsed;        /* non-degenerate faces with fewer than three distinct clusters */
+  uint64_t n_verts, n_tris;  /* of the result: clusters and singles a kept face names; n_tris_in - degenerate_in - collapsed */
+  uint64_t largest_cluster;  /* the largest n chosen (1 where every used vertex stays alone, 0 where none is used) */
+  double max_err;            /* the largest error of a chosen cluster of more than one vertex; 0 where there is none */
+  int32_t exponent;          /* e of the contract */
+  int32_t reserved;
+  double ms_cells;           /* device time, HIP events: used marks, exponent, table (all attempts), sums, positions */
+  double ms_error;           /* the cells' errors, the choice */
+  double ms_faces;           /* face pass; compaction, numbering, remap (not in a dry run) */
+  uint64_t probes;           /* table cells inspected by the inserting pass that succeeded */
+  uint64_t table_cells;      /* its capacity (a power of two, >= 2 cells) */
+  int32_t attempts;          /* inserting passes run */
+  int32_t reserved2;
+} gsdf_adaptive_stats;
+GSDF_ABI_ASSERT(sizeof(gsdf_adaptive_stats) == 272, "gsdf_adaptive_stats is 272 bytes");
+GSDF_ABI_ASSERT(offsetof(gsdf_adaptive_stats, cells) == 32 && offsetof(gsdf_adaptive_stats, chosen) == 40 && offsetof(gsdf_adaptive_stats, singles) == 168,
+                "gsdf_adaptive_stats counts");
+GSDF_ABI_ASSERT(offsetof(gsdf_adaptive_stats, n_verts) == 184 && offsetof(gsdf_adaptive_stats, max_err) == 208 && offsetof(gsdf_adaptive_stats, exponent) == 216 &&
+                offsetof(gsdf_adaptive_stats, ms_cells) == 224, "gsdf_adaptive_stats result and cost");
+int gsdf_hip_indexed_simplify_adaptive(gsdf_indexed* ix, const gsdf_adaptive_opts* o, gsdf_indexed** out, gsdf_adaptive_stats* st);
 
 /* ---- indexed meshes: project onto the field (no reference counterpart) -------------------------------------------------------------
  *

@@ -239,6 +239,57 @@ func (ix *IndexedHIP) Simplify(cell float32, origin ms3.Vec, dry bool) (*Indexed
 	return nx, stats, nil
 }
 
+// AdaptiveStats is gsdf_adaptive_stats: what an error-bounded clustering over nested cells did, and its device time. Chosen is
+// indexed by the level: the clusters of more than one vertex chosen there.
+type AdaptiveStats struct {
+	VIn, FIn, UsedVIn, DegenerateIn          uint64
+	Cells                                    uint64
+	Chosen                                   [16]uint64
+	Singles, Collapsed, V, F, LargestCluster uint64
+	MaxErr                                   float64
+	CellsMillis, ErrorMillis, FacesMillis    float64
+}
+
+// SimplifyAdaptive returns a new, independent mesh in which the used vertices of every chosen cell are merged into one vertex at
+// their mean and the faces that collapse are dropped: a vertex's cell is the coarsest of its `levels` nested cells (edges cell,
+// 2 cell, 4 cell, ..; cell (0, 0, 0) of every level starting at origin) whose mean stays within tol of the plane of every face
+// that touches the cell (gsdf_hip.h states every term). With dry set nothing is built: the mesh returned is nil and the stats say
+// what the result would be.
+func (ix *IndexedHIP) SimplifyAdaptive(cell, tol float32, levels int, origin ms3.Vec, dry bool) (*IndexedHIP, AdaptiveStats, error) {
+	if levels < 0 {
+		levels = 0 // (refused by the library, with its text)
+	}
+	ao := C.gsdf_adaptive_opts{cell: C.float(cell), tol: C.float(tol), levels: C.uint32_t(levels)}
+	ao.origin[0], ao.origin[1], ao.origin[2] = C.float(origin.X), C.float(origin.Y), C.float(origin.Z)
+	var as C.gsdf_adaptive_stats
+	var h *C.gsdf_indexed
+	out := &h
+	if dry {
+		out = nil
+	}
+	if rc := C.gsdf_hip_indexed_simplify_adaptive(ix.h, &ao, out, &as); rc != 0 {
+		return nil, AdaptiveStats{}, hipErr(rc)
+	}
+	stats := AdaptiveStats{
+		VIn: uint64(as.n_verts_in), FIn: uint64(as.n_tris_in), UsedVIn: uint64(as.used_verts_in), DegenerateIn: uint64(as.degenerate_in),
+		Cells: uint64(as.cells), Singles: uint64(as.singles), Collapsed: uint64(as.collapsed), V: uint64(as.n_verts), F: uint64(as.n_tris),
+		LargestCluster: uint64(as.largest_cluster), MaxErr: float64(as.max_err),
+		CellsMillis: float64(as.ms_cells), ErrorMillis: float64(as.ms_error), FacesMillis: float64(as.ms_faces),
+	}
+	for l := range stats.Chosen {
+		stats.Chosen[l] = uint64(as.chosen[l])
+	}
+	if dry {
+		return nil, stats, nil
+	}
+	nx := &IndexedHIP{h: h}
+	var nv, nf C.uint64_t
+	var ms C.double
+	C.gsdf_hip_indexed_counts(h, &nv, &nf, &ms)
+	nx.V, nx.F, nx.WeldMillis = uint64(nv), uint64(nf), float64(ms)
+	return nx, stats, nil
+}
+
 // ProjectStats is gsdf_project_stats: what a projection of the vertices onto a field did, and its device time. Count is indexed by
 // the status byte: skipped, on, converged, iters, flat, clamped, nonfinite, reverted.
 type ProjectStats struct {
