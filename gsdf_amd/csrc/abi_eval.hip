@@ -51,7 +51,7 @@ extern "C" int gsdf_hip_program_create(const gsdf_tree* tree, gsdf_program** out
   if (hipGetDevice(&p->device) != hipSuccess) return cleanup(fail(GSDF_ERR_HIP, "hipGetDevice failed"));
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, p->device) == hipSuccess) p->num_cu = prop.multiProcessorCount;
-  if (p->lds_bytes(p->batch_k()) + 8 * BLOCK * 4 + 4096 + TRI_STAGE * 36 + 64 > 160 * 1024) return cleanup(fail(GSDF_ERR_BAD_TREE, "tree needs more LDS scratch than one CU has"));
+  if (p->lds_bytes(p->batch_k()) + gsdf_program::kCreateExtra > gsdf_program::kLdsPerCu) return cleanup(fail(GSDF_ERR_BAD_TREE, "tree needs more LDS scratch than one CU has"));
   if (hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking) != hipSuccess) return cleanup(fail(GSDF_ERR_HIP, "hipStreamCreate failed"));
   size_t bytes = p->prog.code.size() * sizeof(uint32_t);
   if (hipMalloc((void**)&p->d_code, bytes) != hipSuccess) return cleanup(fail(GSDF_ERR_HIP, "hipMalloc(program) failed"));
@@ -568,6 +568,12 @@ extern "C" int gsdf_hip_program_kernels(const gsdf_program* p, char* dst, size_t
   }
   if (!p->prog.is2d && strlen(buf) + 48 < sizeof buf)  // the projection of mesh vertices (a specialised handle builds its own at its first projection)
     snprintf(buf + strlen(buf), sizeof buf - strlen(buf), " project=project_kernel:%s", p->f_project ? "specialised" : "interpreter");
+  if (strlen(buf) + 160 < sizeof buf) {  // the sweeps that carry a K of their own, and what the LDS limits of the meshers count (gsdf_hip.h: Largest trees)
+    const int dk = ek, dw = gsdf_program::dc_origin_waves(ek);  // (the rule gsdf_hip_mesh_dualcontour launches by; flat: sweep_waves, as its launch)
+    if (p->prog.is2d) snprintf(buf + strlen(buf), sizeof buf - strlen(buf), " image=image2_kernel<%d>:%s", ek, p->f_image ? "specialised" : "interpreter");
+    else snprintf(buf + strlen(buf), sizeof buf - strlen(buf), " flat=flat_grid_kernel<%d,%d>:%s dc=dc_origin_kernel<%d,%d>:%s interval=%d", ek, p->sweep_waves(ek),
+                  p->f_flat_grid ? "specialised" : "interpreter", dk, dw, p->f_dc_origin ? "specialised" : "interpreter", p->prog.lip_depth);
+  }
   if (p->spec_mod && strlen(buf) + 32 < sizeof buf) { strcat(buf, " compiler="); strcat(buf, p->spec_compiler.c_str()); }
   {  // identity of the code that runs: a stored profile describes this handle's kernels only if it carries the same key
     const std::string key = p->spec_mod ? p->spec_key : gsdf_dev::spec_library_key();
@@ -960,6 +966,7 @@ extern "C" int gsdf_hip_normals3(gsdf_program* p, const float* pos, float* norma
   if (!(step > 0)) return fail(GSDF_ERR_BAD_ARGUMENT, "invalid step");
   if (n == 0) return fail(GSDF_ERR_EMPTY_BUFFERS, "empty buffers");
   if (p->prog.is2d) return fail(GSDF_ERR_DIMENSION, "program is 2D");
+  if (int rc = p->normals_refused("gsdf_hip_normals3")) return rc;
   HIP_TRY(hipSetDevice(p->device));
   spec_adopt(p);  // (a background build that has finished: its kernels from here on)
   float *d_p = nullptr, *d_n = nullptr;
@@ -991,6 +998,7 @@ int normals3_dev(gsdf_program* p, const float* d_pos, float* d_nrm, size_t n, fl
   if (!(step > 0)) return fail(GSDF_ERR_BAD_ARGUMENT, "invalid step");
   if (n == 0) return fail(GSDF_ERR_EMPTY_BUFFERS, "empty buffers");
   if (p->prog.is2d) return fail(GSDF_ERR_DIMENSION, "program is 2D");
+  if (int rc = p->normals_refused("the normals of an indexed mesh")) return rc;
   HIP_TRY(hipSetDevice(p->device));
   spec_adopt(p);
   spec_aux(p);
@@ -1014,6 +1022,7 @@ int project_dev(gsdf_program* p, const float* d_pos, size_t n, const gsdf_projec
   if (n == 0) return fail(GSDF_ERR_EMPTY_BUFFERS, "empty buffers");
   if (n >= ((size_t)1 << 32)) return fail(GSDF_ERR_CAPACITY, "project: vertices must stay below 2^32");
   if (p->prog.is2d) return fail(GSDF_ERR_DIMENSION, "program is 2D");
+  if (int rc = p->normals_refused("gsdf_hip_indexed_project")) return rc;
   HIP_TRY(hipSetDevice(p->device));
   spec_adopt(p);
   spec_project(p);

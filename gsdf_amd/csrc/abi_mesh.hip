@@ -433,6 +433,18 @@ static void job_release(gsdf_mesh_job* j, bool failed = true) {
   delete j;
 }
 
+// LDS of the centre tests (kernels_octree.h: prune_kernel): two points per lane over the program's slots and its interval stack, the
+// stage of PRUNE_STAGE cubes, the wave totals. prune_spec_kernel declares a stage of SPEC_STAGE cubes and a few words statically.
+static constexpr size_t lds_prune_of(int cols) { return (size_t)(cols > 0 ? cols : 1) * 2 * BLOCK * sizeof(float) + PRUNE_STAGE * sizeof(Cube) + 64; }
+static constexpr size_t kPruneSpecStatic = SPEC_STAGE * sizeof(Cube) + 256;
+static_assert(lds_prune_of(GSDF_HIP_MAX_COLS_OCTREE) + kPruneSpecStatic <= gsdf_program::kLdsPerCu && lds_prune_of(GSDF_HIP_MAX_COLS_OCTREE + 1) + kPruneSpecStatic > gsdf_program::kLdsPerCu,
+              "gsdf_hip.h: GSDF_HIP_MAX_COLS_OCTREE is the largest slots + interval stack the centre tests fit into a CU's LDS");
+// dual contouring's edge pass: three points per lane and what dc_edges_kernel declares statically (s_pend .. s_word)
+static constexpr size_t lds_dc_edges_of(int slots) { return (size_t)(slots > 0 ? slots : 1) * 3 * BLOCK * sizeof(float) + DC_EDGE_PASSES * BLOCK * sizeof(uint16_t) + 64; }
+static_assert(lds_dc_edges_of(GSDF_HIP_MAX_SLOTS_DC) <= gsdf_program::kLdsPerCu && lds_dc_edges_of(GSDF_HIP_MAX_SLOTS_DC + 1) > gsdf_program::kLdsPerCu,
+              "gsdf_hip.h: GSDF_HIP_MAX_SLOTS_DC is the largest slot count the edge pass fits into a CU's LDS");
+static_assert(GSDF_HIP_MAX_SLOTS_ALL + 16 == GSDF_HIP_MAX_COLS_OCTREE && GSDF_HIP_MAX_SLOTS_ALL <= GSDF_HIP_MAX_SLOTS_DC, "gsdf_hip.h: GSDF_HIP_MAX_SLOTS_ALL");
+
 extern "C" int gsdf_hip_mesh_octree_start(gsdf_program* p, float res, const gsdf_mesh_opts* opts_in, gsdf_mesh_job** out) {
   if (!p || !out) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
   *out = nullptr;
@@ -452,6 +464,15 @@ extern "C" int gsdf_hip_mesh_octree_start(gsdf_program* p, float res, const gsdf
   if (opts.share_corners == 3) opts.share_corners = gsdf_dev::spec_xy_shared_weight(p->prog) < 3 ? 1 : 2;
   if (want_recs && (opts.host_output || opts.max_tris || fused_leaf()))
     return fail(GSDF_ERR_BAD_ARGUMENT, "payload = records goes with the two-kernel leaf phase only (no host_output, max_tris, fused leaf kernel)");
+  {
+    // the largest launch of the descent: prune_spec_kernel (lds_prune_of and its static stage of SPEC_STAGE cubes); of the leaf phase:
+    // the evaluating kernel with its case table (and what its marching half declares statically)
+    int lk0, lw0;
+    size_t lds_leaf;
+    p->leaf_config(&lk0, &lw0, &lds_leaf);
+    const size_t need_prune = lds_prune_of(p->prog.nslots + p->prog.lip_depth) + kPruneSpecStatic, need_leaf = lds_leaf + 256 + 1024;
+    if (int rc = p->lds_refused("gsdf_hip_mesh_octree", need_prune > need_leaf ? need_prune : need_leaf, "slots + interval stack <= " + std::to_string(GSDF_HIP_MAX_COLS_OCTREE))) return rc;
+  }
   HIP_TRY(hipSetDevice(p->device));
 
   // Octree.Reset (octreerenderer.go:71-128) + makeICube (:222-235)
@@ -507,7 +528,7 @@ extern "C" int gsdf_hip_mesh_octree_start(gsdf_program* p, float res, const gsdf
   // multi-GPU: bricks of level ls are dealt to ranks by a hash of their coordinates (brick_owner).
   j->ls = levels < j->lq + 2 ? levels : j->lq + 2;
   j->prune_cols = p->prog.nslots + p->prog.lip_depth;  // interval mode: two points per lane + the interval stack
-  j->lds_prune = (size_t)(j->prune_cols > 0 ? j->prune_cols : 1) * 2 * BLOCK * sizeof(float) + PRUNE_STAGE * sizeof(Cube) + 64;
+  j->lds_prune = lds_prune_of(j->prune_cols);
   j->pmask = opts.prune & ~GSDF_PRUNE_ASSUME_SDF;  // levels to test: 0 none, 1 all, else bit L = Level L
   if ((opts.prune & GSDF_PRUNE_ASSUME_SDF) && j->pmask == 0) j->pmask = 1;
   j->ptest = (opts.prune & GSDF_PRUNE_ASSUME_SDF) ? 2 : 1;
@@ -683,6 +704,12 @@ static int dc_mesh(gsdf_program* p, float res, int chiseled, int shard_rank, int
   if (!(res > 0) || std::isnan(res) || std::isinf(res)) return fail(GSDF_ERR_RESOLUTION, "invalid renderer cube resolution");
   if (shard_count < 1 || shard_rank < 0 || shard_rank >= shard_count) return fail(GSDF_ERR_BAD_ARGUMENT, "bad shard rank/count");
   if (p->mesh_in_flight()) return fail(GSDF_ERR_BAD_ARGUMENT, "an octree mesh of this program is in flight: wait for it first (shared workspace)");
+  {
+    // the largest launch: dc_edges_kernel (three points per lane + 2104 bytes declared statically: s_pend .. s_word), unless a forced
+    // batch size makes it the origin sweep (K points per lane + 32 bytes)
+    const size_t need_edges = lds_dc_edges_of(p->prog.nslots), need_origin = p->lds_bytes(p->batch_k()) + 32;
+    if (int rc = p->lds_refused("dual contouring", need_edges > need_origin ? need_edges : need_origin, std::to_string(GSDF_HIP_MAX_SLOTS_DC) + " slots")) return rc;
+  }
   HIP_TRY(hipSetDevice(p->device));
   hipStream_t s = stream ? (hipStream_t)stream : p->stream;
   // Reset (dual_contour.go:26-41): bounds shifted by -res/2, makeICube
@@ -799,9 +826,10 @@ static int dc_mesh(gsdf_program* p, float res, int chiseled, int shard_rank, int
     const uint32_t* d_keep = nullptr;
     {
       const uint64_t nblk = (uint64_t)tn[0] * tn[1] * tn[2] * 4ull;
-      if (!block_test_off && nblk > 0 && p->dc_tile.ensure((size_t)nblk * sizeof(uint32_t)) == hipSuccess) {
-        const int cols = p->prog.nslots + p->prog.lip_depth;
-        const size_t lds_t = (size_t)(cols > 0 ? cols : 1) * 2 * BLOCK * sizeof(float);
+      const int cols = p->prog.nslots + p->prog.lip_depth;
+      const size_t lds_t = (size_t)(cols > 0 ? cols : 1) * 2 * BLOCK * sizeof(float);
+      // (a tree whose interval stack makes the test ask for more LDS than a CU has goes without it: every block is evaluated)
+      if (!block_test_off && nblk > 0 && lds_t <= gsdf_program::kLdsPerCu && p->dc_tile.ensure((size_t)nblk * sizeof(uint32_t)) == hipSuccess) {
         const unsigned gt = grid_for(nblk, p->num_cu, 8);
         if (p->f_dc_block_test) HIP_TRYM(launch_fn(p->f_dc_block_test, gt, BLOCK, lds_t, s, (const uint32_t*)p->d_code, (int)cols, (int)p->prog.nslots, (int)lk, ox, oy, oz, res,
                                                     (unsigned)zlo, t0[0], t0[1], t0[2], tn[0], tn[1], tn[2], (uint32_t*)p->dc_tile.p));
@@ -819,13 +847,16 @@ static int dc_mesh(gsdf_program* p, float res, int chiseled, int shard_rank, int
     }
     if (p->f_dc_origin) HIP_TRYM(launch_fn(p->f_dc_origin, g1, BLOCK, p->lds_bytes(lk) + 32, s, (const uint32_t*)p->d_code, (int)p->prog.nslots, (int)nshift, ox, oy, oz, res, (int*)grid.p, (Cube*)p->q0.p, (unsigned long long)ccap, (unsigned)zlo, (unsigned)zhi, ub, eb[0], eb[1], eb[2], eb[3], eb[4], eb[5], t0[0], t0[1], t0[2], tn[0], tn[1], tn[2], d_ctr, d_keep));
     else
-    if (lk == 4) LAUNCH_O(4, 3);  // <4, 4> needs scratch: not built (see fn_scratch_bytes)
-    else if (lk == 2) LAUNCH_O(2, 3);  // (<2, 4> sits at its register budget: with the block verdicts' pointer it spills four VGPRs, and a kernel with scratch is not shipped)
-    else LAUNCH_O(1, 4);
+    {  // (W by gsdf_program::dc_origin_waves, the rule gsdf_hip_program_kernels reports by)
+      const int ow = gsdf_program::dc_origin_waves(lk);
+      if (lk == 4 && ow == 3) LAUNCH_O(4, 3);  // <4, 4> needs scratch: not built (see fn_scratch_bytes)
+      else if (lk == 2 && ow == 3) LAUNCH_O(2, 3);  // (<2, 4> sits at its register budget: with the block verdicts' pointer it spills four VGPRs, and a kernel with scratch is not shipped)
+      else if (lk == 1 && ow == 4) LAUNCH_O(1, 4);
+      else return bail(fail(GSDF_ERR_BAD_ARGUMENT, "dual contouring: no origin sweep built for this K and W"));
+    }
 #undef LAUNCH_O
     HIP_TRYM(hipGetLastError());
     HIP_TRYM(hipEventRecord(p->ev_b[0], s));  // origin sweep done
-    if (p->lds_bytes(4) > 150 * 1024) return bail(fail(GSDF_ERR_BAD_TREE, "tree needs too much LDS scratch for the dual contouring edge pass"));
     // (a multiple of DC_PARTS like the sweep's grid: run r goes to workgroup r % grid, hence to the edge list's part r % DC_PARTS --
     // what bounds a part's edge-run descriptors, dc_edge_run_seg)
     const unsigned g_edges = (grid_for(ccap, p->num_cu, 8) + DC_PARTS - 1) / DC_PARTS * DC_PARTS;

@@ -127,6 +127,27 @@ struct gsdf_program {
     return !(4 * rows_e <= 160 * 1024 && 4 * (rows_e + 256) > 160 * 1024);
   }
   size_t lds_bytes(int k = 1) const { return (size_t)(prog.nslots > 0 ? prog.nslots : 1) * k * BLOCK * sizeof(float); }
+  // The largest trees (gsdf_hip.h: "Largest trees"). A workgroup may ask for a CU's whole LDS and no more; an entry point whose
+  // kernels would ask for more refuses the tree on the host, before its first launch: lds_refused(what, dynamic + static bytes of
+  // its most demanding launch, the slot limit that follows from them) is GSDF_OK or GSDF_ERR_BAD_TREE with the limit in the message.
+  static constexpr size_t kLdsPerCu = (size_t)160 * 1024;
+  int lds_refused(const char* what, size_t need, const std::string& limit) const {
+    if (need <= kLdsPerCu) return GSDF_OK;
+    return fail(GSDF_ERR_BAD_TREE, std::string("tree too large for ") + what + ": " + std::to_string(prog.nslots) + " slots (interval stack " +
+                std::to_string(prog.lip_depth) + ") need " + std::to_string(need) + " bytes of LDS per workgroup, a CU has " + std::to_string(kLdsPerCu) +
+                " (limit: " + limit + ")");
+  }
+  // normals_kernel, project_kernel, dc_normals_kernel: two points per lane, no static LDS
+  int normals_refused(const char* what) const { return lds_refused(what, lds_bytes(2), std::to_string(GSDF_HIP_MAX_SLOTS_NORMALS) + " slots"); }
+  static_assert((size_t)GSDF_HIP_MAX_SLOTS_NORMALS * 2 * BLOCK * sizeof(float) <= kLdsPerCu && (size_t)(GSDF_HIP_MAX_SLOTS_NORMALS + 1) * 2 * BLOCK * sizeof(float) > kLdsPerCu,
+                "gsdf_hip.h: GSDF_HIP_MAX_SLOTS_NORMALS is the largest slot count whose two points per lane fit a CU's LDS");
+  // what gsdf_hip_program_create adds to one point per lane (a brick's eight rows, the fused leaf kernel's stages)
+  static constexpr size_t kCreateExtra = 8 * BLOCK * 4 + 4096 + TRI_STAGE * 36 + 64;
+  static_assert((size_t)GSDF_HIP_MAX_SLOTS_CREATE * BLOCK * sizeof(float) + kCreateExtra <= kLdsPerCu && (size_t)(GSDF_HIP_MAX_SLOTS_CREATE + 1) * BLOCK * sizeof(float) + kCreateExtra > kLdsPerCu,
+                "gsdf_hip.h: GSDF_HIP_MAX_SLOTS_CREATE is the largest slot count gsdf_hip_program_create accepts");
+  // dual contouring's origin sweep: the ahead-of-time builds are <4,3>, <2,3>, <1,4> (the others need scratch). One rule for the
+  // launch (abi_mesh.hip: dc_mesh) and for the name gsdf_hip_program_kernels reports.
+  static int dc_origin_waves(int k) { return k == 1 ? 4 : 3; }
   // Workgroups per CU the lattice/eval sweeps are compiled for (their W template argument): 4 when the LDS allows it.
   int sweep_waves(int k) const {
     static const int forced = [] { const char* e = getenv("GSDF_HIP_SWEEP_WAVES"); return e ? atoi(e) : 0; }();  // tuning / debugging knob

@@ -67,6 +67,29 @@ const char* gsdf_hip_last_error(void);
 /* Select the HIP device for handles created by this thread afterwards. device < 0: keep current. */
 int gsdf_hip_init(int device);
 
+/* Largest trees. The evaluator keeps a tree's intermediate values in LDS: one KB per slot (gsdf_hip_program_info: lds_slots) and point
+ * carried per lane, and a workgroup can have a CU's 160 KB at the most. What does not fit is refused on the host with
+ * GSDF_ERR_BAD_TREE, before any kernel is launched, and the handle and the library stay usable:
+ *   gsdf_hip_program_create                                   143 slots (one point per lane above 28 slots); a handle that exists
+ *                                                             evaluates, renders (image2, image2_color, render3) and meshes flat;
+ *   gsdf_hip_normals3, gsdf_hip_indexed_normals,
+ *   gsdf_hip_indexed_project, _deviation                      80 slots (two points per lane);
+ *   gsdf_hip_mesh_octree[_start]                              slots + interval stack <= 67 (the centre tests carry two points per lane
+ *                                                             over both, beside 24 KB of cube stages; the interval stack is as deep as the
+ *                                                             tree's position maps that stretch nest: twist, scale, ... -- "interval=" in
+ *                                                             gsdf_hip_program_kernels);
+ *   gsdf_hip_mesh_dualcontour[_indexed]                       52 slots (the edge pass carries three points per lane). Its block test
+ *                                                             carries two over slots + interval stack: beyond 80 of them (an interval
+ *                                                             stack deeper than 28) the test is left out and every block is
+ *                                                             evaluated -- same triangles, more evaluations.
+ * The library checks the macros below against its kernels' LDS arithmetic when it is compiled.
+ * The interval stack takes a level per frame of brick masks (sixteen at the most) and per nested stretching map, so:
+ * GSDF_HIP_MAX_SLOTS_ALL: up to here every entry point accepts a tree whose interval stack is no deeper than sixteen. */
+#define GSDF_HIP_MAX_SLOTS_CREATE 143
+#define GSDF_HIP_MAX_SLOTS_NORMALS 80
+#define GSDF_HIP_MAX_COLS_OCTREE 67
+#define GSDF_HIP_MAX_SLOTS_DC 52
+#define GSDF_HIP_MAX_SLOTS_ALL 51
 int gsdf_hip_program_create(const gsdf_tree* tree, gsdf_program** out);
 void gsdf_hip_program_destroy(gsdf_program* p);
 int gsdf_hip_program_bounds(const gsdf_program* p, float bb[6]);
@@ -113,7 +136,11 @@ int gsdf_hip_program_specialize_poll(gsdf_program* p, int wait);
  * leaf=leaf_eval_kernel<4,4>:specialised prune=prune_kernel:specialised compiler=hipcc code=<32 hex digits>" (":interpreter" =
  * the ahead-of-time kernels; compiler = what built the specialised ones: the installed hipcc out of process, or the process's
  * hiprtc; code = key of the code that runs: generated source + device headers + options + compiler identity for specialised
- * kernels, the library's device sources otherwise -- a stored profile describes this handle only if it carries the same key). */
+ * kernels, the library's device sources otherwise -- a stored profile describes this handle only if it carries the same key).
+ * Further fields, in front of compiler= and code=: "flat=flat_grid_kernel<K,W>:..." and "dc=dc_origin_kernel<K,W>:..." (3-D: the flat
+ * renderer's lattice pass, dual contouring's origin sweep), "image=image2_kernel<K>:..." (2-D) and "interval=<depth of the interval
+ * stack>" (3-D: what the octree's limit counts beside the slots, see "Largest trees"). Readers split at blanks and '=' and skip the
+ * fields they do not know. */
 int gsdf_hip_program_kernels(const gsdf_program* p, char* dst, size_t dst_cap);
 /* Host-only (run without a GPU): text of the generated evaluator, and a gfx950 hiprtc build of the specialised kernels
  * that stops before loading them. dst may be NULL to query the length. */
@@ -163,7 +190,8 @@ void* gsdf_hip_host_alloc(size_t bytes);
 int gsdf_hip_host_register(void* ptr, size_t bytes);
 int gsdf_hip_host_release(void* ptr);
 /* Device-resident evaluation: d_pos/d_dist are device pointers on the program's GPU; stream is a
- * hipStream_t (NULL = the program's own stream). Asynchronous when stream != NULL. */
+ * hipStream_t (NULL = the program's own stream, a non-blocking one). Asynchronous either way: the kernel is enqueued and the
+ * call returns; synchronise the stream you passed, or the device (hipDeviceSynchronize) when it was the program's own. */
 int gsdf_hip_eval3_dev(gsdf_program* p, const void* d_pos, size_t pos_stride_bytes, float* d_dist, size_t n, void* stream);
 int gsdf_hip_eval2_dev(gsdf_program* p, const void* d_pos, size_t pos_stride_bytes, float* d_dist, size_t n, void* stream);
 /* Central-difference normals (not normalised), host buffers, 12-byte xyz in and out. */

@@ -21,7 +21,7 @@ typedef struct { float x, y; } V2;
 /* ------------------------------------------------------------------------------------------
  * VecPool  (gleval/cpu.go:188-390)
  * ------------------------------------------------------------------------------------------ */
-#define ORC_POOL_MAXBUF 64
+#define ORC_POOL_MAXBUF 1024
 typedef struct {
   void* buf[ORC_POOL_MAXBUF];
   size_t len[ORC_POOL_MAXBUF];
