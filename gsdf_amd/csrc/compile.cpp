@@ -15,6 +15,7 @@
 
 #include "host_math.h"
 #include "dev_ops.h"
+#include "gsdf_seams.h"
 
 namespace gsdf_dev {
 
@@ -233,6 +234,16 @@ bool clobbers(Ctx& c, uint32_t i) {
 }
 
 void gen(Ctx& c, uint32_t i, int depth);
+
+// which seams of array node i may jump: the oracle takes the same decision from the same text (include/gsdf_seams.h)
+unsigned array_seams(const Ctx& c, uint32_t i) {
+  const gsdf_seam_tree st = {c.t->nodes, c.t->links, c.t->aux};
+  return gsdf_array_seams(&st, i);
+}
+bool circ_seams(const Ctx& c, uint32_t i) {
+  const gsdf_seam_tree st = {c.t->nodes, c.t->links, c.t->aux};
+  return gsdf_circ_seams(&st, i) != 0;
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Lower-bound regions. For a subtree S, lower_region() answers with a region G such that, for every point p OUTSIDE G,
@@ -856,6 +867,9 @@ void gen(Ctx& c, uint32_t i, int depth) {
     case GSDF_ARRAY: {                                                                             // :345-397
       need_children(1); child_dim(false);
       int slotP = c.alloc(3), slotD = c.alloc(1);
+      // cell seams that may make the field jump (include/gsdf_seams.h): interval mode gives up on a ball that reaches one
+      const unsigned seams = array_seams(c, i);
+      const int lipd = seams ? c.lip_push() : -1;
       c.op(D_SAVEP3, slotP);
       c.op(D_SETSLOT, slotD); c.f(1e20f);
       for (int k = 0; k < 2; k++) for (int j = 0; j < 2; j++) for (int ii = 0; ii < 2; ii++) {
@@ -864,10 +878,12 @@ void gen(Ctx& c, uint32_t i, int depth) {
         c.f((float)ii); c.f((float)j); c.f((float)k);
         c.f(P[0]); c.f(P[1]); c.f(P[2]);
         c.f(P[3] + -1); c.f(P[4] + -1); c.f(P[5] + -1);
+        if (seams && k == 0 && j == 0 && ii == 0) { c.op(D_LIP_SEAM); c.u(seams); }  // P = the centre relative to its own cell's
         c.discont++; gen(c, c.child(n, 0), depth + 1); c.discont--;
         c.op(D_COMBINE_MIN, slotD);
         if (!(k == 1 && j == 1 && ii == 1)) c.op(D_SAVER, slotD);
       }
+      if (lipd >= 0) c.lip_pop(lipd);
       c.release(4);
       break;
     }
@@ -909,6 +925,9 @@ void gen(Ctx& c, uint32_t i, int depth) {
       bool is2d = n.op == GSDF_CIRCARRAY2D;
       child_dim(is2d);
       int slotP = c.alloc(is2d ? 2 : 3), slotD = c.alloc(1);
+      // sector rays across which the field may jump (include/gsdf_seams.h): interval mode gives up on a ball that reaches one
+      const bool seams = circ_seams(c, i);
+      const int lipd = seams ? c.lip_push() : -1;
       if (!is2d) c.op(D_SAVEP3, slotP);  // keeps z at slotP+2; CIRC_PRE overwrites slotP..+1 with p0.xy
       c.op(D_CIRC_PRE | c.shxy_flag(), slotP);
       c.bump();
@@ -941,6 +960,7 @@ void gen(Ctx& c, uint32_t i, int depth) {
         cg = o;
       }
       if (sector_gate) { c.op(D_CIRC_ORDER, slotP); for (int j = 0; j < 6; j++) c.f(cg.b[j]); }
+      if (seams) { c.op(D_LIP_SEAM, slotP); c.u(8u); }  // the two rays that bound the centre's sector
       c.discont++;  // a sector's copy of the child is evaluated where the point's fold puts it: no brick-level numbers inside
       gen(c, c.child(n, 0), depth + 1);  // pos1 first (or whichever D_CIRC_ORDER put there)
       c.op(D_SAVER, slotD);
@@ -963,6 +983,7 @@ void gen(Ctx& c, uint32_t i, int depth) {
         c.code[(size_t)skip_at] = (uint32_t)((long)c.code.size() - gate_pc);
       }
       c.op(D_COMBINE_MIN, slotD);
+      if (lipd >= 0) c.lip_pop(lipd);
       c.live.pop_back();
       c.release(is2d ? 3 : 4);
       break;
@@ -1081,16 +1102,20 @@ void gen(Ctx& c, uint32_t i, int depth) {
     case GSDF_ARRAY2D: {                                                                           // :914-962
       need_children(1); child_dim(true);
       int slotP = c.alloc(2), slotD = c.alloc(1);
+      const unsigned seams = array_seams(c, i);  // (as GSDF_ARRAY)
+      const int lipd = seams ? c.lip_push() : -1;
       c.op(D_SAVEP2, slotP);
       c.op(D_SETSLOT, slotD); c.f(1e20f);
       for (int j = 0; j < 2; j++) for (int ii = 0; ii < 2; ii++) {
         c.op(D_ARRAY2D_PRE, slotP);
         c.bump();
         c.f((float)ii); c.f((float)j); c.f(P[0]); c.f(P[1]); c.f(P[2] + -1); c.f(P[3] + -1);
+        if (seams && j == 0 && ii == 0) { c.op(D_LIP_SEAM); c.u(seams); }
         c.discont++; gen(c, c.child(n, 0), depth + 1); c.discont--;
         c.op(D_COMBINE_MIN, slotD);
         if (!(j == 1 && ii == 1)) c.op(D_SAVER, slotD);
       }
+      if (lipd >= 0) c.lip_pop(lipd);
       c.release(3);
       break;
     }

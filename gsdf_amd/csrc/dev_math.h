@@ -163,6 +163,12 @@ DM_INL float hypotf_(float p, float q) {
 //          t^2)^2 + 4 t^2)) / 2, largest at the smallest rho; no bound on the axis (LIP_BIG, finite so that nothing
 //          downstream sees Inf - Inf).
 #define GSDF_LIP_BIG 1e18f
+// a lower bound of the distance of (x, y) from the ray y = 0, x >= 0 (a sector ray in the frame of the copy that sits on it):
+// |y| in front of the origin, behind it max(|x|, |y|) <= hypot(x, y). Same float32 sequence as oracle/orc_eval.c: lip_ray_dist.
+DM_INL float lip_ray_dist(float x, float y) {
+  const float ay = absf(y);
+  return x > 0.0f ? ay : maxf(absf(x), ay);
+}
 DM_INL float lip_twist(float rho, float rl, float ak) {
   const float s = ak * (rho + rl);
   return 0.5f * (s + sqrtf_(s * s + 4.0f));

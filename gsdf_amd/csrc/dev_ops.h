@@ -176,6 +176,14 @@ enum DevOp : uint32_t {
   //      (bit 31 of the mask): the brick-level decision replaces it.
   D_SKIP,       // id subst skip|flags<<24 : words from this instruction to the end of the subtree
   D_LIP_DOM,    // kind ida idb kk pinfo   (slot = the combine's; ida / idb = 0xff: none; pinfo = interval-stack depth | is2d << 16)
+  //      D_LIP_SEAM (interval mode only; emitted only for an array node whose seams may make the field jump, include/gsdf_seams.h):
+  //      an array evaluates its child in the copies chosen by the CENTRE's cell or sector; a point of the ball across a
+  //      cell-centre plane or a sector ray sees another set of copies, about which the centre's copies say nothing. Behind the
+  //      first D_ARRAY_PRE / D_ARRAY2D_PRE (P = the centre relative to the nearest cell centre of the array's extent: |P.a| is the
+  //      distance to the nearest seam plane of axis a) resp. behind D_CIRC_PRE (the rays bounding the centre's sector are
+  //      the x axes of the two copies' frames, P and lds[slot..slot + 1]; dev_math.h: lip_ray_dist): a ball that reaches a seam gets no bound, lipR = GSDF_LIP_BIG,
+  //      until the D_LIP_POP behind the node. Nothing is dropped there; the cube is kept and its children are tested again.
+  D_LIP_SEAM,   // mask : bit 0 / 1 / 2: |P.x| / |P.y| / |P.z| <= lipR, bit 3: a sector ray within lipR  (slot = the D_CIRC_PRE's)
   D_OP_COUNT
 };
 
@@ -193,7 +201,7 @@ static const uint8_t kDevOpParams[D_OP_COUNT] = {
     /*MIN*/ 0, /*MAX*/ 0, /*DIFF*/ 0, /*XOR*/ 0, /*SUNION*/ 2, /*SDIFF*/ 2, /*SINTER*/ 2,
     /*GATE2D*/ 10, /*GATE3D*/ 12, /*GATEZC*/ 13, /*UBOUND2D*/ 1, /*UBOUND3D*/ 1, /*GATEOB*/ 14, /*CIRC_ORDER*/ 6,
     /*LIP_PUSH*/ 0, /*LIP_POP*/ 0, /*LIP_MUL*/ 1, /*LIP_WRAP*/ 2,
-    /*SKIP*/ 3, /*LIP_DOM*/ 5,
+    /*SKIP*/ 3, /*LIP_DOM*/ 5, /*LIP_SEAM*/ 1,
 };
 #define GSDF_GATE_SKIP(w) ((w) & 0x00ffffffu)  // a gate's (and D_SKIP's) last parameter word: words to skip | (number + 1) << 24 (D_SKIP: flags << 24)
 #define GSDF_GATE_ID1(w) ((w) >> 24)

@@ -465,6 +465,22 @@ __device__ __forceinline__ void smooth_h(const float (&num)[K], float k, float r
           }                                                                                                                            \
         }                                                                                                                              \
 
+// D_LIP_SEAM (dev_ops.h): a ball that reaches a seam of an array whose field may jump there gets no bound. One text for the
+// interpreter (the dispatch's default branch) and the specialised build, like D_LIP_DOM.
+#define GSDF_LIP_SEAM_BODY \
+        if (LIP) {                                                                                                                     \
+          const uint32_t seams = PU(0);                                                                                                \
+          bool reach = false;                                                                                                          \
+          if ((seams & 1u) != 0u) reach = reach || !(absf(pv[0].x) > lipR);                                                            \
+          if ((seams & 2u) != 0u) reach = reach || !(absf(pv[0].y) > lipR);                                                            \
+          if ((seams & 4u) != 0u) reach = reach || !(absf(pv[0].z) > lipR);                                                            \
+          if ((seams & 8u) != 0u) { /* sector rays: the x axes of the two copies' frames, P and lds[slot..slot + 1] */                 \
+            const float x0 = lds[((slot) * K + LIP_LO) * nthreads], y0 = lds[((slot + 1u) * K + LIP_LO) * nthreads];                   \
+            reach = !(lip_ray_dist(pv[0].x, pv[0].y) > lipR) || !(lip_ray_dist(x0, y0) > lipR);                                        \
+          }                                                                                                                            \
+          if (reach) lipR = GSDF_LIP_BIG;                                                                                              \
+        }                                                                                                                              \
+
 // The test of a D_GATE* instruction (dev_ops.h), shared by the interpreter's four cases and the specialised build's generated
 // text: REGION fills L[] from the gate's region parameters; I0 = index of the `sg` parameter (then kk, oslot, ok, k4, skip word).
 // Leaves far_ (wave-uniform: the child is skipped) and L (the substitute) in scope.
@@ -1441,6 +1457,11 @@ __device__ __forceinline__ void sdf_eval(code_ptr code, P3 (&pv)[K], float (&Rv)
           pc += 6;
           break;
         }
+        if (op == D_LIP_SEAM) {
+          GSDF_LIP_SEAM_BODY
+          pc += 2;
+          break;
+        }
         KLOOP Rv[kp] = __builtin_nanf("");
         return;
     }
@@ -1467,5 +1488,6 @@ namespace gsdf_dev {
 #undef GSDF_GATE_TEST
 #undef GSDF_GATE_TAKEN
 #undef GSDF_LIP_DOM_BODY
+#undef GSDF_LIP_SEAM_BODY
 
 }  // namespace gsdf_dev

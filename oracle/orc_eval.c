@@ -14,6 +14,7 @@
 #include <stdlib.h>
 
 #include "orc_math.h"
+#include "../include/gsdf_seams.h"
 
 typedef struct { float x, y, z; } V3;
 typedef struct { float x, y; } V2;
@@ -280,6 +281,19 @@ static float lip_screw_seam(const orc_sdf* s, uint32_t child, float pitch) {
   }
   return best <= 1e-3f * ap ? 3.0f * best : ap;
 }
+/* Seams of the array nodes (include/gsdf_seams.h decides, per node, which may make the field jump: the device's host
+ * compiler reads the same text). The copies of the child are chosen by the CENTRE's cell or sector; a point of the ball
+ * across a cell-centre plane or a sector ray sees another set of copies. A ball that reaches such a seam gets no bound:
+ * R = LIP_BIG inside the node, so every primitive below answers (-big, +big) and the cube is kept. */
+/* a lower bound of the distance of (x, y) from the ray y = 0, x >= 0: |y| in front of the origin, max(|x|, |y|) behind it */
+static inline float lip_ray_dist(float x, float y) {
+  const float ay = go_absf(y);
+  return x > 0.0f ? ay : go_maxf(go_absf(x), ay);
+}
+static gsdf_seam_tree seam_tree(const orc_sdf* s) {
+  gsdf_seam_tree st = {s->nodes, s->links, s->aux};
+  return st;
+}
 static int eval3_node(const orc_sdf* s, uint32_t ni, const V3* pos, float* dist, size_t n, orc_pool* vp);
 static int eval2_node(const orc_sdf* s, uint32_t ni, const V2* pos, float* dist, size_t n, orc_pool* vp);
 /* the reference's Evaluate of node ni; with an interval context attached, a primitive's distances become bounds */
@@ -508,6 +522,13 @@ static int eval3_node(const orc_sdf* s, uint32_t ni, const V3* pos, float* dist,
       V3 sp = {P[0], P[1], P[2]};
       V3 nn = {P[3] + -1, P[4] + -1, P[5] + -1};
       for (size_t i = 0; i < n; i++) dist[i] = LARGENUM;
+      float* vsave = NULL;
+      unsigned seams = 0;
+      if (vp->lip) {
+        gsdf_seam_tree st = seam_tree(s);
+        seams = gsdf_array_seams(&st, ni);
+        if (seams) vsave = lip_enter(vp, n);
+      }
       for (int k = 0; k < 2 && !err; k++)
         for (int j = 0; j < 2 && !err; j++)
           for (int ii = 0; ii < 2 && !err; ii++) {
@@ -520,9 +541,19 @@ static int eval3_node(const orc_sdf* s, uint32_t ni, const V3* pos, float* dist,
               rid.x = ms1_clamp(rid.x, 0, nn.x); rid.y = ms1_clamp(rid.y, 0, nn.y); rid.z = ms1_clamp(rid.z, 0, nn.z);
               t[ip].x = p.x - sp.x * rid.x; t[ip].y = p.y - sp.y * rid.y; t[ip].z = p.z - sp.z * rid.z;
             }
+            if (seams && k == 0 && j == 0 && ii == 0) /* t = the centre relative to the nearest cell centre of the array's extent */
+              for (size_t jj = 0; jj < n / 2; jj++) {
+                const float e = lip_radius(vp->lip, jj);
+                int reach = 0;
+                if (seams & 1u) reach = reach || !(go_absf(t[2 * jj].x) > e);
+                if (seams & 2u) reach = reach || !(go_absf(t[2 * jj].y) > e);
+                if (seams & 4u) reach = reach || !(go_absf(t[2 * jj].z) > e);
+                if (reach) vp->lip->R[jj] = LIP_BIG;
+              }
             err = eval3(s, CHILD(nd, 0), t, aux, n, vp);
             if (!err) for (size_t i = 0; i < n; i++) dist[i] = go_minf(dist[i], aux[i]);
           }
+      if (vsave) lip_leave(vp, vsave, n);
       REL_F(aux);
       REL_V3(t);
       return err;
@@ -622,8 +653,20 @@ static int eval3_node(const orc_sdf* s, uint32_t ni, const V3* pos, float* dist,
         pos1[i].x = c1 * p.x + s1 * p.y; pos1[i].y = (-s1) * p.x + c1 * p.y; pos1[i].z = p.z;
       }
       float* dist1 = ACQ_F(n);
+      float* vsave = NULL;
+      if (vp->lip) { /* the two rays bounding the centre's sector are the x axes of pos0's and pos1's frames */
+        gsdf_seam_tree st = seam_tree(s);
+        if (gsdf_circ_seams(&st, ni)) {
+          vsave = lip_enter(vp, n);
+          for (size_t j = 0; j < n / 2; j++) {
+            const float e = lip_radius(vp->lip, j);
+            if (!(lip_ray_dist(pos1[2 * j].x, pos1[2 * j].y) > e) || !(lip_ray_dist(pos0[2 * j].x, pos0[2 * j].y) > e)) vp->lip->R[j] = LIP_BIG;
+          }
+        }
+      }
       err = eval3(s, CHILD(nd, 0), pos1, dist1, n, vp);
       if (!err) err = eval3(s, CHILD(nd, 0), pos0, dist, n, vp);
+      if (vsave) lip_leave(vp, vsave, n);
       if (!err) min_reduce(dist, dist1, n);
       REL_F(dist1);
       REL_V3(pos1);
@@ -993,6 +1036,13 @@ static int eval2_node(const orc_sdf* s, uint32_t ni, const V2* pos, float* dist,
       V2 sp = {P[0], P[1]};
       V2 nn = {P[2] + -1, P[3] + -1};
       for (size_t i = 0; i < n; i++) dist[i] = LARGENUM;
+      float* vsave = NULL;
+      unsigned seams = 0;
+      if (vp->lip) { /* as GSDF_ARRAY */
+        gsdf_seam_tree st = seam_tree(s);
+        seams = gsdf_array_seams(&st, ni);
+        if (seams) vsave = lip_enter(vp, n);
+      }
       for (int j = 0; j < 2 && !err; j++)
         for (int ii = 0; ii < 2 && !err; ii++) {
           V2 ij = {(float)ii, (float)j};
@@ -1004,9 +1054,18 @@ static int eval2_node(const orc_sdf* s, uint32_t ni, const V2* pos, float* dist,
             rid.x = ms1_clamp(rid.x, 0, nn.x); rid.y = ms1_clamp(rid.y, 0, nn.y);
             t[ip].x = p.x - sp.x * rid.x; t[ip].y = p.y - sp.y * rid.y;
           }
+          if (seams && j == 0 && ii == 0)
+            for (size_t jj = 0; jj < n / 2; jj++) {
+              const float e = lip_radius(vp->lip, jj);
+              int reach = 0;
+              if (seams & 1u) reach = reach || !(go_absf(t[2 * jj].x) > e);
+              if (seams & 2u) reach = reach || !(go_absf(t[2 * jj].y) > e);
+              if (reach) vp->lip->R[jj] = LIP_BIG;
+            }
           err = eval2(s, CHILD(nd, 0), t, aux, n, vp);
           if (!err) for (size_t i = 0; i < n; i++) dist[i] = go_minf(dist[i], aux[i]);
         }
+      if (vsave) lip_leave(vp, vsave, n);
       REL_F(aux);
       REL_V2(t);
       return err;
@@ -1068,8 +1127,20 @@ static int eval2_node(const orc_sdf* s, uint32_t ni, const V2* pos, float* dist,
         pos1[i].x = c1 * p.x + s1 * p.y; pos1[i].y = (-s1) * p.x + c1 * p.y;
       }
       float* dist1 = ACQ_F(n);
+      float* vsave = NULL;
+      if (vp->lip) { /* as GSDF_CIRCARRAY */
+        gsdf_seam_tree st = seam_tree(s);
+        if (gsdf_circ_seams(&st, ni)) {
+          vsave = lip_enter(vp, n);
+          for (size_t j = 0; j < n / 2; j++) {
+            const float e = lip_radius(vp->lip, j);
+            if (!(lip_ray_dist(pos1[2 * j].x, pos1[2 * j].y) > e) || !(lip_ray_dist(pos0[2 * j].x, pos0[2 * j].y) > e)) vp->lip->R[j] = LIP_BIG;
+          }
+        }
+      }
       err = eval2(s, CHILD(nd, 0), pos1, dist1, n, vp);
       if (!err) err = eval2(s, CHILD(nd, 0), pos0, dist, n, vp);
+      if (vsave) lip_leave(vp, vsave, n);
       if (!err) for (size_t i = 0; i < n; i++) dist[i] = go_minf(dist[i], dist1[i]);
       REL_F(dist1);
       REL_V2(pos1);
@@ -1160,7 +1231,8 @@ int orc_eval3(const orc_sdf* s, orc_pool* vp, const float* pos, float* dist, siz
  * diagonal h is): interval evaluation of the tree, see lipctx. Not a reference function; what the octree's centre tests
  * need in order to stay surface-preserving for fields that are not 1-Lipschitz. For a tree of
  * exact-distance primitives under rigid motions and min / max it returns d -+ h exactly: the reference's predicate.
- * Sector and cell seams of (circular) arrays are taken as continuous, as those nodes' own Bounds() assume. */
+ * Cell seams of arrays and sector seams of circular arrays are continuous only where include/gsdf_seams.h proves it (a
+ * child that is its own mirror image in the seam, ...); a ball that reaches any other seam gets no bound (-big, +big). */
 int orc_eval3_bounds(const orc_sdf* s, orc_pool* vp, const float* pos, float* lo, float* hi, size_t n, float h) {
   if (n == 0) return -1;
   lipctx lc;

@@ -73,8 +73,11 @@ def _sorted(t):
 
 
 def _same_tris(got, want, what):
+    """Bit for bit as sorted triangles; a failure names how many differ and shows three of them as floats."""
     got, want = _sorted(got), _sorted(want)
-    assert got.shape == want.shape and (got == want).all(), (what, got.shape, want.shape)
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    bad = np.flatnonzero((got != want).any(axis=1))
+    assert len(bad) == 0, (what, len(bad), got[bad[:3]].view(np.float32), want[bad[:3]].view(np.float32))
 
 
 def _points(base, seed):
