@@ -163,6 +163,31 @@ extern "C" int gsdf_hip_selftest_sqrt(uint64_t* mismatches) {
   return rc;
 }
 
+// Test hook: one of the device's math routes over n host values (kernels_eval.h: math_selftest_kernel), for a comparison with the
+// oracle's restatement of the same function on the host. y may be null for the functions of one argument; for fn 17 the divisor is
+// divisor (wave-uniform, with the host's RN(1/divisor) where recip_for grants one) and y is not read.
+extern "C" int gsdf_hip_selftest_math(int fn, const float* x, const float* y, float* out, uint64_t n, float divisor) {
+  if (fn < 0 || fn > 17 || !x || !out) return fail(GSDF_ERR_BAD_ARGUMENT, "fn in 0..17, x and out not null");
+  if (n == 0) return GSDF_OK;
+  if (n > (1ull << 28)) return fail(GSDF_ERR_BAD_ARGUMENT, "n <= 2^28");
+  const bool two = fn == 0 || fn == 1 || fn == 8 || fn == 9 || fn == 15;
+  if (two && !y) return fail(GSDF_ERR_BAD_ARGUMENT, "this function takes two operands");
+  float* d_b = nullptr;
+  const size_t bytes = (size_t)n * sizeof(float);
+  HIP_TRY(hipMalloc((void**)&d_b, 3 * bytes));
+  int rc = GSDF_OK;
+  do {
+    if (hipMemcpy(d_b, x, bytes, hipMemcpyHostToDevice) != hipSuccess) { rc = fail(GSDF_ERR_HIP, "copy failed"); break; }
+    if (two && hipMemcpy(d_b + n, y, bytes, hipMemcpyHostToDevice) != hipSuccess) { rc = fail(GSDF_ERR_HIP, "copy failed"); break; }
+    const float r = fn == 17 ? gsdf_dev::recip_for(divisor) : 0.f;
+    hipLaunchKernelGGL(math_selftest_kernel, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, nullptr, fn, d_b, two ? d_b + n : nullptr,
+                       d_b + 2 * n, n, divisor, r);
+    if (hipMemcpy(out, d_b + 2 * n, bytes, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(GSDF_ERR_HIP, "selftest kernel failed"); break; }
+  } while (0);
+  (void)hipFree(d_b);
+  return rc;
+}
+
 static std::string device_arch(int device) {
   hipDeviceProp_t pr;
   if (hipGetDeviceProperties(&pr, device) != hipSuccess) return "gfx950";
@@ -579,6 +604,8 @@ extern "C" int gsdf_hip_program_kernels(const gsdf_program* p, char* dst, size_t
     const std::string key = p->spec_mod ? p->spec_key : gsdf_dev::spec_library_key();
     if (strlen(buf) + 8 + key.size() < sizeof buf) { strcat(buf, " code="); strcat(buf, key.c_str()); }
   }
+  if (strlen(buf) + 56 < sizeof buf)  // the lowering's division census (compile.h): with RN(1/d) / declined / polygons flagged / not flagged
+    snprintf(buf + strlen(buf), sizeof buf - strlen(buf), " recip=%d/%d/%d/%d", p->prog.n_recip, p->prog.n_recip_declined, p->prog.n_poly_recip, p->prog.n_poly_plain);
   if (strlen(buf) + 1 > dst_cap) return fail(GSDF_ERR_SHORT_BUFFER, "short buffer");
   std::memcpy(dst, buf, strlen(buf) + 1);
   return GSDF_OK;

@@ -46,6 +46,8 @@ struct Ctx {
   int slots = 0;      // currently allocated
   int max_slots = 0;
   int lip_depth = 0, max_lip_depth = 0;  // nesting of the position maps that stretch (interval stack of D_LIP_PUSH / _POP)
+  int n_recip = 0, n_recip_declined = 0, n_poly_recip = 0, n_poly_plain = 0;  // Program's diagnostic counts
+  float node_recip(float d) { const float r = recip_for(d); (r != 0.f ? n_recip : n_recip_declined)++; return r; }  // a node's divisor
   int lip_push() { const int d = lip_depth++; if (lip_depth > max_lip_depth) max_lip_depth = lip_depth; op(D_LIP_PUSH, d); return d; }
   void lip_pop(int d) { op(D_LIP_POP, d); lip_depth--; }
   // Brick masks (dev_ops.h: D_SKIP / D_LIP_DOM). discont > 0: inside a position map that jumps (array cell, circular sector, screw
@@ -809,7 +811,7 @@ void gen_combine(Ctx& c, const gsdf_node& n, uint32_t comb, bool has_k, int dept
         c.u((uint32_t)dom_depth | (is2d ? 0x10000u : 0u));
       }
       c.op(comb | swapf, slotD);
-      if (has_k) { c.f(n.p[0]); c.f(recip_for(n.p[0])); }
+      if (has_k) { c.f(n.p[0]); c.f(c.node_recip(n.p[0])); }
     }
     if (k + 1 < n.nchild) {
       if (slotD < 0) slotD = c.alloc(1);
@@ -1013,7 +1015,7 @@ void gen(Ctx& c, uint32_t i, int depth) {
       const int lipd = c.lip_push();  // D_SCREW_PRE stretches the interval radius by the helix map (interp.h, LIP)
       c.op(D_SCREW_PRE | c.hxy_flag() | c.shxy_flag(), s);
       c.bump();
-      c.f(P[0]); c.f(P[1]); c.f(P[2]); c.f(gsdf::tanf32(P[3])); c.f(P[0] / 2); c.f(recip_for(P[0]));
+      c.f(P[0]); c.f(P[1]); c.f(P[2]); c.f(gsdf::tanf32(P[3])); c.f(P[0] / 2); c.f(c.node_recip(P[0]));
       c.op(D_LIP_WRAP); c.f(P[0] / 2); c.f(lip_screw_seam(*c.t, c.child(n, 0), P[0]));
       c.discont++; gen(c, c.child(n, 0), depth + 1); c.discont--;  // (the profile coordinate is a sawtooth of the axial one)
       c.lip_pop(lipd);
@@ -1072,6 +1074,7 @@ void gen(Ctx& c, uint32_t i, int depth) {
           jv0 = iv;
         }
       }
+      (all_recip ? c.n_poly_recip : c.n_poly_plain)++;
       c.op(D_POLY2D); c.u(nv | (all_recip ? 0x80000000u : 0u)); c.f(v[0]); c.f(v[1]);
       while (c.code.size() % 8 != 0) c.u(0);  // edge records: 8 dwords, 32-byte aligned (two s_load_dwordx4 each)
       uint32_t jv = nv - 1;
@@ -1286,6 +1289,7 @@ Program compile(const gsdf_tree& t, size_t max_code_words) {
   p.code = std::move(c.code);
   p.nslots = c.max_slots;
   p.lip_depth = c.max_lip_depth;
+  p.n_recip = c.n_recip; p.n_recip_declined = c.n_recip_declined; p.n_poly_recip = c.n_poly_recip; p.n_poly_plain = c.n_poly_plain;
   p.n_skip_ids = 0;
   for (int v : cand_id) if (v >= 0) p.n_skip_ids++;
   p.is2d = gsdf_op_is2d(t.nodes[t.root].op);

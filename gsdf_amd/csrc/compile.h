@@ -20,6 +20,10 @@ struct Program {
   // surface" for lattice points outside that box by more than r without evaluating them.
   bool has_exact_bb = false;
   float exact_bb[6] = {0};
+  // What the lowering decided about division (diagnostic, read by tests through gsdf_hip_program_kernels): divisors that carry
+  // RN(1/d) for the exact-reciprocal form, divisors recip_for declined (the device divides), polygons whose every |e|^2 is
+  // eligible (approximate culling arithmetic, FAST edge loop) and polygons that lost the flag.
+  int n_recip = 0, n_recip_declined = 0, n_poly_recip = 0, n_poly_plain = 0;
 };
 
 // RN(1/d) for the device's exact division by a wave-uniform divisor, 0 if d is not eligible.

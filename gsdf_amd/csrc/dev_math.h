@@ -6,8 +6,14 @@
 // and its correctly rounded fp32 divide/sqrt expansions. Transcendentals follow the algorithms the
 // reference's math package uses (chewxy/math32 v1.11.1: float32(math.X(float64)) wrappers over Go's
 // Cephes-derived float64 routines for Atan2/Sin/Cos/Acos/Cbrt; float32 ports for Hypot/Sincos), so
-// distances are bit-identical to the CPU path for finite inputs. Not reproduced: Inf/NaN special
-// cases of hypot/atan2 (unreachable with finite positions) and math.Min/Max NaN propagation.
+// distances are bit-identical to the CPU path. Over which inputs that is TESTED, route by route against the oracle's restatement
+// (gsdf_hip_selftest_math, tests/test_gpu_math.py): a sample of about 1e5 finite float32 values per route that spans every binade --
+// both signs, subnormals, zeros, each route's own breakpoints to the last bit, random bit patterns; no exhaustive sweep -- for hypot,
+// atan2 (both routes), cbrt, sqrt, round, floor, min, max and the division by a uniform divisor (eligible for the reciprocal form or not); |x| < 2^29 for sin, cos, the twist's cos / sin pair and Sincos (from
+// there Go reduces by Payne-Hanek, these routes and the oracle keep Cody-Waite: outside the contract); |x| <= 1 for acos; pow(x, 1/3)
+// for x >= 0 within 1 ulp (two libraries). Through trees: parts of 2^-40 .. 2^40 units and positions of 2^-70 .. 2^40 around a unit
+// part (tests/test_gpu_scale.py). Not reproduced: Inf/NaN special cases of hypot/atan2 (unreachable with finite
+// positions) and math.Min/Max NaN propagation.
 #pragma once
 #ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>

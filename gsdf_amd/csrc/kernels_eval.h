@@ -230,6 +230,48 @@ __global__ void __launch_bounds__(BLOCK) div_selftest_kernel(float d, float r, u
   atomicAdd(fast_count, nf);
 }
 
+// The device's LONG routes, one function per call and one element per lane, for a comparison with the oracle's math32 restatement on
+// the host (oracle/orc_math_export.c; tests/test_gpu_math.py): the other selftests hold the short routes to these, this one holds
+// these to the reference. fn 0..12 as orc_math_apply numbers them (x, y are its operands: fn 1 is atan2(y = x[i], x = y[i])); then
+// 13 / 14 cossinf_'s cosine / sine, 15 atan2f_ (short route, long route where it declines), 16 sqrtf_, 17 x[i] / d through
+// div_uniform_k<1> with the wave-uniform divisor d and r = RN(1/d) from the host (0: not eligible), as the interpreter calls it.
+__global__ void __launch_bounds__(BLOCK) math_selftest_kernel(int fn, const float* __restrict__ x, const float* __restrict__ y,
+                                                              float* __restrict__ out, uint64_t n, float d, float r) {
+  const uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+  const bool valid = i < n;
+  // (every lane runs the function, the idle ones on 1: div_uniform_k votes over the whole wave)
+  const float a = valid ? x[i] : 1.0f, b = (valid && y) ? y[i] : 1.0f;
+  float o = 0.0f, s, c;
+  switch (fn) {
+    case 0: o = dm::hypotf_(a, b); break;
+    case 1: o = dm::atan2_ref(a, b); break;
+    case 2: o = dm::sinf_(a); break;
+    case 3: o = dm::cosf_(a); break;
+    case 4: o = dm::acosf_(a); break;
+    case 5: o = dm::cbrtf_(a); break;
+    case 6: dm::sincosf_(a, s, c); o = s; break;
+    case 7: dm::sincosf_(a, s, c); o = c; break;
+    case 8: o = dm::minf(a, b); break;
+    case 9: o = dm::maxf(a, b); break;
+    case 10: o = dm::pow13f_(a); break;
+    case 11: o = dm::roundf_(a); break;
+    case 12: o = dm::floorf_(a); break;
+    case 13: dm::cossinf_(a, c, s); o = c; break;
+    case 14: dm::cossinf_(a, c, s); o = s; break;
+    case 15: o = dm::atan2f_(a, b); break;
+    case 16: o = dm::sqrtf_(a); break;
+    case 17: {
+      const float nn[1] = {a};
+      float q[1];
+      dm::div_uniform_k<1>(nn, d, r, q);
+      o = q[0];
+      break;
+    }
+    default: o = __builtin_nanf(""); break;
+  }
+  if (valid) out[i] = o;
+}
+
 // gleval.NormalsCentralDiff (gleval/gleval.go:53-108); h = step/2.
 __global__ void __launch_bounds__(BLOCK) normals_kernel(const uint32_t* __restrict__ code_g, const float* __restrict__ pos,
                                                         float* __restrict__ nrm, uint64_t n, float h) {

@@ -21,7 +21,7 @@ ErrMismatchBufferLength = "position and distance buffer length mismatch"
 
 # every symbol include/gsdf_hip.h declares
 SYMBOLS = ["gsdf_hip_last_error", "gsdf_hip_init", "gsdf_hip_program_create", "gsdf_hip_program_destroy",
-           "gsdf_hip_program_bounds", "gsdf_hip_program_is2d", "gsdf_hip_program_info", "gsdf_hip_evaluations", "gsdf_hip_lower", "gsdf_hip_lower_region", "gsdf_hip_eval3_submit", "gsdf_hip_eval_wait", "gsdf_hip_host_alloc", "gsdf_hip_host_register", "gsdf_hip_host_release", "gsdf_hip_comm_unique_id", "gsdf_hip_comm_create", "gsdf_hip_comm_rank", "gsdf_hip_comm_world", "gsdf_hip_comm_allreduce_sum_u64", "gsdf_hip_mesh_gatherv", "gsdf_hip_mesh_gatherv_start", "gsdf_hip_mesh_gatherv_wait", "gsdf_hip_comm_destroy", "gsdf_hip_selftest_div", "gsdf_hip_selftest_sqrt", "gsdf_hip_selftest_circ", "gsdf_hip_selftest_atan2", "gsdf_hip_selftest_cossin", "gsdf_hip_mesh_minecraft", "gsdf_hip_blockcache_create", "gsdf_hip_blockcache_reset", "gsdf_hip_blockcache_eval3", "gsdf_hip_blockcache_hits", "gsdf_hip_blockcache_evaluations", "gsdf_hip_blockcache_destroy", "gsdf_hip_program_specialize", "gsdf_hip_program_specialize_async", "gsdf_hip_program_specialize_poll", "gsdf_hip_program_is_specialized", "gsdf_hip_program_kernels", "gsdf_hip_specialize_source", "gsdf_hip_specialize_check",
+           "gsdf_hip_program_bounds", "gsdf_hip_program_is2d", "gsdf_hip_program_info", "gsdf_hip_evaluations", "gsdf_hip_lower", "gsdf_hip_lower_region", "gsdf_hip_eval3_submit", "gsdf_hip_eval_wait", "gsdf_hip_host_alloc", "gsdf_hip_host_register", "gsdf_hip_host_release", "gsdf_hip_comm_unique_id", "gsdf_hip_comm_create", "gsdf_hip_comm_rank", "gsdf_hip_comm_world", "gsdf_hip_comm_allreduce_sum_u64", "gsdf_hip_mesh_gatherv", "gsdf_hip_mesh_gatherv_start", "gsdf_hip_mesh_gatherv_wait", "gsdf_hip_comm_destroy", "gsdf_hip_selftest_div", "gsdf_hip_selftest_sqrt", "gsdf_hip_selftest_circ", "gsdf_hip_selftest_atan2", "gsdf_hip_selftest_cossin", "gsdf_hip_selftest_math", "gsdf_hip_mesh_minecraft", "gsdf_hip_blockcache_create", "gsdf_hip_blockcache_reset", "gsdf_hip_blockcache_eval3", "gsdf_hip_blockcache_hits", "gsdf_hip_blockcache_evaluations", "gsdf_hip_blockcache_destroy", "gsdf_hip_program_specialize", "gsdf_hip_program_specialize_async", "gsdf_hip_program_specialize_poll", "gsdf_hip_program_is_specialized", "gsdf_hip_program_kernels", "gsdf_hip_specialize_source", "gsdf_hip_specialize_check",
            "gsdf_hip_eval3", "gsdf_hip_eval2", "gsdf_hip_eval3_dev", "gsdf_hip_eval2_dev", "gsdf_hip_normals3", "gsdf_hip_image2", "gsdf_hip_image2_color", "gsdf_hip_picture_size", "gsdf_hip_color_iq", "gsdf_hip_color_gradient", "gsdf_hip_view_orbit", "gsdf_hip_render3",
            "gsdf_hip_mesh_octree", "gsdf_hip_mesh_dualcontour", "gsdf_hip_mesh_flat", "gsdf_hip_mesh_stats_get", "gsdf_hip_mesh_read", "gsdf_hip_mesh_dev_tris",
            "gsdf_hip_mesh_stl", "gsdf_hip_mesh_host_tris", "gsdf_hip_mesh_host_stl", "gsdf_hip_mesh_destroy", "gsdf_hip_brick_owner", "gsdf_hip_slab_range",
@@ -216,6 +216,7 @@ def lib():
         L.gsdf_hip_selftest_circ.argtypes = [C.c_float, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.gsdf_hip_selftest_atan2.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.gsdf_hip_selftest_cossin.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.gsdf_hip_selftest_math.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_float]
         L.gsdf_hip_blockcache_create.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_void_p)]
         L.gsdf_hip_blockcache_reset.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float]
         L.gsdf_hip_blockcache_eval3.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t]
@@ -353,6 +354,24 @@ def color_default():
     return c
 
 
+# gsdf_hip_selftest_math's numbering: 0..12 as oracle/orc_math_export.c, then the evaluator's other routes
+MATH_FN = {"hypot": 0, "atan2_ref": 1, "sin": 2, "cos": 3, "acos": 4, "cbrt": 5, "sincos_s": 6, "sincos_c": 7, "min": 8, "max": 9,
+           "pow13": 10, "round": 11, "floor": 12, "cossin_c": 13, "cossin_s": 14, "atan2": 15, "sqrt": 16, "div": 17}
+
+
+def math_apply(name, x, y=None, divisor=1.0):
+    """One of the device's math routes over x (and y) elementwise, one value per lane (test hook: gsdf_hip_selftest_math)."""
+    x = np.ascontiguousarray(x, np.float32)
+    out = np.empty_like(x)
+    if y is not None:
+        y = np.ascontiguousarray(y, np.float32)
+        if y.shape != x.shape:
+            raise ValueError("operands differ in shape")
+    _check(lib().gsdf_hip_selftest_math(MATH_FN[name], x.ctypes.data, y.ctypes.data if y is not None else None, out.ctypes.data, x.size,
+                                        np.float32(divisor)))
+    return out
+
+
 def init(device=-1):
     """gleval.Init1x1GLFW analogue: make sure a HIP device is usable (raises otherwise)."""
     _check(lib().gsdf_hip_init(device))
@@ -400,7 +419,10 @@ class SDFHIP:
         _check(lib().gsdf_hip_program_kernels(self._h, buf, 512))
         kern = dict(kv.split("=") for kv in buf.value.decode().split())
         leaf_k = int(kern["leaf"].split("<")[1].split(",")[0]) if "leaf" in kern else 0  # points per lane of the leaf phase
-        return {"code_words": a.value, "lds_slots": b.value, "specialized": bool(sp), "specialize_s": t.value, "kernels": kern, "leaf_k": leaf_k}
+        # the lowering's division census: divisors with RN(1/d), divisors declined, polygons flagged for the reciprocal form, polygons not
+        recip = dict(zip(("recip", "declined", "poly_recip", "poly_plain"), (int(x) for x in kern["recip"].split("/")))) if "recip" in kern else None
+        return {"code_words": a.value, "lds_slots": b.value, "specialized": bool(sp), "specialize_s": t.value, "kernels": kern, "leaf_k": leaf_k,
+                "recip": recip}
 
     def specialize(self):
         """Build (hiprtc) and switch to kernels specialised for this tree: same bits, no fetch/decode. Returns self."""

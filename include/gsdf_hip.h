@@ -115,6 +115,12 @@ int gsdf_hip_selftest_atan2(int mode, int log2n, uint64_t* mismatches, uint64_t*
  * float64 route of the per-tree kernels, taken only where it provably rounds like the reference's own operation sequence, against that
  * sequence over EVERY float32 argument. mismatches must come back 0. */
 int gsdf_hip_selftest_cossin(uint64_t* mismatches, uint64_t* fast_path_arguments);
+/* Test hook (needs a GPU): the evaluator's own math routes -- the long ones the hooks above take as their yardstick -- applied to n
+ * host values, one per lane, for a comparison with a reference on the host. fn: 0 hypot(x, y), 1 atan2(y = x[i], x = y[i]) by the
+ * reference's float64 sequence, 2 sin, 3 cos, 4 acos, 5 cbrt, 6 / 7 Sincos' sine / cosine, 8 min, 9 max, 10 pow(x, 1/3), 11 round,
+ * 12 floor, 13 / 14 the twist's cosine / sine, 15 atan2 as the evaluator calls it (short route where it decides), 16 sqrt,
+ * 17 x[i] / divisor by the exact-reciprocal division where the divisor is eligible. y may be null for one-operand functions. */
+int gsdf_hip_selftest_math(int fn, const float* x, const float* y, float* out, uint64_t n, float divisor);
 /* Run-time specialisation (no reference counterpart; the reference's GPU path compiles GLSL per tree at
  * gleval/gpu.go:35-54, this is the same step for the HIP backend): builds, with hiprtc, eval / prune / leaf kernels in
  * which this program's instructions are laid out straight-line with literal parameters, and makes the handle launch
@@ -139,8 +145,10 @@ int gsdf_hip_program_specialize_poll(gsdf_program* p, int wait);
  * kernels, the library's device sources otherwise -- a stored profile describes this handle only if it carries the same key).
  * Further fields, in front of compiler= and code=: "flat=flat_grid_kernel<K,W>:..." and "dc=dc_origin_kernel<K,W>:..." (3-D: the flat
  * renderer's lattice pass, dual contouring's origin sweep), "image=image2_kernel<K>:..." (2-D) and "interval=<depth of the interval
- * stack>" (3-D: what the octree's limit counts beside the slots, see "Largest trees"). Readers split at blanks and '=' and skip the
- * fields they do not know. */
+ * stack>" (3-D: what the octree's limit counts beside the slots, see "Largest trees"). Last, "recip=a/b/c/d": what the lowering decided
+ * about division -- a divisors that carry RN(1/d) for the exact-reciprocal form (|d| in [2^-30, 2^30]), b divisors it declined (the
+ * device divides), c polygons whose every squared edge length is eligible, d polygons that are not (read-only, for tests that must
+ * know which form a tree runs). Readers split at blanks and '=' and skip the fields they do not know. */
 int gsdf_hip_program_kernels(const gsdf_program* p, char* dst, size_t dst_cap);
 /* Host-only (run without a GPU): text of the generated evaluator, and a gfx950 hiprtc build of the specialised kernels
  * that stops before loading them. dst may be NULL to query the length. */

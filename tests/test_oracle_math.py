@@ -3,6 +3,7 @@ correctly rounded float32 of the float64 function (chewxy/math32 doc.go), float3
 must stay within their algorithm's error bound."""
 import numpy as np
 
+import math_points as MP
 from oracle.oracle import math_apply
 
 RNG = np.random.default_rng(3)
@@ -80,3 +81,41 @@ def test_pow13():
     x = (RNG.random(5000, np.float32) * 10).astype(np.float32)
     ref = np.cbrt(x.astype(np.float64))
     assert np.abs(math_apply("pow13", x) - ref).max() < 1e-6 * 3
+
+
+# ---- every magnitude: the structured set of tests/math_points.py (all binades, both signs, subnormals, zeros, the routes' breakpoints)
+# beside the random points above. Domains: sin and cos for |x| < 2^29 -- from there Go's math.Sin / math.Cos reduce by Payne-Hanek
+# (go/src/math/sin.go: reduceThreshold = 1 << 29) and the restatement, like the device's routes, keeps Cody-Waite; acos for |x| <= 1.
+
+TRIG_LIMIT = np.float32(2.0 ** 29)
+
+
+def _same_bits(got, want):
+    return int(((got.view(np.uint32) != want.view(np.uint32)) & ~(np.isnan(got) & np.isnan(want))).sum())
+
+
+def test_wrappers_are_rounded_float64_at_every_magnitude():
+    x = MP.one_operand()
+    assert len(x) > 90000 and np.isfinite(x).all()
+    below = np.float32(np.nextafter(TRIG_LIMIT, np.float32(0)))   # 2^29 - 1 ulp: in; 2^29 and 2^29 + 1 ulp: out
+    assert below in x and TRIG_LIMIT in x and np.nextafter(TRIG_LIMIT, np.float32(np.inf)) in x
+    t = x[np.abs(x) < TRIG_LIMIT]
+    assert below in t and -below in t and TRIG_LIMIT not in t
+    assert _same_bits(math_apply("sin", t), np.sin(t.astype(np.float64)).astype(np.float32)) == 0
+    assert _same_bits(math_apply("cos", t), np.cos(t.astype(np.float64)).astype(np.float32)) == 0
+    assert _same_bits(math_apply("cbrt", x), np.cbrt(x.astype(np.float64)).astype(np.float32)) == 0
+    u = x[np.abs(x) <= 1]
+    assert _same_bits(math_apply("acos", u), np.arccos(u.astype(np.float64)).astype(np.float32)) == 0
+    y, xx = MP.two_operands()
+    assert _same_bits(math_apply("atan2", y, xx), np.arctan2(y.astype(np.float64), xx.astype(np.float64)).astype(np.float32)) == 0
+
+
+def test_hypot_float32_port_at_every_magnitude():
+    p, q = MP.two_operands()
+    with np.errstate(over="ignore"):
+        ref = np.hypot(p.astype(np.float64), q.astype(np.float64)).astype(np.float32)
+    got = math_apply("hypot", p, q)
+    fin = np.isfinite(ref)
+    assert np.isfinite(got[fin]).all()                       # no NaN, no overflow where the true value is a float32
+    assert ulps(got[fin], ref[fin]).max() <= 2
+    assert (got[~fin] == ref[~fin]).all()                    # and +Inf where it is not
