@@ -680,6 +680,51 @@ __global__ void __launch_bounds__(BLOCK, WAVES) leaf_kernel(const uint32_t* __re
 // holds its coordinate's value. Same distances, same records, same triangles; 24 % fewer evaluations on average. The reference
 // evaluates every corner of every leaf (marchcubes.go:24-31), so this is an option, not the default; the rows evaluated travel in
 // the group sums (statistics: MeshCounters.n_points).
+// The end of a wave pass of leaf_eval_kernel and leaf_dense_kernel (one body, so that the two cannot drift): the block's header
+// word and group sum, and the cut lanes' records side by side. dc: the lane's corner distances by corner number; index: its
+// marching-cubes case (nb::lt0 of each corner: -0.0 and NaN are not negative); lxy, lz: leaf x | y << 16 and leaf z (16 bits each);
+// blk is wave-uniform. ROWS: the group sum also carries the z rows evaluated, for every block (DZ).
+template <bool NTLDS, bool ROWS>
+__device__ __forceinline__ void leaf_block_tail(const float (&dc)[8], unsigned index, bool pass, unsigned nact, unsigned zrows, uint32_t lxy,
+                                                uint32_t lz, uint64_t blk, unsigned long long n_blocks_cap, const uint8_t* s_nt,
+                                                uint32_t* __restrict__ hdr, uint32_t* __restrict__ rec, unsigned long long* __restrict__ psum) {
+  const bool cut = pass && index != 0u && index != 255u;
+  // compact the cut leaves of this wave's block: rank among the cut lanes, one header word per block
+  const unsigned long long cm = __ballot(cut);
+  const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(cm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)cm, 0u));
+  if (blk < n_blocks_cap) {
+    // header word: records | triangles << 8; the same pair is added to the sum of the block's group of MARCH_GROUP
+    // blocks (low / high half of one 64-bit word: a fire-and-forget atomic, one per wave pass the surface cuts), from which
+    // march_records_kernel derives every workgroup's share of the records and its triangles' place in the output
+    unsigned ntri = 0;
+#ifndef GSDF_EXP_NO_NTRI  // developer experiments (GSDF_HIP_SPEC_FLAGS=-DGSDF_EXP_NO_NTRI / _NO_PSUM): what the counts cost (timing only)
+    if (cm != 0ull) {  // wave-uniform
+      unsigned nt = 0u;  // 0..5
+      if (NTLDS) { if (cut) nt = (unsigned)s_nt[index]; }
+      else { if (cut) nt = (unsigned)GSDF_MC_NTRI[index]; }
+      ntri = (unsigned)__builtin_popcountll(__ballot((nt & 1u) != 0u)) + 2u * (unsigned)__builtin_popcountll(__ballot((nt & 2u) != 0u)) +
+             4u * (unsigned)__builtin_popcountll(__ballot((nt & 4u) != 0u));
+    }
+#endif
+    if ((threadIdx.x & 63u) == 0u) {
+      const uint32_t nrec = (uint32_t)__builtin_popcountll(cm);
+      hdr[blk] = nrec | (ntri << 8);
+#ifndef GSDF_EXP_NO_PSUM
+      if (ROWS) atomicAdd(&psum[blk / MARCH_GROUP], PSUM_PACK(nrec, ntri, nact, zrows));  // (every brick: its rows are counted)
+      else if (nact) atomicAdd(&psum[blk / MARCH_GROUP], PSUM_PACK(nrec, ntri, nact, 0u));  // (a cut leaf is an active one: nrec <= nact)
+#endif
+    }
+    if (cut) {
+      uint2* w = (uint2*)(rec + blk * REC_BLOCK + rank * REC_WORDS);  // 40-byte records: 8-byte aligned, five 8-byte stores
+      w[0] = make_uint2(__float_as_uint(dc[0]), __float_as_uint(dc[1]));
+      w[1] = make_uint2(__float_as_uint(dc[2]), __float_as_uint(dc[3]));
+      w[2] = make_uint2(__float_as_uint(dc[4]), __float_as_uint(dc[5]));
+      w[3] = make_uint2(__float_as_uint(dc[6]), __float_as_uint(dc[7]));
+      w[4] = make_uint2(lxy, lz | (index << 16));
+    }
+  }
+}
+
 template <int K, int WAVES, bool UCUBE = true, bool NTLDS = true, bool BOTH = false, bool DZ = false>
 __global__ void __launch_bounds__(BLOCK, WAVES) leaf_eval_kernel(const uint32_t* __restrict__ code_g, const Cube* __restrict__ cubes,
                                                           unsigned long long cube_cap, int lq, int nslots, float ox, float oy, float oz,
@@ -691,14 +736,19 @@ __global__ void __launch_bounds__(BLOCK, WAVES) leaf_eval_kernel(const uint32_t*
   float* lds = g_smem + threadIdx.x;
   // triangles per marching-cubes case, behind the interpreter's columns (256 B)
   uint8_t* s_nt = (uint8_t*)(g_smem + (size_t)(nslots * K > 8 ? nslots * K : 8) * BLOCK);  // (8 rows at least: the brick's distances)
-  const int sh = lq - 1;
+  // UCUBE: the host launches this form for lq == 3 only, so the shift is a constant and a wave pass is one cube; everything that
+  // depends on the lane alone -- its leaf (li, lj, lk), its words of the record, the addresses of the exchange -- is formed once
+  // per wave, and the pass's bookkeeping (first leaf, block number, validity) stays in scalar registers
+  const int sh = UCUBE ? 2 : lq - 1;
+  const unsigned lane = threadIdx.x & 63u;
+  const unsigned wave_off = __builtin_amdgcn_readfirstlane(threadIdx.x & ~63u);
   // The three loads a wave starts with -- table byte, cube count, first cube -- are issued together (one trip to memory, not
   // three in a row: a workgroup lives for ~5 passes only). The first cube is read before the count is known: its index is
   // clamped into the queue, and the pass is skipped below if the count says so.
   const uint8_t nt0 = NTLDS ? GSDF_MC_NTRI[threadIdx.x] : (uint8_t)0;
   unsigned long long cw_first = 0ull;
   if (UCUBE) {
-    uint64_t ci = uniform_u64(((uint64_t)blockIdx.x * BLOCK + (threadIdx.x & ~63u)) >> (3 * sh));
+    uint64_t ci = ((uint64_t)blockIdx.x * BLOCK + wave_off) >> (3 * sh);
     if (ci >= cube_cap) ci = cube_cap - 1;
     cw_first = *(const unsigned long long*)(cubes + ci);
   }
@@ -716,32 +766,33 @@ __global__ void __launch_bounds__(BLOCK, WAVES) leaf_eval_kernel(const uint32_t*
   const uint64_t step = (uint64_t)gridDim.x * BLOCK;
   // UCUBE: the 64 leaves of a wave pass belong to ONE cube (and n_leaves is a multiple of 64), so the cube is a scalar load --
   // issued one pass ahead: a wave has ~5 passes and the load is a trip to L2/HBM it would otherwise sit out at every start
-  auto cube_word = [&](uint64_t b) -> unsigned long long {
-    const uint64_t li = uniform_u64(b + (threadIdx.x & ~63u));
-    if (li >= n_leaves) return 0ull;
-    return *(const unsigned long long*)(cubes + (li >> (3 * sh)));
+  auto cube_word = [&](uint64_t b) -> unsigned long long {  // b: the wave's first leaf of a pass
+    if (b >= n_leaves) return 0ull;
+    return *(const unsigned long long*)(cubes + (b >> (3 * sh)));
   };
   unsigned long long cw_next = cw_first;
-  for (uint64_t base = (uint64_t)blockIdx.x * BLOCK; base < n_leaves; base += step) {
-    const uint64_t i = base + threadIdx.x;
-    const bool valid = UCUBE ? uniform_u64(base + (threadIdx.x & ~63u)) < n_leaves : i < n_leaves;
+  // UCUBE: `base` is the WAVE's first leaf (a multiple of 64, like n_leaves: a pass is valid as a whole, and a wave whose pass
+  // is not has no later one either); else the workgroup's. The waves of a workgroup therefore make different numbers of passes:
+  // NO WORKGROUP BARRIER may stand in this loop's body (there is none: sdf_eval of a brick, the exchange and the tail are the
+  // wave's own; the one barrier of the UCUBE form, behind the table load, is above)
+  for (uint64_t base = (uint64_t)blockIdx.x * BLOCK + (UCUBE ? wave_off : 0u); base < n_leaves; base += step) {
+    const uint64_t i = base + (UCUBE ? lane : threadIdx.x);
+    const bool valid = UCUBE ? true : i < n_leaves;
     Cube lf = {0, 0, 0, 0};
+    uint32_t lxy = 0u, lz = 0u;  // the record's leaf words: x | y << 16, z
     unsigned nact = 0;  // leaves of this wave pass that pass the corner-0 test (wave-uniform)
     unsigned zrows = 8u;  // z rows of the brick that were evaluated (wave-uniform; fewer than 8 with DZ)
     const unsigned long long cw = cw_next;
-    if (UCUBE) {
-      cw_next = cube_word(base + step);
-      if (!valid) continue;  // wave-uniform: nothing of this pass is read by anyone
-    }
-    if (valid) {
-      Cube pc;
-      if (UCUBE) { pc.x = (uint16_t)cw; pc.y = (uint16_t)(cw >> 16); pc.z = (uint16_t)(cw >> 32); pc.w = 0; }
-      else pc = cubes[i >> (3 * sh)];
+    if (UCUBE) cw_next = cube_word(base + step);
+    if (!UCUBE && valid) {
+      const Cube pc = cubes[i >> (3 * sh)];
       const unsigned l = (unsigned)(i & ((1u << (3 * sh)) - 1u));
       const unsigned m = (1u << sh) - 1u;
       lf.x = (uint16_t)((pc.x << sh) + (l & m));
       lf.y = (uint16_t)((pc.y << sh) + ((l >> sh) & m));
       lf.z = (uint16_t)((pc.z << sh) + ((l >> (2 * sh)) & m));
+      lxy = (uint32_t)lf.x | ((uint32_t)lf.y << 16);
+      lz = (uint32_t)lf.z;
     }
     unsigned index = 0;
     bool pass = false;
@@ -756,7 +807,6 @@ __global__ void __launch_bounds__(BLOCK, WAVES) leaf_eval_kernel(const uint32_t*
       // the same values, same bits as one leaf per lane; only the assignment of points to lanes differs. The distances then
       // change hands through the wave's own (now idle) interpreter columns: leaf (i, j, k) = lane i + 4j + 16k reads corner
       // (cx, cy, cz) from column (2i + cx, 2j + cy), row 2k + cz.
-      const unsigned lane = threadIdx.x & 63u;
       const unsigned bx = ((unsigned)(cw & 0xffffu)) << 2, by = ((unsigned)((cw >> 16) & 0xffffu)) << 2, bz = ((unsigned)((cw >> 32) & 0xffffu)) << 2;
       const float xa = ox + res * (float)(uint16_t)(bx + ((lane & 7u) >> 1)), ya = oy + res * (float)(uint16_t)(by + (lane >> 4));
       const float px = (lane & 1u) ? xa + res : xa, py = (lane & 8u) ? ya + res : ya;
@@ -852,19 +902,28 @@ __global__ void __launch_bounds__(BLOCK, WAVES) leaf_eval_kernel(const uint32_t*
         for (unsigned c0 = 0; c0 < 8; c0 += K) GSDF_COLUMN_PASS
       }
 #undef GSDF_COLUMN_PASS
-      float* D = g_smem + (threadIdx.x & ~63u);  // rows of BLOCK floats; this wave's 64 columns of each
+      // Column (x, y) of a row sits at y * 8 + (x ^ (y & 1)): the odd y columns are mirrored within their x pairs, so that corner
+      // (cx, cy) of a leaf is the word at (2 lj + cy) * 8 + 2 li + (cx ^ cy) = ... + (c & 1) -- the corners in corner order
+      // 0, 1 | 2, 3 at ascending addresses, and every pair of them arrives as the register pair its record store takes. A
+      // permutation within a row of 64 words: the banks are the same.
+      float* D = g_smem + wave_off;  // rows of BLOCK floats; this wave's 64 columns of each
+      const unsigned wcol = lane ^ ((lane >> 3) & 1u);
 #pragma unroll
-      for (int r = 0; r < 8; r++) D[r * BLOCK + lane] = dall[r];
+      for (int r = 0; r < 8; r++) D[r * BLOCK + wcol] = dall[r];
       __builtin_amdgcn_wave_barrier();  // (the wave's LDS operations execute in order; this only pins the compiler's schedule)
       const unsigned li = lane & 3u, lj = (lane >> 2) & 3u, lk = lane >> 4;
+      const unsigned rcol = 16u * lj + 2u * li;  // the leaf's corner 0 within a row
 #pragma unroll
       for (int c = 0; c < 8; c++) {
-        const unsigned cx = (c ^ (c >> 1)) & 1u, cy = (c >> 1) & 1u, cz = (c >> 2) & 1u;
+        const unsigned cy = (c >> 1) & 1u, cz = (c >> 2) & 1u;
         unsigned row = 2u * lk + cz;
         if (DZ && K == 4) row = (unsigned)__builtin_popcount(rowmask & ((2u << row) - 1u)) - 1u;  // the slot that holds this row's value (a row left out = the row before it)
-        dc[c] = D[row * BLOCK + (2u * lj + cy) * 8u + 2u * li + cx];
+        dc[c] = D[row * BLOCK + rcol + cy * 8u + (c & 1u)];
         index |= (nb::lt0(dc[c]) ? 1u : 0u) << c;
       }
+      // leaf = brick * 4 + (li, lj, lk), 16 bits each (the brick's low two bits are clear: + is |)
+      lxy = ((bx & 0xffffu) | ((by & 0xffffu) << 16)) | (li | (lj << 16));
+      lz = (bz & 0xffffu) | lk;
       pass = nb::abs_le(dc[0], cubeDiag);
       nact = (unsigned)__builtin_popcountll(__ballot(pass));
     } else {
@@ -905,42 +964,8 @@ __global__ void __launch_bounds__(BLOCK, WAVES) leaf_eval_kernel(const uint32_t*
       // dall[j] is the distance of corner order[j], order = {0,4,1,5,3,7,2,6}
       dc[0] = dall[0]; dc[1] = dall[2]; dc[2] = dall[6]; dc[3] = dall[4]; dc[4] = dall[1]; dc[5] = dall[3]; dc[6] = dall[7]; dc[7] = dall[5];
     }
-    const bool cut = pass && index != 0u && index != 255u;
-    // compact the cut leaves of this wave's block: rank among the cut lanes, one header word per block
-    const unsigned long long cm = __ballot(cut);
-    const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(cm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)cm, 0u));
-    const uint64_t blk = uniform_u64((base + (uint64_t)(threadIdx.x & ~63u)) >> 6);  // block = wave pass = 64 consecutive leaves
-    if (blk < n_blocks_cap) {
-      // header word: records | triangles << 8; the same pair is added to the sum of the block's group of MARCH_GROUP
-      // blocks (low / high half of one 64-bit word: a fire-and-forget atomic, one per wave pass the surface cuts), from which
-      // march_records_kernel derives every workgroup's share of the records and its triangles' place in the output
-      unsigned ntri = 0;
-#ifndef GSDF_EXP_NO_NTRI  // developer experiments (GSDF_HIP_SPEC_FLAGS=-DGSDF_EXP_NO_NTRI / _NO_PSUM): what the counts cost (timing only)
-      if (cm != 0ull) {  // wave-uniform
-        unsigned nt = 0u;  // 0..5
-        if (NTLDS) { if (cut) nt = (unsigned)s_nt[index]; }
-        else { if (cut) nt = (unsigned)GSDF_MC_NTRI[index]; }
-        ntri = (unsigned)__builtin_popcountll(__ballot((nt & 1u) != 0u)) + 2u * (unsigned)__builtin_popcountll(__ballot((nt & 2u) != 0u)) +
-               4u * (unsigned)__builtin_popcountll(__ballot((nt & 4u) != 0u));
-      }
-#endif
-      if ((threadIdx.x & 63u) == 0u) {
-        const uint32_t nrec = (uint32_t)__builtin_popcountll(cm);
-        hdr[blk] = nrec | (ntri << 8);
-#ifndef GSDF_EXP_NO_PSUM
-        if (DZ && UCUBE && K == 4) atomicAdd(&psum[blk / MARCH_GROUP], PSUM_PACK(nrec, ntri, nact, zrows));  // (every brick: its rows are counted)
-        else if (nact) atomicAdd(&psum[blk / MARCH_GROUP], PSUM_PACK(nrec, ntri, nact, 0u));  // (a cut leaf is an active one: nrec <= nact)
-#endif
-      }
-      if (cut) {
-        uint2* w = (uint2*)(rec + blk * REC_BLOCK + rank * REC_WORDS);  // 40-byte records: 8-byte aligned, five 8-byte stores
-        w[0] = make_uint2(__float_as_uint(dc[0]), __float_as_uint(dc[1]));
-        w[1] = make_uint2(__float_as_uint(dc[2]), __float_as_uint(dc[3]));
-        w[2] = make_uint2(__float_as_uint(dc[4]), __float_as_uint(dc[5]));
-        w[3] = make_uint2(__float_as_uint(dc[6]), __float_as_uint(dc[7]));
-        w[4] = make_uint2((uint32_t)lf.x | ((uint32_t)lf.y << 16), (uint32_t)lf.z | (index << 16));
-      }
-    }
+    const uint64_t blk = UCUBE ? base >> 6 : uniform_u64((base + (uint64_t)(threadIdx.x & ~63u)) >> 6);  // block = wave pass = 64 consecutive leaves
+    leaf_block_tail<NTLDS, DZ && UCUBE && K == 4>(dc, index, pass, nact, zrows, lxy, lz, blk, n_blocks_cap, s_nt, hdr, rec, psum);
   }
   // statistics: active and cut leaves travel in the group sums (PSUM_PACK) and are totalled by march_records_kernel; "leaves
   // whose wave went on to the remaining corners" is every leaf for column bricks (the host knows) and counted here only for
@@ -1072,34 +1097,11 @@ __global__ void __launch_bounds__(BLOCK, WAVES) leaf_dense_kernel(const uint32_t
     __builtin_amdgcn_wave_barrier();  // (the next brick rewrites D and the table)
     const bool pass = nb::abs_le(dc[0], cubeDiag);
     const unsigned nact = (unsigned)__builtin_popcountll(__ballot(pass));
-    const bool cut = pass && index != 0u && index != 255u;
-    const unsigned long long cm = __ballot(cut);
-    const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(cm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)cm, 0u));
-    const uint64_t blk = brick;  // block = brick = 64 consecutive leaves of the queue's order
-    if (blk < n_blocks_cap) {
-      unsigned ntri = 0;
-      if (cm != 0ull) {  // wave-uniform
-        unsigned nt = 0u;  // 0..5
-        if (NTLDS) { if (cut) nt = (unsigned)s_nt[index]; }
-        else { if (cut) nt = (unsigned)GSDF_MC_NTRI[index]; }
-        ntri = (unsigned)__builtin_popcountll(__ballot((nt & 1u) != 0u)) + 2u * (unsigned)__builtin_popcountll(__ballot((nt & 2u) != 0u)) +
-               4u * (unsigned)__builtin_popcountll(__ballot((nt & 4u) != 0u));
-      }
-      if (lane == 0u) {
-        const uint32_t nrec = (uint32_t)__builtin_popcountll(cm);
-        hdr[blk] = nrec | (ntri << 8);
-        if (nact) atomicAdd(&psum[blk / MARCH_GROUP], PSUM_PACK(nrec, ntri, nact, 0u));
-      }
-      if (cut) {
-        const uint32_t lx = (pidx[0] << 2) + la, ly = (pidx[1] << 2) + lb, lz = (pidx[2] << 2) + lc;
-        uint2* w = (uint2*)(rec + blk * REC_BLOCK + rank * REC_WORDS);  // 40-byte records: five 8-byte stores
-        w[0] = make_uint2(__float_as_uint(dc[0]), __float_as_uint(dc[1]));
-        w[1] = make_uint2(__float_as_uint(dc[2]), __float_as_uint(dc[3]));
-        w[2] = make_uint2(__float_as_uint(dc[4]), __float_as_uint(dc[5]));
-        w[3] = make_uint2(__float_as_uint(dc[6]), __float_as_uint(dc[7]));
-        w[4] = make_uint2((lx & 0xffffu) | ((ly & 0xffffu) << 16), (lz & 0xffffu) | (index << 16));
-      }
-    }
+    // leaf = brick * 4 + (la, lb, lc), 16 bits each: the brick's part is scalar and its low two bits are clear (+ is |), the lane's
+    // part does not change from brick to brick -- one or per word and brick, as in leaf_eval_kernel
+    const uint32_t bxy = ((pidx[0] << 2) & 0xffffu) | (((pidx[1] << 2) & 0xffffu) << 16), bzw = (pidx[2] << 2) & 0xffffu;
+    // block = brick = 64 consecutive leaves of the queue's order
+    leaf_block_tail<NTLDS, false>(dc, index, pass, nact, 0u, bxy | (la | (lb << 16)), bzw | lc, brick, n_blocks_cap, s_nt, hdr, rec, psum);
   }
   // statistics: the points evaluated (lane slots, idle ones included), one atomic per workgroup
   __syncthreads();
