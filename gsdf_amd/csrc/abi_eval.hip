@@ -52,10 +52,10 @@ extern "C" int gsdf_hip_program_create(const gsdf_tree* tree, gsdf_program** out
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, p->device) == hipSuccess) p->num_cu = prop.multiProcessorCount;
   if (p->lds_bytes(p->batch_k()) + gsdf_program::kCreateExtra > gsdf_program::kLdsPerCu) return cleanup(fail(GSDF_ERR_BAD_TREE, "tree needs more LDS scratch than one CU has"));
-  if (hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking) != hipSuccess) return cleanup(fail(GSDF_ERR_HIP, "hipStreamCreate failed"));
+  if (p->stream.ensure() != hipSuccess) return cleanup(fail(GSDF_ERR_HIP, "hipStreamCreate failed"));
   size_t bytes = p->prog.code.size() * sizeof(uint32_t);
-  if (hipMalloc((void**)&p->d_code, bytes) != hipSuccess) return cleanup(fail(GSDF_ERR_HIP, "hipMalloc(program) failed"));
-  if (hipMemcpy(p->d_code, p->prog.code.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) return cleanup(fail(GSDF_ERR_HIP, "hipMemcpy(program) failed"));
+  if (hipMalloc((void**)&p->d_code.p, bytes) != hipSuccess) return cleanup(fail(GSDF_ERR_HIP, "hipMalloc(program) failed"));
+  if (hipMemcpy(p->d_code.p, p->prog.code.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) return cleanup(fail(GSDF_ERR_HIP, "hipMemcpy(program) failed"));
   *out = p;
   return GSDF_OK;
 }
@@ -224,18 +224,37 @@ static int spec_build(gsdf_program* p, const std::vector<std::string>& names, hi
 // of scratch, wrote the results of 216 points of a ragged last tile to the wrong addresses). The ahead-of-time
 // interpreter kernels have ONE code shape each, and that shape is what the whole test suite runs.
 static int fn_scratch_bytes(hipFunction_t f) {
-  static const bool allow = getenv("GSDF_HIP_EXP_ALLOW_SCRATCH") != nullptr;  // developer experiments only: timing of a spilling build
+  static const bool allow = env_set("GSDF_HIP_EXP_ALLOW_SCRATCH");  // developer experiments only: timing of a spilling build
   if (allow) return 0;
   int v = 0;
   if (hipFuncGetAttribute(&v, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, f) != hipSuccess) { (void)hipGetLastError(); return 1 << 30; }
   return v;
 }
 static void spec_report(const char* what, const std::string& name, hipFunction_t f, bool used) {
-  if (!getenv("GSDF_HIP_DEBUG")) return;
+  if (!env_set("GSDF_HIP_DEBUG")) return;
   int regs = -1;
   (void)hipFuncGetAttribute(&regs, HIP_FUNC_ATTRIBUTE_NUM_REGS, f);
   fprintf(stderr, "gsdf_hip: %s %s: %d registers, %d B scratch per lane -> %s\n", what, name.c_str(), regs, fn_scratch_bytes(f),
           used ? "used" : "not used (interpreter kernel instead)");
+}
+// No scratch, or not used (see fn_scratch_bytes); wanted = false: a usable build that an earlier one is preferred to.
+static bool spec_usable(const std::string& name, hipFunction_t f, bool wanted = true) {
+  const bool ok = fn_scratch_bytes(f) == 0;
+  spec_report("specialised", name, f, ok && wanted);
+  return ok;
+}
+// The shared tail of the builders below: `names` built into a module the handle keeps, each function checked for scratch and
+// reported; take(i, f) gets the usable ones in the order of the names and says whether it took f. A failed build takes nothing:
+// the interpreter kernels stay in use.
+template <typename Take>
+static void spec_build_group(gsdf_program* p, const std::vector<std::string>& names, Take take) {
+  std::vector<hipFunction_t> f;
+  hipModule_t mod = nullptr;
+  if (spec_build(p, names, &mod, f, &p->spec_compile_s) != GSDF_OK) return;
+  p->mods.keep(mod);
+  for (size_t i = 0; i < names.size(); i++)
+    if (fn_scratch_bytes(f[i]) == 0) spec_report("specialised", names[i], f[i], take(i, f[i]));
+    else spec_report("specialised", names[i], f[i], false);
 }
 
 // Second group of a specialised handle, built the first time one of these entry points runs: the evaluating kernels of
@@ -243,26 +262,14 @@ static void spec_report(const char* what, const std::string& name, hipFunction_t
 void spec_aux(gsdf_program* p) {
   if (!p->spec_mod || p->spec_aux_tried) return;
   p->spec_aux_tried = true;
-  const std::string k = std::to_string(p->batch_k());
-  const std::string kw = k + ", " + std::to_string(p->sweep_waves(p->batch_k()));
-  std::vector<hipFunction_t> f;
+  const int k = p->batch_k();
   if (p->prog.is2d) {
-    if (spec_build(p, {"image2_kernel<" + k + ">"}, &p->spec_mod2, f, &p->spec_compile_s) == GSDF_OK) {
-      const bool ok = fn_scratch_bytes(f[0]) == 0;
-      spec_report("specialised", "image2_kernel", f[0], ok);
-      p->f_image = ok ? f[0] : nullptr;
-    }
+    spec_build_group(p, {"image2_kernel<" + std::to_string(k) + ">"}, [&](size_t, hipFunction_t f) { p->f_image = f; return true; });
   } else {
-    if (spec_build(p, {"dc_origin_kernel<" + kw + ">", "dc_edges_kernel", "dc_normals_kernel", "normals_kernel", "flat_grid_kernel<" + kw + ">", "dc_block_test_kernel"},
-                   &p->spec_mod2, f, &p->spec_compile_s) == GSDF_OK) {
-      const char* nm[6] = {"dc_origin_kernel", "dc_edges_kernel", "dc_normals_kernel", "normals_kernel", "flat_grid_kernel", "dc_block_test_kernel"};
-      hipFunction_t* dst[6] = {&p->f_dc_origin, &p->f_dc_edges, &p->f_dc_normals, &p->f_normals, &p->f_flat_grid, &p->f_dc_block_test};
-      for (int i = 0; i < 6; i++) {
-        const bool ok = fn_scratch_bytes(f[(size_t)i]) == 0;
-        spec_report("specialised", nm[i], f[(size_t)i], ok);
-        *dst[i] = ok ? f[(size_t)i] : nullptr;
-      }
-    }
+    // (both sweeps are built for sweep_variant's W; dual contouring's launch is the same whichever W its kernel was built for)
+    hipFunction_t* dst[6] = {&p->f_dc_origin, &p->f_dc_edges, &p->f_dc_normals, &p->f_normals, &p->f_flat_grid, &p->f_dc_block_test};
+    spec_build_group(p, {p->sweep_variant(k).spec_name("dc_origin_kernel"), "dc_edges_kernel", "dc_normals_kernel", "normals_kernel", p->sweep_variant(k).spec_name("flat_grid_kernel"), "dc_block_test_kernel"},
+                     [&](size_t i, hipFunction_t f) { *dst[i] = f; return true; });
   }
 }
 
@@ -274,28 +281,22 @@ void spec_aux(gsdf_program* p) {
 void spec_leaf_dz(gsdf_program* p) {
   if (!p->spec_mod || p->spec_dz_tried || p->prog.is2d) return;
   p->spec_dz_tried = true;
-  int lk, lw;
-  size_t lds_m;
-  p->leaf_config(&lk, &lw, &lds_m);
-  if (fused_leaf() || lk != 4 || !p->f_leaf || p->spec_leaf_k != 4) return;
-  const std::string nt = p->leaf_nt_in_lds() ? "true" : "false";
-  std::vector<std::string> names;
-  std::vector<int> ws;
-  std::vector<bool> both;
+  const gsdf_program::LeafConfig c = p->leaf_config();
+  if (fused_leaf() || c.k != 4 || !p->f_leaf || p->spec_leaf_k != 4) return;
+  std::vector<LeafVariant> vs;
   auto add = [&](int w, bool b) {
-    for (size_t i = 0; i < ws.size(); i++) if (ws[i] == w && both[i] == b) return;
-    names.push_back("leaf_eval_kernel<4, " + std::to_string(w) + ", true, " + nt + (b ? ", true, true>" : ", false, true>"));
-    ws.push_back(w); both.push_back(b);
+    for (const LeafVariant& v : vs) if (v.w == w && v.both == b) return;
+    vs.push_back({false, 4, w, true, c.ntlds, b, true});
   };
-  if (p->spec_leaf_both) { add(p->spec_leaf_w, true); add(lw, true); }
-  add(p->spec_leaf_w, false); add(lw, false);
-  std::vector<hipFunction_t> f;
-  if (spec_build(p, names, &p->spec_mod_dz, f, &p->spec_compile_s) != GSDF_OK) return;
-  for (size_t i = 0; i < names.size(); i++) {
-    const bool ok = fn_scratch_bytes(f[i]) == 0;
-    spec_report("specialised", names[i], f[i], ok && !p->f_leaf_dz);
-    if (ok && !p->f_leaf_dz) { p->f_leaf_dz = f[i]; p->spec_leaf_dz_w = ws[i]; p->spec_leaf_dz_both = both[i]; }
-  }
+  if (p->spec_leaf_both) { add(p->spec_leaf_w, true); add(c.w, true); }
+  add(p->spec_leaf_w, false); add(c.w, false);
+  std::vector<std::string> names;
+  for (const LeafVariant& v : vs) names.push_back(v.spec_name());
+  spec_build_group(p, names, [&](size_t i, hipFunction_t f) {
+    if (p->f_leaf_dz) return false;
+    p->f_leaf_dz = f; p->spec_leaf_dz_w = vs[i].w; p->spec_leaf_dz_both = vs[i].both;
+    return true;
+  });
 }
 
 // eval_kernel<D, 1, 4> for a specialised handle: one point per lane, what host-mapped Evaluate calls run (eval_dev). Built at the
@@ -305,12 +306,7 @@ void spec_eval_k1(gsdf_program* p) {
   std::lock_guard<std::mutex> lk(mu);
   if (!p->spec_mod || p->spec_k1_tried || p->batch_k() == 1) return;
   p->spec_k1_tried = true;
-  std::vector<hipFunction_t> f;
-  const std::string name = std::string("eval_kernel<") + (p->prog.is2d ? "2" : "3") + ", 1, 4>";
-  if (spec_build(p, {name}, &p->spec_mod_k1, f, &p->spec_compile_s) != GSDF_OK) return;
-  const bool ok = fn_scratch_bytes(f[0]) == 0;
-  spec_report("specialised", name, f[0], ok);
-  if (ok) p->f_eval_k1 = f[0];
+  spec_build_group(p, {SweepVariant{1, 4}.spec_name("eval_kernel", p->prog.is2d ? 2 : 3)}, [&](size_t, hipFunction_t f) { p->f_eval_k1 = f; return true; });
 }
 
 // leaf_dense_kernel (share_corners = 1: every bitwise-distinct lattice point of a brick once) for a specialised handle, at the most
@@ -321,15 +317,13 @@ void spec_leaf_dense(gsdf_program* p) {
   std::vector<std::string> names;
   std::vector<int> ws;
   for (int w = 5; w >= 3; w--)
-    if ((size_t)w * p->lds_dense() <= (size_t)160 * 1024) { names.push_back("leaf_dense_kernel<" + std::to_string(w) + ", true, true>"); ws.push_back(w); }
+    if ((size_t)w * p->lds_dense() <= gsdf_program::kLdsPerCu) { names.push_back("leaf_dense_kernel<" + std::to_string(w) + ", true, true>"); ws.push_back(w); }
   if (names.empty()) return;
-  std::vector<hipFunction_t> f;
-  if (spec_build(p, names, &p->spec_mod_dense, f, &p->spec_compile_s) != GSDF_OK) return;
-  for (size_t i = 0; i < names.size(); i++) {
-    const bool ok = fn_scratch_bytes(f[i]) == 0;
-    spec_report("specialised", names[i], f[i], ok && !p->f_leaf_dense);
-    if (ok && !p->f_leaf_dense) { p->f_leaf_dense = f[i]; p->spec_leaf_dense_w = ws[i]; }
-  }
+  spec_build_group(p, names, [&](size_t i, hipFunction_t f) {
+    if (p->f_leaf_dense) return false;
+    p->f_leaf_dense = f; p->spec_leaf_dense_w = ws[i];
+    return true;
+  });
 }
 
 // view_kernel, both forms (kernels_view.h), for a specialised handle: built at its first frame, in a module of its own that includes
@@ -338,15 +332,8 @@ void spec_leaf_dense(gsdf_program* p) {
 void spec_view(gsdf_program* p) {
   if (!p->spec_mod || p->spec_view_tried || p->prog.is2d) return;
   p->spec_view_tried = true;
-  const std::vector<std::string> names = {"view_kernel<true>", "view_kernel<false>"};
-  std::vector<hipFunction_t> f;
-  if (spec_build(p, names, &p->spec_mod_view, f, &p->spec_compile_s) != GSDF_OK) return;
   hipFunction_t* dst[2] = {&p->f_view, &p->f_view_plain};
-  for (int i = 0; i < 2; i++) {
-    const bool ok = fn_scratch_bytes(f[(size_t)i]) == 0;
-    spec_report("specialised", names[(size_t)i], f[(size_t)i], ok);
-    *dst[i] = ok ? f[(size_t)i] : nullptr;
-  }
+  spec_build_group(p, {"view_kernel<true>", "view_kernel<false>"}, [&](size_t i, hipFunction_t f) { *dst[i] = f; return true; });
 }
 
 // project_kernel (kernels_project.h) for a specialised handle: built at its first projection, in a module of its own that includes
@@ -355,11 +342,7 @@ void spec_view(gsdf_program* p) {
 void spec_project(gsdf_program* p) {
   if (!p->spec_mod || p->spec_project_tried || p->prog.is2d) return;
   p->spec_project_tried = true;
-  std::vector<hipFunction_t> f;
-  if (spec_build(p, {"project_kernel"}, &p->spec_mod_project, f, &p->spec_compile_s) != GSDF_OK) return;
-  const bool ok = fn_scratch_bytes(f[0]) == 0;
-  spec_report("specialised", "project_kernel", f[0], ok);
-  p->f_project = ok ? f[0] : nullptr;
+  spec_build_group(p, {"project_kernel"}, [&](size_t, hipFunction_t f) { p->f_project = f; return true; });
 }
 
 // image2_color_kernel<k, kind> for every conversion kind (kernels_image.h), for a specialised 2-D handle: built at its first picture,
@@ -370,13 +353,7 @@ void spec_image_color(gsdf_program* p) {
   const std::string k = std::to_string(p->batch_k());
   std::vector<std::string> names;
   for (int kind = 0; kind < 4; kind++) names.push_back("image2_color_kernel<" + k + ", " + std::to_string(kind) + ">");
-  std::vector<hipFunction_t> f;
-  if (spec_build(p, names, &p->spec_mod_imgc, f, &p->spec_compile_s) != GSDF_OK) return;
-  for (int i = 0; i < 4; i++) {
-    const bool ok = fn_scratch_bytes(f[(size_t)i]) == 0;
-    spec_report("specialised", names[(size_t)i], f[(size_t)i], ok);
-    p->f_imgc[i] = ok ? f[(size_t)i] : nullptr;
-  }
+  spec_build_group(p, names, [&](size_t i, hipFunction_t f) { p->f_imgc[i] = f; return true; });
 }
 
 // Compile and load kernels specialised for this handle's program (specialize.cpp): eval, prune and leaf kernels of
@@ -390,34 +367,33 @@ extern "C" int gsdf_hip_program_specialize(gsdf_program* p) {
   if (gsdf_dev::spec_instruction_count(p->prog) > 4000)
     return fail(GSDF_ERR_BAD_TREE, "program too large to specialise (more than 4000 instructions): the interpreter kernels stay in use");
   HIP_TRY(hipSetDevice(p->device));
-  int lk, lw;
-  size_t lds_m;
-  p->leaf_config(&lk, &lw, &lds_m);
-  const int ek = p->batch_k();
+  const gsdf_program::LeafConfig c = p->leaf_config();
+  const int lk = c.k, lw = c.w, dim = p->prog.is2d ? 2 : 3;
+  const bool fused = fused_leaf();
+  const SweepVariant ev = p->sweep_variant(p->batch_k());
+  const LeafVariant leaf{fused, lk, lw, !fused, !fused && c.ntlds, false, false};  // the configuration the mesher would pick
+  auto leaf_with = [&](int w, bool both) { LeafVariant v = leaf; v.w = w; v.both = both; return v; };
   std::vector<std::string> names;
-  int both_at = -1, both5_at = -1;
-  const int ew = p->sweep_waves(ek);
-  names.push_back(std::string("eval_kernel<") + (p->prog.is2d ? "2" : "3") + ", " + std::to_string(ek) + ", " + std::to_string(ew) + ">");
+  int five_at = -1, both_at = -1, both5_at = -1;
+  names.push_back(ev.spec_name("eval_kernel", dim));
   if (!p->prog.is2d) {
     names.push_back("prune_kernel");
     names.push_back("prune_spec_kernel");
-    names.push_back(std::string(fused_leaf() ? "leaf_kernel<" : "leaf_eval_kernel<") + std::to_string(lk) + ", " + std::to_string(lw) + (fused_leaf() ? ">" : (p->leaf_nt_in_lds() ? ", true, true, false, false>" : ", true, false, false, false>")));
+    names.push_back(leaf.spec_name());
+    const bool room5 = !fused && lk == 4 && lw == 4 && 5 * c.lds <= gsdf_program::kLdsPerCu;
     // a fifth workgroup per CU where the LDS has room for it (npt-flange's 7 slots): the 96-register build is taken if the
     // compiler reaches it without scratch (-3 % on the evaluating kernel); built beside the 128-register one, same process
-    if (!fused_leaf() && lk == 4 && lw == 4 && 5 * lds_m <= (size_t)160 * 1024) names.push_back("leaf_eval_kernel<4, 5, true, true, false, false>");
+    if (room5) { five_at = (int)names.size(); names.push_back(leaf_with(5, false).spec_name()); }
     // both passes of a column brick in one body -- taken, ahead of the others, if the compiler reaches it without scratch: -7 %
     // where much of the program depends on x and y alone (an atan2, several hypots: npt-flange), -1..2 % elsewhere
-    static const bool both_off = [] { const char* e = getenv("GSDF_HIP_NO_BOTH_PASSES"); return e && atoi(e) != 0; }();  // developer knob (A/B timing)
-    static const int both_min = [] { const char* e = getenv("GSDF_HIP_BOTH_MIN_WEIGHT"); return e ? atoi(e) : 0; }();  // developer knob. 0: always -- programs without x,y-only work gain 1-2 % too (bolt 1.029 -> 1.007 ms, knurled-cylinder 3.19 -> 3.16: one body of eight points schedules a little better than two of four)
-    if (!fused_leaf() && !both_off && lk == 4 && gsdf_dev::spec_xy_shared_weight(p->prog) >= both_min) {
+    static const bool both_off = env_flag("GSDF_HIP_NO_BOTH_PASSES");  // developer knob (A/B timing)
+    static const int both_min = env_int("GSDF_HIP_BOTH_MIN_WEIGHT", 0);  // developer knob. 0: always -- programs without x,y-only work gain 1-2 % too (bolt 1.029 -> 1.007 ms, knurled-cylinder 3.19 -> 3.16: one body of eight points schedules a little better than two of four)
+    if (!fused && !both_off && lk == 4 && gsdf_dev::spec_xy_shared_weight(p->prog) >= both_min) {
       both_at = (int)names.size();
-      names.push_back(std::string("leaf_eval_kernel<4, ") + std::to_string(lw) + (p->leaf_nt_in_lds() ? ", true, true, true, false>" : ", true, false, true, false>"));
+      names.push_back(leaf_with(lw, true).spec_name());
       // ... and at five workgroups per CU (96 registers) where the LDS has room: taken if it builds without scratch
-      static const bool both5_off = [] { const char* e = getenv("GSDF_HIP_NO_BOTH5"); return e && atoi(e) != 0; }();  // developer knob (A/B timing)
-      if (!both5_off && lw == 4 && 5 * lds_m <= (size_t)160 * 1024) {
-        both5_at = (int)names.size();
-        names.push_back(std::string("leaf_eval_kernel<4, 5") + (p->leaf_nt_in_lds() ? ", true, true, true, false>" : ", true, false, true, false>"));
-      }
+      static const bool both5_off = env_flag("GSDF_HIP_NO_BOTH5");  // developer knob (A/B timing)
+      if (!both5_off && room5) { both5_at = (int)names.size(); names.push_back(leaf_with(5, true).spec_name()); }
     }
   }
   std::vector<hipFunction_t> f;
@@ -427,57 +403,32 @@ extern "C" int gsdf_hip_program_specialize(gsdf_program* p) {
   p->spec_mod = mod;
   p->spec_compiler = gsdf_dev::spec_last_compiler();
   p->spec_key = gsdf_dev::spec_last_key();
-  p->spec_eval_k = ek; p->spec_eval_w = ew; p->spec_leaf_k = lk; p->spec_leaf_w = lw;
+  p->spec_eval_k = ev.k; p->spec_eval_w = ev.w; p->spec_leaf_k = lk; p->spec_leaf_w = lw;
   // No scratch, or not used (see fn_scratch_bytes). The eval kernel gets a second chance with the larger register
   // budget of 3 workgroups per CU before the handle falls back to the interpreter kernel for that entry point.
-  {
-    bool ok = fn_scratch_bytes(f[0]) == 0;
-    spec_report("specialised", names[0], f[0], ok);
-    p->f_eval = ok ? f[0] : nullptr;
-    if (!ok && ew == 4) {
-      std::vector<hipFunction_t> f3;
-      const std::string n3 = std::string("eval_kernel<") + (p->prog.is2d ? "2" : "3") + ", " + std::to_string(ek) + ", 3>";
-      if (spec_build(p, {n3}, &p->spec_mod3, f3, &p->spec_compile_s) == GSDF_OK) {
-        ok = fn_scratch_bytes(f3[0]) == 0;
-        spec_report("specialised", n3, f3[0], ok);
-        if (ok) { p->f_eval = f3[0]; p->spec_eval_w = 3; }
-      }
-    }
-  }
+  p->f_eval = spec_usable(names[0], f[0]) ? f[0] : nullptr;
+  if (!p->f_eval && ev.w == 4)
+    spec_build_group(p, {SweepVariant{ev.k, 3}.spec_name("eval_kernel", dim)}, [&](size_t, hipFunction_t f3) { p->f_eval = f3; p->spec_eval_w = 3; return true; });
   if (!p->prog.is2d) {
-    const bool okp = fn_scratch_bytes(f[1]) == 0, okt = fn_scratch_bytes(f[2]) == 0;
-    bool okl = fn_scratch_bytes(f[3]) == 0;
-    spec_report("specialised", names[1], f[1], okp);
-    spec_report("specialised", names[2], f[2], okt);
-    spec_report("specialised", names[3], f[3], okl);
-    p->f_prune = okp ? f[1] : nullptr;
-    p->f_prune_spec = okt ? f[2] : nullptr;
-    p->f_leaf = okl ? f[3] : nullptr;
-    if (f.size() > 4 && both_at != 4) {
-      const bool ok5 = fn_scratch_bytes(f[4]) == 0;
-      spec_report("specialised", names[4], f[4], ok5);
-      if (ok5) { p->f_leaf = f[4]; p->spec_leaf_w = 5; okl = true; }
-    }
-    if (both_at >= 0) {
-      const bool okb = fn_scratch_bytes(f[(size_t)both_at]) == 0;
-      spec_report("specialised", names[(size_t)both_at], f[(size_t)both_at], okb);
-      if (okb) { p->f_leaf = f[(size_t)both_at]; p->spec_leaf_w = lw; p->spec_leaf_both = true; okl = true; }
-      if (both5_at >= 0) {
-        const bool ok5b = fn_scratch_bytes(f[(size_t)both5_at]) == 0;
-        spec_report("specialised", names[(size_t)both5_at], f[(size_t)both5_at], ok5b);
-        if (ok5b) { p->f_leaf = f[(size_t)both5_at]; p->spec_leaf_w = 5; p->spec_leaf_both = true; okl = true; }
-      }
-    }
+    p->f_prune = spec_usable(names[1], f[1]) ? f[1] : nullptr;
+    p->f_prune_spec = spec_usable(names[2], f[2]) ? f[2] : nullptr;
+    // the leaf kernel: each later candidate that builds without scratch is preferred to the ones before it
+    auto take_leaf = [&](int at, int w, bool both) {
+      if (at < 0 || !spec_usable(names[(size_t)at], f[(size_t)at])) return;
+      p->f_leaf = f[(size_t)at]; p->spec_leaf_w = w; p->spec_leaf_both = both;
+    };
+    take_leaf(3, lw, false);
+    take_leaf(five_at, 5, false);
+    take_leaf(both_at, lw, true);
+    take_leaf(both5_at, 5, true);
     // the leaf kernel is where the time goes: before giving it up, trade occupancy for registers (W = workgroups per CU
     // the register budget is sized for; the launch is the same)
-    for (int w2 = lw - 1; !okl && w2 >= 2; w2--) {
+    for (int w2 = lw - 1; !p->f_leaf && w2 >= 2; w2--) {
       std::vector<hipFunction_t> fl;
       hipModule_t m2 = nullptr;
-      const std::string nl = std::string(fused_leaf() ? "leaf_kernel<" : "leaf_eval_kernel<") + std::to_string(lk) + ", " + std::to_string(w2) + (fused_leaf() ? ">" : (p->leaf_nt_in_lds() ? ", true, true, false, false>" : ", true, false, false, false>"));
+      const std::string nl = leaf_with(w2, false).spec_name();
       if (spec_build(p, {nl}, &m2, fl, &p->spec_compile_s) != GSDF_OK) break;
-      okl = fn_scratch_bytes(fl[0]) == 0;
-      spec_report("specialised", nl, fl[0], okl);
-      if (okl) { p->f_leaf = fl[0]; p->spec_leaf_w = w2; p->spec_mod4 = m2; }
+      if (spec_usable(nl, fl[0])) { p->f_leaf = fl[0]; p->spec_leaf_w = w2; p->mods.keep(m2); }
       else (void)hipModuleUnload(m2);
     }
   }
@@ -499,13 +450,13 @@ void spec_adopt_slow(gsdf_program* p) {
     p->spec_compile_s += q->spec_compile_s; p->spec_compiler = q->spec_compiler; p->spec_key = q->spec_key;
     p->spec_eval_k = q->spec_eval_k; p->spec_eval_w = q->spec_eval_w; p->spec_leaf_k = q->spec_leaf_k; p->spec_leaf_w = q->spec_leaf_w;
     p->spec_leaf_both = q->spec_leaf_both;
-    p->spec_mod3 = q->spec_mod3; p->spec_mod4 = q->spec_mod4;
+    p->mods.take(q->mods);
     std::atomic_thread_fence(std::memory_order_release);  // (the configuration before the functions: a reader that sees a function sees what it was built for)
     p->f_prune = q->f_prune; p->f_prune_spec = q->f_prune_spec; p->f_leaf = q->f_leaf; p->f_eval = q->f_eval;
     p->spec_mod = q->spec_mod;
-    q->spec_mod = q->spec_mod3 = q->spec_mod4 = nullptr;
+    q->spec_mod = nullptr;
   }
-  if (q) gsdf_hip_program_destroy(q);
+  delete q;
   p->spec_async.store(0, std::memory_order_release);
 }
 
@@ -529,7 +480,7 @@ extern "C" int gsdf_hip_program_specialize_async(gsdf_program* p) {
     });
   } catch (...) {
     p->spec_shadow = nullptr;
-    gsdf_hip_program_destroy(q);
+    delete q;
     p->spec_async.store(0);
     return fail(GSDF_ERR_CAPACITY, "cannot start the build thread");
   }
@@ -549,7 +500,8 @@ extern "C" int gsdf_hip_program_specialize_poll(gsdf_program* p, int wait) {
   if (p->spec_async.load(std::memory_order_acquire) == 3) {
     std::lock_guard<std::mutex> lk(p->spec_async_mu);
     if (p->spec_thread.joinable()) p->spec_thread.join();
-    if (p->spec_shadow) { gsdf_hip_program_destroy(p->spec_shadow); p->spec_shadow = nullptr; }
+    delete p->spec_shadow;
+    p->spec_shadow = nullptr;
     p->spec_async.store(0);
     return fail(GSDF_ERR_HIP, "background specialisation failed: " + p->spec_async_err);
   }
@@ -566,25 +518,22 @@ extern "C" int gsdf_hip_program_is_specialized(const gsdf_program* p, double* co
  * prune=prune_kernel:specialised" (":interpreter" for the ahead-of-time kernels): what a profile of the handle shows. */
 extern "C" int gsdf_hip_program_kernels(const gsdf_program* p, char* dst, size_t dst_cap) {
   if (!p || !dst || dst_cap == 0) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
-  int lk, lw;
-  size_t lds_m;
-  p->leaf_config(&lk, &lw, &lds_m);
+  // the rules the launches go by: eval_dev's, the leaf phase of a mesh of three levels or more (gsdf_program::leaf_pick)
   const int ek = p->batch_k();
-  const bool se = p->f_eval && p->spec_eval_k == ek, sl = p->f_leaf && p->spec_leaf_k == lk;
-  const int ew = se ? p->spec_eval_w : p->sweep_waves(ek);
-  // ahead-of-time leaf kernels exist at the scratch-free occupancies only (see gsdf_hip_mesh_octree)
-  const int aw = lk == 4 ? (lw == 2 ? 2 : 3) : (lk == 2 ? 3 : 4);
+  const bool se = p->f_eval && p->spec_eval_k == ek;
+  const SweepVariant ev = se ? SweepVariant{ek, p->spec_eval_w} : p->sweep_variant(ek);
+  const LeafPick leaf = p->leaf_pick(3);
+  auto how = [](const void* f) { return f ? "specialised" : "interpreter"; };
   char buf[512];
   if (p->prog.is2d)
-    snprintf(buf, sizeof buf, "eval=eval_kernel<2,%d,%d>:%s", ek, ew, se ? "specialised" : "interpreter");
+    snprintf(buf, sizeof buf, "eval=%s:%s", ev.short_name("eval_kernel", 2).c_str(), how(se ? p->f_eval : nullptr));
   else
-    snprintf(buf, sizeof buf, "eval=eval_kernel<3,%d,%d>:%s leaf=%s<%d,%d%s>:%s prune=prune_kernel:%s", ek, ew, se ? "specialised" : "interpreter",
-             fused_leaf() ? "leaf_kernel" : "leaf_eval_kernel", lk, sl ? p->spec_leaf_w : aw, sl && p->spec_leaf_both ? ",both" : "", sl ? "specialised" : "interpreter",
-             p->f_prune ? "specialised" : "interpreter");
+    snprintf(buf, sizeof buf, "eval=%s:%s leaf=%s:%s prune=prune_kernel:%s", ev.short_name("eval_kernel", 3).c_str(), how(se ? p->f_eval : nullptr),
+             leaf.v.short_name().c_str(), how(leaf.f), how(p->f_prune));
   if (p->f_leaf_dense && strlen(buf) + 64 < sizeof buf)  // the evaluating kernel of share_corners = 1, once it has been built
     snprintf(buf + strlen(buf), sizeof buf - strlen(buf), " leaf_dense=leaf_dense_kernel<%d>:specialised", p->spec_leaf_dense_w);
   if (p->f_leaf_dz && strlen(buf) + 64 < sizeof buf)  // the evaluating kernel of share_corners = 2, once it has been built
-    snprintf(buf + strlen(buf), sizeof buf - strlen(buf), " leaf_rows=leaf_eval_kernel<4,%d%s,rows>:specialised", p->spec_leaf_dz_w, p->spec_leaf_dz_both ? ",both" : "");
+    snprintf(buf + strlen(buf), sizeof buf - strlen(buf), " leaf_rows=%s:specialised", p->leaf_pick(3, true).v.short_name().c_str());
   if (p->prog.is2d && strlen(buf) + 64 < sizeof buf) {  // the picture kernels (a specialised handle builds its own at its first picture)
     std::string kinds;
     for (int i = 0; i < 4; i++) if (p->f_imgc[i]) kinds += std::to_string(i);
@@ -592,12 +541,11 @@ extern "C" int gsdf_hip_program_kernels(const gsdf_program* p, char* dst, size_t
              kinds.empty() ? "interpreter" : ("specialised/" + kinds).c_str());
   }
   if (!p->prog.is2d && strlen(buf) + 48 < sizeof buf)  // the projection of mesh vertices (a specialised handle builds its own at its first projection)
-    snprintf(buf + strlen(buf), sizeof buf - strlen(buf), " project=project_kernel:%s", p->f_project ? "specialised" : "interpreter");
+    snprintf(buf + strlen(buf), sizeof buf - strlen(buf), " project=project_kernel:%s", how(p->f_project));
   if (strlen(buf) + 160 < sizeof buf) {  // the sweeps that carry a K of their own, and what the LDS limits of the meshers count (gsdf_hip.h: Largest trees)
-    const int dk = ek, dw = gsdf_program::dc_origin_waves(ek);  // (the rule gsdf_hip_mesh_dualcontour launches by; flat: sweep_waves, as its launch)
-    if (p->prog.is2d) snprintf(buf + strlen(buf), sizeof buf - strlen(buf), " image=image2_kernel<%d>:%s", ek, p->f_image ? "specialised" : "interpreter");
-    else snprintf(buf + strlen(buf), sizeof buf - strlen(buf), " flat=flat_grid_kernel<%d,%d>:%s dc=dc_origin_kernel<%d,%d>:%s interval=%d", ek, p->sweep_waves(ek),
-                  p->f_flat_grid ? "specialised" : "interpreter", dk, dw, p->f_dc_origin ? "specialised" : "interpreter", p->prog.lip_depth);
+    if (p->prog.is2d) snprintf(buf + strlen(buf), sizeof buf - strlen(buf), " image=image2_kernel<%d>:%s", ek, how(p->f_image));
+    else snprintf(buf + strlen(buf), sizeof buf - strlen(buf), " flat=%s:%s dc=%s:%s interval=%d", p->sweep_variant(ek).short_name("flat_grid_kernel").c_str(), how(p->f_flat_grid),
+                  gsdf_program::dc_origin_variant(ek).short_name("dc_origin_kernel").c_str(), how(p->f_dc_origin), p->prog.lip_depth);
   }
   if (p->spec_mod && strlen(buf) + 32 < sizeof buf) { strcat(buf, " compiler="); strcat(buf, p->spec_compiler.c_str()); }
   {  // identity of the code that runs: a stored profile describes this handle's kernels only if it carries the same key
@@ -672,47 +620,7 @@ extern "C" int gsdf_hip_lower_region(const gsdf_tree* tree, uint32_t node, int* 
   }
 }
 
-extern "C" void gsdf_hip_program_destroy(gsdf_program* p) {
-  if (!p) return;
-  if (p->spec_thread.joinable()) p->spec_thread.join();  // a build under way finishes first (its thread writes into this handle)
-  if (p->spec_shadow) { gsdf_hip_program_destroy(p->spec_shadow); p->spec_shadow = nullptr; }
-  if (p->d_code) (void)hipFree(p->d_code);
-  if (p->d_pos) (void)hipFree(p->d_pos);
-  if (p->d_dist) (void)hipFree(p->d_dist);
-  if (p->h_pos) (void)hipHostFree(p->h_pos);
-  if (p->h_dist) (void)hipHostFree(p->h_dist);
-  for (auto& sl : p->slot) {
-    if (sl.h_pos) (void)hipHostFree(sl.h_pos);
-    if (sl.h_dist) (void)hipHostFree(sl.h_dist);
-    if (sl.h_flag) (void)hipHostFree(sl.h_flag);
-    if (sl.s) (void)hipStreamDestroy(sl.s);
-  }
-  if (p->spec_mod) (void)hipModuleUnload(p->spec_mod);
-  if (p->spec_mod2) (void)hipModuleUnload(p->spec_mod2);
-  if (p->spec_mod3) (void)hipModuleUnload(p->spec_mod3);
-  if (p->spec_mod4) (void)hipModuleUnload(p->spec_mod4);
-  if (p->spec_mod_dz) (void)hipModuleUnload(p->spec_mod_dz);
-  if (p->spec_mod_k1) (void)hipModuleUnload(p->spec_mod_k1);
-  if (p->spec_mod_dense) (void)hipModuleUnload(p->spec_mod_dense);
-  if (p->spec_mod_view) (void)hipModuleUnload(p->spec_mod_view);
-  if (p->spec_mod_project) (void)hipModuleUnload(p->spec_mod_project);
-  if (p->proj_ctr) (void)hipFree(p->proj_ctr);
-  for (auto ev1 : p->ev_proj) if (ev1) (void)hipEventDestroy(ev1);
-  if (p->spec_mod_imgc) (void)hipModuleUnload(p->spec_mod_imgc);
-  p->q0.release(); p->q1.release(); p->ctr.release();
-  p->rec.release(); p->hdr.release(); p->grp.release();
-  p->b_q0.release(); p->b_q1.release(); p->b_ctr.release(); p->b_spec_pass.release(); p->b_rec.release(); p->b_hdr.release(); p->b_grp.release();
-  p->c_q0.release(); p->c_q1.release(); p->c_ctr.release(); p->c_spec_pass.release(); p->c_rec.release(); p->c_hdr.release(); p->c_grp.release();
-  if (p->stream_b) (void)hipStreamDestroy(p->stream_b);
-  if (p->stream_c) (void)hipStreamDestroy(p->stream_c);
-  p->flat_grid.release(); p->flat_bits.release(); p->flat_list.release(); p->dc_tile.release(); p->dc_grid.release(); p->dc_dist.release(); p->dc_fv.release(); p->dc_nrm.release(); p->dc_edge.release(); p->dc_erun.release(); p->dc_flag.release(); p->dc_ix.release(); p->dc_ix_sort.release();
-  for (auto e : p->ev) if (e) (void)hipEventDestroy(e);
-  for (auto e : p->ev_b) if (e) (void)hipEventDestroy(e);
-  for (auto e : p->ev_c) if (e) (void)hipEventDestroy(e);
-  if (p->h_ctr) (void)hipHostFree(p->h_ctr);
-  if (p->stream) (void)hipStreamDestroy(p->stream);
-  delete p;
-}
+extern "C" void gsdf_hip_program_destroy(gsdf_program* p) { delete p; }  // (~gsdf_program, abi_program.h)
 
 extern "C" int gsdf_hip_program_bounds(const gsdf_program* p, float bb[6]) {
   if (!p || !bb) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
@@ -728,6 +636,20 @@ extern "C" int gsdf_hip_program_info(const gsdf_program* p, uint32_t* code_words
 }
 extern "C" uint64_t gsdf_hip_evaluations(const gsdf_program* p) { return p ? p->evals + p->evals_host.load() : 0; }
 
+// The ahead-of-time eval_kernel<DIM, K, W> of a variant: exactly the instantiations this library launches (null: none).
+using eval_kernel_t = decltype(&eval_kernel<3, 4, 4>);
+static eval_kernel_t eval_aot(int dim, SweepVariant v) {
+  const int w = v.k == 1 ? 4 : (v.w == 4 ? 4 : 3);
+  if (dim == 3) {
+    if (v.k == 4) return w == 4 ? eval_kernel<3, 4, 4> : eval_kernel<3, 4, 3>;
+    if (v.k == 2) return w == 4 ? eval_kernel<3, 2, 4> : eval_kernel<3, 2, 3>;
+    return eval_kernel<3, 1, 4>;
+  }
+  if (v.k == 4) return w == 4 ? eval_kernel<2, 4, 4> : eval_kernel<2, 4, 3>;
+  if (v.k == 2) return w == 4 ? eval_kernel<2, 2, 4> : eval_kernel<2, 2, 3>;
+  return eval_kernel<2, 1, 4>;
+}
+
 // host_mapped: the buffers are pinned host memory the kernel reaches across PCIe (the host-buffer API's small and registered calls).
 // Such a call is bound by the reads' latency and bandwidth, not by the evaluation: ONE point per lane puts four times as many
 // workgroups on the bus at once (32 768 points: 128 workgroups instead of 32) -- 24.6 -> 19.6 us per blocking call from registered
@@ -735,7 +657,7 @@ extern "C" uint64_t gsdf_hip_evaluations(const gsdf_program* p) { return p ? p->
 static int eval_dev(gsdf_program* p, int dim, const void* d_pos, size_t stride_bytes, float* d_dist, size_t n, hipStream_t s, bool count = true, bool host_mapped = false) {
   if (stride_bytes % 4 != 0 || stride_bytes < (size_t)dim * 4) return fail(GSDF_ERR_BAD_ARGUMENT, "bad position stride");
   spec_adopt(p);  // (a background build that has finished: its kernels from here on)
-  static const bool k1_off = [] { const char* e = getenv("GSDF_HIP_NO_EVAL_K1"); return e && atoi(e) != 0; }();  // developer knob (A/B timing)
+  static const bool k1_off = env_flag("GSDF_HIP_NO_EVAL_K1");  // developer knob (A/B timing)
   // This entry runs on several host threads at once (the host-buffer calls): the kernel it launches and what that kernel was built
   // for are read as ONE snapshot under the mutex an adopting thread holds while it swaps them (spec_adopt_slow).
   hipFunction_t f_eval = nullptr, f_eval_k1 = nullptr;
@@ -746,29 +668,12 @@ static int eval_dev(gsdf_program* p, int dim, const void* d_pos, size_t stride_b
   }
   const bool latency = host_mapped && !k1_off && (f_eval_k1 != nullptr || f_eval == nullptr);  // (a specialised handle without a K = 1 build keeps its specialised kernel)
   const int k = latency ? 1 : p->batch_k();
-  static const int eval_bpc = [] { const char* e = getenv("GSDF_HIP_EVAL_BPC"); return e ? atoi(e) : 64; }();  // tuning knob: finer grids drain evenly (8 -> 64 per CU: +10 % on npt-flange)
+  static const int eval_bpc = env_int("GSDF_HIP_EVAL_BPC", 64);  // tuning knob: finer grids drain evenly (8 -> 64 per CU: +10 % on npt-flange)
   const unsigned grid = grid_for((n + k - 1) / k, p->num_cu, eval_bpc);
-  const uint32_t sf = (uint32_t)(stride_bytes / 4);
-  const float* q = (const float*)d_pos;
-  const uint64_t nn = (uint64_t)n;
-  const int w = p->sweep_waves(k);
-#define LAUNCH_EVAL(D, KK, WW) hipLaunchKernelGGL((eval_kernel<D, KK, WW>), dim3(grid), dim3(BLOCK), p->lds_bytes(KK), s, p->d_code, q, sf, d_dist, nn)
-  if (latency && f_eval_k1) {
-    HIP_TRY(launch_fn(f_eval_k1, grid, BLOCK, p->lds_bytes(1), s, (const uint32_t*)p->d_code, q, sf, d_dist, nn));
-  } else if (f_eval && spec_eval_k == k) {  // whichever W the specialised kernel was built for: same launch
-    HIP_TRY(launch_fn(f_eval, grid, BLOCK, p->lds_bytes(k), s, (const uint32_t*)p->d_code, q, sf, d_dist, nn));
-  } else
-  if (dim == 3) {
-    if (k == 4) { if (w == 4) LAUNCH_EVAL(3, 4, 4); else LAUNCH_EVAL(3, 4, 3); }
-    else if (k == 2) { if (w == 4) LAUNCH_EVAL(3, 2, 4); else LAUNCH_EVAL(3, 2, 3); }
-    else LAUNCH_EVAL(3, 1, 4);
-  } else {
-    if (k == 4) { if (w == 4) LAUNCH_EVAL(2, 4, 4); else LAUNCH_EVAL(2, 4, 3); }
-    else if (k == 2) { if (w == 4) LAUNCH_EVAL(2, 2, 4); else LAUNCH_EVAL(2, 2, 3); }
-    else LAUNCH_EVAL(2, 1, 4);
-  }
-#undef LAUNCH_EVAL
-  HIP_TRY(hipGetLastError());
+  // the per-tree kernel with one point per lane for a latency-bound call, else the one built for this K (whichever W it was
+  // built for: same launch), else the interpreter's
+  const hipFunction_t f = latency && f_eval_k1 ? f_eval_k1 : (f_eval && spec_eval_k == k ? f_eval : nullptr);
+  HIP_TRY(launch_kernel(eval_aot(dim, p->sweep_variant(k)), f, grid, BLOCK, p->lds_bytes(k), s, p->d_code.p, d_pos, stride_bytes / 4, d_dist, n));
   if (count) p->evals += n;  // (concurrent host-buffer callers count through evals_host instead)
   return GSDF_OK;
 }
@@ -851,7 +756,7 @@ static int eval_submit(gsdf_program* p, int dim, const void* pos, size_t stride,
   if (rc) return rc;
   gsdf_program::Slot& sl = p->slot[si];
   auto bail = [&](int code) { slot_release(p, si); return code; };
-  if (!sl.s && hipStreamCreateWithFlags(&sl.s, hipStreamNonBlocking) != hipSuccess) return bail(fail(GSDF_ERR_HIP, "hipStreamCreate failed"));
+  if (sl.s.ensure() != hipSuccess) return bail(fail(GSDF_ERR_HIP, "hipStreamCreate failed"));
   void* dp = reg_device_ptr(pos, pbytes);
   void* dd = dp ? reg_device_ptr(dist, n_pos * sizeof(float)) : nullptr;
   sl.zero_copy = dp && dd;
@@ -859,28 +764,28 @@ static int eval_submit(gsdf_program* p, int dim, const void* pos, size_t stride,
   sl.n = n_pos;
   if (!sl.zero_copy) {
     if (pbytes > kSmallPos || n_pos > kSmallDist) return bail(fail(GSDF_ERR_BAD_ARGUMENT, "internal: large call on the small path"));
-    if (!sl.h_pos && hipHostMalloc(&sl.h_pos, kSmallPos, hipHostMallocMapped | hipHostMallocPortable) != hipSuccess) return bail(fail(GSDF_ERR_HIP, "hipHostMalloc failed"));
-    if (!sl.h_dist && hipHostMalloc((void**)&sl.h_dist, kSmallDist * sizeof(float), hipHostMallocMapped | hipHostMallocPortable) != hipSuccess) return bail(fail(GSDF_ERR_HIP, "hipHostMalloc failed"));
-    std::memcpy(sl.h_pos, pos, pbytes);
-    if (hipHostGetDevicePointer(&dp, sl.h_pos, 0) != hipSuccess || hipHostGetDevicePointer(&dd, sl.h_dist, 0) != hipSuccess) return bail(fail(GSDF_ERR_HIP, "hipHostGetDevicePointer failed"));
+    if (!sl.h_pos.p && hipHostMalloc(&sl.h_pos.p, kSmallPos, hipHostMallocMapped | hipHostMallocPortable) != hipSuccess) return bail(fail(GSDF_ERR_HIP, "hipHostMalloc failed"));
+    if (!sl.h_dist.p && hipHostMalloc((void**)&sl.h_dist.p, kSmallDist * sizeof(float), hipHostMallocMapped | hipHostMallocPortable) != hipSuccess) return bail(fail(GSDF_ERR_HIP, "hipHostMalloc failed"));
+    std::memcpy(sl.h_pos.p, pos, pbytes);
+    if (hipHostGetDevicePointer(&dp, sl.h_pos.p, 0) != hipSuccess || hipHostGetDevicePointer(&dd, sl.h_dist.p, 0) != hipSuccess) return bail(fail(GSDF_ERR_HIP, "hipHostGetDevicePointer failed"));
   }
   if (p->spec_mod && !p->spec_k1_tried) spec_eval_k1(p);
-  rc = eval_dev(p, dim, dp, stride, (float*)dd, n_pos, sl.s, /*count=*/false, /*host_mapped=*/true);
+  rc = eval_dev(p, dim, dp, stride, (float*)dd, n_pos, sl.s.s, /*count=*/false, /*host_mapped=*/true);
   if (rc) return bail(rc);
   // completion flag behind the kernel (eval_wait polls it; hipStreamSynchronize remains the fallback)
   // (hipStreamWriteValue32 instead of the one-thread kernel was tried: slower, 38.7 vs 29.9 us per blocking pageable call)
-  static const bool use_flag = [] { const char* e = getenv("GSDF_HIP_EVAL_FLAG"); return !e || atoi(e) != 0; }();  // developer knob (A/B timing)
+  static const bool use_flag = env_flag_on("GSDF_HIP_EVAL_FLAG");  // developer knob (A/B timing)
   sl.flagged = false;
   if (use_flag) {
-    if (!sl.h_flag) {
+    if (!sl.h_flag.p) {
       void* hf = nullptr; void* df = nullptr;
       if (hipHostMalloc(&hf, 64, hipHostMallocMapped | hipHostMallocPortable) == hipSuccess && hipHostGetDevicePointer(&df, hf, 0) == hipSuccess) {
-        sl.h_flag = (unsigned*)hf; sl.d_flag = (unsigned*)df; *sl.h_flag = 0u;
+        sl.h_flag.p = (unsigned*)hf; sl.d_flag = (unsigned*)df; *sl.h_flag.p = 0u;
       } else { (void)hipGetLastError(); if (hf) (void)hipHostFree(hf); }
     }
-    if (sl.h_flag) {
+    if (sl.h_flag.p) {
       sl.flag_val = sl.flag_val + 1u ? sl.flag_val + 1u : 1u;
-      hipLaunchKernelGGL(signal_kernel, dim3(1), dim3(1), 0, sl.s, sl.d_flag, sl.flag_val);
+      hipLaunchKernelGGL(signal_kernel, dim3(1), dim3(1), 0, sl.s.s, sl.d_flag, sl.flag_val);
       if (hipGetLastError() == hipSuccess) sl.flagged = true;
     }
   }
@@ -901,7 +806,7 @@ static int eval_wait(gsdf_program* p, int tk) {
   hipError_t e = hipSuccess;
   bool done = false;
   if (sl.flagged) {  // poll the flag the stream writes behind the kernel: ~100 us of spinning at most, then the blocking wait
-    const volatile unsigned* f = sl.h_flag;
+    const volatile unsigned* f = sl.h_flag.p;
     const auto t0 = std::chrono::steady_clock::now();
     for (unsigned spin = 0;; spin++) {
       if (*f == sl.flag_val) { done = true; break; }
@@ -910,8 +815,8 @@ static int eval_wait(gsdf_program* p, int tk) {
     }
     std::atomic_thread_fence(std::memory_order_acquire);
   }
-  if (!done) e = hipStreamSynchronize(sl.s);
-  if (e == hipSuccess && !sl.zero_copy) std::memcpy(sl.user_dist, sl.h_dist, sl.n * sizeof(float));
+  if (!done) e = hipStreamSynchronize(sl.s.s);
+  if (e == hipSuccess && !sl.zero_copy) std::memcpy(sl.user_dist, sl.h_dist.p, sl.n * sizeof(float));
   slot_release(p, ticket);
   if (e != hipSuccess) return fail(GSDF_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
   return GSDF_OK;
@@ -935,22 +840,22 @@ static int eval_host(gsdf_program* p, int dim, const void* pos, size_t stride, s
   static std::mutex big_mu;
   std::lock_guard<std::mutex> lk(big_mu);
   if (pbytes > p->cap_pos_bytes) {
-    if (p->d_pos) (void)hipFree(p->d_pos);
-    p->d_pos = nullptr; p->cap_pos_bytes = 0;
-    HIP_TRY(hipMalloc(&p->d_pos, pbytes));
+    p->d_pos.reset();
+    p->cap_pos_bytes = 0;
+    HIP_TRY(hipMalloc(&p->d_pos.p, pbytes));
     p->cap_pos_bytes = pbytes;
   }
   if (n_pos > p->cap_dist) {
-    if (p->d_dist) (void)hipFree(p->d_dist);
-    p->d_dist = nullptr; p->cap_dist = 0;
-    HIP_TRY(hipMalloc((void**)&p->d_dist, n_pos * sizeof(float)));
+    p->d_dist.reset();
+    p->cap_dist = 0;
+    HIP_TRY(hipMalloc((void**)&p->d_dist.p, n_pos * sizeof(float)));
     p->cap_dist = n_pos;
   }
-  HIP_TRY(hipMemcpyAsync(p->d_pos, pos, pbytes, hipMemcpyHostToDevice, p->stream));
-  int rc = eval_dev(p, dim, p->d_pos, stride, p->d_dist, n_pos, p->stream);
+  HIP_TRY(hipMemcpyAsync(p->d_pos.p, pos, pbytes, hipMemcpyHostToDevice, p->stream.s));
+  int rc = eval_dev(p, dim, p->d_pos.p, stride, p->d_dist.p, n_pos, p->stream.s);
   if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(dist, p->d_dist, n_pos * sizeof(float), hipMemcpyDeviceToHost, p->stream));
-  HIP_TRY(hipStreamSynchronize(p->stream));
+  HIP_TRY(hipMemcpyAsync(dist, p->d_dist.p, n_pos * sizeof(float), hipMemcpyDeviceToHost, p->stream.s));
+  HIP_TRY(hipStreamSynchronize(p->stream.s));
   return GSDF_OK;
 }
 
@@ -978,13 +883,13 @@ extern "C" int gsdf_hip_eval3_dev(gsdf_program* p, const void* d_pos, size_t str
   if (!p || !d_pos || !d_dist) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
   if (n == 0) return fail(GSDF_ERR_EMPTY_BUFFERS, "empty buffers");
   if (p->prog.is2d) return fail(GSDF_ERR_DIMENSION, "program is 2D, eval3 called");
-  return eval_dev(p, 3, d_pos, stride, d_dist, n, stream ? (hipStream_t)stream : p->stream);
+  return eval_dev(p, 3, d_pos, stride, d_dist, n, stream ? (hipStream_t)stream : p->stream.s);
 }
 extern "C" int gsdf_hip_eval2_dev(gsdf_program* p, const void* d_pos, size_t stride, float* d_dist, size_t n, void* stream) {
   if (!p || !d_pos || !d_dist) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
   if (n == 0) return fail(GSDF_ERR_EMPTY_BUFFERS, "empty buffers");
   if (!p->prog.is2d) return fail(GSDF_ERR_DIMENSION, "program is 3D, eval2 called");
-  return eval_dev(p, 2, d_pos, stride, d_dist, n, stream ? (hipStream_t)stream : p->stream);
+  return eval_dev(p, 2, d_pos, stride, d_dist, n, stream ? (hipStream_t)stream : p->stream.s);
 }
 
 extern "C" int gsdf_hip_normals3(gsdf_program* p, const float* pos, float* normals, size_t n, float step) {
@@ -1001,16 +906,14 @@ extern "C" int gsdf_hip_normals3(gsdf_program* p, const float* pos, float* norma
   if (hipMalloc((void**)&d_n, n * 12) != hipSuccess) { (void)hipFree(d_p); return fail(GSDF_ERR_HIP, "hipMalloc failed"); }
   int rc = GSDF_OK;
   do {
-    if (hipMemcpyAsync(d_p, pos, n * 12, hipMemcpyHostToDevice, p->stream) != hipSuccess) { rc = fail(GSDF_ERR_HIP, "H2D copy failed"); break; }
+    if (hipMemcpyAsync(d_p, pos, n * 12, hipMemcpyHostToDevice, p->stream.s) != hipSuccess) { rc = fail(GSDF_ERR_HIP, "H2D copy failed"); break; }
     spec_aux(p);
-    if (p->f_normals) {
-      if (launch_fn(p->f_normals, grid_for(n, p->num_cu, 8), BLOCK, p->lds_bytes(2), p->stream, (const uint32_t*)p->d_code, (const float*)d_p, (float*)d_n,
-                    (uint64_t)n, (float)step) != hipSuccess) { rc = fail(GSDF_ERR_HIP, "kernel launch failed"); break; }
-    } else
-    hipLaunchKernelGGL(normals_kernel, dim3(grid_for(n, p->num_cu, 8)), dim3(BLOCK), p->lds_bytes(2), p->stream, p->d_code, d_p, d_n, (uint64_t)n, step);
-    if (hipGetLastError() != hipSuccess) { rc = fail(GSDF_ERR_HIP, "normals kernel launch failed"); break; }
-    if (hipMemcpyAsync(normals, d_n, n * 12, hipMemcpyDeviceToHost, p->stream) != hipSuccess) { rc = fail(GSDF_ERR_HIP, "D2H copy failed"); break; }
-    if (hipStreamSynchronize(p->stream) != hipSuccess) { rc = fail(GSDF_ERR_HIP, "stream sync failed"); break; }
+    if (launch_kernel(normals_kernel, p->f_normals, grid_for(n, p->num_cu, 8), BLOCK, p->lds_bytes(2), p->stream.s, p->d_code.p, d_p, d_n, n, step) != hipSuccess) {
+      rc = fail(GSDF_ERR_HIP, "normals kernel launch failed");
+      break;
+    }
+    if (hipMemcpyAsync(normals, d_n, n * 12, hipMemcpyDeviceToHost, p->stream.s) != hipSuccess) { rc = fail(GSDF_ERR_HIP, "D2H copy failed"); break; }
+    if (hipStreamSynchronize(p->stream.s) != hipSuccess) { rc = fail(GSDF_ERR_HIP, "stream sync failed"); break; }
     p->evals += 6 * n;
   } while (0);
   (void)hipFree(d_p);
@@ -1029,14 +932,8 @@ int normals3_dev(gsdf_program* p, const float* d_pos, float* d_nrm, size_t n, fl
   HIP_TRY(hipSetDevice(p->device));
   spec_adopt(p);
   spec_aux(p);
-  if (p->f_normals) {
-    HIP_TRY(launch_fn(p->f_normals, grid_for(n, p->num_cu, 8), BLOCK, p->lds_bytes(2), p->stream, (const uint32_t*)p->d_code, (const float*)d_pos, (float*)d_nrm,
-                      (uint64_t)n, (float)step));
-  } else {
-    hipLaunchKernelGGL(normals_kernel, dim3(grid_for(n, p->num_cu, 8)), dim3(BLOCK), p->lds_bytes(2), p->stream, p->d_code, d_pos, d_nrm, (uint64_t)n, step);
-    HIP_TRY(hipGetLastError());
-  }
-  HIP_TRY(hipStreamSynchronize(p->stream));
+  HIP_TRY(launch_kernel(normals_kernel, p->f_normals, grid_for(n, p->num_cu, 8), BLOCK, p->lds_bytes(2), p->stream.s, p->d_code.p, d_pos, d_nrm, n, step));
+  HIP_TRY(hipStreamSynchronize(p->stream.s));
   p->evals += 6 * n;
   return GSDF_OK;
 }
@@ -1053,31 +950,23 @@ int project_dev(gsdf_program* p, const float* d_pos, size_t n, const gsdf_projec
   HIP_TRY(hipSetDevice(p->device));
   spec_adopt(p);
   spec_project(p);
-  if (!p->proj_ctr) HIP_TRY(hipMalloc(&p->proj_ctr, sizeof(ProjectCounters)));
-  for (hipEvent_t& ev1 : p->ev_proj)
-    if (!ev1) HIP_TRY(hipEventCreate(&ev1));
-  hipEvent_t* ev = p->ev_proj;
-  ProjectCounters* d_ctr = (ProjectCounters*)p->proj_ctr;
+  if (!p->proj_ctr.p) HIP_TRY(hipMalloc(&p->proj_ctr.p, sizeof(ProjectCounters)));
+  HIP_TRY(p->ev_proj.ensure());
+  const EventSet<2>& ev = p->ev_proj;
+  ProjectCounters* d_ctr = (ProjectCounters*)p->proj_ctr.p;
   ProjectCounters hc{};
   float ms = 0.f;
   const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
   const float h = o->step * 0.5f;
-  hipError_t e = hipMemsetAsync(d_ctr, 0, sizeof(ProjectCounters), p->stream);
-  if (e == hipSuccess) e = hipEventRecord(ev[0], p->stream);
-  if (e == hipSuccess) {
-    if (p->f_project)
-      e = launch_fn(p->f_project, grid, BLOCK, p->lds_bytes(2), p->stream, (const uint32_t*)p->d_code, (const unsigned*)d_pos, (uint64_t)n, h, (float)o->tol,
-                    (float)o->max_move, (int)o->max_iters, (unsigned*)d_out_pos, d_before, d_after, (unsigned char*)d_status, d_ctr);
-    else {
-      hipLaunchKernelGGL(project_kernel, dim3(grid), dim3(BLOCK), p->lds_bytes(2), p->stream, p->d_code, (const unsigned*)d_pos, (uint64_t)n, h, o->tol, o->max_move,
-                         (int)o->max_iters, (unsigned*)d_out_pos, d_before, d_after, (unsigned char*)d_status, d_ctr);
-      e = hipGetLastError();
-    }
-  }
-  if (e == hipSuccess) e = hipEventRecord(ev[1], p->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(&hc, d_ctr, sizeof hc, hipMemcpyDeviceToHost, p->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-  else (void)hipStreamSynchronize(p->stream);
+  hipError_t e = hipMemsetAsync(d_ctr, 0, sizeof(ProjectCounters), p->stream.s);
+  if (e == hipSuccess) e = hipEventRecord(ev[0], p->stream.s);
+  if (e == hipSuccess)  // (the kernel takes the positions as words: (const unsigned*) cannot be left to the launcher's static_cast)
+    e = launch_kernel(project_kernel, p->f_project, grid, BLOCK, p->lds_bytes(2), p->stream.s, p->d_code.p, (const unsigned*)d_pos, n, h, o->tol, o->max_move, o->max_iters,
+                      (unsigned*)d_out_pos, d_before, d_after, d_status, d_ctr);
+  if (e == hipSuccess) e = hipEventRecord(ev[1], p->stream.s);
+  if (e == hipSuccess) e = hipMemcpyAsync(&hc, d_ctr, sizeof hc, hipMemcpyDeviceToHost, p->stream.s);
+  if (e == hipSuccess) e = hipStreamSynchronize(p->stream.s);
+  else (void)hipStreamSynchronize(p->stream.s);
   if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
   if (e != hipSuccess) return fail(GSDF_ERR_HIP, std::string("project: ") + hipGetErrorString(e));
   p->evals += hc.evals;
@@ -1110,16 +999,12 @@ extern "C" int gsdf_hip_image2(gsdf_program* p, int w, int h, float* dist_out, u
   HIP_TRY(dc.alloc(n * 4));
   const int k = p->batch_k();
   const unsigned grid = grid_for((n + k - 1) / k, p->num_cu, 8);
-#define LAUNCH_IMG(KK) hipLaunchKernelGGL((image2_kernel<KK>), dim3(grid), dim3(BLOCK), p->lds_bytes(KK), p->stream, p->d_code, w, h, xmin, ymax, dx, dy, (float*)dd.p, (uint32_t*)dc.p)
   spec_aux(p);
-  if (p->f_image) HIP_TRY(launch_fn(p->f_image, grid, BLOCK, p->lds_bytes(k), p->stream, (const uint32_t*)p->d_code, (int)w, (int)h, xmin, ymax, dx, dy, (float*)dd.p, (uint32_t*)dc.p));
-  else
-  if (k == 4) LAUNCH_IMG(4); else if (k == 2) LAUNCH_IMG(2); else LAUNCH_IMG(1);
-#undef LAUNCH_IMG
-  HIP_TRY(hipGetLastError());
-  if (dist_out) HIP_TRY(hipMemcpyAsync(dist_out, dd.p, n * 4, hipMemcpyDeviceToHost, p->stream));
-  if (rgba_out) HIP_TRY(hipMemcpyAsync(rgba_out, dc.p, n * 4, hipMemcpyDeviceToHost, p->stream));
-  HIP_TRY(hipStreamSynchronize(p->stream));
+  HIP_TRY(launch_kernel(k == 4 ? image2_kernel<4> : (k == 2 ? image2_kernel<2> : image2_kernel<1>), p->f_image, grid, BLOCK, p->lds_bytes(k), p->stream.s, p->d_code.p, w, h, xmin, ymax,
+                        dx, dy, dd.p, dc.p));
+  if (dist_out) HIP_TRY(hipMemcpyAsync(dist_out, dd.p, n * 4, hipMemcpyDeviceToHost, p->stream.s));
+  if (rgba_out) HIP_TRY(hipMemcpyAsync(rgba_out, dc.p, n * 4, hipMemcpyDeviceToHost, p->stream.s));
+  HIP_TRY(hipStreamSynchronize(p->stream.s));
   p->evals += n;
   return GSDF_OK;
 }
@@ -1220,9 +1105,8 @@ extern "C" int gsdf_hip_render3(gsdf_program* p, const gsdf_view* view, int w, i
   HIP_TRY(d_depth.alloc(n * 4));
   HIP_TRY(d_evals.alloc(n * 4));
   HIP_TRY(d_ctr.alloc(16));
-  HIP_TRY(hipMemsetAsync(d_ctr.p, 0, 16, p->stream));
-  const char* e = getenv("GSDF_HIP_VIEW_REFILL");
-  const bool plain = !(e && atoi(e) != 0);
+  HIP_TRY(hipMemsetAsync(d_ctr.p, 0, 16, p->stream.s));
+  const bool plain = !env_flag("GSDF_HIP_VIEW_REFILL");
   const size_t lds = p->lds_bytes(1);
   // plain: one lane per claim; refilling: persistent, as many workgroups as the CUs hold at once (4 per CU: the launch bounds)
   unsigned grid = (cam.n_claims + BLOCK - 1) / BLOCK;
@@ -1234,17 +1118,14 @@ extern "C" int gsdf_hip_render3(gsdf_program* p, const gsdf_view* view, int w, i
   float* o_depth = (float*)d_depth.p;
   uint32_t* o_evals = (uint32_t*)d_evals.p;
   unsigned long long* o_ctr = (unsigned long long*)d_ctr.p;
-  const hipFunction_t fs = plain ? p->f_view_plain : p->f_view;
-  if (fs) HIP_TRY(launch_fn(fs, grid, BLOCK, lds, p->stream, (const uint32_t*)p->d_code, cam, o_rgba, o_depth, o_evals, o_ctr));
-  else if (plain) hipLaunchKernelGGL((view_kernel<false>), dim3(grid), dim3(BLOCK), lds, p->stream, p->d_code, cam, o_rgba, o_depth, o_evals, o_ctr);
-  else hipLaunchKernelGGL((view_kernel<true>), dim3(grid), dim3(BLOCK), lds, p->stream, p->d_code, cam, o_rgba, o_depth, o_evals, o_ctr);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(launch_kernel(plain ? view_kernel<false> : view_kernel<true>, plain ? p->f_view_plain : p->f_view, grid, BLOCK, lds, p->stream.s, p->d_code.p, cam, o_rgba, o_depth, o_evals,
+                        o_ctr));
   unsigned long long h_ctr[2] = {0, 0};
-  if (rgba_out) HIP_TRY(hipMemcpyAsync(rgba_out, d_rgba.p, n * 4, hipMemcpyDeviceToHost, p->stream));
-  if (depth_out) HIP_TRY(hipMemcpyAsync(depth_out, d_depth.p, n * 4, hipMemcpyDeviceToHost, p->stream));
-  if (evals_out) HIP_TRY(hipMemcpyAsync(evals_out, d_evals.p, n * 4, hipMemcpyDeviceToHost, p->stream));
-  HIP_TRY(hipMemcpyAsync(h_ctr, d_ctr.p, 16, hipMemcpyDeviceToHost, p->stream));
-  HIP_TRY(hipStreamSynchronize(p->stream));
+  if (rgba_out) HIP_TRY(hipMemcpyAsync(rgba_out, d_rgba.p, n * 4, hipMemcpyDeviceToHost, p->stream.s));
+  if (depth_out) HIP_TRY(hipMemcpyAsync(depth_out, d_depth.p, n * 4, hipMemcpyDeviceToHost, p->stream.s));
+  if (evals_out) HIP_TRY(hipMemcpyAsync(evals_out, d_evals.p, n * 4, hipMemcpyDeviceToHost, p->stream.s));
+  HIP_TRY(hipMemcpyAsync(h_ctr, d_ctr.p, 16, hipMemcpyDeviceToHost, p->stream.s));
+  HIP_TRY(hipStreamSynchronize(p->stream.s));
   p->evals += h_ctr[1];
   return GSDF_OK;
 }
@@ -1330,15 +1211,12 @@ extern "C" int gsdf_hip_image2_color(gsdf_program* p, const gsdf_color2* conv, i
   uint32_t* o_rgba = rgba_out ? (uint32_t*)dc.p : nullptr;
   const int k = p->batch_k();
   const unsigned grid = grid_for((n + k - 1) / k, p->num_cu, 8);
-  const hipFunction_t fs = p->f_imgc[conv->kind];
-  if (fs) HIP_TRY(launch_fn(fs, grid, BLOCK, p->lds_bytes(k), p->stream, (const uint32_t*)p->d_code, (int)w, (int)h, xmin, ymax, dx, dy, cv, o_dist, o_rgba));
-  else if (k == 4) hipLaunchKernelGGL((image2_color_kernel<4, -1>), dim3(grid), dim3(BLOCK), p->lds_bytes(4), p->stream, p->d_code, w, h, xmin, ymax, dx, dy, cv, o_dist, o_rgba);
-  else if (k == 2) hipLaunchKernelGGL((image2_color_kernel<2, -1>), dim3(grid), dim3(BLOCK), p->lds_bytes(2), p->stream, p->d_code, w, h, xmin, ymax, dx, dy, cv, o_dist, o_rgba);
-  else hipLaunchKernelGGL((image2_color_kernel<1, -1>), dim3(grid), dim3(BLOCK), p->lds_bytes(1), p->stream, p->d_code, w, h, xmin, ymax, dx, dy, cv, o_dist, o_rgba);
-  HIP_TRY(hipGetLastError());
-  if (dist_out) HIP_TRY(hipMemcpyAsync(dist_out, dd.p, n * 4, hipMemcpyDeviceToHost, p->stream));
-  if (rgba_out) HIP_TRY(hipMemcpyAsync(rgba_out, dc.p, n * 4, hipMemcpyDeviceToHost, p->stream));
-  HIP_TRY(hipStreamSynchronize(p->stream));
+  // (the interpreter's kernel takes the conversion kind as an argument, a per-tree one is built for its kind)
+  HIP_TRY(launch_kernel(k == 4 ? image2_color_kernel<4, -1> : (k == 2 ? image2_color_kernel<2, -1> : image2_color_kernel<1, -1>), p->f_imgc[conv->kind], grid, BLOCK, p->lds_bytes(k),
+                        p->stream.s, p->d_code.p, w, h, xmin, ymax, dx, dy, cv, o_dist, o_rgba));
+  if (dist_out) HIP_TRY(hipMemcpyAsync(dist_out, dd.p, n * 4, hipMemcpyDeviceToHost, p->stream.s));
+  if (rgba_out) HIP_TRY(hipMemcpyAsync(rgba_out, dc.p, n * 4, hipMemcpyDeviceToHost, p->stream.s));
+  HIP_TRY(hipStreamSynchronize(p->stream.s));
   p->evals += n;
   return GSDF_OK;
 }

@@ -10,6 +10,7 @@
 
 #include <atomic>
 #include <cstdint>
+#include <cstdlib>
 #include <string>
 
 #pragma GCC visibility push(default)
@@ -25,6 +26,19 @@ int fail(int code, const std::string& msg);  // sets the calling thread's gsdf_h
     hipError_t _e = (expr);                                                                             \
     if (_e != hipSuccess) return fail(GSDF_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
   } while (0)
+// the same inside a function that has a `bail(code)` to release what it holds on the way out
+#define HIP_TRYM(expr)                                                                                        \
+  do {                                                                                                        \
+    hipError_t _e = (expr);                                                                                   \
+    if (_e != hipSuccess) return bail(fail(GSDF_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e))); \
+  } while (0)
+
+// Environment knobs (tuning, developer A/B switches): a site that reads its knob once keeps the value in a `static const`.
+inline int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+inline uint64_t env_u64(const char* name, uint64_t dflt) { const char* e = getenv(name); return e ? (uint64_t)strtoull(e, nullptr, 10) : dflt; }
+inline bool env_flag(const char* name) { const char* e = getenv(name); return e && atoi(e) != 0; }      // off unless set to non-zero
+inline bool env_flag_on(const char* name) { const char* e = getenv(name); return !e || atoi(e) != 0; }  // on unless set to 0
+inline bool env_set(const char* name) { return getenv(name) != nullptr; }
 
 struct gsdf_mesh {
   int device = 0;

@@ -137,7 +137,7 @@ using TableRun = TableRunOf<TableCounters>;
 template <typename Head, typename Pass>
 int table_build(const char* what, const char* floor_env, uint64_t want, size_t cell_bytes, int dev, hipStream_t s, PoolBuf& table, const void* d_head,
                 Pass pass, TableRunOf<Head>* run) {
-  if (const char* e = getenv(floor_env)) want = (uint64_t)strtoull(e, nullptr, 10);
+  want = env_u64(floor_env, want);  // (developer knob: a floor for the table, so that tests reach the regrowth)
   for (uint64_t cells = 1024;; cells <<= 1) {
     if (cells < want) continue;
     if (cells > ((uint64_t)1 << 32)) return fail(GSDF_ERR_CAPACITY, std::string(what) + ": hash table capacity exceeded");
@@ -672,12 +672,12 @@ extern "C" int gsdf_hip_indexed_simplify(gsdf_indexed* ix, const gsdf_simplify_o
   PoolBuf ctr, used, vcell, table, keep, fcell, blk_cnt, blk_base, total, cpos, first, vnum;
   if (!ctr.take(dev, sizeof(SimplifyCounters)) || !used.take(dev, V * 4) || !vcell.take(dev, V * 4)) return fail(GSDF_ERR_HIP, nomem);
   SimplifyCounters* d_ctr = ctr.as<SimplifyCounters>();
-  EventPair ev_c, ev_f;
-  if (!ev_c.make() || !ev_f.make()) return fail(GSDF_ERR_HIP, "hipEventCreate failed");
+  EventPair ev_cells, ev_f;
+  if (!ev_cells.make() || !ev_f.make()) return fail(GSDF_ERR_HIP, "hipEventCreate failed");
   // 1. used vertices, the exponent, and the cluster table: per cell the key (8 bytes), the label (4), the record (32), the flag (4);
   // cells from 2 V: the number of used vertices is known on the device only at this point, V bounds it (and so the clusters) from
   // above, and asking for 2 V instead of 2 x used saves the round trip that would fetch it
-  HIP_TRY(hipEventRecord(ev_c.a, s));
+  HIP_TRY(hipEventRecord(ev_cells.a, s));
   HIP_TRY(hipMemsetAsync(d_ctr, 0, sizeof(SimplifyCounters), s));
   HIP_TRY(hipMemsetAsync(used.p, 0, V * 4, s));
   LAUNCH(simplify_mark_kernel, nb_f, BLOCK, s, ix->idx.as<unsigned>(), (unsigned long long)F, used.as<unsigned>(), &d_ctr->head);
@@ -708,7 +708,7 @@ extern "C" int gsdf_hip_indexed_simplify(gsdf_indexed* ix, const gsdf_simplify_o
   const int biased = (int)(hd.maxbits >> 23);
   const int e = (biased > 1 ? biased : 1) - 126;
   LAUNCH(simplify_sum_kernel, nb_v, BLOCK, s, ix->verts.p, vcell.as<unsigned>(), (unsigned long long)V, std::ldexp(1.0, 30 - e), tab_acc(cells));
-  HIP_TRY(hipEventRecord(ev_c.b, s));
+  HIP_TRY(hipEventRecord(ev_cells.b, s));
   // 2. faces; the cells' positions. (The new handle's stream is made before the events: it is host work.)
   IndexedPtr nx;
   if (!dry)
@@ -752,7 +752,7 @@ extern "C" int gsdf_hip_indexed_simplify(gsdf_indexed* ix, const gsdf_simplify_o
   gsdf_simplify_stats r{};
   r.n_verts_in = V; r.n_tris_in = F; r.used_verts_in = hd.used; r.degenerate_in = hd.degenerate; r.cells = hd.tab.distinct; r.collapsed = n_collapsed;
   r.n_verts = tl.named; r.n_tris = F2; r.largest_cell = tl.largest; r.exponent = e;
-  r.ms_cells = ev_c.ms(); r.ms_faces = ev_f.ms();
+  r.ms_cells = ev_cells.ms(); r.ms_faces = ev_f.ms();
   r.probes = hd.tab.probes; r.table_cells = cells; r.attempts = run.attempts;
   if (st) *st = r;
   if (!dry) {
@@ -788,12 +788,12 @@ extern "C" int gsdf_hip_indexed_simplify_adaptive(gsdf_indexed* ix, const gsdf_a
   if (!ctr.take(dev, sizeof(AdaptiveCounters)) || !used.take(dev, V * 4) || !vcell.take(dev, (size_t)levels * V * 4) || !vchoice.take(dev, V * 4))
     return fail(GSDF_ERR_HIP, nomem);
   AdaptiveCounters* d_ctr = ctr.as<AdaptiveCounters>();
-  EventPair ev_c, ev_e, ev_f;
-  if (!ev_c.make() || !ev_e.make() || !ev_f.make()) return fail(GSDF_ERR_HIP, "hipEventCreate failed");
+  EventPair ev_cells, ev_e, ev_f;
+  if (!ev_cells.make() || !ev_e.make() || !ev_f.make()) return fail(GSDF_ERR_HIP, "hipEventCreate failed");
   // 1. used vertices, the exponent, and ONE table for the cells of all levels: per cell the key (8 bytes), the label (4), the record
   // (32), the error (8). A surface has about a quarter of a level's cells at the next one, so 3 V cells ask for a load below 0.5
   // in nearly every case; where they do not, the table grows as every table here does.
-  HIP_TRY(hipEventRecord(ev_c.a, s));
+  HIP_TRY(hipEventRecord(ev_cells.a, s));
   HIP_TRY(hipMemsetAsync(d_ctr, 0, sizeof(AdaptiveCounters), s));
   HIP_TRY(hipMemsetAsync(used.p, 0, V * 4, s));
   LAUNCH(simplify_mark_kernel, nb_f, BLOCK, s, ix->idx.as<unsigned>(), (unsigned long long)F, used.as<unsigned>(), &d_ctr->head);
@@ -828,7 +828,7 @@ extern "C" int gsdf_hip_indexed_simplify_adaptive(gsdf_indexed* ix, const gsdf_a
   LAUNCH(adaptive_sum_kernel, nb_v, BLOCK, s, ix->verts.p, vcell.as<unsigned>(), (unsigned long long)V, levels, std::ldexp(1.0, 30 - e), tab_acc(cells));
   LAUNCH(adaptive_place_kernel, grid_for(cells, ix->num_cu, 8), BLOCK, s, tab_key(cells), tab_label(cells), tab_acc(cells), (unsigned long long)cells, ix->verts.p,
          std::ldexp(1.0, e - 30), cpos.p);
-  HIP_TRY(hipEventRecord(ev_c.b, s));
+  HIP_TRY(hipEventRecord(ev_cells.b, s));
   // 2. the cells' errors, and every vertex's choice
   HIP_TRY(hipEventRecord(ev_e.a, s));
   LAUNCH(adaptive_error_kernel, nb_f, BLOCK, s, ix->verts.p, ix->idx.as<unsigned>(), (unsigned long long)F, vcell.as<unsigned>(), (unsigned long long)V, levels,
@@ -886,7 +886,7 @@ extern "C" int gsdf_hip_indexed_simplify_adaptive(gsdf_indexed* ix, const gsdf_a
   r.n_verts = tl.named; r.n_tris = F2; r.largest_cluster = tl.largest;
   std::memcpy(&r.max_err, &tl.max_err, 8);
   r.exponent = e;
-  r.ms_cells = ev_c.ms(); r.ms_error = ev_e.ms(); r.ms_faces = ev_f.ms();
+  r.ms_cells = ev_cells.ms(); r.ms_error = ev_e.ms(); r.ms_faces = ev_f.ms();
   r.probes = hd.tab.probes; r.table_cells = cells; r.attempts = run.attempts;
   if (st) *st = r;
   if (!dry) {

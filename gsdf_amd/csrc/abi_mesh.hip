@@ -30,14 +30,59 @@
 // workspace arenas are reused in stream order and only the pinned counter block and the timing events exist twice.
 namespace {
 constexpr size_t kCtrBytes = (sizeof(MeshCounters) + 255) & ~(size_t)255;  // the group sums follow the counters: one memset clears both
-const bool ctr_from_kernel = [] { const char* e = getenv("GSDF_HIP_CTR_FROM_KERNEL"); return !e || atoi(e) != 0; }();  // developer knobs (A/B timing)
-}  // namespace
+const bool ctr_from_kernel = env_flag_on("GSDF_HIP_CTR_FROM_KERNEL");  // developer knobs (A/B timing)
 
-#define HIP_TRYM(expr)                                                                                   \
-  do {                                                                                                   \
-    hipError_t _e = (expr);                                                                              \
-    if (_e != hipSuccess) return fail(GSDF_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
+// The ahead-of-time kernel of a variant: exactly the instantiations this library launches, null for every other. (A per-tree
+// build has the same parameters whatever its template arguments: launch_kernel takes their types from these.) The kernels come
+// out in the code object in the order they are first named here.
+using leaf_kernel_t = decltype(&leaf_kernel<4, 3>);
+using leaf_eval_kernel_t = decltype(&leaf_eval_kernel<4, 3>);
+using leaf_dense_kernel_t = decltype(&leaf_dense_kernel<3, true, false>);
+using dc_origin_kernel_t = decltype(&dc_origin_kernel<4, 3>);
+using flat_grid_kernel_t = decltype(&flat_grid_kernel<4, 4>);
+leaf_dense_kernel_t leaf_dense_aot(int w) {  // passes of four points per lane, scratch-free occupancies only
+  if (w == 3) return leaf_dense_kernel<3, true, false>;
+  if (w == 2) return leaf_dense_kernel<2, true, false>;
+  return nullptr;
+}
+leaf_eval_kernel_t leaf_eval_aot(const LeafVariant& v) {  // (K, W): gsdf_program::leaf_aot_waves
+  struct Row { int k, w; bool ucube, ntlds, dz; leaf_eval_kernel_t f; };
+  static const Row rows[] = {
+      // distinct z rows: column bricks at four points per lane
+      {4, 2, true, true, true, leaf_eval_kernel<4, 2, true, true, false, true>},   {4, 3, true, true, true, leaf_eval_kernel<4, 3, true, true, false, true>},
+      {4, 2, true, false, true, leaf_eval_kernel<4, 2, true, false, false, true>}, {4, 3, true, false, true, leaf_eval_kernel<4, 3, true, false, false, true>},
+      // a few leaves per pass | a level-3 cube per pass with its case-count table in LDS | in global memory
+      {4, 2, false, true, false, leaf_eval_kernel<4, 2, false, true>}, {4, 2, true, true, false, leaf_eval_kernel<4, 2, true, true>}, {4, 2, true, false, false, leaf_eval_kernel<4, 2, true, false>},
+      {4, 3, false, true, false, leaf_eval_kernel<4, 3, false, true>}, {4, 3, true, true, false, leaf_eval_kernel<4, 3, true, true>}, {4, 3, true, false, false, leaf_eval_kernel<4, 3, true, false>},
+      {2, 3, false, true, false, leaf_eval_kernel<2, 3, false, true>}, {2, 3, true, true, false, leaf_eval_kernel<2, 3, true, true>}, {2, 3, true, false, false, leaf_eval_kernel<2, 3, true, false>},
+      {1, 4, false, true, false, leaf_eval_kernel<1, 4, false, true>}, {1, 4, true, true, false, leaf_eval_kernel<1, 4, true, true>}, {1, 4, true, false, false, leaf_eval_kernel<1, 4, true, false>},
+  };
+  if (v.fused || v.both) return nullptr;
+  for (const Row& r : rows)
+    if (r.k == v.k && r.w == v.w && r.ucube == v.ucube && r.ntlds == v.ntlds && r.dz == v.dz) return r.f;
+  return nullptr;
+}
+constexpr auto leaf_brick_aot = leaf_brick_kernel<4, 2>;  // fused leaf phase, share_corners = 1: one wave per level-3 brick
+leaf_kernel_t leaf_fused_aot(const LeafVariant& v) {
+  if (!v.fused) return nullptr;
+  if (v.k == 4 && v.w == 2) return leaf_kernel<4, 2>;
+  if (v.k == 4 && v.w == 3) return leaf_kernel<4, 3>;
+  if (v.k == 2 && v.w == 3) return leaf_kernel<2, 3>;
+  if (v.k == 1 && v.w == 4) return leaf_kernel<1, 4>;
+  return nullptr;
+}
+dc_origin_kernel_t dc_origin_aot(SweepVariant v) {  // (gsdf_program::dc_origin_variant)
+  if (v.k == 4 && v.w == 3) return dc_origin_kernel<4, 3>;  // <4, 4> needs scratch: not built (see fn_scratch_bytes)
+  if (v.k == 2 && v.w == 3) return dc_origin_kernel<2, 3>;  // (<2, 4> sits at its register budget: with the block verdicts' pointer it spills four VGPRs, and a kernel with scratch is not shipped)
+  if (v.k == 1 && v.w == 4) return dc_origin_kernel<1, 4>;
+  return nullptr;
+}
+flat_grid_kernel_t flat_grid_aot(SweepVariant v) {  // (gsdf_program::sweep_variant)
+  if (v.k == 4) return v.w == 4 ? flat_grid_kernel<4, 4> : flat_grid_kernel<4, 3>;
+  if (v.k == 2) return v.w == 4 ? flat_grid_kernel<2, 4> : flat_grid_kernel<2, 3>;
+  return flat_grid_kernel<1, 4>;
+}
+}  // namespace
 
 struct gsdf_mesh_job {
   gsdf_program* p = nullptr;
@@ -45,7 +90,7 @@ struct gsdf_mesh_job {
   gsdf_mesh_opts opts{};
   float res = 0, ox = 0, oy = 0, oz = 0;
   hipStream_t s = nullptr;
-  int levels = 0, lq = 0, ls = 0, prune_cols = 0, pmask = 0, ptest = 0, lk = 0, lw = 0;
+  int levels = 0, lq = 0, ls = 0, prune_cols = 0, pmask = 0, ptest = 0, lk = 0;
   size_t lds_prune = 0, lds_m = 0;
   bool want_recs = false;
   uint64_t qcap = 0, want = 0, want_rec_n = 0;  // capacities of the next attempt
@@ -53,303 +98,250 @@ struct gsdf_mesh_job {
   int attempt = 0, slot;
   bool used_brick = false, two_kernel = false, ctr_on_host = false, used_dz = false, used_dense = false;
   int chain_first = 0;  // levels <= chain_first were tested by prune_kernel (one launch per level), the ones above speculatively
-  uint64_t nblk = 0;
+  uint64_t nblk = 0, nblk_q = 0, lbound = 0;  // 64-leaf blocks the record arena holds / the queue capacity allows for; leaves the latter bounds
   size_t clear_bytes = 0;
+  bool want_two = false, masks_valid = false;
+  Cube* q[2] = {nullptr, nullptr};  // the cube queues by level parity, and their capacities
+  uint64_t capq[2] = {0, 0};
   MeshCounters* d_ctr = nullptr;
   MeshCounters* hcp = nullptr;  // this job's pinned counter block
-  hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr, evr = nullptr, ev_done = nullptr;
-  // this job's workspace: the handle has two, so that two chains in flight do not share one (they run on two streams, the
+  hipEvent_t ev_done = nullptr;
+  // this job's workspace: the handle has three, so that chains in flight do not share one (they run on streams of their own, the
   // latency-bound top and tail of one under the leaf kernel of the other)
-  struct Ws { gsdf_program::Arena &q0, &q1, &ctr, &spec_pass, &rec, &hdr, &grp; };
-  Ws w;
-  explicit gsdf_mesh_job(gsdf_program* pp, int sl)
-      : p(pp), slot(sl), w(sl == 0 ? Ws{pp->q0, pp->q1, pp->ctr, pp->spec_pass, pp->rec, pp->hdr, pp->grp}
-                           : sl == 1 ? Ws{pp->b_q0, pp->b_q1, pp->b_ctr, pp->b_spec_pass, pp->b_rec, pp->b_hdr, pp->b_grp}
-                                     : Ws{pp->c_q0, pp->c_q1, pp->c_ctr, pp->c_spec_pass, pp->c_rec, pp->c_hdr, pp->c_grp}) {}
+  gsdf_program::OctreeWs& w;
+  explicit gsdf_mesh_job(gsdf_program* pp, int sl) : p(pp), slot(sl), w(pp->ws[sl]) {}
 
   int enqueue();            // one attempt: the whole chain onto the stream, nothing waited for
+  int prepare_outputs();    //   its stages: outputs and capacities,
+  int enqueue_descent();    //   the speculative top and the per-level chain,
+  int enqueue_leaf();       //   the leaf phase,
+  int enqueue_handover();   //   the counters' way to the host
   int finish(bool* again);  // waits for it; *again: a capacity was short -- enqueue() once more (nothing was dropped silently)
   int stats();              // the mesh's statistics from the counters
 };
 
 int gsdf_mesh_job::enqueue() {
-    ctr_on_host = false;
-    used_dz = false;
-    used_dense = false;
-    MeshCounters& hc = *hcp;
-    (void)hc;
-    HIP_TRYM(w.q0.ensure(qcap * sizeof(Cube)));
-    HIP_TRYM(w.q1.ensure(qcap * sizeof(Cube)));
-    const uint64_t cap0 = w.q0.cap / sizeof(Cube), cap1 = w.q1.cap / sizeof(Cube);
-    gsdf_program::Arena* q[2] = {&w.q0, &w.q1};
-    const uint64_t capq[2] = {cap0, cap1};
-    // records payload: room for the packed records instead (sized like the triangles: previous mesh, else a guess + one exact rerun)
-    if (want_recs && !m->d_recs) {
-      const uint64_t nrec = want_rec_n ? want_rec_n : (p->last_recs ? p->last_recs + p->last_recs / 16 + 1024 : (uint64_t)1 << 20);
-      const uint64_t units = (dense_bytes(nrec) + 35) / 36;
-      m->d_recs = (uint8_t*)pool_take(p->device, units, &m->recs_cap36);
-      if (!m->d_recs) { HIP_TRYM(hipMalloc((void**)&m->d_recs, units * 36)); m->recs_cap36 = units; }
-    }
-    // triangle buffer: caller's size, else a pooled buffer, else a guess that is corrected by one exact rerun
-    if (!want_recs && !m->d_tris) {
-      uint64_t need = want ? want : (p->last_tris ? p->last_tris + p->last_tris / 16 + 1024 : (uint64_t)1 << 20);
-      if (opts.host_output) {
-        // triangles straight into pinned host memory: the stage flushes of leaf_kernel are 4.6 KB coalesced bursts,
-        // which PCIe takes well; the transfer then overlaps the kernel instead of following it
-        void* hb = nullptr;
-        size_t hcap = 0;
-        if (int rc = host_buf(&hb, &hcap, (size_t)need * 36)) return rc;
-        m->d_tris = (float*)hb;
-        m->cap = hcap / 36;
-        m->host_out = true;
-      } else {
-        m->d_tris = pool_take(p->device, need, &m->cap);
-        if (!m->d_tris) {
-          HIP_TRYM(hipMalloc((void**)&m->d_tris, need * 36));
-          m->cap = need;
-        }
+  ctr_on_host = false;
+  used_dz = false;
+  used_dense = false;
+  if (int rc = prepare_outputs()) return rc;
+  if (int rc = enqueue_descent()) return rc;  // (ev[0] .. ev[1])
+  if (int rc = enqueue_leaf()) return rc;
+  HIP_TRY(hipEventRecord(w.ev[2], s));
+  return enqueue_handover();
+}
+
+int gsdf_mesh_job::prepare_outputs() {
+  HIP_TRY(w.q0.ensure(qcap * sizeof(Cube)));
+  HIP_TRY(w.q1.ensure(qcap * sizeof(Cube)));
+  q[0] = (Cube*)w.q0.p; q[1] = (Cube*)w.q1.p;
+  capq[0] = w.q0.cap / sizeof(Cube); capq[1] = w.q1.cap / sizeof(Cube);
+  // records payload: room for the packed records instead (sized like the triangles: previous mesh, else a guess + one exact rerun)
+  if (want_recs && !m->d_recs) {
+    const uint64_t nrec = want_rec_n ? want_rec_n : (p->last_recs ? p->last_recs + p->last_recs / 16 + 1024 : (uint64_t)1 << 20);
+    const uint64_t units = (dense_bytes(nrec) + 35) / 36;
+    m->d_recs = (uint8_t*)pool_take(p->device, units, &m->recs_cap36);
+    if (!m->d_recs) { HIP_TRY(hipMalloc((void**)&m->d_recs, units * 36)); m->recs_cap36 = units; }
+  }
+  // triangle buffer: caller's size, else a pooled buffer, else a guess that is corrected by one exact rerun
+  if (!want_recs && !m->d_tris) {
+    uint64_t need = want ? want : (p->last_tris ? p->last_tris + p->last_tris / 16 + 1024 : (uint64_t)1 << 20);
+    if (opts.host_output) {
+      // triangles straight into pinned host memory: the stage flushes of leaf_kernel are 4.6 KB coalesced bursts,
+      // which PCIe takes well; the transfer then overlaps the kernel instead of following it
+      void* hb = nullptr;
+      size_t hcap = 0;
+      if (int rc = host_buf(&hb, &hcap, (size_t)need * 36)) return rc;
+      m->d_tris = (float*)hb;
+      m->cap = hcap / 36;
+      m->host_out = true;
+    } else {
+      m->d_tris = pool_take(p->device, need, &m->cap);
+      if (!m->d_tris) {
+        HIP_TRY(hipMalloc((void**)&m->d_tris, need * 36));
+        m->cap = need;
       }
     }
-    // 64-leaf blocks the queue capacity allows for, and their groups (two-kernel leaf phase)
-    uint64_t lbound = capq[lq & 1] << (3 * (lq - 1));
-    {
-      const uint64_t full = (levels - lq) * 3 >= 40 ? UINT64_MAX : ((uint64_t)1 << (3 * (levels - 1)));
-      if (lbound > full) lbound = full;
+  }
+  // 64-leaf blocks the queue capacity allows for, and their groups (two-kernel leaf phase)
+  lbound = capq[lq & 1] << (3 * (lq - 1));
+  {
+    const uint64_t full = (levels - lq) * 3 >= 40 ? UINT64_MAX : ((uint64_t)1 << (3 * (levels - 1)));
+    if (lbound > full) lbound = full;
+  }
+  // The record arena (2 560 B per block) is sized for the blocks a mesh of this handle actually had (+ 1/8), not for the queue
+  // capacity: a million-cube queue would ask for 2.7 GB, and each queue regrowth for four times more. First mesh: 384 K
+  // blocks (1 GB); a mesh that needs more says so through its survivor count and is repeated once with the exact size.
+  constexpr uint64_t kRecBlocks0 = (uint64_t)384 << 10;
+  nblk_q = (lbound + 63) / 64;
+  nblk = p->rec_blocks ? p->rec_blocks : kRecBlocks0;
+  if (nblk > nblk_q) nblk = nblk_q;
+  const uint64_t ngrp = (nblk + MARCH_GROUP - 1) / MARCH_GROUP;
+  want_two = !fused_leaf();
+  if (want_two && (w.hdr.ensure(nblk * sizeof(uint32_t)) != hipSuccess || w.rec.ensure(nblk * (size_t)REC_BLOCK * sizeof(uint32_t)) != hipSuccess)) {
+    (void)hipGetLastError();  // no room for the records: the fused kernel needs none
+    w.hdr.release(); w.rec.release();
+    want_two = false;
+  }
+  if (want_recs && (!want_two || w.grp.ensure(ngrp * sizeof(unsigned long long)) != hipSuccess)) {
+    (void)hipGetLastError();
+    return (fail(GSDF_ERR_CAPACITY, "no device memory for the cut-leaf record arena (payload = records needs it)"));
+  }
+  clear_bytes = kCtrBytes + (want_two ? ngrp * sizeof(unsigned long long) : 0);
+  HIP_TRY(w.ctr.ensure(clear_bytes));
+  d_ctr = (MeshCounters*)w.ctr.p;
+  // Brick masks (dev_ops.h: D_SKIP): valid when the last level of cubes, which the leaf kernels continue from, is a level-3 brick
+  // that was centre-tested by interval evaluation -- that test leaves, in every surviving cube's w field, which operand
+  // subtrees of the program cannot matter anywhere in the cube. GSDF_HIP_NO_BRICK_MASKS=1: no numbers in the program at all.
+  masks_valid = lq == 3 && ptest == 1 && p->prog.n_skip_ids > 0 && (pmask == 1 || (pmask > 1 && ((pmask >> lq) & 1)));
+  return GSDF_OK;
+}
+
+int gsdf_mesh_job::enqueue_descent() {
+  // the counters and the group sums are cleared by the chain's first kernel (prune_spec_kernel); one launch per level: a memset
+  static const bool use_spec = env_flag_on("GSDF_HIP_PRUNE_SPEC");
+  if (!use_spec) HIP_TRY(hipMemsetAsync(d_ctr, 0, clear_bytes, s));
+  HIP_TRY(hipEventRecord(w.ev[0], s));
+  static const int prune_bpc = env_int("GSDF_HIP_PRUNE_BPC", 2);  // tuning knob: 2 workgroups per CU (round 4: 4 -> 2 is -3 us on a blocking mesh and leaves the CUs to the other mesh in flight: 0.503 -> 0.486 ms per mesh, two in flight)
+  // The first S levels (at most 7: 299,593 cubes) are centre-tested speculatively, every cube of the complete octree at once,
+  // and resolved by a second launch (kernels.h: prune_spec_kernel / prune_resolve_kernel): two launches instead of a chain of
+  // S dependent ones. GSDF_HIP_PRUNE_SPEC=0 keeps one launch per level (cross-check in the tests).
+  int first_level = levels;  // first level of the per-level chain
+  chain_first = levels;
+  unsigned* spec_part = nullptr;  // statistics rows of the speculative top, for the first per-level launch to add up
+  unsigned spec_rows = 0, spec_mask = 0;
+  int spec_top_S = 0;
+  const unsigned test_mask = pmask == 1 ? 0xffffffffu : (unsigned)pmask;
+  if (use_spec) {
+    const int S = levels - lq + 1 < 7 ? levels - lq + 1 : 7;
+    const int last_spec = levels - (S - 1);
+    unsigned n_spec = 0;
+    for (int j = 0; j < S; j++) n_spec += 1u << (3 * j);
+    // the resolve stage's statistics: a row of 16 counts per workgroup behind the pass bytes, added up by the first per-level
+    // launch -- if there is one (else the resolve stage issues its atomics itself)
+    const unsigned rrows = (n_spec + SPEC_STAGE - 1) / SPEC_STAGE;
+    const size_t part_off = ((size_t)n_spec + 63) & ~(size_t)63;
+    // brick masks of the block's last level, when that is the level the leaf kernels continue from (meshes of up to nine levels):
+    // two bytes per cube of that level, behind the statistics rows
+    const unsigned n_last = 1u << (3 * (S - 1));
+    const size_t mask_off_b = (part_off + (size_t)rrows * 16 * sizeof(unsigned) + 63) & ~(size_t)63;
+    const bool spec_masks = masks_valid && last_spec == lq;
+    HIP_TRY(w.spec_pass.ensure(mask_off_b + (spec_masks ? (size_t)n_last * sizeof(uint16_t) : 0)));
+    uint16_t* d_mask16 = spec_masks ? (uint16_t*)((char*)w.spec_pass.p + mask_off_b) : nullptr;
+    const bool chain_follows = last_spec - 1 >= lq;
+    spec_part = chain_follows ? (unsigned*)((char*)w.spec_pass.p + part_off) : nullptr;
+    spec_rows = rrows;
+    spec_top_S = levels | (S << 8);
+    spec_mask = test_mask;
+    const int shard_level = opts.shard_count > 1 ? ls : -1;
+    HIP_TRY(launch_kernel(prune_spec_kernel, p->f_prune_spec, grid_for(n_spec, p->num_cu, 8), BLOCK, lds_prune, s, p->d_code.p, levels, n_spec, prune_cols, p->prog.nslots, ox, oy,
+                          oz, res, test_mask, ptest, shard_level, opts.shard_rank, opts.shard_count, w.spec_pass.p, (unsigned*)d_ctr, clear_bytes / 4, d_mask16, n_spec - n_last));
+    hipLaunchKernelGGL(prune_resolve_kernel, dim3((n_spec + SPEC_STAGE - 1) / SPEC_STAGE), dim3(BLOCK), 0, s, (const uint8_t*)w.spec_pass.p, levels, S,
+                       n_spec, test_mask, q[last_spec & 1], (unsigned long long)capq[last_spec & 1], d_ctr, spec_part,
+                       (const uint16_t*)d_mask16);
+    HIP_TRY(hipGetLastError());
+    first_level = last_spec - 1;
+    chain_first = first_level;
+  }
+  for (int level = first_level; level >= lq; level--) {
+    const int expand = level != levels;
+    const int do_test = (level >= 3 && (pmask == 1 || (pmask > 1 && ((pmask >> level) & 1)))) ? ptest : 0;
+    // upper bound of candidates at this level (for the grid only): 8^(levels-level), capped by the queue
+    uint64_t bound = (levels - level) * 3 >= 40 ? UINT64_MAX : ((uint64_t)1 << (3 * (levels - level)));
+    if (bound > capq[(level + 1) & 1] * 8) bound = capq[(level + 1) & 1] * 8;
+    HIP_TRY(launch_kernel(prune_kernel, p->f_prune, grid_for(bound, p->num_cu, prune_bpc), BLOCK, lds_prune, s, p->d_code.p, q[(level + 1) & 1], capq[(level + 1) & 1], expand, level,
+                          prune_cols, p->prog.nslots, ox, oy, oz, res, do_test, q[level & 1], capq[level & 1], (opts.shard_count > 1 && level == ls) ? 1 : 0, opts.shard_rank,
+                          opts.shard_count, d_ctr, level == first_level ? spec_part : nullptr, spec_rows, spec_top_S, spec_mask));
+  }
+  HIP_TRY(hipEventRecord(w.ev[1], s));
+  return GSDF_OK;
+}
+
+int gsdf_mesh_job::enqueue_leaf() {
+  const uint64_t bound = lbound;
+  const unsigned long long tcap = opts.max_tris ? opts.max_tris : m->cap;
+  static const int leaf_bpc = env_int("GSDF_HIP_LEAF_BPC", 32);  // (round 4: 32 -- the same for one mesh at a time, 0.503 -> 0.475 ms per mesh with two in flight: the other chain's small kernels are dispatched sooner behind a shorter queue of workgroups; the sentence that follows describes the round-3 sweep)  // grid = up to 64 workgroups per CU (4 resident): a few grid-stride iterations each, so the CUs drain evenly at the end (8 per CU: +8 % kernel time; one iteration per workgroup: +10 %)
+  const unsigned grid = grid_for(bound, p->num_cu, leaf_bpc);
+  const Cube* cubes = q[lq & 1];
+  const uint64_t ncubes = capq[lq & 1];
+  if (!want_two) {
+    if (lq == 3 && lk == 4 && opts.share_corners == 1) {
+      // exact corner sharing: one wave per level-3 brick
+      const size_t lds_b = (size_t)(p->prog.nslots * 4) * BLOCK * sizeof(float) + 4096 + TRI_STAGE * 36 + 32 + 4 * 512 * 4 + 4 * 24 * 4;
+      hipLaunchKernelGGL(leaf_brick_aot, dim3(grid_for(ncubes * 64 < bound ? ncubes * 64 : bound, p->num_cu, 8)), dim3(BLOCK), lds_b, s, p->d_code.p, cubes,
+                         (unsigned long long)ncubes, p->prog.nslots, ox, oy, oz, res, m->d_tris, tcap, d_ctr);
+      used_brick = true;
+      HIP_TRY(hipGetLastError());
+    } else {
+      const LeafPick pick = p->leaf_pick(lq);
+      HIP_TRY(launch_kernel(leaf_fused_aot(pick.v), pick.f, grid, BLOCK, lds_m, s, p->d_code.p, cubes, ncubes, lq, p->prog.nslots, ox, oy, oz, res, m->d_tris, tcap, d_ctr));
     }
-    // The record arena (2 560 B per block) is sized for the blocks a mesh of this handle actually had (+ 1/8), not for the queue
-    // capacity: a million-cube queue would ask for 2.7 GB, and each queue regrowth for four times more. First mesh: 384 K
-    // blocks (1 GB); a mesh that needs more says so through its survivor count and is repeated once with the exact size.
-    constexpr uint64_t kRecBlocks0 = (uint64_t)384 << 10;
-    const uint64_t nblk_q = (lbound + 63) / 64;
-    nblk = p->rec_blocks ? p->rec_blocks : kRecBlocks0;
-    if (nblk > nblk_q) nblk = nblk_q;
-    const uint64_t ngrp = (nblk + MARCH_GROUP - 1) / MARCH_GROUP;
-    bool want_two = !fused_leaf();
-    if (want_two && (w.hdr.ensure(nblk * sizeof(uint32_t)) != hipSuccess || w.rec.ensure(nblk * (size_t)REC_BLOCK * sizeof(uint32_t)) != hipSuccess)) {
-      (void)hipGetLastError();  // no room for the records: the fused kernel needs none
-      w.hdr.release(); w.rec.release();
-      want_two = false;
-    }
-    if (want_recs && (!want_two || w.grp.ensure(ngrp * sizeof(unsigned long long)) != hipSuccess)) {
-      (void)hipGetLastError();
-      return (fail(GSDF_ERR_CAPACITY, "no device memory for the cut-leaf record arena (payload = records needs it)"));
-    }
-    clear_bytes = kCtrBytes + (want_two ? ngrp * sizeof(unsigned long long) : 0);
-    HIP_TRYM(w.ctr.ensure(clear_bytes));
-    d_ctr = (MeshCounters*)w.ctr.p;
-    // the counters and the group sums are cleared by the chain's first kernel (prune_spec_kernel); one launch per level: a memset
-    static const bool use_spec = [] { const char* e = getenv("GSDF_HIP_PRUNE_SPEC"); return !e || atoi(e) != 0; }();
-    if (!use_spec) HIP_TRYM(hipMemsetAsync(d_ctr, 0, clear_bytes, s));
-    HIP_TRYM(hipEventRecord(ev0, s));
-    static const int prune_bpc = [] { const char* e = getenv("GSDF_HIP_PRUNE_BPC"); return e ? atoi(e) : 2; }();  // tuning knob: 2 workgroups per CU (round 4: 4 -> 2 is -3 us on a blocking mesh and leaves the CUs to the other mesh in flight: 0.503 -> 0.486 ms per mesh, two in flight)
-    // The first S levels (at most 7: 299,593 cubes) are centre-tested speculatively, every cube of the complete octree at once,
-    // and resolved by a second launch (kernels.h: prune_spec_kernel / prune_resolve_kernel): two launches instead of a chain of
-    // S dependent ones. GSDF_HIP_PRUNE_SPEC=0 keeps one launch per level (cross-check in the tests).
-    int first_level = levels;  // first level of the per-level chain
-    chain_first = levels;
-    // Brick masks (dev_ops.h: D_SKIP): valid when the last level of cubes, which the leaf kernels continue from, is a level-3 brick
-    // that was centre-tested by interval evaluation -- that test leaves, in every surviving cube's w field, which operand
-    // subtrees of the program cannot matter anywhere in the cube. GSDF_HIP_NO_BRICK_MASKS=1: no numbers in the program at all.
-    const bool masks_valid = lq == 3 && ptest == 1 && p->prog.n_skip_ids > 0 && (pmask == 1 || (pmask > 1 && ((pmask >> lq) & 1)));
-    unsigned* spec_part = nullptr;  // statistics rows of the speculative top, for the first per-level launch to add up
-    unsigned spec_rows = 0, spec_mask = 0;
-    int spec_top_S = 0;
-    auto test_mask_of = [](int pm) { return pm == 1 ? 0xffffffffu : (unsigned)pm; };
-    if (use_spec) {
-      const int S = levels - lq + 1 < 7 ? levels - lq + 1 : 7;
-      const int last_spec = levels - (S - 1);
-      unsigned n_spec = 0;
-      for (int j = 0; j < S; j++) n_spec += 1u << (3 * j);
-      // the resolve stage's statistics: a row of 16 counts per workgroup behind the pass bytes, added up by the first per-level
-      // launch -- if there is one (else the resolve stage issues its atomics itself)
-      const unsigned rrows = (n_spec + SPEC_STAGE - 1) / SPEC_STAGE;
-      const size_t part_off = ((size_t)n_spec + 63) & ~(size_t)63;
-      // brick masks of the block's last level, when that is the level the leaf kernels continue from (meshes of up to nine levels):
-      // two bytes per cube of that level, behind the statistics rows
-      const unsigned n_last = 1u << (3 * (S - 1));
-      const size_t mask_off_b = (part_off + (size_t)rrows * 16 * sizeof(unsigned) + 63) & ~(size_t)63;
-      const bool spec_masks = masks_valid && last_spec == lq;
-      HIP_TRYM(w.spec_pass.ensure(mask_off_b + (spec_masks ? (size_t)n_last * sizeof(uint16_t) : 0)));
-      uint16_t* d_mask16 = spec_masks ? (uint16_t*)((char*)w.spec_pass.p + mask_off_b) : nullptr;
-      const bool chain_follows = last_spec - 1 >= lq;
-      spec_part = chain_follows ? (unsigned*)((char*)w.spec_pass.p + part_off) : nullptr;
-      spec_rows = rrows;
-      spec_top_S = levels | (S << 8);
-      spec_mask = test_mask_of(pmask);
-      const unsigned test_mask = test_mask_of(pmask);
-      const int shard_level = opts.shard_count > 1 ? ls : -1;
-      const unsigned sgrid = grid_for(n_spec, p->num_cu, 8);
-      if (p->f_prune_spec) {
-        HIP_TRYM(launch_fn(p->f_prune_spec, sgrid, BLOCK, lds_prune, s, (const uint32_t*)p->d_code, (int)levels, (unsigned)n_spec, (int)prune_cols,
-                           (int)p->prog.nslots, ox, oy, oz, res, (unsigned)test_mask, (int)ptest, (int)shard_level, (unsigned)opts.shard_rank,
-                           (unsigned)opts.shard_count, (uint8_t*)w.spec_pass.p, (unsigned*)d_ctr, (unsigned)(clear_bytes / 4), d_mask16,
-                           (unsigned)(n_spec - n_last)));
-      } else {
-        hipLaunchKernelGGL(prune_spec_kernel, dim3(sgrid), dim3(BLOCK), lds_prune, s, p->d_code, levels, n_spec, prune_cols, p->prog.nslots, ox, oy,
-                           oz, res, test_mask, ptest, shard_level, (unsigned)opts.shard_rank, (unsigned)opts.shard_count, (uint8_t*)w.spec_pass.p,
-                           (unsigned*)d_ctr, (unsigned)(clear_bytes / 4), d_mask16, n_spec - n_last);
-      }
-      HIP_TRYM(hipGetLastError());
-      hipLaunchKernelGGL(prune_resolve_kernel, dim3((n_spec + SPEC_STAGE - 1) / SPEC_STAGE), dim3(BLOCK), 0, s, (const uint8_t*)w.spec_pass.p, levels, S,
-                         n_spec, test_mask, (Cube*)q[last_spec & 1]->p, (unsigned long long)capq[last_spec & 1], d_ctr, spec_part,
-                         (const uint16_t*)d_mask16);
-      HIP_TRYM(hipGetLastError());
-      first_level = last_spec - 1;
-      chain_first = first_level;
-    }
-    for (int level = first_level; level >= lq; level--) {
-      const int expand = level != levels;
-      const int do_test = (level >= 3 && (pmask == 1 || (pmask > 1 && ((pmask >> level) & 1)))) ? ptest : 0;
-      // upper bound of candidates at this level (for the grid only): 8^(levels-level), capped by the queue
-      uint64_t bound = (levels - level) * 3 >= 40 ? UINT64_MAX : ((uint64_t)1 << (3 * (levels - level)));
-      if (bound > capq[(level + 1) & 1] * 8) bound = capq[(level + 1) & 1] * 8;
-      if (p->f_prune) {
-        HIP_TRYM(launch_fn(p->f_prune, grid_for(bound, p->num_cu, prune_bpc), BLOCK, lds_prune, s, (const uint32_t*)p->d_code,
-                           (const Cube*)q[(level + 1) & 1]->p, (unsigned long long)capq[(level + 1) & 1], (int)expand, (int)level,
-                           (int)prune_cols, (int)p->prog.nslots, ox, oy, oz, res, (int)do_test,
-                           (Cube*)q[level & 1]->p, (unsigned long long)capq[level & 1], (int)((opts.shard_count > 1 && level == ls) ? 1 : 0),
-                           (unsigned)opts.shard_rank, (unsigned)opts.shard_count, d_ctr, (const unsigned*)(level == first_level ? spec_part : nullptr),
-                           (unsigned)spec_rows, (int)spec_top_S, (unsigned)spec_mask));
-      } else
-      hipLaunchKernelGGL(prune_kernel, dim3(grid_for(bound, p->num_cu, prune_bpc)), dim3(BLOCK), lds_prune, s, p->d_code,
-                         (const Cube*)q[(level + 1) & 1]->p, (unsigned long long)capq[(level + 1) & 1], expand, level, prune_cols,
-                         p->prog.nslots, ox, oy, oz, res, do_test, (Cube*)q[level & 1]->p,
-                         (unsigned long long)capq[level & 1], (opts.shard_count > 1 && level == ls) ? 1 : 0,
-                         (unsigned)opts.shard_rank, (unsigned)opts.shard_count, d_ctr, (const unsigned*)(level == first_level ? spec_part : nullptr),
-                         spec_rows, spec_top_S, spec_mask);
-      HIP_TRYM(hipGetLastError());
-    }
-    HIP_TRYM(hipEventRecord(ev1, s));
-    {
-      const uint64_t bound = lbound;
-      const unsigned long long tcap = opts.max_tris ? opts.max_tris : m->cap;
-      static const int leaf_bpc = [] { const char* e = getenv("GSDF_HIP_LEAF_BPC"); return e ? atoi(e) : 32; }();  // (round 4: 32 -- the same for one mesh at a time, 0.503 -> 0.475 ms per mesh with two in flight: the other chain's small kernels are dispatched sooner behind a shorter queue of workgroups; the sentence that follows describes the round-3 sweep)  // grid = up to 64 workgroups per CU (4 resident): a few grid-stride iterations each, so the CUs drain evenly at the end (8 per CU: +8 % kernel time; one iteration per workgroup: +10 %)
-#define LAUNCH_LEAF(KK, WW)                                                                                           \
-  hipLaunchKernelGGL((leaf_kernel<KK, WW>), dim3(grid_for(bound, p->num_cu, leaf_bpc)), dim3(BLOCK), lds_m, s, p->d_code,      \
-                     (const Cube*)q[lq & 1]->p, (unsigned long long)capq[lq & 1], lq, p->prog.nslots, ox, oy, oz, res,  \
-                     m->d_tris, tcap, d_ctr)
-      if (want_two) {
-        // two kernels: evaluation + cut-leaf records, then marching cubes over the records
-        uint32_t* d_hdr = (uint32_t*)w.hdr.p;
-        uint32_t* d_rec = (uint32_t*)w.rec.p;
-        unsigned long long* d_psum = (unsigned long long*)((char*)w.ctr.p + kCtrBytes);  // cleared with the counters
-        // share_corners = 1: every bitwise-distinct lattice point of a brick once (kernels_octree.h: leaf_dense_kernel)
-        used_dense = opts.share_corners == 1 && lq == 3 && lk == 4;
-        if (used_dense) spec_leaf_dense(p);
-        // share_corners = 2: the distinct z rows of a brick once each (kernels_octree.h: DZ) -- column bricks at four points per lane
-        used_dz = opts.share_corners == 2 && lq == 3 && lk == 4;
-        if (used_dz) spec_leaf_dz(p);
-        if (used_dz && !p->f_leaf_dz && p->f_leaf && p->spec_leaf_k == lk) used_dz = false;  // no scratch-free build of it for this tree: every row, through the specialised kernel
-#define LAUNCH_LEAF_EVAL_U(KK, WW, UU, NN, LDS)                                                                                    \
-  hipLaunchKernelGGL((leaf_eval_kernel<KK, WW, UU, NN>), dim3(grid_for(bound, p->num_cu, leaf_bpc)), dim3(BLOCK), LDS, s, p->d_code, \
-                     (const Cube*)q[lq & 1]->p, (unsigned long long)capq[lq & 1], lq, p->prog.nslots, ox, oy, oz, res, d_hdr,   \
-                     d_rec, d_psum, (unsigned long long)nblk, d_ctr, (unsigned)(masks_valid ? 1u : 0u))
-        // lq == 3 (three levels or more): a wave pass is one level-3 cube (column bricks, scalar prefetched cube load), its
-        // case-count table in LDS unless that costs a workgroup per CU; else a few leaves (occupancy is no concern: table in LDS)
-#define LAUNCH_LEAF_EVAL(KK, WW)                                                             \
-  do {                                                                                       \
-    if (lq != 3) LAUNCH_LEAF_EVAL_U(KK, WW, false, true, lds_m + 256);                       \
-    else if (p->leaf_nt_in_lds()) LAUNCH_LEAF_EVAL_U(KK, WW, true, true, lds_m);             \
-    else LAUNCH_LEAF_EVAL_U(KK, WW, true, false, lds_m);                                     \
-  } while (0)
-#define LAUNCH_LEAF_EVAL_DZ(WW, NN)                                                                                                 \
-  hipLaunchKernelGGL((leaf_eval_kernel<4, WW, true, NN, false, true>), dim3(grid_for(bound, p->num_cu, leaf_bpc)), dim3(BLOCK), lds_m, s, p->d_code, \
-                     (const Cube*)q[lq & 1]->p, (unsigned long long)capq[lq & 1], lq, p->prog.nslots, ox, oy, oz, res, d_hdr,   \
-                     d_rec, d_psum, (unsigned long long)nblk, d_ctr, (unsigned)(masks_valid ? 1u : 0u))
-        if (used_dense) {
-          const size_t lds_d = p->lds_dense();
-          if (p->f_leaf_dense) {
-            HIP_TRYM(launch_fn(p->f_leaf_dense, grid_for(bound, p->num_cu, leaf_bpc), BLOCK, lds_d, s, (const uint32_t*)p->d_code, (const Cube*)q[lq & 1]->p,
-                               (unsigned long long)capq[lq & 1], (int)p->prog.nslots, ox, oy, oz, res, d_hdr, d_rec, d_psum, (unsigned long long)nblk, d_ctr, (unsigned)(masks_valid ? 1u : 0u)));
-          } else if (3 * lds_d <= (size_t)160 * 1024) {  // the interpreter's kernels: scratch-free occupancies only, passes of four points per lane
-            hipLaunchKernelGGL((leaf_dense_kernel<3, true, false>), dim3(grid_for(bound, p->num_cu, leaf_bpc)), dim3(BLOCK), lds_d, s, p->d_code, (const Cube*)q[lq & 1]->p,
-                               (unsigned long long)capq[lq & 1], p->prog.nslots, ox, oy, oz, res, d_hdr, d_rec, d_psum, (unsigned long long)nblk, d_ctr, (unsigned)(masks_valid ? 1u : 0u));
-          } else {
-            hipLaunchKernelGGL((leaf_dense_kernel<2, true, false>), dim3(grid_for(bound, p->num_cu, leaf_bpc)), dim3(BLOCK), lds_d, s, p->d_code, (const Cube*)q[lq & 1]->p,
-                               (unsigned long long)capq[lq & 1], p->prog.nslots, ox, oy, oz, res, d_hdr, d_rec, d_psum, (unsigned long long)nblk, d_ctr, (unsigned)(masks_valid ? 1u : 0u));
-          }
-        } else if (used_dz && p->f_leaf_dz) {
-          HIP_TRYM(launch_fn(p->f_leaf_dz, grid_for(bound, p->num_cu, leaf_bpc), BLOCK, lds_m, s, (const uint32_t*)p->d_code, (const Cube*)q[lq & 1]->p,
-                             (unsigned long long)capq[lq & 1], (int)lq, (int)p->prog.nslots, ox, oy, oz, res, d_hdr, d_rec, d_psum,
-                             (unsigned long long)nblk, d_ctr, (unsigned)(masks_valid ? 1u : 0u)));
-        } else if (used_dz) {  // the interpreter's kernels (scratch-free occupancies only, as below)
-          if (p->leaf_nt_in_lds()) { if (lw == 2) LAUNCH_LEAF_EVAL_DZ(2, true); else LAUNCH_LEAF_EVAL_DZ(3, true); }
-          else { if (lw == 2) LAUNCH_LEAF_EVAL_DZ(2, false); else LAUNCH_LEAF_EVAL_DZ(3, false); }
-        } else if (p->f_leaf && p->spec_leaf_k == lk && lq == 3) {
-          HIP_TRYM(launch_fn(p->f_leaf, grid_for(bound, p->num_cu, leaf_bpc), BLOCK, lds_m, s, (const uint32_t*)p->d_code, (const Cube*)q[lq & 1]->p,
-                             (unsigned long long)capq[lq & 1], (int)lq, (int)p->prog.nslots, ox, oy, oz, res, d_hdr, d_rec, d_psum,
-                             (unsigned long long)nblk, d_ctr, (unsigned)(masks_valid ? 1u : 0u)));
-        } else {
-          // ahead-of-time kernels exist at the scratch-free occupancies only (tests/test_kernel_resources.py)
-          if (lk == 4) { if (lw == 2) LAUNCH_LEAF_EVAL(4, 2); else LAUNCH_LEAF_EVAL(4, 3); }
-          else if (lk == 2) LAUNCH_LEAF_EVAL(2, 3);
-          else LAUNCH_LEAF_EVAL(1, 4);
-        }
-#undef LAUNCH_LEAF_EVAL
-#undef LAUNCH_LEAF_EVAL_DZ
-#undef LAUNCH_LEAF_EVAL_U
-        HIP_TRYM(hipGetLastError());
-        HIP_TRYM(hipEventRecord(ev3, s));
-        two_kernel = true;
-        if (want_recs) {
-          // no marching here: the records are packed for the gather (scan_groups_kernel + pack_records_kernel), marching cubes
-          // runs where they arrive (march_dense_kernel)
-          uint64_t rec_cap = m->recs_cap36 * 36 / 41;  // 40 B per record + 4 B per 256 of them, rounded: stays inside the buffer
-          if (rec_cap > 2) rec_cap -= 2;
-          hipLaunchKernelGGL(scan_groups_kernel, dim3(1), dim3(1024), 0, s, (const unsigned long long*)d_psum, (unsigned long long)nblk, lq, d_ctr,
-                             (unsigned long long*)w.grp.p, m->d_recs, (unsigned long long)rec_cap,
-                             ctr_from_kernel ? hcp : (MeshCounters*)nullptr);
-          HIP_TRYM(hipGetLastError());
-          const uint64_t ngrp_q = (nblk_q + MARCH_GROUP - 1) / MARCH_GROUP;
-          const uint64_t gmax = (uint64_t)p->num_cu * 8;
-          hipLaunchKernelGGL(pack_records_kernel, dim3((unsigned)(ngrp_q < gmax ? (ngrp_q ? ngrp_q : 1) : gmax)), dim3(BLOCK), 0, s, (const uint32_t*)d_hdr,
-                             (const uint32_t*)d_rec, (const unsigned long long*)w.grp.p, (unsigned long long)nblk, lq, (const MeshCounters*)d_ctr,
-                             m->d_recs, (unsigned long long)rec_cap);
-          ctr_on_host = ctr_from_kernel;
-        } else {
-        // one wave of workgroups: each takes an equal share of the records (computed on device from the group sums)
-        static const int march_bpc = [] { const char* e = getenv("GSDF_HIP_MARCH_BPC"); return e ? atoi(e) : 4; }();  // tuning knob (7 fit a CU; 4 leave LDS and wave slots to the other mesh in flight: 0.503 -> 0.495 ms per mesh, and a blocking mesh loses nothing)
-        const size_t lds_march = MARCH_LDS_BYTES;
-        hipLaunchKernelGGL(march_records_kernel, dim3(grid_for(nblk_q, p->num_cu, march_bpc)), dim3(BLOCK), lds_march, s, d_hdr, d_rec,
-                           d_psum, (unsigned long long)nblk, lq, ox, oy, oz, res, m->d_tris, (uint64_t)tcap, d_ctr,
-                           ctr_from_kernel ? hcp : (MeshCounters*)nullptr);
-        ctr_on_host = ctr_from_kernel;
-        }
-      } else if (lq == 3 && lk == 4 && opts.share_corners == 1) {
-        // exact corner sharing: one wave per level-3 brick
-        const size_t lds_b = (size_t)(p->prog.nslots * 4) * BLOCK * sizeof(float) + 4096 + TRI_STAGE * 36 + 32 + 4 * 512 * 4 + 4 * 24 * 4;
-        hipLaunchKernelGGL((leaf_brick_kernel<4, 2>), dim3(grid_for(capq[lq & 1] * 64 < bound ? capq[lq & 1] * 64 : bound, p->num_cu, 8)),
-                           dim3(BLOCK), lds_b, s, p->d_code, (const Cube*)q[lq & 1]->p, (unsigned long long)capq[lq & 1],
-                           p->prog.nslots, ox, oy, oz, res, m->d_tris, tcap, d_ctr);
-        used_brick = true;
-      } else if (p->f_leaf && p->spec_leaf_k == lk) {  // whichever W it was built for: same launch
-        HIP_TRYM(launch_fn(p->f_leaf, grid_for(bound, p->num_cu, leaf_bpc), BLOCK, lds_m, s, (const uint32_t*)p->d_code, (const Cube*)q[lq & 1]->p,
-                           (unsigned long long)capq[lq & 1], (int)lq, (int)p->prog.nslots, ox, oy, oz, res, m->d_tris,
-                           (unsigned long)tcap, d_ctr));
-      } else {
-        // Ahead-of-time (interpreter) leaf kernels exist only at occupancies the compiler reaches WITHOUT scratch
-        // (tests/test_kernel_resources.py reads the shipped code object): at 4 workgroups per CU (128 VGPRs) the K = 4 and
-        // K = 2 interpreter builds spill, and a spilling build is not trusted (see fn_scratch_bytes).
-        if (lk == 4) { if (lw == 2) LAUNCH_LEAF(4, 2); else LAUNCH_LEAF(4, 3); }
-        else if (lk == 2) LAUNCH_LEAF(2, 3);
-        else LAUNCH_LEAF(1, 4);
-      }
-#undef LAUNCH_LEAF
-      HIP_TRYM(hipGetLastError());
-    }
-    HIP_TRYM(hipEventRecord(ev2, s));
-    // the completion event: ev2 itself when the last kernel has handed the counters to the host (nothing sits between them)
-    if (!ctr_on_host) {
-      HIP_TRYM(hipMemcpyAsync(&hc, d_ctr, sizeof(hc), hipMemcpyDeviceToHost, s));
-      HIP_TRYM(hipEventRecord(evr, s));
-    }
-    ev_done = ctr_on_host ? ev2 : evr;
     return GSDF_OK;
+  }
+  // two kernels: evaluation + cut-leaf records, then marching cubes over the records
+  uint32_t* d_hdr = (uint32_t*)w.hdr.p;
+  uint32_t* d_rec = (uint32_t*)w.rec.p;
+  unsigned long long* d_psum = (unsigned long long*)((char*)w.ctr.p + kCtrBytes);  // cleared with the counters
+  const unsigned use_masks = masks_valid ? 1u : 0u;
+  // share_corners = 1: every bitwise-distinct lattice point of a brick once (kernels_octree.h: leaf_dense_kernel)
+  used_dense = opts.share_corners == 1 && lq == 3 && lk == 4;
+  // share_corners = 2: the distinct z rows of a brick once each (kernels_octree.h: DZ) -- column bricks at four points per lane
+  const bool want_dz = opts.share_corners == 2 && lq == 3 && lk == 4;
+  if (used_dense) {
+    spec_leaf_dense(p);
+    const size_t lds_d = p->lds_dense();
+    HIP_TRY(launch_kernel(leaf_dense_aot(3 * lds_d <= gsdf_program::kLdsPerCu ? 3 : 2), p->f_leaf_dense, grid, BLOCK, lds_d, s, p->d_code.p, cubes, ncubes, p->prog.nslots, ox, oy, oz, res,
+                          d_hdr, d_rec, d_psum, nblk, d_ctr, use_masks));
+  } else {
+    if (want_dz) spec_leaf_dz(p);
+    const LeafPick pick = p->leaf_pick(lq, want_dz);
+    used_dz = pick.v.dz;
+    // (fewer than three levels: a few leaves per pass, and room for the case table whether lds_m counts it or not)
+    HIP_TRY(launch_kernel(leaf_eval_aot(pick.v), pick.f, grid, BLOCK, lq != 3 ? lds_m + 256 : lds_m, s, p->d_code.p, cubes, ncubes, lq, p->prog.nslots, ox, oy, oz, res, d_hdr, d_rec,
+                          d_psum, nblk, d_ctr, use_masks));
+  }
+  HIP_TRY(hipEventRecord(w.ev[3], s));
+  two_kernel = true;
+  if (want_recs) {
+    // no marching here: the records are packed for the gather (scan_groups_kernel + pack_records_kernel), marching cubes
+    // runs where they arrive (march_dense_kernel)
+    uint64_t rec_cap = m->recs_cap36 * 36 / 41;  // 40 B per record + 4 B per 256 of them, rounded: stays inside the buffer
+    if (rec_cap > 2) rec_cap -= 2;
+    hipLaunchKernelGGL(scan_groups_kernel, dim3(1), dim3(1024), 0, s, (const unsigned long long*)d_psum, (unsigned long long)nblk, lq, d_ctr,
+                       (unsigned long long*)w.grp.p, m->d_recs, (unsigned long long)rec_cap,
+                       ctr_from_kernel ? hcp : (MeshCounters*)nullptr);
+    HIP_TRY(hipGetLastError());
+    const uint64_t ngrp_q = (nblk_q + MARCH_GROUP - 1) / MARCH_GROUP;
+    const uint64_t gmax = (uint64_t)p->num_cu * 8;
+    hipLaunchKernelGGL(pack_records_kernel, dim3((unsigned)(ngrp_q < gmax ? (ngrp_q ? ngrp_q : 1) : gmax)), dim3(BLOCK), 0, s, (const uint32_t*)d_hdr,
+                       (const uint32_t*)d_rec, (const unsigned long long*)w.grp.p, (unsigned long long)nblk, lq, (const MeshCounters*)d_ctr,
+                       m->d_recs, (unsigned long long)rec_cap);
+  } else {
+    // one wave of workgroups: each takes an equal share of the records (computed on device from the group sums)
+    static const int march_bpc = env_int("GSDF_HIP_MARCH_BPC", 4);  // tuning knob (7 fit a CU; 4 leave LDS and wave slots to the other mesh in flight: 0.503 -> 0.495 ms per mesh, and a blocking mesh loses nothing)
+    const size_t lds_march = MARCH_LDS_BYTES;
+    hipLaunchKernelGGL(march_records_kernel, dim3(grid_for(nblk_q, p->num_cu, march_bpc)), dim3(BLOCK), lds_march, s, d_hdr, d_rec,
+                       d_psum, (unsigned long long)nblk, lq, ox, oy, oz, res, m->d_tris, (uint64_t)tcap, d_ctr,
+                       ctr_from_kernel ? hcp : (MeshCounters*)nullptr);
+  }
+  ctr_on_host = ctr_from_kernel;
+  HIP_TRY(hipGetLastError());
+  return GSDF_OK;
+}
+
+int gsdf_mesh_job::enqueue_handover() {
+  // the completion event: the leaf phase's own when the last kernel has handed the counters to the host (nothing sits between them)
+  if (!ctr_on_host) {
+    HIP_TRY(hipMemcpyAsync(hcp, d_ctr, sizeof(MeshCounters), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipEventRecord(w.ev[4], s));
+  }
+  ev_done = ctr_on_host ? w.ev[2] : w.ev[4];
+  return GSDF_OK;
 }
 
 int gsdf_mesh_job::finish(bool* again) {
     MeshCounters& hc = *hcp;
-    HIP_TRYM(hipEventSynchronize(ev_done));
+    HIP_TRY(hipEventSynchronize(ev_done));
     if (hc.q_overflow) {  // a cube queue was too small: double and redo (exact: nothing was dropped silently)
       if (attempt >= 8) return (fail(GSDF_ERR_CAPACITY, "octree queue capacity exceeded"));
       qcap *= 4;
@@ -389,9 +381,9 @@ int gsdf_mesh_job::finish(bool* again) {
 int gsdf_mesh_job::stats() {
   MeshCounters& hc = *hcp;
   float ms01 = 0, ms12 = 0, ms13 = 0;
-  HIP_TRYM(hipEventElapsedTime(&ms01, ev0, ev1));
-  HIP_TRYM(hipEventElapsedTime(&ms12, ev1, ev2));
-  if (two_kernel) HIP_TRYM(hipEventElapsedTime(&ms13, ev1, ev3));  // the evaluating kernel alone
+  HIP_TRY(hipEventElapsedTime(&ms01, w.ev[0], w.ev[1]));
+  HIP_TRY(hipEventElapsedTime(&ms12, w.ev[1], w.ev[2]));
+  if (two_kernel) HIP_TRY(hipEventElapsedTime(&ms13, w.ev[1], w.ev[3]));  // the evaluating kernel alone
   uint64_t evals_prune = 0, pruned = 0;
   for (int level = levels; level >= lq; level--) {
     evals_prune += hc.n_items[level];
@@ -421,14 +413,13 @@ int gsdf_mesh_job::stats() {
   if (want_recs) { m->payload = GSDF_PAYLOAD_RECORDS; m->n_recs = hc.n_cut; p->last_recs = hc.n_cut; m->weldable = opts.shard_count == 1; }
   return GSDF_OK;
 }
-#undef HIP_TRYM
 
 static void job_release(gsdf_mesh_job* j, bool failed = true) {
   if (!j) return;
   // the way out of a failed start / wait: a partly enqueued chain may still be running -- nothing goes back to the pool, and the
   // workspace is not handed to the next job, under it
   if (failed && j->s) { (void)hipStreamSynchronize(j->s); (void)hipGetLastError(); }
-  if (j->p) j->p->job_busy[j->slot] = false;
+  if (j->p) j->w.job_busy = false;
   if (j->m) gsdf_hip_mesh_destroy(j->m);
   delete j;
 }
@@ -467,10 +458,7 @@ extern "C" int gsdf_hip_mesh_octree_start(gsdf_program* p, float res, const gsdf
   {
     // the largest launch of the descent: prune_spec_kernel (lds_prune_of and its static stage of SPEC_STAGE cubes); of the leaf phase:
     // the evaluating kernel with its case table (and what its marching half declares statically)
-    int lk0, lw0;
-    size_t lds_leaf;
-    p->leaf_config(&lk0, &lw0, &lds_leaf);
-    const size_t need_prune = lds_prune_of(p->prog.nslots + p->prog.lip_depth) + kPruneSpecStatic, need_leaf = lds_leaf + 256 + 1024;
+    const size_t need_prune = lds_prune_of(p->prog.nslots + p->prog.lip_depth) + kPruneSpecStatic, need_leaf = p->leaf_config().lds + 256 + 1024;
     if (int rc = p->lds_refused("gsdf_hip_mesh_octree", need_prune > need_leaf ? need_prune : need_leaf, "slots + interval stack <= " + std::to_string(GSDF_HIP_MAX_COLS_OCTREE))) return rc;
   }
   HIP_TRY(hipSetDevice(p->device));
@@ -485,7 +473,7 @@ extern "C" int gsdf_hip_mesh_octree_start(gsdf_program* p, float res, const gsdf
   if (levels > 17) return fail(GSDF_ERR_RESOLUTION, "resolution too fine: more than 17 octree levels");
 
   int slot = -1;
-  for (int k = 0; k < gsdf_program::kJobs; k++) if (!p->job_busy[k]) { slot = k; break; }
+  for (int k = 0; k < gsdf_program::kJobs; k++) if (!p->ws[k].job_busy) { slot = k; break; }
   if (slot < 0) return fail(GSDF_ERR_BAD_ARGUMENT, "three meshes of this program are in flight already: wait for one (gsdf_hip_mesh_octree_wait)");
   // Each slot has a workspace and a stream of its own: two chains in flight run beside each other (a caller's stream takes both).
   // Measured at npt-flange resdiv 1600, per mesh: one blocking call at a time 0.59 ms; two chains back to back on ONE stream 0.58;
@@ -493,19 +481,19 @@ extern "C" int gsdf_hip_mesh_octree_start(gsdf_program* p, float res, const gsdf
   // kernel of the other. Tried and dropped: one stream for the evaluating kernels of all meshes and side streams for the stages
   // around them, ordered by events (a three-stage pipeline): 0.54, and a blocking call 0.61 -- every cross-stream event wait is
   // ~10 us on this runtime.
-  hipStream_t* own = slot == 1 ? &p->stream_b : (slot == 2 ? &p->stream_c : nullptr);
-  if (own && !opts.stream && !*own && hipStreamCreateWithFlags(own, hipStreamNonBlocking) != hipSuccess) {
+  gsdf_program::OctreeWs& w = p->ws[slot];
+  if (slot > 0 && !opts.stream && w.own.ensure() != hipSuccess) {  // (slot 0 runs on the handle's stream)
     (void)hipGetLastError();
     return fail(GSDF_ERR_HIP, "hipStreamCreate failed");
   }
-  hipStream_t s = opts.stream ? (hipStream_t)opts.stream : (own ? *own : p->stream);
+  hipStream_t s = opts.stream ? (hipStream_t)opts.stream : (slot > 0 ? w.own.s : p->stream.s);
   gsdf_mesh_job* j = new (std::nothrow) gsdf_mesh_job(p, slot);
   gsdf_mesh* m = new (std::nothrow) gsdf_mesh();
   if (!j || !m) { delete j; delete m; return fail(GSDF_ERR_BAD_ARGUMENT, "out of memory"); }
   j->m = m; j->opts = opts; j->res = res; j->s = s; j->levels = levels; j->want_recs = want_recs;
   j->ox = mn[0]; j->oy = mn[1]; j->oz = mn[2];
-  p->job_busy[slot] = true;
-  p->job_stream[slot] = s;
+  w.job_busy = true;
+  w.job_stream = s;
   m->device = p->device;
   m->stream = s;
   m->num_cu = p->num_cu;
@@ -514,12 +502,9 @@ extern "C" int gsdf_hip_mesh_octree_start(gsdf_program* p, float res, const gsdf
   m->st.origin[0] = j->ox; m->st.origin[1] = j->oy; m->st.origin[2] = j->oz;
   auto bail = [&](int code) { job_release(j); return code; };
   static_assert(sizeof(MeshCounters) <= 2048, "counters: a 2 KB slot of the pinned block each (slot 1: DCCounters of dual contouring)");
-  if (!p->h_ctr && hipHostMalloc(&p->h_ctr, 16384, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return bail(fail(GSDF_ERR_HIP, "hipHostMalloc of the counter block failed")); }
-  j->hcp = (MeshCounters*)((char*)p->h_ctr + (size_t)slot * 4096);
-  hipEvent_t* evs = slot == 0 ? p->ev : (slot == 1 ? p->ev_b : p->ev_c);
-  for (int k = 0; k < 5; k++)
-    if (!evs[k] && hipEventCreate(&evs[k]) != hipSuccess) return bail(fail(GSDF_ERR_HIP, "hipEventCreate failed"));
-  j->ev0 = evs[0]; j->ev1 = evs[1]; j->ev2 = evs[2]; j->ev3 = evs[3]; j->evr = evs[4];
+  if (!p->h_ctr.p && hipHostMalloc(&p->h_ctr.p, 16384, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return bail(fail(GSDF_ERR_HIP, "hipHostMalloc of the counter block failed")); }
+  j->hcp = (MeshCounters*)((char*)p->h_ctr.p + (size_t)slot * 4096);
+  if (w.ev.ensure() != hipSuccess) return bail(fail(GSDF_ERR_HIP, "hipEventCreate failed"));
 
   // ---- level-synchronous descent from the top cube to level lq = min(levels, 3). The whole chain
   // (memset, one prune launch per level, the leaf kernel) is enqueued without a host round trip: each
@@ -532,17 +517,14 @@ extern "C" int gsdf_hip_mesh_octree_start(gsdf_program* p, float res, const gsdf
   j->pmask = opts.prune & ~GSDF_PRUNE_ASSUME_SDF;  // levels to test: 0 none, 1 all, else bit L = Level L
   if ((opts.prune & GSDF_PRUNE_ASSUME_SDF) && j->pmask == 0) j->pmask = 1;
   j->ptest = (opts.prune & GSDF_PRUNE_ASSUME_SDF) ? 2 : 1;
-  p->leaf_config(&j->lk, &j->lw, &j->lds_m);
-  {
-    static const size_t lds_pad = [] { const char* e = getenv("GSDF_HIP_LEAF_LDS_PAD"); return e ? (size_t)atoi(e) : (size_t)0; }();  // developer knob: LDS a leaf workgroup asks for beyond its need (occupancy experiments)
-    j->lds_m += lds_pad;
-  }
+  static const size_t lds_pad = (size_t)env_int("GSDF_HIP_LEAF_LDS_PAD", 0);  // developer knob: LDS a leaf workgroup asks for beyond its need (occupancy experiments)
+  j->lk = p->leaf_config().k;
+  j->lds_m = p->leaf_config().lds + lds_pad;
   j->qcap = j->w.q0.cap / sizeof(Cube);
   {
     // 1 M cubes (8 MB) per queue to start with; GSDF_HIP_QCAP_MIN lowers it so that tests can drive the
     // overflow -> grow -> rerun path (the arenas only ever grow, so a handle that already meshed keeps its size)
-    const char* e = getenv("GSDF_HIP_QCAP_MIN");
-    const uint64_t qmin = e ? (uint64_t)strtoull(e, nullptr, 10) : ((uint64_t)1 << 20);
+    const uint64_t qmin = env_u64("GSDF_HIP_QCAP_MIN", (uint64_t)1 << 20);  // (read at every mesh)
     if (j->qcap < qmin) j->qcap = qmin;
     if (j->qcap < 64) j->qcap = 64;
   }
@@ -600,7 +582,7 @@ int mesh_march_dense(const uint8_t* d_buf, const gsdf_dense_part* parts, int npa
   if (chunks == 0) return GSDF_OK;
   // the table is small and the copy's source is this stack frame: hipMemcpyAsync from pageable memory stages it before returning
   HIP_TRY(hipMemcpyAsync(d_parts, &h, sizeof h, hipMemcpyHostToDevice, s));
-  static const int march_bpc = [] { const char* e = getenv("GSDF_HIP_MARCH_BPC"); return e ? atoi(e) : 4; }();  // tuning knob (7 fit a CU; 4 leave LDS and wave slots to the other mesh in flight: 0.503 -> 0.495 ms per mesh, and a blocking mesh loses nothing)
+  static const int march_bpc = env_int("GSDF_HIP_MARCH_BPC", 4);  // tuning knob (see enqueue_leaf)
   const uint64_t gmax = (uint64_t)num_cu * (uint64_t)(march_bpc > 0 ? march_bpc : 4);
   const size_t lds = MARCH_DENSE_LDS_BYTES;
   hipLaunchKernelGGL(march_dense_kernel, dim3((unsigned)(chunks < gmax ? chunks : gmax)), dim3(BLOCK), lds, s, d_buf, (const DenseParts*)d_parts, ox, oy, oz, res, d_tris);
@@ -711,7 +693,7 @@ static int dc_mesh(gsdf_program* p, float res, int chiseled, int shard_rank, int
     if (int rc = p->lds_refused("dual contouring", need_edges > need_origin ? need_edges : need_origin, std::to_string(GSDF_HIP_MAX_SLOTS_DC) + " slots")) return rc;
   }
   HIP_TRY(hipSetDevice(p->device));
-  hipStream_t s = stream ? (hipStream_t)stream : p->stream;
+  hipStream_t s = stream ? (hipStream_t)stream : p->stream.s;
   // Reset (dual_contour.go:26-41): bounds shifted by -res/2, makeICube
   const float sub = res / 2;
   float mn[3], mx[3];
@@ -744,21 +726,16 @@ static int dc_mesh(gsdf_program* p, float res, int chiseled, int shard_rank, int
     gsdf_hip_mesh_destroy(m);
     return code;
   };
-#define HIP_TRYM(expr)                                                                                          \
-  do {                                                                                                          \
-    hipError_t _e = (expr);                                                                                     \
-    if (_e != hipSuccess) return bail(fail(GSDF_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e))); \
-  } while (0)
-  for (auto& e : p->ev)
-    if (!e) HIP_TRYM(hipEventCreate(&e));
-  for (auto& e : p->ev_b)
-    if (!e) HIP_TRYM(hipEventCreate(&e));
+  gsdf_program::OctreeWs& w0 = p->ws[0];  // its first queue, its counters and its events serve here too (no octree mesh is in flight)
+  const EventSet<5>& ev = w0.ev;
+  HIP_TRYM(w0.ev.ensure());
+  HIP_TRYM(p->dc_ev.ensure());
   // Workspace lives in the program handle (grow-only): the index grid alone is 4.3 GB at 1024^3 cells, and a
   // hipMalloc/hipFree pair of that size per mesh cost more wall time than the whole device pass.
-  gsdf_program::Arena &grid = p->dc_grid, &d2 = p->dc_dist, &f2 = p->dc_fv, &n2 = p->dc_nrm, &e2 = p->dc_edge;
+  Arena &grid = p->dc_grid, &d2 = p->dc_dist, &f2 = p->dc_fv, &n2 = p->dc_nrm, &e2 = p->dc_edge;
   HIP_TRYM(grid.ensure(ncell * sizeof(int)));
-  HIP_TRYM(p->ctr.ensure(sizeof(MeshCounters) > sizeof(DCCounters) ? sizeof(MeshCounters) : sizeof(DCCounters)));
-  DCCounters* d_ctr = (DCCounters*)p->ctr.p;
+  HIP_TRYM(w0.ctr.ensure(sizeof(MeshCounters) > sizeof(DCCounters) ? sizeof(MeshCounters) : sizeof(DCCounters)));
+  DCCounters* d_ctr = (DCCounters*)w0.ctr.p;
   const int lk = p->batch_k();
   // Kept cubes hug the surface: ~ c * n^2 of the n^3 lattice. Start from the previous pass on this handle, else from
   // 12 n^2 (an overflow repeats the full-lattice origin pass, so be generous: 84 B per cube).
@@ -800,7 +777,7 @@ static int dc_mesh(gsdf_program* p, float res, int chiseled, int shard_rank, int
     const uint64_t ecap = 3 * ccap, tcap = 2 * ecap;
     // run descriptors (kernels_dc.h: DC_DESC): the origin sweep's follow the cubes in q0, the edge stage's have an arena of their own
     const uint64_t crun_cap = DC_PARTS * dc_cube_run_seg(ntiles), erun_cap = DC_PARTS * dc_edge_run_seg(ccap, ntiles);
-    HIP_TRYM(p->q0.ensure((ccap + crun_cap) * sizeof(Cube) + ccap * sizeof(float)));  // (+ the sweep's distance of every kept cube, behind the descriptors)
+    HIP_TRYM(w0.q0.ensure((ccap + crun_cap) * sizeof(Cube) + ccap * sizeof(float)));  // (+ the sweep's distance of every kept cube, behind the descriptors)
     HIP_TRYM(p->dc_erun.ensure(erun_cap * sizeof(unsigned long long)));
     HIP_TRYM(p->dc_flag.ensure(ccap));  // "this cube is placed", a byte per cube: set by the edge stage, read by the placement stage
     HIP_TRYM(d2.ensure(ccap * sizeof(float4)));
@@ -815,14 +792,13 @@ static int dc_mesh(gsdf_program* p, float res, int chiseled, int shard_rank, int
     HIP_TRYM(hipMemsetAsync(d_ctr, 0, sizeof(DCCounters), s));
     HIP_TRYM(hipMemsetAsync(p->dc_flag.p, 0, ccap, s));
     if (shard_count > 1) HIP_TRYM(hipMemsetAsync(grid.p, 0xff, ncell * sizeof(int), s));  // cells outside the slab read as empty
-    HIP_TRYM(hipEventRecord(p->ev[0], s));
-    static const int origin_grid = [] { const char* e = getenv("GSDF_HIP_DC_ORIGIN_GRID"); return e ? atoi(e) : 0; }();  // developer knob: workgroups of the origin sweep (1 = tiles strictly in order)
+    HIP_TRYM(hipEventRecord(ev[0], s));
+    static const int origin_grid = env_int("GSDF_HIP_DC_ORIGIN_GRID", 0);  // developer knob: workgroups of the origin sweep (1 = tiles strictly in order)
     unsigned g1 = origin_grid > 0 ? (unsigned)origin_grid : grid_for((nslab + lk - 1) / lk, p->num_cu, 32);
     g1 = (g1 + DC_PARTS - 1) / DC_PARTS * DC_PARTS;  // tile T goes to workgroup T % g1, hence to part T % DC_PARTS: what bounds a part's run descriptors (dc_cube_run_seg)
-#define LAUNCH_O(KK, WW) hipLaunchKernelGGL((dc_origin_kernel<KK, WW>), dim3(g1), dim3(BLOCK), p->lds_bytes(KK) + 32, s, p->d_code, p->prog.nslots, nshift, ox, oy, oz, res, (int*)grid.p, (Cube*)p->q0.p, (unsigned long long)ccap, zlo, zhi, ub, eb[0], eb[1], eb[2], eb[3], eb[4], eb[5], t0[0], t0[1], t0[2], tn[0], tn[1], tn[2], d_ctr, d_keep)
     // Stage 0: the interval test of the sweep's blocks (kernels_dc.h: dc_block_test_kernel), one lane per block of 8 x 8 x K origins.
     // GSDF_HIP_NO_DC_BLOCK_TEST=1: every block is evaluated (developer knob: A/B timing, cross-check in the tests).
-    static const bool block_test_off = [] { const char* e = getenv("GSDF_HIP_NO_DC_BLOCK_TEST"); return e && atoi(e) != 0; }();
+    static const bool block_test_off = env_flag("GSDF_HIP_NO_DC_BLOCK_TEST");
     const uint32_t* d_keep = nullptr;
     {
       const uint64_t nblk = (uint64_t)tn[0] * tn[1] * tn[2] * 4ull;
@@ -831,11 +807,8 @@ static int dc_mesh(gsdf_program* p, float res, int chiseled, int shard_rank, int
       // (a tree whose interval stack makes the test ask for more LDS than a CU has goes without it: every block is evaluated)
       if (!block_test_off && nblk > 0 && lds_t <= gsdf_program::kLdsPerCu && p->dc_tile.ensure((size_t)nblk * sizeof(uint32_t)) == hipSuccess) {
         const unsigned gt = grid_for(nblk, p->num_cu, 8);
-        if (p->f_dc_block_test) HIP_TRYM(launch_fn(p->f_dc_block_test, gt, BLOCK, lds_t, s, (const uint32_t*)p->d_code, (int)cols, (int)p->prog.nslots, (int)lk, ox, oy, oz, res,
-                                                    (unsigned)zlo, t0[0], t0[1], t0[2], tn[0], tn[1], tn[2], (uint32_t*)p->dc_tile.p));
-        else hipLaunchKernelGGL(dc_block_test_kernel, dim3(gt), dim3(BLOCK), lds_t, s, p->d_code, cols, p->prog.nslots, lk, ox, oy, oz, res, zlo, t0[0], t0[1], t0[2], tn[0], tn[1],
-                                tn[2], (uint32_t*)p->dc_tile.p);
-        HIP_TRYM(hipGetLastError());
+        HIP_TRYM(launch_kernel(dc_block_test_kernel, p->f_dc_block_test, gt, BLOCK, lds_t, s, p->d_code.p, cols, p->prog.nslots, lk, ox, oy, oz, res, zlo, t0[0], t0[1], t0[2], tn[0],
+                               tn[1], tn[2], p->dc_tile.p));
         // ... and "no cube here" in the cleared tiles next to evaluated ones: the cells the later stages read and the sweep does not write
         hipLaunchKernelGGL(dc_grid_clear_kernel, dim3(grid_for((uint64_t)((tn[0] + 3) / 4) * ((tn[1] + 3) / 4) * ((tn[2] + 3) / 4) * BLOCK, p->num_cu, 16)), dim3(BLOCK), 0, s, (int*)grid.p, nshift, lk, zlo, zhi, t0[0], t0[1], t0[2], tn[0], tn[1],
                            tn[2], (const uint32_t*)p->dc_tile.p);
@@ -845,40 +818,27 @@ static int dc_mesh(gsdf_program* p, float res, int chiseled, int shard_rank, int
         (void)hipGetLastError();
       }
     }
-    if (p->f_dc_origin) HIP_TRYM(launch_fn(p->f_dc_origin, g1, BLOCK, p->lds_bytes(lk) + 32, s, (const uint32_t*)p->d_code, (int)p->prog.nslots, (int)nshift, ox, oy, oz, res, (int*)grid.p, (Cube*)p->q0.p, (unsigned long long)ccap, (unsigned)zlo, (unsigned)zhi, ub, eb[0], eb[1], eb[2], eb[3], eb[4], eb[5], t0[0], t0[1], t0[2], tn[0], tn[1], tn[2], d_ctr, d_keep));
-    else
-    {  // (W by gsdf_program::dc_origin_waves, the rule gsdf_hip_program_kernels reports by)
-      const int ow = gsdf_program::dc_origin_waves(lk);
-      if (lk == 4 && ow == 3) LAUNCH_O(4, 3);  // <4, 4> needs scratch: not built (see fn_scratch_bytes)
-      else if (lk == 2 && ow == 3) LAUNCH_O(2, 3);  // (<2, 4> sits at its register budget: with the block verdicts' pointer it spills four VGPRs, and a kernel with scratch is not shipped)
-      else if (lk == 1 && ow == 4) LAUNCH_O(1, 4);
-      else return bail(fail(GSDF_ERR_BAD_ARGUMENT, "dual contouring: no origin sweep built for this K and W"));
+    {  // (a per-tree kernel is the same launch whichever W it was built for)
+      const dc_origin_kernel_t aot = dc_origin_aot(gsdf_program::dc_origin_variant(lk));
+      if (!aot && !p->f_dc_origin) return bail(fail(GSDF_ERR_BAD_ARGUMENT, "dual contouring: no origin sweep built for this K and W"));
+      HIP_TRYM(launch_kernel(aot, p->f_dc_origin, g1, BLOCK, p->lds_bytes(lk) + 32, s, p->d_code.p, p->prog.nslots, nshift, ox, oy, oz, res, grid.p, w0.q0.p, ccap, zlo, zhi, ub, eb[0], eb[1],
+                             eb[2], eb[3], eb[4], eb[5], t0[0], t0[1], t0[2], tn[0], tn[1], tn[2], d_ctr, d_keep));
     }
-#undef LAUNCH_O
-    HIP_TRYM(hipGetLastError());
-    HIP_TRYM(hipEventRecord(p->ev_b[0], s));  // origin sweep done
+    HIP_TRYM(hipEventRecord(p->dc_ev[0], s));  // origin sweep done
     // (a multiple of DC_PARTS like the sweep's grid: run r goes to workgroup r % grid, hence to the edge list's part r % DC_PARTS --
     // what bounds a part's edge-run descriptors, dc_edge_run_seg)
     const unsigned g_edges = (grid_for(ccap, p->num_cu, 8) + DC_PARTS - 1) / DC_PARTS * DC_PARTS;
-    if (p->f_dc_edges) HIP_TRYM(launch_fn(p->f_dc_edges, g_edges, BLOCK, p->lds_bytes(3), s, (const uint32_t*)p->d_code, (const Cube*)p->q0.p,
-                       (unsigned long long)ccap, ox, oy, oz, res, (float4*)d2.p, (float*)f2.p, (unsigned*)e2.p, (unsigned long long)ecap, (unsigned long long*)p->dc_erun.p, (unsigned long long)ntiles, (const int*)grid.p, (int)nshift, (unsigned char*)p->dc_flag.p, d_ctr));
-    else
-    hipLaunchKernelGGL(dc_edges_kernel, dim3(g_edges), dim3(BLOCK), p->lds_bytes(3), s, p->d_code, (const Cube*)p->q0.p,
-                       (unsigned long long)ccap, ox, oy, oz, res, (float4*)d2.p, (float*)f2.p, (unsigned*)e2.p, (unsigned long long)ecap, (unsigned long long*)p->dc_erun.p, (unsigned long long)ntiles, (const int*)grid.p, (int)nshift, (unsigned char*)p->dc_flag.p, d_ctr);
-    HIP_TRYM(hipGetLastError());
-    HIP_TRYM(hipEventRecord(p->ev_b[1], s));  // edges done
-    if (p->f_dc_normals) HIP_TRYM(launch_fn(p->f_dc_normals, grid_for(ecap, p->num_cu, 8), BLOCK, p->lds_bytes(2), s, (const uint32_t*)p->d_code, (const Cube*)p->q0.p,
-                       (const float4*)d2.p, (const unsigned*)e2.p, (const unsigned long long*)p->dc_erun.p, (unsigned long long)ccap, (unsigned long long)ntiles, ox, oy, oz, res, h, (float*)n2.p, d_ctr));
-    else
-    hipLaunchKernelGGL(dc_normals_kernel, dim3(grid_for(ecap, p->num_cu, 8)), dim3(BLOCK), p->lds_bytes(2), s, p->d_code, (const Cube*)p->q0.p,
-                       (const float4*)d2.p, (const unsigned*)e2.p, (const unsigned long long*)p->dc_erun.p, (unsigned long long)ccap, (unsigned long long)ntiles, ox, oy, oz, res, h, (float*)n2.p, d_ctr);
-    HIP_TRYM(hipGetLastError());
-    HIP_TRYM(hipEventRecord(p->ev_b[2], s));  // normals done
-    hipLaunchKernelGGL(dc_place_kernel, dim3(grid_for(ccap * 4, p->num_cu, 16)), dim3(DC_BLOCK), 0, s, (const Cube*)p->q0.p,
+    HIP_TRYM(launch_kernel(dc_edges_kernel, p->f_dc_edges, g_edges, BLOCK, p->lds_bytes(3), s, p->d_code.p, w0.q0.p, ccap, ox, oy, oz, res, d2.p, f2.p, e2.p, ecap, p->dc_erun.p, ntiles, grid.p,
+                           nshift, p->dc_flag.p, d_ctr));
+    HIP_TRYM(hipEventRecord(p->dc_ev[1], s));  // edges done
+    HIP_TRYM(launch_kernel(dc_normals_kernel, p->f_dc_normals, grid_for(ecap, p->num_cu, 8), BLOCK, p->lds_bytes(2), s, p->d_code.p, w0.q0.p, d2.p, e2.p, p->dc_erun.p, ccap, ntiles, ox, oy, oz,
+                           res, h, n2.p, d_ctr));
+    HIP_TRYM(hipEventRecord(p->dc_ev[2], s));  // normals done
+    hipLaunchKernelGGL(dc_place_kernel, dim3(grid_for(ccap * 4, p->num_cu, 16)), dim3(DC_BLOCK), 0, s, (const Cube*)w0.q0.p,
                        (unsigned long long)ccap, (const float4*)d2.p, (const int*)grid.p, (const float*)n2.p, nshift, ox, oy, oz, res,
                        sqrtLambda, (float*)f2.p, zown_hi, (const unsigned char*)p->dc_flag.p, d_ctr);
     HIP_TRYM(hipGetLastError());
-    HIP_TRYM(hipEventRecord(p->ev_b[3], s));  // placement done
+    HIP_TRYM(hipEventRecord(p->dc_ev[3], s));  // placement done
     if (out_ix) {
       // the quads counted row by row and the rows scanned (kernels_dc_indexed.h, passes A and B); their number comes back with the
       // counters, and the rest of the stage runs once the lists are known to have held
@@ -886,7 +846,7 @@ static int dc_mesh(gsdf_program* p, float res, int chiseled, int shard_rank, int
       HIP_TRYM(p->dc_ix.ensure(ixw.bytes));
       uint8_t* w = (uint8_t*)p->dc_ix.p;
       HIP_TRYM(hipMemsetAsync(w + ixw.row_cnt, 0, ixw.n_rows * 4, s));
-      hipLaunchKernelGGL(dci_count_kernel, dim3(grid_for(ecap, p->num_cu, 8)), dim3(BLOCK), 0, s, (const Cube*)p->q0.p, (const float4*)d2.p, (const unsigned*)e2.p,
+      hipLaunchKernelGGL(dci_count_kernel, dim3(grid_for(ecap, p->num_cu, 8)), dim3(BLOCK), 0, s, (const Cube*)w0.q0.p, (const float4*)d2.p, (const unsigned*)e2.p,
                          (unsigned long long)ecap, (const int*)grid.p, nshift, (unsigned*)(w + ixw.row_cnt), (unsigned*)(w + ixw.place), (uint4*)(w + ixw.quad), d_ctr);
       HIP_TRYM(hipGetLastError());
       hipLaunchKernelGGL(dci_row_sum_kernel, dim3(ixw.n_row_blocks), dim3(BLOCK), 0, s, (const unsigned*)(w + ixw.row_cnt), (unsigned)ixw.n_rows,
@@ -897,14 +857,14 @@ static int dc_mesh(gsdf_program* p, float res, int chiseled, int shard_rank, int
       hipLaunchKernelGGL(dci_row_base_kernel, dim3(ixw.n_row_blocks), dim3(BLOCK), 0, s, (const unsigned*)(w + ixw.row_cnt), (unsigned)ixw.n_rows,
                          (const unsigned*)(w + ixw.blk_base), (unsigned*)(w + ixw.row_base));
       HIP_TRYM(hipGetLastError());
-      HIP_TRYM(hipEventRecord(p->ev[2], s));
+      HIP_TRYM(hipEventRecord(ev[2], s));
       HIP_TRYM(hipMemcpyAsync(&n_quads, w + ixw.total, sizeof n_quads, hipMemcpyDeviceToHost, s));
     } else {
-    hipLaunchKernelGGL(dc_quads_kernel, dim3(grid_for(ecap, p->num_cu, 8)), dim3(BLOCK), 0, s, (const Cube*)p->q0.p, (const float4*)d2.p,
+    hipLaunchKernelGGL(dc_quads_kernel, dim3(grid_for(ecap, p->num_cu, 8)), dim3(BLOCK), 0, s, (const Cube*)w0.q0.p, (const float4*)d2.p,
                        (const unsigned*)e2.p, (unsigned long long)ecap, (const int*)grid.p, (const float*)f2.p, nshift, zown_lo, zown_hi,
                        m->d_tris, (unsigned long long)m->cap, d_ctr);
     HIP_TRYM(hipGetLastError());
-    HIP_TRYM(hipEventRecord(p->ev[1], s));
+    HIP_TRYM(hipEventRecord(ev[1], s));
     }
     HIP_TRYM(hipMemcpyAsync(&hc, d_ctr, sizeof(hc), hipMemcpyDeviceToHost, s));
     HIP_TRYM(hipStreamSynchronize(s));
@@ -941,20 +901,20 @@ static int dc_mesh(gsdf_program* p, float res, int chiseled, int shard_rank, int
     const uint8_t* w = (const uint8_t*)p->dc_ix.p;
     unsigned long long* d_bad = (unsigned long long*)((uint8_t*)p->dc_ix.p + ixw.bad);
     unsigned long long n_bad = 0;
-    hipError_t e = hipEventRecord(p->ev[3], s);
+    hipError_t e = hipEventRecord(ev[3], s);
     if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0, 8, s);
     if (e == hipSuccess) {
-      hipLaunchKernelGGL(dci_scatter_kernel, dim3(grid_for(ecap, p->num_cu, 8)), dim3(BLOCK), 0, s, (const Cube*)p->q0.p, (const unsigned*)e2.p, (unsigned long long)ecap,
+      hipLaunchKernelGGL(dci_scatter_kernel, dim3(grid_for(ecap, p->num_cu, 8)), dim3(BLOCK), 0, s, (const Cube*)w0.q0.p, (const unsigned*)e2.p, (unsigned long long)ecap,
                          nshift, (const unsigned*)(w + ixw.row_base), (const unsigned*)(w + ixw.place), (unsigned long long)Q, xa, src, d_bad, d_ctr);
       e = hipGetLastError();
     }
     if (e == hipSuccess) {
-      hipLaunchKernelGGL(dci_rank_kernel, dim3((unsigned)((Q + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, (const Cube*)p->q0.p, (const unsigned*)e2.p, (unsigned long long)ecap,
+      hipLaunchKernelGGL(dci_rank_kernel, dim3((unsigned)((Q + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, (const Cube*)w0.q0.p, (const unsigned*)e2.p, (unsigned long long)ecap,
                          nshift, (const unsigned*)(w + ixw.row_base), (const unsigned*)(w + ixw.row_cnt), (const unsigned*)xa, (const unsigned*)src,
                          (const uint4*)(w + ixw.quad), (unsigned long long)Q, (unsigned long long)final_ccap, (unsigned*)slots, d_bad);
       e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipEventRecord(p->ev[1], s);
+    if (e == hipSuccess) e = hipEventRecord(ev[1], s);
     // every slot written, every index in range? (kernels_dc_indexed.h: *bad) -- known before anything reads the slots
     if (e == hipSuccess) e = hipMemcpyAsync(&n_bad, d_bad, sizeof n_bad, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -964,14 +924,14 @@ static int dc_mesh(gsdf_program* p, float res, int chiseled, int shard_rank, int
       if (e == hipSuccess) return bail(fail(GSDF_ERR_HIP, "dual contouring, indexed: internal error (" + std::to_string(n_bad) + " quads out of place in the ordering pass)"));
       return bail(fail(GSDF_ERR_HIP, std::string("dual contouring, indexed: the ordering pass: ") + hipGetErrorString(e)));
     }
-    const hipEvent_t key_ev[4] = {p->ev_b[3], p->ev[2], p->ev[3], p->ev[1]};  // passes A + B, passes C + D
-    if (int rc = indexed_from_cube_slots(p->device, p->num_cu, s, slots, slot_cap, 6 * Q, final_ccap, (const float*)f2.p, p->q0.p, key_ev, out_ix)) return bail(rc);
+    const hipEvent_t key_ev[4] = {p->dc_ev[3], ev[2], ev[3], ev[1]};  // passes A + B, passes C + D
+    if (int rc = indexed_from_cube_slots(p->device, p->num_cu, s, slots, slot_cap, 6 * Q, final_ccap, (const float*)f2.p, w0.q0.p, key_ev, out_ix)) return bail(rc);
     hc.n_tris = Q;
   }
   float ms = 0;
-  HIP_TRYM(hipEventElapsedTime(&ms, p->ev[0], p->ev[1]));
+  HIP_TRYM(hipEventElapsedTime(&ms, ev[0], ev[1]));
   {  // per stage (gsdf_hip_mesh_stage_ms): origin sweep, edges, normals, placement, quads
-    hipEvent_t cut[6] = {p->ev[0], p->ev_b[0], p->ev_b[1], p->ev_b[2], p->ev_b[3], p->ev[1]};
+    const hipEvent_t cut[6] = {ev[0], p->dc_ev[0], p->dc_ev[1], p->dc_ev[2], p->dc_ev[3], ev[1]};
     static const char* const names[5] = {"dc_origin", "dc_edges", "dc_normals", "dc_place", "dc_quads"};
     m->n_stages = 5;
     for (int k = 0; k < 5; k++) {
@@ -982,7 +942,7 @@ static int dc_mesh(gsdf_program* p, float res, int chiseled, int shard_rank, int
     }
   }
   {
-    static const bool dbg = [] { const char* e = getenv("GSDF_HIP_DC_DEBUG"); return e && atoi(e) != 0; }();  // developer knob
+    static const bool dbg = env_flag("GSDF_HIP_DC_DEBUG");  // developer knob
     if (dbg) fprintf(stderr, "dc: cubes %llu in %llu runs, edges %llu in %llu runs\n", (unsigned long long)n_cubes, (unsigned long long)n_cube_runs,
                      (unsigned long long)n_edges, (unsigned long long)n_edge_runs);
   }
@@ -999,7 +959,6 @@ static int dc_mesh(gsdf_program* p, float res, int chiseled, int shard_rank, int
   p->evals += m->st.evals;
   *out = m;
   return GSDF_OK;
-#undef HIP_TRYM
 }
 
 extern "C" int gsdf_hip_mesh_dualcontour(gsdf_program* p, float res, int chiseled, int shard_rank, int shard_count, void* stream,
@@ -1033,7 +992,7 @@ extern "C" int gsdf_hip_mesh_minecraft(gsdf_program* p, float res, void* stream,
   if (!(res > 0) || std::isnan(res) || std::isinf(res)) return fail(GSDF_ERR_RESOLUTION, "invalid renderer cube resolution");
   if (p->mesh_in_flight()) return fail(GSDF_ERR_BAD_ARGUMENT, "an octree mesh of this program is in flight: wait for it first (shared workspace)");
   HIP_TRY(hipSetDevice(p->device));
-  hipStream_t s = stream ? (hipStream_t)stream : p->stream;
+  hipStream_t s = stream ? (hipStream_t)stream : p->stream.s;
   // makeICube over the SDF's own bounds (dual_contour.go:298-299; glrender.go:222-235)
   const float* bb = p->prog.bb;
   const float longAxis = fmaxf(bb[3] - bb[0], fmaxf(bb[4] - bb[1], bb[5] - bb[2]));
@@ -1057,11 +1016,6 @@ extern "C" int gsdf_hip_mesh_minecraft(gsdf_program* p, float res, void* stream,
     gsdf_hip_mesh_destroy(m);
     return code;
   };
-#define HIP_TRYM(expr)                                                                                          \
-  do {                                                                                                          \
-    hipError_t _e = (expr);                                                                                     \
-    if (_e != hipSuccess) return bail(fail(GSDF_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e))); \
-  } while (0)
   HIP_TRYM(hipMalloc((void**)&d_pos, n_cubes * 48));
   HIP_TRYM(hipMalloc((void**)&d_dist, n_cubes * 16));
   HIP_TRYM(hipMalloc((void**)&d_ctr, 8));
@@ -1087,7 +1041,6 @@ extern "C" int gsdf_hip_mesh_minecraft(gsdf_program* p, float res, void* stream,
   m->st.evals = 4 * n_cubes;
   m->st.leaf_cubes = n_cubes;
   (void)hipFree(d_pos); (void)hipFree(d_dist); (void)hipFree(d_ctr);
-#undef HIP_TRYM
   *out = m;
   return GSDF_OK;
 }
@@ -1101,7 +1054,7 @@ extern "C" int gsdf_hip_mesh_flat(gsdf_program* p, float res, int shard_rank, in
   if (shard_count < 1 || shard_rank < 0 || shard_rank >= shard_count) return fail(GSDF_ERR_BAD_ARGUMENT, "bad shard rank/count");
   if (p->mesh_in_flight()) return fail(GSDF_ERR_BAD_ARGUMENT, "an octree mesh of this program is in flight: wait for it first (shared workspace)");
   HIP_TRY(hipSetDevice(p->device));
-  hipStream_t s = stream ? (hipStream_t)stream : p->stream;
+  hipStream_t s = stream ? (hipStream_t)stream : p->stream.s;
   // Reset (:36-80)
   float mn[3], mx[3];
   scale_centered(p->prog.bb, 1.01f, mn, mx);
@@ -1126,16 +1079,12 @@ extern "C" int gsdf_hip_mesh_flat(gsdf_program* p, float res, int shard_rank, in
   m->st.levels = 0; m->st.res = res;
   m->st.origin[0] = ox; m->st.origin[1] = oy; m->st.origin[2] = oz;
   auto bail = [&](int code) { gsdf_hip_mesh_destroy(m); return code; };
-#define HIP_TRYM(expr)                                                                                          \
-  do {                                                                                                          \
-    hipError_t _e = (expr);                                                                                     \
-    if (_e != hipSuccess) return bail(fail(GSDF_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e))); \
-  } while (0)
   if (ncz == 0) { *out = m; return GSDF_OK; }  // more ranks than cube planes: nothing for this one
-  for (auto& e : p->ev)
-    if (!e) HIP_TRYM(hipEventCreate(&e));
-  HIP_TRYM(p->ctr.ensure(sizeof(MeshCounters)));
-  MeshCounters* d_ctr = (MeshCounters*)p->ctr.p;
+  gsdf_program::OctreeWs& w0 = p->ws[0];  // its counters and its events serve here too (no octree mesh is in flight)
+  const EventSet<5>& ev = w0.ev;
+  HIP_TRYM(w0.ev.ensure());
+  HIP_TRYM(w0.ctr.ensure(sizeof(MeshCounters)));
+  MeshCounters* d_ctr = (MeshCounters*)w0.ctr.p;
   {
     // refuse up front what cannot fit (a failed multi-hundred-GB hipMalloc is slow and leaves the allocator fragmented)
     size_t mfree = 0, mtotal = 0;
@@ -1160,21 +1109,15 @@ extern "C" int gsdf_hip_mesh_flat(gsdf_program* p, float res, int shard_rank, in
   unsigned long long* nearbits = negbits + (size_t)wpp * nk;
   const int ek = p->batch_k();
   spec_aux(p);
-  HIP_TRYM(hipEventRecord(p->ev[0], s));
+  HIP_TRYM(hipEventRecord(ev[0], s));
   {
     const uint64_t npass = ((sxy + (uint64_t)BLOCK - 1) / (uint64_t)BLOCK) * ((nk + ek - 1) / ek);
-    static const int bpc = [] { const char* e = getenv("GSDF_HIP_EVAL_BPC"); return e ? atoi(e) : 64; }();
+    static const int bpc = env_int("GSDF_HIP_EVAL_BPC", 64);
     const uint64_t gmax = (uint64_t)p->num_cu * (uint64_t)(bpc > 0 ? bpc : 64);
     const unsigned g = (unsigned)(npass < gmax ? npass : gmax);
-    if (p->f_flat_grid) HIP_TRYM(launch_fn(p->f_flat_grid, g, BLOCK, p->lds_bytes(ek), s, (const uint32_t*)p->d_code, ox, oy, oz, res, sx, sy, c0, nk, grid, negbits, nearbits));
-#define LAUNCH_FG(KK, WW) hipLaunchKernelGGL((flat_grid_kernel<KK, WW>), dim3(g), dim3(BLOCK), p->lds_bytes(KK), s, p->d_code, ox, oy, oz, res, sx, sy, c0, nk, grid, negbits, nearbits)
-    else if (ek == 4) { if (p->sweep_waves(4) == 4) LAUNCH_FG(4, 4); else LAUNCH_FG(4, 3); }
-    else if (ek == 2) { if (p->sweep_waves(2) == 4) LAUNCH_FG(2, 4); else LAUNCH_FG(2, 3); }
-    else LAUNCH_FG(1, 4);
-#undef LAUNCH_FG
-    HIP_TRYM(hipGetLastError());
+    HIP_TRYM(launch_kernel(flat_grid_aot(p->sweep_variant(ek)), p->f_flat_grid, g, BLOCK, p->lds_bytes(ek), s, p->d_code.p, ox, oy, oz, res, sx, sy, c0, nk, grid, negbits, nearbits));
   }
-  HIP_TRYM(hipEventRecord(p->ev[1], s));
+  HIP_TRYM(hipEventRecord(ev[1], s));
   // ReadTriangles: the triangle count is not known in advance; the pass is cheap (HBM-bound over the grid), so a
   // buffer that turns out too small is replaced by one of the exact size and only this pass is repeated.
   MeshCounters hc{};
@@ -1186,10 +1129,10 @@ extern "C" int gsdf_hip_mesh_flat(gsdf_program* p, float res, int shard_rank, in
       if (!m->d_tris) { HIP_TRYM(hipMalloc((void**)&m->d_tris, want * 36)); m->cap = want; }
     }
     HIP_TRYM(hipMemsetAsync(d_ctr, 0, sizeof(MeshCounters), s));
-    HIP_TRYM(hipEventRecord(p->ev[2], s));
+    HIP_TRYM(hipEventRecord(ev[2], s));
     // default: the marching pass over the bit planes (flat_cut_scan_kernel + flat_march_list_kernel); GSDF_HIP_FLAT_STREAM=1:
     // the pass that streams the float grid (flat_march_kernel, the kernel of rounds 1-2), kept for comparison -- same triangles
-    static const bool stream_march = [] { const char* e = getenv("GSDF_HIP_FLAT_STREAM"); return e && atoi(e) != 0; }();
+    static const bool stream_march = env_flag("GSDF_HIP_FLAT_STREAM");
     if (nx >= 65536u || ny >= 65536u || (uint64_t)c0 + ncz >= 65536u)  // record coordinates are 16-bit
       return bail(fail(GSDF_ERR_RESOLUTION, "resolution too fine for the flat renderer's lattice"));
     if (stream_march) {
@@ -1197,7 +1140,7 @@ extern "C" int gsdf_hip_mesh_flat(gsdf_program* p, float res, int shard_rank, in
       if ((double)npass + 1e6 >= 4294967296.0) return bail(fail(GSDF_ERR_RESOLUTION, "resolution too fine for the flat renderer's lattice"));
       // four workgroups per CU are resident (36 KB of LDS each): a grid of exactly those, ~200 passes per wave, measured best
       // (0.63 ms; 8 per CU 0.66, 32 per CU 0.74, 6 per CU 0.82 -- the stride between a wave's passes matters)
-      static const int mbpc = [] { const char* e = getenv("GSDF_HIP_FLAT_BPC"); return e ? atoi(e) : 4; }();  // tuning knob
+      static const int mbpc = env_int("GSDF_HIP_FLAT_BPC", 4);  // tuning knob
       const uint64_t gmax = (uint64_t)p->num_cu * (uint64_t)(mbpc > 0 ? mbpc : 4);
       const uint64_t nwg = (npass + 3) / 4;
       const size_t lds = (size_t)256 * 16 + (size_t)4 * FLAT_WAVE_RECS * REC_WORDS * 4 + (size_t)4 * 5 * FLAT_WAVE_RECS * 2;
@@ -1211,8 +1154,7 @@ extern "C" int gsdf_hip_mesh_flat(gsdf_program* p, float res, int shard_rank, in
       }
       unsigned long long* list = (unsigned long long*)p->flat_list.p;
       const uint64_t npass = (((uint64_t)sx * ny + 4095u) >> 12) * ncz;  // wave passes of the scan: 4096 cubes each
-      static const int sbpc = [] { const char* e = getenv("GSDF_HIP_FLAT_SCAN_BPC"); return e ? atoi(e) : 16; }();   // tuning knobs
-      static const int lbpc = [] { const char* e = getenv("GSDF_HIP_FLAT_LIST_BPC"); return e ? atoi(e) : 6; }();
+      static const int sbpc = env_int("GSDF_HIP_FLAT_SCAN_BPC", 16), lbpc = env_int("GSDF_HIP_FLAT_LIST_BPC", 6);  // tuning knobs
       const uint64_t gmax = (uint64_t)p->num_cu * (uint64_t)(sbpc > 0 ? sbpc : 16), nwg = (npass + 3) / 4;
       hipLaunchKernelGGL(flat_cut_scan_kernel, dim3((unsigned)(nwg < gmax ? (nwg ? nwg : 1) : gmax)), dim3(BLOCK), 0, s, (const unsigned long long*)negbits,
                          (const unsigned long long*)nearbits, wpp, nx, ny, ncz, list, (uint64_t)m->cap, d_ctr);
@@ -1220,7 +1162,7 @@ extern "C" int gsdf_hip_mesh_flat(gsdf_program* p, float res, int shard_rank, in
                          (const unsigned long long*)list, (uint64_t)m->cap, nx, ny, c0, ox, oy, oz, res, m->d_tris, (uint64_t)m->cap, d_ctr);
     }
     HIP_TRYM(hipGetLastError());
-    HIP_TRYM(hipEventRecord(p->ev[3], s));
+    HIP_TRYM(hipEventRecord(ev[3], s));
     HIP_TRYM(hipMemcpyAsync(&hc, d_ctr, sizeof(hc), hipMemcpyDeviceToHost, s));
     HIP_TRYM(hipStreamSynchronize(s));
     if (hc.overflow) {
@@ -1239,8 +1181,8 @@ extern "C" int gsdf_hip_mesh_flat(gsdf_program* p, float res, int shard_rank, in
     break;
   }
   float ms_grid = 0;
-  HIP_TRYM(hipEventElapsedTime(&ms_march, p->ev[2], p->ev[3]));  // the last (successful) marching pass
-  HIP_TRYM(hipEventElapsedTime(&ms_grid, p->ev[0], p->ev[1]));
+  HIP_TRYM(hipEventElapsedTime(&ms_march, ev[2], ev[3]));  // the last (successful) marching pass
+  HIP_TRYM(hipEventElapsedTime(&ms_grid, ev[0], ev[1]));
   m->st.n_tris = hc.n_tris;
   m->st.evals = sxy * nk;  // FlatRenderer.Evaluations(): every lattice corner once
   m->st.evals_prune = 0;
@@ -1256,7 +1198,6 @@ extern "C" int gsdf_hip_mesh_flat(gsdf_program* p, float res, int shard_rank, in
   p->last_tris = hc.n_tris;
   *out = m;
   return GSDF_OK;
-#undef HIP_TRYM
 }
 
 // Pure host helper (no GPU): owner rank of the brick (x,y,z) under the multi-GPU partition that

@@ -1,5 +1,6 @@
 // abi_program.h -- the program handle and the launch helpers of the translation units that own kernels (abi_eval.hip,
 // abi_mesh.hip, abi_indexed.hip). Include after the kernel headers: the handle's LDS arithmetic uses their constants (BLOCK, TRI_STAGE, ...).
+// What the handle owns frees itself (Arena, Owned, EventSet, Stream, Modules below): gsdf_hip_program_destroy is `delete`.
 #pragma once
 #include <condition_variable>
 #include <mutex>
@@ -8,27 +9,146 @@
 
 #include "abi_host.h"
 #include "compile.h"
+#include "launch_args.h"
 #include "specialize.h"
+
+// ---- owners of device resources: each frees what it holds, none can be copied, all are no-ops on null ---------------------------
+struct NoCopy {
+  NoCopy() = default;
+  NoCopy(const NoCopy&) = delete;
+  NoCopy& operator=(const NoCopy&) = delete;
+};
+// grow-only device memory, reused by every call on the handle
+struct Arena : NoCopy {
+  void* p = nullptr;
+  size_t cap = 0;
+  ~Arena() { release(); }
+  hipError_t ensure(size_t bytes) {
+    if (bytes <= cap) return hipSuccess;
+    release();
+    size_t want = bytes + bytes / 4 + 4096;
+    hipError_t e = hipMalloc(&p, want);
+    if (e == hipSuccess) cap = want;
+    return e;
+  }
+  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+};
+// one allocation of exactly the size asked for: device memory (hipFree) or pinned host memory (hipHostFree)
+template <typename T, hipError_t (*Free)(void*)>
+struct Owned : NoCopy {
+  T* p = nullptr;
+  ~Owned() { reset(); }
+  void reset() { if (p) (void)Free((void*)p); p = nullptr; }
+};
+template <typename T> using DevPtr = Owned<T, hipFree>;
+template <typename T> using PinnedPtr = Owned<T, hipHostFree>;
+template <int N>
+struct EventSet : NoCopy {
+  hipEvent_t e[N] = {};
+  ~EventSet() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+  hipError_t ensure() {  // created at first use, kept
+    for (hipEvent_t& x : e)
+      if (!x) { hipError_t r = hipEventCreate(&x); if (r != hipSuccess) return r; }
+    return hipSuccess;
+  }
+  hipEvent_t operator[](int i) const { return e[i]; }
+};
+struct Stream : NoCopy {
+  hipStream_t s = nullptr;
+  ~Stream() { if (s) (void)hipStreamDestroy(s); }
+  hipError_t ensure() { return s ? hipSuccess : hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
+};
+// run-time modules a handle has loaded beside its first (gsdf_program::spec_mod): unloaded with the handle
+struct Modules : NoCopy {
+  std::mutex mu;  // (the builders run on whichever thread first needs a kernel: a mesher's and a host-buffer call's may meet here)
+  std::vector<hipModule_t> v;
+  ~Modules() { for (hipModule_t m : v) (void)hipModuleUnload(m); }
+  void keep(hipModule_t m) { if (m) { std::lock_guard<std::mutex> lk(mu); v.push_back(m); } }
+  void take(Modules& from) {
+    std::lock_guard<std::mutex> lk(mu);
+    v.insert(v.end(), from.v.begin(), from.v.end());
+    from.v.clear();
+  }
+};
+
+// ---- kernel variants as data ----------------------------------------------------------------------------------------------------
+// Which instantiation a launch site runs, and what it is called: the name expression the run-time compiler is handed
+// (spec_name: "leaf_eval_kernel<4, 3, true, true, false, false>") and the short form gsdf_hip_program_kernels reports
+// (short_name: "leaf_eval_kernel<4,3>"). Stored profiles and the tests compare both strings.
+struct SweepVariant {  // eval_kernel<DIM, K, W> (dim = 2 | 3); flat_grid_kernel<K, W>, dc_origin_kernel<K, W> (dim = 0)
+  int k, w;
+  std::string spec_name(const char* base, int dim = 0) const { return std::string(base) + "<" + (dim ? std::to_string(dim) + ", " : "") + std::to_string(k) + ", " + std::to_string(w) + ">"; }
+  std::string short_name(const char* base, int dim = 0) const { return std::string(base) + "<" + (dim ? std::to_string(dim) + "," : "") + std::to_string(k) + "," + std::to_string(w) + ">"; }
+};
+struct LeafVariant {  // leaf_kernel<K, W> (fused) | leaf_eval_kernel<K, W, UCUBE, NTLDS, BOTH, DZ> (kernels_octree.h)
+  bool fused;
+  int k, w;
+  bool ucube, ntlds, both, dz;
+  std::string spec_name() const {
+    const std::string kw = std::to_string(k) + ", " + std::to_string(w);
+    if (fused) return "leaf_kernel<" + kw + ">";
+    auto b = [](bool x) { return x ? ", true" : ", false"; };
+    return "leaf_eval_kernel<" + kw + b(ucube) + b(ntlds) + b(both) + b(dz) + ">";
+  }
+  std::string short_name() const {
+    return std::string(fused ? "leaf_kernel<" : "leaf_eval_kernel<") + std::to_string(k) + "," + std::to_string(w) + (both ? ",both" : "") + (dz ? ",rows" : "") + ">";
+  }
+};
+struct LeafPick { LeafVariant v; hipFunction_t f; };  // f: the handle's per-tree build of v; null: the ahead-of-time kernel of v
+
+// Leaf phase: two kernels by default (leaf_eval_kernel: evaluation + cut-leaf records, no barrier and no atomic in its
+// loop; march_records_kernel: marching cubes over the records); GSDF_HIP_FUSED_LEAF=1 keeps the fused leaf_kernel.
+inline bool fused_leaf() {
+  static const bool f = env_flag("GSDF_HIP_FUSED_LEAF");
+  return f;
+}
 
 struct gsdf_program {
   gsdf_dev::Program prog;
   int device = 0;
-  uint32_t* d_code = nullptr;
-  hipStream_t stream = nullptr;
-  hipStream_t stream_b = nullptr;  // the octree mesher's second chain in flight (created on first use)
-  hipStream_t stream_c = nullptr;  // its third
+  Stream stream;  // (declared ahead of everything that ran on it: destroyed last)
+  // Workspace of one octree mesh in flight, grow-only, reused by every gsdf_hip_mesh_octree call that gets the slot. Slot 0 runs on
+  // the handle's stream, slots 1 and 2 on streams of their own (created on first use): gsdf_hip_mesh_octree_start.
+  // Three chains: measured at npt-flange resdiv 1600 with one, two, three, four and six meshes in flight (tools/gpu_pipe_depth.py,
+  // round 6): 0.452, 0.365-0.369, 0.340, 0.374, 0.358 ms per mesh -- a third chain fills what two leave idle around the evaluating
+  // kernel (the five dependent launches of the centre tests, the marching kernel's latency-bound passes), a fourth only adds contention.
+  struct OctreeWs {
+    Stream own;
+    Arena q0, q1;     // the two cube queues the descent alternates between
+    Arena ctr;        // MeshCounters, then the group sums of the two-kernel leaf phase (one clear covers both)
+    Arena spec_pass;  // the speculative top: pass bytes, statistics rows, brick masks
+    Arena rec, hdr;   // cut-leaf records and block headers of the two-kernel leaf phase
+    Arena grp;        // payload = records: scanned group sums
+    EventSet<5> ev;   // chain start, descent done, leaf phase done, evaluating kernel done, counters on the host
+    bool job_busy = false;
+    hipStream_t job_stream = nullptr;
+  };
+  static constexpr int kJobs = 3;
+  OctreeWs ws[kJobs];  // dual contouring and the flat renderer use ws[0].q0, .ctr and .ev too (they refuse to run beside an octree mesh)
+  bool mesh_in_flight() const { for (const OctreeWs& w : ws) if (w.job_busy) return true; return false; }
+  DevPtr<uint32_t> d_code;
   std::atomic<uint64_t> evals{0};  // (atomic: host-buffer calls of several threads and a mesher may count at the same time)
   // staging for the host-buffer API
-  void* d_pos = nullptr;
-  float* d_dist = nullptr;
+  DevPtr<void> d_pos;
+  DevPtr<float> d_dist;
   size_t cap_pos_bytes = 0, cap_dist = 0;
-  // pinned, device-mapped host staging for small host-buffer calls (the reference's callers hand over <= 32768 points)
-  void* h_pos = nullptr;   // (slot 0 of the staging slots below; kept for the struct's older users)
-  float* h_dist = nullptr;
   // Staging slots of the host-buffer API: pinned, device-mapped position / distance buffers with a stream each, so that
   // several host threads (glrender.FlatRenderer evaluates from numParallel goroutines, flatrenderer.go:120-129) -- or one
   // caller pipelining gsdf_hip_eval3_submit / gsdf_hip_eval_wait -- have calls in flight at the same time.
-  struct Slot { void* h_pos = nullptr; float* h_dist = nullptr; hipStream_t s = nullptr; bool busy = false; bool waiting = false; unsigned gen = 0; float* user_dist = nullptr; size_t n = 0; bool zero_copy = false; unsigned* h_flag = nullptr; unsigned* d_flag = nullptr; unsigned flag_val = 0; bool flagged = false; };  // gen: bumped at every acquisition; a ticket is slot | gen << 8, so a stale or repeated wait is refused instead of releasing somebody else's call
+  struct Slot : NoCopy {
+    Stream s;
+    PinnedPtr<void> h_pos;
+    PinnedPtr<float> h_dist;
+    bool busy = false, waiting = false;
+    unsigned gen = 0;  // bumped at every acquisition; a ticket is slot | gen << 8, so a stale or repeated wait is refused instead of releasing somebody else's call
+    float* user_dist = nullptr;
+    size_t n = 0;
+    bool zero_copy = false;
+    PinnedPtr<unsigned> h_flag;
+    unsigned* d_flag = nullptr;
+    unsigned flag_val = 0;
+    bool flagged = false;
+  };
   // h_flag / d_flag: a word of pinned, device-mapped memory the stream writes flag_val into behind the kernel (completion by
   // polling: a blocking call of 4 096 points is 26 us through hipStreamSynchronize, of which the kernel is a few)
   static constexpr int kSlots = 4;
@@ -37,40 +157,24 @@ struct gsdf_program {
   std::condition_variable slot_cv;
   std::atomic<uint64_t> evals_host{0};
   int num_cu = 256;
-  // mesher workspace, grow-only, reused by every gsdf_hip_mesh_octree call on this handle
-  struct Arena {
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes) {
-      if (bytes <= cap) return hipSuccess;
-      if (p) (void)hipFree(p);
-      p = nullptr; cap = 0;
-      size_t want = bytes + bytes / 4 + 4096;
-      hipError_t e = hipMalloc(&p, want);
-      if (e == hipSuccess) cap = want;
-      return e;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-  } q0, q1, ctr, spec_pass, dc_tile, dc_grid, dc_dist, dc_fv, dc_nrm, dc_edge, dc_erun, dc_flag, dc_ix, dc_ix_sort, flat_grid, flat_bits, flat_list, rec, hdr, grp, b_q0, b_q1, b_ctr, b_spec_pass, b_rec, b_hdr, b_grp, c_q0, c_q1, c_ctr, c_spec_pass, c_rec, c_hdr, c_grp;  // b_* / c_*: the octree mesher's second and third workspace (its further chains in flight run on stream_b / stream_c, beside the first: gsdf_hip_mesh_octree_start)  // flat_bits: sign and near-surface bit planes of the flat renderer's lattice (flat_grid_kernel -> flat_cut_scan_kernel), flat_list: the cut cubes (-> flat_march_list_kernel)  // rec / hdr: cut-leaf records and block headers of the two-kernel leaf phase (the group sums follow the counters in ctr)  // dc_*: dual contouring workspace (index grid: 4 B per lattice cell; dc_ix, dc_ix_sort: the indexed quad stage, kernels_dc_indexed.h); flat_grid: FlatRenderer distances
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  hipEvent_t ev_b[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // second set: the octree mesher has up to three chains in flight (gsdf_hip_mesh_octree_start)
-  hipEvent_t ev_c[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // third set
-  // Three chains: measured at npt-flange resdiv 1600 with one, two, three, four and six meshes in flight (tools/gpu_pipe_depth.py,
-  // round 6): 0.452, 0.365-0.369, 0.340, 0.374, 0.358 ms per mesh -- a third chain fills what two leave idle around the evaluating
-  // kernel (the five dependent launches of the centre tests, the marching kernel's latency-bound passes), a fourth only adds contention.
-  static constexpr int kJobs = 3;
-  bool job_busy[kJobs] = {false, false, false};
-  hipStream_t job_stream[kJobs] = {nullptr, nullptr, nullptr};
-  bool mesh_in_flight() const { return job_busy[0] || job_busy[1] || job_busy[2]; }
-  void* h_ctr = nullptr;  // pinned host copy of the device counters (a pageable destination makes the D2H copy a staged, blocking one)
+  // dual contouring workspace (index grid: 4 B per lattice cell)
+  Arena dc_tile, dc_grid, dc_dist, dc_fv, dc_nrm, dc_edge, dc_erun, dc_flag;
+  Arena dc_ix, dc_ix_sort;  // its indexed quad stage (kernels_dc_indexed.h)
+  EventSet<4> dc_ev;        // its stage marks: origin sweep, edges, normals, placement done
+  Arena flat_grid;          // FlatRenderer distances
+  Arena flat_bits;          // sign and near-surface bit planes of the flat renderer's lattice (flat_grid_kernel -> flat_cut_scan_kernel)
+  Arena flat_list;          // the cut cubes (-> flat_march_list_kernel)
+  PinnedPtr<void> h_ctr;  // pinned host copy of the device counters (a pageable destination makes the D2H copy a staged, blocking one)
   uint64_t last_tris = 0;  // triangle count of the previous mesh on this handle: sizes the next output buffer
   uint64_t last_recs = 0;  // cut leaves of the previous mesh with payload = records: sizes the next payload buffer
   uint64_t rec_blocks = 0;  // 64-leaf blocks the cut-leaf record arena is sized for (0: first mesh, start with kRecBlocks0)
   uint64_t last_dc_cubes = 0;  // kept cubes of the previous dual contouring pass: sizes the next queues
-  // run-time specialised kernels for this program (gsdf_hip_program_specialize): hiprtc module, else interpreter
-  hipModule_t spec_mod = nullptr, spec_mod2 = nullptr, spec_mod3 = nullptr, spec_mod4 = nullptr;  // spec_mod4: leaf kernel rebuilt with a larger register budget; spec_mod2: second group, built on first use (see spec_aux); spec_mod3: eval kernel rebuilt for 3 workgroups per CU
+  // run-time specialised kernels for this program (gsdf_hip_program_specialize): hiprtc module, else interpreter. spec_mod, the
+  // first group's module, being non-null means "specialised"; every later module (the eval kernel rebuilt for 3 workgroups per CU,
+  // the leaf kernel rebuilt with a larger register budget, the groups built on first use below) is kept in mods.
+  hipModule_t spec_mod = nullptr;
+  Modules mods;
   hipFunction_t f_eval_k1 = nullptr;  // eval_kernel<D, 1, 4>: one point per lane, for host-mapped calls (abi_eval.hip: eval_dev, spec_eval_k1)
-  hipModule_t spec_mod_k1 = nullptr;
   bool spec_k1_tried = false;
   hipFunction_t f_eval = nullptr, f_prune = nullptr, f_prune_spec = nullptr, f_leaf = nullptr;
   hipFunction_t f_dc_block_test = nullptr;  // the interval test of dual contouring's origin sweep, block by block (kernels_dc.h: dc_block_test_kernel)
@@ -79,30 +183,25 @@ struct gsdf_program {
   int spec_eval_k = 0, spec_eval_w = 0, spec_leaf_k = 0, spec_leaf_w = 0;
   bool spec_leaf_both = false;  // the specialised leaf kernel has both column passes in one body (kernels_octree.h: BOTH)
   // distinct z rows (gsdf_mesh_opts.share_corners = 2; kernels_octree.h: DZ): built the first time a mesh asks for it (spec_leaf_dz)
-  hipModule_t spec_mod_dz = nullptr;
   hipFunction_t f_leaf_dz = nullptr;
   bool spec_dz_tried = false, spec_leaf_dz_both = false;
   int spec_leaf_dz_w = 0;
   // distinct lattice points (share_corners = 1; kernels_octree.h: leaf_dense_kernel): likewise built on first use (spec_leaf_dense)
-  hipModule_t spec_mod_dense = nullptr;
   hipFunction_t f_leaf_dense = nullptr;
   bool spec_dense_tried = false;
   int spec_leaf_dense_w = 0;
   size_t lds_dense() const { return (size_t)(prog.nslots * 4 > 8 ? prog.nslots * 4 : 8) * BLOCK * sizeof(float) + 256 + 4 * 512 * sizeof(float) + 4 * 24 * sizeof(float) + 16; }
   // the UI's view (kernels_view.h: view_kernel<REFILL>, <plain>) for a specialised handle: built on its first frame (spec_view)
-  hipModule_t spec_mod_view = nullptr;
   hipFunction_t f_view = nullptr, f_view_plain = nullptr;
   bool spec_view_tried = false;
   // the projection of mesh vertices onto the field (kernels_project.h: project_kernel) for a specialised handle: built on its first
   // projection (spec_project)
-  hipModule_t spec_mod_project = nullptr;
   hipFunction_t f_project = nullptr;
   bool spec_project_tried = false;
-  void* proj_ctr = nullptr;                          // its counters on the device and the two events around its launch: made at the
-  hipEvent_t ev_proj[2] = {nullptr, nullptr};        // first projection, kept for the next (project_dev)
+  DevPtr<void> proj_ctr;  // its counters on the device and the two events around its launch: made at the
+  EventSet<2> ev_proj;    // first projection, kept for the next (project_dev)
   // the 2-D picture (kernels_image.h: image2_color_kernel<K, kind> per conversion kind) for a specialised handle: built on its first
   // gsdf_hip_image2_color (spec_image_color)
-  hipModule_t spec_mod_imgc = nullptr;
   hipFunction_t f_imgc[4] = {nullptr, nullptr, nullptr, nullptr};
   bool spec_imgc_tried = false;
   double spec_compile_s = 0;
@@ -116,15 +215,53 @@ struct gsdf_program {
   std::string spec_async_err;
   std::string spec_compiler;  // hipcc | hiprtc | cache: what built the specialised kernels
   std::string spec_key;       // key of that build (specialize.cpp: build_key)
+  // A build under way finishes first (its thread writes into this handle), then the shadow handle goes; the members free
+  // themselves in reverse order of declaration: modules, events, device and pinned memory, the streams last.
+  ~gsdf_program() {
+    if (spec_thread.joinable()) spec_thread.join();
+    delete spec_shadow;
+    if (spec_mod) (void)hipModuleUnload(spec_mod);
+  }
   // leaf kernel batching: K = 4 while 3 workgroups still fit the CU's LDS (<= 11 slots); 12..15 slots run K = 2 at 4
   // waves/SIMD instead of K = 4 at 2 (knurled-cylinder: 23.3 vs 23.8 ms). A 4th wave per SIMD is worth more than the
   // ~30 VGPRs it costs (flange 3.28 -> 2.95 ms), but only if 4 workgroups fit the CU's 160 KB of LDS.
-  void leaf_config(int* k, int* w, size_t* lds) const;
-  bool leaf_nt_in_lds() const {  // see leaf_config
+  struct LeafConfig { int k, w; size_t lds; bool ntlds; };
+  LeafConfig leaf_config() const {
+    static const int forced_w = env_int("GSDF_HIP_LEAF_WAVES", 0);  // tuning knob
+    const bool fused = fused_leaf();
     const int ns = prog.nslots > 0 ? prog.nslots : 1;
     const int lk = (batch_k() == 4 && ns > 11) ? 2 : batch_k();
+    // The evaluating kernel needs the interpreter's columns only (8 rows at least: a brick's distances) + the 256-byte
+    // triangles-per-case table, unless it is exactly that table which would cost the fourth workgroup per CU (40 rows = 40 KB): the
+    // kernel then reads the counts from the table in global memory. The fused kernel adds its stages to LEAF_MIN_COLS columns.
     const size_t rows_e = (size_t)(ns * lk > 8 ? ns * lk : 8) * BLOCK * sizeof(float);
-    return !(4 * rows_e <= 160 * 1024 && 4 * (rows_e + 256) > 160 * 1024);
+    const bool ntlds = !(4 * rows_e <= kLdsPerCu && 4 * (rows_e + 256) > kLdsPerCu);
+    const size_t lds = fused ? (size_t)(ns * lk > LEAF_MIN_COLS ? ns * lk : LEAF_MIN_COLS) * BLOCK * sizeof(float) + 4096 + TRI_STAGE * 36 + 64
+                             : rows_e + (ntlds ? 256 : 0);
+    int w = forced_w ? forced_w : (4 * lds <= kLdsPerCu ? 4 : 3);
+    if (lk == 4) { if (w != 2 && w != 4 && !(!fused && w == 5 && 5 * lds <= kLdsPerCu)) w = 3; }
+    else if (lk == 2) { if (w != 4) w = 3; }
+    else w = 4;
+    return {lk, w, lds, ntlds};
+  }
+  // Ahead-of-time (interpreter) leaf kernels exist only at occupancies the compiler reaches WITHOUT scratch
+  // (tests/test_kernel_resources.py reads the shipped code object): at 4 workgroups per CU (128 VGPRs) the K = 4 and
+  // K = 2 interpreter builds spill, and a spilling build is not trusted (see fn_scratch_bytes).
+  static int leaf_aot_waves(int k, int w) { return k == 4 ? (w == 2 ? 2 : 3) : (k == 2 ? 3 : 4); }
+  // What the leaf phase of a mesh launches whose last level of cubes is lq (3 for meshes of three levels or more: a wave pass is one
+  // level-3 cube -- column bricks, scalar prefetched cube load -- its case-count table in LDS unless that costs a workgroup per CU;
+  // else a few leaves: occupancy is no concern, table in LDS). rows: share_corners = 2 asks for the distinct z rows of a brick once
+  // each (kernels_octree.h: DZ); a specialised handle without a scratch-free build of that form evaluates every row through its
+  // specialised kernel (v.dz comes back false). The per-tree kernel is the same launch whichever W it was built for.
+  LeafPick leaf_pick(int lq, bool rows = false) const {
+    const LeafConfig c = leaf_config();
+    const bool spec = f_leaf && spec_leaf_k == c.k;
+    const int aw = leaf_aot_waves(c.k, c.w);
+    if (fused_leaf()) return spec ? LeafPick{{true, c.k, spec_leaf_w, false, false, false, false}, f_leaf} : LeafPick{{true, c.k, aw, false, false, false, false}, nullptr};
+    if (rows && f_leaf_dz) return {{false, 4, spec_leaf_dz_w, true, c.ntlds, spec_leaf_dz_both, true}, f_leaf_dz};
+    if (rows && !spec) return {{false, 4, aw, true, c.ntlds, false, true}, nullptr};
+    if (spec && lq == 3) return {{false, c.k, spec_leaf_w, true, c.ntlds, spec_leaf_both, false}, f_leaf};
+    return {{false, c.k, aw, lq == 3, lq == 3 ? c.ntlds : true, false, false}, nullptr};
   }
   size_t lds_bytes(int k = 1) const { return (size_t)(prog.nslots > 0 ? prog.nslots : 1) * k * BLOCK * sizeof(float); }
   // The largest trees (gsdf_hip.h: "Largest trees"). A workgroup may ask for a CU's whole LDS and no more; an entry point whose
@@ -147,60 +284,39 @@ struct gsdf_program {
                 "gsdf_hip.h: GSDF_HIP_MAX_SLOTS_CREATE is the largest slot count gsdf_hip_program_create accepts");
   // dual contouring's origin sweep: the ahead-of-time builds are <4,3>, <2,3>, <1,4> (the others need scratch). One rule for the
   // launch (abi_mesh.hip: dc_mesh) and for the name gsdf_hip_program_kernels reports.
-  static int dc_origin_waves(int k) { return k == 1 ? 4 : 3; }
+  static SweepVariant dc_origin_variant(int k) { return {k, k == 1 ? 4 : 3}; }
   // Workgroups per CU the lattice/eval sweeps are compiled for (their W template argument): 4 when the LDS allows it.
   int sweep_waves(int k) const {
-    static const int forced = [] { const char* e = getenv("GSDF_HIP_SWEEP_WAVES"); return e ? atoi(e) : 0; }();  // tuning / debugging knob
+    static const int forced = env_int("GSDF_HIP_SWEEP_WAVES", 0);  // tuning / debugging knob
     if (k != 1 && (forced == 3 || forced == 4)) return forced;
-    return (k == 1 || 4 * (lds_bytes(k) + 64) <= (size_t)160 * 1024) ? 4 : 3;
+    return (k == 1 || 4 * (lds_bytes(k) + 64) <= kLdsPerCu) ? 4 : 3;
   }
+  SweepVariant sweep_variant(int k) const { return {k, sweep_waves(k)}; }
   // Points carried per lane: as many as keep >= 2 workgroups per CU resident (160 KB LDS per CU).
   int batch_k() const {
-    static const int forced = [] { const char* e = getenv("GSDF_HIP_BATCH_K"); return e ? atoi(e) : 0; }();  // tuning knob
+    static const int forced = env_int("GSDF_HIP_BATCH_K", 0);  // tuning knob
     if (forced == 1 || forced == 2 || forced == 4) return forced;
     return prog.nslots <= 12 ? 4 : (prog.nslots <= 28 ? 2 : 1);
   }
 };
 
-// Leaf phase: two kernels by default (leaf_eval_kernel: evaluation + cut-leaf records, no barrier and no atomic in its
-// loop; march_records_kernel: marching cubes over the records); GSDF_HIP_FUSED_LEAF=1 keeps the fused leaf_kernel.
-inline bool fused_leaf() {
-  static const bool f = [] { const char* e = getenv("GSDF_HIP_FUSED_LEAF"); return e && atoi(e) != 0; }();
-  return f;
-}
-
-inline void gsdf_program::leaf_config(int* k, int* w, size_t* lds) const {
-  if (!fused_leaf()) {  // the evaluating kernel needs the interpreter's columns only
-    static const int forced_w = [] { const char* e = getenv("GSDF_HIP_LEAF_WAVES"); return e ? atoi(e) : 0; }();  // tuning knob
-    const int ns = prog.nslots > 0 ? prog.nslots : 1;
-    const int lk = (batch_k() == 4 && ns > 11) ? 2 : batch_k();
-    // (8 rows at least: a brick's distances) + the 256-byte triangles-per-case table, unless it is exactly that table which
-    // would cost the fourth workgroup per CU (40 rows = 40 KB): the kernel then reads the counts from the table in global memory
-    const size_t rows_e = (size_t)(ns * lk > 8 ? ns * lk : 8) * BLOCK * sizeof(float);
-    const size_t lds_e = rows_e + (leaf_nt_in_lds() ? 256 : 0);
-    int ww = forced_w ? forced_w : (4 * lds_e <= 160 * 1024 ? 4 : 3);
-    if (lk == 4) { if (ww != 2 && ww != 4 && !(ww == 5 && 5 * lds_e <= 160 * 1024)) ww = 3; }
-    else if (lk == 2) { if (ww != 4) ww = 3; }
-    else ww = 4;
-    *k = lk; *w = ww; *lds = lds_e;
-    return;
-  }
-  static const int forced_w = [] { const char* e = getenv("GSDF_HIP_LEAF_WAVES"); return e ? atoi(e) : 0; }();  // tuning knob
-  const int ns = prog.nslots;
-  const int lk = (batch_k() == 4 && ns > 11) ? 2 : batch_k();
-  const size_t lds_m = (size_t)(ns * lk > LEAF_MIN_COLS ? ns * lk : LEAF_MIN_COLS) * BLOCK * sizeof(float) + 4096 + TRI_STAGE * 36 + 64;
-  int ww = forced_w ? forced_w : (4 * lds_m <= 160 * 1024 ? 4 : 3);
-  if (lk == 4) { if (ww != 2 && ww != 4) ww = 3; }
-  else if (lk == 2) { if (ww != 4) ww = 3; }
-  else ww = 4;
-  *k = lk; *w = ww; *lds = lds_m;
-}
-
-// hipModuleLaunchKernel with typed arguments (the specialised kernels take exactly the ahead-of-time kernels' parameters)
-template <typename... A>
-static hipError_t launch_fn(hipFunction_t f, unsigned grid, unsigned block, size_t lds, hipStream_t s, A... a) {
-  void* args[] = {(void*)&a...};
+// One launch path for the kernels that exist twice: `aot`, the ahead-of-time (interpreter) kernel, gives the parameter types
+// P...; `f` is the handle's per-tree build with the same parameters, launched instead when there is one. Every argument is
+// converted to the kernel's own parameter type, whatever the type of the expression at the call (launch_args.h). aot may be a
+// null pointer of the right type where no ahead-of-time build of the variant exists: without f that is an error, not a launch.
+inline hipError_t launch_fn(hipFunction_t f, unsigned grid, unsigned block, size_t lds, hipStream_t s, void** args) {
   return hipModuleLaunchKernel(f, grid, 1, 1, block, 1, 1, (unsigned)lds, s, args, nullptr);
+}
+template <typename... P, typename... A>
+inline hipError_t launch_kernel(void (*aot)(P...), hipFunction_t f, unsigned grid, unsigned block, size_t lds, hipStream_t s, const A&... a) {
+  static_assert(launch_args::accepts<void(P...), const A&...>::value, "kernel launch: argument count or types do not fit the kernel's signature");
+  if (f) {
+    launch_args::Marshalled<void(P...)> m(a...);
+    return launch_fn(f, grid, block, lds, s, m.args());
+  }
+  if (!aot) return hipErrorInvalidDeviceFunction;
+  hipLaunchKernelGGL(aot, dim3(grid), dim3(block), lds, s, static_cast<P>(a)...);
+  return hipGetLastError();
 }
 
 inline unsigned grid_for(uint64_t n, int num_cu, int blocks_per_cu) {
