@@ -1,0 +1,108 @@
+#!/usr/bin/env python3
+"""Vector outlines traced on the GPU, written as SVG: the curve a laser cutter or plotter takes for a 2-D part, and the contours a
+slicer wants of a 3-D part at each layer height:
+
+    python examples/render_svg.py text -o text.svg                             # the 2-D scenes of render_png.py: image, text, thread
+    python examples/render_svg.py npt-flange --slice 5 -o flange.svg           # one contour of a 3-D scene (npt-flange, bolt) at z = 5
+    python examples/render_svg.py bolt --layer-height 2 --report -o bolt.svg   # every layer of thickness 2, with a report
+
+The lattice spacing is the diagonal of the part's bounds / --resdiv (default 400), or --res. Every layer is one even-odd <path>:
+outer boundaries counter-clockwise, holes clockwise. --report prints loops, vertices, outer and hole counts and the area of every
+layer, and the device time of the two stages (evaluation, tracing). The SVG is written with the standard library only."""
+import argparse
+import importlib.util
+import math
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+SCENES_2D = ("image", "text", "thread")
+SCENES_3D = ("npt-flange", "bolt")
+
+
+def scene(name):
+    """The 2-D scenes are render_png.py's; the 3-D ones the scaffold's benchmark scenes."""
+    if name in SCENES_2D:
+        spec = importlib.util.spec_from_file_location("render_png", os.path.join(ROOT, "examples", "render_png.py"))
+        mod = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+        return mod.scene(name)
+    from scaffold.builder import Builder
+    return Builder().Scene(name)
+
+
+def spacing(bb, is3d, resdiv):
+    """The default lattice spacing: the diagonal of the bounds (xy for a 2-D part) / resdiv, float32."""
+    import numpy as np
+    return np.float32(math.sqrt(sum(float(bb[a + 3] - bb[a]) ** 2 for a in ((0, 1, 2) if is3d else (0, 1)))) / resdiv)
+
+
+def trace(hip, sdf, res, z=None):
+    """A ContourHIP of `sdf`: its outline (2-D) or its slices at the heights z (3-D)."""
+    return hip.ContourHIP.outline(sdf, res) if sdf.is2d else hip.ContourHIP.slices(sdf, res, z)
+
+
+def report(c, z=None):
+    import numpy as np
+    st = c.stats
+    areas = c.areas()
+    lines = [f"lattice {st.nx} x {st.ny} x {st.n_layers} layers = {st.evals} evaluations; {st.n_loops} loops, {st.n_verts} vertices, "
+             f"{st.saddle_cells} saddle cells, {st.nonfinite_nodes} non-finite nodes, {st.border_inside} forced outside; {st.rank_rounds} ranking rounds",
+             f"device time {st.ms_device:.3f} ms = evaluation {st.ms_eval:.3f} + tracing {st.ms_trace:.3f} "
+             f"({st.evals / max(st.ms_eval, 1e-9) / 1e6:.1f} G evaluations/s in the evaluation stage)"]
+    for k in range(c.n_layers):
+        a = areas[c.loop_layer == k]
+        n = int(sum(c.loop_start[q + 1] - c.loop_start[q] for q in range(c.n_loops) if c.loop_layer[q] == k))
+        at = "" if z is None else f" z = {float(np.float32(z[k])):.6g}:"
+        lines.append(f"layer {k}:{at} {len(a)} loops ({int((a > 0).sum())} outer, {int((a < 0).sum())} holes), {n} vertices, area {a.sum():.6g}")
+    return "\n".join(lines)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("scene", choices=SCENES_2D + SCENES_3D)
+    ap.add_argument("--res", type=float, default=None, help="lattice spacing (default: diagonal of the bounds / --resdiv)")
+    ap.add_argument("--resdiv", type=float, default=400.0)
+    ap.add_argument("--slice", type=float, default=None, metavar="Z", help="3-D scenes: one contour at this height")
+    ap.add_argument("--layer-height", type=float, default=None, metavar="H", help="3-D scenes: a contour at the middle of every layer of this thickness")
+    ap.add_argument("--report", action="store_true")
+    ap.add_argument("--interpreter", action="store_true", help="skip the per-tree kernel build")
+    ap.add_argument("-o", "--output", default=None)
+    args = ap.parse_args(argv)
+
+    import numpy as np
+    from gsdf_amd import hip, svg
+
+    is3d = args.scene in SCENES_3D
+    if is3d == (args.slice is None and args.layer_height is None) or (args.slice is not None and args.layer_height is not None):
+        ap.error("a 3-D scene takes --slice Z or --layer-height H; a 2-D scene takes neither")
+    hip.init(0)
+    t0 = time.perf_counter()
+    s = scene(args.scene)
+    sdf = (hip.SDF3HIP if is3d else hip.SDF2HIP)(s)
+    if not args.interpreter:
+        sdf.specialize()
+    bb = sdf.Bounds()
+    res = np.float32(args.res) if args.res is not None else spacing(bb, is3d, args.resdiv)
+    z = None
+    if is3d:
+        z = np.array([args.slice], np.float32) if args.slice is not None else hip.layer_heights(bb, args.layer_height)
+        if len(z) == 0:
+            ap.error("no layer of that thickness has its middle inside the part")
+    t1 = time.perf_counter()
+    c = trace(hip, sdf, res, z)
+    t2 = time.perf_counter()
+    out = args.output or f"{args.scene}.svg"
+    svg.write_svg(out, [c.loops(k) for k in range(c.n_layers)], z=z)
+    print(f"{args.scene} res {float(res):.6g}: setup {t1 - t0:.2f} s, contours {(t2 - t1) * 1e3:.1f} ms (the first call includes the kernels' build); "
+          f"{c.n_loops} loops, {c.n_verts} vertices in {c.n_layers} layer(s); written to {out}")
+    if args.report:
+        print(report(c, z))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

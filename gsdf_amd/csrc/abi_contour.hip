@@ -1,0 +1,271 @@
+// abi_contour.hip -- C ABI (include/gsdf_hip.h, section "contours"): the outline of a 2-D part and the z-slices of a 3-D part as
+// ordered closed loops, traced on the device. The gsdf_contour handle, gsdf_hip_contour2 / gsdf_hip_slice3, counts / read / stats.
+// Kernels: kernels_contour.h. The distances come from the program's own Evaluate (gsdf_hip_eval2_dev / gsdf_hip_eval3_dev:
+// interpreter or per-tree kernels, whichever the handle has); no interpreter kernel is compiled here.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <deque>
+#include <memory>
+#include <new>
+#include <vector>
+
+#include "kernels_common.h"
+#include "kernels_contour.h"
+#include "abi_program.h"
+
+struct gsdf_contour {
+  int device = 0;
+  uint64_t n_loops = 0, n_verts = 0;
+  DevPtr<float> xy;
+  DevPtr<unsigned> keys, loop_start, loop_layer;  // loop_start: n_loops + 1
+  gsdf_contour_stats st{};
+};
+
+extern "C" void gsdf_hip_contour_destroy(gsdf_contour* c) {
+  if (!c) return;
+  (void)hipSetDevice(c->device);
+  delete c;
+}
+
+namespace {
+struct ContourDelete { void operator()(gsdf_contour* c) const { gsdf_hip_contour_destroy(c); } };
+using ContourPtr = std::unique_ptr<gsdf_contour, ContourDelete>;
+
+#define LAUNCH(KERNEL, GRID, STREAM, ...)                                          \
+  do {                                                                             \
+    hipLaunchKernelGGL(KERNEL, dim3(GRID), dim3(BLOCK), 0, STREAM, __VA_ARGS__);   \
+    HIP_TRY(hipGetLastError());                                                    \
+  } while (0)
+
+unsigned blocks_of(uint64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
+
+template <typename T>
+bool dev_alloc(DevPtr<T>& b, uint64_t n) {
+  b.reset();
+  if (hipMalloc((void**)&b.p, (n ? n : 1) * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); b.p = nullptr; return false; }
+  return true;
+}
+
+// nodes along one axis (gsdf_hip.h, "Lattice"): floor(fl(fl(hi - lo) / res)) + 4; 0 for a count that cannot be a lattice's
+uint64_t axis_nodes(float lo, float hi, float res) {
+  const float size = hi - lo;
+  const float q = size / res;
+  if (!(q >= 0.f)) return 4;  // (an empty or inverted box: the ring of outside cells alone)
+  if (!(q < 2147483648.f)) return 0;
+  return (uint64_t)std::floor(q) + 4;
+}
+
+unsigned ceil_log2(uint64_t n) {
+  unsigned r = 0;
+  while (((uint64_t)1 << r) < n) r++;
+  return r;
+}
+
+// the loops of one chunk of whole layers, still on the device
+struct Part {
+  uint64_t n_verts = 0, n_loops = 0;
+  DevPtr<float> xy;
+  DevPtr<unsigned> keys, loop_start, loop_layer;
+};
+
+// what every chunk of a call shares: node-sized buffers for the largest chunk, vertex-sized ones that grow
+struct Workspace {
+  DevPtr<float> pos, dist, z;
+  DevPtr<unsigned> succ, blk_cnt, blk_base, layer_base;
+  DevPtr<unsigned long long> totals;  // [0] cut edges, [1] loops, [2] vertices of the loops
+  DevPtr<ContourCounters> ctr;
+  Arena verts;  // nine arrays of V words
+  Arena blk;    // four arrays of blocks_of(V) words
+  EventSet<7> ev;
+};
+
+int contour_run(gsdf_program* p, int dim, float res, const float* z, uint32_t n_z, const gsdf_contour_opts* o, gsdf_contour** out) {
+  if (!p || !out) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  *out = nullptr;
+  if (p->prog.is2d != (dim == 2)) return fail(GSDF_ERR_DIMENSION, dim == 2 ? "program is 3D, contour2 called" : "program is 2D, slice3 called");
+  if (dim == 3 && (!z || n_z == 0)) return fail(GSDF_ERR_BAD_ARGUMENT, "slice3 needs at least one z");
+  const float* bb = p->prog.bb;
+  if (!std::isfinite(res) || !(res > 0.f)) return fail(GSDF_ERR_BAD_ARGUMENT, "contour: res must be finite and positive");
+  for (int a = 0; a < 6; a++)
+    if (a % 3 != 2 && !std::isfinite(bb[a])) return fail(GSDF_ERR_BAD_ARGUMENT, "contour: the program's bounds are not finite");
+  const uint64_t nx = axis_nodes(bb[0], bb[3], res), ny = axis_nodes(bb[1], bb[4], res);
+  if (nx == 0 || ny == 0 || nx * ny >= ((uint64_t)1 << 31)) return fail(GSDF_ERR_BAD_ARGUMENT, "contour: the lattice needs 2^31 nodes or more at this res");
+  const uint64_t N = nx * ny, E = 2 * N, L = dim == 2 ? 1 : n_z;
+  ContourLattice lat{(unsigned)nx, (unsigned)ny, bb[0] - res, bb[1] - res, res};
+  // layers per chunk: max_nodes nodes, at least one layer, and slots (layer * E + key) below 2^32
+  uint64_t max_nodes = o && o->max_nodes ? o->max_nodes : (uint64_t)GSDF_CONTOUR_DEFAULT_MAX_NODES;
+  uint64_t per_chunk = max_nodes / N;
+  if (per_chunk < 1) per_chunk = 1;
+  if (per_chunk > (((uint64_t)1 << 31) - 1) / N) per_chunk = (((uint64_t)1 << 31) - 1) / N;
+  if (per_chunk > L) per_chunk = L;
+
+  HIP_TRY(hipSetDevice(p->device));
+  spec_adopt(p);
+  hipStream_t s = p->stream.s;
+  std::deque<Part> parts;  // (ahead of the handle and the workspace; all of them outlive the work on s: every way out below has waited for it)
+  Workspace w;
+  ContourPtr c(new (std::nothrow) gsdf_contour());
+  if (!c) return fail(GSDF_ERR_BAD_ARGUMENT, "out of memory");
+  c->device = p->device;
+  const char* nomem = "contour: no device memory for the workspace";
+  const uint64_t chunk_nodes = per_chunk * N, chunk_slots = per_chunk * E;
+  const unsigned slot_blocks = blocks_of(chunk_slots);
+  // (the vertex numbers of the slots live where the positions were: 8 bytes per node either way)
+  if (!dev_alloc(w.pos, chunk_nodes * (dim == 2 ? 2 : 3)) || !dev_alloc(w.dist, chunk_nodes) || !dev_alloc(w.succ, chunk_slots) || !dev_alloc(w.blk_cnt, slot_blocks) ||
+      !dev_alloc(w.blk_base, slot_blocks) || !dev_alloc(w.layer_base, per_chunk + 1) || !dev_alloc(w.totals, 3) || !dev_alloc(w.ctr, 1) || !dev_alloc(w.z, L))
+    return fail(GSDF_ERR_HIP, nomem);
+  if (w.ev.ensure() != hipSuccess) return fail(GSDF_ERR_HIP, "hipEventCreate failed");
+  // on every way out from here the stream is drained before the buffers above go
+  struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{s};
+  if (dim == 3) HIP_TRY(hipMemcpyAsync(w.z.p, z, (size_t)L * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemsetAsync(w.ctr.p, 0, sizeof(ContourCounters), s));
+
+  gsdf_contour_stats& st = c->st;
+  st.nx = (uint32_t)nx;
+  st.ny = (uint32_t)ny;
+  st.n_layers = (uint32_t)L;
+  std::vector<unsigned> h_base(per_chunk + 1);
+  uint64_t largest_layer = 0;
+  auto interval_ms = [&](int a, int b) { float t = 0; return hipEventElapsedTime(&t, w.ev[a], w.ev[b]) == hipSuccess ? (double)t : 0.0; };
+
+  for (uint64_t l0 = 0; l0 < L; l0 += per_chunk) {
+    const uint64_t Lc = L - l0 < per_chunk ? L - l0 : per_chunk;
+    const uint64_t nodes = Lc * N, slots = Lc * E;
+    const unsigned nb_slots = blocks_of(slots);
+    // 1. evaluate: positions, then the program's Evaluate over them
+    HIP_TRY(hipEventRecord(w.ev[0], s));
+    if (dim == 2) LAUNCH(contour_pos_kernel<2>, blocks_of(nodes), s, lat, (const float*)nullptr, (unsigned long long)nodes, w.pos.p);
+    else LAUNCH(contour_pos_kernel<3>, blocks_of(nodes), s, lat, (const float*)(w.z.p + l0), (unsigned long long)nodes, w.pos.p);
+    if (int rc = dim == 2 ? gsdf_hip_eval2_dev(p, w.pos.p, 8, w.dist.p, (size_t)nodes, (void*)s) : gsdf_hip_eval3_dev(p, w.pos.p, 12, w.dist.p, (size_t)nodes, (void*)s)) return rc;
+    HIP_TRY(hipEventRecord(w.ev[1], s));
+    // 2. cells -> succ over the edge slots; cut edges per block, per layer
+    HIP_TRY(hipMemsetAsync(w.succ.p, 0xff, (size_t)slots * 4, s));
+    LAUNCH(contour_cells_kernel, blocks_of(nodes), s, lat, (const float*)w.dist.p, (unsigned long long)nodes, w.succ.p, w.ctr.p);
+    LAUNCH(contour_count_kernel, nb_slots, s, (const unsigned*)w.succ.p, (unsigned long long)slots, w.blk_cnt.p);
+    if (int rc = launch_block_scan(w.blk_cnt.p, nb_slots, w.blk_base.p, w.totals.p, s)) return rc;
+    LAUNCH(contour_layer_base_kernel, blocks_of(Lc + 1), s, (const unsigned*)w.succ.p, (const unsigned*)w.blk_base.p, (const unsigned long long*)w.totals.p, (unsigned)E,
+           (unsigned)Lc, w.layer_base.p);
+    HIP_TRY(hipEventRecord(w.ev[2], s));
+    HIP_TRY(hipMemcpyAsync(h_base.data(), w.layer_base.p, (size_t)(Lc + 1) * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    st.ms_eval += interval_ms(0, 1);
+    st.ms_trace += interval_ms(1, 2);
+    const uint64_t V = h_base[Lc];
+    uint64_t chunk_largest = 0;
+    for (uint64_t l = 0; l < Lc; l++) chunk_largest = std::max<uint64_t>(chunk_largest, h_base[l + 1] - h_base[l]);
+    largest_layer = std::max(largest_layer, chunk_largest);
+    if (V == 0) continue;
+    if (st.n_verts + V >= ((uint64_t)1 << 32)) return fail(GSDF_ERR_CAPACITY, "contour: 2^32 vertices or more");
+    // 3. vertex numbers, links, the leaders by pointer jumping, the ranks by list ranking: rounds for the chunk's largest layer
+    const unsigned nb_v = blocks_of(V);
+    if (w.verts.ensure((size_t)V * 9 * 4) != hipSuccess || w.blk.ensure((size_t)nb_v * 4 * 4) != hipSuccess) return fail(GSDF_ERR_HIP, nomem);
+    unsigned* va = (unsigned*)w.verts.p;
+    unsigned *slot_of = va, *pred = va + V, *mn[2] = {va + 2 * V, va + 3 * V}, *lk[2] = {va + 4 * V, va + 5 * V}, *rk[2] = {va + 6 * V, va + 7 * V}, *start_of = va + 8 * V;
+    unsigned* ba = (unsigned*)w.blk.p;
+    unsigned *blk_loops = ba, *blk_len = ba + nb_v, *base_loops = ba + 2 * (size_t)nb_v, *base_len = ba + 3 * (size_t)nb_v;
+    unsigned* vnum = (unsigned*)w.pos.p;
+    const unsigned rounds = ceil_log2(chunk_largest);
+    HIP_TRY(hipEventRecord(w.ev[3], s));
+    LAUNCH(contour_number_kernel, nb_slots, s, (const unsigned*)w.succ.p, (unsigned long long)slots, (const unsigned*)w.blk_base.p, (unsigned)V, vnum, slot_of, w.ctr.p);
+    LAUNCH(contour_link_kernel, nb_v, s, (const unsigned*)w.succ.p, (unsigned long long)slots, (const unsigned*)vnum, (const unsigned*)slot_of, (unsigned)V, pred, mn[0], lk[0],
+           w.ctr.p);
+    int cur = 0;
+    for (unsigned r = 0; r < rounds; r++, cur ^= 1)
+      LAUNCH(contour_min_kernel, nb_v, s, (const unsigned*)mn[cur], (const unsigned*)lk[cur], (unsigned)V, mn[cur ^ 1], lk[cur ^ 1]);
+    const unsigned* leader = mn[cur];
+    LAUNCH(contour_rank_init_kernel, nb_v, s, leader, (const unsigned*)pred, (unsigned)V, rk[0], lk[0]);
+    int rc_ = 0;
+    for (unsigned r = 0; r < rounds; r++, rc_ ^= 1)
+      LAUNCH(contour_rank_kernel, nb_v, s, (const unsigned*)rk[rc_], (const unsigned*)lk[rc_], (unsigned)V, rk[rc_ ^ 1], lk[rc_ ^ 1]);
+    const unsigned* rank = rk[rc_];
+    // 4. leaders -> loops
+    LAUNCH(contour_leader_count_kernel, nb_v, s, leader, (const unsigned*)pred, rank, (unsigned)V, blk_loops, blk_len);
+    if (int rc = launch_block_scan(blk_loops, nb_v, base_loops, w.totals.p + 1, s)) return rc;
+    if (int rc = launch_block_scan(blk_len, nb_v, base_len, w.totals.p + 2, s)) return rc;
+    HIP_TRY(hipEventRecord(w.ev[4], s));
+    unsigned long long h_tot[3] = {0, 0, 0};
+    ContourCounters h_ctr;
+    HIP_TRY(hipMemcpyAsync(h_tot, w.totals.p, sizeof h_tot, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&h_ctr, w.ctr.p, sizeof h_ctr, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    st.ms_trace += interval_ms(3, 4);
+    const uint64_t nl = h_tot[1];
+    if (h_ctr.bad || nl == 0 || nl > V || h_tot[2] != V) return fail(GSDF_ERR_HIP, "contour: internal error (succ is not a permutation of the cut edges)");
+    // 5. emit
+    parts.emplace_back();
+    Part& part = parts.back();
+    part.n_verts = V;
+    part.n_loops = nl;
+    if (!dev_alloc(part.xy, 2 * V) || !dev_alloc(part.keys, V) || !dev_alloc(part.loop_start, nl) || !dev_alloc(part.loop_layer, nl)) return fail(GSDF_ERR_HIP, nomem);
+    HIP_TRY(hipEventRecord(w.ev[5], s));
+    LAUNCH(contour_leader_number_kernel, nb_v, s, leader, (const unsigned*)pred, rank, (const unsigned*)slot_of, (unsigned)V, (const unsigned*)base_loops, (const unsigned*)base_len,
+           (unsigned)nl, (unsigned)E, (unsigned)l0, (unsigned)st.n_verts, start_of, part.loop_start.p, part.loop_layer.p, w.ctr.p);
+    LAUNCH(contour_emit_kernel, nb_v, s, lat, (const float*)w.dist.p, (const unsigned*)slot_of, leader, rank, (const unsigned*)start_of, (unsigned)V, (unsigned)E, part.xy.p,
+           part.keys.p, w.ctr.p);
+    HIP_TRY(hipEventRecord(w.ev[6], s));
+    HIP_TRY(hipStreamSynchronize(s));
+    st.ms_trace += interval_ms(5, 6);
+    st.n_verts += V;
+    st.n_loops += nl;
+  }
+  // the counters of the whole call; the chunks' loops behind one another
+  ContourCounters h_ctr;
+  HIP_TRY(hipMemcpyAsync(&h_ctr, w.ctr.p, sizeof h_ctr, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (h_ctr.bad) return fail(GSDF_ERR_HIP, "contour: internal error (a vertex out of range)");
+  st.border_inside = h_ctr.border_inside;
+  st.nonfinite_nodes = h_ctr.nonfinite_nodes;
+  st.saddle_cells = h_ctr.saddle_cells;
+  st.rank_rounds = ceil_log2(largest_layer);
+  st.evals = N * L;
+  st.ms_device = st.ms_eval + st.ms_trace;
+  c->n_verts = st.n_verts;
+  c->n_loops = st.n_loops;
+  if (!dev_alloc(c->xy, 2 * c->n_verts) || !dev_alloc(c->keys, c->n_verts) || !dev_alloc(c->loop_start, c->n_loops + 1) || !dev_alloc(c->loop_layer, c->n_loops))
+    return fail(GSDF_ERR_HIP, "contour: no device memory for the result");
+  uint64_t v0 = 0, q0 = 0;
+  for (const Part& part : parts) {
+    HIP_TRY(hipMemcpyAsync(c->xy.p + 2 * v0, part.xy.p, (size_t)part.n_verts * 8, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(c->keys.p + v0, part.keys.p, (size_t)part.n_verts * 4, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(c->loop_start.p + q0, part.loop_start.p, (size_t)part.n_loops * 4, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(c->loop_layer.p + q0, part.loop_layer.p, (size_t)part.n_loops * 4, hipMemcpyDeviceToDevice, s));
+    v0 += part.n_verts;
+    q0 += part.n_loops;
+  }
+  const unsigned end = (unsigned)c->n_verts;
+  HIP_TRY(hipMemcpyAsync(c->loop_start.p + c->n_loops, &end, 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  *out = c.release();
+  return GSDF_OK;
+}
+}  // namespace
+
+extern "C" int gsdf_hip_contour2(gsdf_program* p2d, float res, const gsdf_contour_opts* o, gsdf_contour** out) { return contour_run(p2d, 2, res, nullptr, 1, o, out); }
+extern "C" int gsdf_hip_slice3(gsdf_program* p3d, float res, const float* z, uint32_t n_z, const gsdf_contour_opts* o, gsdf_contour** out) {
+  return contour_run(p3d, 3, res, z, n_z, o, out);
+}
+
+extern "C" int gsdf_hip_contour_counts(const gsdf_contour* c, uint32_t* n_layers, uint64_t* n_loops, uint64_t* n_verts) {
+  if (!c) return fail(GSDF_ERR_BAD_ARGUMENT, "null contour");
+  if (n_layers) *n_layers = c->st.n_layers;
+  if (n_loops) *n_loops = c->n_loops;
+  if (n_verts) *n_verts = c->n_verts;
+  return GSDF_OK;
+}
+
+extern "C" int gsdf_hip_contour_read(const gsdf_contour* c, float* xy, uint32_t* keys, uint32_t* loop_start, uint32_t* loop_layer) {
+  if (!c) return fail(GSDF_ERR_BAD_ARGUMENT, "null contour");
+  HIP_TRY(hipSetDevice(c->device));
+  if (xy && c->n_verts) HIP_TRY(hipMemcpy(xy, c->xy.p, (size_t)c->n_verts * 8, hipMemcpyDeviceToHost));
+  if (keys && c->n_verts) HIP_TRY(hipMemcpy(keys, c->keys.p, (size_t)c->n_verts * 4, hipMemcpyDeviceToHost));
+  if (loop_start) HIP_TRY(hipMemcpy(loop_start, c->loop_start.p, (size_t)(c->n_loops + 1) * 4, hipMemcpyDeviceToHost));
+  if (loop_layer && c->n_loops) HIP_TRY(hipMemcpy(loop_layer, c->loop_layer.p, (size_t)c->n_loops * 4, hipMemcpyDeviceToHost));
+  return GSDF_OK;
+}
+
+extern "C" int gsdf_hip_contour_stats_get(const gsdf_contour* c, gsdf_contour_stats* st) {
+  if (!c || !st) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  *st = c->st;
+  return GSDF_OK;
+}

@@ -29,7 +29,8 @@ SYMBOLS = ["gsdf_hip_last_error", "gsdf_hip_init", "gsdf_hip_program_create", "g
            "gsdf_hip_mesh_read_records", "gsdf_hip_mesh_weld", "gsdf_hip_indexed_counts", "gsdf_hip_indexed_stats_get", "gsdf_hip_indexed_read",
            "gsdf_hip_indexed_normals", "gsdf_hip_indexed_read_normals", "gsdf_hip_indexed_ply", "gsdf_hip_indexed_host_ply", "gsdf_hip_indexed_destroy",
            "gsdf_hip_indexed_create", "gsdf_hip_indexed_report", "gsdf_hip_indexed_shells", "gsdf_hip_indexed_read_shell_of", "gsdf_hip_indexed_extract",
-           "gsdf_hip_indexed_simplify", "gsdf_hip_indexed_simplify_adaptive", "gsdf_hip_indexed_project", "gsdf_hip_indexed_read_fit", "gsdf_hip_mesh_dualcontour_indexed"]
+           "gsdf_hip_indexed_simplify", "gsdf_hip_indexed_simplify_adaptive", "gsdf_hip_indexed_project", "gsdf_hip_indexed_read_fit", "gsdf_hip_mesh_dualcontour_indexed",
+           "gsdf_hip_contour2", "gsdf_hip_slice3", "gsdf_hip_contour_counts", "gsdf_hip_contour_read", "gsdf_hip_contour_stats_get", "gsdf_hip_contour_destroy"]
 
 
 PRUNE_ASSUME_SDF = 1 << 30  # gsdf_hip.h: GSDF_PRUNE_ASSUME_SDF
@@ -152,6 +153,23 @@ class ProjectStats(C.Structure):
                 ("over_tol_after", C.c_uint64), ("max_abs_before", C.c_float), ("max_abs_after", C.c_float), ("steps_max", C.c_uint32),
                 ("reserved", C.c_uint32), ("ms_device", C.c_double)]
     RESULT_BYTES = 112
+
+    def result_bytes(self):
+        return bytes(self)[:self.RESULT_BYTES]
+
+
+class ContourOpts(C.Structure):
+    """gsdf_contour_opts (gsdf_hip.h): lattice nodes per chunk of whole layers (0: the library's default)."""
+    _fields_ = [("max_nodes", C.c_uint64)]
+
+
+class ContourStats(C.Structure):
+    """gsdf_contour_stats (gsdf_hip.h): what a contour / slice call did; bytes 0 .. 63 (RESULT_BYTES) are a function of the program, res
+    and the z list alone, the three times say what the run cost (evaluation, tracing, their sum)."""
+    _fields_ = [("n_verts", C.c_uint64), ("n_loops", C.c_uint64), ("border_inside", C.c_uint64), ("nonfinite_nodes", C.c_uint64),
+                ("saddle_cells", C.c_uint64), ("evals", C.c_uint64), ("nx", C.c_uint32), ("ny", C.c_uint32), ("n_layers", C.c_uint32),
+                ("rank_rounds", C.c_uint32), ("ms_device", C.c_double), ("ms_eval", C.c_double), ("ms_trace", C.c_double)]
+    RESULT_BYTES = 64
 
     def result_bytes(self):
         return bytes(self)[:self.RESULT_BYTES]
@@ -283,6 +301,13 @@ def lib():
         L.gsdf_hip_indexed_project.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(ProjectOpts), C.POINTER(C.c_void_p), C.POINTER(ProjectStats)]
         L.gsdf_hip_indexed_read_fit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.gsdf_hip_mesh_dualcontour_indexed.argtypes = [C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(MeshStats)]
+        L.gsdf_hip_contour2.argtypes = [C.c_void_p, C.c_float, C.POINTER(ContourOpts), C.POINTER(C.c_void_p)]
+        L.gsdf_hip_slice3.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_uint32, C.POINTER(ContourOpts), C.POINTER(C.c_void_p)]
+        L.gsdf_hip_contour_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.gsdf_hip_contour_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.gsdf_hip_contour_stats_get.argtypes = [C.c_void_p, C.POINTER(ContourStats)]
+        L.gsdf_hip_contour_destroy.argtypes = [C.c_void_p]
+        L.gsdf_hip_contour_destroy.restype = None
         L.gsdf_hip_brick_owner.restype = C.c_uint32
         L.gsdf_hip_brick_owner.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         L.gsdf_hip_slab_range.restype = None
@@ -935,6 +960,82 @@ class IndexedHIP:
         a = np.frombuffer(raw, dtype=np.uint8)
         a.flags.writeable = False
         return a
+
+
+def layer_heights(bounds, h):
+    """The mid-heights of the layers of thickness h that cover the z extent of `bounds` (6 floats): z_k = fl(bb.min.z + fl((k + 0.5) h)),
+    float32, for every k whose z_k lies below bb.max.z."""
+    bb = np.asarray(bounds, np.float32).reshape(6)
+    h = np.float32(h)
+    if not (np.isfinite(h) and h > 0):
+        raise ValueError("layer height must be finite and positive")
+    n = int(np.ceil(float(np.float32(bb[5] - bb[2]) / h))) + 1
+    z = (np.float32(bb[2]) + (np.arange(n, dtype=np.float32) + np.float32(0.5)) * h).astype(np.float32)
+    return np.ascontiguousarray(z[z < bb[5]])
+
+
+class ContourHIP:
+    """The outline of a 2-D part or the z-slices of a 3-D part as ordered closed loops, traced on the device (gsdf_contour; the
+    "contours" section of gsdf_hip.h states the arithmetic). Independent of the program it was traced from."""
+
+    def __init__(self, handle):
+        self._h = handle
+        nl, nq, nv = C.c_uint32(), C.c_uint64(), C.c_uint64()
+        _check(lib().gsdf_hip_contour_counts(handle, C.byref(nl), C.byref(nq), C.byref(nv)))
+        self.n_layers, self.n_loops, self.n_verts = int(nl.value), int(nq.value), int(nv.value)
+        self.xy = np.empty((self.n_verts, 2), np.float32)
+        self.keys = np.empty(self.n_verts, np.uint32)
+        self.loop_start = np.empty(self.n_loops + 1, np.uint32)
+        self.loop_layer = np.empty(self.n_loops, np.uint32)
+        _check(lib().gsdf_hip_contour_read(handle, self.xy.ctypes.data, self.keys.ctypes.data, self.loop_start.ctypes.data, self.loop_layer.ctypes.data))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().gsdf_hip_contour_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @classmethod
+    def outline(cls, sdf2, res, max_nodes=0):
+        """gsdf_hip_contour2: the outline of the 2-D part `sdf2` (an SDF2HIP) on a lattice of spacing res, one layer."""
+        h, o = C.c_void_p(), ContourOpts(int(max_nodes))
+        _check(lib().gsdf_hip_contour2(sdf2._h, np.float32(res), C.byref(o), C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def slices(cls, sdf3, res, z, max_nodes=0):
+        """gsdf_hip_slice3: the contours of the 3-D part `sdf3` in the planes z[k] (float32), one layer each; max_nodes: lattice nodes
+        per chunk of whole layers (0: the default; the result does not depend on it)."""
+        z = np.ascontiguousarray(z, np.float32).reshape(-1)
+        h, o = C.c_void_p(), ContourOpts(int(max_nodes))
+        _check(lib().gsdf_hip_slice3(sdf3._h, np.float32(res), z.ctypes.data if len(z) else None, len(z), C.byref(o), C.byref(h)))
+        return cls(h)
+
+    @property
+    def stats(self):
+        st = ContourStats()
+        _check(lib().gsdf_hip_contour_stats_get(self._h, C.byref(st)))
+        return st
+
+    def loops(self, layer=None):
+        """The loops (of one layer, or of all) as (n, 2) float32 arrays, in the handle's order."""
+        return [self.xy[self.loop_start[q]:self.loop_start[q + 1]] for q in range(self.n_loops) if layer is None or self.loop_layer[q] == layer]
+
+    def areas(self):
+        """Signed area of every loop: the float64 shoelace sum over the handle's order, on the host (outer boundaries > 0, holes < 0)."""
+        return np.array([loop_area(l) for l in self.loops()], np.float64)
+
+
+def loop_area(xy):
+    """Float64 shoelace area of one closed loop, (n, 2)."""
+    p = np.asarray(xy, np.float64)
+    q = np.roll(p, -1, axis=0)
+    return 0.5 * float(np.sum(p[:, 0] * q[:, 1] - q[:, 0] * p[:, 1]))
 
 
 class PendingMesh:

@@ -1,0 +1,79 @@
+"""SVG outlines with the standard library only (struct, re): the loops of a ContourHIP as one even-odd <path> per layer, and their
+reader. Coordinates are written as the shortest decimal that reads back as the same float32, so write followed by read is bit-exact;
+the y axis points up in the part and down in SVG, and is turned by one transform around the paths, not by changing coordinates."""
+import re
+import struct
+
+import numpy as np
+
+
+def fmt(v):
+    """The shortest decimal (%.{p}g, p = 1 .. 9) that rounds back to the float32 `v`, to the bit (negative zero, subnormals)."""
+    v = float(v)
+    want = struct.pack("<f", v)
+    if want in (b"\x00\x00\x80\x7f", b"\x00\x00\x80\xff") or v != v:
+        raise ValueError("a coordinate is not finite")
+    for p in range(1, 10):
+        s = "%.*g" % (p, v)
+        try:
+            if struct.pack("<f", float(s)) == want:
+                return s
+        except OverflowError:  # (a shorter decimal of the largest floats rounds past them)
+            pass
+    raise AssertionError("nine digits always identify a float32")
+
+
+def write_svg(path, layers, z=None, stroke_width=None):
+    """layers: a list (one entry per layer) of lists of loops, each loop (n, 2) float32 in order of travel. One
+    <path fill-rule="evenodd"> per layer (an empty layer: an empty path), each loop `M x y L x y ... Z`. z (optional): the layers'
+    heights, kept as data-z."""
+    lo, hi = [None, None], [None, None]
+    for loops in layers:
+        for l in loops:
+            a = np.asarray(l, np.float32).reshape(-1, 2)
+            if len(a):
+                for k in (0, 1):
+                    mn, mx = float(a[:, k].min()), float(a[:, k].max())
+                    lo[k] = mn if lo[k] is None else min(lo[k], mn)
+                    hi[k] = mx if hi[k] is None else max(hi[k], mx)
+    if lo[0] is None:
+        lo, hi = [0.0, 0.0], [1.0, 1.0]
+    w, h = max(hi[0] - lo[0], 1e-30), max(hi[1] - lo[1], 1e-30)
+    pad = 0.02 * max(w, h)
+    sw = stroke_width if stroke_width is not None else 0.002 * max(w, h)
+    out = ['<?xml version="1.0" encoding="UTF-8"?>\n',
+           '<svg xmlns="http://www.w3.org/2000/svg" viewBox="%.9g %.9g %.9g %.9g">\n' % (lo[0] - pad, -(hi[1] + pad), w + 2 * pad, h + 2 * pad),
+           '<g transform="scale(1,-1)" fill="#c8d4e4" stroke="#203040" stroke-width="%.9g">\n' % sw]
+    for k, loops in enumerate(layers):
+        d = []
+        for l in loops:
+            a = np.asarray(l, np.float32).reshape(-1, 2)
+            if len(a) == 0:
+                continue
+            pts = ["%s %s" % (fmt(x), fmt(y)) for x, y in a]
+            d.append("M " + " L ".join(pts) + " Z")
+        zattr = "" if z is None else ' data-z="%s"' % fmt(np.float32(z[k]))
+        out.append('<path id="layer%d"%s fill-rule="evenodd" d="%s"/>\n' % (k, zattr, " ".join(d)))
+    out.append("</g>\n</svg>\n")
+    with open(path, "w", encoding="utf-8") as f:
+        f.write("".join(out))
+
+
+_PATH = re.compile(r'<path\b[^>]*?\bd="([^"]*)"[^>]*/>')
+_NUM = r"[-+]?(?:\d+\.?\d*|\.\d+)(?:[eE][-+]?\d+)?"
+_LOOP = re.compile(r"M\s*((?:%s[\s,]*|L\s*)+)Z" % _NUM)
+
+
+def read_svg(path):
+    """The loops of a file written by write_svg: a list per layer (per <path>) of (n, 2) float32 arrays."""
+    text = open(path, encoding="utf-8").read()
+    layers = []
+    for m in _PATH.finditer(text):
+        loops = []
+        for lm in _LOOP.finditer(m.group(1)):
+            vals = [float(s) for s in re.findall(_NUM, lm.group(1))]
+            if len(vals) % 2:
+                raise ValueError("odd number of coordinates in a loop")
+            loops.append(np.array(vals, np.float64).astype(np.float32).reshape(-1, 2))
+        layers.append(loops)
+    return layers

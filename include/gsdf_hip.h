@@ -935,6 +935,70 @@ int gsdf_hip_indexed_read_fit(const gsdf_indexed* ix, float* dist_before, float*
  * kernels_topo.h: cube_first_kernel, cube_number_kernel (abi_indexed.hip); a numpy restatement: tests/dcref.py. */
 int gsdf_hip_mesh_dualcontour_indexed(gsdf_program* p, float res, int chiseled, void* stream, gsdf_indexed** out, gsdf_mesh_stats* st /* optional */);
 
+/* ---- contours: a 2-D part's outline and a 3-D part's z-slices as ordered closed loops (no reference counterpart: the reference's
+ * only 2-D output is a picture) ---------------------------------------------------------------------------------------------------
+ *
+ * gsdf_hip_contour2 traces the zero set of a 2-D program on a square lattice of spacing res; gsdf_hip_slice3 does the same for a 3-D
+ * program in the planes z = z[k], one LAYER per z, each traced independently of the others on the same xy lattice. The result is a
+ * gsdf_contour handle: closed polygons (loops) whose vertices lie on lattice edges, each loop in order of travel with the part on its
+ * left (outer boundaries counter-clockwise, holes clockwise). All arithmetic below is float32, every operation rounded once (fl), never
+ * fused; the result is a function of the program, res and the z list alone, to the byte -- not of thread order, of the chunking
+ * (max_nodes) or of whether the interpreter or the per-tree kernels evaluated.
+ *
+ * Lattice. bb = the program's bounds. x0 = fl(bb.min.x - res); nx = int(floor(fl(fl(bb.max.x - bb.min.x) / res))) + 4;
+ *   x_i = fl(x0 + fl(float(i) res)), i = 0 .. nx - 1; y likewise. The last node lies more than res beyond bb.max: a full ring of
+ *   cells outside the bounds on every side. A box that is empty or inverted along an axis (size 0 or the quotient not >= 0) has
+ *   4 nodes along it: no loops, no error. GSDF_ERR_BAD_ARGUMENT: res not finite or <= 0, x or y bounds not finite,
+ *   a quotient >= 2^31, nx ny >= 2^31 -- all refused before anything is allocated. Node (i, j) of layer k is evaluated at
+ *   (x_i, y_j) or (x_i, y_j, z[k]) by the program's ordinary Evaluate: d.
+ * Inside. A node is inside iff d < 0 and it is not on the lattice border (i = 0, nx - 1 or j = 0, ny - 1). NaN and both zeros are
+ *   outside; -Inf is inside. A border node with d < 0 is forced outside and counted in border_inside: every loop closes, whatever the
+ *   field does. nonfinite_nodes counts the nodes (border included) whose d is NaN or +-Inf.
+ * Vertices. A lattice edge is cut iff its two nodes differ in the inside test. Its key is 2 (j nx + i) + axis, (i, j) its lower node,
+ *   axis 0 along x, 1 along y. With d_lo, d_hi the distances at the lower and the higher node: t = fl(d_lo / fl(d_lo - d_hi)) if both
+ *   are finite and the OUTSIDE node has d >= 0 (it has not where the border rule forced it outside), else t = 0.5. The division is the
+ *   correctly rounded one. The cut coordinate is fl(c_lo + fl(t res)), c_lo the lower node's; the other coordinate is the node's own.
+ * Segments. A cell (i, j), i < nx - 1, j < ny - 1, has corners c0 (i, j), c1 (i+1, j), c2 (i+1, j+1), c3 (i, j+1), case = the sum of
+ *   2^c over its inside corners, and edges B (bottom, key(i, j, 0)), R (key(i+1, j, 1)), T (key(i, j+1, 0)), L (key(i, j, 1)).
+ *   Oriented segments tail -> head, the part on the left:  1 B>L  2 R>B  3 R>L  4 T>R  6 T>B  7 T>L  8 L>T  9 B>T  11 R>T  12 L>R
+ *   13 B>R  14 L>B;  the saddles 5: B>L and T>R, 10: R>B and L>T (the two inside corners are never joined: a fixed rule, no extra
+ *   evaluation; saddle_cells counts them);  0 and 15: none. Every cut edge is the tail of exactly one segment and the head of exactly
+ *   one: succ (tail -> head) is a permutation of the cut edges of a layer and its cycles are the loops.
+ * Order. A loop's leader is its smallest key. Loops are ordered by (layer, leader), increasing; a loop's vertices start at its leader
+ *   and follow succ. (A leader is always an axis-1 edge.) loop_start[q] is the first vertex of loop q, loop_start[n_loops] = n_verts;
+ *   loop_layer[q] its layer (an index into z; 0 for gsdf_hip_contour2); keys[v] the edge key of vertex v within its layer;
+ *   xy[2 v], xy[2 v + 1] its coordinates. Areas are the caller's (a shoelace sum over this order); not part of the contract.
+ * Chunks. The layers are evaluated and traced in chunks of whole layers of at most max_nodes lattice nodes (0: the default below;
+ *   always at least one layer), so that a tall stack does not hold every layer's workspace (24 bytes per node) at once. The result
+ *   and the integer statistics do not depend on it.
+ * Statistics. rank_rounds = ceil(log2(the largest number of vertices in one layer)) (0 for none): the rounds of pointer jumping that
+ *   layer needs, once for the leaders and once for the ranks; a chunk runs the rounds of its own largest layer, one launch per round,
+ *   no host round trip inside. evals = nx ny n_layers, by which the program's evaluation count grows. ms_eval = device time of the
+ *   lattice positions and the Evaluate, ms_trace = device time of everything behind it (intervals between the host's waits, which
+ *   are left out), ms_device = their sum. Bytes 0 .. 63 of the record are a function of the inputs alone.
+ * Errors. GSDF_ERR_DIMENSION: gsdf_hip_contour2 on a 3-D program, gsdf_hip_slice3 on a 2-D one. GSDF_ERR_BAD_ARGUMENT: the lattice
+ *   rules above, n_z == 0, a null z. GSDF_ERR_CAPACITY: 2^32 vertices or more. Blocking; the handle is independent of the program
+ *   afterwards. Out of scope: DXF / G-code, polyline simplification and arc fitting, tool offsets (Offset2D in the tree is exact),
+ *   infill, sharded or gathered contours, a fused lattice kernel, asymptotic-decider saddles, areas on the device.
+ * Kernels: gsdf_amd/csrc/kernels_contour.h (abi_contour.hip); a numpy restatement over the oracle: tests/contourref.py. */
+typedef struct gsdf_contour gsdf_contour; /* loops, resident in HBM */
+#define GSDF_CONTOUR_DEFAULT_MAX_NODES 16777216 /* 2^24 nodes: 0.4 GB of workspace */
+typedef struct gsdf_contour_opts {
+  uint64_t max_nodes; /* lattice nodes per chunk of whole layers; 0 = GSDF_CONTOUR_DEFAULT_MAX_NODES */
+} gsdf_contour_opts;
+typedef struct gsdf_contour_stats {
+  uint64_t n_verts, n_loops, border_inside, nonfinite_nodes, saddle_cells, evals;
+  uint32_t nx, ny, n_layers, rank_rounds;
+  double ms_device, ms_eval, ms_trace;
+} gsdf_contour_stats;
+int gsdf_hip_contour2(gsdf_program* p2d, float res, const gsdf_contour_opts* o /* optional */, gsdf_contour** out);
+int gsdf_hip_slice3(gsdf_program* p3d, float res, const float* z, uint32_t n_z, const gsdf_contour_opts* o /* optional */, gsdf_contour** out);
+int gsdf_hip_contour_counts(const gsdf_contour* c, uint32_t* n_layers, uint64_t* n_loops, uint64_t* n_verts); /* each optional */
+/* xy 2 n_verts floats, keys n_verts, loop_start n_loops + 1, loop_layer n_loops; any pointer may be NULL */
+int gsdf_hip_contour_read(const gsdf_contour* c, float* xy, uint32_t* keys, uint32_t* loop_start, uint32_t* loop_layer);
+int gsdf_hip_contour_stats_get(const gsdf_contour* c, gsdf_contour_stats* st);
+void gsdf_hip_contour_destroy(gsdf_contour* c);
+
 /* ---- multi-GPU (one process per GPU). The meshers shard with NO data-path collective (shard_rank / shard_count above); the
  * one exchange is the final variable-length gather of the ranks' results, over xGMI, inside this library: a Go caller needs no
  * Python for it. Replaces nothing in the reference (single device; its analogue of the split is the goroutine split of
