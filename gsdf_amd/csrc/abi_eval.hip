@@ -1,4 +1,4 @@
-// abi_eval.hip -- C ABI (include/gsdf_hip.h), evaluator side: program handles and their run-time specialisation, the
+// abi_eval.hip -- C ABI (include/gsdf_hip.h), evaluator side: program handles (their per-tree kernels: abi_spec.hip), the
 // gleval.SDF3 / SDF2 Evaluate drop-ins (host buffers, pipelined tickets, registered memory, device-resident), central-difference
 // normals, the 2-D image renderer and its colour conversions, the UI's view of a 3-D part, the block cache. Kernels: kernels_eval.h,
 // kernels_image.h, kernels_view.h and kernels_project.h over the interpreter of interp.h.
@@ -188,410 +188,6 @@ extern "C" int gsdf_hip_selftest_math(int fn, const float* x, const float* y, fl
   return rc;
 }
 
-static std::string device_arch(int device) {
-  hipDeviceProp_t pr;
-  if (hipGetDeviceProperties(&pr, device) != hipSuccess) return "gfx950";
-  std::string arch = pr.gcnArchName;
-  if (arch.find(':') != std::string::npos) arch = arch.substr(0, arch.find(':'));
-  return arch;
-}
-
-// hiprtc build + module load of `names` for the handle's program; fns receives one function per name.
-static int spec_build(gsdf_program* p, const std::vector<std::string>& names, hipModule_t* mod_out, std::vector<hipFunction_t>& fns, double* secs) {
-  std::vector<char> co;
-  std::vector<std::string> low;
-  std::string log;
-  const auto t0 = std::chrono::steady_clock::now();
-  if (!gsdf_dev::spec_compile(p->prog, device_arch(p->device), names, co, low, log)) return fail(GSDF_ERR_HIP, "specialised build failed:\n" + log);
-  if (secs) *secs += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  hipModule_t mod = nullptr;
-  HIP_TRY(hipModuleLoadData(&mod, co.data()));
-  fns.assign(names.size(), nullptr);
-  for (size_t i = 0; i < names.size(); i++) {
-    hipError_t e = hipModuleGetFunction(&fns[i], mod, low[i].c_str());
-    if (e != hipSuccess) {
-      (void)hipModuleUnload(mod);
-      return fail(GSDF_ERR_HIP, std::string("hipModuleGetFunction: ") + hipGetErrorString(e));
-    }
-  }
-  *mod_out = mod;
-  return GSDF_OK;
-}
-
-// Scratch (private segment) bytes per lane of a built kernel. A specialised kernel is used only if this is 0: its code
-// shape is new for every tree, and a build that spills registers inside divergent regions has been seen to lose the
-// spilled values of the lanes that were inactive at the spill (2-D fuzz tree 708: eval_kernel<2,4,4>, 128 VGPRs + 132 B
-// of scratch, wrote the results of 216 points of a ragged last tile to the wrong addresses). The ahead-of-time
-// interpreter kernels have ONE code shape each, and that shape is what the whole test suite runs.
-static int fn_scratch_bytes(hipFunction_t f) {
-  static const bool allow = env_set("GSDF_HIP_EXP_ALLOW_SCRATCH");  // developer experiments only: timing of a spilling build
-  if (allow) return 0;
-  int v = 0;
-  if (hipFuncGetAttribute(&v, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, f) != hipSuccess) { (void)hipGetLastError(); return 1 << 30; }
-  return v;
-}
-static void spec_report(const char* what, const std::string& name, hipFunction_t f, bool used) {
-  if (!env_set("GSDF_HIP_DEBUG")) return;
-  int regs = -1;
-  (void)hipFuncGetAttribute(&regs, HIP_FUNC_ATTRIBUTE_NUM_REGS, f);
-  fprintf(stderr, "gsdf_hip: %s %s: %d registers, %d B scratch per lane -> %s\n", what, name.c_str(), regs, fn_scratch_bytes(f),
-          used ? "used" : "not used (interpreter kernel instead)");
-}
-// No scratch, or not used (see fn_scratch_bytes); wanted = false: a usable build that an earlier one is preferred to.
-static bool spec_usable(const std::string& name, hipFunction_t f, bool wanted = true) {
-  const bool ok = fn_scratch_bytes(f) == 0;
-  spec_report("specialised", name, f, ok && wanted);
-  return ok;
-}
-// The shared tail of the builders below: `names` built into a module the handle keeps, each function checked for scratch and
-// reported; take(i, f) gets the usable ones in the order of the names and says whether it took f. A failed build takes nothing:
-// the interpreter kernels stay in use.
-template <typename Take>
-static void spec_build_group(gsdf_program* p, const std::vector<std::string>& names, Take take) {
-  std::vector<hipFunction_t> f;
-  hipModule_t mod = nullptr;
-  if (spec_build(p, names, &mod, f, &p->spec_compile_s) != GSDF_OK) return;
-  p->mods.keep(mod);
-  for (size_t i = 0; i < names.size(); i++)
-    if (fn_scratch_bytes(f[i]) == 0) spec_report("specialised", names[i], f[i], take(i, f[i]));
-    else spec_report("specialised", names[i], f[i], false);
-}
-
-// Second group of a specialised handle, built the first time one of these entry points runs: the evaluating kernels of
-// dual contouring, central-difference normals, the flat renderer's lattice pass and the 2-D image renderer. Failure leaves the interpreter kernels in use.
-void spec_aux(gsdf_program* p) {
-  if (!p->spec_mod || p->spec_aux_tried) return;
-  p->spec_aux_tried = true;
-  const int k = p->batch_k();
-  if (p->prog.is2d) {
-    spec_build_group(p, {"image2_kernel<" + std::to_string(k) + ">"}, [&](size_t, hipFunction_t f) { p->f_image = f; return true; });
-  } else {
-    // (both sweeps are built for sweep_variant's W; dual contouring's launch is the same whichever W its kernel was built for)
-    hipFunction_t* dst[6] = {&p->f_dc_origin, &p->f_dc_edges, &p->f_dc_normals, &p->f_normals, &p->f_flat_grid, &p->f_dc_block_test};
-    spec_build_group(p, {p->sweep_variant(k).spec_name("dc_origin_kernel"), "dc_edges_kernel", "dc_normals_kernel", "normals_kernel", p->sweep_variant(k).spec_name("flat_grid_kernel"), "dc_block_test_kernel"},
-                     [&](size_t i, hipFunction_t f) { *dst[i] = f; return true; });
-  }
-}
-
-// leaf_eval_kernel with distinct z rows (kernels_octree.h: DZ) for a specialised handle whose leaf phase runs four points per
-// lane: the one-body form at the occupancy the handle's evaluating kernel has, then at four workgroups per CU, then the two-site
-// form; the first that builds without scratch is taken. If none does (knurled-cylinder with hipcc 7.2: three variants of the
-// second pass in one body want more than 128 registers; at three workgroups per CU the option costs more than it saves), a
-// specialised handle keeps evaluating every row with its specialised kernel.
-void spec_leaf_dz(gsdf_program* p) {
-  if (!p->spec_mod || p->spec_dz_tried || p->prog.is2d) return;
-  p->spec_dz_tried = true;
-  const gsdf_program::LeafConfig c = p->leaf_config();
-  if (fused_leaf() || c.k != 4 || !p->f_leaf || p->spec_leaf_k != 4) return;
-  std::vector<LeafVariant> vs;
-  auto add = [&](int w, bool b) {
-    for (const LeafVariant& v : vs) if (v.w == w && v.both == b) return;
-    vs.push_back({false, 4, w, true, c.ntlds, b, true});
-  };
-  if (p->spec_leaf_both) { add(p->spec_leaf_w, true); add(c.w, true); }
-  add(p->spec_leaf_w, false); add(c.w, false);
-  std::vector<std::string> names;
-  for (const LeafVariant& v : vs) names.push_back(v.spec_name());
-  spec_build_group(p, names, [&](size_t i, hipFunction_t f) {
-    if (p->f_leaf_dz) return false;
-    p->f_leaf_dz = f; p->spec_leaf_dz_w = vs[i].w; p->spec_leaf_dz_both = vs[i].both;
-    return true;
-  });
-}
-
-// eval_kernel<D, 1, 4> for a specialised handle: one point per lane, what host-mapped Evaluate calls run (eval_dev). Built at the
-// first such call, in a module of its own (the first group's build key -- the handle's code identity -- stays what it is).
-void spec_eval_k1(gsdf_program* p) {
-  static std::mutex mu;  // host-buffer calls may come from several threads
-  std::lock_guard<std::mutex> lk(mu);
-  if (!p->spec_mod || p->spec_k1_tried || p->batch_k() == 1) return;
-  p->spec_k1_tried = true;
-  spec_build_group(p, {SweepVariant{1, 4}.spec_name("eval_kernel", p->prog.is2d ? 2 : 3)}, [&](size_t, hipFunction_t f) { p->f_eval_k1 = f; return true; });
-}
-
-// leaf_dense_kernel (share_corners = 1: every bitwise-distinct lattice point of a brick once) for a specialised handle, at the most
-// workgroups per CU its LDS allows for which the compiler needs no scratch. Failure leaves the interpreter's kernel in use.
-void spec_leaf_dense(gsdf_program* p) {
-  if (!p->spec_mod || p->spec_dense_tried || p->prog.is2d || fused_leaf()) return;
-  p->spec_dense_tried = true;
-  std::vector<std::string> names;
-  std::vector<int> ws;
-  for (int w = 5; w >= 3; w--)
-    if ((size_t)w * p->lds_dense() <= gsdf_program::kLdsPerCu) { names.push_back("leaf_dense_kernel<" + std::to_string(w) + ", true, true>"); ws.push_back(w); }
-  if (names.empty()) return;
-  spec_build_group(p, names, [&](size_t i, hipFunction_t f) {
-    if (p->f_leaf_dense) return false;
-    p->f_leaf_dense = f; p->spec_leaf_dense_w = ws[i];
-    return true;
-  });
-}
-
-// view_kernel, both forms (kernels_view.h), for a specialised handle: built at its first frame, in a module of its own that includes
-// kernels_common.h and kernels_view.h only (specialize.cpp: spec_includes). A form that fails to build or needs scratch stays on the
-// interpreter kernel.
-void spec_view(gsdf_program* p) {
-  if (!p->spec_mod || p->spec_view_tried || p->prog.is2d) return;
-  p->spec_view_tried = true;
-  hipFunction_t* dst[2] = {&p->f_view, &p->f_view_plain};
-  spec_build_group(p, {"view_kernel<true>", "view_kernel<false>"}, [&](size_t i, hipFunction_t f) { *dst[i] = f; return true; });
-}
-
-// project_kernel (kernels_project.h) for a specialised handle: built at its first projection, in a module of its own that includes
-// kernels_common.h and kernels_project.h only (specialize.cpp: spec_includes). If it fails to build or needs scratch the interpreter
-// kernel stays in use.
-void spec_project(gsdf_program* p) {
-  if (!p->spec_mod || p->spec_project_tried || p->prog.is2d) return;
-  p->spec_project_tried = true;
-  spec_build_group(p, {"project_kernel"}, [&](size_t, hipFunction_t f) { p->f_project = f; return true; });
-}
-
-// image2_color_kernel<k, kind> for every conversion kind (kernels_image.h), for a specialised 2-D handle: built at its first picture,
-// in a module of its own (specialize.cpp: spec_includes). A kernel that fails to build or needs scratch stays on the interpreter kernel.
-void spec_image_color(gsdf_program* p) {
-  if (!p->spec_mod || p->spec_imgc_tried || !p->prog.is2d) return;
-  p->spec_imgc_tried = true;
-  const std::string k = std::to_string(p->batch_k());
-  std::vector<std::string> names;
-  for (int kind = 0; kind < 4; kind++) names.push_back("image2_color_kernel<" + k + ", " + std::to_string(kind) + ">");
-  spec_build_group(p, names, [&](size_t i, hipFunction_t f) { p->f_imgc[i] = f; return true; });
-}
-
-// Compile and load kernels specialised for this handle's program (specialize.cpp): eval, prune and leaf kernels of
-// the configuration the mesher would pick. Afterwards gsdf_hip_eval*/gsdf_hip_mesh_octree launch them instead of the
-// interpreter kernels; results are bit-identical (same statements, same compiler flags). Idempotent.
-extern "C" int gsdf_hip_program_specialize(gsdf_program* p) {
-  if (!p) return fail(GSDF_ERR_BAD_ARGUMENT, "null program");
-  if (p->spec_mod) return GSDF_OK;
-  // straight-line code grows with the program (multi-evaluation nodes are unrolled at lowering time): beyond a few
-  // thousand instructions the build takes minutes and the code no longer fits the instruction cache
-  if (gsdf_dev::spec_instruction_count(p->prog) > 4000)
-    return fail(GSDF_ERR_BAD_TREE, "program too large to specialise (more than 4000 instructions): the interpreter kernels stay in use");
-  HIP_TRY(hipSetDevice(p->device));
-  const gsdf_program::LeafConfig c = p->leaf_config();
-  const int lk = c.k, lw = c.w, dim = p->prog.is2d ? 2 : 3;
-  const bool fused = fused_leaf();
-  const SweepVariant ev = p->sweep_variant(p->batch_k());
-  const LeafVariant leaf{fused, lk, lw, !fused, !fused && c.ntlds, false, false};  // the configuration the mesher would pick
-  auto leaf_with = [&](int w, bool both) { LeafVariant v = leaf; v.w = w; v.both = both; return v; };
-  std::vector<std::string> names;
-  int five_at = -1, both_at = -1, both5_at = -1;
-  names.push_back(ev.spec_name("eval_kernel", dim));
-  if (!p->prog.is2d) {
-    names.push_back("prune_kernel");
-    names.push_back("prune_spec_kernel");
-    names.push_back(leaf.spec_name());
-    const bool room5 = !fused && lk == 4 && lw == 4 && 5 * c.lds <= gsdf_program::kLdsPerCu;
-    // a fifth workgroup per CU where the LDS has room for it (npt-flange's 7 slots): the 96-register build is taken if the
-    // compiler reaches it without scratch (-3 % on the evaluating kernel); built beside the 128-register one, same process
-    if (room5) { five_at = (int)names.size(); names.push_back(leaf_with(5, false).spec_name()); }
-    // both passes of a column brick in one body -- taken, ahead of the others, if the compiler reaches it without scratch: -7 %
-    // where much of the program depends on x and y alone (an atan2, several hypots: npt-flange), -1..2 % elsewhere
-    static const bool both_off = env_flag("GSDF_HIP_NO_BOTH_PASSES");  // developer knob (A/B timing)
-    static const int both_min = env_int("GSDF_HIP_BOTH_MIN_WEIGHT", 0);  // developer knob. 0: always -- programs without x,y-only work gain 1-2 % too (bolt 1.029 -> 1.007 ms, knurled-cylinder 3.19 -> 3.16: one body of eight points schedules a little better than two of four)
-    if (!fused && !both_off && lk == 4 && gsdf_dev::spec_xy_shared_weight(p->prog) >= both_min) {
-      both_at = (int)names.size();
-      names.push_back(leaf_with(lw, true).spec_name());
-      // ... and at five workgroups per CU (96 registers) where the LDS has room: taken if it builds without scratch
-      static const bool both5_off = env_flag("GSDF_HIP_NO_BOTH5");  // developer knob (A/B timing)
-      if (!both5_off && room5) { both5_at = (int)names.size(); names.push_back(leaf_with(5, true).spec_name()); }
-    }
-  }
-  std::vector<hipFunction_t> f;
-  hipModule_t mod = nullptr;
-  const int rc = spec_build(p, names, &mod, f, &p->spec_compile_s);
-  if (rc != GSDF_OK) return rc;
-  p->spec_mod = mod;
-  p->spec_compiler = gsdf_dev::spec_last_compiler();
-  p->spec_key = gsdf_dev::spec_last_key();
-  p->spec_eval_k = ev.k; p->spec_eval_w = ev.w; p->spec_leaf_k = lk; p->spec_leaf_w = lw;
-  // No scratch, or not used (see fn_scratch_bytes). The eval kernel gets a second chance with the larger register
-  // budget of 3 workgroups per CU before the handle falls back to the interpreter kernel for that entry point.
-  p->f_eval = spec_usable(names[0], f[0]) ? f[0] : nullptr;
-  if (!p->f_eval && ev.w == 4)
-    spec_build_group(p, {SweepVariant{ev.k, 3}.spec_name("eval_kernel", dim)}, [&](size_t, hipFunction_t f3) { p->f_eval = f3; p->spec_eval_w = 3; return true; });
-  if (!p->prog.is2d) {
-    p->f_prune = spec_usable(names[1], f[1]) ? f[1] : nullptr;
-    p->f_prune_spec = spec_usable(names[2], f[2]) ? f[2] : nullptr;
-    // the leaf kernel: each later candidate that builds without scratch is preferred to the ones before it
-    auto take_leaf = [&](int at, int w, bool both) {
-      if (at < 0 || !spec_usable(names[(size_t)at], f[(size_t)at])) return;
-      p->f_leaf = f[(size_t)at]; p->spec_leaf_w = w; p->spec_leaf_both = both;
-    };
-    take_leaf(3, lw, false);
-    take_leaf(five_at, 5, false);
-    take_leaf(both_at, lw, true);
-    take_leaf(both5_at, 5, true);
-    // the leaf kernel is where the time goes: before giving it up, trade occupancy for registers (W = workgroups per CU
-    // the register budget is sized for; the launch is the same)
-    for (int w2 = lw - 1; !p->f_leaf && w2 >= 2; w2--) {
-      std::vector<hipFunction_t> fl;
-      hipModule_t m2 = nullptr;
-      const std::string nl = leaf_with(w2, false).spec_name();
-      if (spec_build(p, {nl}, &m2, fl, &p->spec_compile_s) != GSDF_OK) break;
-      if (spec_usable(nl, fl[0])) { p->f_leaf = fl[0]; p->spec_leaf_w = w2; p->mods.keep(m2); }
-      else (void)hipModuleUnload(m2);
-    }
-  }
-  return GSDF_OK;
-}
-// ---- specialisation in the background -----------------------------------------------------------------------------------------
-// Every example of the reference is one tree -> one mesh -> one file (examples/npt-flange/flange.go:61-98): a caller that waits for
-// a compiler before its only mesh has gained nothing. _async starts the build (and the module load) on a thread of its own and
-// returns; the handle keeps meshing and evaluating through the interpreter kernels and switches to the specialised ones at the
-// first entry-point call after they are ready -- same bits either way (same statements, same flags), so a mesh may even change
-// kernels between its attempts. With GSDF_HIP_CACHE_DIR set and the tree seen before, "ready" is a file read away.
-void spec_adopt_slow(gsdf_program* p) {
-  std::lock_guard<std::mutex> lk(p->spec_async_mu);
-  if (p->spec_async.load(std::memory_order_acquire) != 2) return;  // another thread of the caller was faster
-  if (p->spec_thread.joinable()) p->spec_thread.join();
-  gsdf_program* q = p->spec_shadow;
-  p->spec_shadow = nullptr;
-  if (q && !p->spec_mod) {
-    p->spec_compile_s += q->spec_compile_s; p->spec_compiler = q->spec_compiler; p->spec_key = q->spec_key;
-    p->spec_eval_k = q->spec_eval_k; p->spec_eval_w = q->spec_eval_w; p->spec_leaf_k = q->spec_leaf_k; p->spec_leaf_w = q->spec_leaf_w;
-    p->spec_leaf_both = q->spec_leaf_both;
-    p->mods.take(q->mods);
-    std::atomic_thread_fence(std::memory_order_release);  // (the configuration before the functions: a reader that sees a function sees what it was built for)
-    p->f_prune = q->f_prune; p->f_prune_spec = q->f_prune_spec; p->f_leaf = q->f_leaf; p->f_eval = q->f_eval;
-    p->spec_mod = q->spec_mod;
-    q->spec_mod = nullptr;
-  }
-  delete q;
-  p->spec_async.store(0, std::memory_order_release);
-}
-
-extern "C" int gsdf_hip_program_specialize_async(gsdf_program* p) {
-  if (!p) return fail(GSDF_ERR_BAD_ARGUMENT, "null program");
-  std::lock_guard<std::mutex> lk(p->spec_async_mu);
-  if (p->spec_mod || p->spec_async.load() != 0) return GSDF_OK;  // specialised already, or a build is under way / waiting to be adopted
-  if (gsdf_dev::spec_instruction_count(p->prog) > 4000)
-    return fail(GSDF_ERR_BAD_TREE, "program too large to specialise (more than 4000 instructions): the interpreter kernels stay in use");
-  gsdf_program* q = new (std::nothrow) gsdf_program;
-  if (!q) return fail(GSDF_ERR_CAPACITY, "out of memory");
-  q->prog = p->prog; q->device = p->device; q->num_cu = p->num_cu;  // all a build reads (no streams, no device memory)
-  p->spec_shadow = q;
-  p->spec_async_err.clear();
-  p->spec_async.store(1, std::memory_order_release);
-  try {
-    p->spec_thread = std::thread([p, q] {
-      const int rc = gsdf_hip_program_specialize(q);
-      if (rc != GSDF_OK) p->spec_async_err = gsdf_hip_last_error();  // (the error text is the building thread's)
-      p->spec_async.store(rc == GSDF_OK ? 2 : 3, std::memory_order_release);
-    });
-  } catch (...) {
-    p->spec_shadow = nullptr;
-    delete q;
-    p->spec_async.store(0);
-    return fail(GSDF_ERR_CAPACITY, "cannot start the build thread");
-  }
-  return GSDF_OK;
-}
-
-/* 1: the handle runs specialised kernels now; 0: the build is still under way (wait = 0) or none was started; a negative status if
- * the build failed (the interpreter kernels stay in use; gsdf_hip_last_error has the compiler's words). wait != 0 blocks until the
- * build has finished. */
-extern "C" int gsdf_hip_program_specialize_poll(gsdf_program* p, int wait) {
-  if (!p) return fail(GSDF_ERR_BAD_ARGUMENT, "null program");
-  if (wait) {
-    std::unique_lock<std::mutex> lk(p->spec_async_mu);
-    if (p->spec_async.load() == 1 && p->spec_thread.joinable()) p->spec_thread.join();
-  }
-  spec_adopt(p);
-  if (p->spec_async.load(std::memory_order_acquire) == 3) {
-    std::lock_guard<std::mutex> lk(p->spec_async_mu);
-    if (p->spec_thread.joinable()) p->spec_thread.join();
-    delete p->spec_shadow;
-    p->spec_shadow = nullptr;
-    p->spec_async.store(0);
-    return fail(GSDF_ERR_HIP, "background specialisation failed: " + p->spec_async_err);
-  }
-  return p->spec_mod ? 1 : 0;
-}
-
-/* 1 if the handle runs specialised kernels; compile_seconds (optional) = what the build took */
-extern "C" int gsdf_hip_program_is_specialized(const gsdf_program* p, double* compile_seconds) {
-  if (compile_seconds) *compile_seconds = p ? p->spec_compile_s : 0.0;
-  return p && p->spec_mod ? 1 : 0;
-}
-
-/* The kernels this handle launches, e.g. "eval=eval_kernel<3,4,4>:specialised leaf=leaf_kernel<4,3>:specialised
- * prune=prune_kernel:specialised" (":interpreter" for the ahead-of-time kernels): what a profile of the handle shows. */
-extern "C" int gsdf_hip_program_kernels(const gsdf_program* p, char* dst, size_t dst_cap) {
-  if (!p || !dst || dst_cap == 0) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
-  // the rules the launches go by: eval_dev's, the leaf phase of a mesh of three levels or more (gsdf_program::leaf_pick)
-  const int ek = p->batch_k();
-  const bool se = p->f_eval && p->spec_eval_k == ek;
-  const SweepVariant ev = se ? SweepVariant{ek, p->spec_eval_w} : p->sweep_variant(ek);
-  const LeafPick leaf = p->leaf_pick(3);
-  auto how = [](const void* f) { return f ? "specialised" : "interpreter"; };
-  char buf[512];
-  if (p->prog.is2d)
-    snprintf(buf, sizeof buf, "eval=%s:%s", ev.short_name("eval_kernel", 2).c_str(), how(se ? p->f_eval : nullptr));
-  else
-    snprintf(buf, sizeof buf, "eval=%s:%s leaf=%s:%s prune=prune_kernel:%s", ev.short_name("eval_kernel", 3).c_str(), how(se ? p->f_eval : nullptr),
-             leaf.v.short_name().c_str(), how(leaf.f), how(p->f_prune));
-  if (p->f_leaf_dense && strlen(buf) + 64 < sizeof buf)  // the evaluating kernel of share_corners = 1, once it has been built
-    snprintf(buf + strlen(buf), sizeof buf - strlen(buf), " leaf_dense=leaf_dense_kernel<%d>:specialised", p->spec_leaf_dense_w);
-  if (p->f_leaf_dz && strlen(buf) + 64 < sizeof buf)  // the evaluating kernel of share_corners = 2, once it has been built
-    snprintf(buf + strlen(buf), sizeof buf - strlen(buf), " leaf_rows=%s:specialised", p->leaf_pick(3, true).v.short_name().c_str());
-  if (p->prog.is2d && strlen(buf) + 64 < sizeof buf) {  // the picture kernels (a specialised handle builds its own at its first picture)
-    std::string kinds;
-    for (int i = 0; i < 4; i++) if (p->f_imgc[i]) kinds += std::to_string(i);
-    snprintf(buf + strlen(buf), sizeof buf - strlen(buf), " picture=image2_color_kernel<%d,kind>:%s", ek,
-             kinds.empty() ? "interpreter" : ("specialised/" + kinds).c_str());
-  }
-  if (!p->prog.is2d && strlen(buf) + 48 < sizeof buf)  // the projection of mesh vertices (a specialised handle builds its own at its first projection)
-    snprintf(buf + strlen(buf), sizeof buf - strlen(buf), " project=project_kernel:%s", how(p->f_project));
-  if (strlen(buf) + 160 < sizeof buf) {  // the sweeps that carry a K of their own, and what the LDS limits of the meshers count (gsdf_hip.h: Largest trees)
-    if (p->prog.is2d) snprintf(buf + strlen(buf), sizeof buf - strlen(buf), " image=image2_kernel<%d>:%s", ek, how(p->f_image));
-    else snprintf(buf + strlen(buf), sizeof buf - strlen(buf), " flat=%s:%s dc=%s:%s interval=%d", p->sweep_variant(ek).short_name("flat_grid_kernel").c_str(), how(p->f_flat_grid),
-                  gsdf_program::dc_origin_variant(ek).short_name("dc_origin_kernel").c_str(), how(p->f_dc_origin), p->prog.lip_depth);
-  }
-  if (p->spec_mod && strlen(buf) + 32 < sizeof buf) { strcat(buf, " compiler="); strcat(buf, p->spec_compiler.c_str()); }
-  {  // identity of the code that runs: a stored profile describes this handle's kernels only if it carries the same key
-    const std::string key = p->spec_mod ? p->spec_key : gsdf_dev::spec_library_key();
-    if (strlen(buf) + 8 + key.size() < sizeof buf) { strcat(buf, " code="); strcat(buf, key.c_str()); }
-  }
-  if (strlen(buf) + 56 < sizeof buf)  // the lowering's division census (compile.h): with RN(1/d) / declined / polygons flagged / not flagged
-    snprintf(buf + strlen(buf), sizeof buf - strlen(buf), " recip=%d/%d/%d/%d", p->prog.n_recip, p->prog.n_recip_declined, p->prog.n_poly_recip, p->prog.n_poly_plain);
-  if (strlen(buf) + 1 > dst_cap) return fail(GSDF_ERR_SHORT_BUFFER, "short buffer");
-  std::memcpy(dst, buf, strlen(buf) + 1);
-  return GSDF_OK;
-}
-
-// Host-only (no GPU): the generated evaluator source of a tree's specialised build, and a hiprtc compile of the
-// specialised kernels for gfx950 that stops before loading them (proves the generated code builds).
-extern "C" int gsdf_hip_specialize_source(const gsdf_tree* tree, char* dst, size_t dst_cap, size_t* len) {
-  if (!tree) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
-  try {
-    const std::string s = gsdf_dev::spec_source(gsdf_dev::compile(*tree));
-    if (len) *len = s.size();
-    if (dst) {
-      if (dst_cap < s.size() + 1) return fail(GSDF_ERR_SHORT_BUFFER, "short buffer");
-      std::memcpy(dst, s.c_str(), s.size() + 1);
-    }
-    return GSDF_OK;
-  } catch (const std::exception& e) {
-    return fail(GSDF_ERR_BAD_TREE, e.what());
-  }
-}
-extern "C" int gsdf_hip_specialize_check(const gsdf_tree* tree, size_t* code_object_bytes) {
-  if (!tree) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
-  try {
-    const gsdf_dev::Program pr = gsdf_dev::compile(*tree);
-    std::vector<char> co;
-    std::vector<std::string> low;
-    std::string log;
-    const std::vector<std::string> names = pr.is2d ? std::vector<std::string>{"eval_kernel<2, 4, 4>"}
-                                                   : std::vector<std::string>{"eval_kernel<3, 4, 4>", "prune_kernel", "prune_spec_kernel", "leaf_eval_kernel<4, 4, true, true, false, false>", "leaf_eval_kernel<4, 4, true, true, true, true>", "leaf_dense_kernel<4, true, true>", "leaf_kernel<4, 4>", "flat_grid_kernel<4, 4>"};
-    if (!gsdf_dev::spec_compile(pr, "gfx950", names, co, low, log)) return fail(GSDF_ERR_HIP, "specialised build failed:\n" + log);
-    if (code_object_bytes) *code_object_bytes = co.size();
-    return GSDF_OK;
-  } catch (const std::exception& e) {
-    return fail(GSDF_ERR_BAD_TREE, e.what());
-  }
-}
-
 // Host-only (no GPU): lower a tree to the device instruction stream, for inspection/tests.
 extern "C" int gsdf_hip_lower(const gsdf_tree* tree, uint32_t* code_out, uint32_t code_cap, uint32_t* code_words, uint32_t* lds_slots) {
   if (!tree) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
@@ -659,12 +255,12 @@ static int eval_dev(gsdf_program* p, int dim, const void* d_pos, size_t stride_b
   spec_adopt(p);  // (a background build that has finished: its kernels from here on)
   static const bool k1_off = env_flag("GSDF_HIP_NO_EVAL_K1");  // developer knob (A/B timing)
   // This entry runs on several host threads at once (the host-buffer calls): the kernel it launches and what that kernel was built
-  // for are read as ONE snapshot under the mutex an adopting thread holds while it swaps them (spec_adopt_slow).
+  // for are read as ONE snapshot under the mutex every writer of them holds: adoption and the K = 1 group's build (abi_spec.hip).
   hipFunction_t f_eval = nullptr, f_eval_k1 = nullptr;
   int spec_eval_k = 0;
   {
     std::lock_guard<std::mutex> lk(p->spec_async_mu);
-    f_eval = p->f_eval; f_eval_k1 = p->f_eval_k1; spec_eval_k = p->spec_eval_k;
+    f_eval = p->spec.f_eval; f_eval_k1 = p->spec.f_eval_k1; spec_eval_k = p->spec.eval_k;
   }
   const bool latency = host_mapped && !k1_off && (f_eval_k1 != nullptr || f_eval == nullptr);  // (a specialised handle without a K = 1 build keeps its specialised kernel)
   const int k = latency ? 1 : p->batch_k();
@@ -769,7 +365,7 @@ static int eval_submit(gsdf_program* p, int dim, const void* pos, size_t stride,
     std::memcpy(sl.h_pos.p, pos, pbytes);
     if (hipHostGetDevicePointer(&dp, sl.h_pos.p, 0) != hipSuccess || hipHostGetDevicePointer(&dd, sl.h_dist.p, 0) != hipSuccess) return bail(fail(GSDF_ERR_HIP, "hipHostGetDevicePointer failed"));
   }
-  if (p->spec_mod && !p->spec_k1_tried) spec_eval_k1(p);
+  spec_ensure(p, SPEC_EVAL_K1);  // (eval_kernel<D, 1, 4> of a specialised handle, at its first host-mapped call)
   rc = eval_dev(p, dim, dp, stride, (float*)dd, n_pos, sl.s.s, /*count=*/false, /*host_mapped=*/true);
   if (rc) return bail(rc);
   // completion flag behind the kernel (eval_wait polls it; hipStreamSynchronize remains the fallback)
@@ -907,8 +503,8 @@ extern "C" int gsdf_hip_normals3(gsdf_program* p, const float* pos, float* norma
   int rc = GSDF_OK;
   do {
     if (hipMemcpyAsync(d_p, pos, n * 12, hipMemcpyHostToDevice, p->stream.s) != hipSuccess) { rc = fail(GSDF_ERR_HIP, "H2D copy failed"); break; }
-    spec_aux(p);
-    if (launch_kernel(normals_kernel, p->f_normals, grid_for(n, p->num_cu, 8), BLOCK, p->lds_bytes(2), p->stream.s, p->d_code.p, d_p, d_n, n, step) != hipSuccess) {
+    spec_ensure(p, SPEC_AUX);
+    if (launch_kernel(normals_kernel, p->spec.f_normals, grid_for(n, p->num_cu, 8), BLOCK, p->lds_bytes(2), p->stream.s, p->d_code.p, d_p, d_n, n, step) != hipSuccess) {
       rc = fail(GSDF_ERR_HIP, "normals kernel launch failed");
       break;
     }
@@ -931,8 +527,8 @@ int normals3_dev(gsdf_program* p, const float* d_pos, float* d_nrm, size_t n, fl
   if (int rc = p->normals_refused("the normals of an indexed mesh")) return rc;
   HIP_TRY(hipSetDevice(p->device));
   spec_adopt(p);
-  spec_aux(p);
-  HIP_TRY(launch_kernel(normals_kernel, p->f_normals, grid_for(n, p->num_cu, 8), BLOCK, p->lds_bytes(2), p->stream.s, p->d_code.p, d_pos, d_nrm, n, step));
+  spec_ensure(p, SPEC_AUX);
+  HIP_TRY(launch_kernel(normals_kernel, p->spec.f_normals, grid_for(n, p->num_cu, 8), BLOCK, p->lds_bytes(2), p->stream.s, p->d_code.p, d_pos, d_nrm, n, step));
   HIP_TRY(hipStreamSynchronize(p->stream.s));
   p->evals += 6 * n;
   return GSDF_OK;
@@ -949,7 +545,7 @@ int project_dev(gsdf_program* p, const float* d_pos, size_t n, const gsdf_projec
   if (int rc = p->normals_refused("gsdf_hip_indexed_project")) return rc;
   HIP_TRY(hipSetDevice(p->device));
   spec_adopt(p);
-  spec_project(p);
+  spec_ensure(p, SPEC_PROJECT);
   if (!p->proj_ctr.p) HIP_TRY(hipMalloc(&p->proj_ctr.p, sizeof(ProjectCounters)));
   HIP_TRY(p->ev_proj.ensure());
   const EventSet<2>& ev = p->ev_proj;
@@ -961,7 +557,7 @@ int project_dev(gsdf_program* p, const float* d_pos, size_t n, const gsdf_projec
   hipError_t e = hipMemsetAsync(d_ctr, 0, sizeof(ProjectCounters), p->stream.s);
   if (e == hipSuccess) e = hipEventRecord(ev[0], p->stream.s);
   if (e == hipSuccess)  // (the kernel takes the positions as words: (const unsigned*) cannot be left to the launcher's static_cast)
-    e = launch_kernel(project_kernel, p->f_project, grid, BLOCK, p->lds_bytes(2), p->stream.s, p->d_code.p, (const unsigned*)d_pos, n, h, o->tol, o->max_move, o->max_iters,
+    e = launch_kernel(project_kernel, p->spec.f_project, grid, BLOCK, p->lds_bytes(2), p->stream.s, p->d_code.p, (const unsigned*)d_pos, n, h, o->tol, o->max_move, o->max_iters,
                       (unsigned*)d_out_pos, d_before, d_after, d_status, d_ctr);
   if (e == hipSuccess) e = hipEventRecord(ev[1], p->stream.s);
   if (e == hipSuccess) e = hipMemcpyAsync(&hc, d_ctr, sizeof hc, hipMemcpyDeviceToHost, p->stream.s);
@@ -999,8 +595,8 @@ extern "C" int gsdf_hip_image2(gsdf_program* p, int w, int h, float* dist_out, u
   HIP_TRY(dc.alloc(n * 4));
   const int k = p->batch_k();
   const unsigned grid = grid_for((n + k - 1) / k, p->num_cu, 8);
-  spec_aux(p);
-  HIP_TRY(launch_kernel(k == 4 ? image2_kernel<4> : (k == 2 ? image2_kernel<2> : image2_kernel<1>), p->f_image, grid, BLOCK, p->lds_bytes(k), p->stream.s, p->d_code.p, w, h, xmin, ymax,
+  spec_ensure(p, SPEC_AUX);
+  HIP_TRY(launch_kernel(k == 4 ? image2_kernel<4> : (k == 2 ? image2_kernel<2> : image2_kernel<1>), p->spec.f_image, grid, BLOCK, p->lds_bytes(k), p->stream.s, p->d_code.p, w, h, xmin, ymax,
                         dx, dy, dd.p, dc.p));
   if (dist_out) HIP_TRY(hipMemcpyAsync(dist_out, dd.p, n * 4, hipMemcpyDeviceToHost, p->stream.s));
   if (rgba_out) HIP_TRY(hipMemcpyAsync(rgba_out, dc.p, n * 4, hipMemcpyDeviceToHost, p->stream.s));
@@ -1093,7 +689,7 @@ extern "C" int gsdf_hip_render3(gsdf_program* p, const gsdf_view* view, int w, i
   }
   HIP_TRY(hipSetDevice(p->device));
   spec_adopt(p);  // (a background build that has finished: its kernels from here on)
-  spec_view(p);
+  spec_ensure(p, SPEC_VIEW);
   ViewCam cam;
   for (int a = 0; a < 3; a++) { cam.ro[a] = view->ro[a]; cam.uu[a] = view->uu[a]; cam.vv[a] = view->vv[a]; cam.ww[a] = view->ww[a]; }
   cam.tmax = 1.3f * view->char_dist;
@@ -1118,7 +714,7 @@ extern "C" int gsdf_hip_render3(gsdf_program* p, const gsdf_view* view, int w, i
   float* o_depth = (float*)d_depth.p;
   uint32_t* o_evals = (uint32_t*)d_evals.p;
   unsigned long long* o_ctr = (unsigned long long*)d_ctr.p;
-  HIP_TRY(launch_kernel(plain ? view_kernel<false> : view_kernel<true>, plain ? p->f_view_plain : p->f_view, grid, BLOCK, lds, p->stream.s, p->d_code.p, cam, o_rgba, o_depth, o_evals,
+  HIP_TRY(launch_kernel(plain ? view_kernel<false> : view_kernel<true>, plain ? p->spec.f_view_plain : p->spec.f_view, grid, BLOCK, lds, p->stream.s, p->d_code.p, cam, o_rgba, o_depth, o_evals,
                         o_ctr));
   unsigned long long h_ctr[2] = {0, 0};
   if (rgba_out) HIP_TRY(hipMemcpyAsync(rgba_out, d_rgba.p, n * 4, hipMemcpyDeviceToHost, p->stream.s));
@@ -1193,7 +789,7 @@ extern "C" int gsdf_hip_image2_color(gsdf_program* p, const gsdf_color2* conv, i
     return fail(GSDF_ERR_BAD_ARGUMENT, "gradient length must be >= 0");
   HIP_TRY(hipSetDevice(p->device));
   spec_adopt(p);  // (a background build that has finished: its kernels from here on)
-  spec_image_color(p);
+  spec_ensure(p, SPEC_PICTURE);
   const size_t n = (size_t)w * (size_t)h;
   // gsdf_hip_image2's lattice, statement for statement
   const float szx = p->prog.bb[3] - p->prog.bb[0], szy = p->prog.bb[4] - p->prog.bb[1];
@@ -1212,7 +808,7 @@ extern "C" int gsdf_hip_image2_color(gsdf_program* p, const gsdf_color2* conv, i
   const int k = p->batch_k();
   const unsigned grid = grid_for((n + k - 1) / k, p->num_cu, 8);
   // (the interpreter's kernel takes the conversion kind as an argument, a per-tree one is built for its kind)
-  HIP_TRY(launch_kernel(k == 4 ? image2_color_kernel<4, -1> : (k == 2 ? image2_color_kernel<2, -1> : image2_color_kernel<1, -1>), p->f_imgc[conv->kind], grid, BLOCK, p->lds_bytes(k),
+  HIP_TRY(launch_kernel(k == 4 ? image2_color_kernel<4, -1> : (k == 2 ? image2_color_kernel<2, -1> : image2_color_kernel<1, -1>), p->spec.f_imgc[conv->kind], grid, BLOCK, p->lds_bytes(k),
                         p->stream.s, p->d_code.p, w, h, xmin, ymax, dx, dy, cv, o_dist, o_rgba));
   if (dist_out) HIP_TRY(hipMemcpyAsync(dist_out, dd.p, n * 4, hipMemcpyDeviceToHost, p->stream.s));
   if (rgba_out) HIP_TRY(hipMemcpyAsync(rgba_out, dc.p, n * 4, hipMemcpyDeviceToHost, p->stream.s));

@@ -234,7 +234,7 @@ int gsdf_mesh_job::enqueue_descent() {
     spec_top_S = levels | (S << 8);
     spec_mask = test_mask;
     const int shard_level = opts.shard_count > 1 ? ls : -1;
-    HIP_TRY(launch_kernel(prune_spec_kernel, p->f_prune_spec, grid_for(n_spec, p->num_cu, 8), BLOCK, lds_prune, s, p->d_code.p, levels, n_spec, prune_cols, p->prog.nslots, ox, oy,
+    HIP_TRY(launch_kernel(prune_spec_kernel, p->spec.f_prune_spec, grid_for(n_spec, p->num_cu, 8), BLOCK, lds_prune, s, p->d_code.p, levels, n_spec, prune_cols, p->prog.nslots, ox, oy,
                           oz, res, test_mask, ptest, shard_level, opts.shard_rank, opts.shard_count, w.spec_pass.p, (unsigned*)d_ctr, clear_bytes / 4, d_mask16, n_spec - n_last));
     hipLaunchKernelGGL(prune_resolve_kernel, dim3((n_spec + SPEC_STAGE - 1) / SPEC_STAGE), dim3(BLOCK), 0, s, (const uint8_t*)w.spec_pass.p, levels, S,
                        n_spec, test_mask, q[last_spec & 1], (unsigned long long)capq[last_spec & 1], d_ctr, spec_part,
@@ -249,7 +249,7 @@ int gsdf_mesh_job::enqueue_descent() {
     // upper bound of candidates at this level (for the grid only): 8^(levels-level), capped by the queue
     uint64_t bound = (levels - level) * 3 >= 40 ? UINT64_MAX : ((uint64_t)1 << (3 * (levels - level)));
     if (bound > capq[(level + 1) & 1] * 8) bound = capq[(level + 1) & 1] * 8;
-    HIP_TRY(launch_kernel(prune_kernel, p->f_prune, grid_for(bound, p->num_cu, prune_bpc), BLOCK, lds_prune, s, p->d_code.p, q[(level + 1) & 1], capq[(level + 1) & 1], expand, level,
+    HIP_TRY(launch_kernel(prune_kernel, p->spec.f_prune, grid_for(bound, p->num_cu, prune_bpc), BLOCK, lds_prune, s, p->d_code.p, q[(level + 1) & 1], capq[(level + 1) & 1], expand, level,
                           prune_cols, p->prog.nslots, ox, oy, oz, res, do_test, q[level & 1], capq[level & 1], (opts.shard_count > 1 && level == ls) ? 1 : 0, opts.shard_rank,
                           opts.shard_count, d_ctr, level == first_level ? spec_part : nullptr, spec_rows, spec_top_S, spec_mask));
   }
@@ -288,12 +288,12 @@ int gsdf_mesh_job::enqueue_leaf() {
   // share_corners = 2: the distinct z rows of a brick once each (kernels_octree.h: DZ) -- column bricks at four points per lane
   const bool want_dz = opts.share_corners == 2 && lq == 3 && lk == 4;
   if (used_dense) {
-    spec_leaf_dense(p);
+    spec_ensure(p, SPEC_DENSE);
     const size_t lds_d = p->lds_dense();
-    HIP_TRY(launch_kernel(leaf_dense_aot(3 * lds_d <= gsdf_program::kLdsPerCu ? 3 : 2), p->f_leaf_dense, grid, BLOCK, lds_d, s, p->d_code.p, cubes, ncubes, p->prog.nslots, ox, oy, oz, res,
+    HIP_TRY(launch_kernel(leaf_dense_aot(3 * lds_d <= gsdf_program::kLdsPerCu ? 3 : 2), p->spec.f_leaf_dense, grid, BLOCK, lds_d, s, p->d_code.p, cubes, ncubes, p->prog.nslots, ox, oy, oz, res,
                           d_hdr, d_rec, d_psum, nblk, d_ctr, use_masks));
   } else {
-    if (want_dz) spec_leaf_dz(p);
+    if (want_dz) spec_ensure(p, SPEC_ROWS);
     const LeafPick pick = p->leaf_pick(lq, want_dz);
     used_dz = pick.v.dz;
     // (fewer than three levels: a few leaves per pass, and room for the case table whether lds_m counts it or not)
@@ -747,7 +747,7 @@ static int dc_mesh(gsdf_program* p, float res, int chiseled, int shard_rank, int
   DcIndexedWs ixw{};
   const float h = (chiseled ? (float)1e-4 : (float)2e-8) * 0.5f;  // NormalsCentralDiff: step *= 0.5
   const float sqrtLambda = chiseled ? (float)(std::sqrt(1e-5) * 1e-4) : (float)std::sqrt(1e-5);
-  spec_aux(p);
+  spec_ensure(p, SPEC_AUX);
   const int ub = p->prog.has_exact_bb ? 1 : 0;
   const float* eb = p->prog.exact_bb;
   // tile range of the origin sweep (8 x 8 x 4K cells per tile, z tiles counted from zlo)
@@ -807,7 +807,7 @@ static int dc_mesh(gsdf_program* p, float res, int chiseled, int shard_rank, int
       // (a tree whose interval stack makes the test ask for more LDS than a CU has goes without it: every block is evaluated)
       if (!block_test_off && nblk > 0 && lds_t <= gsdf_program::kLdsPerCu && p->dc_tile.ensure((size_t)nblk * sizeof(uint32_t)) == hipSuccess) {
         const unsigned gt = grid_for(nblk, p->num_cu, 8);
-        HIP_TRYM(launch_kernel(dc_block_test_kernel, p->f_dc_block_test, gt, BLOCK, lds_t, s, p->d_code.p, cols, p->prog.nslots, lk, ox, oy, oz, res, zlo, t0[0], t0[1], t0[2], tn[0],
+        HIP_TRYM(launch_kernel(dc_block_test_kernel, p->spec.f_dc_block_test, gt, BLOCK, lds_t, s, p->d_code.p, cols, p->prog.nslots, lk, ox, oy, oz, res, zlo, t0[0], t0[1], t0[2], tn[0],
                                tn[1], tn[2], p->dc_tile.p));
         // ... and "no cube here" in the cleared tiles next to evaluated ones: the cells the later stages read and the sweep does not write
         hipLaunchKernelGGL(dc_grid_clear_kernel, dim3(grid_for((uint64_t)((tn[0] + 3) / 4) * ((tn[1] + 3) / 4) * ((tn[2] + 3) / 4) * BLOCK, p->num_cu, 16)), dim3(BLOCK), 0, s, (int*)grid.p, nshift, lk, zlo, zhi, t0[0], t0[1], t0[2], tn[0], tn[1],
@@ -820,18 +820,18 @@ static int dc_mesh(gsdf_program* p, float res, int chiseled, int shard_rank, int
     }
     {  // (a per-tree kernel is the same launch whichever W it was built for)
       const dc_origin_kernel_t aot = dc_origin_aot(gsdf_program::dc_origin_variant(lk));
-      if (!aot && !p->f_dc_origin) return bail(fail(GSDF_ERR_BAD_ARGUMENT, "dual contouring: no origin sweep built for this K and W"));
-      HIP_TRYM(launch_kernel(aot, p->f_dc_origin, g1, BLOCK, p->lds_bytes(lk) + 32, s, p->d_code.p, p->prog.nslots, nshift, ox, oy, oz, res, grid.p, w0.q0.p, ccap, zlo, zhi, ub, eb[0], eb[1],
+      if (!aot && !p->spec.f_dc_origin) return bail(fail(GSDF_ERR_BAD_ARGUMENT, "dual contouring: no origin sweep built for this K and W"));
+      HIP_TRYM(launch_kernel(aot, p->spec.f_dc_origin, g1, BLOCK, p->lds_bytes(lk) + 32, s, p->d_code.p, p->prog.nslots, nshift, ox, oy, oz, res, grid.p, w0.q0.p, ccap, zlo, zhi, ub, eb[0], eb[1],
                              eb[2], eb[3], eb[4], eb[5], t0[0], t0[1], t0[2], tn[0], tn[1], tn[2], d_ctr, d_keep));
     }
     HIP_TRYM(hipEventRecord(p->dc_ev[0], s));  // origin sweep done
     // (a multiple of DC_PARTS like the sweep's grid: run r goes to workgroup r % grid, hence to the edge list's part r % DC_PARTS --
     // what bounds a part's edge-run descriptors, dc_edge_run_seg)
     const unsigned g_edges = (grid_for(ccap, p->num_cu, 8) + DC_PARTS - 1) / DC_PARTS * DC_PARTS;
-    HIP_TRYM(launch_kernel(dc_edges_kernel, p->f_dc_edges, g_edges, BLOCK, p->lds_bytes(3), s, p->d_code.p, w0.q0.p, ccap, ox, oy, oz, res, d2.p, f2.p, e2.p, ecap, p->dc_erun.p, ntiles, grid.p,
+    HIP_TRYM(launch_kernel(dc_edges_kernel, p->spec.f_dc_edges, g_edges, BLOCK, p->lds_bytes(3), s, p->d_code.p, w0.q0.p, ccap, ox, oy, oz, res, d2.p, f2.p, e2.p, ecap, p->dc_erun.p, ntiles, grid.p,
                            nshift, p->dc_flag.p, d_ctr));
     HIP_TRYM(hipEventRecord(p->dc_ev[1], s));  // edges done
-    HIP_TRYM(launch_kernel(dc_normals_kernel, p->f_dc_normals, grid_for(ecap, p->num_cu, 8), BLOCK, p->lds_bytes(2), s, p->d_code.p, w0.q0.p, d2.p, e2.p, p->dc_erun.p, ccap, ntiles, ox, oy, oz,
+    HIP_TRYM(launch_kernel(dc_normals_kernel, p->spec.f_dc_normals, grid_for(ecap, p->num_cu, 8), BLOCK, p->lds_bytes(2), s, p->d_code.p, w0.q0.p, d2.p, e2.p, p->dc_erun.p, ccap, ntiles, ox, oy, oz,
                            res, h, n2.p, d_ctr));
     HIP_TRYM(hipEventRecord(p->dc_ev[2], s));  // normals done
     hipLaunchKernelGGL(dc_place_kernel, dim3(grid_for(ccap * 4, p->num_cu, 16)), dim3(DC_BLOCK), 0, s, (const Cube*)w0.q0.p,
@@ -1108,14 +1108,14 @@ extern "C" int gsdf_hip_mesh_flat(gsdf_program* p, float res, int shard_rank, in
   unsigned long long* negbits = (unsigned long long*)p->flat_bits.p;
   unsigned long long* nearbits = negbits + (size_t)wpp * nk;
   const int ek = p->batch_k();
-  spec_aux(p);
+  spec_ensure(p, SPEC_AUX);
   HIP_TRYM(hipEventRecord(ev[0], s));
   {
     const uint64_t npass = ((sxy + (uint64_t)BLOCK - 1) / (uint64_t)BLOCK) * ((nk + ek - 1) / ek);
     static const int bpc = env_int("GSDF_HIP_EVAL_BPC", 64);
     const uint64_t gmax = (uint64_t)p->num_cu * (uint64_t)(bpc > 0 ? bpc : 64);
     const unsigned g = (unsigned)(npass < gmax ? npass : gmax);
-    HIP_TRYM(launch_kernel(flat_grid_aot(p->sweep_variant(ek)), p->f_flat_grid, g, BLOCK, p->lds_bytes(ek), s, p->d_code.p, ox, oy, oz, res, sx, sy, c0, nk, grid, negbits, nearbits));
+    HIP_TRYM(launch_kernel(flat_grid_aot(p->sweep_variant(ek)), p->spec.f_flat_grid, g, BLOCK, p->lds_bytes(ek), s, p->d_code.p, ox, oy, oz, res, sx, sy, c0, nk, grid, negbits, nearbits));
   }
   HIP_TRYM(hipEventRecord(ev[1], s));
   // ReadTriangles: the triangle count is not known in advance; the pass is cheap (HBM-bound over the grid), so a

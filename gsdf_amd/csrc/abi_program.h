@@ -1,6 +1,7 @@
 // abi_program.h -- the program handle and the launch helpers of the translation units that own kernels (abi_eval.hip,
-// abi_mesh.hip, abi_indexed.hip). Include after the kernel headers: the handle's LDS arithmetic uses their constants (BLOCK, TRI_STAGE, ...).
-// What the handle owns frees itself (Arena, Owned, EventSet, Stream, Modules below): gsdf_hip_program_destroy is `delete`.
+// abi_mesh.hip, abi_indexed.hip, abi_contour.hip) and of abi_spec.hip, which builds the handle's per-tree kernels. Include after
+// kernels_common.h: the handle's LDS arithmetic uses its constants (BLOCK, TRI_STAGE, ...).
+// What the handle owns frees itself (Arena, Owned, EventSet, Stream, SpecKernels below): gsdf_hip_program_destroy is `delete`.
 #pragma once
 #include <condition_variable>
 #include <mutex>
@@ -58,18 +59,6 @@ struct Stream : NoCopy {
   ~Stream() { if (s) (void)hipStreamDestroy(s); }
   hipError_t ensure() { return s ? hipSuccess : hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
 };
-// run-time modules a handle has loaded beside its first (gsdf_program::spec_mod): unloaded with the handle
-struct Modules : NoCopy {
-  std::mutex mu;  // (the builders run on whichever thread first needs a kernel: a mesher's and a host-buffer call's may meet here)
-  std::vector<hipModule_t> v;
-  ~Modules() { for (hipModule_t m : v) (void)hipModuleUnload(m); }
-  void keep(hipModule_t m) { if (m) { std::lock_guard<std::mutex> lk(mu); v.push_back(m); } }
-  void take(Modules& from) {
-    std::lock_guard<std::mutex> lk(mu);
-    v.insert(v.end(), from.v.begin(), from.v.end());
-    from.v.clear();
-  }
-};
 
 // ---- kernel variants as data ----------------------------------------------------------------------------------------------------
 // Which instantiation a launch site runs, and what it is called: the name expression the run-time compiler is handed
@@ -95,6 +84,40 @@ struct LeafVariant {  // leaf_kernel<K, W> (fused) | leaf_eval_kernel<K, W, UCUB
   }
 };
 struct LeafPick { LeafVariant v; hipFunction_t f; };  // f: the handle's per-tree build of v; null: the ahead-of-time kernel of v
+
+// ---- everything a per-tree ("specialised") build of a handle has produced (abi_spec.hip) -----------------------------------------
+// The groups of kernels a specialised handle builds the first time an entry point needs them (spec_ensure): the evaluating kernels of
+// dual contouring, normals, the flat lattice pass and the 2-D image; distinct z rows (share_corners = 2; kernels_octree.h: DZ);
+// eval_kernel<D, 1, 4> for host-mapped calls; distinct lattice points (share_corners = 1: leaf_dense_kernel); the UI's view
+// (kernels_view.h); the projection of mesh vertices (kernels_project.h); the 2-D picture, one kernel per conversion kind (kernels_image.h).
+enum SpecGroup { SPEC_AUX, SPEC_ROWS, SPEC_EVAL_K1, SPEC_DENSE, SPEC_VIEW, SPEC_PROJECT, SPEC_PICTURE, SPEC_GROUPS };
+struct SpecBuilt {  // what was built, for which template arguments, by what
+  std::vector<hipModule_t> mods;  // the first group's module, then every later one (a kernel rebuilt for another W, the groups above)
+  int eval_k = 0, eval_w = 0, leaf_k = 0, leaf_w = 0, rows_w = 0, dense_w = 0;
+  bool leaf_both = false, rows_both = false;  // both column passes in one body (kernels_octree.h: BOTH)
+  std::string compiler, key;  // hipcc | hiprtc | cache; key of the first group's build (specialize.cpp: build_key)
+  double compile_s = 0;
+};
+struct SpecFns {  // null: the ahead-of-time (interpreter) kernel runs
+  hipFunction_t f_eval = nullptr, f_eval_k1 = nullptr, f_prune = nullptr, f_prune_spec = nullptr, f_leaf = nullptr, f_leaf_dz = nullptr, f_leaf_dense = nullptr;
+  hipFunction_t f_dc_block_test = nullptr, f_dc_origin = nullptr, f_dc_edges = nullptr, f_dc_normals = nullptr, f_normals = nullptr, f_image = nullptr, f_flat_grid = nullptr;
+  hipFunction_t f_view = nullptr, f_view_plain = nullptr, f_project = nullptr, f_imgc[4] = {nullptr, nullptr, nullptr, nullptr};
+};
+struct SpecKernels : SpecBuilt, SpecFns, NoCopy {
+  std::atomic<unsigned> todo{0};  // bit g: group g is still to be tried. 0 on a handle that is not specialised: spec_ensure's lock-free exit
+  ~SpecKernels() { for (hipModule_t m : mods) (void)hipModuleUnload(m); }
+  bool specialised() const { return !mods.empty(); }
+  // Everything `from` built becomes this one's, whatever members the structs above have: the configuration before the functions (a
+  // reader that sees a function sees what it was built for), the groups to build last. What this one held goes away with `from`,
+  // except the seconds it spent compiling.
+  void take(SpecKernels& from) {
+    std::swap(static_cast<SpecBuilt&>(*this), static_cast<SpecBuilt&>(from));
+    compile_s += from.compile_s;
+    std::atomic_thread_fence(std::memory_order_release);
+    static_cast<SpecFns&>(*this) = from;
+    todo.store(from.todo.load(), std::memory_order_release);
+  }
+};
 
 // Leaf phase: two kernels by default (leaf_eval_kernel: evaluation + cut-leaf records, no barrier and no atomic in its
 // loop; march_records_kernel: marching cubes over the records); GSDF_HIP_FUSED_LEAF=1 keeps the fused leaf_kernel.
@@ -169,58 +192,26 @@ struct gsdf_program {
   uint64_t last_recs = 0;  // cut leaves of the previous mesh with payload = records: sizes the next payload buffer
   uint64_t rec_blocks = 0;  // 64-leaf blocks the cut-leaf record arena is sized for (0: first mesh, start with kRecBlocks0)
   uint64_t last_dc_cubes = 0;  // kept cubes of the previous dual contouring pass: sizes the next queues
-  // run-time specialised kernels for this program (gsdf_hip_program_specialize): hiprtc module, else interpreter. spec_mod, the
-  // first group's module, being non-null means "specialised"; every later module (the eval kernel rebuilt for 3 workgroups per CU,
-  // the leaf kernel rebuilt with a larger register budget, the groups built on first use below) is kept in mods.
-  hipModule_t spec_mod = nullptr;
-  Modules mods;
-  hipFunction_t f_eval_k1 = nullptr;  // eval_kernel<D, 1, 4>: one point per lane, for host-mapped calls (abi_eval.hip: eval_dev, spec_eval_k1)
-  bool spec_k1_tried = false;
-  hipFunction_t f_eval = nullptr, f_prune = nullptr, f_prune_spec = nullptr, f_leaf = nullptr;
-  hipFunction_t f_dc_block_test = nullptr;  // the interval test of dual contouring's origin sweep, block by block (kernels_dc.h: dc_block_test_kernel)
-  hipFunction_t f_dc_origin = nullptr, f_dc_edges = nullptr, f_dc_normals = nullptr, f_normals = nullptr, f_image = nullptr, f_flat_grid = nullptr;
-  bool spec_aux_tried = false;
-  int spec_eval_k = 0, spec_eval_w = 0, spec_leaf_k = 0, spec_leaf_w = 0;
-  bool spec_leaf_both = false;  // the specialised leaf kernel has both column passes in one body (kernels_octree.h: BOTH)
-  // distinct z rows (gsdf_mesh_opts.share_corners = 2; kernels_octree.h: DZ): built the first time a mesh asks for it (spec_leaf_dz)
-  hipFunction_t f_leaf_dz = nullptr;
-  bool spec_dz_tried = false, spec_leaf_dz_both = false;
-  int spec_leaf_dz_w = 0;
-  // distinct lattice points (share_corners = 1; kernels_octree.h: leaf_dense_kernel): likewise built on first use (spec_leaf_dense)
-  hipFunction_t f_leaf_dense = nullptr;
-  bool spec_dense_tried = false;
-  int spec_leaf_dense_w = 0;
+  // run-time specialised kernels for this program (gsdf_hip_program_specialize): per-tree modules, else the interpreter's kernels.
+  // Written under spec_async_mu by adoption and by spec_ensure; the host-buffer calls, which may run on several threads, read their
+  // kernels under it too (abi_eval.hip: eval_dev). Every other reader relies on the one-caller-at-a-time rule of gsdf_hip.h.
+  SpecKernels spec;
   size_t lds_dense() const { return (size_t)(prog.nslots * 4 > 8 ? prog.nslots * 4 : 8) * BLOCK * sizeof(float) + 256 + 4 * 512 * sizeof(float) + 4 * 24 * sizeof(float) + 16; }
-  // the UI's view (kernels_view.h: view_kernel<REFILL>, <plain>) for a specialised handle: built on its first frame (spec_view)
-  hipFunction_t f_view = nullptr, f_view_plain = nullptr;
-  bool spec_view_tried = false;
-  // the projection of mesh vertices onto the field (kernels_project.h: project_kernel) for a specialised handle: built on its first
-  // projection (spec_project)
-  hipFunction_t f_project = nullptr;
-  bool spec_project_tried = false;
-  DevPtr<void> proj_ctr;  // its counters on the device and the two events around its launch: made at the
+  DevPtr<void> proj_ctr;  // the projection's counters on the device and the two events around its launch: made at the
   EventSet<2> ev_proj;    // first projection, kept for the next (project_dev)
-  // the 2-D picture (kernels_image.h: image2_color_kernel<K, kind> per conversion kind) for a specialised handle: built on its first
-  // gsdf_hip_image2_color (spec_image_color)
-  hipFunction_t f_imgc[4] = {nullptr, nullptr, nullptr, nullptr};
-  bool spec_imgc_tried = false;
-  double spec_compile_s = 0;
   // Specialisation in the background (gsdf_hip_program_specialize_async): a thread builds and loads the kernels on a shadow handle
   // (this program, this device, nothing else) while the interpreter kernels serve; the entry points adopt the result at their
-  // next call (abi_eval.hip: spec_adopt). 0 idle | 1 building | 2 built, to be adopted | 3 failed (spec_async_err)
+  // next call (abi_spec.hip: spec_adopt). 0 idle | 1 building | 2 built, to be adopted | 3 failed (spec_async_err)
   std::atomic<int> spec_async{0};
   std::thread spec_thread;
   gsdf_program* spec_shadow = nullptr;
   std::mutex spec_async_mu;
   std::string spec_async_err;
-  std::string spec_compiler;  // hipcc | hiprtc | cache: what built the specialised kernels
-  std::string spec_key;       // key of that build (specialize.cpp: build_key)
   // A build under way finishes first (its thread writes into this handle), then the shadow handle goes; the members free
-  // themselves in reverse order of declaration: modules, events, device and pinned memory, the streams last.
+  // themselves in reverse order of declaration: modules (spec), events, device and pinned memory, the streams last.
   ~gsdf_program() {
     if (spec_thread.joinable()) spec_thread.join();
     delete spec_shadow;
-    if (spec_mod) (void)hipModuleUnload(spec_mod);
   }
   // leaf kernel batching: K = 4 while 3 workgroups still fit the CU's LDS (<= 11 slots); 12..15 slots run K = 2 at 4
   // waves/SIMD instead of K = 4 at 2 (knurled-cylinder: 23.3 vs 23.8 ms). A 4th wave per SIMD is worth more than the
@@ -255,12 +246,12 @@ struct gsdf_program {
   // specialised kernel (v.dz comes back false). The per-tree kernel is the same launch whichever W it was built for.
   LeafPick leaf_pick(int lq, bool rows = false) const {
     const LeafConfig c = leaf_config();
-    const bool spec = f_leaf && spec_leaf_k == c.k;
+    const bool own = spec.f_leaf && spec.leaf_k == c.k;
     const int aw = leaf_aot_waves(c.k, c.w);
-    if (fused_leaf()) return spec ? LeafPick{{true, c.k, spec_leaf_w, false, false, false, false}, f_leaf} : LeafPick{{true, c.k, aw, false, false, false, false}, nullptr};
-    if (rows && f_leaf_dz) return {{false, 4, spec_leaf_dz_w, true, c.ntlds, spec_leaf_dz_both, true}, f_leaf_dz};
-    if (rows && !spec) return {{false, 4, aw, true, c.ntlds, false, true}, nullptr};
-    if (spec && lq == 3) return {{false, c.k, spec_leaf_w, true, c.ntlds, spec_leaf_both, false}, f_leaf};
+    if (fused_leaf()) return own ? LeafPick{{true, c.k, spec.leaf_w, false, false, false, false}, spec.f_leaf} : LeafPick{{true, c.k, aw, false, false, false, false}, nullptr};
+    if (rows && spec.f_leaf_dz) return {{false, 4, spec.rows_w, true, c.ntlds, spec.rows_both, true}, spec.f_leaf_dz};
+    if (rows && !own) return {{false, 4, aw, true, c.ntlds, false, true}, nullptr};
+    if (own && lq == 3) return {{false, c.k, spec.leaf_w, true, c.ntlds, spec.leaf_both, false}, spec.f_leaf};
     return {{false, c.k, aw, lq == 3, lq == 3 ? c.ntlds : true, false, false}, nullptr};
   }
   size_t lds_bytes(int k = 1) const { return (size_t)(prog.nslots > 0 ? prog.nslots : 1) * k * BLOCK * sizeof(float); }
@@ -327,16 +318,13 @@ inline unsigned grid_for(uint64_t n, int num_cu, int blocks_per_cu) {
   return (unsigned)b;
 }
 
-// Second group of a specialised handle (dual contouring, normals, flat lattice pass, image renderer), built on first use:
-// abi_eval.hip.
-void spec_aux(gsdf_program* p);
 // A background build (gsdf_hip_program_specialize_async) that has finished is taken over here: called at the top of the entry
-// points that launch evaluating kernels. One relaxed load when there is nothing to adopt.
+// points that launch evaluating kernels. One relaxed load when there is nothing to adopt. abi_spec.hip.
 void spec_adopt_slow(gsdf_program* p);
 inline void spec_adopt(gsdf_program* p) { if (p->spec_async.load(std::memory_order_acquire) == 2) spec_adopt_slow(p); }
-// The evaluating kernel with distinct z rows for a specialised handle, built on first use: abi_eval.hip.
-void spec_leaf_dz(gsdf_program* p);
-void spec_leaf_dense(gsdf_program* p);
+// The kernels of group g for a specialised handle, built the first time an entry point asks (abi_spec.hip). One atomic load and no
+// lock where there is nothing to build: the handle is not specialised, or the group has been tried.
+void spec_ensure(gsdf_program* p, SpecGroup g);
 // gleval.NormalsCentralDiff on device-resident points (abi_eval.hip; what gsdf_hip_normals3 launches): blocking.
 int normals3_dev(gsdf_program* p, const float* d_pos, float* d_nrm, size_t n, float step);
 // The projection of device-resident points onto the field (abi_eval.hip; what gsdf_hip_indexed_project launches; gsdf_hip.h states
@@ -344,12 +332,6 @@ int normals3_dev(gsdf_program* p, const float* d_pos, float* d_nrm, size_t n, fl
 // each optional; st->n_verts .. steps_max and ms_device are filled. Blocking. The options are the caller's to check.
 int project_dev(gsdf_program* p, const float* d_pos, size_t n, const gsdf_project_opts* o, float* d_out_pos, float* d_before, float* d_after,
                 uint8_t* d_status, gsdf_project_stats* st);
-// project_kernel for a specialised handle, built at its first projection: abi_eval.hip.
-void spec_project(gsdf_program* p);
-// The view kernels for a specialised handle, built on its first gsdf_hip_render3: abi_eval.hip.
-void spec_view(gsdf_program* p);
-// The picture kernels for a specialised 2-D handle, built on its first gsdf_hip_image2_color: abi_eval.hip.
-void spec_image_color(gsdf_program* p);
 
 namespace {
 // ms3.Box.ScaleCentered(1.01) = NewCenteredBox(Center(), MulElem(scale, Size())) [external]; float32, unfused.

@@ -175,6 +175,82 @@ def test_background_specialisation(gpu, tmp_path, monkeypatch):
     assert gpu.SDF3HIP(s).specialize_poll() is False
 
 
+def _sphere_and_box(b):
+    """A handful of slots (K = 4): small enough that every per-tree build is a second, large enough to take every group."""
+    return b.Union(b.NewSphere(1.0), b.Translate(b.NewBox(1.2, 0.9, 1.6, 0.1), 0.45, 0.2, -0.15))
+
+
+def test_adoption_takes_everything_the_build_produced(gpu, tmp_path, monkeypatch):
+    """A handle that adopted a background build reports, key for key, what a handle of the same tree specialised synchronously
+    reports (but for who compiled: the second build is a cache read) -- at once, and after the groups built on first use (distinct
+    rows, distinct points, normals) have been built on both. Every result is the oracle's, bit for bit."""
+    monkeypatch.setenv("GSDF_HIP_CACHE_DIR", str(tmp_path))
+    b = Builder()
+    sh = _sphere_and_box(b)
+    ref = OracleSDF(sh.tree())
+    bg = gpu.SDF3HIP(sh).specialize_async()
+    assert bg.specialize_poll(wait=True) and bg.info()["specialized"]
+    fg = gpu.SDF3HIP(sh).specialize()
+    assert fg.info()["leaf_k"] == 4
+
+    def report(sdf):
+        k = dict(sdf.info()["kernels"])
+        assert k.pop("compiler") in ("cache", "hipcc", "hiprtc")
+        return k
+    assert report(bg) == report(fg) and "specialised" in report(bg)["leaf"] and "specialised" in report(bg)["eval"]
+    res = np.float32(float(sh.Diagonal()) / 20)
+    want = _sorted(ref.render_octree(res, 4096, True).tris)
+    rng = np.random.default_rng(5)
+    bb = sh.Bounds()
+    pos = (bb[:3] + rng.random((256, 3), np.float32) * (bb[3:] - bb[:3])).astype(np.float32)
+    nrm = ref.normals_central_diff(pos, 1e-3)
+    for sdf in (bg, fg):
+        for share in (0, 2, 1):
+            got = _sorted(gpu.OctreeHIP(sdf, res, share_corners=share).RenderAll())
+            assert got.shape == want.shape and (got.view(np.uint32) == want.view(np.uint32)).all(), share
+        assert _mismatch(sdf.normals(pos, 1e-3).ravel(), nrm.ravel()) == 0
+    assert report(bg) == report(fg)
+
+
+def test_concurrent_first_use_of_the_one_point_kernel(gpu, tmp_path, monkeypatch):
+    """Four host threads make the first host-mapped Evaluate calls of a freshly specialised handle at the same moment: the call
+    that builds eval_kernel<3,1,4> on first use. Every result, and a fifth call's afterwards, is the oracle's."""
+    import threading
+    monkeypatch.setenv("GSDF_HIP_CACHE_DIR", str(tmp_path))
+    b = Builder()
+    sh = _sphere_and_box(b)
+    ref = OracleSDF(sh.tree())
+    bb = sh.Bounds()
+    rng = np.random.default_rng(6)
+    n = 4096
+    bufs = []
+    for _ in range(5):
+        ppos, pdist = gpu.host_array((n, 3)), gpu.host_array((n,))
+        ppos[:] = (bb[:3] + rng.random((n, 3), np.float32) * (bb[3:] - bb[:3])).astype(np.float32)
+        pdist[:] = np.nan
+        bufs.append((ppos, pdist, ref.Evaluate(np.array(ppos))))
+    sdf = gpu.SDF3HIP(sh).specialize()
+    gate = threading.Barrier(4)
+    errs = []
+
+    def call(i):
+        try:
+            gate.wait()
+            sdf.Evaluate(bufs[i][0], bufs[i][1])
+        except Exception as e:   # (an assertion in a thread would be lost)
+            errs.append(repr(e))
+    th = [threading.Thread(target=call, args=(i,)) for i in range(4)]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join()
+    assert not errs, errs
+    sdf.Evaluate(bufs[4][0], bufs[4][1])
+    for i, (_, pdist, want) in enumerate(bufs):
+        assert _mismatch(np.asarray(pdist), want) == 0, i
+    assert sdf.Evaluations() == 5 * n
+
+
 def test_rotated_screws_through_the_short_atan2_route(gpu):
     """A screw under a general rotation leaves no two points of a lane with equal x, y in its frame: every point takes math32.Atan2
     on its own, which the specialised kernels evaluate by the short float64 route (dm::atan2_fast, accepted only where its float32 is

@@ -38,7 +38,7 @@ def device_code_object(lib_path, workdir):
     subprocess.check_output([os.path.join(LLVM, "llvm-objdump"), "--offloading", local], text=True, cwd=workdir)
     objs = [os.path.join(workdir, f) for f in sorted(os.listdir(workdir)) if "amdgcn" in f and "gfx950" in f]
     assert objs, "no gfx950 code object in " + lib_path
-    return objs  # one per translation unit that owns kernels (abi_eval.hip, abi_mesh.hip, abi_indexed.hip)
+    return objs  # one per translation unit that owns kernels (abi_eval.hip, abi_mesh.hip, abi_indexed.hip, abi_contour.hip; abi_spec.hip owns none)
 
 
 @pytest.mark.skipif(not os.path.exists(os.path.join(LLVM, "llvm-readelf")), reason="ROCm LLVM tools not installed")
