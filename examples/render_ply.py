@@ -28,6 +28,12 @@ binary STL's of the same mesh, and the weld's device time.
                          mesher straight to an indexed mesh (gsdf_hip_mesh_dualcontour_indexed: one vertex per kept cube, faces in
                          lattice order, the same file byte for byte on every run); every option above works after it
     --chiseled           with --renderer dualcontour: DualContourLeastSquares.Chiseled
+    --thickness [THIN]   last, whatever came before: the WALL THICKNESS at every vertex of the mesh that is written -- the distance
+                         to the opposite wall along the inward normal, a ray marched through the part's exact field
+                         (gsdf_hip_indexed_thickness, on device: from res / 4 inside the surface, normal by central differences of
+                         res / 4, on the far wall within res / 1024, at most the bounds' diagonal). Prints min, max, the vertices
+                         thinner than THIN (0) and the status table, and writes the thickness as the vertices' `quality` property
+                         (+Inf: the ray left the part; NaN: no answer). At a sharp convex edge it is legitimately small
 With --simplify / --max-tris, --normals are those of the simplified mesh and --report prints a second report for it; with --project
 they are those of the projected mesh, and --report also prints how far the vertices were from the surface before and after, and
 the projected mesh's report: its volume is the point of the exercise. The grid starts
@@ -75,6 +81,8 @@ def main(argv=None):
     ap.add_argument("--before-project", default=None, metavar="F", help="with --project: also write the mesh before the projection to F")
     ap.add_argument("--renderer", choices=["octree", "dualcontour"], default="octree", help="the mesher: octree + weld, or dual contouring straight to an indexed mesh")
     ap.add_argument("--chiseled", action="store_true", help="with --renderer dualcontour: the chiseled vertex placement")
+    ap.add_argument("--thickness", type=float, nargs="?", const=0.0, default=None, metavar="THIN",
+                    help="wall thickness per vertex along the inward normal, written as the quality property; counts the vertices thinner than THIN")
     args = ap.parse_args(argv)
     if args.before_project and args.project is None:
         ap.error("--before-project needs --project")
@@ -84,6 +92,8 @@ def main(argv=None):
         ap.error("--adaptive needs a tolerance >= 0 and --levels 1 .. 16")
     if args.adaptive is not None and args.max_tris > 0 and not args.adaptive > 0:
         ap.error("--adaptive with --max-tris needs a tolerance > 0 to double")
+    if args.thickness is not None and not args.thickness >= 0:
+        ap.error("--thickness needs a THIN >= 0")
 
     import numpy as np
     from gsdf_amd import hip
@@ -167,6 +177,16 @@ def main(argv=None):
             print_report(args.scene + " projected", ix)
     out = args.output or f"{args.scene}.ply"
     data = ix.ply_view()
+    if args.thickness is not None:
+        from gsdf_amd import ply
+        quarter = res / np.float32(4)
+        th, status, ts = ix.thickness(sdf, quarter, quarter, np.float32(shape.Diagonal()), res / np.float32(1024), thin=np.float32(args.thickness))
+        counts = ", ".join(f"{n.lower()} {ts.count[k]}" for k, n in enumerate(hip.RAY_STATUS) if ts.count[k])
+        print(f"{args.scene} thickness: min {ts.t_min:.6g}, max {ts.t_max:.6g} ({ts.t_min / float(res):.4g} .. {ts.t_max / float(res):.4g} res); "
+              f"{ts.below} of {ts.n} vertices below {args.thickness:g}; {counts}; {ts.evals} evaluations ({ts.evals / ts.n:.1f} per vertex), "
+              f"at most {ts.steps_max} per ray, device {ts.ms_device:.3f} ms")
+        v, i, nrm = ply.parse_ply(data)   # the library's own file, and the thickness behind its vertex properties
+        data = ply.ply_bytes(v, i, nrm, quality=th)
     with open(out, "wb") as f:
         f.write(data)
     t3 = time.perf_counter()

@@ -1,7 +1,7 @@
 // abi_eval.hip -- C ABI (include/gsdf_hip.h), evaluator side: program handles (their per-tree kernels: abi_spec.hip), the
 // gleval.SDF3 / SDF2 Evaluate drop-ins (host buffers, pipelined tickets, registered memory, device-resident), central-difference
 // normals, the 2-D image renderer and its colour conversions, the UI's view of a 3-D part, the block cache. Kernels: kernels_eval.h,
-// kernels_image.h, kernels_view.h and kernels_project.h over the interpreter of interp.h.
+// kernels_image.h, kernels_view.h, kernels_project.h and kernels_ray.h over the interpreter of interp.h.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -16,6 +16,7 @@
 #include "kernels_eval.h"
 #include "kernels_view.h"
 #include "kernels_project.h"
+#include "kernels_ray.h"
 #include "kernels_image.h"
 #include "abi_program.h"
 
@@ -575,6 +576,105 @@ int project_dev(gsdf_program* p, const float* d_pos, size_t n, const gsdf_projec
   r.steps_max = hc.steps_max;
   r.ms_device = (double)ms;
   *st = r;
+  return GSDF_OK;
+}
+
+// ---- rays (kernels_ray.h; gsdf_hip.h: "rays") -------------------------------------------------------------------------------------
+int ray_opts_refused(const gsdf_ray_opts* o, const char* what) {
+  const std::string w = std::string(what) + ": ";
+  if (!std::isfinite(o->t0) || !(o->t0 >= 0.0f)) return fail(GSDF_ERR_BAD_ARGUMENT, w + "t0 must be finite and not negative");
+  if (!(o->tmax >= o->t0)) return fail(GSDF_ERR_BAD_ARGUMENT, w + "tmax must be t0 at least");
+  if (!std::isfinite(o->tol) || !(o->tol >= 0.0f)) return fail(GSDF_ERR_BAD_ARGUMENT, w + "tol must be finite and not negative");
+  if (!std::isfinite(o->min_step) || !(o->min_step >= 0.0f)) return fail(GSDF_ERR_BAD_ARGUMENT, w + "min_step must be finite and not negative");
+  if (o->max_steps < 1 || o->max_steps > 4096) return fail(GSDF_ERR_BAD_ARGUMENT, w + "max_steps must be 1 .. 4096");
+  if (o->refine < 0 || o->refine > 32) return fail(GSDF_ERR_BAD_ARGUMENT, w + "refine must be 0 .. 32");
+  if (o->flags != 0) return fail(GSDF_ERR_BAD_ARGUMENT, w + "unknown flags " + std::to_string(o->flags));
+  if (o->reserved != 0) return fail(GSDF_ERR_BAD_ARGUMENT, w + "the reserved word must be 0");
+  return GSDF_OK;
+}
+
+// what both entry points refuse whatever the options: no rays, too many, a 2-D program
+static int ray_call_refused(const gsdf_program* p, size_t n) {
+  if (n == 0) return fail(GSDF_ERR_EMPTY_BUFFERS, "empty buffers");
+  if (n >= ((size_t)1 << 32)) return fail(GSDF_ERR_CAPACITY, "rays must stay below 2^32");
+  if (p->prog.is2d) return fail(GSDF_ERR_DIMENSION, "rays: the program is 2D");
+  return GSDF_OK;
+}
+
+// ray_kernel on device-resident rays, or on device-resident vertices (step > 0: the thickness form), over the interpreter or the
+// handle's specialised build of it (abi_program.h). One launch, as project_dev: the counters (the handle's, made at its first cast,
+// as are the two events) are cleared on the stream in front of it and read behind it. One cast per program at a time.
+int ray_dev(gsdf_program* p, const float* d_in, size_t n, const gsdf_ray_opts* o, float step, float thin, float* d_t, float* d_d, uint8_t* d_status,
+            uint16_t* d_steps, gsdf_ray_stats* st) {
+  const bool thick = step > 0.0f;
+  if (int rc = ray_call_refused(p, n)) return rc;
+  if (thick) { if (int rc = p->normals_refused("gsdf_hip_indexed_thickness")) return rc; }
+  HIP_TRY(hipSetDevice(p->device));
+  spec_adopt(p);
+  spec_ensure(p, SPEC_RAY);
+  if (!p->ray_ctr.p) HIP_TRY(hipMalloc(&p->ray_ctr.p, sizeof(RayCounters)));
+  HIP_TRY(p->ev_ray.ensure());
+  const EventSet<2>& ev = p->ev_ray;
+  RayCounters* d_ctr = (RayCounters*)p->ray_ctr.p;
+  RayCounters hc{};
+  float ms = 0.f;
+  const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
+  RayParams prm{};
+  prm.t0 = o->t0 + 0.0f;  // (-0 -> +0: every t a ray reports is then >= +0)
+  prm.tmax = o->tmax; prm.tol = o->tol; prm.min_step = o->min_step;
+  prm.h = step * 0.5f; prm.thin = thin;
+  prm.max_steps = o->max_steps; prm.refine = o->refine;
+  hipError_t e = hipMemsetAsync(d_ctr, 0, sizeof(RayCounters), p->stream.s);
+  if (e == hipSuccess) e = hipEventRecord(ev[0], p->stream.s);
+  if (e == hipSuccess) {  // (the kernel takes its input as words: (const unsigned*) cannot be left to the launcher's static_cast)
+    if (thick)
+      e = launch_kernel(ray_kernel<true>, p->spec.f_ray_thick, grid, BLOCK, p->lds_bytes(2), p->stream.s, p->d_code.p, (const unsigned*)d_in, n, prm, d_t, d_d, d_status,
+                        (unsigned short*)d_steps, d_ctr);
+    else
+      e = launch_kernel(ray_kernel<false>, p->spec.f_ray, grid, BLOCK, p->lds_bytes(1), p->stream.s, p->d_code.p, (const unsigned*)d_in, n, prm, d_t, d_d, d_status,
+                        (unsigned short*)d_steps, d_ctr);
+  }
+  if (e == hipSuccess) e = hipEventRecord(ev[1], p->stream.s);
+  if (e == hipSuccess) e = hipMemcpyAsync(&hc, d_ctr, sizeof hc, hipMemcpyDeviceToHost, p->stream.s);
+  if (e == hipSuccess) e = hipStreamSynchronize(p->stream.s);
+  else (void)hipStreamSynchronize(p->stream.s);
+  if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+  if (e != hipSuccess) return fail(GSDF_ERR_HIP, std::string("rays: ") + hipGetErrorString(e));
+  p->evals += hc.evals;
+  gsdf_ray_stats r{};
+  r.n = n;
+  for (int k = 0; k < 8; k++) r.count[k] = hc.count[k];
+  r.evals = hc.evals; r.steps_max = hc.steps_max; r.below = hc.below;
+  const unsigned tmin = RAY_INF - hc.t_min_inv;
+  std::memcpy(&r.t_min, &tmin, 4);
+  std::memcpy(&r.t_max, &hc.t_max, 4);
+  r.ms_device = (double)ms;
+  *st = r;
+  return GSDF_OK;
+}
+
+// Host buffers, blocking, on the path gsdf_hip_normals3 takes: the rays in, the kernel, the outputs the caller asked for out.
+extern "C" int gsdf_hip_raycast3(gsdf_program* p, const float* rays, size_t n, const gsdf_ray_opts* o, float thin, float* t_out, float* d_out, uint8_t* status_out,
+                                 uint16_t* steps_out, gsdf_ray_stats* st) {
+  if (!p || !rays || !o) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  if (!t_out && !d_out && !status_out && !steps_out && !st) return fail(GSDF_ERR_BAD_ARGUMENT, "raycast: no output asked for");
+  if (int rc = ray_opts_refused(o, "raycast")) return rc;
+  if (int rc = ray_call_refused(p, n)) return rc;  // (before anything is allocated; ray_dev asks again)
+  HIP_TRY(hipSetDevice(p->device));
+  DevBuf d_rays, d_t, d_d, d_s, d_n;
+  HIP_TRY(d_rays.alloc(n * 24));
+  if (t_out) HIP_TRY(d_t.alloc(n * 4));
+  if (d_out) HIP_TRY(d_d.alloc(n * 4));
+  if (status_out) HIP_TRY(d_s.alloc(n));
+  if (steps_out) HIP_TRY(d_n.alloc(n * 2));
+  HIP_TRY(hipMemcpyAsync(d_rays.p, rays, n * 24, hipMemcpyHostToDevice, p->stream.s));
+  gsdf_ray_stats r{};
+  if (int rc = ray_dev(p, (const float*)d_rays.p, n, o, 0.0f, thin, (float*)d_t.p, (float*)d_d.p, (uint8_t*)d_s.p, (uint16_t*)d_n.p, &r)) return rc;
+  if (t_out) HIP_TRY(hipMemcpy(t_out, d_t.p, n * 4, hipMemcpyDeviceToHost));
+  if (d_out) HIP_TRY(hipMemcpy(d_out, d_d.p, n * 4, hipMemcpyDeviceToHost));
+  if (status_out) HIP_TRY(hipMemcpy(status_out, d_s.p, n, hipMemcpyDeviceToHost));
+  if (steps_out) HIP_TRY(hipMemcpy(steps_out, d_n.p, n * 2, hipMemcpyDeviceToHost));
+  if (st) *st = r;
   return GSDF_OK;
 }
 

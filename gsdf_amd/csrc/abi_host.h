@@ -1,7 +1,7 @@
 // abi_host.h -- what the translation units of the C ABI share on the host side: error plumbing, the mesh handle, the buffer
 // pools. No device code (abi_comm.cpp and abi_host.cpp are plain C++).
 //   abi_host.cpp  error text, triangle / pinned-buffer pools, result copies
-//   abi_eval.hip  programs, gleval.SDF3 / SDF2 Evaluate, normals, projection, image / view / picture renderers, block cache
+//   abi_eval.hip  programs, gleval.SDF3 / SDF2 Evaluate, normals, projection, rays, image / view / picture renderers, block cache
 //   abi_spec.hip  per-tree (specialised) kernels of a program: first build, background build and adoption, the groups built on
 //                 first use (spec_ensure), the report of what a handle launches. Host code only: it owns no kernel
 //   abi_mesh.hip  octree / flat / dual-contouring meshers and the mesh accessors

@@ -937,6 +937,29 @@ extern "C" int gsdf_hip_indexed_project(gsdf_indexed* ix, gsdf_program* p, const
   return GSDF_OK;
 }
 
+// ---- wall thickness (kernels_ray.h; the launch is abi_eval.hip's ray_dev on the device-resident vertices) ---------------------------
+extern "C" int gsdf_hip_indexed_thickness(gsdf_indexed* ix, gsdf_program* p, const gsdf_thickness_opts* o, float* thickness_out, uint8_t* status_out, gsdf_ray_stats* st) {
+  if (!o) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  if (int rc = ray_opts_refused(&o->ray, "thickness")) return rc;
+  if (!std::isfinite(o->step) || !(o->step > 0.0f)) return fail(GSDF_ERR_BAD_ARGUMENT, "thickness: the step must be positive and finite");
+  if (o->reserved[0] != 0 || o->reserved[1] != 0) return fail(GSDF_ERR_BAD_ARGUMENT, "thickness: the reserved words must be 0");
+  if (!ix || !p || (!thickness_out && !status_out && !st)) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  if (p->prog.is2d) return fail(GSDF_ERR_DIMENSION, "thickness: the program is 2D");
+  if (p->device != ix->device) return fail(GSDF_ERR_BAD_ARGUMENT, "the program and the indexed mesh live on different devices");
+  HIP_TRY(hipSetDevice(ix->device));
+  const uint64_t V = ix->n_verts;
+  DevPtr<float> d_t;
+  DevPtr<uint8_t> d_s;
+  if (thickness_out) HIP_TRY(hipMalloc((void**)&d_t.p, V * 4));
+  if (status_out) HIP_TRY(hipMalloc((void**)&d_s.p, V));
+  gsdf_ray_stats r{};
+  if (int rc = ray_dev(p, ix->verts.p, (size_t)V, &o->ray, o->step, o->thin, d_t.p, nullptr, d_s.p, nullptr, &r)) return rc;
+  if (thickness_out) HIP_TRY(hipMemcpy(thickness_out, d_t.p, V * 4, hipMemcpyDeviceToHost));
+  if (status_out) HIP_TRY(hipMemcpy(status_out, d_s.p, V, hipMemcpyDeviceToHost));
+  if (st) *st = r;
+  return GSDF_OK;
+}
+
 extern "C" int gsdf_hip_indexed_read_fit(const gsdf_indexed* ix, float* dist_before, float* dist_after, uint8_t* status) {
   if (!ix) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
   if (!ix->has_fit) return fail(GSDF_ERR_BAD_ARGUMENT, "no fit: the handle was not made by gsdf_hip_indexed_project");

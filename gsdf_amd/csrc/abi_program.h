@@ -89,8 +89,9 @@ struct LeafPick { LeafVariant v; hipFunction_t f; };  // f: the handle's per-tre
 // The groups of kernels a specialised handle builds the first time an entry point needs them (spec_ensure): the evaluating kernels of
 // dual contouring, normals, the flat lattice pass and the 2-D image; distinct z rows (share_corners = 2; kernels_octree.h: DZ);
 // eval_kernel<D, 1, 4> for host-mapped calls; distinct lattice points (share_corners = 1: leaf_dense_kernel); the UI's view
-// (kernels_view.h); the projection of mesh vertices (kernels_project.h); the 2-D picture, one kernel per conversion kind (kernels_image.h).
-enum SpecGroup { SPEC_AUX, SPEC_ROWS, SPEC_EVAL_K1, SPEC_DENSE, SPEC_VIEW, SPEC_PROJECT, SPEC_PICTURE, SPEC_GROUPS };
+// (kernels_view.h); the projection of mesh vertices (kernels_project.h); the 2-D picture, one kernel per conversion kind (kernels_image.h);
+// rays and wall thickness (kernels_ray.h).
+enum SpecGroup { SPEC_AUX, SPEC_ROWS, SPEC_EVAL_K1, SPEC_DENSE, SPEC_VIEW, SPEC_PROJECT, SPEC_PICTURE, SPEC_RAY, SPEC_GROUPS };
 struct SpecBuilt {  // what was built, for which template arguments, by what
   std::vector<hipModule_t> mods;  // the first group's module, then every later one (a kernel rebuilt for another W, the groups above)
   int eval_k = 0, eval_w = 0, leaf_k = 0, leaf_w = 0, rows_w = 0, dense_w = 0;
@@ -102,6 +103,7 @@ struct SpecFns {  // null: the ahead-of-time (interpreter) kernel runs
   hipFunction_t f_eval = nullptr, f_eval_k1 = nullptr, f_prune = nullptr, f_prune_spec = nullptr, f_leaf = nullptr, f_leaf_dz = nullptr, f_leaf_dense = nullptr;
   hipFunction_t f_dc_block_test = nullptr, f_dc_origin = nullptr, f_dc_edges = nullptr, f_dc_normals = nullptr, f_normals = nullptr, f_image = nullptr, f_flat_grid = nullptr;
   hipFunction_t f_view = nullptr, f_view_plain = nullptr, f_project = nullptr, f_imgc[4] = {nullptr, nullptr, nullptr, nullptr};
+  hipFunction_t f_ray = nullptr, f_ray_thick = nullptr;
 };
 struct SpecKernels : SpecBuilt, SpecFns, NoCopy {
   std::atomic<unsigned> todo{0};  // bit g: group g is still to be tried. 0 on a handle that is not specialised: spec_ensure's lock-free exit
@@ -199,6 +201,8 @@ struct gsdf_program {
   size_t lds_dense() const { return (size_t)(prog.nslots * 4 > 8 ? prog.nslots * 4 : 8) * BLOCK * sizeof(float) + 256 + 4 * 512 * sizeof(float) + 4 * 24 * sizeof(float) + 16; }
   DevPtr<void> proj_ctr;  // the projection's counters on the device and the two events around its launch: made at the
   EventSet<2> ev_proj;    // first projection, kept for the next (project_dev)
+  DevPtr<void> ray_ctr;   // the same for rays and wall thickness: made at the first cast (ray_dev)
+  EventSet<2> ev_ray;
   // Specialisation in the background (gsdf_hip_program_specialize_async): a thread builds and loads the kernels on a shadow handle
   // (this program, this device, nothing else) while the interpreter kernels serve; the entry points adopt the result at their
   // next call (abi_spec.hip: spec_adopt). 0 idle | 1 building | 2 built, to be adopted | 3 failed (spec_async_err)
@@ -265,7 +269,7 @@ struct gsdf_program {
                 std::to_string(prog.lip_depth) + ") need " + std::to_string(need) + " bytes of LDS per workgroup, a CU has " + std::to_string(kLdsPerCu) +
                 " (limit: " + limit + ")");
   }
-  // normals_kernel, project_kernel, dc_normals_kernel: two points per lane, no static LDS
+  // normals_kernel, project_kernel, ray_kernel<true>, dc_normals_kernel: two points per lane, no static LDS
   int normals_refused(const char* what) const { return lds_refused(what, lds_bytes(2), std::to_string(GSDF_HIP_MAX_SLOTS_NORMALS) + " slots"); }
   static_assert((size_t)GSDF_HIP_MAX_SLOTS_NORMALS * 2 * BLOCK * sizeof(float) <= kLdsPerCu && (size_t)(GSDF_HIP_MAX_SLOTS_NORMALS + 1) * 2 * BLOCK * sizeof(float) > kLdsPerCu,
                 "gsdf_hip.h: GSDF_HIP_MAX_SLOTS_NORMALS is the largest slot count whose two points per lane fit a CU's LDS");
@@ -332,6 +336,14 @@ int normals3_dev(gsdf_program* p, const float* d_pos, float* d_nrm, size_t n, fl
 // each optional; st->n_verts .. steps_max and ms_device are filled. Blocking. The options are the caller's to check.
 int project_dev(gsdf_program* p, const float* d_pos, size_t n, const gsdf_project_opts* o, float* d_out_pos, float* d_before, float* d_after,
                 uint8_t* d_status, gsdf_project_stats* st);
+// Rays through the field (abi_eval.hip; what gsdf_hip_raycast3 and gsdf_hip_indexed_thickness launch; gsdf_hip.h states the
+// arithmetic). d_in on the program's device: n rays of 24 bytes, or, with step > 0, n vertices of 12 bytes whose rays the kernel
+// builds along the inward normal (h = step / 2; d_t then receives the thickness). d_t, d_d (n floats), d_status (n bytes), d_steps
+// (n uint16) each optional; *st is filled. Blocking. The options are the caller's to check.
+int ray_dev(gsdf_program* p, const float* d_in, size_t n, const gsdf_ray_opts* o, float step, float thin, float* d_t, float* d_d, uint8_t* d_status,
+            uint16_t* d_steps, gsdf_ray_stats* st);
+// gsdf_ray_opts as gsdf_hip.h allows them: GSDF_OK, or GSDF_ERR_BAD_ARGUMENT with `what` in front of the text
+int ray_opts_refused(const gsdf_ray_opts* o, const char* what);
 
 namespace {
 // ms3.Box.ScaleCentered(1.01) = NewCenteredBox(Center(), MulElem(scale, Size())) [external]; float32, unfused.

@@ -131,6 +131,9 @@ void spec_ensure(gsdf_program* p, SpecGroup g) {
     case SPEC_PROJECT:
       if (!is2d) cs = {{"project_kernel", &k.f_project}};
       break;
+    case SPEC_RAY:  // both forms: the caller's rays, and the rays of a mesh's vertices (wall thickness)
+      if (!is2d) cs = {{"ray_kernel<false>", &k.f_ray}, {"ray_kernel<true>", &k.f_ray_thick}};
+      break;
     case SPEC_PICTURE:
       for (int kind = 0; kind < 4 && is2d; kind++) cs.push_back({"image2_color_kernel<" + std::to_string(ek) + ", " + std::to_string(kind) + ">", &k.f_imgc[kind]});
       break;
@@ -294,7 +297,8 @@ extern "C" int gsdf_hip_program_is_specialized(const gsdf_program* p, double* co
 /* The kernels this handle launches, e.g. "eval=eval_kernel<3,4,4>:specialised leaf=leaf_kernel<4,3>:specialised
  * prune=prune_kernel:specialised" (":interpreter" for the ahead-of-time kernels): what a profile of the handle shows. One cap: a
  * field is appended only while the whole text stays under 512 bytes, what the callers' buffers hold (the longest seen: 397 bytes,
- * npt-flange specialised with its distinct-rows and distinct-points kernels built). */
+ * npt-flange specialised with its distinct-rows and distinct-points kernels built, before the 27 bytes of " ray=" came behind them:
+ * 424). Fields are appended in the order of their age, so the one a cap would drop first is the newest. */
 extern "C" int gsdf_hip_program_kernels(const gsdf_program* p, char* dst, size_t dst_cap) {
   if (!p || !dst || dst_cap == 0) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
   // the rules the launches go by: eval_dev's, the leaf phase of a mesh of three levels or more (gsdf_program::leaf_pick)
@@ -328,6 +332,7 @@ extern "C" int gsdf_hip_program_kernels(const gsdf_program* p, char* dst, size_t
   add(" code=" + (k.specialised() ? k.key : gsdf_dev::spec_library_key()));
   // the lowering's division census (compile.h): with RN(1/d) / declined / polygons flagged / not flagged
   add(" recip=" + std::to_string(p->prog.n_recip) + "/" + std::to_string(p->prog.n_recip_declined) + "/" + std::to_string(p->prog.n_poly_recip) + "/" + std::to_string(p->prog.n_poly_plain));
+  if (!is2d) add(" ray=ray_kernel:" + how(k.f_ray));  // rays and wall thickness (built at the first cast); the newest field, so the first to go
   if (s.size() + 1 > dst_cap) return fail(GSDF_ERR_SHORT_BUFFER, "short buffer");
   std::memcpy(dst, s.c_str(), s.size() + 1);
   return GSDF_OK;

@@ -57,6 +57,16 @@ __device__ __forceinline__ bool abs_ge(float v, float lim) {
   const unsigned a = __float_as_uint(v) & 0x7fffffffu;
   return a >= __float_as_uint(lim) && a <= 0x7f800000u;
 }
+// the per-vertex / per-ray kernels (kernels_project.h, kernels_ray.h): |v| as bits; NaN by its bits; |v| > lim for the bits of a finite
+// lim >= 0, false for a NaN v; the largest of a wave's unsigned values, in every lane
+__device__ __forceinline__ unsigned abs_bits(float v) { return __float_as_uint(v) & 0x7fffffffu; }
+__device__ __forceinline__ bool is_nan(float v) { return abs_bits(v) > 0x7f800000u; }
+__device__ __forceinline__ bool abs_gt(float v, unsigned lim_bits) { const unsigned a = abs_bits(v); return a > lim_bits && a <= 0x7f800000u; }
+__device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) { const unsigned o = (unsigned)__shfl_xor((int)v, off, 64); v = o > v ? o : v; }
+  return v;
+}
 }  // namespace nb
 
 // wave64 compaction: returns the global slot for lanes with keep=true (others undefined).

@@ -36,15 +36,7 @@ struct ProjectCounters {
 };
 
 namespace project {
-__device__ __forceinline__ unsigned abs_bits(float v) { return __float_as_uint(v) & 0x7fffffffu; }
-__device__ __forceinline__ bool is_nan(float v) { return abs_bits(v) > 0x7f800000u; }
-// |v| > lim for a finite lim >= 0, false for a NaN v: non-negative floats order like their bit patterns
-__device__ __forceinline__ bool abs_gt(float v, unsigned lim_bits) { const unsigned a = abs_bits(v); return a > lim_bits && a <= 0x7f800000u; }
-__device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) { const unsigned o = (unsigned)__shfl_xor((int)v, off, 64); v = o > v ? o : v; }
-  return v;
-}
+using nb::abs_bits; using nb::is_nan; using nb::abs_gt; using nb::wave_max_u32;  // (kernels_common.h)
 __device__ __forceinline__ void wave_count(bool flag, unsigned long long* counter) {
   const unsigned long long m = __ballot(flag);
   if ((threadIdx.x & 63u) == 0u && m) atomicAdd(counter, (unsigned long long)__builtin_popcountll(m));

@@ -30,6 +30,7 @@ SYMBOLS = ["gsdf_hip_last_error", "gsdf_hip_init", "gsdf_hip_program_create", "g
            "gsdf_hip_indexed_normals", "gsdf_hip_indexed_read_normals", "gsdf_hip_indexed_ply", "gsdf_hip_indexed_host_ply", "gsdf_hip_indexed_destroy",
            "gsdf_hip_indexed_create", "gsdf_hip_indexed_report", "gsdf_hip_indexed_shells", "gsdf_hip_indexed_read_shell_of", "gsdf_hip_indexed_extract",
            "gsdf_hip_indexed_simplify", "gsdf_hip_indexed_simplify_adaptive", "gsdf_hip_indexed_project", "gsdf_hip_indexed_read_fit", "gsdf_hip_mesh_dualcontour_indexed",
+           "gsdf_hip_raycast3", "gsdf_hip_indexed_thickness",
            "gsdf_hip_contour2", "gsdf_hip_slice3", "gsdf_hip_contour_counts", "gsdf_hip_contour_read", "gsdf_hip_contour_stats_get", "gsdf_hip_contour_destroy"]
 
 
@@ -153,6 +154,32 @@ class ProjectStats(C.Structure):
                 ("over_tol_after", C.c_uint64), ("max_abs_before", C.c_float), ("max_abs_after", C.c_float), ("steps_max", C.c_uint32),
                 ("reserved", C.c_uint32), ("ms_device", C.c_double)]
     RESULT_BYTES = 112
+
+    def result_bytes(self):
+        return bytes(self)[:self.RESULT_BYTES]
+
+
+class RayOpts(C.Structure):
+    """gsdf_ray_opts (gsdf_hip.h, "rays"): where the march starts and ends, the hit tolerance, the shortest step, the march evaluations
+    and the bisections of a crossing's bracket."""
+    _fields_ = [("t0", C.c_float), ("tmax", C.c_float), ("tol", C.c_float), ("min_step", C.c_float), ("max_steps", C.c_int32),
+                ("refine", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class ThicknessOpts(C.Structure):
+    """gsdf_thickness_opts (gsdf_hip.h): a RayOpts, the central-difference step of the inward normal and the `thin` the stats count below."""
+    _fields_ = [("ray", RayOpts), ("step", C.c_float), ("thin", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
+RAY_STATUS = ["SKIPPED", "HIT", "CROSSED", "MISS", "STEPS", "NONFINITE", "FLAT"]  # gsdf_hip.h: GSDF_RAY_*
+
+
+class RayStats(C.Structure):
+    """gsdf_ray_stats (gsdf_hip.h): what a batch of rays (the thickness of a mesh) found; bytes 0 .. 103 (RESULT_BYTES) are a function
+    of the inputs alone, ms_device says what the run cost."""
+    _fields_ = [("n", C.c_uint64), ("count", C.c_uint64 * 8), ("evals", C.c_uint64), ("steps_max", C.c_uint32), ("t_min", C.c_float),
+                ("t_max", C.c_float), ("reserved", C.c_uint32), ("below", C.c_uint64), ("ms_device", C.c_double)]
+    RESULT_BYTES = 104
 
     def result_bytes(self):
         return bytes(self)[:self.RESULT_BYTES]
@@ -300,6 +327,9 @@ def lib():
         L.gsdf_hip_indexed_simplify_adaptive.argtypes = [C.c_void_p, C.POINTER(AdaptiveOpts), C.POINTER(C.c_void_p), C.POINTER(AdaptiveStats)]
         L.gsdf_hip_indexed_project.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(ProjectOpts), C.POINTER(C.c_void_p), C.POINTER(ProjectStats)]
         L.gsdf_hip_indexed_read_fit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.gsdf_hip_raycast3.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayOpts), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.POINTER(RayStats)]
+        L.gsdf_hip_indexed_thickness.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(ThicknessOpts), C.c_void_p, C.c_void_p, C.POINTER(RayStats)]
         L.gsdf_hip_mesh_dualcontour_indexed.argtypes = [C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(MeshStats)]
         L.gsdf_hip_contour2.argtypes = [C.c_void_p, C.c_float, C.POINTER(ContourOpts), C.POINTER(C.c_void_p)]
         L.gsdf_hip_slice3.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_uint32, C.POINTER(ContourOpts), C.POINTER(C.c_void_p)]
@@ -544,6 +574,23 @@ class SDFHIP:
         out = np.empty_like(pos)
         _check(lib().gsdf_hip_normals3(self._h, pos.ctypes.data, out.ctypes.data, pos.shape[0], step))
         return out
+
+    def raycast(self, origins, dirs, t0=0.0, tmax=float("inf"), tol=1e-4, min_step=0.0, max_steps=256, refine=8, thin=0.0):
+        """gsdf_hip_raycast3: the rays origins + t dirs ((n, 3) each; dirs used as given, so t is in units of |dir|) sphere-traced
+        through the field from t0, from outside or inside the part: (t (n,) float32, d (n,) float32, status (n,) uint8 -- see
+        RAY_STATUS --, steps (n,) uint16, RayStats). A query, not a guarantee: see the header."""
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        r = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        if o.shape != r.shape:
+            raise ValueError("origins and dirs differ in shape")
+        rays = np.ascontiguousarray(np.concatenate([o, r], axis=1))
+        n = len(rays)
+        t, d, status, steps = np.empty(n, np.float32), np.empty(n, np.float32), np.empty(n, np.uint8), np.empty(n, np.uint16)
+        ro = RayOpts(t0=np.float32(t0), tmax=np.float32(tmax), tol=np.float32(tol), min_step=np.float32(min_step), max_steps=int(max_steps), refine=int(refine))
+        st = RayStats()
+        _check(lib().gsdf_hip_raycast3(self._h, rays.ctypes.data, n, C.byref(ro), np.float32(thin), t.ctypes.data, d.ctypes.data, status.ctypes.data,
+                                       steps.ctypes.data, C.byref(st)))
+        return t, d, status, steps, st
 
 
 def host_array(shape, dtype=np.float32):
@@ -922,6 +969,21 @@ class IndexedHIP:
         """How far the vertices are from the surface of `sdf`: the dry run of project() with no step, one evaluation per vertex
         (ProjectStats: max_abs_before, over_tol_before, count[ON])."""
         return self.project(sdf, 1.0, tol, 0.0, max_iters=0, dry=True)[1]
+
+    def thickness(self, sdf, step, t0, tmax, tol, min_step=0.0, max_steps=256, refine=8, thin=0.0, dry=False):
+        """gsdf_hip_indexed_thickness: per vertex, the distance to the opposite wall of `sdf` (an SDF3HIP) along the inward normal
+        (central differences of `step`, as normals()), marched through the field from t0 (pick t0 > tol): (thickness (V,) float32 --
+        +Inf where the ray left through tmax, NaN where it has no answer --, status (V,) uint8, see RAY_STATUS, RayStats: t_min,
+        t_max, below = the vertices thinner than `thin`). dry: (None, None, RayStats)."""
+        ro = RayOpts(t0=np.float32(t0), tmax=np.float32(tmax), tol=np.float32(tol), min_step=np.float32(min_step), max_steps=int(max_steps), refine=int(refine))
+        o = ThicknessOpts(ray=ro, step=np.float32(step), thin=np.float32(thin))
+        st = RayStats()
+        if dry:
+            _check(lib().gsdf_hip_indexed_thickness(self._h, sdf._h, C.byref(o), None, None, C.byref(st)))
+            return None, None, st
+        th, status = np.empty(self.n_verts, np.float32), np.empty(self.n_verts, np.uint8)
+        _check(lib().gsdf_hip_indexed_thickness(self._h, sdf._h, C.byref(o), th.ctypes.data, status.ctypes.data, C.byref(st)))
+        return th, status, st
 
     def fit(self):
         """Of a handle project() made: (d_before (V,) float32, d_after (V,) float32, status (V,) uint8, see PROJECT_STATUS)."""

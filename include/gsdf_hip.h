@@ -73,7 +73,8 @@ int gsdf_hip_init(int device);
  *   gsdf_hip_program_create                                   143 slots (one point per lane above 28 slots); a handle that exists
  *                                                             evaluates, renders (image2, image2_color, render3) and meshes flat;
  *   gsdf_hip_normals3, gsdf_hip_indexed_normals,
- *   gsdf_hip_indexed_project, _deviation                      80 slots (two points per lane);
+ *   gsdf_hip_indexed_project, _deviation,
+ *   gsdf_hip_indexed_thickness                                80 slots (two points per lane);
  *   gsdf_hip_mesh_octree[_start]                              slots + interval stack <= 67 (the centre tests carry two points per lane
  *                                                             over both, beside 24 KB of cube stages; the interval stack is as deep as the
  *                                                             tree's position maps that stretch nest: twist, scale, ... -- "interval=" in
@@ -891,6 +892,99 @@ GSDF_ABI_ASSERT(offsetof(gsdf_project_stats, count) == 8 && offsetof(gsdf_projec
 GSDF_ABI_ASSERT(offsetof(gsdf_project_stats, max_abs_before) == 96 && offsetof(gsdf_project_stats, steps_max) == 104 && offsetof(gsdf_project_stats, ms_device) == 112, "gsdf_project_stats maxima and cost");
 int gsdf_hip_indexed_project(gsdf_indexed* ix, gsdf_program* p, const gsdf_project_opts* o, gsdf_indexed** out, gsdf_project_stats* st);
 int gsdf_hip_indexed_read_fit(const gsdf_indexed* ix, float* dist_before, float* dist_after, uint8_t* status);
+
+/* ---- rays (no reference counterpart) --------------------------------------------------------------------------------------------
+ *
+ * "What does this ray hit, and how far away?": a batch of the caller's own rays sphere-traced through the field of a 3-D program,
+ * from outside or from inside the part (picking, line of sight, drop to the surface), and, with the rays built from the vertices of
+ * an indexed mesh along their inward normals, the WALL THICKNESS of that mesh. The result is a function of the rays (the mesh), the
+ * program and the options alone, to the bit. Kernel: gsdf_amd/csrc/kernels_ray.h (abi_eval.hip: ray_dev); a numpy restatement:
+ * tests/rayref.py.
+ *
+ * A ray is 24 bytes: the origin o[3], then the direction r[3], used as given: r is NOT normalised, so t is in units of |r|.
+ *   pos(t) = (o.x + t * r.x, o.y + t * r.y, o.z + t * r.z).
+ * Options (gsdf_ray_opts). t0 finite and >= 0 (a t0 of -0 is taken as +0); tmax >= t0, +Inf allowed; tol and min_step finite and
+ *   >= 0; 1 <= max_steps <= 4096; 0 <= refine <= 32; flags == 0 and reserved == 0 -- anything else is GSDF_ERR_BAD_ARGUMENT.
+ * Arithmetic. Every operation below is ONE IEEE float32 operation, round to nearest, never contracted; sqrt and the division are
+ *   correctly rounded; comparisons are IEEE (false on a NaN operand); "d is NaN" is a test of d's bit pattern. sdf() is the program's
+ *   distance, gsdf_hip_eval3's. signbit(d) is d's sign bit (set for -0).
+ * Marching one ray.
+ *   1. If a component of o or r is NaN or infinite: status SKIPPED, nothing is evaluated, t and d are the quiet NaN 0x7fc00000.
+ *   2. t = t0, d = sdf(pos(t))  (march evaluation 1). If d is NaN: status NONFINITE. If NOT (|d| > tol): status HIT. Otherwise
+ *      inside = signbit(d).
+ *   3. Loop. If the march evaluations so far >= max_steps: status STEPS, reporting the last t and d. tp = t, dp = d. s = |d|; if
+ *      s < min_step then s = min_step. t = tp + s. If t > tmax: status MISS, reporting tp and dp. d = sdf(pos(t))  (a march
+ *      evaluation). If d is NaN: status NONFINITE. If NOT (|d| > tol): status HIT. If signbit(d) != inside: status CROSSED with the
+ *      bracket a = tp, b = t, db = d, on to 4. Otherwise repeat.
+ *   4. Refinement, for a CROSSED ray, up to `refine` times: m = a + (b - a) * 0.5f. Stop if NOT (m > a AND m < b). dm = sdf(pos(m))
+ *      (a refine evaluation). Stop if dm is NaN. If NOT (|dm| > tol): b = m, db = dm, stop. If signbit(dm) == inside: a = m;
+ *      otherwise b = m, db = dm. A CROSSED ray reports t = b, d = db: the nearest point known to lie on the far side.
+ *   HIT, STEPS and NONFINITE report the t of their last evaluation; HIT and STEPS its d; NONFINITE the quiet NaN 0x7fc00000 for d.
+ * Outputs per ray, each optional: t and d (floats), status (one byte, GSDF_RAY_*), steps (uint16: march plus refine evaluations).
+ * Status. GSDF_RAY_SKIPPED 0, _HIT 1, _CROSSED 2, _MISS 3, _STEPS 4, _NONFINITE 5, _FLAT 6 (thickness only).
+ * A query, not a guarantee. As for gsdf_hip_render3: a field that is not 1-Lipschitz (twist, a scaled part, a shell of one), or a
+ *   min_step larger than a wall, can step over a wall. The sign test catches a single crossing inside a step; a double crossing --
+ *   into a wall and out of it again in one step -- is missed, and the ray goes on as if the wall were not there.
+ * gsdf_ray_stats. Bytes 0 .. 103 (n .. below) are a function of the inputs alone, byte for byte; ms_device says what this run cost.
+ *   count[k]: rays of status k. evals: every evaluation (thickness: the six taps of every vertex that reached them too);
+ *   gsdf_hip_evaluations(p) grows by exactly that (padding lanes and finished lanes do not count). steps_max: the most march plus
+ *   refine evaluations of any ray. t_min, t_max: the smallest and the largest t over the HIT and CROSSED rays (+Inf and 0 when
+ *   there is none). below: the HIT and CROSSED rays with t < thin (a NaN thin counts none). Every one is an integer sum, maximum or
+ *   minimum (t >= 0 there, so its bits order as unsigned integers): any order of atomics gives the same bytes.
+ *
+ * gsdf_hip_raycast3(p, rays, n, o, thin, t_out, d_out, status_out, steps_out, st): host buffers, blocking, on the path
+ *   gsdf_hip_normals3 takes. A 2-D program: GSDF_ERR_DIMENSION. n == 0: GSDF_ERR_EMPTY_BUFFERS. n >= 2^32: GSDF_ERR_CAPACITY. Bad
+ *   options, a null p, rays or o, or all five outputs NULL: GSDF_ERR_BAD_ARGUMENT. On an error nothing is written.
+ *
+ * gsdf_hip_indexed_thickness(ix, p, o, thickness_out, status_out, st): the RAY definition of wall thickness -- per vertex, the
+ *   distance to the opposite wall along the inward normal, marched through the exact field and not through triangles. At a sharp
+ *   convex edge it is legitimately small. gsdf_thickness_opts is a gsdf_ray_opts plus step (the central-difference step, finite and
+ *   > 0: h = step * 0.5f, as gsdf_hip_indexed_project's step 2) and thin. Per vertex x (all V of them, used by a face or not):
+ *   a NaN or infinite coordinate: SKIPPED. Otherwise g_k = sdf(x + h e_k) - sdf(x - h e_k), k = x, y, z (six evaluations;
+ *   gsdf_hip_normals3's points and subtraction); s = (g.x g.x + g.y g.y) + g.z g.z; if NOT (s > 0): status FLAT. len = sqrt(s);
+ *   r = (-(g.x / len), -(g.y / len), -(g.z / len)); o = x; then the march above from t0. The caller picks t0 > tol so that the march
+ *   does not stop on the wall it starts from. thickness[v] is t for HIT and CROSSED, +Inf for MISS and the quiet NaN 0x7fc00000
+ *   otherwise. The same limits as gsdf_hip_indexed_project (80 slots; a program on another device: GSDF_ERR_BAD_ARGUMENT; 2-D:
+ *   GSDF_ERR_DIMENSION). Both outputs NULL with st != NULL is the DRY report; all three NULL: GSDF_ERR_BAD_ARGUMENT.
+ * Not done here: sphere-definition (medial) thickness, rays against meshes, 2-D rays, the normal at the hit (run gsdf_hip_normals3 on
+ *   pos(t)), interval-guarded marching that would make the query a guarantee, sorting rays for coherence. */
+enum { GSDF_RAY_SKIPPED = 0, GSDF_RAY_HIT = 1, GSDF_RAY_CROSSED = 2, GSDF_RAY_MISS = 3, GSDF_RAY_STEPS = 4, GSDF_RAY_NONFINITE = 5,
+       GSDF_RAY_FLAT = 6 };
+typedef struct gsdf_ray_opts {
+  float t0;           /* where the march starts; finite, >= 0 */
+  float tmax;         /* a step that would pass it is a MISS; >= t0, +Inf allowed */
+  float tol;          /* a ray has hit when NOT (|d| > tol); finite, >= 0 */
+  float min_step;     /* no step is shorter; finite, >= 0 */
+  int32_t max_steps;  /* march evaluations per ray, 1 .. 4096 */
+  int32_t refine;     /* bisections of a crossing's bracket, 0 .. 32 */
+  uint32_t flags;     /* 0; others refused */
+  uint32_t reserved;  /* 0; others refused */
+} gsdf_ray_opts;
+GSDF_ABI_ASSERT(sizeof(gsdf_ray_opts) == 32, "gsdf_ray_opts is 32 bytes");
+GSDF_ABI_ASSERT(offsetof(gsdf_ray_opts, tmax) == 4 && offsetof(gsdf_ray_opts, tol) == 8 && offsetof(gsdf_ray_opts, min_step) == 12 && offsetof(gsdf_ray_opts, max_steps) == 16 && offsetof(gsdf_ray_opts, refine) == 20 && offsetof(gsdf_ray_opts, flags) == 24, "gsdf_ray_opts fields");
+typedef struct gsdf_thickness_opts {
+  gsdf_ray_opts ray;
+  float step;            /* central-difference step, > 0 and finite: h = step / 2 */
+  float thin;            /* st->below counts the vertices thinner than this */
+  uint32_t reserved[2];  /* 0; others refused */
+} gsdf_thickness_opts;
+GSDF_ABI_ASSERT(sizeof(gsdf_thickness_opts) == 48, "gsdf_thickness_opts is 48 bytes");
+GSDF_ABI_ASSERT(offsetof(gsdf_thickness_opts, step) == 32 && offsetof(gsdf_thickness_opts, thin) == 36, "gsdf_thickness_opts fields");
+typedef struct gsdf_ray_stats {
+  uint64_t n;
+  uint64_t count[8];   /* rays per status */
+  uint64_t evals;
+  uint32_t steps_max;
+  float t_min, t_max;  /* over the HIT and CROSSED rays; +Inf and 0 when there is none */
+  uint32_t reserved;
+  uint64_t below;      /* HIT and CROSSED rays with t < thin */
+  double ms_device;    /* device time of the kernel, HIP events */
+} gsdf_ray_stats;
+GSDF_ABI_ASSERT(sizeof(gsdf_ray_stats) == 112, "gsdf_ray_stats is 112 bytes");
+GSDF_ABI_ASSERT(offsetof(gsdf_ray_stats, count) == 8 && offsetof(gsdf_ray_stats, evals) == 72 && offsetof(gsdf_ray_stats, steps_max) == 80 && offsetof(gsdf_ray_stats, t_min) == 84, "gsdf_ray_stats counts");
+GSDF_ABI_ASSERT(offsetof(gsdf_ray_stats, t_max) == 88 && offsetof(gsdf_ray_stats, below) == 96 && offsetof(gsdf_ray_stats, ms_device) == 104, "gsdf_ray_stats extremes and cost");
+int gsdf_hip_raycast3(gsdf_program* p, const float* rays, size_t n, const gsdf_ray_opts* o, float thin, float* t_out, float* d_out, uint8_t* status_out, uint16_t* steps_out, gsdf_ray_stats* st);
+int gsdf_hip_indexed_thickness(gsdf_indexed* ix, gsdf_program* p, const gsdf_thickness_opts* o, float* thickness_out, uint8_t* status_out, gsdf_ray_stats* st);
 
 /* ---- indexed meshes: dual contouring (no reference counterpart: the reference's dual-contouring mesh is a triangle list too) -------
  *

@@ -353,6 +353,82 @@ func (ix *IndexedHIP) Fit() (before, after []float32, status []uint8, err error)
 	return before, after, status, nil
 }
 
+// Ray is one ray of RaycastHIP: 24 bytes, the origin and the direction. The direction is used as given, so T is in units of its length.
+type Ray struct {
+	Origin, Dir ms3.Vec
+}
+
+// RayOpts is gsdf_ray_opts: where the march starts (T0) and ends (TMax, +Inf allowed), the hit tolerance, the shortest step, the
+// march evaluations per ray (1 .. 4096) and the bisections of a crossing's bracket (0 .. 32).
+type RayOpts struct {
+	T0, TMax, Tol, MinStep float32
+	MaxSteps, Refine       int
+}
+
+// RayStats is gsdf_ray_stats: what a batch of rays, or the thickness of a mesh, found, and its device time. Count is indexed by the
+// status byte: skipped, hit, crossed, miss, steps, nonfinite, flat. TMin and TMax are over the hit and crossed rays (+Inf and 0
+// when there is none); Below counts those with t < thin.
+type RayStats struct {
+	N           uint64
+	Count       [8]uint64
+	Evaluations uint64
+	StepsMax    uint32
+	TMin, TMax  float32
+	Below       uint64
+	Millis      float64
+}
+
+func rayStats(rs *C.gsdf_ray_stats) RayStats {
+	stats := RayStats{
+		N: uint64(rs.n), Evaluations: uint64(rs.evals), StepsMax: uint32(rs.steps_max), TMin: float32(rs.t_min), TMax: float32(rs.t_max),
+		Below: uint64(rs.below), Millis: float64(rs.ms_device),
+	}
+	for k := range stats.Count {
+		stats.Count[k] = uint64(rs.count[k])
+	}
+	return stats
+}
+
+// RaycastHIP sphere-traces rays through the field of s on the device, from outside or inside the part (gsdf_hip.h states every
+// term): per ray the parameter t of what it found, the distance there, the status byte and the evaluations it took. A query, not
+// a guarantee: a field that is not 1-Lipschitz, or a MinStep larger than a wall, can step over a wall.
+func RaycastHIP(s *gleval.SDF3HIP, rays []Ray, o RayOpts, thin float32) (t, d []float32, status []uint8, steps []uint16, stats RayStats, err error) {
+	if len(rays) == 0 {
+		return nil, nil, nil, nil, RayStats{}, hipErr(C.GSDF_ERR_EMPTY_BUFFERS)
+	}
+	ro := C.gsdf_ray_opts{t0: C.float(o.T0), tmax: C.float(o.TMax), tol: C.float(o.Tol), min_step: C.float(o.MinStep), max_steps: C.int32_t(o.MaxSteps), refine: C.int32_t(o.Refine)}
+	var rs C.gsdf_ray_stats
+	t, d, status, steps = make([]float32, len(rays)), make([]float32, len(rays)), make([]uint8, len(rays)), make([]uint16, len(rays))
+	if rc := C.gsdf_hip_raycast3(hipProgram(s), (*C.float)(unsafe.Pointer(&rays[0])), C.size_t(len(rays)), &ro, C.float(thin), (*C.float)(unsafe.Pointer(&t[0])), (*C.float)(unsafe.Pointer(&d[0])), (*C.uint8_t)(unsafe.Pointer(&status[0])), (*C.uint16_t)(unsafe.Pointer(&steps[0])), &rs); rc != 0 {
+		return nil, nil, nil, nil, RayStats{}, hipErr(rc)
+	}
+	return t, d, status, steps, rayStats(&rs), nil
+}
+
+// Thickness is the wall thickness of the mesh against the field of s, by rays: per vertex the distance to the opposite wall along
+// the inward normal (central differences of step, as Normals), marched through the field from o.T0 (pick it above o.Tol). +Inf
+// where the ray left through o.TMax, NaN where there is no answer; at a sharp convex edge it is legitimately small. With dry set
+// only the stats are computed (TMin, TMax, Below: the vertices thinner than thin).
+func (ix *IndexedHIP) Thickness(s *gleval.SDF3HIP, o RayOpts, step, thin float32, dry bool) (thickness []float32, status []uint8, stats RayStats, err error) {
+	to := C.gsdf_thickness_opts{step: C.float(step), thin: C.float(thin)}
+	to.ray = C.gsdf_ray_opts{t0: C.float(o.T0), tmax: C.float(o.TMax), tol: C.float(o.Tol), min_step: C.float(o.MinStep), max_steps: C.int32_t(o.MaxSteps), refine: C.int32_t(o.Refine)}
+	var rs C.gsdf_ray_stats
+	if ix.V == 0 {
+		return nil, nil, RayStats{}, hipErr(C.GSDF_ERR_EMPTY_BUFFERS)
+	}
+	if dry {
+		if rc := C.gsdf_hip_indexed_thickness(ix.h, hipProgram(s), &to, nil, nil, &rs); rc != 0 {
+			return nil, nil, RayStats{}, hipErr(rc)
+		}
+		return nil, nil, rayStats(&rs), nil
+	}
+	thickness, status = make([]float32, ix.V), make([]uint8, ix.V)
+	if rc := C.gsdf_hip_indexed_thickness(ix.h, hipProgram(s), &to, (*C.float)(unsafe.Pointer(&thickness[0])), (*C.uint8_t)(unsafe.Pointer(&status[0])), &rs); rc != 0 {
+		return nil, nil, RayStats{}, hipErr(rc)
+	}
+	return thickness, status, rayStats(&rs), nil
+}
+
 // Close frees the device and pinned host buffers of the mesh.
 func (ix *IndexedHIP) Close() {
 	if ix.h != nil {
