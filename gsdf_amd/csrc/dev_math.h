@@ -44,6 +44,60 @@ DM_INL float signf(float a) { return a == 0.0f ? 0.0f : copysignf_(1.0f, a); }
 DM_INL float clampf(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
 DM_INL float mixf(float x, float y, float a) { return x * (1.0f - a) + y * a; }
 
+// ---- Wave votes and lane masks that stay on the scalar unit.
+// A compare writes its lane mask into an SGPR pair; a vote should cost the compares, scalar and/or, one scalar compare with exec.
+// What hipcc / hiprtc for gfx950 make of the source forms (-O3; "round trip" = v_cndmask_b32 v, 0, 1, mask + v_cmp_ne_u32 mask', 0, v:
+// two instructions of the 4-cycle class that move a mask the SGPRs already hold through a VGPR):
+//   __all(p), p = several ANDed compares                 compares, s_and, ROUND TRIP, s_cmp_lg_u64 vcc, exec
+//   ballot_w64(p) == read_exec(), p compound             the same
+//   ballot_w64(!p) == 0, p compound, feeding a branch    negated compares, s_or, s_cbranch_vccz -- but under -fno-honor-nans (the
+//                                                        per-tree build) the ROUND TRIP is back, and the negation is folded into the
+//                                                        compare (!(x >= c) becomes x < c: a NaN then VOTES FOR the short route)
+//   the same feeding a select (small bodies)             ROUND TRIP
+//   __any(p) / ballot_w64(p) != 0, p compound            ROUND TRIP under -fno-honor-nans
+//   popcount(__ballot(a && b))                           s_and, ROUND TRIP, s_bcnt1
+//   ballot_w64(a) & ballot_w64(b), a and b ONE compare   compares, s_and; then s_cmp_eq_u64 m, exec / s_bcnt1 / mbcnt: no round trip,
+//                                                        the compares as written (NaN fails an ordered compare), either flag set
+// So: every ballot here takes ONE comparison, compound predicates are and/or of such masks, and "all" is a scalar compare of the
+// mask with the active lanes. Inactive lanes are 0 in every ballot and in wave_exec(), so the votes hold for any exec mask; all
+// ballots of one vote must run under the same exec (wave-uniform control flow between them).
+DM_INL uint64_t wave_mask(bool one_compare) { return __builtin_amdgcn_ballot_w64(one_compare); }
+DM_INL uint64_t wave_exec() { return __builtin_amdgcn_ballot_w64(true); }
+DM_INL bool wave_all(bool one_compare) { return wave_mask(one_compare) == wave_exec(); }
+DM_INL bool wave_any(bool one_compare) { return wave_mask(one_compare) != 0ull; }
+DM_INL bool wave_all_of(uint64_t m) { return (wave_exec() & ~m) == 0ull; }
+// "every point of every lane passes every test": one also() per comparison
+struct wave_ok {
+  uint64_t m = ~0ull;
+  DM_INL void also(bool one_compare) { m &= wave_mask(one_compare); }
+  DM_INL bool all() const { return wave_all_of(m); }
+};
+// A wave-uniform word whose bits are flags that cross branches (the brick mask). Tested as `((w >> n) & 1u) != 0u` on the plain word, the
+// compiler hoists the tests, keeps each flag as a lane mask and, where the far side of a branch wants its negation, inverts it through a
+// VGPR (v_cndmask 0/1, v_cmp_ne 1). Here the shift comes back through readfirstlane -- which costs nothing on a value that already sits
+// in an SGPR -- so every use is its own SGPR integer, tested with s_bitcmp / s_cmp where it stands; the call sites read as before.
+// (Not for a vote's verdict: that one IS a lane mask, and readfirstlane makes it a v_cndmask and a v_readfirstlane.)
+struct uniform_word {
+  uint32_t w;
+  DM_INL uint32_t operator>>(uint32_t n) const { return (uint32_t)__builtin_amdgcn_readfirstlane((int)(w >> n)); }
+};
+// A predicate that is needed BOTH as the lane's flag and as the wave's mask (a lane stores where its flag is set, at the rank mbcnt takes
+// from the mask): written once, from single comparisons, and combined with & | ~ so that the two cannot drift apart. ~ masks with exec:
+// inactive lanes stay 0 in every mask.
+struct lane_pred {
+  bool lane;
+  uint64_t wave;
+};
+DM_INL lane_pred pred(bool one_compare) { return lane_pred{one_compare, wave_mask(one_compare)}; }
+DM_INL lane_pred operator&(lane_pred a, lane_pred b) { return lane_pred{a.lane && b.lane, a.wave & b.wave}; }
+DM_INL lane_pred operator|(lane_pred a, lane_pred b) { return lane_pred{a.lane || b.lane, a.wave | b.wave}; }
+DM_INL lane_pred operator~(lane_pred a) { return lane_pred{!a.lane, wave_exec() & ~a.wave}; }
+// the same accumulation for one lane on its own (code outside the voted call sites)
+struct lane_ok {
+  bool v = true;
+  DM_INL void also(bool p) { v = v && p; }
+};
+
 // Correctly rounded n/d for a WAVE-UNIFORM divisor d whose correctly rounded reciprocal r = RN(1/d) was
 // computed on the host (compile.cpp: recip_for): q0 = RN(n*r), two Markstein corrections
 // q <- RN(q + RN(n - d*q)*r) with the residual exact by FMA. After the first correction q is a faithful
@@ -66,8 +120,7 @@ DM_INL float div_by_uniform(float n, float d, float r) {
 // (wave-uniform branch; identical bits either way).
 template <int K>
 DM_INL void div_uniform_k(const float (&n)[K], float d, float r, float (&q)[K]) {
-  bool fast = r != 0.0f;
-  if (fast) {
+  if (r != 0.0f) {
     float nmin = 1.0f, nmax = 1.0f;
 #pragma unroll
     for (int k = 0; k < K; k++) {
@@ -75,12 +128,11 @@ DM_INL void div_uniform_k(const float (&n)[K], float d, float r, float (&q)[K]) 
       nmin = minf(nmin, absf(n[k]));
       nmax = maxf(nmax, absf(n[k]));
     }
-    fast = __all(nmin >= 8.0779357e-28f /* 2^-90 */ && nmax <= 1.2379400e+27f /* 2^90 */) != 0;
+    // (the verdict is tested where it is formed: a wave-uniform bool carried over the branch comes back as a vector i1)
+    if (wave_all_of(wave_mask(nmin >= 8.0779357e-28f /* 2^-90 */) & wave_mask(nmax <= 1.2379400e+27f /* 2^90 */))) return;
   }
-  if (!fast) {
 #pragma unroll
-    for (int k = 0; k < K; k++) q[k] = n[k] / d;
-  }
+  for (int k = 0; k < K; k++) q[k] = n[k] / d;
 }
 DM_INL bool div_fast_ok(float n) {
   const float a = absf(n);
@@ -138,7 +190,7 @@ DM_INL void sqrt_k(const float (&s)[K], float (&r)[K]) {
   }
   // (v_min_f32 drops a NaN operand: a NaN argument beside ordinary ones takes the core, which returns what v_sqrt_f32 returns for it,
   // as the expansion does; all NaN: the compare fails, the compiler's path)
-  if (__all(m >= 1.2621774483536189e-29f /* 2^-96 */)) {
+  if (wave_all(m >= 1.2621774483536189e-29f /* 2^-96 */)) {
 #pragma unroll
     for (int k = 0; k < K; k++) r[k] = sqrt_core(s[k]);
     return;
@@ -321,11 +373,12 @@ DM_INL float atan2_ref(float yf, float xf) {
 // does not cover (hi outside [2^-100, 2^100]: zeros, infinities, NaN, where v_rcp_f32 would leave the normal range) -- the caller
 // votes and evaluates atan2_ref for the wave. ~46 instructions. Checked on device against atan2_ref: gsdf_hip_selftest_atan2
 // (2^32 hashed pairs of every magnitude and sign, 2^30 pairs searched towards rounding boundaries, lattice-shaped pairs).
-DM_INL float atan2_fast(float yf, float xf, bool& ok) {
+template <typename OK /* wave_ok: the caller votes; lane_ok */>
+DM_INL float atan2_fast(float yf, float xf, OK& ok) {
   const float ax = absf(xf), ay = absf(yf);
   const float hi = maxf(ax, ay), lo = minf(ax, ay);
   const bool swap = ay > ax;
-  ok = (__float_as_uint(hi) - 0x0D800000u) < (0x71800000u - 0x0D800000u);  // 2^-100 <= hi < 2^100 (also: not 0, Inf, NaN)
+  ok.also((__float_as_uint(hi) - 0x0D800000u) < (0x71800000u - 0x0D800000u));  // 2^-100 <= hi < 2^100 (also: not 0, Inf, NaN)
   const double hid = (double)hi, lod = (double)lo;
   double rr = (double)__builtin_amdgcn_rcpf(hi);
   rr = __builtin_fma(rr, __builtin_fma(-hid, rr, 1.0), rr);
@@ -354,14 +407,14 @@ DM_INL float atan2_fast(float yf, float xf, bool& ok) {
   double r = __builtin_fma((double)k, DM_PI / 2, sa);  // >= +0
   r = __longlong_as_double(__double_as_longlong(r) | ((long long)(__float_as_uint(yf) >> 31) << 63));  // copysign(r, y)
   const float f1 = (float)__builtin_fma(r, 0x1p-40, r), f2 = (float)__builtin_fma(r, -0x1p-40, r);
-  ok = ok && (__float_as_uint(f1) == __float_as_uint(f2));
+  ok.also(__float_as_uint(f1) == __float_as_uint(f2));
   return f1;
 }
 // (single points: selftests, code outside the interpreter's voted call sites)
 DM_INL float atan2f_(float yf, float xf) {
-  bool ok;
+  lane_ok ok;
   const float f = atan2_fast(yf, xf, ok);
-  return ok ? f : atan2_ref(yf, xf);
+  return ok.v ? f : atan2_ref(yf, xf);
 }
 
 DM_INL double trig_poly_sin(double z, double zz) {
@@ -432,10 +485,11 @@ DM_INL void cossinf_(float xf, float& c_out, float& s_out) {
 // 2^-49 (relative) of Go's float64 g, and float32(g) is decided wherever every float64 within 2^-44 of r rounds to one float32:
 // float32(r (1 + 2^-44)) == float32(r (1 - 2^-44)), bit for bit, for both results. One value in ~2^19 is rejected. ~62 instructions.
 // Checked against cossinf_ on device for EVERY float32 argument (gsdf_hip_selftest_cossin: 2^32 bit patterns).
-DM_INL void cossin_fast(float xf, float& c_out, float& s_out, bool& ok) {
+template <typename OK /* wave_ok or lane_ok, as atan2_fast */>
+DM_INL void cossin_fast(float xf, float& c_out, float& s_out, OK& ok) {
   const double xs = (double)xf;
   const double x = __builtin_fabs(xs);
-  ok = absf(xf) < 1048576.0f;  // 2^20 (NaN: false)
+  ok.also(absf(xf) < 1048576.0f);  // 2^20 (NaN: false)
   int j = (int)(x * (4.0 / DM_PI));  // truncates; < 1.34e6
   j += j & 1;                        // "map zeros to origin": odd octants belong to the next even one
   const double y = (double)j;
@@ -465,7 +519,8 @@ DM_INL void cossin_fast(float xf, float& c_out, float& s_out, bool& ok) {
   const double sn = __longlong_as_double(__double_as_longlong(s0) ^ ((long long)ssign << 63));
   const float c1 = (float)__builtin_fma(c, 0x1p-44, c), c2 = (float)__builtin_fma(c, -0x1p-44, c);
   const float s1 = (float)__builtin_fma(sn, 0x1p-44, sn), s2 = (float)__builtin_fma(sn, -0x1p-44, sn);
-  ok = ok && __float_as_uint(c1) == __float_as_uint(c2) && __float_as_uint(s1) == __float_as_uint(s2);
+  ok.also(__float_as_uint(c1) == __float_as_uint(c2));
+  ok.also(__float_as_uint(s1) == __float_as_uint(s2));
   c_out = c1;
   s_out = xf == 0.0f ? xf : s1;  // Sin(+-0) = +-0
 }

@@ -115,7 +115,10 @@ __device__ __forceinline__ bool poly_edges(code_ptr code, uint32_t q, uint32_t n
     KLOOP neg[kp] = ((negm[kp] >> lane) & 1ull) != 0ull;
   }
   if (!FAST) return true;
-  return __all(nmin >= 8.0779357e-28f /* 2^-90 */ && nmax <= 1.2379400e+27f /* 2^90 */);
+  // (the two comparisons stand here, beside their ballots: left to itself the compiler evaluates them at the end of each path into
+  // this block -- constants where no edge was kept -- and the ballots of the merged booleans go through a VGPR each)
+  asm volatile("" : "+v"(nmin), "+v"(nmax));
+  return wave_all_of(wave_mask(nmin >= 8.0779357e-28f /* 2^-90 */) & wave_mask(nmax <= 1.2379400e+27f /* 2^90 */));
 }
 
 // Edge culling for poly2D where a wave is spatially compact: the leaf kernel's bricks (one wave = the corners of 4x4x4
@@ -220,8 +223,10 @@ __device__ __forceinline__ void poly_cull(code_ptr code, uint32_t q0, uint32_t n
   // above the smallest padded upper bound. (Round 3 padded every edge by the largest m of the wave: one more reduction.)
   const float m = 1.0e-5f * (absf(wx) + absf(wy) + absf(ex) + absf(ey) + rb + absf(cx) + absf(cy));
   const float U = wave_minmax<false>(valid ? (dc + rb) + m : __builtin_inff());
-  keepd = __builtin_amdgcn_ballot_w64(valid && !((dc - rb) - m > U));
-  keeps = __builtin_amdgcn_ballot_w64(valid && !((y0 >= v1y && y0 >= v2y) || (y1 < v1y && y1 < v2y)));
+  // (one ballot per comparison, combined as masks: dev_math.h, wave_mask; the negations are of masks, the comparisons stay as written)
+  const uint64_t vm = nv >= 64u ? ~0ull : (1ull << nv) - 1ull;  // valid, as the wave's lane mask (all 64 lanes are active: wave_box)
+  keepd = vm & ~wave_mask((dc - rb) - m > U);
+  keeps = vm & ~((wave_mask(y0 >= v1y) & wave_mask(y0 >= v2y)) | (wave_mask(y1 < v1y) & wave_mask(y1 < v2y)));
 }
 
 // f(P.x, P.y) of the K points of a lane for the instructions flagged D_FLAG_SHXY (hypot, atan2).
@@ -274,9 +279,9 @@ __device__ __forceinline__ void atan2_shared(const P3 (&pv)[K], float (&out)[K],
   // (one angle per lane for all of its points -- a column brick under an axis-aligned frame, npt-flange's thread -- is cheap either
   // way, and the short route's float64 temporaries cost that build its fifth workgroup per CU: the reference's sequence there)
   if (!(shared && column)) {  // (wave-uniform: instruction flags)
-    bool ok = true;
-    xy_shared<K>(pv, out, shared, brick, [&ok](float x, float y) { bool o; const float v = dm::atan2_fast(y, x, o); ok = ok && o; return v; }, column);
-    if (__all(ok)) return;
+    dm::wave_ok ok;  // (every call of the lambda runs under the same exec: xy_shared branches on wave-uniform flags only)
+    xy_shared<K>(pv, out, shared, brick, [&ok](float x, float y) { return dm::atan2_fast(y, x, ok); }, column);
+    if (ok.all()) return;
   }
 #endif
   xy_shared<K>(pv, out, shared, brick, [](float x, float y) { return dm::atan2_ref(y, x); }, column);
@@ -286,9 +291,9 @@ __device__ __forceinline__ void atan2_shared(const P3 (&pv)[K], float (&out)[K],
 // some lane's result is not decided by the short route. (Per-tree builds only, like the short atan2: see atan2_shared.)
 __device__ __forceinline__ void cossin_voted(float x, float& c, float& s) {
 #if defined(GSDF_SPECIALIZED) && !defined(GSDF_NO_COSSIN_FAST)
-  bool ok;
+  dm::wave_ok ok;
   dm::cossin_fast(x, c, s, ok);
-  if (__all(ok)) return;
+  if (ok.all()) return;
 #endif
   dm::cossinf_(x, c, s);
 }
@@ -358,23 +363,27 @@ template <int K, int DIM, bool LIP = false>
 __device__ __forceinline__ bool gate_far(const P3 (&pv)[K], const float (&a)[K], const float (&L)[K], float sg, float kk,
                                          const float (&c)[K], bool has_outer, float ok, float k4, bool* lane_good = nullptr) {
   using namespace dm;
-  bool far = true, far2 = true;
+  // the wave's verdict as lane masks, one ballot per comparison (dev_math.h: wave_mask); the lane's own verdict (interval mode only)
+  // is its bit of the mask (a comparison that also fed a per-lane && would lose its ballot's fold: a round trip each)
+  uint64_t farm = ~0ull, far2m = ~0ull;
   KLOOP {
     float S = absf(pv[kp].x) + absf(pv[kp].y);
     if (DIM == 3) S += absf(pv[kp].z);
     const float pad = 2e-6f * S;
-    const bool g1 = (L[kp] > 0.0f) && (L[kp] > sg * a[kp] + kk + (1e-3f * (L[kp] + absf(a[kp])) + pad));
-    bool g2 = false;
+    const uint64_t m1 = wave_mask(L[kp] > 0.0f) & wave_mask(L[kp] > sg * a[kp] + kk + (1e-3f * (L[kp] + absf(a[kp])) + pad));
+    uint64_t m2 = 0ull;
     if (has_outer) {
       const float U = maxf(a[kp], -L[kp]) + k4;
-      g2 = (U < 0.0f) && (c[kp] + U <= -ok - (1e-3f * (absf(c[kp]) + absf(U)) + pad));
+      m2 = wave_mask(U < 0.0f) & wave_mask(c[kp] + U <= -ok - (1e-3f * (absf(c[kp]) + absf(U)) + pad));
     }
-    if (LIP) { far = far && g1; far2 = far2 && g2; }
-    else far = far && (g1 || g2);
+    if (LIP) { farm &= m1; far2m &= m2; }
+    else farm &= m1 | m2;
   }
-  if (LIP) far = far || (has_outer && far2);
-  if (lane_good != nullptr) *lane_good = far;
-  return __all(far) != 0;
+  if (LIP) {
+    if (has_outer) farm |= far2m;
+    if (lane_good != nullptr) *lane_good = ((farm >> lane_id()) & 1ull) != 0ull;
+  }
+  return wave_all_of(farm);
 }
 
 // hypot of the K points of a lane for the "outside distance" terms hypot(max(a,0), max(b,0)) of boxes, cylinders, prisms
@@ -385,14 +394,14 @@ template <int K>
 __device__ __forceinline__ void hypot_k(const float (&a)[K], const float (&b)[K], float (&out)[K]) {
   using namespace dm;
   float hi[K], lo[K];
-  bool z = true;
+  wave_ok z;
   KLOOP {
     const float p = absf(a[kp]), q = absf(b[kp]);
     hi[kp] = maxf(p, q);
     lo[kp] = minf(p, q);
-    z = z && (lo[kp] == 0.0f);
+    z.also(lo[kp] == 0.0f);
   }
-  if (__all(z)) {
+  if (z.all()) {
     KLOOP out[kp] = hi[kp];
   } else {
     KLOOP {
@@ -409,9 +418,10 @@ template <int K, int SIGN>
 __device__ __forceinline__ void smooth_h(const float (&num)[K], float k, float rk, float (&h)[K]) {
   using namespace dm;
   const float thr = absf(0.5f * k) * 1.001f;
-  bool out = k != 0.0f;
-  KLOOP out = out && (absf(num[kp]) >= thr);
-  if (__all(out)) {
+  wave_ok out;
+  out.also(k != 0.0f);
+  KLOOP out.also(absf(num[kp]) >= thr);
+  if (out.all()) {
     KLOOP h[kp] = (((num[kp] > 0.0f) == (k > 0.0f)) == (SIGN > 0)) ? 1.0f : 0.0f;
   } else {
     float q[K];
@@ -481,6 +491,7 @@ __device__ __forceinline__ void smooth_h(const float (&num)[K], float k, float r
           if (reach) lipR = GSDF_LIP_BIG;                                                                                              \
         }                                                                                                                              \
 
+static_assert(GSDF_BRICK_MASK_VALID == 1u << 31, "GSDF_GATE_TEST reads the brick mask's valid flag as bit 31");
 // The test of a D_GATE* instruction (dev_ops.h), shared by the interpreter's four cases and the specialised build's generated
 // text: REGION fills L[] from the gate's region parameters; I0 = index of the `sg` parameter (then kk, oslot, ok, k4, skip word).
 // Leaves far_ (wave-uniform: the child is skipped) and L (the substitute) in scope.
@@ -490,7 +501,7 @@ __device__ __forceinline__ void smooth_h(const float (&num)[K], float k, float r
   {                                                                                                                         \
     const uint32_t gid1 = GSDF_GATE_ID1(PU((I0) + 5));                                                                      \
     /* a numbered child under a valid brick mask: the centre test decided for the whole brick (D_SKIP), no per-point test */ \
-    const bool untested = !LIP && gid1 != 0u && (bmask & GSDF_BRICK_MASK_VALID) != 0u;                                      \
+    const bool untested = !LIP && gid1 != 0u && ((bmask >> 31u) & 1u) != 0u; /* GSDF_BRICK_MASK_VALID; bmask: dm::uniform_word */ \
     if (!untested) {                                                                                                        \
       float a[K], cc[K];                                                                                                    \
       const uint32_t oslot = PU((I0) + 2);                                                                                  \
@@ -515,12 +526,13 @@ __device__ __forceinline__ void sdf_eval(code_ptr code, P3 (&pv)[K], float (&Rv)
                                          float* __restrict__ lds /* already offset by tid */, const uint32_t nthreads,
                                          const bool brick = false /* wave-uniform: the wave is spatially compact (polygon edge culling pays, poly_cull); with SHARE = 2 also: point kp has the same z in every lane; see xy_shared */,
                                          const float lip_h = 0.0f, const uint32_t lip_base = 0u,
-                                         const uint32_t bmask = 0u /* wave-uniform: the brick mask of the cube this wave evaluates (dev_ops.h: D_SKIP); 0 where a wave is no brick */,
+                                         const uint32_t bmask_w = 0u /* wave-uniform: the brick mask of the cube this wave evaluates (dev_ops.h: D_SKIP); 0 where a wave is no brick */,
                                          uint32_t* lip_fired = nullptr /* interval mode: this lane's brick mask is OR-ed in here */,
                                          XYCache* xyc = nullptr /* column bricks: what the lane's other pass already knows (see XYCache) */) {
   using namespace dm;
   static_assert(!LIP || (K == 2 && SHARE == 0), "interval mode: two points per lane, lower and upper bound");
   [[maybe_unused]] float lipR = lip_h;
+  const dm::uniform_word bmask{bmask_w};  // (its bit tests stay scalar: dev_math.h)
   KLOOP Rv[kp] = 0.0f;
   float hxy[K];  // hypot(P.x, P.y) cache shared by sibling primitives (validity is tracked by the host compiler)
   KLOOP hxy[kp] = 0.0f;
@@ -1142,8 +1154,9 @@ __device__ __forceinline__ void sdf_eval(code_ptr code, P3 (&pv)[K], float (&Rv)
         bool fast = !sh_xy;
         if (fast) {
           const float inv_angle = __builtin_amdgcn_rcpf(PF(0)), m = 6e-6f * inv_angle;
-          KLOOP fast = dm::circ_sector_fast(pv[kp].x, pv[kp].y, inv_angle, m, idv[kp]) && fast;
-          fast = __builtin_amdgcn_ballot_w64(!fast) == 0ull;  // wave-uniform
+          dm::wave_ok decided;
+          KLOOP decided.also(dm::circ_sector_fast(pv[kp].x, pv[kp].y, inv_angle, m, idv[kp]));
+          fast = decided.all();  // wave-uniform
         }
         if (!fast) {
           float th[K];  // atan2(P.y, P.x): a function of x,y only (a rare path -- a point on a sector boundary: the reference's sequence)

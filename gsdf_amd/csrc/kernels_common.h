@@ -55,7 +55,13 @@ __device__ __forceinline__ bool nan_or_inf(float v) { return __builtin_amdgcn_cl
 __device__ __forceinline__ bool abs_le(float v, float lim) { return (__float_as_uint(v) & 0x7fffffffu) <= __float_as_uint(lim); }
 __device__ __forceinline__ bool abs_ge(float v, float lim) {
   const unsigned a = __float_as_uint(v) & 0x7fffffffu;
-  return a >= __float_as_uint(lim) && a <= 0x7f800000u;
+  return a >= __float_as_uint(lim) && a <= 0x7f800000u;  // (abs_ge_p below: the same two comparisons)
+}
+// abs_le / abs_ge as lane flag and wave mask at once (dev_math.h: lane_pred), from the same comparisons
+__device__ __forceinline__ dm::lane_pred abs_le_p(float v, float lim) { return dm::pred(abs_le(v, lim)); }
+__device__ __forceinline__ dm::lane_pred abs_ge_p(float v, float lim) {
+  const unsigned a = __float_as_uint(v) & 0x7fffffffu;
+  return dm::pred(a >= __float_as_uint(lim)) & dm::pred(a <= 0x7f800000u);
 }
 // the per-vertex / per-ray kernels (kernels_project.h, kernels_ray.h): |v| as bits; NaN by its bits; |v| > lim for the bits of a finite
 // lim >= 0, false for a NaN v; the largest of a wave's unsigned values, in every lane

@@ -224,6 +224,7 @@ __global__ void __launch_bounds__(BLOCK, W) dc_origin_kernel(const uint32_t* __r
     float d[K];
     unsigned cx[K], cy[K], cz[K];
     bool valid[K];
+    dm::lane_pred pvalid[K];
 #pragma unroll
     for (int kp = 0; kp < K; kp++) {
       const unsigned j = (unsigned)kp * BLOCK + threadIdx.x;
@@ -231,24 +232,26 @@ __global__ void __launch_bounds__(BLOCK, W) dc_origin_kernel(const uint32_t* __r
       cy[kp] = ty * 8u + ((j >> 3) & 7u);
       cz[kp] = zlo + tz * (4u * K) + wave * (unsigned)K + (unsigned)kp;  // (j >> 6 = 4 kp + wave until round 4: the wave's K levels four apart)
       (void)j;
-      valid[kp] = cx[kp] < n && cy[kp] < n && cz[kp] < zhi;
+      pvalid[kp] = dm::pred(cx[kp] < n) & dm::pred(cy[kp] < n) & dm::pred(cz[kp] < zhi);  // (flag and mask of one predicate: dev_math.h, lane_pred)
+      valid[kp] = pvalid[kp].lane;
       p[kp] = P3{ox + res * (float)cx[kp], oy + res * (float)cy[kp], oz + res * (float)cz[kp]};  // CubeOrigin, size = res
     }
     // Trees whose field is >= the distance to a known box (use_box): a wave whose cells all lie outside that box by
     // more than the keep radius needs no evaluation -- |d| >= distance to the box > 2*res decides "not kept" exactly.
     // (The reference sweeps its cubic lattice unconditionally; a long thin part fills a few percent of it.)
-    bool far = use_box != 0;
+    // (the vote as lane masks, one ballot per comparison: dev_math.h, wave_mask)
+    unsigned long long farm = ~0ull;
 #pragma unroll
     for (int kp = 0; kp < K; kp++) {
       const float L = dm::maxf(dm::maxf(dm::maxf(bx0 - p[kp].x, p[kp].x - bx1), dm::maxf(by0 - p[kp].y, p[kp].y - by1)),
                                dm::maxf(bz0 - p[kp].z, p[kp].z - bz1));
-      far = far && (!valid[kp] || L > maxDist * 1.001f);
+      farm &= ~pvalid[kp].wave | dm::wave_mask(L > maxDist * 1.001f);
     }
     // ... and a wave whose block the interval test cleared (dc_block_test_kernel): nothing of it is within the keep radius
     const uint32_t bflag = block_keep != nullptr ? (uint32_t)__builtin_amdgcn_readfirstlane((int)block_keep[T * 4ull + wave]) : 0x80000000u;
     const bool cleared = (bflag >> 31) == 0u;
     const uint32_t bmask = block_keep != nullptr ? ((bflag & 0xffffu) | GSDF_BRICK_MASK_VALID) : 0u;  // (no test, no mask: the gates are tested per wave)
-    if (cleared || __all(far)) {
+    if (cleared || (use_box != 0 && dm::wave_all_of(farm))) {
 #pragma unroll
       for (int kp = 0; kp < K; kp++) d[kp] = 3.0e38f;
     } else {

@@ -184,9 +184,9 @@ __global__ void __launch_bounds__(BLOCK) atan2_selftest_kernel(int mode, int log
         y = best;
       }
     }
-    bool ok;
+    dm::lane_ok ok;
     const float a = dm::atan2_fast(y, x, ok);
-    if (ok) {
+    if (ok.v) {
       nf++;
       if (__float_as_uint(a) != __float_as_uint(dm::atan2_ref(y, x))) nb++;
     }
@@ -203,9 +203,9 @@ __global__ void __launch_bounds__(BLOCK) cossin_selftest_kernel(unsigned long lo
   for (unsigned long long i = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x; i < (1ull << 32); i += (unsigned long long)gridDim.x * BLOCK) {
     const float x = __uint_as_float((unsigned)i);
     float c, s;
-    bool ok;
+    dm::lane_ok ok;
     dm::cossin_fast(x, c, s, ok);
-    if (!ok) continue;
+    if (!ok.v) continue;
     nf++;
     float cr, sr;
     dm::cossinf_(x, cr, sr);

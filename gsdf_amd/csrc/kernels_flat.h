@@ -45,7 +45,9 @@ __global__ void __launch_bounds__(BLOCK, W) flat_grid_kernel(const uint32_t* __r
       if (ok) grid[(uint64_t)k * FLAT_PITCH(sx) * sy + (uint64_t)j * FLAT_PITCH(sx) + i] = d[z];
       // the two things the marching pass wants to know about most corners, one bit each (see flat_cut_scan_kernel):
       // word (t * 4 + wave) of plane k, bit = lane, i.e. bit (i + sx * j) of the plane in the UNPADDED corner order
-      const unsigned long long ng = __ballot(ok && nb::lt0(d[z])), nr = __ballot(ok && nb::abs_le(d[z], cubeDiag));
+      // (one ballot per comparison, combined as masks: dev_math.h, wave_mask)
+      const unsigned long long okm = dm::wave_mask(col < sxy) & dm::wave_mask(k < nk);
+      const unsigned long long ng = okm & dm::wave_mask(nb::lt0(d[z])), nr = okm & dm::wave_mask(nb::abs_le(d[z], cubeDiag));
       if (k < nk && (threadIdx.x & 63u) == 0u) {
         const uint64_t wi = (uint64_t)k * (tpg * (BLOCK / 64)) + (uint64_t)t * (BLOCK / 64) + (threadIdx.x >> 6);
         negbits[wi] = ng;

@@ -84,7 +84,10 @@ __global__ void __launch_bounds__(BLOCK) prune_kernel(const uint32_t* __restrict
       c.y = (uint16_t)(pc.y * 2 + ((k >> 1) & 1));
       c.z = (uint16_t)(pc.z * 2 + ((k >> 2) & 1));
     }
-    bool keep = valid;
+    // keep: the lane's flag and the wave's mask of one predicate (dev_math.h: lane_pred) -- the lane stores where its flag is set, at
+    // the rank the mask gives it
+    const dm::lane_pred pvalid = dm::pred(valid);
+    dm::lane_pred pkeep = pvalid;
     if (do_test) {
       const float cx0 = ox + size * (float)c.x, cy0 = oy + size * (float)c.y, cz0 = oz + size * (float)c.z;
       P3 p;  // CubeCenter = Scale(0.5, Add(min, max)), max = min + size
@@ -95,20 +98,21 @@ __global__ void __launch_bounds__(BLOCK) prune_kernel(const uint32_t* __restrict
       float dv[2];
       if (do_test == 2) {
         gsdf_dev::sdf_eval<2>(code, pv, dv, lds, BLOCK);
-        keep = valid && !nb::abs_ge(dv[0], maxDist);
+        pkeep = pvalid & ~nb::abs_ge_p(dv[0], maxDist);
       } else {
         // interval evaluation over the cube's bounding ball; `fired` = this cube's brick mask (dev_ops.h: D_SKIP), handed on in
         // Cube.w: the leaf kernels read it at the last level (there the cube IS the brick a wave evaluates), the levels above ignore it
         uint32_t fired = 0u;
         gsdf_dev::sdf_eval<2, 0, true>(code, pv, dv, lds, BLOCK, false, maxDist, (uint32_t)lip_base, 0u, &fired);
-        keep = valid && !(nb::ge0(dv[0]) || nb::le0(dv[1]));
+        pkeep = pvalid & ~(dm::pred(nb::ge0(dv[0])) | dm::pred(nb::le0(dv[1])));
         c.w = (uint16_t)fired;
       }
     }
-    const unsigned long long pm = __ballot(keep);
+    const unsigned long long pm = pkeep.wave;
     if (lane == 0) my_pass += (unsigned long long)__builtin_popcountll(pm);
-    if (shard_here) keep = keep && (brick_owner(c.x, c.y, c.z, shard_count) == shard_rank);
-    const unsigned long long km = __ballot(keep);
+    if (shard_here) pkeep = pkeep & dm::pred(brick_owner(c.x, c.y, c.z, shard_count) == shard_rank);
+    const bool keep = pkeep.lane;
+    const unsigned long long km = pkeep.wave;
     const unsigned lane_prefix = __builtin_amdgcn_mbcnt_hi((unsigned)(km >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)km, 0u));
     if (lane == 0) s_w[wave] = (unsigned)__builtin_popcountll(km);
     __syncthreads();
@@ -582,10 +586,10 @@ __global__ void __launch_bounds__(BLOCK, WAVES) leaf_kernel(const uint32_t* __re
         index |= (nb::lt0(dk[kp]) ? 1u : 0u) << c;
       }
       if (c0 == 0) {
-        pass = valid && nb::abs_le(dk[0], cubeDiag);
-        const unsigned long long pmask = __ballot(pass);
+        const dm::lane_pred pvalid = dm::pred(valid), ppass = pvalid & nb::abs_le_p(dk[0], cubeDiag);  // (flag and mask of one predicate: dev_math.h, lane_pred)
+        pass = ppass.lane;
+        const unsigned long long vmask = pvalid.wave, pmask = ppass.wave;
         if (pmask == 0ull) break;  // wave-uniform
-        const unsigned long long vmask = __ballot(valid);
         // wave-uniform counters (every lane adds the same scalar): they live in SGPRs, not in four VGPRs
         my_active += (unsigned)__builtin_popcountll(pmask);
         my_cont += (unsigned)__builtin_popcountll(vmask);
@@ -685,12 +689,14 @@ __global__ void __launch_bounds__(BLOCK, WAVES) leaf_kernel(const uint32_t* __re
 // marching-cubes case (nb::lt0 of each corner: -0.0 and NaN are not negative); lxy, lz: leaf x | y << 16 and leaf z (16 bits each);
 // blk is wave-uniform. ROWS: the group sum also carries the z rows evaluated, for every block (DZ).
 template <bool NTLDS, bool ROWS>
-__device__ __forceinline__ void leaf_block_tail(const float (&dc)[8], unsigned index, bool pass, unsigned nact, unsigned zrows, uint32_t lxy,
+__device__ __forceinline__ void leaf_block_tail(const float (&dc)[8], unsigned index, dm::lane_pred pass /* the corner-0 test: lane flag and wave mask */, unsigned nact, unsigned zrows, uint32_t lxy,
                                                 uint32_t lz, uint64_t blk, unsigned long long n_blocks_cap, const uint8_t* s_nt,
                                                 uint32_t* __restrict__ hdr, uint32_t* __restrict__ rec, unsigned long long* __restrict__ psum) {
-  const bool cut = pass && index != 0u && index != 255u;
-  // compact the cut leaves of this wave's block: rank among the cut lanes, one header word per block
-  const unsigned long long cm = __ballot(cut);
+  // compact the cut leaves of this wave's block: rank among the cut lanes, one header word per block (the lane's flag and the wave's
+  // mask of one predicate, a ballot per comparison: dev_math.h, lane_pred)
+  const dm::lane_pred pcut = pass & dm::pred(index != 0u) & dm::pred(index != 255u);
+  const bool cut = pcut.lane;
+  const unsigned long long cm = pcut.wave;
   const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(cm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)cm, 0u));
   if (blk < n_blocks_cap) {
     // header word: records | triangles << 8; the same pair is added to the sum of the block's group of MARCH_GROUP
@@ -795,7 +801,7 @@ __global__ void __launch_bounds__(BLOCK, WAVES) leaf_eval_kernel(const uint32_t*
       lz = (uint32_t)lf.z;
     }
     unsigned index = 0;
-    bool pass = false;
+    dm::lane_pred pass = {false, 0ull};  // the corner-0 test: the lane's flag and the wave's mask (dev_math.h: lane_pred)
     float dc[8];  // the leaf's corner distances, by corner number
     if (UCUBE) {
       // COLUMN BRICK. The 512 evaluations of a brick -- 64 leaves x 8 corners -- are the product of eight x, eight y and eight z
@@ -924,8 +930,8 @@ __global__ void __launch_bounds__(BLOCK, WAVES) leaf_eval_kernel(const uint32_t*
       // leaf = brick * 4 + (li, lj, lk), 16 bits each (the brick's low two bits are clear: + is |)
       lxy = ((bx & 0xffffu) | ((by & 0xffffu) << 16)) | (li | (lj << 16));
       lz = (bz & 0xffffu) | lk;
-      pass = nb::abs_le(dc[0], cubeDiag);
-      nact = (unsigned)__builtin_popcountll(__ballot(pass));
+      pass = nb::abs_le_p(dc[0], cubeDiag);
+      nact = (unsigned)__builtin_popcountll(pass.wave);
     } else {
       const float x0 = ox + res * (float)lf.x, y0 = oy + res * (float)lf.y, z0 = oz + res * (float)lf.z;
       const float x1 = x0 + res, y1 = y0 + res, z1 = z0 + res;  // Box max = origin + size
@@ -953,12 +959,11 @@ __global__ void __launch_bounds__(BLOCK, WAVES) leaf_eval_kernel(const uint32_t*
           index |= (nb::lt0(dk[kp]) ? 1u : 0u) << c;
         }
         if (c0 == 0) {
-          pass = valid && nb::abs_le(dk[0], cubeDiag);
-          const unsigned long long pmask = __ballot(pass);
-          if (pmask == 0ull) break;  // wave-uniform
-          const unsigned long long vmask = __ballot(valid);
-          nact = (unsigned)__builtin_popcountll(pmask);
-          my_cont += (unsigned)__builtin_popcountll(vmask);
+          const dm::lane_pred pvalid = dm::pred(valid);
+          pass = pvalid & nb::abs_le_p(dk[0], cubeDiag);
+          if (pass.wave == 0ull) break;  // wave-uniform
+          nact = (unsigned)__builtin_popcountll(pass.wave);
+          my_cont += (unsigned)__builtin_popcountll(pvalid.wave);
         }
       }
       // dall[j] is the distance of corner order[j], order = {0,4,1,5,3,7,2,6}
@@ -1095,8 +1100,8 @@ __global__ void __launch_bounds__(BLOCK, WAVES) leaf_dense_kernel(const uint32_t
       index |= (nb::lt0(dc[c]) ? 1u : 0u) << c;
     }
     __builtin_amdgcn_wave_barrier();  // (the next brick rewrites D and the table)
-    const bool pass = nb::abs_le(dc[0], cubeDiag);
-    const unsigned nact = (unsigned)__builtin_popcountll(__ballot(pass));
+    const dm::lane_pred pass = nb::abs_le_p(dc[0], cubeDiag);
+    const unsigned nact = (unsigned)__builtin_popcountll(pass.wave);
     // leaf = brick * 4 + (la, lb, lc), 16 bits each: the brick's part is scalar and its low two bits are clear (+ is |), the lane's
     // part does not change from brick to brick -- one or per word and brick, as in leaf_eval_kernel
     const uint32_t bxy = ((pidx[0] << 2) & 0xffffu) | (((pidx[1] << 2) & 0xffffu) << 16), bzw = (pidx[2] << 2) & 0xffffu;
@@ -1841,8 +1846,9 @@ __global__ void __launch_bounds__(BLOCK, WAVES) leaf_brick_kernel(const uint32_t
     unsigned index = 0;
 #pragma unroll
     for (unsigned cc = 0; cc < 8; cc++) index |= (nb::lt0(vdist(cc)) ? 1u : 0u) << cc;
-    const bool pass = bvalid && nb::abs_le(vdist(0), cubeDiag);
-    const unsigned long long pmask = __ballot(pass);
+    const dm::lane_pred ppass = dm::pred(bvalid) & nb::abs_le_p(vdist(0), cubeDiag);
+    const bool pass = ppass.lane;
+    const unsigned long long pmask = ppass.wave;
     if (lane == 0) my_active += (unsigned long long)__builtin_popcountll(pmask);
     if (!pass) index = 0;
     mc_emit_block(index, x0, y0, z0, x1, y1, z1, vdist, s_tri, s_stage, s_misc, s_base, tris, tri_cap, ctr);

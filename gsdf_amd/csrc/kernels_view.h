@@ -108,7 +108,7 @@ __global__ void __launch_bounds__(BLOCK, 4) view_kernel(const uint32_t* __restri
         }
       }
     }
-    if (__ballot(pix >= 0) == 0ull) break;
+    if (!dm::wave_any(pix >= 0)) break;
     const bool act = pix >= 0;
     // pos = ro + t rd; the normal's taps at the hit position (ui.go:324,338-339,254-260)
     const float hx = cam.ro[0] + t * rx, hy = cam.ro[1] + t * ry, hz = cam.ro[2] + t * rz;
