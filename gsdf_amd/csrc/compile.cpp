@@ -947,7 +947,7 @@ void gen(Ctx& c, uint32_t i, int depth) {
       // nearer one's value (gen_combine's rule for min). Worth it for a child that costs and has a (turned) box for a
       // region: the wave starts with the copy nearer that box (D_CIRC_ORDER) and tests the other (D_GATEOB).
       Region cg;
-      static const bool sector_off = [] { const char* e = getenv("GSDF_HIP_NO_SECTOR_GATE"); return e && atoi(e) != 0; }();  // developer knob (A/B timing)
+      const bool sector_off = [] { const char* e = getenv("GSDF_HIP_NO_SECTOR_GATE"); return e && atoi(e) != 0; }();  // developer knob (A/B timing, tests/test_progcheck.py), read at every compile
       // kSectorGateMinCost: order + gate cost ~26 instructions per point and fire for ~40 % of knurled-cylinder's surface bricks
       // (on the lands between its grooves both copies are equally near): at that scene's 95-instruction child the gate costs
       // what it saves (3.375 vs 3.370 ms, profiles/r3b_*), so it is reserved for children that cost several times the test
