@@ -166,12 +166,13 @@ extern "C" int gsdf_hip_selftest_sqrt(uint64_t* mismatches) {
 
 // Test hook: one of the device's math routes over n host values (kernels_eval.h: math_selftest_kernel), for a comparison with the
 // oracle's restatement of the same function on the host. y may be null for the functions of one argument; for fn 17 the divisor is
-// divisor (wave-uniform, with the host's RN(1/divisor) where recip_for grants one) and y is not read.
+// divisor (wave-uniform, with the host's RN(1/divisor) where recip_for grants one) and y is not read; for fn 20 / 21 it is the third
+// slab distance.
 extern "C" int gsdf_hip_selftest_math(int fn, const float* x, const float* y, float* out, uint64_t n, float divisor) {
-  if (fn < 0 || fn > 17 || !x || !out) return fail(GSDF_ERR_BAD_ARGUMENT, "fn in 0..17, x and out not null");
+  if (fn < 0 || fn > 21 || !x || !out) return fail(GSDF_ERR_BAD_ARGUMENT, "fn in 0..21, x and out not null");
   if (n == 0) return GSDF_OK;
   if (n > (1ull << 28)) return fail(GSDF_ERR_BAD_ARGUMENT, "n <= 2^28");
-  const bool two = fn == 0 || fn == 1 || fn == 8 || fn == 9 || fn == 15;
+  const bool two = fn == 0 || fn == 1 || fn == 8 || fn == 9 || fn == 15 || fn >= 18;
   if (two && !y) return fail(GSDF_ERR_BAD_ARGUMENT, "this function takes two operands");
   float* d_b = nullptr;
   const size_t bytes = (size_t)n * sizeof(float);

@@ -411,6 +411,68 @@ __device__ __forceinline__ void hypot_k(const float (&a)[K], const float (&b)[K]
   }
 }
 
+// Face form of the "inside + outside" distance of boxes, cylinders, prisms and extrusions, for the K points of a lane. With slab
+// distances u, v (each <= 0 inside its slab) those shapes return
+//     min(0, max(u, v)) + hypot(max(u, 0), max(v, 0))
+// in either operand order of the min and of the sum. Where u <= 0 or v <= 0 at EVERY point of the wave -- all of a shape's
+// neighbourhood but the wedge beyond an edge -- that sum is  max(u, v) + 0.0f  bit for bit, with m = max(u, v):
+//     m > 0:   min gives +0, one hypot argument is 0 and hypot(m, 0) = m (hypot_k's voted path): +0 + m = m = m + 0
+//     m < 0:   min gives m, both hypot arguments are 0: m + (+0)
+//     m = +-0: a sum of zeros of which hypot's is +0, so +0 whatever signs min and max pick; and (+-0) + (+0) = +0
+// The + 0.0f is what makes the last case hold (a bare max could return -0 where the sum gives +0); nothing here is compiled with
+// signed zeros ignored, so it stays. A NaN slab distance fails its compare and is dropped by v_min / v_max on both sides alike.
+// The condition implies hypot_k's (lo == 0 everywhere), so those waves took its short route already: what goes is the clamps,
+// the min and hypot_k's own max / min / compare per point -- instructions of the 4-cycle class. It only has to be sufficient: a
+// wave that fails it runs the caller's statements as they were. face2_k / face3_k are the votes (tested where they are formed,
+// one ballot per comparison: dev_math.h, wave_mask), face_val the value. -DGSDF_NO_FACE_FORM: the votes fail at compile time.
+// Three slabs (D_BOX): min(max(qx, qy, qz), 0) + norm3(max(q, 0)...) with at least two of the three <= 0 at every point; both inner
+// hypot_k votes are implied (max(qy,0), max(qz,0) not both > 0; then that hypot and max(qx,0) not both > 0), same three cases.
+template <int K>
+__device__ __forceinline__ bool face2_k(const float (&u)[K], const float (&v)[K]) {
+#ifndef GSDF_NO_FACE_FORM
+  using namespace dm;
+  uint64_t m = ~0ull;
+  KLOOP m &= wave_mask(u[kp] <= 0.0f) | wave_mask(v[kp] <= 0.0f);
+  return wave_all_of(m);
+#else
+  return false;
+#endif
+}
+template <int K>
+__device__ __forceinline__ bool face3_k(const float (&u)[K], const float (&v)[K], const float (&w)[K]) {
+#ifndef GSDF_NO_FACE_FORM
+  using namespace dm;
+  uint64_t m = ~0ull;
+  KLOOP {
+    const uint64_t mu = wave_mask(u[kp] <= 0.0f), mv = wave_mask(v[kp] <= 0.0f), mw = wave_mask(w[kp] <= 0.0f);
+    m &= (mu & mv) | ((mu | mv) & mw);
+  }
+  return wave_all_of(m);
+#else
+  return false;
+#endif
+}
+__device__ __forceinline__ float face_val(float m) { return m + 0.0f; }
+// The ops' votes. Per-tree kernels only, like the other short routes (dev_math.h: sqrt_k): with every op's two forms side by side the
+// ahead-of-time interpreter kernels lose registers (project_kernel, image2_color_kernel and flat_grid_kernel spill; tests/
+// test_kernel_resources.py), and a per-tree kernel holds only the ops of its tree. The interpreter runs the statements as they were.
+template <int K>
+__device__ __forceinline__ bool face2_op(const float (&u)[K], const float (&v)[K]) {
+#ifdef GSDF_SPECIALIZED
+  return face2_k<K>(u, v);
+#else
+  return false;
+#endif
+}
+template <int K>
+__device__ __forceinline__ bool face3_op(const float (&u)[K], const float (&v)[K], const float (&w)[K]) {
+#ifdef GSDF_SPECIALIZED
+  return face3_k<K>(u, v, w);
+#else
+  return false;
+#endif
+}
+
 // Blend weight of the smooth combines, h = clamp(0.5 + sign * num / k, 0, 1) for the K points of a lane. Away from the
 // blend zone -- |num| >= 0.5005 k for every point of the wave -- the quotient is beyond +-0.5 whatever its rounding, so
 // the clamp yields exactly 0 or 1 and the division is skipped (wave vote); the callers' formulas run unchanged on h.
@@ -568,16 +630,24 @@ __device__ __forceinline__ void sdf_eval(code_ptr code, P3 (&pv)[K], float (&Rv)
       case D_BOX: {
         {
           const float r = PF(3);
-          float mx[K], my[K], mz[K], in[K], hyz[K], n3[K];
+          float u[K], v[K], w[K];
           KLOOP {
             const P3& p = pv[kp];
-            const float qx = (absf(p.x) - PF(0)) + r, qy = (absf(p.y) - PF(1)) + r, qz = (absf(p.z) - PF(2)) + r;
-            mx[kp] = maxf(qx, 0.f); my[kp] = maxf(qy, 0.f); mz[kp] = maxf(qz, 0.f);
-            in[kp] = minf(maxf(qx, maxf(qy, qz)), 0.0f);
+            u[kp] = (absf(p.x) - PF(0)) + r; v[kp] = (absf(p.y) - PF(1)) + r; w[kp] = (absf(p.z) - PF(2)) + r;
           }
-          hypot_k<K>(my, mz, hyz);   // ms3.Norm = hypot(x, hypot(y, z))
-          hypot_k<K>(mx, hyz, n3);
-          KLOOP Rv[kp] = n3[kp] + in[kp] - r;
+          if (face3_op<K>(u, v, w)) {  // at most one slab distance positive anywhere in the wave: face2_k
+            KLOOP Rv[kp] = face_val(maxf(u[kp], maxf(v[kp], w[kp]))) - r;
+          } else {
+            float mx[K], my[K], mz[K], in[K], hyz[K], n3[K];
+            KLOOP {
+              const float qx = u[kp], qy = v[kp], qz = w[kp];
+              mx[kp] = maxf(qx, 0.f); my[kp] = maxf(qy, 0.f); mz[kp] = maxf(qz, 0.f);
+              in[kp] = minf(maxf(qx, maxf(qy, qz)), 0.0f);
+            }
+            hypot_k<K>(my, mz, hyz);   // ms3.Norm = hypot(x, hypot(y, z))
+            hypot_k<K>(mx, hyz, n3);
+            KLOOP Rv[kp] = n3[kp] + in[kp] - r;
+          }
         }
         pc += 5;
         break;
@@ -619,14 +689,20 @@ __device__ __forceinline__ void sdf_eval(code_ptr code, P3 (&pv)[K], float (&Rv)
       case D_CYL0: {
         ENSURE_HXY();
         {
-          float ax[K], ay[K], in[K], h[K];
-          KLOOP {
-            const float dx = hxy[kp] - PF(0), dy = absf(pv[kp].z) - PF(1);
-            in[kp] = minf(0.f, maxf(dx, dy));
-            ax[kp] = maxf(0.f, dx); ay[kp] = maxf(0.f, dy);
+          float u[K], v[K];
+          KLOOP { u[kp] = hxy[kp] - PF(0); v[kp] = absf(pv[kp].z) - PF(1); }
+          if (face2_op<K>(u, v)) {  // no point of the wave beyond the rim: face2_k
+            KLOOP Rv[kp] = face_val(maxf(u[kp], v[kp]));
+          } else {
+            float ax[K], ay[K], in[K], h[K];
+            KLOOP {
+              const float dx = u[kp], dy = v[kp];
+              in[kp] = minf(0.f, maxf(dx, dy));
+              ax[kp] = maxf(0.f, dx); ay[kp] = maxf(0.f, dy);
+            }
+            hypot_k<K>(ax, ay, h);
+            KLOOP Rv[kp] = in[kp] + h[kp];
           }
-          hypot_k<K>(ax, ay, h);
-          KLOOP Rv[kp] = in[kp] + h[kp];
         }
         pc += 3;
         break;
@@ -635,23 +711,28 @@ __device__ __forceinline__ void sdf_eval(code_ptr code, P3 (&pv)[K], float (&Rv)
         ENSURE_HXY();
         {
           const float round = PF(2);
-          float ax[K], ay[K], in[K], h[K];
-          KLOOP {
-            const float dx = hxy[kp] - PF(0) + round, dy = absf(pv[kp].z) - PF(1);
-            in[kp] = minf(maxf(dx, dy), 0.f);
-            ax[kp] = maxf(dx, 0.f); ay[kp] = maxf(dy, 0.f);
+          float u[K], v[K];
+          KLOOP { u[kp] = hxy[kp] - PF(0) + round; v[kp] = absf(pv[kp].z) - PF(1); }
+          if (face2_op<K>(u, v)) {
+            KLOOP Rv[kp] = face_val(maxf(u[kp], v[kp])) - round;
+          } else {
+            float ax[K], ay[K], in[K], h[K];
+            KLOOP {
+              const float dx = u[kp], dy = v[kp];
+              in[kp] = minf(maxf(dx, dy), 0.f);
+              ax[kp] = maxf(dx, 0.f); ay[kp] = maxf(dy, 0.f);
+            }
+            hypot_k<K>(ax, ay, h);
+            KLOOP Rv[kp] = in[kp] + h[kp] - round;
           }
-          hypot_k<K>(ax, ay, h);
-          KLOOP Rv[kp] = in[kp] + h[kp] - round;
         }
         pc += 4;
         break;
       }
       case D_HEX: {
-        float hax[K], hay[K], hh[K];
+        float u[K], v[K];
         KLOOP {
           [[maybe_unused]] P3& p = pv[kp];
-          [[maybe_unused]] float& R = Rv[kp];
           const float k1 = -0.8660254037844386f, k2 = 0.5f, twok1 = -1.7320508075688772f;
           const float h1 = PF(0), h2 = PF(1), clm = PF(2);
           float px = absf(p.x), py = absf(p.y), pz = absf(p.z);
@@ -660,11 +741,21 @@ __device__ __forceinline__ void sdf_eval(code_ptr code, P3 (&pv)[K], float (&Rv)
           py -= 1.0f * pm;
           float d1 = hypotf_(px - clampf(px, -clm, clm), py - h1) * signf(py - h1);
           float d2 = pz - h2;
-          hax[kp] = maxf(d1, 0.f); hay[kp] = maxf(d2, 0.f);
-          R = minf(maxf(d1, d2), 0.f);
+          u[kp] = d1; v[kp] = d2;
         }
-        hypot_k<K>(hax, hay, hh);
-        KLOOP Rv[kp] = Rv[kp] + hh[kp];
+        if (face2_op<K>(u, v)) {
+          KLOOP Rv[kp] = face_val(maxf(u[kp], v[kp]));
+        } else {
+          float hax[K], hay[K], hh[K];
+          KLOOP {
+            [[maybe_unused]] float& R = Rv[kp];
+            const float d1 = u[kp], d2 = v[kp];
+            hax[kp] = maxf(d1, 0.f); hay[kp] = maxf(d2, 0.f);
+            R = minf(maxf(d1, d2), 0.f);
+          }
+          hypot_k<K>(hax, hay, hh);
+          KLOOP Rv[kp] = Rv[kp] + hh[kp];
+        }
         pc += 4;
         break;
       }
@@ -771,16 +862,24 @@ __device__ __forceinline__ void sdf_eval(code_ptr code, P3 (&pv)[K], float (&Rv)
         break;
       }
       case D_RECT2D: {
-        float rax[K], ray[K], rh[K];
+        float u[K], v[K];
         KLOOP {
           [[maybe_unused]] P3& p = pv[kp];
-          [[maybe_unused]] float& R = Rv[kp];
-          float dx = absf(p.x) - PF(0), dy = absf(p.y) - PF(1);
-          rax[kp] = maxf(dx, 0.f); ray[kp] = maxf(dy, 0.f);
-          R = minf(0.f, maxf(dx, dy));
+          u[kp] = absf(p.x) - PF(0); v[kp] = absf(p.y) - PF(1);
         }
-        hypot_k<K>(rax, ray, rh);
-        KLOOP Rv[kp] = rh[kp] + Rv[kp];
+        if (face2_op<K>(u, v)) {
+          KLOOP Rv[kp] = face_val(maxf(u[kp], v[kp]));
+        } else {
+          float rax[K], ray[K], rh[K];
+          KLOOP {
+            [[maybe_unused]] float& R = Rv[kp];
+            float dx = u[kp], dy = v[kp];
+            rax[kp] = maxf(dx, 0.f); ray[kp] = maxf(dy, 0.f);
+            R = minf(0.f, maxf(dx, dy));
+          }
+          hypot_k<K>(rax, ray, rh);
+          KLOOP Rv[kp] = rh[kp] + Rv[kp];
+        }
         pc += 3;
         break;
       }
@@ -1238,16 +1337,21 @@ __device__ __forceinline__ void sdf_eval(code_ptr code, P3 (&pv)[K], float (&Rv)
         break;
       }
       case D_EXTRUDE_POST: {
-        float eax[K], eay[K], eh[K];
-        KLOOP {
-          [[maybe_unused]] P3& p = pv[kp];
-          [[maybe_unused]] float& R = Rv[kp];
-          float wy = LDSF(slot);
-          eax[kp] = maxf(R, 0.f); eay[kp] = maxf(wy, 0.f);
-          R = minf(0.f, maxf(R, wy));
+        float v[K];
+        KLOOP v[kp] = LDSF(slot);
+        if (face2_op<K>(Rv, v)) {
+          KLOOP Rv[kp] = face_val(maxf(Rv[kp], v[kp]));
+        } else {
+          float eax[K], eay[K], eh[K];
+          KLOOP {
+            [[maybe_unused]] float& R = Rv[kp];
+            float wy = v[kp];
+            eax[kp] = maxf(R, 0.f); eay[kp] = maxf(wy, 0.f);
+            R = minf(0.f, maxf(R, wy));
+          }
+          hypot_k<K>(eax, eay, eh);
+          KLOOP Rv[kp] = Rv[kp] + eh[kp];
         }
-        hypot_k<K>(eax, eay, eh);
-        KLOOP Rv[kp] = Rv[kp] + eh[kp];
         pc += 1;
         break;
       }

@@ -235,6 +235,9 @@ __global__ void __launch_bounds__(BLOCK) div_selftest_kernel(float d, float r, u
 // these to the reference. fn 0..12 as orc_math_apply numbers them (x, y are its operands: fn 1 is atan2(y = x[i], x = y[i])); then
 // 13 / 14 cossinf_'s cosine / sine, 15 atan2f_ (short route, long route where it declines), 16 sqrtf_, 17 x[i] / d through
 // div_uniform_k<1> with the wave-uniform divisor d and r = RN(1/d) from the host (0: not eligible), as the interpreter calls it.
+// 18..21 the "inside + outside" distance of two slab distances (x, y) and of three (x, y and the wave-uniform d), interp.h: face2_k --
+// 18 / 20 as the ops run it (the face form where the wave's vote passes, else the legacy statements), 19 / 21 the legacy statements
+// always (min + hypot_k chain, D_CYL0's and D_BOX's operand order): each pair must agree bit for bit on any input.
 __global__ void __launch_bounds__(BLOCK) math_selftest_kernel(int fn, const float* __restrict__ x, const float* __restrict__ y,
                                                               float* __restrict__ out, uint64_t n, float d, float r) {
   const uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
@@ -265,6 +268,29 @@ __global__ void __launch_bounds__(BLOCK) math_selftest_kernel(int fn, const floa
       float q[1];
       dm::div_uniform_k<1>(nn, d, r, q);
       o = q[0];
+      break;
+    }
+    case 18: case 19: case 20: case 21: {
+      // (the idle lanes run on -1: inside every slab, they leave the vote to the wave's values)
+      const float u[1] = {valid ? a : -1.0f}, v[1] = {valid ? b : -1.0f}, w[1] = {d};
+      const bool three = fn >= 20;
+      const bool face = fn == 18 ? gsdf_dev::face2_k<1>(u, v) : (fn == 20 ? gsdf_dev::face3_k<1>(u, v, w) : false);
+      if (face) {
+        o = gsdf_dev::face_val(three ? dm::maxf(u[0], dm::maxf(v[0], w[0])) : dm::maxf(u[0], v[0]));
+      } else if (three) {  // D_BOX's statements
+        const float mx[1] = {dm::maxf(u[0], 0.f)}, my[1] = {dm::maxf(v[0], 0.f)}, mz[1] = {dm::maxf(w[0], 0.f)};
+        const float in = dm::minf(dm::maxf(u[0], dm::maxf(v[0], w[0])), 0.0f);
+        float hyz[1], n3[1];
+        gsdf_dev::hypot_k<1>(my, mz, hyz);
+        gsdf_dev::hypot_k<1>(mx, hyz, n3);
+        o = n3[0] + in;
+      } else {  // D_CYL0's statements
+        const float in = dm::minf(0.f, dm::maxf(u[0], v[0]));
+        const float ax[1] = {dm::maxf(0.f, u[0])}, ay[1] = {dm::maxf(0.f, v[0])};
+        float h[1];
+        gsdf_dev::hypot_k<1>(ax, ay, h);
+        o = in + h[0];
+      }
       break;
     }
     default: o = __builtin_nanf(""); break;

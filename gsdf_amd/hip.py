@@ -411,7 +411,8 @@ def color_default():
 
 # gsdf_hip_selftest_math's numbering: 0..12 as oracle/orc_math_export.c, then the evaluator's other routes
 MATH_FN = {"hypot": 0, "atan2_ref": 1, "sin": 2, "cos": 3, "acos": 4, "cbrt": 5, "sincos_s": 6, "sincos_c": 7, "min": 8, "max": 9,
-           "pow13": 10, "round": 11, "floor": 12, "cossin_c": 13, "cossin_s": 14, "atan2": 15, "sqrt": 16, "div": 17}
+           "pow13": 10, "round": 11, "floor": 12, "cossin_c": 13, "cossin_s": 14, "atan2": 15, "sqrt": 16, "div": 17,
+           "face2": 18, "face2_legacy": 19, "face3": 20, "face3_legacy": 21}
 
 
 def math_apply(name, x, y=None, divisor=1.0):

@@ -120,7 +120,10 @@ int gsdf_hip_selftest_cossin(uint64_t* mismatches, uint64_t* fast_path_arguments
  * host values, one per lane, for a comparison with a reference on the host. fn: 0 hypot(x, y), 1 atan2(y = x[i], x = y[i]) by the
  * reference's float64 sequence, 2 sin, 3 cos, 4 acos, 5 cbrt, 6 / 7 Sincos' sine / cosine, 8 min, 9 max, 10 pow(x, 1/3), 11 round,
  * 12 floor, 13 / 14 the twist's cosine / sine, 15 atan2 as the evaluator calls it (short route where it decides), 16 sqrt,
- * 17 x[i] / divisor by the exact-reciprocal division where the divisor is eligible. y may be null for one-operand functions. */
+ * 17 x[i] / divisor by the exact-reciprocal division where the divisor is eligible, 18 min(0, max(x, y)) + hypot(max(x, 0),
+ * max(y, 0)) as the box-like primitives run it (max(x, y) + 0 where every wave of 64 consecutive values has x <= 0 or y <= 0 throughout,
+ * else term by term), 19 the same term by term always, 20 / 21 likewise for three terms, the third being divisor. Each pair agrees
+ * bit for bit. y may be null for one-operand functions. */
 int gsdf_hip_selftest_math(int fn, const float* x, const float* y, float* out, uint64_t n, float divisor);
 /* Run-time specialisation (no reference counterpart; the reference's GPU path compiles GLSL per tree at
  * gleval/gpu.go:35-54, this is the same step for the HIP backend): builds, with hiprtc, eval / prune / leaf kernels in
