@@ -1,7 +1,8 @@
-// abi_eval.hip -- C ABI (include/gsdf_hip.h), evaluator side: program handles (their per-tree kernels: abi_spec.hip), the
-// gleval.SDF3 / SDF2 Evaluate drop-ins (host buffers, pipelined tickets, registered memory, device-resident), central-difference
-// normals, the 2-D image renderer and its colour conversions, the UI's view of a 3-D part, the block cache. Kernels: kernels_eval.h,
-// kernels_image.h, kernels_view.h, kernels_project.h and kernels_ray.h over the interpreter of interp.h.
+// abi_eval.hip -- C ABI (include/gsdf_hip.h), evaluator side, what launches kernels: program handles (their per-tree kernels:
+// abi_spec.hip), the self-test hooks, the gleval.SDF3 / SDF2 Evaluate drop-ins (host buffers, pipelined tickets, registered memory,
+// device-resident), central-difference normals, projection, rays, the 2-D image and picture renderers, the UI's view of a 3-D part.
+// Kernels: kernels_eval.h, kernels_image.h, kernels_view.h, kernels_project.h and kernels_ray.h over the interpreter of interp.h.
+// The entry points of this side that need no GPU (camera, colour conversions, block cache): abi_evalhost.cpp.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -10,7 +11,6 @@
 #include <cstring>
 #include <new>
 #include <thread>
-#include <unordered_map>
 
 #include "kernels_common.h"
 #include "kernels_eval.h"
@@ -61,6 +61,21 @@ extern "C" int gsdf_hip_program_create(const gsdf_tree* tree, gsdf_program** out
   return GSDF_OK;
 }
 
+// What the exhaustive self-test hooks below share: a zeroed block of two counters on the device, `launch(counters)` on the null
+// stream, the two words back in *out0 and *out1 (either may be null; written on success only).
+template <typename Launch>
+static int selftest_run(uint64_t* out0, uint64_t* out1, Launch&& launch) {
+  DevBuf d_c;
+  HIP_TRY(d_c.alloc(16));
+  if (hipMemset(d_c.p, 0, 16) != hipSuccess) return fail(GSDF_ERR_HIP, "memset failed");
+  launch((unsigned long long*)d_c.p);
+  unsigned long long h[2] = {0, 0};
+  if (hipMemcpy(h, d_c.p, 16, hipMemcpyDeviceToHost) != hipSuccess) return fail(GSDF_ERR_HIP, "selftest kernel failed");
+  if (out0) *out0 = h[0];
+  if (out1) *out1 = h[1];
+  return GSDF_OK;
+}
+
 // Test hook: runs dm::div_by_uniform(n, d, RN(1/d)) for all 2^32 numerators n on the GPU and counts results that
 // differ from n / d among the numerators the interpreter would send down the fast path.
 extern "C" int gsdf_hip_selftest_div(float d, uint64_t* mismatches, uint64_t* fast_path_numerators, float* recip) {
@@ -69,19 +84,7 @@ extern "C" int gsdf_hip_selftest_div(float d, uint64_t* mismatches, uint64_t* fa
   if (mismatches) *mismatches = 0;
   if (fast_path_numerators) *fast_path_numerators = 0;
   if (r == 0.f) return GSDF_OK;  // divisor not eligible: the device always uses the IEEE expansion
-  unsigned long long* d_c = nullptr;
-  HIP_TRY(hipMalloc((void**)&d_c, 16));
-  int rc = GSDF_OK;
-  do {
-    if (hipMemset(d_c, 0, 16) != hipSuccess) { rc = fail(GSDF_ERR_HIP, "memset failed"); break; }
-    hipLaunchKernelGGL(div_selftest_kernel, dim3(4096), dim3(BLOCK), 0, nullptr, d, r, d_c, d_c + 1);
-    unsigned long long h[2] = {0, 0};
-    if (hipMemcpy(h, d_c, 16, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(GSDF_ERR_HIP, "selftest kernel failed"); break; }
-    if (mismatches) *mismatches = h[0];
-    if (fast_path_numerators) *fast_path_numerators = h[1];
-  } while (0);
-  (void)hipFree(d_c);
-  return rc;
+  return selftest_run(mismatches, fast_path_numerators, [&](unsigned long long* c) { hipLaunchKernelGGL(div_selftest_kernel, dim3(4096), dim3(BLOCK), 0, nullptr, d, r, c, c + 1); });
 }
 
 // Test hook: dm::circ_sector_fast (the circular array's sector index without the angle) against the reference's
@@ -92,19 +95,7 @@ extern "C" int gsdf_hip_selftest_circ(float ncirc, uint64_t* mismatches, uint64_
   if (fast_path_points) *fast_path_points = 0;
   if (!(ncirc >= 1.f)) return fail(GSDF_ERR_BAD_ARGUMENT, "ncirc must be >= 1");
   const float angle = 6.2831853071795862f / ncirc;
-  unsigned long long* d_c = nullptr;
-  HIP_TRY(hipMalloc((void**)&d_c, 16));
-  int rc = GSDF_OK;
-  do {
-    if (hipMemset(d_c, 0, 16) != hipSuccess) { rc = fail(GSDF_ERR_HIP, "memset failed"); break; }
-    hipLaunchKernelGGL(circ_selftest_kernel, dim3(4096), dim3(BLOCK), 0, nullptr, angle, d_c, d_c + 1);
-    unsigned long long h[2] = {0, 0};
-    if (hipMemcpy(h, d_c, 16, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(GSDF_ERR_HIP, "selftest kernel failed"); break; }
-    if (mismatches) *mismatches = h[0];
-    if (fast_path_points) *fast_path_points = h[1];
-  } while (0);
-  (void)hipFree(d_c);
-  return rc;
+  return selftest_run(mismatches, fast_path_points, [&](unsigned long long* c) { hipLaunchKernelGGL(circ_selftest_kernel, dim3(4096), dim3(BLOCK), 0, nullptr, angle, c, c + 1); });
 }
 
 // Test hook: dm::atan2_fast (float32 of math.Atan2 without the reference's float64 operation sequence, accepted only where the
@@ -113,19 +104,7 @@ extern "C" int gsdf_hip_selftest_atan2(int mode, int log2n, uint64_t* mismatches
   if (mismatches) *mismatches = 0;
   if (fast_path_points) *fast_path_points = 0;
   if (mode < 0 || mode > 2 || log2n < 0 || log2n > 40) return fail(GSDF_ERR_BAD_ARGUMENT, "mode in 0..2, log2n in 0..40");
-  unsigned long long* d_c = nullptr;
-  HIP_TRY(hipMalloc((void**)&d_c, 16));
-  int rc = GSDF_OK;
-  do {
-    if (hipMemset(d_c, 0, 16) != hipSuccess) { rc = fail(GSDF_ERR_HIP, "memset failed"); break; }
-    hipLaunchKernelGGL(atan2_selftest_kernel, dim3(4096), dim3(BLOCK), 0, nullptr, mode, log2n, d_c, d_c + 1);
-    unsigned long long h[2] = {0, 0};
-    if (hipMemcpy(h, d_c, 16, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(GSDF_ERR_HIP, "selftest kernel failed"); break; }
-    if (mismatches) *mismatches = h[0];
-    if (fast_path_points) *fast_path_points = h[1];
-  } while (0);
-  (void)hipFree(d_c);
-  return rc;
+  return selftest_run(mismatches, fast_path_points, [&](unsigned long long* c) { hipLaunchKernelGGL(atan2_selftest_kernel, dim3(4096), dim3(BLOCK), 0, nullptr, mode, log2n, c, c + 1); });
 }
 
 // Test hook: dm::cossin_fast (float32 of math.Cos / math.Sin by FMAs, accepted only where the rounding is decided) against dm::cossinf_,
@@ -133,35 +112,13 @@ extern "C" int gsdf_hip_selftest_atan2(int mode, int log2n, uint64_t* mismatches
 extern "C" int gsdf_hip_selftest_cossin(uint64_t* mismatches, uint64_t* fast_path_arguments) {
   if (mismatches) *mismatches = 0;
   if (fast_path_arguments) *fast_path_arguments = 0;
-  unsigned long long* d_c = nullptr;
-  HIP_TRY(hipMalloc((void**)&d_c, 16));
-  int rc = GSDF_OK;
-  do {
-    if (hipMemset(d_c, 0, 16) != hipSuccess) { rc = fail(GSDF_ERR_HIP, "memset failed"); break; }
-    hipLaunchKernelGGL(cossin_selftest_kernel, dim3(4096), dim3(BLOCK), 0, nullptr, d_c, d_c + 1);
-    unsigned long long h[2] = {0, 0};
-    if (hipMemcpy(h, d_c, 16, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(GSDF_ERR_HIP, "selftest kernel failed"); break; }
-    if (mismatches) *mismatches = h[0];
-    if (fast_path_arguments) *fast_path_arguments = h[1];
-  } while (0);
-  (void)hipFree(d_c);
-  return rc;
+  return selftest_run(mismatches, fast_path_arguments, [&](unsigned long long* c) { hipLaunchKernelGGL(cossin_selftest_kernel, dim3(4096), dim3(BLOCK), 0, nullptr, c, c + 1); });
 }
 
 // Test hook: dm::sqrt_1to2 against sqrtf for all 8,388,609 floats in [1, 2]; dm::sqrt_core against sqrtf for every float >= 2^-96.
 extern "C" int gsdf_hip_selftest_sqrt(uint64_t* mismatches) {
-  unsigned long long* d_c = nullptr;
-  HIP_TRY(hipMalloc((void**)&d_c, 8));
-  int rc = GSDF_OK;
-  unsigned long long h = 0;
-  if (hipMemset(d_c, 0, 8) != hipSuccess) rc = fail(GSDF_ERR_HIP, "memset failed");
-  if (!rc) {
-    hipLaunchKernelGGL(sqrt_selftest_kernel, dim3(1024), dim3(BLOCK), 0, nullptr, d_c);
-    if (hipMemcpy(&h, d_c, 8, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(GSDF_ERR_HIP, "selftest kernel failed");
-  }
-  (void)hipFree(d_c);
-  if (mismatches) *mismatches = h;
-  return rc;
+  if (mismatches) *mismatches = 0;
+  return selftest_run(mismatches, nullptr, [&](unsigned long long* c) { hipLaunchKernelGGL(sqrt_selftest_kernel, dim3(1024), dim3(BLOCK), 0, nullptr, c); });
 }
 
 // Test hook: one of the device's math routes over n host values (kernels_eval.h: math_selftest_kernel), for a comparison with the
@@ -174,48 +131,17 @@ extern "C" int gsdf_hip_selftest_math(int fn, const float* x, const float* y, fl
   if (n > (1ull << 28)) return fail(GSDF_ERR_BAD_ARGUMENT, "n <= 2^28");
   const bool two = fn == 0 || fn == 1 || fn == 8 || fn == 9 || fn == 15 || fn >= 18;
   if (two && !y) return fail(GSDF_ERR_BAD_ARGUMENT, "this function takes two operands");
-  float* d_b = nullptr;
   const size_t bytes = (size_t)n * sizeof(float);
-  HIP_TRY(hipMalloc((void**)&d_b, 3 * bytes));
-  int rc = GSDF_OK;
-  do {
-    if (hipMemcpy(d_b, x, bytes, hipMemcpyHostToDevice) != hipSuccess) { rc = fail(GSDF_ERR_HIP, "copy failed"); break; }
-    if (two && hipMemcpy(d_b + n, y, bytes, hipMemcpyHostToDevice) != hipSuccess) { rc = fail(GSDF_ERR_HIP, "copy failed"); break; }
-    const float r = fn == 17 ? gsdf_dev::recip_for(divisor) : 0.f;
-    hipLaunchKernelGGL(math_selftest_kernel, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, nullptr, fn, d_b, two ? d_b + n : nullptr,
-                       d_b + 2 * n, n, divisor, r);
-    if (hipMemcpy(out, d_b + 2 * n, bytes, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(GSDF_ERR_HIP, "selftest kernel failed"); break; }
-  } while (0);
-  (void)hipFree(d_b);
-  return rc;
-}
-
-// Host-only (no GPU): lower a tree to the device instruction stream, for inspection/tests.
-extern "C" int gsdf_hip_lower(const gsdf_tree* tree, uint32_t* code_out, uint32_t code_cap, uint32_t* code_words, uint32_t* lds_slots) {
-  if (!tree) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
-  try {
-    gsdf_dev::Program pr = gsdf_dev::compile(*tree);
-    if (code_words) *code_words = (uint32_t)pr.code.size();
-    if (lds_slots) *lds_slots = (uint32_t)pr.nslots;
-    if (code_out) {
-      if (code_cap < pr.code.size()) return fail(GSDF_ERR_SHORT_BUFFER, "short buffer");
-      std::memcpy(code_out, pr.code.data(), pr.code.size() * sizeof(uint32_t));
-    }
-    return GSDF_OK;
-  } catch (const std::exception& e) {
-    return fail(GSDF_ERR_BAD_TREE, e.what());
-  }
-}
-
-// Host-only test hook: the lower-bound region the compiler claims for the subtree of `node` (0 none, 1 box, 2 z-cylinder).
-extern "C" int gsdf_hip_lower_region(const gsdf_tree* tree, uint32_t node, int* kind, float params[8]) {
-  if (!tree || !kind || !params) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
-  try {
-    *kind = gsdf_dev::region_of(*tree, node, params);
-    return GSDF_OK;
-  } catch (const std::exception& e) {
-    return fail(GSDF_ERR_BAD_TREE, e.what());
-  }
+  DevBuf buf;
+  HIP_TRY(buf.alloc(3 * bytes));
+  float* d_b = (float*)buf.p;
+  if (hipMemcpy(d_b, x, bytes, hipMemcpyHostToDevice) != hipSuccess) return fail(GSDF_ERR_HIP, "copy failed");
+  if (two && hipMemcpy(d_b + n, y, bytes, hipMemcpyHostToDevice) != hipSuccess) return fail(GSDF_ERR_HIP, "copy failed");
+  const float r = fn == 17 ? gsdf_dev::recip_for(divisor) : 0.f;
+  hipLaunchKernelGGL(math_selftest_kernel, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, nullptr, fn, d_b, two ? d_b + n : nullptr,
+                     d_b + 2 * n, n, divisor, r);
+  if (hipMemcpy(out, d_b + 2 * n, bytes, hipMemcpyDeviceToHost) != hipSuccess) return fail(GSDF_ERR_HIP, "selftest kernel failed");
+  return GSDF_OK;
 }
 
 extern "C" void gsdf_hip_program_destroy(gsdf_program* p) { delete p; }  // (~gsdf_program, abi_program.h)
@@ -324,6 +250,19 @@ extern "C" int gsdf_hip_host_release(void* ptr) {  // gsdf_hip_host_alloc'ed: fr
 
 static constexpr size_t kSmallPos = (size_t)1 << 20, kSmallDist = (size_t)1 << 18;
 
+// What every Evaluate drop-in refuses: a program of the other dimension; for the host-buffer forms, gleval's argument errors first.
+static int eval_dim_refused(const gsdf_program* p, int dim) {
+  if (p->prog.is2d != (dim == 2)) return fail(GSDF_ERR_DIMENSION, dim == 2 ? "program is 3D, eval2 called" : "program is 2D, eval3 called");
+  return GSDF_OK;
+}
+static int eval_args_refused(const gsdf_program* p, int dim, const void* pos, const float* dist, size_t n_pos, size_t n_dist) {
+  if (!p) return fail(GSDF_ERR_BAD_ARGUMENT, "null program");
+  if (n_pos != n_dist) return fail(GSDF_ERR_LENGTH_MISMATCH, "position and distance buffer length mismatch");
+  if (n_pos == 0) return fail(GSDF_ERR_EMPTY_BUFFERS, "empty buffers");
+  if (!pos || !dist) return fail(GSDF_ERR_BAD_ARGUMENT, "null buffer");
+  return eval_dim_refused(p, dim);
+}
+
 static int slot_acquire(gsdf_program* p, int* idx) {
   std::unique_lock<std::mutex> lk(p->slot_mu);
   for (;;) {
@@ -342,11 +281,7 @@ static void slot_release(gsdf_program* p, int idx) {
 // distances to -- pinned, device-mapped host memory across PCIe itself: the caller's own buffers when they are registered
 // (zero copy), else the slot's staging buffers (one memcpy in, one out).
 static int eval_submit(gsdf_program* p, int dim, const void* pos, size_t stride, size_t n_pos, float* dist, size_t n_dist, int* ticket) {
-  if (!p) return fail(GSDF_ERR_BAD_ARGUMENT, "null program");
-  if (n_pos != n_dist) return fail(GSDF_ERR_LENGTH_MISMATCH, "position and distance buffer length mismatch");
-  if (n_pos == 0) return fail(GSDF_ERR_EMPTY_BUFFERS, "empty buffers");
-  if (!pos || !dist) return fail(GSDF_ERR_BAD_ARGUMENT, "null buffer");
-  if (p->prog.is2d != (dim == 2)) return fail(GSDF_ERR_DIMENSION, dim == 2 ? "program is 3D, eval2 called" : "program is 2D, eval3 called");
+  if (int rc = eval_args_refused(p, dim, pos, dist, n_pos, n_dist)) return rc;
   HIP_TRY(hipSetDevice(p->device));
   const size_t pbytes = n_pos * stride;
   int si = -1;
@@ -421,18 +356,14 @@ static int eval_wait(gsdf_program* p, int tk) {
 }
 
 static int eval_host(gsdf_program* p, int dim, const void* pos, size_t stride, size_t n_pos, float* dist, size_t n_dist) {
-  if (!p) return fail(GSDF_ERR_BAD_ARGUMENT, "null program");
   const size_t pbytes = n_pos * stride;
   const bool small = pbytes <= kSmallPos && n_pos <= kSmallDist;
   if (small || (pos && dist && n_pos == n_dist && n_pos && reg_device_ptr(pos, pbytes) && reg_device_ptr(dist, n_pos * sizeof(float)))) {
     int t = -1;
     const int rc = eval_submit(p, dim, pos, stride, n_pos, dist, n_dist, &t);
-    return rc ? rc : eval_wait(p, t);
+    return rc ? rc : eval_wait(p, t);  // (eval_submit checks the arguments, a null program first)
   }
-  if (n_pos != n_dist) return fail(GSDF_ERR_LENGTH_MISMATCH, "position and distance buffer length mismatch");
-  if (n_pos == 0) return fail(GSDF_ERR_EMPTY_BUFFERS, "empty buffers");
-  if (!pos || !dist) return fail(GSDF_ERR_BAD_ARGUMENT, "null buffer");
-  if (p->prog.is2d != (dim == 2)) return fail(GSDF_ERR_DIMENSION, dim == 2 ? "program is 3D, eval2 called" : "program is 2D, eval3 called");
+  if (int rc = eval_args_refused(p, dim, pos, dist, n_pos, n_dist)) return rc;
   HIP_TRY(hipSetDevice(p->device));
   // large calls: DMA in, kernel, DMA out on the program's stream (one caller at a time, as before)
   static std::mutex big_mu;
@@ -477,68 +408,84 @@ extern "C" int gsdf_hip_eval3(gsdf_program* p, const void* pos, size_t stride, s
 extern "C" int gsdf_hip_eval2(gsdf_program* p, const void* pos, size_t stride, size_t n_pos, float* dist, size_t n_dist) {
   return eval_host(p, 2, pos, stride, n_pos, dist, n_dist);
 }
-extern "C" int gsdf_hip_eval3_dev(gsdf_program* p, const void* d_pos, size_t stride, float* d_dist, size_t n, void* stream) {
+static int eval_dev_entry(gsdf_program* p, int dim, const void* d_pos, size_t stride, float* d_dist, size_t n, void* stream) {
   if (!p || !d_pos || !d_dist) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
   if (n == 0) return fail(GSDF_ERR_EMPTY_BUFFERS, "empty buffers");
-  if (p->prog.is2d) return fail(GSDF_ERR_DIMENSION, "program is 2D, eval3 called");
-  return eval_dev(p, 3, d_pos, stride, d_dist, n, stream ? (hipStream_t)stream : p->stream.s);
+  if (int rc = eval_dim_refused(p, dim)) return rc;
+  return eval_dev(p, dim, d_pos, stride, d_dist, n, stream ? (hipStream_t)stream : p->stream.s);
+}
+extern "C" int gsdf_hip_eval3_dev(gsdf_program* p, const void* d_pos, size_t stride, float* d_dist, size_t n, void* stream) {
+  return eval_dev_entry(p, 3, d_pos, stride, d_dist, n, stream);
 }
 extern "C" int gsdf_hip_eval2_dev(gsdf_program* p, const void* d_pos, size_t stride, float* d_dist, size_t n, void* stream) {
-  if (!p || !d_pos || !d_dist) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
-  if (n == 0) return fail(GSDF_ERR_EMPTY_BUFFERS, "empty buffers");
-  if (!p->prog.is2d) return fail(GSDF_ERR_DIMENSION, "program is 3D, eval2 called");
-  return eval_dev(p, 2, d_pos, stride, d_dist, n, stream ? (hipStream_t)stream : p->stream.s);
+  return eval_dev_entry(p, 2, d_pos, stride, d_dist, n, stream);
 }
 
-extern "C" int gsdf_hip_normals3(gsdf_program* p, const float* pos, float* normals, size_t n, float step) {
-  if (!p || !pos || !normals) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+// gleval.NormalsCentralDiff on device-resident points, enqueued on the handle's stream: the checks (`what` names the caller in the
+// text of a tree too large for two points per lane) and normals_kernel over the interpreter or the handle's build of it. The
+// callers synchronise and count the 6 n evaluations.
+static int normals_enqueue(gsdf_program* p, const float* d_pos, float* d_nrm, size_t n, float step, const char* what) {
   step *= 0.5f;
   if (!(step > 0)) return fail(GSDF_ERR_BAD_ARGUMENT, "invalid step");
   if (n == 0) return fail(GSDF_ERR_EMPTY_BUFFERS, "empty buffers");
   if (p->prog.is2d) return fail(GSDF_ERR_DIMENSION, "program is 2D");
-  if (int rc = p->normals_refused("gsdf_hip_normals3")) return rc;
+  if (int rc = p->normals_refused(what)) return rc;
   HIP_TRY(hipSetDevice(p->device));
   spec_adopt(p);  // (a background build that has finished: its kernels from here on)
-  float *d_p = nullptr, *d_n = nullptr;
-  HIP_TRY(hipMalloc((void**)&d_p, n * 12));
-  if (hipMalloc((void**)&d_n, n * 12) != hipSuccess) { (void)hipFree(d_p); return fail(GSDF_ERR_HIP, "hipMalloc failed"); }
-  int rc = GSDF_OK;
-  do {
-    if (hipMemcpyAsync(d_p, pos, n * 12, hipMemcpyHostToDevice, p->stream.s) != hipSuccess) { rc = fail(GSDF_ERR_HIP, "H2D copy failed"); break; }
-    spec_ensure(p, SPEC_AUX);
-    if (launch_kernel(normals_kernel, p->spec.f_normals, grid_for(n, p->num_cu, 8), BLOCK, p->lds_bytes(2), p->stream.s, p->d_code.p, d_p, d_n, n, step) != hipSuccess) {
-      rc = fail(GSDF_ERR_HIP, "normals kernel launch failed");
-      break;
-    }
-    if (hipMemcpyAsync(normals, d_n, n * 12, hipMemcpyDeviceToHost, p->stream.s) != hipSuccess) { rc = fail(GSDF_ERR_HIP, "D2H copy failed"); break; }
-    if (hipStreamSynchronize(p->stream.s) != hipSuccess) { rc = fail(GSDF_ERR_HIP, "stream sync failed"); break; }
-    p->evals += 6 * n;
-  } while (0);
-  (void)hipFree(d_p);
-  (void)hipFree(d_n);
-  return rc;
+  spec_ensure(p, SPEC_AUX);
+  if (launch_kernel(normals_kernel, p->spec.f_normals, grid_for(n, p->num_cu, 8), BLOCK, p->lds_bytes(2), p->stream.s, p->d_code.p, d_pos, d_nrm, n, step) != hipSuccess)
+    return fail(GSDF_ERR_HIP, "normals kernel launch failed");
+  return GSDF_OK;
+}
+
+// Host buffers, blocking. (The points go to the device ahead of the checks: a refused call has paid for the copy, no more.)
+extern "C" int gsdf_hip_normals3(gsdf_program* p, const float* pos, float* normals, size_t n, float step) {
+  if (!p || !pos || !normals) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  HIP_TRY(hipSetDevice(p->device));
+  DevBuf d_p, d_n;
+  HIP_TRY(d_p.alloc(n * 12));
+  HIP_TRY(d_n.alloc(n * 12));
+  if (hipMemcpyAsync(d_p.p, pos, n * 12, hipMemcpyHostToDevice, p->stream.s) != hipSuccess) return fail(GSDF_ERR_HIP, "H2D copy failed");
+  if (int rc = normals_enqueue(p, (const float*)d_p.p, (float*)d_n.p, n, step, "gsdf_hip_normals3")) return rc;
+  if (hipMemcpyAsync(normals, d_n.p, n * 12, hipMemcpyDeviceToHost, p->stream.s) != hipSuccess) return fail(GSDF_ERR_HIP, "D2H copy failed");
+  if (hipStreamSynchronize(p->stream.s) != hipSuccess) return fail(GSDF_ERR_HIP, "stream sync failed");
+  p->evals += 6 * n;
+  return GSDF_OK;
 }
 
 // The same on device-resident points (gsdf_hip_indexed_normals: the welded vertices of a mesh): d_pos, d_nrm 12-byte xyz on the
 // program's device; blocking. The launch is gsdf_hip_normals3's, so the values are.
 int normals3_dev(gsdf_program* p, const float* d_pos, float* d_nrm, size_t n, float step) {
-  step *= 0.5f;
-  if (!(step > 0)) return fail(GSDF_ERR_BAD_ARGUMENT, "invalid step");
-  if (n == 0) return fail(GSDF_ERR_EMPTY_BUFFERS, "empty buffers");
-  if (p->prog.is2d) return fail(GSDF_ERR_DIMENSION, "program is 2D");
-  if (int rc = p->normals_refused("the normals of an indexed mesh")) return rc;
-  HIP_TRY(hipSetDevice(p->device));
-  spec_adopt(p);
-  spec_ensure(p, SPEC_AUX);
-  HIP_TRY(launch_kernel(normals_kernel, p->spec.f_normals, grid_for(n, p->num_cu, 8), BLOCK, p->lds_bytes(2), p->stream.s, p->d_code.p, d_pos, d_nrm, n, step));
+  if (int rc = normals_enqueue(p, d_pos, d_nrm, n, step, "the normals of an indexed mesh")) return rc;
   HIP_TRY(hipStreamSynchronize(p->stream.s));
   p->evals += 6 * n;
   return GSDF_OK;
 }
 
+// One kernel with counters on the handle's stream, blocking: `cl`'s counter block (C, made at the handle's first launch of the kind,
+// as are the two events) is cleared in front of `launch(counters)` and copied to *hc behind it; the stream is synchronised whatever
+// failed; *ms is the device time between the two events; the handle counts hc->evals. `what` goes in front of an error's text.
+// One such call per program at a time, like every call on the handle's stream.
+template <typename C, typename Launch>
+static int counted_launch(gsdf_program* p, gsdf_program::CountedLaunch& cl, const char* what, C* hc, float* ms, Launch&& launch) {
+  if (!cl.ctr.p) HIP_TRY(hipMalloc(&cl.ctr.p, sizeof(C)));
+  HIP_TRY(cl.ev.ensure());
+  C* d_ctr = (C*)cl.ctr.p;
+  hipError_t e = hipMemsetAsync(d_ctr, 0, sizeof(C), p->stream.s);
+  if (e == hipSuccess) e = hipEventRecord(cl.ev[0], p->stream.s);
+  if (e == hipSuccess) e = launch(d_ctr);
+  if (e == hipSuccess) e = hipEventRecord(cl.ev[1], p->stream.s);
+  if (e == hipSuccess) e = hipMemcpyAsync(hc, d_ctr, sizeof(C), hipMemcpyDeviceToHost, p->stream.s);
+  if (e == hipSuccess) e = hipStreamSynchronize(p->stream.s);
+  else (void)hipStreamSynchronize(p->stream.s);
+  if (e == hipSuccess) e = hipEventElapsedTime(ms, cl.ev[0], cl.ev[1]);
+  if (e != hipSuccess) return fail(GSDF_ERR_HIP, std::string(what) + hipGetErrorString(e));
+  p->evals += hc->evals;
+  return GSDF_OK;
+}
+
 // gsdf_hip_indexed_project's kernel on device-resident points (abi_program.h): project_kernel over the interpreter, or the handle's
-// specialised build of it. One launch: the counters (the handle's, made at its first projection, as are the two events) are cleared on
-// the stream in front of it and read behind it. One projection per program at a time, like every call on the handle's stream.
+// specialised build of it, as one counted launch.
 int project_dev(gsdf_program* p, const float* d_pos, size_t n, const gsdf_project_opts* o, float* d_out_pos, float* d_before, float* d_after,
                 uint8_t* d_status, gsdf_project_stats* st) {
   if (n == 0) return fail(GSDF_ERR_EMPTY_BUFFERS, "empty buffers");
@@ -548,26 +495,16 @@ int project_dev(gsdf_program* p, const float* d_pos, size_t n, const gsdf_projec
   HIP_TRY(hipSetDevice(p->device));
   spec_adopt(p);
   spec_ensure(p, SPEC_PROJECT);
-  if (!p->proj_ctr.p) HIP_TRY(hipMalloc(&p->proj_ctr.p, sizeof(ProjectCounters)));
-  HIP_TRY(p->ev_proj.ensure());
-  const EventSet<2>& ev = p->ev_proj;
-  ProjectCounters* d_ctr = (ProjectCounters*)p->proj_ctr.p;
   ProjectCounters hc{};
   float ms = 0.f;
   const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
   const float h = o->step * 0.5f;
-  hipError_t e = hipMemsetAsync(d_ctr, 0, sizeof(ProjectCounters), p->stream.s);
-  if (e == hipSuccess) e = hipEventRecord(ev[0], p->stream.s);
-  if (e == hipSuccess)  // (the kernel takes the positions as words: (const unsigned*) cannot be left to the launcher's static_cast)
-    e = launch_kernel(project_kernel, p->spec.f_project, grid, BLOCK, p->lds_bytes(2), p->stream.s, p->d_code.p, (const unsigned*)d_pos, n, h, o->tol, o->max_move, o->max_iters,
-                      (unsigned*)d_out_pos, d_before, d_after, d_status, d_ctr);
-  if (e == hipSuccess) e = hipEventRecord(ev[1], p->stream.s);
-  if (e == hipSuccess) e = hipMemcpyAsync(&hc, d_ctr, sizeof hc, hipMemcpyDeviceToHost, p->stream.s);
-  if (e == hipSuccess) e = hipStreamSynchronize(p->stream.s);
-  else (void)hipStreamSynchronize(p->stream.s);
-  if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-  if (e != hipSuccess) return fail(GSDF_ERR_HIP, std::string("project: ") + hipGetErrorString(e));
-  p->evals += hc.evals;
+  // (the kernel takes the positions as words: (const unsigned*) cannot be left to the launcher's static_cast)
+  if (int rc = counted_launch(p, p->proj, "project: ", &hc, &ms, [&](ProjectCounters* d_ctr) {
+        return launch_kernel(project_kernel, p->spec.f_project, grid, BLOCK, p->lds_bytes(2), p->stream.s, p->d_code.p, (const unsigned*)d_pos, n, h, o->tol, o->max_move, o->max_iters,
+                             (unsigned*)d_out_pos, d_before, d_after, d_status, d_ctr);
+      }))
+    return rc;
   gsdf_project_stats r{};
   r.n_verts = n;
   for (int k = 0; k < 8; k++) r.count[k] = hc.count[k];
@@ -603,8 +540,7 @@ static int ray_call_refused(const gsdf_program* p, size_t n) {
 }
 
 // ray_kernel on device-resident rays, or on device-resident vertices (step > 0: the thickness form), over the interpreter or the
-// handle's specialised build of it (abi_program.h). One launch, as project_dev: the counters (the handle's, made at its first cast,
-// as are the two events) are cleared on the stream in front of it and read behind it. One cast per program at a time.
+// handle's specialised build of it (abi_program.h), as one counted launch.
 int ray_dev(gsdf_program* p, const float* d_in, size_t n, const gsdf_ray_opts* o, float step, float thin, float* d_t, float* d_d, uint8_t* d_status,
             uint16_t* d_steps, gsdf_ray_stats* st) {
   const bool thick = step > 0.0f;
@@ -613,10 +549,6 @@ int ray_dev(gsdf_program* p, const float* d_in, size_t n, const gsdf_ray_opts* o
   HIP_TRY(hipSetDevice(p->device));
   spec_adopt(p);
   spec_ensure(p, SPEC_RAY);
-  if (!p->ray_ctr.p) HIP_TRY(hipMalloc(&p->ray_ctr.p, sizeof(RayCounters)));
-  HIP_TRY(p->ev_ray.ensure());
-  const EventSet<2>& ev = p->ev_ray;
-  RayCounters* d_ctr = (RayCounters*)p->ray_ctr.p;
   RayCounters hc{};
   float ms = 0.f;
   const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
@@ -625,23 +557,15 @@ int ray_dev(gsdf_program* p, const float* d_in, size_t n, const gsdf_ray_opts* o
   prm.tmax = o->tmax; prm.tol = o->tol; prm.min_step = o->min_step;
   prm.h = step * 0.5f; prm.thin = thin;
   prm.max_steps = o->max_steps; prm.refine = o->refine;
-  hipError_t e = hipMemsetAsync(d_ctr, 0, sizeof(RayCounters), p->stream.s);
-  if (e == hipSuccess) e = hipEventRecord(ev[0], p->stream.s);
-  if (e == hipSuccess) {  // (the kernel takes its input as words: (const unsigned*) cannot be left to the launcher's static_cast)
-    if (thick)
-      e = launch_kernel(ray_kernel<true>, p->spec.f_ray_thick, grid, BLOCK, p->lds_bytes(2), p->stream.s, p->d_code.p, (const unsigned*)d_in, n, prm, d_t, d_d, d_status,
-                        (unsigned short*)d_steps, d_ctr);
-    else
-      e = launch_kernel(ray_kernel<false>, p->spec.f_ray, grid, BLOCK, p->lds_bytes(1), p->stream.s, p->d_code.p, (const unsigned*)d_in, n, prm, d_t, d_d, d_status,
-                        (unsigned short*)d_steps, d_ctr);
-  }
-  if (e == hipSuccess) e = hipEventRecord(ev[1], p->stream.s);
-  if (e == hipSuccess) e = hipMemcpyAsync(&hc, d_ctr, sizeof hc, hipMemcpyDeviceToHost, p->stream.s);
-  if (e == hipSuccess) e = hipStreamSynchronize(p->stream.s);
-  else (void)hipStreamSynchronize(p->stream.s);
-  if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-  if (e != hipSuccess) return fail(GSDF_ERR_HIP, std::string("rays: ") + hipGetErrorString(e));
-  p->evals += hc.evals;
+  // (the kernel takes its input as words: (const unsigned*) cannot be left to the launcher's static_cast)
+  if (int rc = counted_launch(p, p->ray, "rays: ", &hc, &ms, [&](RayCounters* d_ctr) {
+        if (thick)
+          return launch_kernel(ray_kernel<true>, p->spec.f_ray_thick, grid, BLOCK, p->lds_bytes(2), p->stream.s, p->d_code.p, (const unsigned*)d_in, n, prm, d_t, d_d, d_status,
+                               (unsigned short*)d_steps, d_ctr);
+        return launch_kernel(ray_kernel<false>, p->spec.f_ray, grid, BLOCK, p->lds_bytes(1), p->stream.s, p->d_code.p, (const unsigned*)d_in, n, prm, d_t, d_d, d_status,
+                             (unsigned short*)d_steps, d_ctr);
+      }))
+    return rc;
   gsdf_ray_stats r{};
   r.n = n;
   for (int k = 0; k < 8; k++) r.count[k] = hc.count[k];
@@ -679,6 +603,34 @@ extern "C" int gsdf_hip_raycast3(gsdf_program* p, const float* rays, size_t n, c
   return GSDF_OK;
 }
 
+// ---- 2-D images (kernels_image.h) ---------------------------------------------------------------------------------------------------
+// The pixel lattice of both renderers over Bounds(), image.go:82-88: dx = sz.X/dxi ; bb.Min += (dx/2, dy/2) ; y = bb.Max.Y - j*dy ;
+// x = i*dx + bb.Min.X. k points per lane on `grid` workgroups.
+struct ImageLattice {
+  float dx, dy, xmin, ymax;
+  size_t n;
+  int k;
+  unsigned grid;
+};
+static ImageLattice image_lattice(const gsdf_program* p, int w, int h) {
+  ImageLattice l;
+  l.n = (size_t)w * (size_t)h;
+  const float szx = p->prog.bb[3] - p->prog.bb[0], szy = p->prog.bb[4] - p->prog.bb[1];
+  l.dx = szx / (float)w; l.dy = szy / (float)h;
+  l.xmin = p->prog.bb[0] + l.dx / 2; l.ymax = p->prog.bb[4];
+  l.k = p->batch_k();
+  l.grid = grid_for((l.n + l.k - 1) / l.k, p->num_cu, 8);
+  return l;
+}
+// behind the kernel: the planes the caller asked for to the host, one synchronise, n evaluations counted
+static int image_finish(gsdf_program* p, size_t n, float* dist_out, const void* d_dist, uint8_t* rgba_out, const void* d_rgba) {
+  if (dist_out) HIP_TRY(hipMemcpyAsync(dist_out, d_dist, n * 4, hipMemcpyDeviceToHost, p->stream.s));
+  if (rgba_out) HIP_TRY(hipMemcpyAsync(rgba_out, d_rgba, n * 4, hipMemcpyDeviceToHost, p->stream.s));
+  HIP_TRY(hipStreamSynchronize(p->stream.s));
+  p->evals += n;
+  return GSDF_OK;
+}
+
 // glrender.ImageRendererSDF2.Render for a 2D program: w x h pixels over Bounds(); host outputs (either may be NULL).
 extern "C" int gsdf_hip_image2(gsdf_program* p, int w, int h, float* dist_out, uint8_t* rgba_out) {
   if (!p) return fail(GSDF_ERR_BAD_ARGUMENT, "null program");
@@ -686,87 +638,17 @@ extern "C" int gsdf_hip_image2(gsdf_program* p, int w, int h, float* dist_out, u
   if (w <= 0 || h <= 0) return fail(GSDF_ERR_BAD_ARGUMENT, "bad image size");
   HIP_TRY(hipSetDevice(p->device));
   spec_adopt(p);  // (a background build that has finished: its kernels from here on)
-  const size_t n = (size_t)w * (size_t)h;
-  // image.go:82-88: dx = sz.X/dxi ; bb.Min += (dx/2, dy/2) ; y = bb.Max.Y - j*dy ; x = i*dx + bb.Min.X
-  const float szx = p->prog.bb[3] - p->prog.bb[0], szy = p->prog.bb[4] - p->prog.bb[1];
-  const float dx = szx / (float)w, dy = szy / (float)h;
-  const float xmin = p->prog.bb[0] + dx / 2, ymax = p->prog.bb[4];
-  DevBuf dd, dc;
-  HIP_TRY(dd.alloc(n * 4));
-  HIP_TRY(dc.alloc(n * 4));
-  const int k = p->batch_k();
-  const unsigned grid = grid_for((n + k - 1) / k, p->num_cu, 8);
+  const ImageLattice l = image_lattice(p, w, h);
+  DevBuf dd, dc;  // (both planes, whichever the caller takes)
+  HIP_TRY(dd.alloc(l.n * 4));
+  HIP_TRY(dc.alloc(l.n * 4));
   spec_ensure(p, SPEC_AUX);
-  HIP_TRY(launch_kernel(k == 4 ? image2_kernel<4> : (k == 2 ? image2_kernel<2> : image2_kernel<1>), p->spec.f_image, grid, BLOCK, p->lds_bytes(k), p->stream.s, p->d_code.p, w, h, xmin, ymax,
-                        dx, dy, dd.p, dc.p));
-  if (dist_out) HIP_TRY(hipMemcpyAsync(dist_out, dd.p, n * 4, hipMemcpyDeviceToHost, p->stream.s));
-  if (rgba_out) HIP_TRY(hipMemcpyAsync(rgba_out, dc.p, n * 4, hipMemcpyDeviceToHost, p->stream.s));
-  HIP_TRY(hipStreamSynchronize(p->stream.s));
-  p->evals += n;
-  return GSDF_OK;
+  HIP_TRY(launch_kernel(l.k == 4 ? image2_kernel<4> : (l.k == 2 ? image2_kernel<2> : image2_kernel<1>), p->spec.f_image, l.grid, BLOCK, p->lds_bytes(l.k), p->stream.s, p->d_code.p, w, h,
+                        l.xmin, l.ymax, l.dx, l.dy, dd.p, dc.p));
+  return image_finish(p, l.n, dist_out, dd.p, rgba_out, dc.p);
 }
 
-// ---- the UI's view of a 3-D part (gsdfaux.UI, gsdfaux/ui.go:247-355): camera helper and frame --------------------------------
-namespace {
-// math32.Hypot (scaffold/ms.hpp: hypotf32): the bounds' Diagonal() = Norm(Size()) by nested hypot
-float hypot32(float p, float q) {
-  if (std::isinf(p) || std::isinf(q)) return INFINITY;
-  if (p != p || q != q) return NAN;
-  p = std::fabs(p); q = std::fabs(q);
-  if (p < q) std::swap(p, q);
-  if (p == 0) return 0;
-  q = q / p;
-  return p * std::sqrt(1 + q * q);
-}
-void normalize3(const float a[3], float out[3]) {
-  const float len = std::sqrt((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]);
-  out[0] = a[0] / len; out[1] = a[1] / len; out[2] = a[2] / len;
-}
-void cross3(const float a[3], const float b[3], float out[3]) {
-  out[0] = a[1] * b[2] - a[2] * b[1];
-  out[1] = a[2] * b[0] - a[0] * b[2];
-  out[2] = a[0] * b[1] - a[1] * b[0];
-}
-bool finite_all(const float* v, int n) {
-  for (int i = 0; i < n; i++) if (!std::isfinite(v[i])) return false;
-  return true;
-}
-}  // namespace
-
-// ui.go:18 (diag), 123 (camDist = diag), 220 (charDist = camDist + diag), 276-297 (orbit camera). Host only.
-extern "C" int gsdf_hip_view_orbit(const float bb[6], float yaw, float pitch, float cam_dist, const float target[3], gsdf_view* view) {
-  if (!bb || !view) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
-  if (!finite_all(bb, 6) || !std::isfinite(yaw) || !std::isfinite(pitch) || !std::isfinite(cam_dist) || (target && !finite_all(target, 3)))
-    return fail(GSDF_ERR_BAD_ARGUMENT, "non-finite bounds, angle, distance or target");
-  const float diag = hypot32(bb[3] - bb[0], hypot32(bb[4] - bb[1], bb[5] - bb[2]));
-  const float cd = cam_dist > 0.f ? cam_dist : diag;
-  if (!(cd > 0.f) || !std::isfinite(cd + diag)) return fail(GSDF_ERR_BAD_ARGUMENT, "empty bounds and no camera distance");
-  const float kPi = 3.14159265359f;  // ui.go:269
-  const float lim_lo = -kPi / 2.0f + 0.01f, lim_hi = kPi / 2.0f - 0.01f;
-  const float pc = std::fmin(std::fmax(pitch, lim_lo), lim_hi);
-  const float cp = (float)std::cos((double)pc), sp = (float)std::sin((double)pc);
-  const float cy = (float)std::cos((double)yaw), sy = (float)std::sin((double)yaw);
-  const float dir[3] = {cp * sy, sp, cp * cy};
-  const float ta[3] = {target ? target[0] : 0.f, target ? target[1] : 0.f, target ? target[2] : 0.f};
-  gsdf_view v;
-  std::memset(&v, 0, sizeof v);
-  float fwd[3], right[3];
-  for (int a = 0; a < 3; a++) v.ro[a] = ta[a] - dir[a] * cd;
-  for (int a = 0; a < 3; a++) fwd[a] = ta[a] - v.ro[a];
-  normalize3(fwd, v.ww);
-  const float up[3] = {0.f, 1.f, 0.f};
-  cross3(v.ww, up, right);
-  normalize3(right, v.uu);
-  cross3(v.uu, v.ww, v.vv);
-  v.char_dist = cd + diag;
-  v.aa = 1;
-  v.max_steps = 256;
-  if (!finite_all(v.ro, 3) || !finite_all(v.uu, 3) || !finite_all(v.vv, 3) || !finite_all(v.ww, 3))
-    return fail(GSDF_ERR_BAD_ARGUMENT, "degenerate camera (the camera distance vanishes next to the target)");
-  *view = v;
-  return GSDF_OK;
-}
-
+// ---- the UI's view of a 3-D part (gsdfaux.UI, gsdfaux/ui.go:247-355): the frame (the orbit camera: abi_evalhost.cpp) ----------------
 // One UI frame (ui.go:247-355) of a 3-D program: view_kernel over the interpreter, or the handle's specialised build of it.
 // The plain form runs by default: measured against the refilling one (tools/view_bench.py, profiles/view_*), it is 1.3-2x faster on
 // every frame tried. GSDF_HIP_VIEW_REFILL=1 (read at every call; developer knob for the A/B and its parity
@@ -828,54 +710,7 @@ extern "C" int gsdf_hip_render3(gsdf_program* p, const gsdf_view* view, int w, i
 }
 
 // ---- a 2-D part's picture with gsdfaux's colour conversions (gsdfaux.RenderPNGFile, gsdfaux/gsdfaux.go:264-296; color.go) --------
-// RenderPNGFile's picture size (gsdfaux.go:271-274). Host only.
-extern "C" int gsdf_hip_picture_size(const float bb[6], int pic_height, int* w) {
-  if (!bb || !w) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
-  if (!finite_all(bb, 6)) return fail(GSDF_ERR_BAD_ARGUMENT, "non-finite bounds");
-  if (pic_height < 1 || pic_height > 16384) return fail(GSDF_ERR_BAD_ARGUMENT, "picture height must be 1 .. 16384");
-  const float szx = bb[3] - bb[0], szy = bb[4] - bb[1];
-  if (!(szy > 0.f) || !std::isfinite(szx) || !std::isfinite(szy)) return fail(GSDF_ERR_BAD_ARGUMENT, "empty or non-finite bounds");
-  const double pix_per_unit = (double)pic_height / (double)szy;
-  const double wd = pix_per_unit * (double)szx;
-  if (!(wd >= 1.0 && wd < 16385.0)) return fail(GSDF_ERR_BAD_ARGUMENT, "picture width comes out outside 1 .. 16384");
-  *w = (int)wd;
-  return GSDF_OK;
-}
-
-// ColorConversionInigoQuilez with RenderPNGFile's default, ms2.Box.Diagonal() / 3 (gsdfaux.go:268). Host only.
-extern "C" int gsdf_hip_color_iq(const float bb[6], float char_dist, gsdf_color2* out) {
-  if (!out || (!bb && !(char_dist > 0.f))) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
-  float cd = char_dist;
-  if (!std::isfinite(cd)) return fail(GSDF_ERR_BAD_ARGUMENT, "non-finite characteristic distance");
-  if (!(cd > 0.f)) {
-    if (!finite_all(bb, 6)) return fail(GSDF_ERR_BAD_ARGUMENT, "non-finite bounds");
-    cd = hypot32(bb[3] - bb[0], bb[4] - bb[1]) / 3.f;
-    if (!(cd > 0.f) || !std::isfinite(cd)) return fail(GSDF_ERR_BAD_ARGUMENT, "empty bounds and no characteristic distance");
-  }
-  gsdf_color2 c;
-  std::memset(&c, 0, sizeof c);
-  c.kind = GSDF_COLOR_IQ;
-  c.length = cd;
-  *out = c;
-  return GSDF_OK;
-}
-
-// ColorConversionLinearGradient (color.go:50-71): Go's `c0 == color.Black && c1 == color.White` selects the black-and-white closure.
-extern "C" int gsdf_hip_color_gradient(float length, const uint8_t c0[4], const uint8_t c1[4], gsdf_color2* out) {
-  if (!c0 || !c1 || !out) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
-  if (!std::isfinite(length) || length < 0.f) return fail(GSDF_ERR_BAD_ARGUMENT, "gradient length must be finite and >= 0");
-  gsdf_color2 c;
-  std::memset(&c, 0, sizeof c);
-  const bool black = c0[0] == 0 && c0[1] == 0 && c0[2] == 0 && c0[3] == 255;
-  const bool white = c1[0] == 255 && c1[1] == 255 && c1[2] == 255 && c1[3] == 255;
-  c.kind = black && white ? GSDF_COLOR_BW_SMOOTH : GSDF_COLOR_GRADIENT;
-  c.length = length;
-  std::memcpy(c.c0, c0, 4);
-  std::memcpy(c.c1, c1, 4);
-  *out = c;
-  return GSDF_OK;
-}
-
+// (the picture size and the conversions' constructors: abi_evalhost.cpp)
 // ImageRendererSDF2.Render (image.go:76-118) with a conversion of gsdfaux: image2_color_kernel over the interpreter (the kind a
 // kernel argument), or the handle's specialised build of it (one kernel per kind).
 extern "C" int gsdf_hip_image2_color(gsdf_program* p, const gsdf_color2* conv, int w, int h, uint8_t* rgba_out, float* dist_out) {
@@ -891,118 +726,19 @@ extern "C" int gsdf_hip_image2_color(gsdf_program* p, const gsdf_color2* conv, i
   HIP_TRY(hipSetDevice(p->device));
   spec_adopt(p);  // (a background build that has finished: its kernels from here on)
   spec_ensure(p, SPEC_PICTURE);
-  const size_t n = (size_t)w * (size_t)h;
-  // gsdf_hip_image2's lattice, statement for statement
-  const float szx = p->prog.bb[3] - p->prog.bb[0], szy = p->prog.bb[4] - p->prog.bb[1];
-  const float dx = szx / (float)w, dy = szy / (float)h;
-  const float xmin = p->prog.bb[0] + dx / 2, ymax = p->prog.bb[4];
+  const ImageLattice l = image_lattice(p, w, h);
   ColorConv cv;
   cv.kind = conv->kind;
   cv.length = conv->length;
   cv.c0 = (uint32_t)conv->c0[0] | ((uint32_t)conv->c0[1] << 8) | ((uint32_t)conv->c0[2] << 16) | ((uint32_t)conv->c0[3] << 24);
   cv.c1 = (uint32_t)conv->c1[0] | ((uint32_t)conv->c1[1] << 8) | ((uint32_t)conv->c1[2] << 16) | ((uint32_t)conv->c1[3] << 24);
   DevBuf dd, dc;  // (an output not asked for is neither allocated nor written)
-  if (dist_out) HIP_TRY(dd.alloc(n * 4));
-  if (rgba_out) HIP_TRY(dc.alloc(n * 4));
+  if (dist_out) HIP_TRY(dd.alloc(l.n * 4));
+  if (rgba_out) HIP_TRY(dc.alloc(l.n * 4));
   float* o_dist = dist_out ? (float*)dd.p : nullptr;
   uint32_t* o_rgba = rgba_out ? (uint32_t*)dc.p : nullptr;
-  const int k = p->batch_k();
-  const unsigned grid = grid_for((n + k - 1) / k, p->num_cu, 8);
   // (the interpreter's kernel takes the conversion kind as an argument, a per-tree one is built for its kind)
-  HIP_TRY(launch_kernel(k == 4 ? image2_color_kernel<4, -1> : (k == 2 ? image2_color_kernel<2, -1> : image2_color_kernel<1, -1>), p->spec.f_imgc[conv->kind], grid, BLOCK, p->lds_bytes(k),
-                        p->stream.s, p->d_code.p, w, h, xmin, ymax, dx, dy, cv, o_dist, o_rgba));
-  if (dist_out) HIP_TRY(hipMemcpyAsync(dist_out, dd.p, n * 4, hipMemcpyDeviceToHost, p->stream.s));
-  if (rgba_out) HIP_TRY(hipMemcpyAsync(rgba_out, dc.p, n * 4, hipMemcpyDeviceToHost, p->stream.s));
-  HIP_TRY(hipStreamSynchronize(p->stream.s));
-  p->evals += n;
-  return GSDF_OK;
-}
-
-// ---- gleval.BlockCachedSDF3 (gleval/gleval.go:110-218) over a HIP program ---------------------------------------
-// Host-side wrapper, as in the reference: a lossy cache keyed by the lattice cell of the position
-// (int(mul * (p - bb.Min)) per axis, mul = 1/res); misses are evaluated in ONE batch by the wrapped evaluator.
-struct gsdf_blockcache {
-  gsdf_program* sdf = nullptr;
-  float mul[3] = {0, 0, 0};
-  struct Key { long long x, y, z; bool operator==(const Key& o) const { return x == o.x && y == o.y && z == o.z; } };
-  struct Hash {
-    size_t operator()(const Key& k) const {
-      unsigned long long h = (unsigned long long)k.x * 0x9E3779B97F4A7C15ull;
-      h ^= (unsigned long long)k.y + 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2);
-      h ^= (unsigned long long)k.z + 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2);
-      return (size_t)h;
-    }
-  };
-  std::unordered_map<Key, float, Hash> m;
-  std::vector<float> posbuf, distbuf;
-  std::vector<size_t> idxbuf;
-  uint64_t hits = 0, evals = 0;
-};
-
-extern "C" int gsdf_hip_blockcache_reset(gsdf_blockcache* c, gsdf_program* sdf, float resx, float resy, float resz) {
-  if (!c || !sdf) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
-  if (resx <= 0 || resy <= 0 || resz <= 0 || std::isnan(resx) || std::isnan(resy) || std::isnan(resz))
-    return fail(GSDF_ERR_RESOLUTION, "invalid resolution for BlockCachedSDF3");  // gleval.go:127-129
-  if (sdf->prog.is2d) return fail(GSDF_ERR_DIMENSION, "program is 2D");
-  c->m.clear();
-  c->sdf = sdf;
-  c->mul[0] = 1.0f / resx; c->mul[1] = 1.0f / resy; c->mul[2] = 1.0f / resz;  // DivElem({1,1,1}, res)
-  c->posbuf.clear(); c->distbuf.clear(); c->idxbuf.clear();
-  c->hits = 0; c->evals = 0;  // Reset also resets the statistics (gleval.go:124)
-  return GSDF_OK;
-}
-extern "C" int gsdf_hip_blockcache_create(gsdf_program* sdf, float resx, float resy, float resz, gsdf_blockcache** out) {
-  if (!out) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
-  *out = nullptr;
-  gsdf_blockcache* c = new (std::nothrow) gsdf_blockcache();
-  if (!c) return fail(GSDF_ERR_BAD_ARGUMENT, "out of memory");
-  const int rc = gsdf_hip_blockcache_reset(c, sdf, resx, resy, resz);
-  if (rc) { delete c; return rc; }
-  *out = c;
-  return GSDF_OK;
-}
-extern "C" void gsdf_hip_blockcache_destroy(gsdf_blockcache* c) { delete c; }
-extern "C" uint64_t gsdf_hip_blockcache_hits(const gsdf_blockcache* c) { return c ? c->hits : 0; }
-extern "C" uint64_t gsdf_hip_blockcache_evaluations(const gsdf_blockcache* c) { return c ? c->evals : 0; }
-
-// (*BlockCachedSDF3).Evaluate (gleval.go:154-211). pos: n x 3 float32 with the given byte stride (12 or 16).
-extern "C" int gsdf_hip_blockcache_eval3(gsdf_blockcache* c, const void* pos, size_t stride, size_t n_pos, float* dist, size_t n_dist) {
-  if (!c || !c->sdf) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
-  if (n_pos != n_dist) return fail(GSDF_ERR_LENGTH_MISMATCH, "position and distance buffer length mismatch");
-  if (n_pos == 0) return fail(GSDF_ERR_EMPTY_BUFFERS, "empty buffers");
-  if (!pos || !dist) return fail(GSDF_ERR_BAD_ARGUMENT, "null buffer");
-  if (stride % 4 != 0 || stride < 12) return fail(GSDF_ERR_BAD_ARGUMENT, "bad position stride");
-  const float* bbmin = c->sdf->prog.bb;
-  auto key_of = [&](const float* p) {
-    // tp = MulElem(mul, Sub(p, bb.Min)); int(tp.X) truncates toward zero (Go float->int conversion)
-    gsdf_blockcache::Key k;
-    k.x = (long long)(c->mul[0] * (p[0] - bbmin[0]));
-    k.y = (long long)(c->mul[1] * (p[1] - bbmin[1]));
-    k.z = (long long)(c->mul[2] * (p[2] - bbmin[2]));
-    return k;
-  };
-  c->posbuf.clear();
-  c->idxbuf.clear();
-  const char* base = (const char*)pos;
-  for (size_t i = 0; i < n_pos; i++) {
-    const float* p = (const float*)(base + i * stride);
-    auto it = c->m.find(key_of(p));
-    if (it != c->m.end()) {
-      dist[i] = it->second;
-    } else {
-      c->posbuf.insert(c->posbuf.end(), p, p + 3);
-      c->idxbuf.push_back(i);
-    }
-  }
-  const size_t nseek = c->idxbuf.size();
-  if (nseek > 0) {
-    c->distbuf.resize(nseek);
-    const int rc = gsdf_hip_eval3(c->sdf, c->posbuf.data(), 12, nseek, c->distbuf.data(), nseek);
-    if (rc) return rc;
-    for (size_t i = 0; i < nseek; i++) c->m[key_of(&c->posbuf[3 * i])] = c->distbuf[i];  // later entries of a cell overwrite
-    for (size_t i = 0; i < nseek; i++) dist[c->idxbuf[i]] = c->distbuf[i];
-  }
-  c->evals += n_pos;
-  c->hits += n_pos - nseek;
-  return GSDF_OK;
+  HIP_TRY(launch_kernel(l.k == 4 ? image2_color_kernel<4, -1> : (l.k == 2 ? image2_color_kernel<2, -1> : image2_color_kernel<1, -1>), p->spec.f_imgc[conv->kind], l.grid, BLOCK,
+                        p->lds_bytes(l.k), p->stream.s, p->d_code.p, w, h, l.xmin, l.ymax, l.dx, l.dy, cv, o_dist, o_rgba));
+  return image_finish(p, l.n, dist_out, dd.p, rgba_out, dc.p);
 }

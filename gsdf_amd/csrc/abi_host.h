@@ -1,7 +1,9 @@
 // abi_host.h -- what the translation units of the C ABI share on the host side: error plumbing, the mesh handle, the buffer
-// pools. No device code (abi_comm.cpp and abi_host.cpp are plain C++).
+// pools. No device code (abi_comm.cpp, abi_evalhost.cpp and abi_host.cpp are plain C++).
 //   abi_host.cpp  error text, triangle / pinned-buffer pools, result copies
-//   abi_eval.hip  programs, gleval.SDF3 / SDF2 Evaluate, normals, projection, rays, image / view / picture renderers, block cache
+//   abi_eval.hip  programs, self-test hooks, gleval.SDF3 / SDF2 Evaluate, normals, projection, rays, image / view / picture renderers
+//   abi_evalhost.cpp  the evaluator side without a GPU: lowering for inspection, orbit camera, picture size, colour conversions,
+//                 block cache (over the public ABI of a program)
 //   abi_spec.hip  per-tree (specialised) kernels of a program: first build, background build and adoption, the groups built on
 //                 first use (spec_ensure), the report of what a handle launches. Host code only: it owns no kernel
 //   abi_mesh.hip  octree / flat / dual-contouring meshers and the mesh accessors
@@ -13,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cmath>
 #include <cstdint>
 #include <cstdlib>
 #include <string>
@@ -43,6 +46,11 @@ inline uint64_t env_u64(const char* name, uint64_t dflt) { const char* e = geten
 inline bool env_flag(const char* name) { const char* e = getenv(name); return e && atoi(e) != 0; }      // off unless set to non-zero
 inline bool env_flag_on(const char* name) { const char* e = getenv(name); return !e || atoi(e) != 0; }  // on unless set to 0
 inline bool env_set(const char* name) { return getenv(name) != nullptr; }
+
+inline bool finite_all(const float* v, int n) {
+  for (int i = 0; i < n; i++) if (!std::isfinite(v[i])) return false;
+  return true;
+}
 
 struct gsdf_mesh {
   int device = 0;

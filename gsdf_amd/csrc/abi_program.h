@@ -199,10 +199,10 @@ struct gsdf_program {
   // kernels under it too (abi_eval.hip: eval_dev). Every other reader relies on the one-caller-at-a-time rule of gsdf_hip.h.
   SpecKernels spec;
   size_t lds_dense() const { return (size_t)(prog.nslots * 4 > 8 ? prog.nslots * 4 : 8) * BLOCK * sizeof(float) + 256 + 4 * 512 * sizeof(float) + 4 * 24 * sizeof(float) + 16; }
-  DevPtr<void> proj_ctr;  // the projection's counters on the device and the two events around its launch: made at the
-  EventSet<2> ev_proj;    // first projection, kept for the next (project_dev)
-  DevPtr<void> ray_ctr;   // the same for rays and wall thickness: made at the first cast (ray_dev)
-  EventSet<2> ev_ray;
+  // A kernel's counters on the device and the two events around its launch: made at the first launch of the kind, kept for the
+  // next (abi_eval.hip: counted_launch). One per kind: the projection (project_dev); rays and wall thickness (ray_dev).
+  struct CountedLaunch { DevPtr<void> ctr; EventSet<2> ev; };
+  CountedLaunch proj, ray;
   // Specialisation in the background (gsdf_hip_program_specialize_async): a thread builds and loads the kernels on a shadow handle
   // (this program, this device, nothing else) while the interpreter kernels serve; the entry points adopt the result at their
   // next call (abi_spec.hip: spec_adopt). 0 idle | 1 building | 2 built, to be adopted | 3 failed (spec_async_err)

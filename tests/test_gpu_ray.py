@@ -12,7 +12,7 @@ from corpus import shapes3d
 from oracle.oracle import OracleSDF
 from scaffold.builder import Builder
 from test_gpu_nan import degenerate_trees
-from test_gpu_project import simplified
+from test_gpu_project import opts_for, simplified
 from test_gpu_weld import SMALL
 from test_ray_ref import shell_node_tree, shell_tree
 
@@ -189,6 +189,33 @@ def test_small_shapes(gpu, name):
     assert interp.info()["kernels"]["ray"] == "ray_kernel:interpreter", interp.info()["kernels"]
     if name == "sphere":   # every inward ray of the unit sphere crosses it: about 2, whatever the vertex
         assert ta[2].count[R.HIT] + ta[2].count[R.CROSSED] == len(v) and 1.9 < ta[2].t_min <= ta[2].t_max < 2.1
+
+
+@pytest.mark.parametrize("form", ["interpreter", "specialised"])
+def test_projection_and_rays_take_turns_on_one_handle(gpu, form):
+    """The projection and the rays each keep a counter block on the handle, cleared at every call: a projection, then a dry
+    projection, a dry thickness and 64 + 1 rays, then the projection again, all on ONE handle. The second projection's stats and
+    outputs are the first's, and the handle's counter grows by the three calls' evaluations, no more."""
+    sx, v, _, _, res = simplified(gpu, "sphere")
+    shape = dict(shapes3d()[1])["sphere"]
+    sdf = gpu.SDF3HIP(shape)
+    if form == "specialised":
+        sdf.specialize()
+    po = opts_for(res)
+    first, st1 = sx.project(sdf, **po)
+    e0 = sdf.Evaluations()
+    _, dry = sx.project(sdf, dry=True, **po)
+    _, _, th = sx.thickness(sdf, dry=True, **thickness_opts(res))
+    o, r = corner_rays(shape.Bounds(), 64 + 1, 5)
+    rays = sdf.raycast(o, r, tmax=F(2), tol=F(res / F(1024)), max_steps=96)
+    assert sdf.Evaluations() - e0 == dry.evals + th.evals + rays[4].evals and min(dry.evals, th.evals, rays[4].evals) > 0
+    assert th.n == len(v) and rays[4].n == 65 and th.count[R.HIT] + th.count[R.CROSSED] == len(v) and rays[4].count[R.HIT] + rays[4].count[R.CROSSED] > 0
+    second, st2 = sx.project(sdf, **po)
+    assert dry.result_bytes() == st1.result_bytes() == st2.result_bytes()
+    assert [x.tobytes() for x in second.read() + second.fit()] == [x.tobytes() for x in first.read() + first.fit()]
+    again = sdf.raycast(o, r, tmax=F(2), tol=F(res / F(1024)), max_steps=96)
+    assert again[4].result_bytes() == rays[4].result_bytes() and [x.tobytes() for x in again[:4]] == [x.tobytes() for x in rays[:4]]
+    assert sdf.info()["kernels"]["ray"] == ("ray_kernel:specialised" if form == "specialised" else "ray_kernel:interpreter")
 
 
 def test_slab_thickness_and_flat(gpu):
