@@ -35,7 +35,6 @@ const bool ctr_from_kernel = env_flag_on("GSDF_HIP_CTR_FROM_KERNEL");  // develo
 // The ahead-of-time kernel of a variant: exactly the instantiations this library launches, null for every other. (A per-tree
 // build has the same parameters whatever its template arguments: launch_kernel takes their types from these.) The kernels come
 // out in the code object in the order they are first named here.
-using leaf_kernel_t = decltype(&leaf_kernel<4, 3>);
 using leaf_eval_kernel_t = decltype(&leaf_eval_kernel<4, 3>);
 using leaf_dense_kernel_t = decltype(&leaf_dense_kernel<3, true, false>);
 using dc_origin_kernel_t = decltype(&dc_origin_kernel<4, 3>);
@@ -57,18 +56,9 @@ leaf_eval_kernel_t leaf_eval_aot(const LeafVariant& v) {  // (K, W): gsdf_progra
       {2, 3, false, true, false, leaf_eval_kernel<2, 3, false, true>}, {2, 3, true, true, false, leaf_eval_kernel<2, 3, true, true>}, {2, 3, true, false, false, leaf_eval_kernel<2, 3, true, false>},
       {1, 4, false, true, false, leaf_eval_kernel<1, 4, false, true>}, {1, 4, true, true, false, leaf_eval_kernel<1, 4, true, true>}, {1, 4, true, false, false, leaf_eval_kernel<1, 4, true, false>},
   };
-  if (v.fused || v.both) return nullptr;
+  if (v.both) return nullptr;
   for (const Row& r : rows)
     if (r.k == v.k && r.w == v.w && r.ucube == v.ucube && r.ntlds == v.ntlds && r.dz == v.dz) return r.f;
-  return nullptr;
-}
-constexpr auto leaf_brick_aot = leaf_brick_kernel<4, 2>;  // fused leaf phase, share_corners = 1: one wave per level-3 brick
-leaf_kernel_t leaf_fused_aot(const LeafVariant& v) {
-  if (!v.fused) return nullptr;
-  if (v.k == 4 && v.w == 2) return leaf_kernel<4, 2>;
-  if (v.k == 4 && v.w == 3) return leaf_kernel<4, 3>;
-  if (v.k == 2 && v.w == 3) return leaf_kernel<2, 3>;
-  if (v.k == 1 && v.w == 4) return leaf_kernel<1, 4>;
   return nullptr;
 }
 dc_origin_kernel_t dc_origin_aot(SweepVariant v) {  // (gsdf_program::dc_origin_variant)
@@ -96,11 +86,11 @@ struct gsdf_mesh_job {
   uint64_t qcap = 0, want = 0, want_rec_n = 0;  // capacities of the next attempt
   // the attempt in flight
   int attempt = 0, slot;
-  bool used_brick = false, two_kernel = false, ctr_on_host = false, used_dz = false, used_dense = false;
+  bool ctr_on_host = false, used_dz = false, used_dense = false;
   int chain_first = 0;  // levels <= chain_first were tested by prune_kernel (one launch per level), the ones above speculatively
   uint64_t nblk = 0, nblk_q = 0, lbound = 0;  // 64-leaf blocks the record arena holds / the queue capacity allows for; leaves the latter bounds
   size_t clear_bytes = 0;
-  bool want_two = false, masks_valid = false;
+  bool masks_valid = false;
   Cube* q[2] = {nullptr, nullptr};  // the cube queues by level parity, and their capacities
   uint64_t capq[2] = {0, 0};
   MeshCounters* d_ctr = nullptr;
@@ -147,8 +137,8 @@ int gsdf_mesh_job::prepare_outputs() {
   if (!want_recs && !m->d_tris) {
     uint64_t need = want ? want : (p->last_tris ? p->last_tris + p->last_tris / 16 + 1024 : (uint64_t)1 << 20);
     if (opts.host_output) {
-      // triangles straight into pinned host memory: the stage flushes of leaf_kernel are 4.6 KB coalesced bursts,
-      // which PCIe takes well; the transfer then overlaps the kernel instead of following it
+      // triangles straight into pinned host memory: the marching kernel's stores are coalesced bursts, which PCIe takes
+      // well; the transfer then overlaps the kernel instead of following it
       void* hb = nullptr;
       size_t hcap = 0;
       if (int rc = host_buf(&hb, &hcap, (size_t)need * 36)) return rc;
@@ -163,7 +153,7 @@ int gsdf_mesh_job::prepare_outputs() {
       }
     }
   }
-  // 64-leaf blocks the queue capacity allows for, and their groups (two-kernel leaf phase)
+  // 64-leaf blocks the queue capacity allows for, and their groups
   lbound = capq[lq & 1] << (3 * (lq - 1));
   {
     const uint64_t full = (levels - lq) * 3 >= 40 ? UINT64_MAX : ((uint64_t)1 << (3 * (levels - 1)));
@@ -177,17 +167,18 @@ int gsdf_mesh_job::prepare_outputs() {
   nblk = p->rec_blocks ? p->rec_blocks : kRecBlocks0;
   if (nblk > nblk_q) nblk = nblk_q;
   const uint64_t ngrp = (nblk + MARCH_GROUP - 1) / MARCH_GROUP;
-  want_two = !fused_leaf();
-  if (want_two && (w.hdr.ensure(nblk * sizeof(uint32_t)) != hipSuccess || w.rec.ensure(nblk * (size_t)REC_BLOCK * sizeof(uint32_t)) != hipSuccess)) {
-    (void)hipGetLastError();  // no room for the records: the fused kernel needs none
-    w.hdr.release(); w.rec.release();
-    want_two = false;
+  const size_t hdr_bytes = nblk * sizeof(uint32_t), rec_bytes = nblk * (size_t)REC_BLOCK * sizeof(uint32_t);
+  if (w.hdr.ensure(hdr_bytes) != hipSuccess || w.rec.ensure(rec_bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    w.hdr.release(); w.rec.release();  // (the workspace stays usable: a later mesh asks again)
+    return fail(GSDF_ERR_CAPACITY, "no device memory for the cut-leaf record arena (" + std::to_string(nblk) + " blocks: " + std::to_string(hdr_bytes) + " + " +
+                                       std::to_string(rec_bytes) + " bytes)");
   }
-  if (want_recs && (!want_two || w.grp.ensure(ngrp * sizeof(unsigned long long)) != hipSuccess)) {
+  if (want_recs && w.grp.ensure(ngrp * sizeof(unsigned long long)) != hipSuccess) {
     (void)hipGetLastError();
     return (fail(GSDF_ERR_CAPACITY, "no device memory for the cut-leaf record arena (payload = records needs it)"));
   }
-  clear_bytes = kCtrBytes + (want_two ? ngrp * sizeof(unsigned long long) : 0);
+  clear_bytes = kCtrBytes + ngrp * sizeof(unsigned long long);
   HIP_TRY(w.ctr.ensure(clear_bytes));
   d_ctr = (MeshCounters*)w.ctr.p;
   // Brick masks (dev_ops.h: D_SKIP): valid when the last level of cubes, which the leaf kernels continue from, is a level-3 brick
@@ -264,21 +255,7 @@ int gsdf_mesh_job::enqueue_leaf() {
   const unsigned grid = grid_for(bound, p->num_cu, leaf_bpc);
   const Cube* cubes = q[lq & 1];
   const uint64_t ncubes = capq[lq & 1];
-  if (!want_two) {
-    if (lq == 3 && lk == 4 && opts.share_corners == 1) {
-      // exact corner sharing: one wave per level-3 brick
-      const size_t lds_b = (size_t)(p->prog.nslots * 4) * BLOCK * sizeof(float) + 4096 + TRI_STAGE * 36 + 32 + 4 * 512 * 4 + 4 * 24 * 4;
-      hipLaunchKernelGGL(leaf_brick_aot, dim3(grid_for(ncubes * 64 < bound ? ncubes * 64 : bound, p->num_cu, 8)), dim3(BLOCK), lds_b, s, p->d_code.p, cubes,
-                         (unsigned long long)ncubes, p->prog.nslots, ox, oy, oz, res, m->d_tris, tcap, d_ctr);
-      used_brick = true;
-      HIP_TRY(hipGetLastError());
-    } else {
-      const LeafPick pick = p->leaf_pick(lq);
-      HIP_TRY(launch_kernel(leaf_fused_aot(pick.v), pick.f, grid, BLOCK, lds_m, s, p->d_code.p, cubes, ncubes, lq, p->prog.nslots, ox, oy, oz, res, m->d_tris, tcap, d_ctr));
-    }
-    return GSDF_OK;
-  }
-  // two kernels: evaluation + cut-leaf records, then marching cubes over the records
+  // evaluation + cut-leaf records, then marching cubes over the records
   uint32_t* d_hdr = (uint32_t*)w.hdr.p;
   uint32_t* d_rec = (uint32_t*)w.rec.p;
   unsigned long long* d_psum = (unsigned long long*)((char*)w.ctr.p + kCtrBytes);  // cleared with the counters
@@ -301,7 +278,6 @@ int gsdf_mesh_job::enqueue_leaf() {
                           d_psum, nblk, d_ctr, use_masks));
   }
   HIP_TRY(hipEventRecord(w.ev[3], s));
-  two_kernel = true;
   if (want_recs) {
     // no marching here: the records are packed for the gather (scan_groups_kernel + pack_records_kernel), marching cubes
     // runs where they arrive (march_dense_kernel)
@@ -348,15 +324,13 @@ int gsdf_mesh_job::finish(bool* again) {
       *again = true;
       return GSDF_OK;
     }
-    if (two_kernel) {  // more blocks than the record arena holds: the blocks beyond it were skipped -- repeat with room for all
-      const uint64_t need = ((hc.n_level[lq] << (3 * (lq - 1))) + 63) / 64;
-      if (need > nblk) {
-        if (attempt >= 8) return (fail(GSDF_ERR_CAPACITY, "cut-leaf record arena capacity exceeded"));
-        p->rec_blocks = need + need / 8 + 1024;
-        two_kernel = false;
-        *again = true;
+    // more blocks than the record arena holds: the blocks beyond it were skipped -- repeat with room for all
+    const uint64_t need = ((hc.n_level[lq] << (3 * (lq - 1))) + 63) / 64;
+    if (need > nblk) {
+      if (attempt >= 8) return (fail(GSDF_ERR_CAPACITY, "cut-leaf record arena capacity exceeded"));
+      p->rec_blocks = need + need / 8 + 1024;
+      *again = true;
       return GSDF_OK;
-      }
     }
     if (hc.overflow && want_recs) {  // record payload too small: the scan knows the exact count
       if (attempt >= 8) return (fail(GSDF_ERR_CAPACITY, "device record buffer capacity exceeded"));
@@ -383,7 +357,7 @@ int gsdf_mesh_job::stats() {
   float ms01 = 0, ms12 = 0, ms13 = 0;
   HIP_TRY(hipEventElapsedTime(&ms01, w.ev[0], w.ev[1]));
   HIP_TRY(hipEventElapsedTime(&ms12, w.ev[1], w.ev[2]));
-  if (two_kernel) HIP_TRY(hipEventElapsedTime(&ms13, w.ev[1], w.ev[3]));  // the evaluating kernel alone
+  HIP_TRY(hipEventElapsedTime(&ms13, w.ev[1], w.ev[3]));  // the evaluating kernel alone
   uint64_t evals_prune = 0, pruned = 0;
   for (int level = levels; level >= lq; level--) {
     evals_prune += hc.n_items[level];
@@ -393,8 +367,8 @@ int gsdf_mesh_job::stats() {
     if (hc.n_items[level]) pruned += (hc.n_items[level] - passed) << (3 * (level - 1));  // DecomposesTo(1) = 8^(level-1)
   }
   const uint64_t n_leaves = hc.n_level[lq] << (3 * (lq - 1));
-  const uint64_t evals_leaf = used_brick || ((used_dz || used_dense) && two_kernel) ? hc.n_points  // distinct lattice points (share_corners = 1) / distinct z rows of the bricks (= 2) evaluated once each
-                                         : n_leaves * (uint64_t)lk + (uint64_t)(8 - lk) * (two_kernel && lq == 3 ? n_leaves : hc.n_cont);  // evaluations actually executed (a column brick always evaluates all eight rows: leaf_eval_kernel counts nothing)
+  const uint64_t evals_leaf = used_dz || used_dense ? hc.n_points  // distinct lattice points (share_corners = 1) / distinct z rows of the bricks (= 2) evaluated once each
+                                                    : n_leaves * (uint64_t)lk + (uint64_t)(8 - lk) * (lq == 3 ? n_leaves : hc.n_cont);  // evaluations actually executed (a column brick always evaluates all eight rows: leaf_eval_kernel counts nothing)
   m->st.n_tris = hc.n_tris;
   m->st.evals = evals_prune + evals_leaf;
   m->st.evals_prune = evals_prune;
@@ -404,8 +378,8 @@ int gsdf_mesh_job::stats() {
   m->st.active_leaves = hc.n_active;
   m->st.ms_prune = ms01;
   m->st.ms_leaf = ms12;
-  m->st.ms_march = two_kernel ? ms13 : ms12;
-  m->st.ms_emit = two_kernel ? ms12 - ms13 : 0.0;
+  m->st.ms_march = ms13;
+  m->st.ms_emit = ms12 - ms13;
   m->st.cut_leaves = hc.n_cut;
   m->st.ms_total = (double)ms01 + (double)ms12;
   p->evals += m->st.evals;
@@ -453,8 +427,8 @@ extern "C" int gsdf_hip_mesh_octree_start(gsdf_program* p, float res, const gsdf
   // rows, the packed points of 1 give that up): hypot / atan2 sharing instructions weighted as for the one-body leaf kernel. bolt (0)
   // and knurled-cylinder (2) gain 9 % / 17 % from 1, npt-flange (7) loses 40 % with it and breaks even with 2.
   if (opts.share_corners == 3) opts.share_corners = gsdf_dev::spec_xy_shared_weight(p->prog) < 3 ? 1 : 2;
-  if (want_recs && (opts.host_output || opts.max_tris || fused_leaf()))
-    return fail(GSDF_ERR_BAD_ARGUMENT, "payload = records goes with the two-kernel leaf phase only (no host_output, max_tris, fused leaf kernel)");
+  if (want_recs && (opts.host_output || opts.max_tris))
+    return fail(GSDF_ERR_BAD_ARGUMENT, "payload = records goes with the two-kernel leaf phase only (no host_output, max_tris)");
   {
     // the largest launch of the descent: prune_spec_kernel (lds_prune_of and its static stage of SPEC_STAGE cubes); of the leaf phase:
     // the evaluating kernel with its case table (and what its marching half declares statically)
@@ -1130,44 +1104,29 @@ extern "C" int gsdf_hip_mesh_flat(gsdf_program* p, float res, int shard_rank, in
     }
     HIP_TRYM(hipMemsetAsync(d_ctr, 0, sizeof(MeshCounters), s));
     HIP_TRYM(hipEventRecord(ev[2], s));
-    // default: the marching pass over the bit planes (flat_cut_scan_kernel + flat_march_list_kernel); GSDF_HIP_FLAT_STREAM=1:
-    // the pass that streams the float grid (flat_march_kernel, the kernel of rounds 1-2), kept for comparison -- same triangles
-    static const bool stream_march = env_flag("GSDF_HIP_FLAT_STREAM");
+    // the marching pass over the bit planes: flat_cut_scan_kernel + flat_march_list_kernel
     if (nx >= 65536u || ny >= 65536u || (uint64_t)c0 + ncz >= 65536u)  // record coordinates are 16-bit
       return bail(fail(GSDF_ERR_RESOLUTION, "resolution too fine for the flat renderer's lattice"));
-    if (stream_march) {
-      const uint64_t npass = (uint64_t)((nx + FLAT_TX - 1) / FLAT_TX) * ((ny + FLAT_ROWS - 1) / FLAT_ROWS) * ncz;  // wave passes: FLAT_TX x FLAT_ROWS cubes each
-      if ((double)npass + 1e6 >= 4294967296.0) return bail(fail(GSDF_ERR_RESOLUTION, "resolution too fine for the flat renderer's lattice"));
-      // four workgroups per CU are resident (36 KB of LDS each): a grid of exactly those, ~200 passes per wave, measured best
-      // (0.63 ms; 8 per CU 0.66, 32 per CU 0.74, 6 per CU 0.82 -- the stride between a wave's passes matters)
-      static const int mbpc = env_int("GSDF_HIP_FLAT_BPC", 4);  // tuning knob
-      const uint64_t gmax = (uint64_t)p->num_cu * (uint64_t)(mbpc > 0 ? mbpc : 4);
-      const uint64_t nwg = (npass + 3) / 4;
-      const size_t lds = (size_t)256 * 16 + (size_t)4 * FLAT_WAVE_RECS * REC_WORDS * 4 + (size_t)4 * 5 * FLAT_WAVE_RECS * 2;
-      hipLaunchKernelGGL(flat_march_kernel, dim3((unsigned)(nwg < gmax ? (nwg ? nwg : 1) : gmax)), dim3(BLOCK), lds, s, (const float*)grid, nx, ny, ncz, c0,
-                         ox, oy, oz, res, m->d_tris, (uint64_t)m->cap, d_ctr);
-    } else {
-      // a cut cube has at least one triangle: a list of the triangle buffer's capacity overflows only if that does
-      if (p->flat_list.ensure((size_t)m->cap * sizeof(unsigned long long)) != hipSuccess) {
-        (void)hipGetLastError();
-        return bail(fail(GSDF_ERR_CAPACITY, "flat renderer: no device memory for the list of cut cubes"));
-      }
-      unsigned long long* list = (unsigned long long*)p->flat_list.p;
-      const uint64_t npass = (((uint64_t)sx * ny + 4095u) >> 12) * ncz;  // wave passes of the scan: 4096 cubes each
-      static const int sbpc = env_int("GSDF_HIP_FLAT_SCAN_BPC", 16), lbpc = env_int("GSDF_HIP_FLAT_LIST_BPC", 6);  // tuning knobs
-      const uint64_t gmax = (uint64_t)p->num_cu * (uint64_t)(sbpc > 0 ? sbpc : 16), nwg = (npass + 3) / 4;
-      hipLaunchKernelGGL(flat_cut_scan_kernel, dim3((unsigned)(nwg < gmax ? (nwg ? nwg : 1) : gmax)), dim3(BLOCK), 0, s, (const unsigned long long*)negbits,
-                         (const unsigned long long*)nearbits, wpp, nx, ny, ncz, list, (uint64_t)m->cap, d_ctr);
-      hipLaunchKernelGGL(flat_march_list_kernel, dim3((unsigned)p->num_cu * (unsigned)(lbpc > 0 ? lbpc : 6)), dim3(BLOCK), FLATB_LDS_BYTES, s, (const float*)grid,
-                         (const unsigned long long*)list, (uint64_t)m->cap, nx, ny, c0, ox, oy, oz, res, m->d_tris, (uint64_t)m->cap, d_ctr);
+    // a cut cube has at least one triangle: a list of the triangle buffer's capacity overflows only if that does
+    if (p->flat_list.ensure((size_t)m->cap * sizeof(unsigned long long)) != hipSuccess) {
+      (void)hipGetLastError();
+      return bail(fail(GSDF_ERR_CAPACITY, "flat renderer: no device memory for the list of cut cubes"));
     }
+    unsigned long long* list = (unsigned long long*)p->flat_list.p;
+    const uint64_t npass = (((uint64_t)sx * ny + 4095u) >> 12) * ncz;  // wave passes of the scan: 4096 cubes each
+    static const int sbpc = env_int("GSDF_HIP_FLAT_SCAN_BPC", 16), lbpc = env_int("GSDF_HIP_FLAT_LIST_BPC", 6);  // tuning knobs
+    const uint64_t gmax = (uint64_t)p->num_cu * (uint64_t)(sbpc > 0 ? sbpc : 16), nwg = (npass + 3) / 4;
+    hipLaunchKernelGGL(flat_cut_scan_kernel, dim3((unsigned)(nwg < gmax ? (nwg ? nwg : 1) : gmax)), dim3(BLOCK), 0, s, (const unsigned long long*)negbits,
+                       (const unsigned long long*)nearbits, wpp, nx, ny, ncz, list, (uint64_t)m->cap, d_ctr);
+    hipLaunchKernelGGL(flat_march_list_kernel, dim3((unsigned)p->num_cu * (unsigned)(lbpc > 0 ? lbpc : 6)), dim3(BLOCK), FLATB_LDS_BYTES, s, (const float*)grid,
+                       (const unsigned long long*)list, (uint64_t)m->cap, nx, ny, c0, ox, oy, oz, res, m->d_tris, (uint64_t)m->cap, d_ctr);
     HIP_TRYM(hipGetLastError());
     HIP_TRYM(hipEventRecord(ev[3], s));
     HIP_TRYM(hipMemcpyAsync(&hc, d_ctr, sizeof(hc), hipMemcpyDeviceToHost, s));
     HIP_TRYM(hipStreamSynchronize(s));
     if (hc.overflow) {
-      // The float-stream pass keeps counting: n_tris is exact. So does the bit-plane pass as long as its cut-cube list held
-      // every cut cube (n_cut <= capacity); if not, n_cut is still exact and n_tris covers the listed cubes only: a cut cube
+      // The marching pass keeps counting: n_tris is exact as long as its cut-cube list held every cut cube
+      // (n_cut <= capacity); if not, n_cut is still exact and n_tris covers the listed cubes only: a cut cube
       // has 1 to 5 triangles (2.2 on the configs' surfaces), so room for 3 per cut cube holds the list for certain and
       // the triangles nearly always -- one more exact rerun otherwise.
       if (attempt >= 5) return bail(fail(GSDF_ERR_CAPACITY, "device triangle buffer capacity exceeded"));

@@ -1,6 +1,6 @@
 // abi_program.h -- the program handle and the launch helpers of the translation units that own kernels (abi_eval.hip,
 // abi_mesh.hip, abi_indexed.hip, abi_contour.hip) and of abi_spec.hip, which builds the handle's per-tree kernels. Include after
-// kernels_common.h: the handle's LDS arithmetic uses its constants (BLOCK, TRI_STAGE, ...).
+// kernels_common.h: the handle's LDS arithmetic uses its constants (BLOCK, ...).
 // What the handle owns frees itself (Arena, Owned, EventSet, Stream, SpecKernels below): gsdf_hip_program_destroy is `delete`.
 #pragma once
 #include <condition_variable>
@@ -69,18 +69,15 @@ struct SweepVariant {  // eval_kernel<DIM, K, W> (dim = 2 | 3); flat_grid_kernel
   std::string spec_name(const char* base, int dim = 0) const { return std::string(base) + "<" + (dim ? std::to_string(dim) + ", " : "") + std::to_string(k) + ", " + std::to_string(w) + ">"; }
   std::string short_name(const char* base, int dim = 0) const { return std::string(base) + "<" + (dim ? std::to_string(dim) + "," : "") + std::to_string(k) + "," + std::to_string(w) + ">"; }
 };
-struct LeafVariant {  // leaf_kernel<K, W> (fused) | leaf_eval_kernel<K, W, UCUBE, NTLDS, BOTH, DZ> (kernels_octree.h)
-  bool fused;
+struct LeafVariant {  // leaf_eval_kernel<K, W, UCUBE, NTLDS, BOTH, DZ> (kernels_octree.h)
   int k, w;
   bool ucube, ntlds, both, dz;
   std::string spec_name() const {
-    const std::string kw = std::to_string(k) + ", " + std::to_string(w);
-    if (fused) return "leaf_kernel<" + kw + ">";
     auto b = [](bool x) { return x ? ", true" : ", false"; };
-    return "leaf_eval_kernel<" + kw + b(ucube) + b(ntlds) + b(both) + b(dz) + ">";
+    return "leaf_eval_kernel<" + std::to_string(k) + ", " + std::to_string(w) + b(ucube) + b(ntlds) + b(both) + b(dz) + ">";
   }
   std::string short_name() const {
-    return std::string(fused ? "leaf_kernel<" : "leaf_eval_kernel<") + std::to_string(k) + "," + std::to_string(w) + (both ? ",both" : "") + (dz ? ",rows" : "") + ">";
+    return "leaf_eval_kernel<" + std::to_string(k) + "," + std::to_string(w) + (both ? ",both" : "") + (dz ? ",rows" : "") + ">";
   }
 };
 struct LeafPick { LeafVariant v; hipFunction_t f; };  // f: the handle's per-tree build of v; null: the ahead-of-time kernel of v
@@ -120,13 +117,6 @@ struct SpecKernels : SpecBuilt, SpecFns, NoCopy {
     todo.store(from.todo.load(), std::memory_order_release);
   }
 };
-
-// Leaf phase: two kernels by default (leaf_eval_kernel: evaluation + cut-leaf records, no barrier and no atomic in its
-// loop; march_records_kernel: marching cubes over the records); GSDF_HIP_FUSED_LEAF=1 keeps the fused leaf_kernel.
-inline bool fused_leaf() {
-  static const bool f = env_flag("GSDF_HIP_FUSED_LEAF");
-  return f;
-}
 
 struct gsdf_program {
   gsdf_dev::Program prog;
@@ -223,18 +213,16 @@ struct gsdf_program {
   struct LeafConfig { int k, w; size_t lds; bool ntlds; };
   LeafConfig leaf_config() const {
     static const int forced_w = env_int("GSDF_HIP_LEAF_WAVES", 0);  // tuning knob
-    const bool fused = fused_leaf();
     const int ns = prog.nslots > 0 ? prog.nslots : 1;
     const int lk = (batch_k() == 4 && ns > 11) ? 2 : batch_k();
     // The evaluating kernel needs the interpreter's columns only (8 rows at least: a brick's distances) + the 256-byte
     // triangles-per-case table, unless it is exactly that table which would cost the fourth workgroup per CU (40 rows = 40 KB): the
-    // kernel then reads the counts from the table in global memory. The fused kernel adds its stages to LEAF_MIN_COLS columns.
+    // kernel then reads the counts from the table in global memory.
     const size_t rows_e = (size_t)(ns * lk > 8 ? ns * lk : 8) * BLOCK * sizeof(float);
     const bool ntlds = !(4 * rows_e <= kLdsPerCu && 4 * (rows_e + 256) > kLdsPerCu);
-    const size_t lds = fused ? (size_t)(ns * lk > LEAF_MIN_COLS ? ns * lk : LEAF_MIN_COLS) * BLOCK * sizeof(float) + 4096 + TRI_STAGE * 36 + 64
-                             : rows_e + (ntlds ? 256 : 0);
+    const size_t lds = rows_e + (ntlds ? 256 : 0);
     int w = forced_w ? forced_w : (4 * lds <= kLdsPerCu ? 4 : 3);
-    if (lk == 4) { if (w != 2 && w != 4 && !(!fused && w == 5 && 5 * lds <= kLdsPerCu)) w = 3; }
+    if (lk == 4) { if (w != 2 && w != 4 && !(w == 5 && 5 * lds <= kLdsPerCu)) w = 3; }
     else if (lk == 2) { if (w != 4) w = 3; }
     else w = 4;
     return {lk, w, lds, ntlds};
@@ -252,11 +240,10 @@ struct gsdf_program {
     const LeafConfig c = leaf_config();
     const bool own = spec.f_leaf && spec.leaf_k == c.k;
     const int aw = leaf_aot_waves(c.k, c.w);
-    if (fused_leaf()) return own ? LeafPick{{true, c.k, spec.leaf_w, false, false, false, false}, spec.f_leaf} : LeafPick{{true, c.k, aw, false, false, false, false}, nullptr};
-    if (rows && spec.f_leaf_dz) return {{false, 4, spec.rows_w, true, c.ntlds, spec.rows_both, true}, spec.f_leaf_dz};
-    if (rows && !own) return {{false, 4, aw, true, c.ntlds, false, true}, nullptr};
-    if (own && lq == 3) return {{false, c.k, spec.leaf_w, true, c.ntlds, spec.leaf_both, false}, spec.f_leaf};
-    return {{false, c.k, aw, lq == 3, lq == 3 ? c.ntlds : true, false, false}, nullptr};
+    if (rows && spec.f_leaf_dz) return {{4, spec.rows_w, true, c.ntlds, spec.rows_both, true}, spec.f_leaf_dz};
+    if (rows && !own) return {{4, aw, true, c.ntlds, false, true}, nullptr};
+    if (own && lq == 3) return {{c.k, spec.leaf_w, true, c.ntlds, spec.leaf_both, false}, spec.f_leaf};
+    return {{c.k, aw, lq == 3, lq == 3 ? c.ntlds : true, false, false}, nullptr};
   }
   size_t lds_bytes(int k = 1) const { return (size_t)(prog.nslots > 0 ? prog.nslots : 1) * k * BLOCK * sizeof(float); }
   // The largest trees (gsdf_hip.h: "Largest trees"). A workgroup may ask for a CU's whole LDS and no more; an entry point whose
@@ -273,8 +260,10 @@ struct gsdf_program {
   int normals_refused(const char* what) const { return lds_refused(what, lds_bytes(2), std::to_string(GSDF_HIP_MAX_SLOTS_NORMALS) + " slots"); }
   static_assert((size_t)GSDF_HIP_MAX_SLOTS_NORMALS * 2 * BLOCK * sizeof(float) <= kLdsPerCu && (size_t)(GSDF_HIP_MAX_SLOTS_NORMALS + 1) * 2 * BLOCK * sizeof(float) > kLdsPerCu,
                 "gsdf_hip.h: GSDF_HIP_MAX_SLOTS_NORMALS is the largest slot count whose two points per lane fit a CU's LDS");
-  // what gsdf_hip_program_create adds to one point per lane (a brick's eight rows, the fused leaf kernel's stages)
-  static constexpr size_t kCreateExtra = 8 * BLOCK * 4 + 4096 + TRI_STAGE * 36 + 64;
+  // what gsdf_hip_program_create adds to one point per lane. Kept as it was for ABI stability (GSDF_HIP_MAX_SLOTS_CREATE is a public,
+  // tested limit): a brick's eight rows, and the 4096 + 128 * 36 + 64 bytes of triangle table, LDS triangle stage and scan words
+  // that a leaf kernel which also emitted the triangles once added; no kernel asks for more
+  static constexpr size_t kCreateExtra = 8 * BLOCK * 4 + 4096 + 128 * 36 + 64;
   static_assert((size_t)GSDF_HIP_MAX_SLOTS_CREATE * BLOCK * sizeof(float) + kCreateExtra <= kLdsPerCu && (size_t)(GSDF_HIP_MAX_SLOTS_CREATE + 1) * BLOCK * sizeof(float) + kCreateExtra > kLdsPerCu,
                 "gsdf_hip.h: GSDF_HIP_MAX_SLOTS_CREATE is the largest slot count gsdf_hip_program_create accepts");
   // dual contouring's origin sweep: the ahead-of-time builds are <4,3>, <2,3>, <1,4> (the others need scratch). One rule for the

@@ -109,10 +109,10 @@ void spec_ensure(gsdf_program* p, SpecGroup g) {
       // one-body form at the occupancy that kernel has, then at the configured one, then the two-site form at each; the first that builds
       // without scratch is taken. If none does (knurled-cylinder with hipcc 7.2: three variants of the second pass in one body want more
       // than 128 registers; at three workgroups per CU the option costs more than it saves) every row keeps going through f_leaf.
-      if (is2d || fused_leaf() || c.k != 4 || !k.f_leaf || k.leaf_k != 4) break;
+      if (is2d || c.k != 4 || !k.f_leaf || k.leaf_k != 4) break;
       auto add = [&](int w, bool b) {
         for (const SpecCand& v : cs) if (v.w == w && v.both == b) return;
-        cs.push_back({LeafVariant{false, 4, w, true, c.ntlds, b, true}.spec_name(), &k.f_leaf_dz, w, b});
+        cs.push_back({LeafVariant{4, w, true, c.ntlds, b, true}.spec_name(), &k.f_leaf_dz, w, b});
       };
       if (k.leaf_both) { add(k.leaf_w, true); add(c.w, true); }
       add(k.leaf_w, false); add(c.w, false);
@@ -122,7 +122,7 @@ void spec_ensure(gsdf_program* p, SpecGroup g) {
       if (ek != 1) cs = {{SweepVariant{1, 4}.spec_name("eval_kernel", is2d ? 2 : 3), &k.f_eval_k1}};
       break;
     case SPEC_DENSE:  // at the most workgroups per CU the LDS allows for which the compiler needs no scratch
-      for (int w = 5; w >= 3 && !is2d && !fused_leaf(); w--)
+      for (int w = 5; w >= 3 && !is2d; w--)
         if ((size_t)w * p->lds_dense() <= gsdf_program::kLdsPerCu) cs.push_back({"leaf_dense_kernel<" + std::to_string(w) + ", true, true>", &k.f_leaf_dense, w});
       break;
     case SPEC_VIEW:  // both forms; this module and the next two include their own kernel header only (specialize.cpp: spec_includes)
@@ -164,9 +164,8 @@ extern "C" int gsdf_hip_program_specialize(gsdf_program* p) {
   HIP_TRY(hipSetDevice(p->device));
   const gsdf_program::LeafConfig c = p->leaf_config();
   const int lk = c.k, lw = c.w, dim = p->prog.is2d ? 2 : 3;
-  const bool fused = fused_leaf();
   const SweepVariant ev = p->sweep_variant(p->batch_k());
-  const LeafVariant leaf{fused, lk, lw, !fused, !fused && c.ntlds, false, false};  // the configuration the mesher would pick
+  const LeafVariant leaf{lk, lw, true, c.ntlds, false, false};  // the configuration the mesher would pick
   auto leaf_with = [&](int w, bool both) { LeafVariant v = leaf; v.w = w; v.both = both; return v; };
   std::vector<std::string> names{ev.spec_name("eval_kernel", dim)};
   std::vector<LeafVariant> leaves;  // the leaf kernel's candidates: each later one that builds without scratch is preferred to the ones before it
@@ -174,7 +173,7 @@ extern "C" int gsdf_hip_program_specialize(gsdf_program* p) {
     names.push_back("prune_kernel");
     names.push_back("prune_spec_kernel");
     leaves.push_back(leaf);
-    const bool room5 = !fused && lk == 4 && lw == 4 && 5 * c.lds <= gsdf_program::kLdsPerCu;
+    const bool room5 = lk == 4 && lw == 4 && 5 * c.lds <= gsdf_program::kLdsPerCu;
     // a fifth workgroup per CU where the LDS has room for it (npt-flange's 7 slots): the 96-register build is taken if the
     // compiler reaches it without scratch (-3 % on the evaluating kernel); built beside the 128-register one, same process
     if (room5) leaves.push_back(leaf_with(5, false));
@@ -182,7 +181,7 @@ extern "C" int gsdf_hip_program_specialize(gsdf_program* p) {
     // where much of the program depends on x and y alone (an atan2, several hypots: npt-flange), -1..2 % elsewhere
     static const bool both_off = env_flag("GSDF_HIP_NO_BOTH_PASSES");  // developer knob (A/B timing)
     static const int both_min = env_int("GSDF_HIP_BOTH_MIN_WEIGHT", 0);  // developer knob. 0: always -- programs without x,y-only work gain 1-2 % too (bolt 1.029 -> 1.007 ms, knurled-cylinder 3.19 -> 3.16: one body of eight points schedules a little better than two of four)
-    if (!fused && !both_off && lk == 4 && gsdf_dev::spec_xy_shared_weight(p->prog) >= both_min) {
+    if (!both_off && lk == 4 && gsdf_dev::spec_xy_shared_weight(p->prog) >= both_min) {
       leaves.push_back(leaf_with(lw, true));
       // ... and at five workgroups per CU (96 registers) where the LDS has room: taken if it builds without scratch
       static const bool both5_off = env_flag("GSDF_HIP_NO_BOTH5");  // developer knob (A/B timing)
@@ -294,7 +293,7 @@ extern "C" int gsdf_hip_program_is_specialized(const gsdf_program* p, double* co
   return p && p->spec.specialised() ? 1 : 0;
 }
 
-/* The kernels this handle launches, e.g. "eval=eval_kernel<3,4,4>:specialised leaf=leaf_kernel<4,3>:specialised
+/* The kernels this handle launches, e.g. "eval=eval_kernel<3,4,4>:specialised leaf=leaf_eval_kernel<4,3>:specialised
  * prune=prune_kernel:specialised" (":interpreter" for the ahead-of-time kernels): what a profile of the handle shows. One cap: a
  * field is appended only while the whole text stays under 512 bytes, what the callers' buffers hold (the longest seen: 397 bytes,
  * npt-flange specialised with its distinct-rows and distinct-points kernels built, before the 27 bytes of " ray=" came behind them:
@@ -362,7 +361,7 @@ extern "C" int gsdf_hip_specialize_check(const gsdf_tree* tree, size_t* code_obj
     std::vector<std::string> low;
     std::string log;
     const std::vector<std::string> names = pr.is2d ? std::vector<std::string>{"eval_kernel<2, 4, 4>"}
-                                                   : std::vector<std::string>{"eval_kernel<3, 4, 4>", "prune_kernel", "prune_spec_kernel", "leaf_eval_kernel<4, 4, true, true, false, false>", "leaf_eval_kernel<4, 4, true, true, true, true>", "leaf_dense_kernel<4, true, true>", "leaf_kernel<4, 4>", "flat_grid_kernel<4, 4>"};
+                                                   : std::vector<std::string>{"eval_kernel<3, 4, 4>", "prune_kernel", "prune_spec_kernel", "leaf_eval_kernel<4, 4, true, true, false, false>", "leaf_eval_kernel<4, 4, true, true, true, true>", "leaf_dense_kernel<4, true, true>", "flat_grid_kernel<4, 4>"};
     if (!gsdf_dev::spec_compile(pr, "gfx950", names, co, low, log)) return fail(GSDF_ERR_HIP, "specialised build failed:\n" + log);
     if (code_object_bytes) *code_object_bytes = co.size();
     return GSDF_OK;

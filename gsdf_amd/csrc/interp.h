@@ -24,7 +24,7 @@ typedef const v4f __attribute__((address_space(4))) * f4ptr;
 struct P3 { float x, y, z; };
 
 // Lane number within the wave (mbcnt pair; `threadIdx.x & 63` is equivalent here but, measured, costs the leaf kernels
-// registers: knurled-cylinder's leaf_kernel<4,3> 168 VGPRs + 1 spill instead of 168 + 0).
+// registers: knurled-cylinder's leaf kernel of four points per lane, 168 VGPRs + 1 spill instead of 168 + 0).
 __device__ __forceinline__ uint32_t lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 
 // Slot s of point k of this lane: one float per lane per (slot, k) -> conflict-free columns.

@@ -12,16 +12,15 @@
 //   prune_kernel         octree level: centre sample, keep unless the field's bounds over the cube exclude 0
 //                        (|d| >= size*sqrt3/2 for a distance field), block-wide compaction of survivors
 //                                                                   glrender/octreerenderer.go:240-284
-//   leaf_kernel          8 leaf corners (corner 0 first, reject |d0| > 2*sqrt3*res) + marching cubes
-//                        with the LDS triangle table; triangles are built one per lane from an LDS
-//                        owner list (mc_emit_balanced), staged in LDS and flushed coalesced
+//   leaf_eval_kernel, march_records_kernel
+//                        8 leaf corners (corner 0 first, reject |d0| > 2*sqrt3*res), the cut leaves left as records;
+//                        marching cubes over the records, one triangle per lane from an LDS owner list
 //                                                                   glrender/marchcubes.go:14-98
 //   flat_grid_kernel     SDF on every corner of the flat lattice    glrender/flatrenderer.go:103-182
 //                        (+ two bits per corner: d < 0, |d| <= 2 sqrt3 res)
 //   flat_cut_scan_kernel, flat_march_list_kernel
 //                        marching cubes of every lattice cube: cut cubes found from the bit planes, listed, marched
 //                                                                   glrender/flatrenderer.go:186-256
-//   flat_march_kernel    the same from the float grid alone (GSDF_HIP_FLAT_STREAM=1; rounds 1-2)
 //   dc_*_kernel          dual contouring stages                     glrender/dual_contour*.go
 //   stl_kernel           50-byte STL records staged through LDS     glrender/stl.go:15-62
 //   normals_kernel       central differences                        gleval/gleval.go:53-108

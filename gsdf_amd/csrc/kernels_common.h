@@ -9,8 +9,6 @@ using gsdf_dev::code_ptr;
 using gsdf_dev::P3;
 
 #define BLOCK 256
-#define LEAF_MIN_COLS 14  // leaf_kernel's LDS columns per lane: 8 corner distances + 3 origin + 3 for the owner list / cube indices
-#define TRI_STAGE 128  // triangles staged in LDS per workgroup before one coalesced flush (4.5 KB: lets 4 workgroups of a 7-slot program share a CU)
 
 // ---------------------------------------------------------------------------------------------
 // device side
@@ -36,7 +34,7 @@ struct MeshCounters {
   unsigned long long overflow;             // triangle buffer overflow flag
   unsigned long long n_cont;               // leaves whose wave went on to the remaining corners
   unsigned long long q_overflow;           // cube queue capacity exceeded
-  unsigned long long n_points;             // lattice points evaluated by leaf_brick_kernel
+  unsigned long long n_points;             // distinct z rows / lattice points evaluated (the distinct-row and dense forms of the leaf phase)
   unsigned long long n_cut;                // leaves the surface cuts (records written by leaf_eval_kernel)
 };
 

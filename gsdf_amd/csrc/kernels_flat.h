@@ -1,6 +1,6 @@
 // kernels_flat.h -- glrender.FlatRenderer on device (glrender/flatrenderer.go:36-256): the lattice pass and the marching passes.
 #pragma once
-#include "kernels_octree.h"  // marching-cubes emission helpers, record layout
+#include "kernels_octree.h"  // mc_interp, record layout
 
 // =================================================================================================
 // FlatRenderer on device (glrender/flatrenderer.go): the SDF on every corner of the (nx+1)(ny+1)(nz+1) lattice into a
@@ -12,8 +12,8 @@
 // its K points enter the evaluator with bitwise equal x,y (COLUMN mode: every hypot/atan2 of x,y is computed once per
 // lane, not once per point); a workgroup pass covers BLOCK columns of one group of K planes, and stores stay coalesced
 // (consecutive lanes = consecutive columns of a plane). (i,j) comes from one division per lane and pass.
-// Rows of the distance grid start on a 256-byte boundary (pitch = sx rounded up to 64 floats): flat_march_kernel's row loads
-// (64 lanes x 4 B) then cover two 128-byte lines instead of straddling three.
+// Rows of the distance grid start on a 256-byte boundary (pitch = sx rounded up to 64 floats): a wave's row load
+// (64 lanes x 4 B) then covers two 128-byte lines instead of straddling three.
 #define FLAT_PITCH(sx) (((sx) + 63u) & ~63u)
 template <int K, int W = 3>
 __global__ void __launch_bounds__(BLOCK, W) flat_grid_kernel(const uint32_t* __restrict__ code_g, float ox, float oy, float oz, float res,
@@ -58,34 +58,16 @@ __global__ void __launch_bounds__(BLOCK, W) flat_grid_kernel(const uint32_t* __r
 }
 
 #ifndef GSDF_SPECIALIZED
-// flat_march_kernel (GSDF_HIP_FLAT_STREAM=1; the default marching pass is flat_cut_scan_kernel + flat_march_list_kernel
-// below): marching cubes of every cube of the lattice from the distance grid (FlatRenderer.ReadTriangles,
-// glrender/flatrenderer.go:186-256). HBM-bound by design: 4 B per lattice corner in, 36 B per triangle out. Round 2:
-// every WAVE on its own -- no workgroup barrier and no shared stage in the loop (round 1's kernel had one barrier per
-// pass and its waves waited 68 % of their cycles at 32 % of the HBM peak).
-//   * a wave pass = FLAT_TX consecutive x cubes x FLAT_ROWS rows at one z: corner 0 of the rows per lane, prefetched two
-//     passes ahead; the other corners only in waves where some lane passes the reference's |d0| <= 2*sqrt3*res test
-//     (:207-209) -- ~85 % of the passes end there -- and then from the neighbouring lanes / rows and one batch of ten loads;
-//   * cubes the surface cuts are appended (ballot rank) as records -- 8 distances, cube coordinates, case index -- to a
-//     buffer of FLAT_WAVE_RECS records in LDS that only this wave touches;
-//   * when the buffer cannot take another row (> FLAT_WAVE_RECS - 64 records) the wave marches it: triangle counts per
-//     record from the LDS table, exclusive prefix from three ballots, ONE global atomic for the whole flush (~350
-//     triangles: ~20 K atomics per mesh, well under the ~88 per microsecond a counter word takes), then every lane builds
-//     its record's triangles and stores them at their final address.
-// LDS: [tri table 4 KB (row byte 15 = triangle count) | 4 x FLAT_WAVE_RECS x 10 words | 4 x 5 FLAT_WAVE_RECS u16 owner lists].
-#define FLAT_ROWS 8        // cube rows of a pass
-#define FLAT_TX 63         // cube columns of a pass (lane 63 supplies the last x + 1 neighbour)
-#define FLAT_WAVE_RECS 160  // records per wave buffer (8 KB per wave with the owner list: four workgroups per CU)
-// marching cubes of the buffered records, wave-local and balanced: an owner list (triangle -> record, number) from the
-// ballot prefix sums, then ONE OUTPUT VERTEX PER LANE -- every lane busy, a wave store = 768 contiguous bytes (the first
-// version built each record's triangles in its own lane: 2.2 triangles on average, 5 at most, three divisions each, and
-// 36-byte pieces scattered per lane: that, not memory, was most of the 0.39 ms the active passes cost)
-// KNOWN: the first triangle's index is given (`known`, wave-uniform) instead of taken from the append counter.
-// Returns the number of triangles of the records.
-template <int RECS, bool KNOWN = false>
+// Marching cubes of a wave's buffered records (buf: [REC_WORDS][RECS] words in LDS that only this wave touches -- 8 distances,
+// cube x | y << 16, cube z | case index << 16; s_tri: the triangle table, row byte 15 = triangle count), wave-local and
+// balanced: an owner list (triangle -> record, number) from the ballot prefix sums, then ONE OUTPUT VERTEX PER LANE -- every
+// lane busy, a wave store = 768 contiguous bytes (building each record's triangles in its own lane means 2.2 triangles on
+// average, 5 at most, three divisions each, and 36-byte pieces scattered per lane).
+// gbase (wave-uniform): the index of the records' first triangle. Returns the number of triangles of the records.
+template <int RECS>
 __device__ __forceinline__ unsigned flat_flush_wave(uint32_t* buf, uint16_t* own, const int8_t* s_tri, unsigned& cnt, unsigned lane, float ox, float oy,
                                                     float oz, float res, float* __restrict__ tris, uint64_t tri_cap, MeshCounters* __restrict__ ctr,
-                                                    unsigned long long known = 0ull) {
+                                                    unsigned long long gbase) {
   auto below = [](unsigned long long m) { return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u)); };
   if (cnt == 0) return 0u;
   unsigned total = 0;
@@ -98,12 +80,7 @@ __device__ __forceinline__ unsigned flat_flush_wave(uint32_t* buf, uint16_t* own
     for (unsigned k = 0; k < nt; k++) own[first + k] = (uint16_t)(i | (k << 8));
     total += (unsigned)__builtin_popcountll(q0) + 2u * (unsigned)__builtin_popcountll(q1) + 4u * (unsigned)__builtin_popcountll(q2);
   }
-  unsigned long long gbase = known;
-  if (!KNOWN) {
-    if (lane == 0) gbase = atomicAdd(&ctr->n_tris, (unsigned long long)total);
-    gbase = uniform_u64(gbase);
-  }
-  if (gbase + total > tri_cap) {  // wave-uniform: the counter keeps counting, the host learns the exact size and reruns
+  if (gbase + total > tri_cap) {  // wave-uniform: the host learns the exact size from the counters and reruns
     if (lane == 0) ctr->overflow = 1ull;
     cnt = 0;
     return total;
@@ -119,7 +96,7 @@ __device__ __forceinline__ unsigned flat_flush_wave(uint32_t* buf, uint16_t* own
     const uint32_t xy = buf[8 * RECS + i], zi = buf[9 * RECS + i];
     const int e = s_tri[(zi >> 16) * 16 + 3u * k + (2u - j)];  // reversed winding (marchcubes.go:64-68)
     const unsigned ca = GSDF_MC_PAIR_A(e), cb = GSDF_MC_PAIR_B(e);
-    // cube origin exactly as the fused round-1 kernel formed it: o + (float)index * res
+    // cube origin: o + (float)index * res
     const float x0 = ox + (float)(xy & 0xffffu) * res, y0 = oy + (float)(xy >> 16) * res, z0 = oz + (float)(zi & 0xffffu) * res;
     const float x1 = x0 + res, y1 = y0 + res, z1 = z0 + res;
     const bool ax = ((ca ^ (ca >> 1)) & 1u) != 0u, ay = ((ca >> 1) & 1u) != 0u, az = ((ca >> 2) & 1u) != 0u;
@@ -139,141 +116,13 @@ __device__ __forceinline__ unsigned flat_flush_wave(uint32_t* buf, uint16_t* own
   return total;
 }
 
-__global__ void __launch_bounds__(BLOCK, 4) flat_march_kernel(const float* __restrict__ grid, unsigned nx, unsigned ny, unsigned ncz,
-                                                           unsigned czfirst, float ox, float oy, float oz, float res,
-                                                           float* __restrict__ tris, uint64_t tri_cap, MeshCounters* __restrict__ ctr) {
-  int8_t* s_tri = (int8_t*)g_smem;
-  uint32_t* buf = (uint32_t*)(s_tri + 256 * 16) + (threadIdx.x >> 6) * (FLAT_WAVE_RECS * REC_WORDS);  // [REC_WORDS][FLAT_WAVE_RECS], this wave's
-  uint16_t* own = (uint16_t*)((uint32_t*)(s_tri + 256 * 16) + 4 * FLAT_WAVE_RECS * REC_WORDS) + (threadIdx.x >> 6) * (5 * FLAT_WAVE_RECS);  // this wave's owner list
-  for (int k = threadIdx.x; k < 256 * 16; k += BLOCK) s_tri[k] = (k & 15) == 15 ? (int8_t)GSDF_MC_NTRI[k >> 4] : GSDF_MC_TRI[k >> 4][k & 15];
-  __syncthreads();
-  const unsigned sx = FLAT_PITCH(nx + 1);  // row pitch
-  const uint64_t sxy = (uint64_t)sx * (ny + 1);
-  const unsigned lane = threadIdx.x & 63u;
-  const unsigned txn = (nx + FLAT_TX - 1) / FLAT_TX, tyn = (ny + FLAT_ROWS - 1) / FLAT_ROWS;
-  const unsigned npass = txn * tyn * ncz;  // wave passes, < 2^32 (host checks)
-  const float cubeDiag = 2 * 1.73205080757f * res;  // marchcubes.go:19 / flatrenderer.go:207
-  unsigned my_active = 0;  // wave-uniform
-  unsigned cnt = 0;        // records in this wave's buffer (wave-uniform)
-  auto below = [](unsigned long long m) { return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u)); };
-
-  auto flush = [&]() { (void)flat_flush_wave<FLAT_WAVE_RECS>(buf, own, s_tri, cnt, lane, ox, oy, oz, res, tris, tri_cap, ctr); };
-
-  auto pass_coords = [&](unsigned w, unsigned& tx, unsigned& ty, unsigned& cz) {
-    const unsigned wr = w / txn;
-    tx = w - wr * txn;
-    cz = wr / tyn;
-    ty = wr - cz * tyn;
-  };
-  // (lane 63 of a tile holds the x + 1 neighbours of lane 62's cubes and owns none itself: tiles are FLAT_TX = 63 cubes wide)
-  auto load_d0 = [&](unsigned tx, unsigned ty, unsigned cz, float (&d0)[FLAT_ROWS]) {
-    const unsigned cx = tx * FLAT_TX + lane, cy0 = ty * FLAT_ROWS;
-    const float* g0 = grid + (uint64_t)cz * sxy + (uint64_t)cy0 * sx + cx;
-#pragma unroll
-    for (int r = 0; r < FLAT_ROWS; r++) d0[r] = (cx <= nx && cy0 + (unsigned)r <= ny) ? g0[(uint64_t)r * sx] : __builtin_inff();
-  };
-  const unsigned wid = blockIdx.x * 4u + (threadIdx.x >> 6), wstride = gridDim.x * 4u;
-  // corner 0 of the next TWO passes is in flight while a pass is examined: with one (round 2's first version) a wave had
-  // 2 KB outstanding, 12 waves per CU (166 registers: the seven other corners of all eight rows were loaded together) --
-  // a quarter of what 8 TB/s needs at ~2 us per trip. Now 4 KB per wave at 16 waves per CU.
-  float dn1[FLAT_ROWS], dn2[FLAT_ROWS];
-  unsigned t1x = 0, t1y = 0, t1z = 0, t2x = 0, t2y = 0, t2z = 0;
-#pragma unroll
-  for (int r = 0; r < FLAT_ROWS; r++) dn1[r] = dn2[r] = __builtin_inff();
-  if (wid < npass) {
-    pass_coords(wid, t1x, t1y, t1z);
-    load_d0(t1x, t1y, t1z, dn1);
-  }
-  if ((uint64_t)wid + wstride < npass) {
-    pass_coords(wid + wstride, t2x, t2y, t2z);
-    load_d0(t2x, t2y, t2z, dn2);
-  }
-  for (unsigned w = wid; w < npass; w += wstride) {  // wave-uniform
-    const unsigned tx = t1x, ty = t1y, cz = t1z;
-    const unsigned cx = tx * FLAT_TX + lane, cy0 = ty * FLAT_ROWS;
-    const bool cube_x = lane < FLAT_TX && cx < nx;  // this lane owns a cube column
-    const float* g0 = grid + (uint64_t)cz * sxy + (uint64_t)cy0 * sx + cx;
-    float d0[FLAT_ROWS];
-    bool any_act = false;
-#pragma unroll
-    for (int r = 0; r < FLAT_ROWS; r++) {
-      d0[r] = dn1[r];
-      dn1[r] = dn2[r];
-      any_act = any_act || (cube_x && cy0 + (unsigned)r < ny && nb::abs_le(d0[r], cubeDiag));
-    }
-    t1x = t2x; t1y = t2y; t1z = t2z;
-    if ((uint64_t)w + 2ull * wstride < npass) {
-      pass_coords(w + 2u * wstride, t2x, t2y, t2z);
-      load_d0(t2x, t2y, t2z, dn2);
-    }
-    if (__ballot(any_act) == 0ull) continue;  // wave-uniform
-#ifdef GSDF_EXP_FLAT_STREAM_ONLY  // developer experiment: the streaming read of corner 0 alone (timing only)
-    my_active += 1u;
-    continue;
-#endif
-    // The other seven corners of the active cubes. Three of them are in registers already -- x + 1 is the next lane, y + 1
-    // the lane's next row -- and the plane above is fetched as nine rows at once: ONE trip to memory per active pass (the
-    // first version fetched seven corners per active row, two rows at a time: four trips in a row, 0.27 ms of the
-    // kernel's 0.74).
-    const bool corner_x = cx <= nx;
-    float up[FLAT_ROWS + 1];  // plane z + 1, rows 0..8
-#pragma unroll
-    for (int r = 0; r <= FLAT_ROWS; r++) up[r] = (corner_x && cy0 + (unsigned)r <= ny) ? g0[sxy + (uint64_t)r * sx] : __builtin_inff();
-    const float d8 = (corner_x && cy0 + FLAT_ROWS <= ny) ? g0[(uint64_t)FLAT_ROWS * sx] : __builtin_inff();  // plane z, row 8
-#pragma unroll
-    for (int r = 0; r < FLAT_ROWS; r++) {
-      const bool act = cube_x && cy0 + (unsigned)r < ny && nb::abs_le(d0[r], cubeDiag);  // the reference's |d0| <= 2*sqrt3*res test (:207-209)
-      const unsigned long long am = __ballot(act);
-      if (am == 0ull) continue;  // wave-uniform
-      my_active += (unsigned)__builtin_popcountll(am);
-      const float c3 = r + 1 < FLAT_ROWS ? d0[r + 1 < FLAT_ROWS ? r + 1 : 0] : d8;
-      const float c1 = __shfl_down(d0[r], 1, 64), c2 = __shfl_down(c3, 1, 64);
-      const float c4 = up[r], c7 = up[r + 1], c5 = __shfl_down(c4, 1, 64), c6 = __shfl_down(c7, 1, 64);
-      unsigned ix = 0;
-      if (act) {
-        ix = (nb::lt0(d0[r]) ? 1u : 0u) | (nb::lt0(c1) ? 2u : 0u) | (nb::lt0(c2) ? 4u : 0u) | (nb::lt0(c3) ? 8u : 0u) | (nb::lt0(c4) ? 16u : 0u) |
-             (nb::lt0(c5) ? 32u : 0u) | (nb::lt0(c6) ? 64u : 0u) | (nb::lt0(c7) ? 128u : 0u);
-        if (ix == 255u) ix = 0u;
-      }
-      const unsigned long long cm = __ballot(ix != 0u);
-      if (cm == 0ull) continue;  // wave-uniform
-      if (cnt + 64u > FLAT_WAVE_RECS) flush();  // room for a whole row
-      if (ix) {
-        const unsigned pos = cnt + below(cm);
-        buf[0 * FLAT_WAVE_RECS + pos] = __float_as_uint(d0[r]);
-        buf[1 * FLAT_WAVE_RECS + pos] = __float_as_uint(c1);
-        buf[2 * FLAT_WAVE_RECS + pos] = __float_as_uint(c2);
-        buf[3 * FLAT_WAVE_RECS + pos] = __float_as_uint(c3);
-        buf[4 * FLAT_WAVE_RECS + pos] = __float_as_uint(c4);
-        buf[5 * FLAT_WAVE_RECS + pos] = __float_as_uint(c5);
-        buf[6 * FLAT_WAVE_RECS + pos] = __float_as_uint(c6);
-        buf[7 * FLAT_WAVE_RECS + pos] = __float_as_uint(c7);
-        buf[8 * FLAT_WAVE_RECS + pos] = cx | ((cy0 + (unsigned)r) << 16);
-        buf[9 * FLAT_WAVE_RECS + pos] = (czfirst + cz) | (ix << 16);
-      }
-      cnt += (unsigned)__builtin_popcountll(cm);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    }
-  }
-  flush();
-  // statistics: one atomic per workgroup
-  __syncthreads();
-  unsigned* s_stat = (unsigned*)(s_tri + 256 * 16);
-  if (lane == 0) s_stat[threadIdx.x >> 6] = my_active;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned long long a = (unsigned long long)s_stat[0] + s_stat[1] + s_stat[2] + s_stat[3];
-    if (a) atomicAdd(&ctr->n_active, a);
-  }
-}
-
 // The marching pass driven by the two bit planes flat_grid_kernel leaves beside the grid -- "distance < 0" and
 // "|distance| <= 2*sqrt3*res" per lattice corner, bit (i + sx*j) of plane k in words of 64. Which cubes the surface cuts (the
 // reference's corner-0 test, then a case index other than 0 and 255: flatrenderer.go:207-225, marchcubes.go:20-40), and with
 // which case index, is a matter of eight shifted copies of the sign words: one LANE decides 64 cubes with a few dozen integer
 // instructions and 72 bytes of loads, and only for the cubes that are cut (0.7 % at npt-flange resdiv 1600) are the eight
-// distances fetched from the grid -- 1/32 of the bytes flat_march_kernel streams for the same decisions on the same
-// comparisons. Two kernels, like the octree's leaf phase, because cut cubes come in slabs (a machined face parallel to a
+// distances fetched from the grid -- 1/32 of the bytes a pass that streams the float grid reads for the same decisions on the
+// same comparisons. Two kernels, like the octree's leaf phase, because cut cubes come in slabs (a machined face parallel to a
 // lattice plane cuts every cube of it) and because a counter word takes only ~88 returning atomics per microsecond:
 //   flat_cut_scan_kernel   a wave pass = 64 words = 4096 consecutive cubes (corner order, rows run on) of one plane. A
 //                          workgroup walks its passes twice: once counting cut cubes (a popcount), then -- after ONE atomic
@@ -282,7 +131,7 @@ __global__ void __launch_bounds__(BLOCK, 4) flat_march_kernel(const float* __res
 //   flat_march_list_kernel the list in equal shares. A wave first adds up the triangles of its entries (count table in LDS)
 //                          and reserves them with ONE atomic, then takes 64 cut cubes per trip to memory, one output vertex
 //                          per lane, its triangles back to back: no atomic, no barrier in the loop.
-// (Measured on the way, npt-flange resdiv 1600 / 400, where flat_march_kernel takes 0.63 / 0.08 ms: one kernel doing both,
+// (Measured on the way, npt-flange resdiv 1600 / 400, where a pass that streams the float grid takes 0.63 / 0.08 ms: one kernel doing both,
 // one atomic per flush: 0.56 / 0.18 ms -- a wave that draws a pass inside a face has 4096 cubes to march, 64 dependent trips,
 // while its neighbours have none; scan + list kernels with one atomic per pass and per flush: 1.22 / 0.08 ms -- over 100 K atomics
 // on two words inside 0.1 ms of work; triangle offsets fixed by the scan, three per-lane loops with a table lookup per cut
@@ -503,7 +352,7 @@ __global__ void __launch_bounds__(BLOCK, 6) flat_march_list_kernel(const float* 
     }
     cnt = here;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    base += flat_flush_wave<FLATB_RECS, true>(buf, own, s_tri, cnt, lane, ox, oy, oz, res, tris, tri_cap, ctr, base);
+    base += flat_flush_wave<FLATB_RECS>(buf, own, s_tri, cnt, lane, ox, oy, oz, res, tris, tri_cap, ctr, base);
     cur = nxt;
   }
 }

@@ -1,6 +1,6 @@
 // kernels_octree.h -- the octree mesher: centre tests of the cube levels (prune_kernel; the speculative top: prune_spec_kernel +
-// prune_resolve_kernel), the leaf phase (leaf_eval_kernel -> cut-leaf records -> march_records_kernel; the fused leaf_kernel and
-// the corner-sharing leaf_brick_kernel) and the marching-cubes emission helpers the flat renderer's kernels use too.
+// prune_resolve_kernel), the leaf phase (leaf_eval_kernel -> cut-leaf records -> march_records_kernel) and the marching-cubes
+// interpolation the flat renderer's kernels use too.
 //   glrender/octreerenderer.go:43-284, glrender/marchcubes.go:14-98
 #pragma once
 #include "kernels_common.h"
@@ -300,346 +300,14 @@ __device__ __forceinline__ void mc_interp(float ax, float ay, float az, float bx
   rx = x; ry = y; rz = z;
 }
 
-// (LEAF_MIN_COLS and TRI_STAGE, which the host's LDS arithmetic needs too, are in kernels_common.h)
-
-// Marching cubes of one leaf per lane + block-wide triangle emission (shared by both leaf kernels).
-// vslot: the lane's 8 corner distances in its LDS column; index: the 8-bit inside mask (0 = no triangles).
-// Block-uniform control flow: every thread of the workgroup must call this the same number of times.
-template <int STAGE = TRI_STAGE, typename CornerDist>
-__device__ __forceinline__ void mc_emit_block(unsigned index, float x0, float y0, float z0, float x1, float y1, float z1,
-                                              CornerDist vdist, const int8_t* s_tri, float* s_stage, unsigned* s_misc,
-                                              unsigned long long* s_base, float* __restrict__ tris, uint64_t tri_cap,
-                                              MeshCounters* __restrict__ ctr) {
-  const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  unsigned nt = 0;
-  {
-    const int8_t* row = s_tri + index * 16;
-    while (nt < 5 && row[3 * nt] >= 0) nt++;
-  }
-  // block exclusive scan of nt: wave scan + 4 wave totals through LDS
-  unsigned incl = nt;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    unsigned v = __shfl_up(incl, off, 64);
-    if (lane >= (unsigned)off) incl += v;
-  }
-  if (lane == 63) s_misc[wave] = incl;
-  __syncthreads();  // (A)
-  const unsigned w0 = s_misc[0], w1 = s_misc[1], w2 = s_misc[2], w3 = s_misc[3];
-  const unsigned total = w0 + w1 + w2 + w3;
-  const unsigned wpre = (wave > 0 ? w0 : 0u) + (wave > 1 ? w1 : 0u) + (wave > 2 ? w2 : 0u);
-  unsigned cur = s_misc[4];
-  const bool direct = total > STAGE;  // block-uniform
-  unsigned long long gbase = 0;
-  if (!direct && cur + total > STAGE) {  // flush the stage first (block-uniform)
-    if (threadIdx.x == 0) *s_base = atomicAdd(&ctr->n_tris, (unsigned long long)cur);
-    __syncthreads();
-    const unsigned long long fb = *s_base;
-    if (fb + cur <= tri_cap) {
-      float* dst = tris + fb * 9;
-      for (unsigned k = threadIdx.x; k < cur * 9; k += BLOCK) dst[k] = s_stage[k];
-    } else if (threadIdx.x == 0) {
-      ctr->overflow = 1ull;
-    }
-    __syncthreads();
-    cur = 0;
-  }
-  if (direct) {
-    if (threadIdx.x == 0) *s_base = atomicAdd(&ctr->n_tris, (unsigned long long)total);
-    __syncthreads();
-    gbase = *s_base;
-    if (gbase + total > tri_cap) {
-      if (threadIdx.x == 0) ctr->overflow = 1ull;
-      nt = 0;
-    }
-  }
-  if (nt) {
-    const unsigned first = wpre + (incl - nt);
-    float* dst = direct ? (tris + (gbase + first) * 9) : (s_stage + (size_t)(cur + first) * 9);
-    const int8_t* row = s_tri + index * 16;
-    for (unsigned t = 0; t < nt; t++) {
-#pragma unroll
-      for (int k = 0; k < 3; k++) {
-        const int e = row[3 * t + (2 - k)];  // reversed winding (marchcubes.go:64-68)
-        const unsigned a = GSDF_MC_PAIR_A(e), b = GSDF_MC_PAIR_B(e);
-        const float va = vdist(a), vb = vdist(b);
-        const float pax = ((a ^ (a >> 1)) & 1u) ? x1 : x0, pay = ((a >> 1) & 1u) ? y1 : y0, paz = ((a >> 2) & 1u) ? z1 : z0;
-        const float pbx = ((b ^ (b >> 1)) & 1u) ? x1 : x0, pby = ((b >> 1) & 1u) ? y1 : y0, pbz = ((b >> 2) & 1u) ? z1 : z0;
-        float rx, ry, rz;
-        mc_interp(pax, pay, paz, pbx, pby, pbz, va, vb, rx, ry, rz);
-        dst[9 * t + 3 * k + 0] = rx;
-        dst[9 * t + 3 * k + 1] = ry;
-        dst[9 * t + 3 * k + 2] = rz;
-      }
-    }
-  }
-  __syncthreads();  // (B)
-  if (threadIdx.x == 0 && !direct) s_misc[4] = cur + total;
-}
-
-// Final flush of the LDS triangle stage (all threads of the workgroup).
-__device__ __forceinline__ void mc_final_flush(float* s_stage, unsigned* s_misc, unsigned long long* s_base,
-                                               float* __restrict__ tris, uint64_t tri_cap, MeshCounters* __restrict__ ctr) {
-  __syncthreads();
-  const unsigned cur = s_misc[4];
-  if (cur) {
-    if (threadIdx.x == 0) *s_base = atomicAdd(&ctr->n_tris, (unsigned long long)cur);
-    __syncthreads();
-    const unsigned long long fb = *s_base;
-    if (fb + cur <= tri_cap) {
-      float* dst = tris + fb * 9;
-      for (unsigned k = threadIdx.x; k < cur * 9; k += BLOCK) dst[k] = s_stage[k];
-    } else if (threadIdx.x == 0) {
-      ctr->overflow = 1ull;
-    }
-  }
-}
-
-
-// Balanced marching-cubes emission of one workgroup pass: ONE TRIANGLE PER LANE instead of one cube per lane.
-// Every lane brings NC cubes (index[c] = 8-bit inside mask; 0 and 255 give no triangles). The block prefix sum of the
-// per-cube triangle counts gives every triangle a slot; the cubes write an owner list (cube id = c*BLOCK + thread,
-// triangle number) into LDS, and lane t builds triangle t from its owner's data: corner(id, 0..7) = corner distances,
-// origin(id, x0, y0, z0) = min corner (max corner = min + res, as Box{origin, origin+size}). With ~1 cube in 5 cut by
-// the surface and up to five triangles per cube, the cube-per-lane loop of mc_emit_block keeps a wave busy for five
-// rounds on behalf of a few lanes; here all lanes work for ceil(total/BLOCK) rounds.
-// Triangles are staged in LDS (`cur` = staged count: block-uniform, held in a register by every thread) and flushed
-// coalesced with ONE append on the global counter per STAGE triangles.
-// Block-uniform control flow: every thread of the workgroup calls this together. Ends with a barrier, so the caller
-// may overwrite whatever corner()/origin() read. LDS: s_owner[5*BLOCK*NC] u16, s_index[BLOCK*NC] u8.
-template <int STAGE>
-__device__ __forceinline__ void mc_stage_flush(float* s_stage, unsigned long long* s_base, unsigned& cur, float* __restrict__ tris,
-                                               uint64_t tri_cap, MeshCounters* __restrict__ ctr) {
-#ifdef GSDF_EXP_NO_FLUSH  // developer experiment: emission without the global append (timing only)
-  __syncthreads();
-  cur = 0;
-  return;
-#endif
-  if (threadIdx.x == 0) *s_base = atomicAdd(&ctr->n_tris, (unsigned long long)cur);
-  __syncthreads();
-  const unsigned long long fb = *s_base;
-  if (fb + cur <= tri_cap) {
-    float* dst = tris + fb * 9;
-    for (unsigned k = threadIdx.x; k < cur * 9; k += BLOCK) dst[k] = s_stage[k];
-  } else if (threadIdx.x == 0) {
-    ctr->overflow = 1ull;  // the counter keeps counting: the host learns the exact size and reruns
-  }
-  __syncthreads();
-  cur = 0;
-}
-
-template <int NC, int STAGE, typename Corner, typename Origin>
-__device__ __forceinline__ void mc_emit_balanced(const unsigned (&index)[NC], uint16_t* s_owner, uint8_t* s_index, const int8_t* s_tri,
-                                                 float* s_stage, unsigned* s_misc, unsigned long long* s_base, unsigned& cur,
-                                                 float res, Corner corner, Origin origin, float* __restrict__ tris, uint64_t tri_cap,
-                                                 MeshCounters* __restrict__ ctr) {
-  constexpr unsigned ID_BITS = NC == 1 ? 8 : (NC == 2 ? 9 : (NC <= 4 ? 10 : 11));
-  static_assert(NC <= 8, "owner entries are 16 bits: 3 bits of triangle number + 11 bits of cube id");
-  const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  unsigned nt[NC], ntl = 0;
-#pragma unroll
-  for (int c = 0; c < NC; c++) {
-    unsigned n = 0;
-    if (index[c]) {  // row 0 is empty anyway; saves the LDS walk for the common case
-      const int8_t* row = s_tri + index[c] * 16;
-      while (n < 5 && row[3 * n] >= 0) n++;
-    }
-    nt[c] = n;
-    ntl += n;
-  }
-  if (!__syncthreads_or((int)ntl)) return;  // no triangles anywhere in this pass (block-uniform)
-  unsigned incl = ntl;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const unsigned u = __shfl_up(incl, off, 64);
-    if (lane >= (unsigned)off) incl += u;
-  }
-  if (lane == 63) s_misc[wave] = incl;
-  __syncthreads();
-  // block-uniform values read back from LDS: pin them to SGPRs (the compiler cannot know they are uniform)
-  const unsigned w0 = __builtin_amdgcn_readfirstlane(s_misc[0]), w1 = __builtin_amdgcn_readfirstlane(s_misc[1]),
-                 w2 = __builtin_amdgcn_readfirstlane(s_misc[2]), w3 = __builtin_amdgcn_readfirstlane(s_misc[3]);
-  const unsigned total = w0 + w1 + w2 + w3;
-  const unsigned wave_u = __builtin_amdgcn_readfirstlane(wave);
-  unsigned first = (wave_u > 0 ? w0 : 0u) + (wave_u > 1 ? w1 : 0u) + (wave_u > 2 ? w2 : 0u) + (incl - ntl);
-#pragma unroll
-  for (int c = 0; c < NC; c++) {
-    if (nt[c]) {
-      const unsigned id = (unsigned)c * BLOCK + threadIdx.x;
-      s_index[id] = (uint8_t)index[c];
-      for (unsigned k = 0; k < nt[c]; k++) s_owner[first + k] = (uint16_t)(id | (k << ID_BITS));
-      first += nt[c];
-    }
-  }
-  __syncthreads();
-  for (unsigned done = 0; done < total;) {  // block-uniform
-    const unsigned room = STAGE - cur, left = total - done;
-    const unsigned n = left < room ? left : room;
-#ifndef GSDF_EXP_NO_BUILD  // developer experiment: emission without building the triangles (timing only)
-    for (unsigned t = threadIdx.x; t < n; t += BLOCK) {
-      const unsigned o = s_owner[done + t];
-      const unsigned k = o >> ID_BITS, id = o & ((1u << ID_BITS) - 1u);
-      float x0, y0, z0;
-      origin(id, x0, y0, z0);
-      const float x1 = x0 + res, y1 = y0 + res, z1 = z0 + res;
-      const int8_t* row = s_tri + (unsigned)s_index[id] * 16 + 3 * k;
-      float* dst = s_stage + (size_t)(cur + t) * 9;
-#pragma unroll
-      for (int j = 0; j < 3; j++) {
-        const int e = row[2 - j];  // reversed winding (marchcubes.go:64-68)
-        const unsigned ca = GSDF_MC_PAIR_A(e), cb = GSDF_MC_PAIR_B(e);
-        const bool ax = ((ca ^ (ca >> 1)) & 1u) != 0u, ay = ((ca >> 1) & 1u) != 0u, az = ((ca >> 2) & 1u) != 0u;
-        const bool bx = ((cb ^ (cb >> 1)) & 1u) != 0u, by = ((cb >> 1) & 1u) != 0u, bz = ((cb >> 2) & 1u) != 0u;
-        float rx, ry, rz;
-        mc_interp(ax ? x1 : x0, ay ? y1 : y0, az ? z1 : z0, bx ? x1 : x0, by ? y1 : y0, bz ? z1 : z0, corner(id, ca), corner(id, cb),
-                  rx, ry, rz);
-        dst[3 * j + 0] = rx;
-        dst[3 * j + 1] = ry;
-        dst[3 * j + 2] = rz;
-      }
-    }
-#endif
-    cur += n;
-    done += n;
-    __syncthreads();
-    if (cur == STAGE) mc_stage_flush<STAGE>(s_stage, s_base, cur, tris, tri_cap, ctr);
-  }
-}
-
-// Leaf kernel: one lane per leaf cube of every surviving level-lq cube (64 leaves of a level-3 cube
-// = one wave). Corner 0 first; the wave runs the other 7 corners only if some lane passes the
-// reference's |d0| <= 2*sqrt3*res test (marchcubes.go:20-23). Marching cubes reads the triangle
-// table from LDS; triangles are staged in LDS and flushed with ONE global atomic per flush
-// (a single counter word saturates at ~88 atomics/us on MI355X, so per-wave appends do not scale).
-// LDS: [max(nslots*K, LEAF_MIN_COLS) floats per lane | tri table 256x16 i8 | TRI_STAGE*9 floats | 8 words]. The lane's 8 corner
-// distances reuse the interpreter's slot columns: the distances of the earlier passes ride in registers until the
-// last pass has finished with the slots, then all 8 are stored for marching cubes' dynamically indexed reads.
-template <int K, int WAVES>
-__global__ void __launch_bounds__(BLOCK, WAVES) leaf_kernel(const uint32_t* __restrict__ code_g, const Cube* __restrict__ cubes,
-                                                     unsigned long long cube_cap, int lq, int nslots, float ox, float oy, float oz,
-                                                     float res, float* __restrict__ tris, uint64_t tri_cap,
-                                                     MeshCounters* __restrict__ ctr) {
-  code_ptr code = as_code(code_g);
-  float* lds = g_smem + threadIdx.x;
-  float* vslot = lds;  // 8 per-lane corner distances, written after the last interpreter pass (aliases the slots)
-  // columns 8..10: the lane's cube origin; columns 11..13 (3 KB, block-shared): owner list + cube indices of the
-  // balanced emission -- all of it aliases slot columns, which are idle between the last evaluation and the barrier
-  // that ends the emission
-  uint16_t* s_owner = (uint16_t*)(g_smem + 11 * BLOCK);  // [5 * BLOCK]
-  uint8_t* s_index = (uint8_t*)(s_owner + 5 * BLOCK);    // [BLOCK]
-  int8_t* s_tri = (int8_t*)(g_smem + (size_t)(nslots * K > LEAF_MIN_COLS ? nslots * K : LEAF_MIN_COLS) * BLOCK);
-  float* s_stage = (float*)(s_tri + 256 * 16);
-  unsigned* s_misc = (unsigned*)(s_stage + TRI_STAGE * 9);  // [0..3] wave sums
-  unsigned long long* s_base = (unsigned long long*)(s_misc + 6);
-  for (int k = threadIdx.x; k < 256 * 16; k += BLOCK) s_tri[k] = GSDF_MC_TRI[k >> 4][k & 15];
-  __syncthreads();
-  unsigned cur = 0;  // triangles in the LDS stage (block-uniform)
-
-  const float cubeDiag = 2 * 1.73205080757f * res;  // marchcubes.go:19
-  const int sh = lq - 1;
-  unsigned long long n_cubes = uniform_u64(ctr->n_level[lq]);  // survivors of the last prune level (device-side count)
-  if (n_cubes > cube_cap) n_cubes = cube_cap;                  // queue overflowed: host reruns with larger queues
-  const uint64_t n_leaves = uniform_u64(n_cubes << (3 * sh));  // wave-uniform: keep it in SGPRs (the clamp above is a per-lane select otherwise)
-  unsigned my_active = 0, my_cont = 0;  // per wave, < 2^32: a workgroup visits at most 2^32 / BLOCK iterations
-  const uint64_t step = (uint64_t)gridDim.x * BLOCK;
-  for (uint64_t base = (uint64_t)blockIdx.x * BLOCK; base < n_leaves; base += step) {
-    const uint64_t i = base + threadIdx.x;
-    const bool valid = i < n_leaves;
-    Cube lf = {0, 0, 0, 0};
-    if (valid) {
-      const Cube pc = cubes[i >> (3 * sh)];
-      const unsigned l = (unsigned)(i & ((1u << (3 * sh)) - 1u));
-      const unsigned m = (1u << sh) - 1u;
-      lf.x = (uint16_t)((pc.x << sh) + (l & m));
-      lf.y = (uint16_t)((pc.y << sh) + ((l >> sh) & m));
-      lf.z = (uint16_t)((pc.z << sh) + ((l >> (2 * sh)) & m));
-    }
-    const float x0 = ox + res * (float)lf.x, y0 = oy + res * (float)lf.y, z0 = oz + res * (float)lf.z;
-    const float x1 = x0 + res, y1 = y0 + res, z1 = z0 + res;  // Box max = origin + size
-    // Single interpreter call site, K corners per pass (corner 0 is in the first pass); the wave goes on
-    // to the remaining corners only if some lane passes the reference's corner-0 test.
-    unsigned index = 0;
-    bool pass = false;
-    float dall[8];  // distances in evaluation order; shifted so that the final contents sit at static positions
-#pragma unroll
-    for (int j = 0; j < 8; j++) dall[j] = 0.f;
-#pragma unroll 1
-    for (unsigned c0 = 0; c0 < 8; c0 += K) {
-      P3 pk[K];
-      float dk[K];
-      // Corner order {0,4,1,5 | 3,7,2,6}: consecutive points share x,y and (K = 4) points j, j+2 share z, which is
-      // what the interpreter's PAIRED mode needs to compute hypot/atan2(x,y) and twist sin/cos(z) once per pair.
-#pragma unroll
-      for (int kp = 0; kp < K; kp++) {
-        const unsigned c = (0x62735140u >> (4u * (c0 + kp))) & 7u;
-        pk[kp].x = ((c ^ (c >> 1)) & 1u) ? x1 : x0;
-        pk[kp].y = ((c >> 1) & 1u) ? y1 : y0;
-        pk[kp].z = ((c >> 2) & 1u) ? z1 : z0;
-      }
-      gsdf_dev::sdf_eval<K, true>(code, pk, dk, lds, BLOCK, /*brick=*/sh == 2);  // lq == 3: one wave = one 4x4x4 brick
-#pragma unroll
-      for (int j = 0; j < 8 - K; j++) dall[j] = dall[j + K];  // static shift register: no dynamic register index
-#pragma unroll
-      for (int kp = 0; kp < K; kp++) {
-        const unsigned c = (0x62735140u >> (4u * (c0 + kp))) & 7u;
-        dall[8 - K + kp] = dk[kp];
-        index |= (nb::lt0(dk[kp]) ? 1u : 0u) << c;
-      }
-      if (c0 == 0) {
-        const dm::lane_pred pvalid = dm::pred(valid), ppass = pvalid & nb::abs_le_p(dk[0], cubeDiag);  // (flag and mask of one predicate: dev_math.h, lane_pred)
-        pass = ppass.lane;
-        const unsigned long long vmask = pvalid.wave, pmask = ppass.wave;
-        if (pmask == 0ull) break;  // wave-uniform
-        // wave-uniform counters (every lane adds the same scalar): they live in SGPRs, not in four VGPRs
-        my_active += (unsigned)__builtin_popcountll(pmask);
-        my_cont += (unsigned)__builtin_popcountll(vmask);
-      }
-    }
-    if (!pass || index == 255u) index = 0;
-#ifdef GSDF_EXP_NO_EMIT  // developer experiment (GSDF_HIP_SPEC_FLAGS=-DGSDF_EXP_NO_EMIT): evaluation cost alone
-    index = 0;
-#endif
-    // after the last pass dall[j] is the distance of corner order[j] (an early exit leaves index == 0: nothing is read)
-    if (index) {
-#pragma unroll
-      for (int j = 0; j < 8; j++) vslot[((0x62735140u >> (4u * j)) & 7u) * BLOCK] = dall[j];
-      lds[8 * BLOCK] = x0;
-      lds[9 * BLOCK] = y0;
-      lds[10 * BLOCK] = z0;
-    }
-    const unsigned index1[1] = {index};
-    mc_emit_balanced<1, TRI_STAGE>(
-        index1, s_owner, s_index, s_tri, s_stage, s_misc, s_base, cur, res,
-        [&](unsigned id, unsigned cc) { return g_smem[cc * BLOCK + id]; },
-        [&](unsigned id, float& ax, float& ay, float& az) {
-          ax = g_smem[8 * BLOCK + id];
-          ay = g_smem[9 * BLOCK + id];
-          az = g_smem[10 * BLOCK + id];
-        },
-        tris, tri_cap, ctr);
-  }
-  __syncthreads();
-  if (cur) mc_stage_flush<TRI_STAGE>(s_stage, s_base, cur, tris, tri_cap, ctr);
-  // statistics: two atomics per workgroup, not per wave (they share the L2 atomic unit with the triangle appends)
-  __syncthreads();
-  unsigned* s_stat = (unsigned*)s_stage;
-  if ((threadIdx.x & 63u) == 0u) { s_stat[2 * (threadIdx.x >> 6)] = my_active; s_stat[2 * (threadIdx.x >> 6) + 1] = my_cont; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned long long a = (unsigned long long)s_stat[0] + s_stat[2] + s_stat[4] + s_stat[6];
-    const unsigned long long c = (unsigned long long)s_stat[1] + s_stat[3] + s_stat[5] + s_stat[7];
-    if (c) { atomicAdd(&ctr->n_active, a); atomicAdd(&ctr->n_cont, c); }
-  }
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
-// Two-kernel leaf phase (default): leaf_eval_kernel evaluates, march_records_kernel builds the triangles.
+// The leaf phase: leaf_eval_kernel evaluates, march_records_kernel builds the triangles.
 //
-// The fused leaf_kernel above spends 45 % of its time in the emission (block scan, owner list, LDS stage, four workgroup
-// barriers per pass and a global append every ~1.4 passes): the four waves of a workgroup stall together at every barrier
-// and at the atomic's round trip, with only 3-4 waves per SIMD to cover for them. Here the evaluating kernel has NO
-// barrier and NO atomic in its loop -- its waves are independent -- and leaves, per 64-leaf block (one wave pass), the leaves
-// the surface cuts as compact records in HBM:
+// Two kernels and not one: a single kernel that evaluates and emits spends 45 % of its time in the emission (block scan, owner
+// list, LDS stage, four workgroup barriers per pass and a global append every ~1.4 passes): the four waves of a workgroup stall
+// together at every barrier and at the atomic's round trip, with only 3-4 waves per SIMD to cover for them (0.88 ms where the
+// two kernels take 0.48 + 0.16). The evaluating kernel has NO barrier and NO atomic in its loop -- its waves are independent --
+// and leaves, per 64-leaf block (one wave pass), the leaves the surface cuts as compact records in HBM:
 //     hdr[block]                    = number of records (0..64) | number of triangles << 8
 //     rec[block][r][c], c < 10      = the block's records side by side (r = rank among the wave's cut lanes): 8 corner distances
 //                                     (corner order 0..7), leaf x | y << 16, leaf z | index << 16 (40 B per cut leaf, ~16 % of
@@ -650,8 +318,8 @@ __global__ void __launch_bounds__(BLOCK, WAVES) leaf_kernel(const uint32_t* __re
 // march_records_kernel then runs marching cubes over the records alone (see there): it needs no append counter, because the
 // evaluating kernel also leaves the triangle count of every block (hdr, bits 8..) and the sums of both counts per group of
 // MARCH_GROUP blocks (psum).
-// Same float operations on the same values as the fused kernel: the leaf origin is recomputed from the stored leaf
-// coordinates by the expression the evaluation used.
+// The marching kernel recomputes the leaf origin from the stored leaf coordinates by the expression the evaluation used: the
+// same float operations on the same values.
 // ---------------------------------------------------------------------------------------------------------------------
 #define REC_BLOCK (64 * REC_WORDS)  // dwords per 64-leaf block
 #define MARCH_GROUP 64              // blocks per entry of the group sums (records, triangles, active leaves) the evaluating kernel accumulates
@@ -1743,119 +1411,5 @@ __global__ void __launch_bounds__(BLOCK, 6) march_dense_kernel(const uint8_t* __
     out += n;
     if (pn != p && pn < np) out = parts->p[pn].tri0;  // (the same number, unless a payload's counts are damaged)
     p = pn; c = cn;
-  }
-}
-
-// Leaf kernel with exact corner sharing (level-3 bricks: one wave = one brick of 4x4x4 leaves).
-// The reference evaluates 8 corners per leaf: 512 evaluations per brick. Neighbouring leaves share lattice
-// planes, but the two coordinate expressions of a plane -- A(i) = O + res*i (min corner of leaf i) and
-// B(i) = A(i-1) + res (max corner of leaf i-1) -- are only sometimes the same float (64-73 % of planes at
-// resdiv 1600). Per axis the brick therefore has 5..8 bitwise-distinct coordinates (A0, {B1,A1}, {B2,A2},
-// {B3,A3}, B4 with equal pairs merged); every distinct point is evaluated ONCE (typically ~6x6x6 = 216
-// instead of 512: one 4-points-per-lane pass instead of two) and each leaf corner reads the value of
-// exactly the coordinates the reference would have evaluated, so distances, signs and triangles stay
-// bit-identical.
-// LDS: [nslots*K floats per lane | tri table | triangle stage | misc | 4 x 512 distances | 4 x 24 coordinates].
-template <int K, int WAVES>
-__global__ void __launch_bounds__(BLOCK, WAVES) leaf_brick_kernel(const uint32_t* __restrict__ code_g, const Cube* __restrict__ cubes,
-                                                                  unsigned long long cube_cap, int nslots, float ox, float oy, float oz,
-                                                                  float res, float* __restrict__ tris, uint64_t tri_cap,
-                                                                  MeshCounters* __restrict__ ctr) {
-  code_ptr code = as_code(code_g);
-  float* lds = g_smem + threadIdx.x;
-  int8_t* s_tri = (int8_t*)(g_smem + (size_t)(nslots * K) * BLOCK);
-  float* s_stage = (float*)(s_tri + 256 * 16);
-  unsigned* s_misc = (unsigned*)(s_stage + TRI_STAGE * 9);
-  unsigned long long* s_base = (unsigned long long*)(s_misc + 6);
-  float* s_D = (float*)(s_base + 1);
-  float* s_val = s_D + 4 * 512;
-  for (int k = threadIdx.x; k < 256 * 16; k += BLOCK) s_tri[k] = GSDF_MC_TRI[k >> 4][k & 15];
-  if (threadIdx.x == 0) s_misc[4] = 0;
-  __syncthreads();
-
-  const float cubeDiag = 2 * 1.73205080757f * res;  // marchcubes.go:19
-  unsigned long long n_cubes = uniform_u64(ctr->n_level[3]);
-  if (n_cubes > cube_cap) n_cubes = cube_cap;
-  const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  float* D = s_D + wave * 512;
-  float* val = s_val + wave * 24;
-  const float org[3] = {ox, oy, oz};
-  unsigned long long my_active = 0, my_points = 0;
-  const uint64_t step = (uint64_t)gridDim.x * 4;
-  for (uint64_t base = (uint64_t)blockIdx.x * 4; base < n_cubes; base += step) {  // block-uniform trip count
-    const uint64_t brick = base + wave;
-    const bool bvalid = brick < n_cubes;
-    Cube pc = {0, 0, 0, 0};
-    if (bvalid) pc = cubes[brick];
-    const unsigned pidx[3] = {pc.x, pc.y, pc.z};
-    // per-axis mismatch bits m_p (p = 1..3): plane p has two distinct floats
-    unsigned mb[3], nax[3];
-#pragma unroll
-    for (int ax = 0; ax < 3; ax++) {
-      const unsigned i0 = pidx[ax] * 4u;
-      float A[4];
-#pragma unroll
-      for (int k = 0; k < 4; k++) A[k] = org[ax] + res * (float)(i0 + k);  // CubeOrigin of leaf i0+k
-      unsigned m = 0;
-#pragma unroll
-      for (int k = 1; k < 4; k++) m |= ((A[k - 1] + res) != A[k] ? 1u : 0u) << (k - 1);
-      mb[ax] = m;
-      nax[ax] = 5u + __builtin_popcount(m);
-    }
-    if (lane < 12) {  // coordinate table: lane (axis, a) writes A_a and B_{a+1} at their distinct-value slots
-      const unsigned ax = lane >> 2, a = lane & 3u;
-      const float Aa = org[ax] + res * (float)(pidx[ax] * 4u + a);
-      const unsigned u = a + __builtin_popcount(mb[ax] & ((1u << a) - 1u));
-      val[ax * 8 + u] = Aa;
-      val[ax * 8 + u + 1] = Aa + res;  // Box max = origin + size
-    }
-    __builtin_amdgcn_wave_barrier();
-    const unsigned nx = nax[0], nxy = nax[0] * nax[1], N = nxy * nax[2];
-    const float inx = 1.0f / (float)nx, inxy = 1.0f / (float)nxy;
-    if (bvalid && lane == 0) my_points += N;
-#pragma unroll 1
-    for (unsigned t0 = 0; t0 < N; t0 += 64 * K) {  // wave-uniform: 1 pass when N <= 256
-      P3 pk[K];
-      float dk[K];
-#pragma unroll
-      for (int kp = 0; kp < K; kp++) {
-        unsigned t = t0 + kp * 64 + lane;
-        if (t >= N) t = N - 1;  // idle slots re-evaluate the last point (result discarded)
-        const unsigned uz = (unsigned)(((float)t + 0.5f) * inxy);
-        const unsigned r = t - uz * nxy;
-        const unsigned uy = (unsigned)(((float)r + 0.5f) * inx);
-        const unsigned ux = r - uy * nx;
-        pk[kp] = P3{val[ux], val[8 + uy], val[16 + uz]};
-      }
-      gsdf_dev::sdf_eval<K>(code, pk, dk, lds, BLOCK);
-#pragma unroll
-      for (int kp = 0; kp < K; kp++) {
-        const unsigned t = t0 + kp * 64 + lane;
-        if (t < N) D[t] = dk[kp];
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
-    // this lane's leaf (a,b,c) and its corner 0 index in the distinct-point lattice
-    const unsigned la = lane & 3u, lb = (lane >> 2) & 3u, lc = lane >> 4;
-    const unsigned ux0 = la + __builtin_popcount(mb[0] & ((1u << la) - 1u));
-    const unsigned uy0 = lb + __builtin_popcount(mb[1] & ((1u << lb) - 1u));
-    const unsigned uz0 = lc + __builtin_popcount(mb[2] & ((1u << lc) - 1u));
-    const unsigned tb = ux0 + nx * uy0 + nxy * uz0;
-    auto vdist = [&](unsigned cc) { return D[tb + ((cc ^ (cc >> 1)) & 1u) + nx * ((cc >> 1) & 1u) + nxy * ((cc >> 2) & 1u)]; };
-    const float x0 = val[ux0], x1 = val[ux0 + 1], y0 = val[8 + uy0], y1 = val[8 + uy0 + 1], z0 = val[16 + uz0], z1 = val[16 + uz0 + 1];
-    unsigned index = 0;
-#pragma unroll
-    for (unsigned cc = 0; cc < 8; cc++) index |= (nb::lt0(vdist(cc)) ? 1u : 0u) << cc;
-    const dm::lane_pred ppass = dm::pred(bvalid) & nb::abs_le_p(vdist(0), cubeDiag);
-    const bool pass = ppass.lane;
-    const unsigned long long pmask = ppass.wave;
-    if (lane == 0) my_active += (unsigned long long)__builtin_popcountll(pmask);
-    if (!pass) index = 0;
-    mc_emit_block(index, x0, y0, z0, x1, y1, z1, vdist, s_tri, s_stage, s_misc, s_base, tris, tri_cap, ctr);
-  }
-  mc_final_flush(s_stage, s_misc, s_base, tris, tri_cap, ctr);
-  if (lane == 0 && my_points) {
-    atomicAdd(&ctr->n_active, my_active);
-    atomicAdd(&ctr->n_points, my_points);
   }
 }

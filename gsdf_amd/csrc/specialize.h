@@ -18,7 +18,7 @@ int spec_instruction_count(const Program& p);
 int spec_xy_shared_weight(const Program& p);
 
 // Compile kernels.h with the specialised evaluator for `arch` (e.g. "gfx950") and instantiate `name_exprs`
-// ("leaf_kernel<4, 4>", "prune_kernel", ...). On success returns true and fills the code object and the lowered
+// ("leaf_eval_kernel<4, 4, true, true, false, false>", "prune_kernel", ...). On success returns true and fills the code object and the lowered
 // (mangled) names in the same order; otherwise `log` holds the compiler output. Needs no GPU.
 bool spec_compile(const Program& p, const std::string& arch, const std::vector<std::string>& name_exprs,
                   std::vector<char>& code_object, std::vector<std::string>& lowered, std::string& log);

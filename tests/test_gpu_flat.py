@@ -72,28 +72,6 @@ def test_flat_row_lengths_around_the_bit_words(gpu, nx):
         assert _same(np.concatenate(parts), ref.tris)
 
 
-def test_flat_float_stream_pass_gives_the_same_triangles(gpu):
-    """GSDF_HIP_FLAT_STREAM=1 selects the marching pass of rounds 1-2 (flat_march_kernel, which streams the float grid) in
-    place of the bit-plane pass; read once per process, hence the subprocess."""
-    import hashlib, os, subprocess, sys
-    code = ("import hashlib, numpy as np\n"
-            "from scaffold.builder import Builder\n"
-            "from gsdf_amd import hip\n"
-            "hip.init(0)\n"
-            "s = Builder().Scene('npt-flange')\n"
-            "t = hip.FlatHIP(hip.SDF3HIP(s), np.float32(float(s.Diagonal()) / 233)).RenderAll().reshape(-1, 9)\n"
-            "t = t[np.lexsort(t.view(np.uint32).T[::-1])]\n"
-            "print(len(t), hashlib.sha256(t.tobytes()).hexdigest())\n")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, GSDF_HIP_FLAT_STREAM="1", PYTHONPATH=root)
-    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300, cwd=root)
-    assert out.returncode == 0, out.stderr[-2000:]
-    n, digest = out.stdout.split()[-2:]
-    s = Builder().Scene("npt-flange")
-    t = _sorted(gpu.FlatHIP(gpu.SDF3HIP(s), np.float32(float(s.Diagonal()) / 233)).RenderAll())
-    assert int(n) == len(t) and digest == hashlib.sha256(t.tobytes()).hexdigest()
-
-
 def test_flat_sharded_union_equals_whole(gpu):
     b = Builder()
     s = b.Scene("npt-flange")

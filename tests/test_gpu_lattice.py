@@ -1,15 +1,10 @@
 """Lattice-aligned fields with exact zeros (tests/lattice_trees.py) through every marching path of the device, against the oracle
 bit for bit: mcInterpolate's snap, t = 0.5 and -0.0 branches in the record marchers (march_vertex, per wave and per workgroup), the
-corner-sharing leaf kernels, the flat renderer's own marching (mc_interp), the fused leaf kernels (mc_emit_balanced / mc_emit_block,
-in a child process: GSDF_HIP_FUSED_LEAF is read once per process), the weld's lattice-point keys, and the same again through the
-kernels specialised per tree. Then what a degenerate field hands downstream: zero-area triangles in the STL writer, faces with
+corner-sharing leaf kernels, the flat renderer's own marching (mc_interp), the weld's lattice-point keys, and the same again through
+the kernels specialised per tree. Then what a degenerate field hands downstream: zero-area triangles in the STL writer, faces with
 repeated indices and non-manifold edges in the report, extract and simplify kernels, simplify's grid ON the lattice planes.
 
 tests/test_lattice_ref.py shows on the CPU that the families reach these branches in numbers and that twin and oracle agree there."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
@@ -138,17 +133,6 @@ def test_every_marching_path_matches_the_oracle_specialised(gpu, name):
     17.8 s in specialize() and 92.6 s for the case, the rest being the builds that share_corners = 1 and 2 and the flat renderer
     start on first use. The interpreter cases above take 0.03-1.3 s each."""
     check_paths(gpu, name, specialised=True)
-
-
-def test_fused_leaf_kernels_in_a_child_process(gpu):
-    """mc_emit_balanced (leaf_kernel) and mc_emit_block (leaf_brick_kernel, share_corners = 1) run only under GSDF_HIP_FUSED_LEAF=1,
-    which the library reads once per process: tests/lattice_fused.py is that process."""
-    env = dict(os.environ, GSDF_HIP_FUSED_LEAF="1")
-    worker = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lattice_fused.py")
-    pr = subprocess.run([sys.executable, worker], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
-    out = pr.stdout.decode(errors="replace")
-    print(out[-3000:])
-    assert pr.returncode == 0 and "fused ok" in out, out[-3000:]
 
 
 DOWNSTREAM = ["spheres0", "boxeszero"]

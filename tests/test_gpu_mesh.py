@@ -60,23 +60,20 @@ def test_scene_mesh_identical_to_oracle(gpu, scene, key):
     assert [int(getattr(rows.stats, k)) for k in ("n_tris", "leaf_cubes", "active_leaves", "cut_leaves", "evals_prune")] == \
            [int(getattr(oc.stats, k)) for k in ("n_tris", "leaf_cubes", "active_leaves", "cut_leaves", "evals_prune")]
     assert 5 * int(rows.stats.leaf_cubes) <= int(rows.stats.evals_leaf) <= int(oc.stats.evals_leaf) == 8 * int(oc.stats.leaf_cubes)
-    if sdf.info()["leaf_k"] == 4 and not os.environ.get("GSDF_HIP_FUSED_LEAF"):
+    if sdf.info()["leaf_k"] == 4:
         assert rows.stats.evals_leaf < oc.stats.evals_leaf
         # ... and exactly what the oracle counts for the surviving bricks: 64 columns x the distinct z rows of each; every distinct
         # lattice point in passes of 256 lane slots (the interpreter's build of leaf_dense_kernel has no tail passes)
         assert int(rows.stats.evals_leaf) == ref.evals_rows and int(shared.stats.evals_leaf) == ref.evals_points_256
-    elif sdf.info()["leaf_k"] == 4:
-        assert int(shared.stats.evals_leaf) == ref.evals_points   # (the fused leaf_brick_kernel counts points, not lane slots)   # (a brick has 5..8 distinct rows; all eight only where every plane's two floats differ)
-    if not os.environ.get("GSDF_HIP_FUSED_LEAF"):   # (packed records are the two-kernel leaf phase's; the fused kernel of tools/gpu_variants*.sh has none)
-        rrec = gpu.OctreeHIP(sdf, res, share_corners=2, payload=gpu.PAYLOAD_RECORDS)
-        assert rrec.payload()[0] == gpu.PAYLOAD_RECORDS and rrec.payload()[1] == int(oc.stats.cut_leaves)
-        rrec.march()
-        assert (_sorted(rrec.RenderAll()).view(np.uint32) == tg.view(np.uint32)).all()
-        assert int(rrec.stats.evals_leaf) == int(rows.stats.evals_leaf)
-        prec = gpu.OctreeHIP(sdf, res, share_corners=1, payload=gpu.PAYLOAD_RECORDS)   # distinct lattice points + packed records
-        assert prec.payload()[1] == int(oc.stats.cut_leaves) and int(prec.stats.evals_leaf) == int(shared.stats.evals_leaf)
-        prec.march()
-        assert (_sorted(prec.RenderAll()).view(np.uint32) == tg.view(np.uint32)).all()
+    rrec = gpu.OctreeHIP(sdf, res, share_corners=2, payload=gpu.PAYLOAD_RECORDS)
+    assert rrec.payload()[0] == gpu.PAYLOAD_RECORDS and rrec.payload()[1] == int(oc.stats.cut_leaves)
+    rrec.march()
+    assert (_sorted(rrec.RenderAll()).view(np.uint32) == tg.view(np.uint32)).all()
+    assert int(rrec.stats.evals_leaf) == int(rows.stats.evals_leaf)
+    prec = gpu.OctreeHIP(sdf, res, share_corners=1, payload=gpu.PAYLOAD_RECORDS)   # distinct lattice points + packed records
+    assert prec.payload()[1] == int(oc.stats.cut_leaves) and int(prec.stats.evals_leaf) == int(shared.stats.evals_leaf)
+    prec.march()
+    assert (_sorted(prec.RenderAll()).view(np.uint32) == tg.view(np.uint32)).all()
     # pruning must not change the surface (flat renderer == octree renderer in the reference's README)
     if key != "npt_flange_resdiv400":
         assert gpu.OctreeHIP(sdf, res, prune=False).n_tris() == g["n_tris"]

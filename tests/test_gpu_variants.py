@@ -13,7 +13,6 @@ for its rung. Between them the assertions name every instantiation:
   image2_kernel<4> <2> <1>, image2_color_kernel<4,kind> <2,kind> <1,kind>                                           (b, 2-D)
   eval_kernel<3,2,4> <3,1,4> <3,4,3>, leaf_eval_kernel<2,3> <1,4> <4,2> on the example scenes                        (c, forced)
   the specialised builds of eval / leaf / prune for one lifted tree per class                                       (d)
-(leaf_kernel<K,W>, the fused leaf phase, runs under GSDF_HIP_FUSED_LEAF=1 only: test_gpu_lattice.py's child process.)
 
 Time, one run on one MI355X machine: this file 40 s (38 cases), straight after it the rest of the GPU suite (338 cases, which is the
 parent commit's suite) 596 s. Per case: every op of a dimension in one class 0.15-0.4 s (40 to 45 trees, four evaluations each), the
@@ -230,7 +229,7 @@ TEN_SLOTS = {"knurled-cylinder": ("eval_kernel<3,4,3>", "flat_grid_kernel<4,3>")
 def test_example_scenes_under_a_forced_variant(gpu, knob):
     """The knobs are statics read once per process: tests/variant_worker.py is that process, one at a time."""
     key, val = knob.split("=")
-    env = {k: v for k, v in os.environ.items() if k not in ("GSDF_HIP_BATCH_K", "GSDF_HIP_SWEEP_WAVES", "GSDF_HIP_LEAF_WAVES", "GSDF_HIP_FUSED_LEAF")}
+    env = {k: v for k, v in os.environ.items() if k not in ("GSDF_HIP_BATCH_K", "GSDF_HIP_SWEEP_WAVES", "GSDF_HIP_LEAF_WAVES")}
     env[key] = val
     worker = os.path.join(os.path.dirname(os.path.abspath(__file__)), "variant_worker.py")
     pr = subprocess.run([sys.executable, worker], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=240)

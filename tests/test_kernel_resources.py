@@ -48,7 +48,9 @@ def test_no_shipped_kernel_uses_scratch():
     with tempfile.TemporaryDirectory() as tmp:
         rows = [r for obj in device_code_object(lib, tmp) for r in kernel_notes(obj)]
     names = [r["name"] for r in rows]
-    assert len(rows) >= 30 and any("leaf_kernel" in n for n in names) and any("eval_kernel" in n for n in names), names
+    assert len(rows) >= 30 and any("leaf_eval_kernel" in n for n in names) and any("eval_kernel" in n for n in names), names
+    # one leaf phase and one flat marching pass: the library ships no second form of either (flat_march_list_kernel is the pass)
+    assert not [n for n in names if "leaf_kernel" in n or "leaf_brick_kernel" in n or "flat_march_kernel" in n]
     bad = [(r["name"], r["private_segment_fixed_size"], r.get("vgpr_spill_count")) for r in rows if int(r["private_segment_fixed_size"]) != 0]
     assert not bad, f"kernels with scratch (bytes, spilled VGPRs): {bad}"
     # wave64 kernels with 256-thread workgroups: the occupancy the host counts on needs <= 512 / W VGPRs, which the

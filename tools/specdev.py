@@ -2,7 +2,7 @@
 """Developer tool (host only, no GPU): build the run-time specialised kernels of a scene from the CURRENT interp.h /
 kernels.h and report registers / scratch per kernel; optionally dump the ISA.
 
-  tools/specdev.py npt-flange "leaf_kernel<4, 4>" [--isa out.s] [--keep dir]
+  tools/specdev.py npt-flange "leaf_eval_kernel<4, 4, true, true, true, false>" [--isa out.s] [--keep dir]
   tools/specdev.py fuzz2d:708:1 "eval_kernel<2, 4, 4>"
 """
 import argparse, ctypes as C, os, re, subprocess, sys, tempfile
