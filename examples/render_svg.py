@@ -5,10 +5,14 @@ slicer wants of a 3-D part at each layer height:
     python examples/render_svg.py text -o text.svg                             # the 2-D scenes of render_png.py: image, text, thread
     python examples/render_svg.py npt-flange --slice 5 -o flange.svg           # one contour of a 3-D scene (npt-flange, bolt) at z = 5
     python examples/render_svg.py bolt --layer-height 2 --report -o bolt.svg   # every layer of thickness 2, with a report
+    python examples/render_svg.py text --simplify 0.125 --report -o text.svg   # vertices within res / 8 of a chord dropped on the GPU
 
 The lattice spacing is the diagonal of the part's bounds / --resdiv (default 400), or --res. Every layer is one even-odd <path>:
 outer boundaries counter-clockwise, holes clockwise. --report prints loops, vertices, outer and hole counts and the area of every
-layer, and the device time of the two stages (evaluation, tracing). The SVG is written with the standard library only."""
+layer, and the device time of the two stages (evaluation, tracing). --simplify TOL drops the vertices that lie within TOL x res of a
+dyadic chord of their loop (gsdf_hip_contour_simplify; --levels, --passes as there), --max-verts N doubles that tolerance until at
+most N vertices are left; the report then adds the vertices before and after, the largest deviation and the layers' areas and lengths
+summed on the device. The SVG is written with the standard library only."""
 import argparse
 import importlib.util
 import math
@@ -61,6 +65,17 @@ def report(c, z=None):
     return "\n".join(lines)
 
 
+def simplify_report(before, c, st, tol):
+    """What --simplify did, and the simplified layers' measures from the device."""
+    lines = [f"simplified at tol {float(tol):.6g}: {before} -> {c.n_verts} vertices in {c.n_loops} loops ({st.loops_changed} loops changed), max_dev {st.max_dev:.6g}, "
+             f"largest span level {st.max_level}, device time {st.ms_device:.3f} ms"]
+    _, layers = c.measures()
+    for k, m in enumerate(layers):
+        lines.append(f"layer {k} on the device: {m['n_loops']} loops, {m['n_verts']} vertices, area {m['area']:.9g}, length {m['length']:.9g} "
+                     f"(measures: {type(c).measures_ms():.3f} ms)")
+    return "\n".join(lines)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("scene", choices=SCENES_2D + SCENES_3D)
@@ -68,6 +83,10 @@ def main(argv=None):
     ap.add_argument("--resdiv", type=float, default=400.0)
     ap.add_argument("--slice", type=float, default=None, metavar="Z", help="3-D scenes: one contour at this height")
     ap.add_argument("--layer-height", type=float, default=None, metavar="H", help="3-D scenes: a contour at the middle of every layer of this thickness")
+    ap.add_argument("--simplify", type=float, default=None, metavar="TOL", help="drop vertices within TOL x res of a dyadic chord of their loop")
+    ap.add_argument("--levels", type=int, default=8, help="--simplify: dyadic levels, 1 .. 16")
+    ap.add_argument("--passes", type=int, default=1, help="--simplify: passes, 1 .. 8 (the deviations add)")
+    ap.add_argument("--max-verts", type=int, default=None, metavar="N", help="--simplify: double the tolerance until at most N vertices are left")
     ap.add_argument("--report", action="store_true")
     ap.add_argument("--interpreter", action="store_true", help="skip the per-tree kernel build")
     ap.add_argument("-o", "--output", default=None)
@@ -95,12 +114,24 @@ def main(argv=None):
     t1 = time.perf_counter()
     c = trace(hip, sdf, res, z)
     t2 = time.perf_counter()
+    traced, simplified = c, None
+    if args.simplify is not None:
+        tol = np.float32(np.float32(args.simplify) * res)
+        if args.max_verts is not None:
+            c, st, tol = traced.simplify_to(args.max_verts, tol, args.levels, args.passes)
+        else:
+            c, st = traced.simplify(tol, args.levels, args.passes)
+        simplified = (st, tol)
+    elif args.max_verts is not None:
+        ap.error("--max-verts goes with --simplify TOL, the tolerance the doubling starts from")
     out = args.output or f"{args.scene}.svg"
     svg.write_svg(out, [c.loops(k) for k in range(c.n_layers)], z=z)
     print(f"{args.scene} res {float(res):.6g}: setup {t1 - t0:.2f} s, contours {(t2 - t1) * 1e3:.1f} ms (the first call includes the kernels' build); "
           f"{c.n_loops} loops, {c.n_verts} vertices in {c.n_layers} layer(s); written to {out}")
     if args.report:
-        print(report(c, z))
+        print(report(traced, z))
+        if simplified:
+            print(simplify_report(traced.n_verts, c, *simplified))
     return 0
 
 

@@ -2,16 +2,20 @@
 // ordered closed loops, traced on the device. The gsdf_contour handle, gsdf_hip_contour2 / gsdf_hip_slice3, counts / read / stats.
 // Kernels: kernels_contour.h. The distances come from the program's own Evaluate (gsdf_hip_eval2_dev / gsdf_hip_eval3_dev:
 // interpreter or per-tree kernels, whichever the handle has); no interpreter kernel is compiled here.
+// Behind the tracer (section "contours: simplify and measures", kernels_contour_simplify.h): gsdf_hip_contour_create uploads loops,
+// gsdf_hip_contour_simplify drops vertices within a tolerance of dyadic chords, gsdf_hip_contour_measures sums areas and lengths.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <deque>
+#include <limits>
 #include <memory>
 #include <new>
 #include <vector>
 
 #include "kernels_common.h"
 #include "kernels_contour.h"
+#include "kernels_contour_simplify.h"
 #include "abi_program.h"
 
 struct gsdf_contour {
@@ -267,5 +271,247 @@ extern "C" int gsdf_hip_contour_read(const gsdf_contour* c, float* xy, uint32_t*
 extern "C" int gsdf_hip_contour_stats_get(const gsdf_contour* c, gsdf_contour_stats* st) {
   if (!c || !st) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
   *st = c->st;
+  return GSDF_OK;
+}
+
+// ---- loops after tracing: upload, simplify, measures (gsdf_hip.h, "contours: simplify and measures") -------------------------------
+namespace {
+// a handle for n_verts vertices in n_loops loops: buffers only, the stats' three counts set
+int contour_new(int device, uint64_t n_verts, uint64_t n_loops, uint32_t n_layers, ContourPtr* out) {
+  ContourPtr c(new (std::nothrow) gsdf_contour());
+  if (!c) return fail(GSDF_ERR_BAD_ARGUMENT, "out of memory");
+  c->device = device;
+  c->n_verts = n_verts;
+  c->n_loops = n_loops;
+  c->st.n_verts = n_verts;
+  c->st.n_loops = n_loops;
+  c->st.n_layers = n_layers;
+  if (!dev_alloc(c->xy, 2 * n_verts) || !dev_alloc(c->keys, n_verts) || !dev_alloc(c->loop_start, n_loops + 1) || !dev_alloc(c->loop_layer, n_loops))
+    return fail(GSDF_ERR_HIP, "contour: no device memory for the result");
+  *out = std::move(c);
+  return GSDF_OK;
+}
+
+// the loops one pass reads or writes (device pointers; the owner is a handle)
+struct LoopsView {
+  uint64_t n_verts, n_loops;
+  float* xy;
+  unsigned *keys, *loop_start;
+};
+LoopsView view_of(const gsdf_contour* c) { return LoopsView{c->n_verts, c->n_loops, c->xy.p, c->keys.p, c->loop_start.p}; }
+
+struct SimplifyWs {
+  DevPtr<unsigned> loop_of, rej, changed, blk_cnt, blk_base;
+  DevPtr<unsigned char> keep;
+  DevPtr<unsigned long long> total;
+  DevPtr<CsimpCounters> ctr;
+  EventSet<4> ev;
+};
+}  // namespace
+
+extern "C" int gsdf_hip_contour_create(const float* xy, uint64_t n_verts, const uint32_t* loop_start, uint64_t n_loops, const uint32_t* loop_layer, uint32_t n_layers,
+                                       const uint32_t* keys, gsdf_contour** out) {
+  if (!out) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  *out = nullptr;
+  if (n_loops == 0 || n_verts == 0) return fail(GSDF_ERR_EMPTY_BUFFERS, "empty buffers");
+  if (!xy || !loop_start) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  if (n_verts >= ((uint64_t)1 << 32)) return fail(GSDF_ERR_CAPACITY, "contour: 2^32 vertices or more");
+  if (n_layers == 0) return fail(GSDF_ERR_BAD_ARGUMENT, "contour: n_layers must be at least 1");
+  if (loop_start[0] != 0) return fail(GSDF_ERR_BAD_ARGUMENT, "contour: loop 0 starts at vertex " + std::to_string(loop_start[0]) + ", not at 0");
+  for (uint64_t q = 0; q < n_loops; q++)
+    if ((uint64_t)loop_start[q + 1] < (uint64_t)loop_start[q] + 3)
+      return fail(GSDF_ERR_BAD_ARGUMENT, "contour: loop " + std::to_string(q) + " (vertices " + std::to_string(loop_start[q]) + " .. " + std::to_string(loop_start[q + 1]) +
+                                             ") has fewer than 3 vertices");
+  if (loop_start[n_loops] != n_verts)
+    return fail(GSDF_ERR_BAD_ARGUMENT, "contour: loop " + std::to_string(n_loops - 1) + " ends at vertex " + std::to_string(loop_start[n_loops]) + ", the handle has " +
+                                           std::to_string(n_verts) + " vertices");
+  if (loop_layer)
+    for (uint64_t q = 0; q < n_loops; q++) {
+      if (loop_layer[q] >= n_layers)
+        return fail(GSDF_ERR_BAD_ARGUMENT, "contour: loop " + std::to_string(q) + " names layer " + std::to_string(loop_layer[q]) + ", the handle has " + std::to_string(n_layers) + " layers");
+      if (q > 0 && loop_layer[q] < loop_layer[q - 1])
+        return fail(GSDF_ERR_BAD_ARGUMENT, "contour: loop " + std::to_string(q) + " is in layer " + std::to_string(loop_layer[q]) + ", behind a loop of layer " + std::to_string(loop_layer[q - 1]));
+    }
+  for (uint64_t i = 0; i < 2 * n_verts; i++)
+    if (!std::isfinite(xy[i])) return fail(GSDF_ERR_BAD_ARGUMENT, "contour: vertex " + std::to_string(i / 2) + " has a NaN or infinite coordinate");
+  int device = 0;
+  HIP_TRY(hipGetDevice(&device));
+  ContourPtr c;
+  if (int rc = contour_new(device, n_verts, n_loops, n_layers, &c)) return rc;
+  hipError_t e = hipMemcpy(c->xy.p, xy, (size_t)n_verts * 8, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(c->loop_start.p, loop_start, (size_t)(n_loops + 1) * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = keys ? hipMemcpy(c->keys.p, keys, (size_t)n_verts * 4, hipMemcpyHostToDevice) : hipMemset(c->keys.p, 0, (size_t)n_verts * 4);
+  if (e == hipSuccess) e = loop_layer ? hipMemcpy(c->loop_layer.p, loop_layer, (size_t)n_loops * 4, hipMemcpyHostToDevice) : hipMemset(c->loop_layer.p, 0, (size_t)n_loops * 4);
+  if (e != hipSuccess) return fail(GSDF_ERR_HIP, std::string("contour upload: ") + hipGetErrorString(e));
+  *out = c.release();
+  return GSDF_OK;
+}
+
+extern "C" int gsdf_hip_contour_simplify(const gsdf_contour* c, const gsdf_contour_simplify_opts* o, gsdf_contour** out, gsdf_contour_simplify_stats* st_out) {
+  if (out) *out = nullptr;
+  if (!c || !o) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  if (!(o->tol >= 0.f)) return fail(GSDF_ERR_BAD_ARGUMENT, "contour simplify: tol must be a number >= 0");
+  if (o->levels > CSIMP_MAX_LEVELS) return fail(GSDF_ERR_BAD_ARGUMENT, "contour simplify: levels must be 1 .. 16 (0: 8)");
+  if (o->passes > 8) return fail(GSDF_ERR_BAD_ARGUMENT, "contour simplify: passes must be 1 .. 8 (0: 1)");
+  const bool dry = o->dry != 0;
+  if (!out && !dry) return fail(GSDF_ERR_BAD_ARGUMENT, "contour simplify: out may be null in a dry run only");
+  const unsigned levels = o->levels ? o->levels : 8u, passes = o->passes ? o->passes : 1u;
+  const double tol2 = (double)o->tol * (double)o->tol;
+  gsdf_contour_simplify_stats st{};
+  st.n_verts_in = st.n_verts_out = c->n_verts;
+  st.n_loops = c->n_loops;
+
+  HIP_TRY(hipSetDevice(c->device));
+  ContourPtr cur;  // the previous pass's result; null: the caller's handle
+  if (c->n_verts > 0 && c->n_loops > 0) {
+    const uint64_t V0 = c->n_verts, NL = c->n_loops;
+    Stream stream;  // (ahead of the workspace: the work on it is over before the buffers go, and it goes last)
+    HIP_TRY(stream.ensure());
+    hipStream_t s = stream.s;
+    SimplifyWs w;
+    const unsigned nb0 = blocks_of(V0);
+    if (!dev_alloc(w.loop_of, V0) || !dev_alloc(w.rej, V0) || !dev_alloc(w.changed, NL) || !dev_alloc(w.blk_cnt, nb0) || !dev_alloc(w.blk_base, nb0) || !dev_alloc(w.keep, V0) ||
+        !dev_alloc(w.total, 1) || !dev_alloc(w.ctr, 1))
+      return fail(GSDF_ERR_HIP, "contour simplify: no device memory for the workspace");
+    if (w.ev.ensure() != hipSuccess) return fail(GSDF_ERR_HIP, "hipEventCreate failed");
+    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{s};
+    HIP_TRY(hipMemsetAsync(w.ctr.p, 0, sizeof(CsimpCounters), s));
+    auto interval_ms = [&](int a, int b) { float t = 0; return hipEventElapsedTime(&t, w.ev[a], w.ev[b]) == hipSuccess ? (double)t : 0.0; };
+    for (unsigned pass = 0; pass < passes; pass++) {
+      const LoopsView in = view_of(cur ? cur.get() : c);
+      const uint64_t V = in.n_verts;
+      const unsigned nb = blocks_of(V);
+      const bool last = pass + 1 == passes;
+      HIP_TRY(hipEventRecord(w.ev[0], s));
+      HIP_TRY(hipMemsetAsync(w.rej.p, 0, (size_t)V * 4, s));
+      HIP_TRY(hipMemsetAsync(w.changed.p, 0, (size_t)NL * 4, s));
+      LAUNCH(cloop_of_kernel, nb, s, (const unsigned*)in.loop_start, (unsigned)NL, (unsigned)V, w.loop_of.p);
+      LAUNCH(csimp_reject_kernel, nb, s, (const float*)in.xy, (const unsigned*)in.loop_start, (const unsigned*)w.loop_of.p, (unsigned)V, levels, tol2, w.rej.p);
+      LAUNCH(csimp_mark_kernel, nb, s, (const float*)in.xy, (const unsigned*)in.loop_start, (const unsigned*)w.loop_of.p, (unsigned)V, levels, (const unsigned*)w.rej.p, w.keep.p,
+             w.changed.p, w.blk_cnt.p, w.ctr.p);
+      if (int rc = launch_block_scan(w.blk_cnt.p, nb, w.blk_base.p, w.total.p, s)) return rc;
+      HIP_TRY(hipEventRecord(w.ev[1], s));
+      unsigned long long h_total = 0;
+      HIP_TRY(hipMemcpyAsync(&h_total, w.total.p, 8, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+      st.ms_device += interval_ms(0, 1);
+      if (h_total < 3 * NL || h_total > V) return fail(GSDF_ERR_HIP, "contour simplify: internal error (a loop kept fewer than 3 vertices)");
+      st.n_verts_out = h_total;
+      if (last && dry) break;
+      ContourPtr next;
+      if (int rc = contour_new(c->device, h_total, NL, c->st.n_layers, &next)) return rc;
+      HIP_TRY(hipEventRecord(w.ev[2], s));
+      LAUNCH(csimp_emit_kernel, nb, s, (const unsigned*)in.xy, (const unsigned*)in.keys, (const unsigned*)in.loop_start, (const unsigned*)w.loop_of.p, (unsigned)V, (unsigned)NL,
+             (const unsigned char*)w.keep.p, (const unsigned*)w.blk_base.p, (unsigned)h_total, (unsigned*)next->xy.p, next->keys.p, next->loop_start.p, w.ctr.p);
+      HIP_TRY(hipMemcpyAsync(next->loop_layer.p, c->loop_layer.p, (size_t)NL * 4, hipMemcpyDeviceToDevice, s));
+      HIP_TRY(hipEventRecord(w.ev[3], s));
+      HIP_TRY(hipStreamSynchronize(s));
+      st.ms_device += interval_ms(2, 3);
+      cur = std::move(next);
+    }
+    CsimpCounters h_ctr;
+    HIP_TRY(hipMemcpyAsync(&h_ctr, w.ctr.p, sizeof h_ctr, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (h_ctr.bad) return fail(GSDF_ERR_HIP, "contour simplify: internal error (a vertex out of range)");
+    for (unsigned k = 0; k <= CSIMP_MAX_LEVELS; k++) {
+      st.spans[k] = h_ctr.spans[k];
+      if (h_ctr.spans[k]) st.max_level = k;
+    }
+    st.loops_changed = h_ctr.loops_changed;
+    double q2 = 0;
+    std::memcpy(&q2, &h_ctr.max_q2, 8);
+    st.max_dev = std::sqrt(q2);
+  }
+  if (!dry && !cur) {  // a handle without loops: its copy
+    if (int rc = contour_new(c->device, c->n_verts, c->n_loops, c->st.n_layers, &cur)) return rc;
+    const unsigned zero = 0;
+    HIP_TRY(hipMemcpy(cur->loop_start.p, &zero, 4, hipMemcpyHostToDevice));
+  }
+  if (st_out) *st_out = st;
+  if (!dry) *out = cur.release();
+  return GSDF_OK;
+}
+
+namespace {
+thread_local double g_measures_ms = 0;
+}
+extern "C" double gsdf_hip_contour_measures_ms(void) { return g_measures_ms; }
+
+extern "C" int gsdf_hip_contour_measures(const gsdf_contour* c, gsdf_loop_measure* loops, gsdf_layer_measure* layers) {
+  if (!c) return fail(GSDF_ERR_BAD_ARGUMENT, "null contour");
+  g_measures_ms = 0;
+  const uint64_t V = c->n_verts, NL = c->n_loops;
+  const uint32_t L = c->st.n_layers;
+  const float inf = std::numeric_limits<float>::infinity();
+  std::vector<CmeasAcc> h_acc(NL);
+  std::vector<unsigned> h_start(NL + 1), h_layer(NL);
+  unsigned long long h_maxbits = 0;
+  if (V > 0 && NL > 0) {
+    HIP_TRY(hipSetDevice(c->device));
+    Stream stream;
+    HIP_TRY(stream.ensure());
+    hipStream_t s = stream.s;
+    DevPtr<unsigned> loop_of;
+    DevPtr<CmeasAcc> acc;
+    DevPtr<unsigned long long> maxbits;
+    EventSet<2> ev;
+    if (!dev_alloc(loop_of, V) || !dev_alloc(acc, NL) || !dev_alloc(maxbits, 1)) return fail(GSDF_ERR_HIP, "contour measures: no device memory for the workspace");
+    if (ev.ensure() != hipSuccess) return fail(GSDF_ERR_HIP, "hipEventCreate failed");
+    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{s};
+    const unsigned nb = blocks_of(V), nb_max = blocks_of(2 * V) < 1024u ? blocks_of(2 * V) : 1024u;
+    HIP_TRY(hipEventRecord(ev[0], s));
+    HIP_TRY(hipMemsetAsync(maxbits.p, 0, 8, s));
+    LAUNCH(cmeas_maxbits_kernel, nb_max, s, (const float*)c->xy.p, (unsigned long long)(2 * V), maxbits.p);
+    LAUNCH(cmeas_init_kernel, blocks_of(NL), s, acc.p, (unsigned)NL);
+    LAUNCH(cloop_of_kernel, nb, s, (const unsigned*)c->loop_start.p, (unsigned)NL, (unsigned)V, loop_of.p);
+    LAUNCH(cmeas_kernel, nb, s, (const float*)c->xy.p, (const unsigned*)c->loop_start.p, (const unsigned*)loop_of.p, (unsigned)V, (const unsigned long long*)maxbits.p, acc.p);
+    HIP_TRY(hipEventRecord(ev[1], s));
+    HIP_TRY(hipMemcpyAsync(h_acc.data(), acc.p, (size_t)NL * sizeof(CmeasAcc), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h_start.data(), c->loop_start.p, (size_t)(NL + 1) * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h_layer.data(), c->loop_layer.p, (size_t)NL * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&h_maxbits, maxbits.p, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    float t = 0;
+    if (hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess) g_measures_ms = t;
+  }
+  // integers -> float64 with one rounding each, times the inverse power of two (exact); area = sum / 2
+  const unsigned biased = (unsigned)(h_maxbits >> 23);
+  const int e = (int)(biased > 1u ? biased : 1u) - 126;
+  auto whole = [](unsigned long long lo, unsigned long long hi) { return (__int128)(long long)hi * ((__int128)1 << 32) + (__int128)lo; };
+  auto unordered = [](unsigned o) { const unsigned b = o ^ ((o >> 31) ? 0x80000000u : 0xffffffffu); float f; std::memcpy(&f, &b, 4); return f; };
+  struct LayerAcc { __int128 area = 0, length = 0; unsigned bb[4] = {CMEAS_BB_MIN_INIT, CMEAS_BB_MIN_INIT, CMEAS_BB_MAX_INIT, CMEAS_BB_MAX_INIT}; uint32_t n_loops = 0, n_verts = 0; };
+  std::vector<LayerAcc> la(layers ? L : 0);
+  for (uint64_t q = 0; q < NL; q++) {
+    const CmeasAcc& a = h_acc[q];
+    const __int128 area = whole(a.sum[0], a.sum[1]), length = whole(a.sum[2], a.sum[3]);
+    if (loops) {
+      gsdf_loop_measure& m = loops[q];
+      m.area = std::ldexp((double)area, 2 * e - 62);
+      m.length = std::ldexp((double)length, e - 60);
+      for (int k = 0; k < 4; k++) m.bbox[k] = unordered(a.bb[k]);
+      m.n_verts = h_start[q + 1] - h_start[q];
+      m.layer = h_layer[q];
+    }
+    if (layers && h_layer[q] < L) {
+      LayerAcc& l = la[h_layer[q]];
+      l.area += area;
+      l.length += length;
+      for (int k = 0; k < 2; k++) {
+        l.bb[k] = std::min(l.bb[k], a.bb[k]);
+        l.bb[2 + k] = std::max(l.bb[2 + k], a.bb[2 + k]);
+      }
+      l.n_loops++;
+      l.n_verts += h_start[q + 1] - h_start[q];
+    }
+  }
+  if (layers)
+    for (uint32_t l = 0; l < L; l++) {
+      gsdf_layer_measure& m = layers[l];
+      m.area = std::ldexp((double)la[l].area, 2 * e - 62);
+      m.length = std::ldexp((double)la[l].length, e - 60);
+      for (int k = 0; k < 4; k++) m.bbox[k] = la[l].n_loops ? unordered(la[l].bb[k]) : (k < 2 ? inf : -inf);
+      m.n_loops = la[l].n_loops;
+      m.n_verts = la[l].n_verts;
+    }
   return GSDF_OK;
 }

@@ -31,7 +31,8 @@ SYMBOLS = ["gsdf_hip_last_error", "gsdf_hip_init", "gsdf_hip_program_create", "g
            "gsdf_hip_indexed_create", "gsdf_hip_indexed_report", "gsdf_hip_indexed_shells", "gsdf_hip_indexed_read_shell_of", "gsdf_hip_indexed_extract",
            "gsdf_hip_indexed_simplify", "gsdf_hip_indexed_simplify_adaptive", "gsdf_hip_indexed_project", "gsdf_hip_indexed_read_fit", "gsdf_hip_mesh_dualcontour_indexed",
            "gsdf_hip_raycast3", "gsdf_hip_indexed_thickness",
-           "gsdf_hip_contour2", "gsdf_hip_slice3", "gsdf_hip_contour_counts", "gsdf_hip_contour_read", "gsdf_hip_contour_stats_get", "gsdf_hip_contour_destroy"]
+           "gsdf_hip_contour2", "gsdf_hip_slice3", "gsdf_hip_contour_counts", "gsdf_hip_contour_read", "gsdf_hip_contour_stats_get", "gsdf_hip_contour_destroy",
+           "gsdf_hip_contour_create", "gsdf_hip_contour_simplify", "gsdf_hip_contour_measures", "gsdf_hip_contour_measures_ms"]
 
 
 PRUNE_ASSUME_SDF = 1 << 30  # gsdf_hip.h: GSDF_PRUNE_ASSUME_SDF
@@ -202,6 +203,27 @@ class ContourStats(C.Structure):
         return bytes(self)[:self.RESULT_BYTES]
 
 
+class ContourSimplifyOpts(C.Structure):
+    """gsdf_contour_simplify_opts (gsdf_hip.h): the deviation a dropped vertex may have, the number of dyadic levels, the passes, dry."""
+    _fields_ = [("tol", C.c_float), ("levels", C.c_uint32), ("passes", C.c_uint32), ("dry", C.c_uint32)]
+
+
+class ContourSimplifyStats(C.Structure):
+    """gsdf_contour_simplify_stats (gsdf_hip.h): what a simplification of loops did; bytes 0 .. 183 (RESULT_BYTES) are a function of the
+    loops and the options alone, ms_device says what the run cost."""
+    _fields_ = [("n_verts_in", C.c_uint64), ("n_verts_out", C.c_uint64), ("n_loops", C.c_uint64), ("loops_changed", C.c_uint64),
+                ("spans", C.c_uint64 * 17), ("max_level", C.c_uint32), ("reserved", C.c_uint32), ("max_dev", C.c_double), ("ms_device", C.c_double)]
+    RESULT_BYTES = 184
+
+    def result_bytes(self):
+        return bytes(self)[:self.RESULT_BYTES]
+
+
+# gsdf_loop_measure / gsdf_layer_measure (gsdf_hip.h) as numpy records: one per loop in loop order, one per layer
+LOOP_MEASURE_DTYPE = np.dtype([("area", "<f8"), ("length", "<f8"), ("bbox", "<f4", (4,)), ("n_verts", "<u4"), ("layer", "<u4")])
+LAYER_MEASURE_DTYPE = np.dtype([("area", "<f8"), ("length", "<f8"), ("bbox", "<f4", (4,)), ("n_loops", "<u4"), ("n_verts", "<u4")])
+
+
 # gsdf_shell (gsdf_hip.h) as a numpy record: one per shell, in increasing order of the label (the shell's smallest vertex number)
 SHELL_DTYPE = np.dtype([("n_verts", "<u8"), ("n_tris", "<u8"), ("nonfinite", "<u8"), ("edges", "<u8"), ("boundary_edges", "<u8"),
                         ("nonmanifold_edges", "<u8"), ("misoriented_edges", "<u8"), ("euler", "<i8"), ("area", "<f8"), ("volume", "<f8"),
@@ -338,6 +360,11 @@ def lib():
         L.gsdf_hip_contour_stats_get.argtypes = [C.c_void_p, C.POINTER(ContourStats)]
         L.gsdf_hip_contour_destroy.argtypes = [C.c_void_p]
         L.gsdf_hip_contour_destroy.restype = None
+        L.gsdf_hip_contour_create.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_void_p)]
+        L.gsdf_hip_contour_simplify.argtypes = [C.c_void_p, C.POINTER(ContourSimplifyOpts), C.POINTER(C.c_void_p), C.POINTER(ContourSimplifyStats)]
+        L.gsdf_hip_contour_measures.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.gsdf_hip_contour_measures_ms.argtypes = []
+        L.gsdf_hip_contour_measures_ms.restype = C.c_double
         L.gsdf_hip_brick_owner.restype = C.c_uint32
         L.gsdf_hip_brick_owner.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         L.gsdf_hip_slab_range.restype = None
@@ -1079,11 +1106,71 @@ class ContourHIP:
         _check(lib().gsdf_hip_slice3(sdf3._h, np.float32(res), z.ctypes.data if len(z) else None, len(z), C.byref(o), C.byref(h)))
         return cls(h)
 
+    @classmethod
+    def from_arrays(cls, xy, loop_start, loop_layer=None, n_layers=1, keys=None):
+        """gsdf_hip_contour_create: host loops on the device. xy (n, 2) float32, loop_start n_loops + 1, loop_layer n_loops (None: all 0),
+        keys n (None: they read back as 0)."""
+        xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        loop_start = np.ascontiguousarray(loop_start, np.uint32).reshape(-1)
+        n_loops = max(len(loop_start) - 1, 0)
+        if loop_layer is not None:
+            loop_layer = np.ascontiguousarray(loop_layer, np.uint32).reshape(-1)
+            if len(loop_layer) != n_loops:
+                raise ValueError(f"from_arrays: {len(loop_layer)} layers for {n_loops} loops")
+        if keys is not None:
+            keys = np.ascontiguousarray(keys, np.uint32).reshape(-1)
+            if len(keys) != len(xy):
+                raise ValueError(f"from_arrays: {len(keys)} keys for {len(xy)} vertices")
+        h = C.c_void_p()
+        _check(lib().gsdf_hip_contour_create(xy.ctypes.data if len(xy) else None, len(xy), loop_start.ctypes.data if len(loop_start) else None, n_loops,
+                                             None if loop_layer is None else loop_layer.ctypes.data, int(n_layers),
+                                             None if keys is None else keys.ctypes.data, C.byref(h)))
+        return cls(h)
+
     @property
     def stats(self):
         st = ContourStats()
         _check(lib().gsdf_hip_contour_stats_get(self._h, C.byref(st)))
         return st
+
+    def simplify(self, tol, levels=8, passes=1, dry=False):
+        """gsdf_hip_contour_simplify: the loops without the vertices that lie within tol of a dyadic chord of their loop (gsdf_hip.h,
+        "contours: simplify and measures"): (a new ContourHIP, ContourSimplifyStats). dry: (None, ContourSimplifyStats)."""
+        o = ContourSimplifyOpts(np.float32(tol), int(levels), int(passes), int(bool(dry)))
+        st, h = ContourSimplifyStats(), C.c_void_p()
+        _check(lib().gsdf_hip_contour_simplify(self._h, C.byref(o), None if dry else C.byref(h), C.byref(st)))
+        return (None if dry else ContourHIP(h)), st
+
+    def simplify_to(self, max_verts, tol0, levels=8, passes=1):
+        """The first of tol0, 2 tol0, 4 tol0, ... (float32 doubling: exact) whose simplification has at most max_verts vertices, found by
+        dry runs (one pass never keeps more at a larger tol); then those loops: (ContourHIP, ContourSimplifyStats, tol). ValueError for
+        tol0 <= 0, or when +Inf still keeps more (every loop keeps ceil(n / 2^kmax) >= 3 vertices)."""
+        tol = np.float32(tol0)
+        if not tol > 0:
+            raise ValueError(f"simplify_to: tol0 must be positive to be doubled, not {float(tol)!r}")
+        _, st = self.simplify(np.inf, levels, passes, dry=True)
+        if st.n_verts_out > max_verts:
+            raise ValueError(f"simplify_to: {st.n_verts_out} vertices are kept at any tol with levels {int(levels)} and passes {int(passes)}, more than {max_verts}")
+        while True:
+            _, st = self.simplify(tol, levels, passes, dry=True)
+            if st.n_verts_out <= max_verts:
+                c, st = self.simplify(tol, levels, passes)
+                return c, st, tol
+            with np.errstate(over="ignore"):
+                tol = np.float32(tol * np.float32(2))
+
+    def measures(self):
+        """gsdf_hip_contour_measures: (loops, layers) as numpy records (LOOP_MEASURE_DTYPE per loop, LAYER_MEASURE_DTYPE per layer):
+        signed area, length and box, summed on the device as integers (order-independent to the bit)."""
+        loops = np.zeros(self.n_loops, LOOP_MEASURE_DTYPE)
+        layers = np.zeros(self.n_layers, LAYER_MEASURE_DTYPE)
+        _check(lib().gsdf_hip_contour_measures(self._h, loops.ctypes.data if self.n_loops else None, layers.ctypes.data if self.n_layers else None))
+        return loops, layers
+
+    @staticmethod
+    def measures_ms():
+        """Device milliseconds (HIP events) of this thread's last measures()."""
+        return float(lib().gsdf_hip_contour_measures_ms())
 
     def loops(self, layer=None):
         """The loops (of one layer, or of all) as (n, 2) float32 arrays, in the handle's order."""

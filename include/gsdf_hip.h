@@ -1074,8 +1074,8 @@ int gsdf_hip_mesh_dualcontour_indexed(gsdf_program* p, float res, int chiseled, 
  *   are left out), ms_device = their sum. Bytes 0 .. 63 of the record are a function of the inputs alone.
  * Errors. GSDF_ERR_DIMENSION: gsdf_hip_contour2 on a 3-D program, gsdf_hip_slice3 on a 2-D one. GSDF_ERR_BAD_ARGUMENT: the lattice
  *   rules above, n_z == 0, a null z. GSDF_ERR_CAPACITY: 2^32 vertices or more. Blocking; the handle is independent of the program
- *   afterwards. Out of scope: DXF / G-code, polyline simplification and arc fitting, tool offsets (Offset2D in the tree is exact),
- *   infill, sharded or gathered contours, a fused lattice kernel, asymptotic-decider saddles, areas on the device.
+ *   afterwards. Out of scope: DXF / G-code, arc fitting, tool offsets (Offset2D in the tree is exact), infill, sharded or gathered
+ *   contours, a fused lattice kernel, asymptotic-decider saddles. (Simplification and the loops' areas on the device: the next section.)
  * Kernels: gsdf_amd/csrc/kernels_contour.h (abi_contour.hip); a numpy restatement over the oracle: tests/contourref.py. */
 typedef struct gsdf_contour gsdf_contour; /* loops, resident in HBM */
 #define GSDF_CONTOUR_DEFAULT_MAX_NODES 16777216 /* 2^24 nodes: 0.4 GB of workspace */
@@ -1094,6 +1094,115 @@ int gsdf_hip_contour_counts(const gsdf_contour* c, uint32_t* n_layers, uint64_t*
 int gsdf_hip_contour_read(const gsdf_contour* c, float* xy, uint32_t* keys, uint32_t* loop_start, uint32_t* loop_layer);
 int gsdf_hip_contour_stats_get(const gsdf_contour* c, gsdf_contour_stats* st);
 void gsdf_hip_contour_destroy(gsdf_contour* c);
+
+/* ---- contours: simplify and measures (no reference counterpart) -------------------------------------------------------------------
+ *
+ * The tracer returns one vertex per cut lattice edge: a straight side is hundreds of collinear points. What a cutter or a slicer asks
+ * of loops before it takes them: fewer vertices within a stated deviation, and each loop's area, length and box. All of it runs on the
+ * device, on any gsdf_contour handle (traced, uploaded or simplified), and is a function of the handle's arrays and the options alone,
+ * to the byte: NOT of the order in which threads arrive. Kernels: gsdf_amd/csrc/kernels_contour_simplify.h (abi_contour.hip); a numpy
+ * restatement: tests/contoursimpref.py.
+ *
+ * gsdf_hip_contour_create uploads host loops (an SVG read back, or any polygons): xy 2 n_verts floats, loop_start n_loops + 1 (loop q
+ *   is the vertices loop_start[q] .. loop_start[q + 1] - 1, in order), loop_layer n_loops or NULL (all 0), keys n_verts or NULL (then
+ *   they read back as 0). The device of the calling thread (gsdf_hip_init). GSDF_ERR_BAD_ARGUMENT, refused before anything is
+ *   allocated, the text names the loop or the vertex: loop_start[0] != 0; loop_start[n_loops] != n_verts; a loop of fewer than 3
+ *   vertices; loop_layer decreasing, or >= n_layers (so n_layers == 0); a NaN or infinite coordinate. n_loops == 0 or n_verts == 0:
+ *   GSDF_ERR_EMPTY_BUFFERS; n_verts >= 2^32: GSDF_ERR_CAPACITY. Every accessor above works on the result; its gsdf_contour_stats has
+ *   n_verts, n_loops and n_layers set, every other integer 0, the times 0. The same holds for a handle gsdf_hip_contour_simplify made.
+ *   Every coordinate of every handle is finite (the tracer makes no other, this call takes no other).
+ *
+ * gsdf_hip_contour_simplify: dyadic chord simplification. tol in the coordinates' unit, levels 1 .. 16 (0: 8), passes 1 .. 8 (0: 1).
+ * One pass, per loop. The loop's vertices are p_0 .. p_(n-1), p_0 its leader (first vertex); read it as the open polyline p_0 .. p_n
+ *   with p_n = p_0. kmax = the largest k <= levels with 3 2^k <= n (0 for n < 6: such a loop is unchanged). For k = 1 .. kmax and
+ *   m = 0, 1, ..., the SPAN (k, m) runs from s = m 2^k to e = min(s + 2^k, n); a span with e - s < 2 has no interior and does not
+ *   count. A span is ACCEPTABLE iff every interior vertex p_j (s < j < e) has q2(p_s, p_e, p_j) <= tol2, tol2 = (double)tol (double)tol.
+ * The distance q2(a, b, p): every coordinate taken as (double)float32 (exact); every operation below is one IEEE float64 operation,
+ *   in this order, none contracted (the library is built with -ffp-contract=off):
+ *     u = b - a;  dd = u.x u.x + u.y u.y;  w = p - a;  t = w.x u.x + w.y u.y
+ *     if dd == 0 or t <= 0:  q2 = w.x w.x + w.y w.y
+ *     else if t >= dd:       v = p - b,  q2 = v.x v.x + v.y v.y
+ *     else:                  cr = w.x u.y - w.y u.x,  q2 = (cr cr) / dd
+ *   the squared distance of p to the SEGMENT a b (not to the line). A comparison with a NaN is false (no finite input makes one).
+ * Dropping and keeping. Vertex j is DROPPED iff it is interior to some acceptable span of its loop; every other vertex is KEPT. The
+ *   output has the same loops, in the same order and in the same layers, each its kept vertices in order, their coordinate bits and
+ *   keys carried over; loop_start is recomputed. Position 0 is interior to no span: leaders stay, and so does the loop order.
+ * Guarantees (derived; tests/test_contour_simplify_ref.py holds the restatement to them). Vertices m 2^kmax are interior to no span:
+ *   every loop keeps at least ceil(n / 2^kmax) >= 3 vertices. Dyadic spans nest (two of them are disjoint inside or one holds the
+ *   other), so the kept neighbours of a dropped vertex are exactly the ends of the MAXIMAL acceptable span around it (the acceptable
+ *   span no acceptable span contains), and the vertex lies within tol of the segment that replaces it. The tol-neighbourhood of a
+ *   segment is convex: the Hausdorff distance between the old and the new loop is <= tol both ways, and |area change| <= tol x (old
+ *   perimeter). Raising tol or levels only drops more vertices.
+ * passes repeats the rule on the previous pass's result with the same tol; the deviations add: <= passes tol to the original. A second
+ *   pass removes what the dyadic alignment keeps (a rectangle with 37 and 41 collinear vertices per side, 156 in all, keeps 19
+ *   after one pass at tol 0, 10 after two, 6 after three).
+ * NOT promised: that the result is free of self-intersections; that two loops closer than 2 tol stay apart. Out of scope: arc
+ *   fitting, DXF / G-code, optimal (Douglas-Peucker / Imai-Iri) vertex counts.
+ * Statistics. Bytes 0 .. 183 (n_verts_in .. max_dev) are a function of the inputs alone: n_verts_out of the last pass; loops_changed
+ *   = loops that lost a vertex, summed over passes; spans[k] = maximal acceptable spans of level k, summed over passes; max_level =
+ *   the largest k with spans[k] > 0 (0: none); max_dev = the correctly rounded float64 square root of the largest q2 of any dropped
+ *   vertex against the chord of its maximal span, over all passes (on the device an unsigned 64-bit maximum over the bit patterns
+ *   of non-negative doubles, as the adaptive simplification's max_err), 0 if nothing was dropped. ms_device: HIP events around the
+ *   kernels of every pass (the host's waits between them left out).
+ * dry != 0 fills the statistics and builds no handle: out may be NULL, and is set to NULL if it is not.
+ * Errors. GSDF_ERR_BAD_ARGUMENT: tol NaN or < 0 (+Inf is allowed: every span is acceptable); levels > 16; passes > 8; out NULL
+ *   without dry. A handle without loops gives a handle without loops.
+ *
+ * gsdf_hip_contour_measures: per loop (loops: n_loops records, loop order, or NULL) and per layer (layers: n_layers records, or NULL)
+ *   the signed area (the part on the left: outer boundaries > 0, holes < 0), the length and the box, order-independent to the bit by
+ *   the scheme of "report and extract" above. e = the smallest integer >= -125 with |x| < 2^e for every coordinate of the handle (from
+ *   the largest |bits|: e = max(biased exponent, 1) - 126). Per vertex j of a loop, with its successor j+1 (the leader behind the last),
+ *   coordinates as (double)float32, one IEEE float64 operation each, none contracted:
+ *     area term   = x_j y_(j+1) - x_(j+1) y_j       (both products are exact: 24 x 24 bits; ONE rounded subtraction)
+ *     length term = sqrt(dx dx + dy dy), dx = x_(j+1) - x_j, dy likewise   (correctly rounded square root)
+ *   |area term| < 2^(2e+1) and length term < 2^(e+3/2) (|dx|, |dy| < 2^(e+1)). Each term is multiplied by the power of two 2^(61-2e)
+ *   resp. 2^(60-e) (exact), rounded to the nearest integer, ties to even: |q| < 2^62 resp. < 2^61.5. The q are summed as INTEGERS
+ *   (on the device: q's low 32 bits and its arithmetic-shifted rest in separate 64-bit words, which the 2^32 vertices a handle can
+ *   hold cannot overflow). The result is that integer converted to float64 with ONE rounding (to nearest even) times the inverse
+ *   power of two (exact: never subnormal); area = that / 2 (exact). A layer's sums are the integer sums of its loops, converted
+ *   likewise. bbox = min x, min y, max x, max y of the vertices, compared as order-preserving float32 bits (-0 below +0); a layer
+ *   without a loop has min = +inf, max = -inf, sums 0. Error of the quantisation: at most n / 2 units of 2^(2e-62) for the area of
+ *   n vertices, i.e. n 2^-65 of the square [-2^e, 2^e]^2 that holds them, and n / 2 units of 2^(e-60) for the length: far below what
+ *   float32 coordinates carry. Derived, not measured. gsdf_hip_contour_measures_ms: the device time (HIP events) of the calling
+ *   thread's last gsdf_hip_contour_measures, 0 before the first. */
+typedef struct gsdf_contour_simplify_opts {
+  float tol;       /* >= 0, +Inf allowed */
+  uint32_t levels; /* 1 .. 16; 0 = 8 */
+  uint32_t passes; /* 1 .. 8; 0 = 1 */
+  uint32_t dry;    /* non-zero: statistics only */
+} gsdf_contour_simplify_opts;
+GSDF_ABI_ASSERT(sizeof(gsdf_contour_simplify_opts) == 16, "gsdf_contour_simplify_opts is 16 bytes");
+GSDF_ABI_ASSERT(offsetof(gsdf_contour_simplify_opts, levels) == 4 && offsetof(gsdf_contour_simplify_opts, passes) == 8 && offsetof(gsdf_contour_simplify_opts, dry) == 12, "gsdf_contour_simplify_opts fields");
+typedef struct gsdf_contour_simplify_stats {
+  uint64_t n_verts_in, n_verts_out, n_loops, loops_changed;
+  uint64_t spans[17]; /* [k]: maximal acceptable spans of level k ([0] stays 0) */
+  uint32_t max_level, reserved;
+  double max_dev;
+  double ms_device;
+} gsdf_contour_simplify_stats;
+GSDF_ABI_ASSERT(sizeof(gsdf_contour_simplify_stats) == 192, "gsdf_contour_simplify_stats is 192 bytes");
+GSDF_ABI_ASSERT(offsetof(gsdf_contour_simplify_stats, n_loops) == 16 && offsetof(gsdf_contour_simplify_stats, spans) == 32 && offsetof(gsdf_contour_simplify_stats, max_level) == 168, "gsdf_contour_simplify_stats counts");
+GSDF_ABI_ASSERT(offsetof(gsdf_contour_simplify_stats, max_dev) == 176 && offsetof(gsdf_contour_simplify_stats, ms_device) == 184, "gsdf_contour_simplify_stats deviation and cost");
+typedef struct gsdf_loop_measure {
+  double area, length;
+  float bbox[4]; /* min x y, max x y */
+  uint32_t n_verts, layer;
+} gsdf_loop_measure;
+GSDF_ABI_ASSERT(sizeof(gsdf_loop_measure) == 40, "gsdf_loop_measure is 40 bytes");
+GSDF_ABI_ASSERT(offsetof(gsdf_loop_measure, length) == 8 && offsetof(gsdf_loop_measure, bbox) == 16 && offsetof(gsdf_loop_measure, n_verts) == 32 && offsetof(gsdf_loop_measure, layer) == 36, "gsdf_loop_measure fields");
+typedef struct gsdf_layer_measure {
+  double area, length;
+  float bbox[4];
+  uint32_t n_loops, n_verts;
+} gsdf_layer_measure;
+GSDF_ABI_ASSERT(sizeof(gsdf_layer_measure) == 40, "gsdf_layer_measure is 40 bytes");
+GSDF_ABI_ASSERT(offsetof(gsdf_layer_measure, length) == 8 && offsetof(gsdf_layer_measure, bbox) == 16 && offsetof(gsdf_layer_measure, n_loops) == 32 && offsetof(gsdf_layer_measure, n_verts) == 36, "gsdf_layer_measure fields");
+int gsdf_hip_contour_create(const float* xy, uint64_t n_verts, const uint32_t* loop_start, uint64_t n_loops, const uint32_t* loop_layer /* NULL: all 0 */,
+                            uint32_t n_layers, const uint32_t* keys /* NULL: read back as 0 */, gsdf_contour** out);
+int gsdf_hip_contour_simplify(const gsdf_contour* c, const gsdf_contour_simplify_opts* o, gsdf_contour** out /* NULL allowed iff dry */,
+                              gsdf_contour_simplify_stats* st /* optional */);
+int gsdf_hip_contour_measures(const gsdf_contour* c, gsdf_loop_measure* loops /* n_loops or NULL */, gsdf_layer_measure* layers /* n_layers or NULL */);
+double gsdf_hip_contour_measures_ms(void);
 
 /* ---- multi-GPU (one process per GPU). The meshers shard with NO data-path collective (shard_rank / shard_count above); the
  * one exchange is the final variable-length gather of the ranks' results, over xGMI, inside this library: a Go caller needs no

@@ -6,6 +6,8 @@ package gsdfaux
 // and SliceHIP the contours of a 3-D part at the given heights, on the device (gsdf_hip_contour2 / gsdf_hip_slice3): closed loops
 // in order of travel with the part on the left (outer boundaries counter-clockwise, holes clockwise), ordered by (layer, smallest
 // edge key), byte for byte the same on every run. The reference has no counterpart: its only 2-D output is RenderPNGFile's picture.
+// Behind the tracer: NewContourHIP takes host loops, Simplify drops vertices within a tolerance of dyadic chords and Measures sums
+// the loops' areas, lengths and boxes, all on the device (gsdf_hip_contour_create / _simplify / _measures).
 
 /*
 #cgo CFLAGS: -I${SRCDIR}/../third_party/gsdf_amd/include
@@ -17,6 +19,7 @@ import "C"
 
 import (
 	"errors"
+	"math"
 	"runtime"
 
 	"github.com/soypat/geometry/ms2"
@@ -94,4 +97,121 @@ func SliceHIP(sdf *gleval.SDF3HIP, res float32, z []float32, maxNodes uint64) (*
 		return nil, errors.New("gsdf_hip: " + C.GoString(C.gsdf_hip_last_error()))
 	}
 	return contoursFromHandle(h)
+}
+
+// NewContourHIP makes a ContoursHIP of host loops (an SVG read back, or any polygons) after the checks of gsdf_hip_contour_create:
+// loopStart has one entry more than there are loops, every loop has 3 vertices or more, loopLayer (nil: all 0) does not decrease
+// and stays below layers, every coordinate is finite. keys may be nil (then they are 0).
+func NewContourHIP(verts []ms2.Vec, loopStart, loopLayer []uint32, layers int, keys []uint32) (*ContoursHIP, error) {
+	c := &ContoursHIP{Verts: verts, Keys: keys, LoopStart: loopStart, LoopLayer: loopLayer, Layers: layers}
+	h, err := c.upload()
+	if err != nil {
+		return nil, err
+	}
+	return contoursFromHandle(h)
+}
+
+// upload puts the loops on the device of the calling thread; the caller destroys the handle.
+func (c *ContoursHIP) upload() (*C.gsdf_contour, error) {
+	if len(c.Verts) == 0 || len(c.LoopStart) < 2 {
+		return nil, errors.New("gsdfaux: no loops")
+	}
+	nLoops := len(c.LoopStart) - 1
+	if (c.Keys != nil && len(c.Keys) != len(c.Verts)) || (c.LoopLayer != nil && len(c.LoopLayer) != nLoops) {
+		return nil, errors.New("gsdfaux: keys or loop layers do not match the vertices or loops")
+	}
+	var keys, layer *C.uint32_t
+	if c.Keys != nil {
+		keys = (*C.uint32_t)(&c.Keys[0])
+	}
+	if c.LoopLayer != nil {
+		layer = (*C.uint32_t)(&c.LoopLayer[0])
+	}
+	var h *C.gsdf_contour
+	rc := C.gsdf_hip_contour_create((*C.float)(&c.Verts[0].X), C.uint64_t(len(c.Verts)), (*C.uint32_t)(&c.LoopStart[0]), C.uint64_t(nLoops), layer, C.uint32_t(c.Layers), keys, &h)
+	runtime.KeepAlive(c)
+	if rc != 0 {
+		return nil, errors.New("gsdf_hip: " + C.GoString(C.gsdf_hip_last_error()))
+	}
+	return h, nil
+}
+
+// SimplifyStatsHIP says what Simplify did: everything but DeviceMillis is a function of the loops and the arguments alone.
+type SimplifyStatsHIP struct {
+	VertsIn, VertsOut, Loops, LoopsChanged uint64
+	Spans                                  [17]uint64 // maximal acceptable spans by level, summed over passes
+	MaxLevel                               int
+	MaxDev                                 float64 // the largest distance of a dropped vertex to the segment that replaces it (per pass)
+	DeviceMillis                           float64
+}
+
+// Simplify drops, on the device, the vertices that lie within tol of a dyadic chord of their loop (gsdf_hip_contour_simplify: the
+// contract is in gsdf_hip.h). levels 1 .. 16 (0: 8), passes 1 .. 8 (0: 1); the result lies within passes x tol of c, both ways, keeps
+// every loop, its first vertex and at least 3 vertices of it. c is not changed.
+func (c *ContoursHIP) Simplify(tol float32, levels, passes int) (*ContoursHIP, SimplifyStatsHIP, error) {
+	var stats SimplifyStatsHIP
+	if len(c.LoopStart) < 2 {
+		return &ContoursHIP{LoopStart: []uint32{0}, Layers: c.Layers}, stats, nil
+	}
+	h, err := c.upload()
+	if err != nil {
+		return nil, stats, err
+	}
+	defer C.gsdf_hip_contour_destroy(h)
+	so := C.gsdf_contour_simplify_opts{tol: C.float(tol), levels: C.uint32_t(levels), passes: C.uint32_t(passes)}
+	var sst C.gsdf_contour_simplify_stats
+	var out *C.gsdf_contour
+	if rc := C.gsdf_hip_contour_simplify(h, &so, &out, &sst); rc != 0 {
+		return nil, stats, errors.New("gsdf_hip: " + C.GoString(C.gsdf_hip_last_error()))
+	}
+	stats = SimplifyStatsHIP{VertsIn: uint64(sst.n_verts_in), VertsOut: uint64(sst.n_verts_out), Loops: uint64(sst.n_loops), LoopsChanged: uint64(sst.loops_changed),
+		MaxLevel: int(sst.max_level), MaxDev: float64(sst.max_dev), DeviceMillis: float64(sst.ms_device)}
+	for k := range stats.Spans {
+		stats.Spans[k] = uint64(sst.spans[k])
+	}
+	res, err := contoursFromHandle(out)
+	return res, stats, err
+}
+
+// LoopMeasureHIP is one loop's (one layer's) signed area (outer boundaries > 0, holes < 0), length and box.
+type LoopMeasureHIP struct {
+	Area, Length float64
+	Min, Max     ms2.Vec
+	Verts        int
+	Layer        int // of a loop; of a layer: its number of loops
+}
+
+// Measures sums, on the device, area, length and box of every loop and of every layer (gsdf_hip_contour_measures): integer sums, the
+// same bits whatever the order of the threads. In a layer's record Layer holds the number of its loops.
+func (c *ContoursHIP) Measures() (loops, layers []LoopMeasureHIP, err error) {
+	layers = make([]LoopMeasureHIP, c.Layers)
+	inf := float32(math.Inf(1))
+	for k := range layers {
+		layers[k].Min, layers[k].Max = ms2.Vec{X: inf, Y: inf}, ms2.Vec{X: -inf, Y: -inf}
+	}
+	if len(c.LoopStart) < 2 {
+		return nil, layers, nil
+	}
+	h, err := c.upload()
+	if err != nil {
+		return nil, nil, err
+	}
+	defer C.gsdf_hip_contour_destroy(h)
+	lm := make([]C.gsdf_loop_measure, len(c.LoopStart)-1)
+	ym := make([]C.gsdf_layer_measure, c.Layers)
+	if rc := C.gsdf_hip_contour_measures(h, &lm[0], &ym[0]); rc != 0 {
+		return nil, nil, errors.New("gsdf_hip: " + C.GoString(C.gsdf_hip_last_error()))
+	}
+	loops = make([]LoopMeasureHIP, len(lm))
+	for q := range lm {
+		m := &lm[q]
+		loops[q] = LoopMeasureHIP{Area: float64(m.area), Length: float64(m.length), Min: ms2.Vec{X: float32(m.bbox[0]), Y: float32(m.bbox[1])},
+			Max: ms2.Vec{X: float32(m.bbox[2]), Y: float32(m.bbox[3])}, Verts: int(m.n_verts), Layer: int(m.layer)}
+	}
+	for k := range ym {
+		m := &ym[k]
+		layers[k] = LoopMeasureHIP{Area: float64(m.area), Length: float64(m.length), Min: ms2.Vec{X: float32(m.bbox[0]), Y: float32(m.bbox[1])},
+			Max: ms2.Vec{X: float32(m.bbox[2]), Y: float32(m.bbox[3])}, Verts: int(m.n_verts), Layer: int(m.n_loops)}
+	}
+	return loops, layers, nil
 }
