@@ -20,6 +20,9 @@ binary STL's of the same mesh, and the weld's device time.
                          of the plane of every face touching the cell: flat faces collapse into large cells, thread flanks keep theirs.
                          With --max-tris N: the first tolerance of TOL, 2 TOL, 4 TOL, ... x res that leaves at most N faces
     --levels N           with --adaptive: the number of nested grids (8: cells of up to 128 finest cells)
+    --clean              then drop the faces that clustering folded onto each other: of the faces over one set of three vertices at
+                         most one stays, opposite pairs cancel (gsdf_hip_indexed_clean, on device; after --simplify / --adaptive,
+                         before --project). Prints what it dropped; with --report also the cleaned mesh's report
     --project [ITERS]    then move every vertex onto the part's surface by up to ITERS (8) Newton steps along the field's gradient
                          (gsdf_hip_indexed_project, on device: step res / 4, on the surface within res / 1024, never further than the
                          simplify cell -- or res -- from where it was): clustering pulls the surface inwards on every convex part
@@ -63,7 +66,8 @@ def print_report(name, ix):
               f"misoriented {s['misoriented_edges']}")
 
 
-def main(argv=None):
+def parse_args(argv=None):
+    """The command line, checked: needs no device."""
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("scene", choices=SCENES)
     ap.add_argument("--resdiv", type=int, default=400, help="resolution = bounding-box diagonal / resdiv (the examples' -resdiv)")
@@ -77,6 +81,7 @@ def main(argv=None):
     ap.add_argument("--max-tris", type=int, default=0, metavar="N", help="cluster in cells of 2 res, 4 res, ... until at most N faces are left")
     ap.add_argument("--adaptive", type=float, default=None, metavar="TOL", help="cluster adaptively: a cell's mean stays within TOL x res of its faces' planes")
     ap.add_argument("--levels", type=int, default=8, metavar="N", help="with --adaptive: nested grids, 1 .. 16")
+    ap.add_argument("--clean", action="store_true", help="after the clustering: keep at most one face per set of three vertices, cancel opposite pairs")
     ap.add_argument("--project", type=int, nargs="?", const=8, default=None, metavar="ITERS", help="move the vertices onto the surface by up to ITERS (8) Newton steps")
     ap.add_argument("--before-project", default=None, metavar="F", help="with --project: also write the mesh before the projection to F")
     ap.add_argument("--renderer", choices=["octree", "dualcontour"], default="octree", help="the mesher: octree + weld, or dual contouring straight to an indexed mesh")
@@ -94,6 +99,11 @@ def main(argv=None):
         ap.error("--adaptive with --max-tris needs a tolerance > 0 to double")
     if args.thickness is not None and not args.thickness >= 0:
         ap.error("--thickness needs a THIN >= 0")
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
 
     import numpy as np
     from gsdf_amd import hip
@@ -159,6 +169,15 @@ def main(argv=None):
             ix.normals(sdf, np.float32(float(res) * 1e-3))
         if args.report:
             print_report(args.scene + " simplified", ix)
+    if args.clean:
+        folded = ix
+        ix, cs = folded.clean(merge=False, faces=True)
+        print(f"{args.scene} cleaned: V {folded.n_verts} -> {ix.n_verts}, F {folded.n_tris} -> {ix.n_tris} ({cs.opposite_faces} opposite and {cs.duplicate_faces} "
+              f"duplicate faces dropped, {cs.degenerate} degenerate; {cs.face_sets} sets, {cs.cancelled_sets} cancelled, the largest of {cs.largest_set} faces; "
+              f"device {cs.ms_merge + cs.ms_faces + cs.ms_result:.3f} ms: merge {cs.ms_merge:.3f}, faces {cs.ms_faces:.3f}, result {cs.ms_result:.3f}; "
+              f"{cs.face_probes} probes of {cs.face_table_cells} cells, {cs.face_attempts} pass)")
+        if args.report:
+            print_report(args.scene + " cleaned", ix)
     if project:
         before = ix
         if args.before_project:

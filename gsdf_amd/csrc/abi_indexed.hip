@@ -3,7 +3,7 @@
 // projection of the vertices onto a program's field (its kernel is abi_eval.hip's: project_dev), and the numbering of dual
 // contouring's quads into a handle (indexed_from_cube_slots: abi_mesh.hip orders them and owns the evaluating stages).
 // Kernels: kernels_weld.h (weld, PLY, and the table / scan / remap every pass shares), kernels_topo.h (report, extract),
-// kernels_simplify.h (simplify), kernels_simplify_adaptive.h (adaptive simplify). No
+// kernels_simplify.h (simplify), kernels_simplify_adaptive.h (adaptive simplify), kernels_clean.h (clean). No
 // interpreter kernel is compiled here: of the meshers this unit needs mesh_march_dense alone, and abi_mesh.hip owns that.
 #include <algorithm>
 #include <cmath>
@@ -19,6 +19,7 @@
 #include "kernels_topo.h"
 #include "kernels_simplify.h"
 #include "kernels_simplify_adaptive.h"
+#include "kernels_clean.h"
 #include "abi_program.h"
 
 namespace {
@@ -893,6 +894,125 @@ extern "C" int gsdf_hip_indexed_simplify_adaptive(gsdf_indexed* ix, const gsdf_a
     nx->n_verts = V2;
     nx->n_tris = F2;
     nx->ms_device = r.ms_cells + r.ms_error + r.ms_faces;
+    *out = nx.release();
+  }
+  return GSDF_OK;
+}
+
+// ---- clean (kernels_clean.h) -----------------------------------------------------------------------------------------------------------
+extern "C" int gsdf_hip_indexed_clean(gsdf_indexed* ix, const gsdf_clean_opts* o, gsdf_indexed** out, gsdf_clean_stats* st) {
+  if (out) *out = nullptr;
+  if (!o) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  if (o->flags == 0) return fail(GSDF_ERR_BAD_ARGUMENT, "clean: no flags: nothing to do");
+  if (o->flags & ~(GSDF_CLEAN_MERGE_POSITIONS | GSDF_CLEAN_FACES)) return fail(GSDF_ERR_BAD_ARGUMENT, "clean: unknown flags " + std::to_string(o->flags));
+  if (o->reserved[0] != 0 || o->reserved[1] != 0 || o->reserved[2] != 0) return fail(GSDF_ERR_BAD_ARGUMENT, "clean: the reserved words must be 0");
+  if (!ix || (!out && !st)) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  HIP_TRY(hipSetDevice(ix->device));
+  const int dev = ix->device;
+  hipStream_t s = ix->stream;
+  const bool dry = out == nullptr, merge = (o->flags & GSDF_CLEAN_MERGE_POSITIONS) != 0, faces = (o->flags & GSDF_CLEAN_FACES) != 0;
+  const uint64_t V = ix->n_verts, F = ix->n_tris, S = 3 * F;
+  const unsigned nb_f = blocks_of(F), nb_s = blocks_of(S);
+  const char* nomem = "clean: no device memory for the workspace";
+  const char* floor_env = "GSDF_HIP_CLEAN_CELLS_MIN";
+  PoolBuf ctr, vtab, vcls, midx, ftab, fcell, named, keep, blk_cnt, blk_base, total, first, vnum;
+  if (!ctr.take(dev, sizeof(CleanCounters)) || !named.take(dev, V * 4) || !blk_cnt.take(dev, (size_t)nb_s * 4) || !blk_base.take(dev, (size_t)nb_s * 4))
+    return fail(GSDF_ERR_HIP, nomem);
+  CleanCounters* d_ctr = ctr.as<CleanCounters>();
+  EventPair ev_m, ev_f, ev_r;
+  if (!ev_m.make() || !ev_f.make() || !ev_r.make()) return fail(GSDF_ERR_HIP, "hipEventCreate failed");
+  HIP_TRY(hipMemsetAsync(d_ctr, 0, sizeof(CleanCounters), s));
+  // 1. the vertex table: 4 bytes per cell (the representative), cells from 2 V (at most V classes); every vertex's class; the faces
+  // over classes, in a copy (the handle's own faces stay as they are)
+  const unsigned* d_idx = ix->idx.as<unsigned>();
+  TableRun vrun, frun;
+  HIP_TRY(hipEventRecord(ev_m.a, s));
+  if (merge) {
+    if (!vcls.take(dev, V * 4) || !midx.take(dev, S * 4)) return fail(GSDF_ERR_HIP, nomem);
+    if (int rc = table_build("clean", floor_env, 2 * V, 4, dev, s, vtab, &d_ctr->vtab, [&](uint64_t cells) -> int {
+          HIP_TRY(hipMemsetAsync(vtab.p, 0xff, cells * 4, s));
+          HIP_TRY(hipMemsetAsync(&d_ctr->vtab, 0, sizeof(TableCounters), s));
+          LAUNCH(clean_vert_insert_kernel, grid_for(V, ix->num_cu, 16), BLOCK, s, ix->verts.as<unsigned>(), (unsigned long long)V, vtab.as<unsigned>(),
+                 (unsigned)(cells - 1), vcls.as<unsigned>(), &d_ctr->vtab);
+          return GSDF_OK;
+        }, &vrun))
+      return rc;
+    if (vrun.cells > ((uint64_t)1 << 31)) return fail(GSDF_ERR_CAPACITY, "clean: hash table capacity exceeded");  // (a cell number is 32 bits, all ones = none)
+    LAUNCH(clean_vert_class_kernel, grid_for(V, ix->num_cu, 16), BLOCK, s, vtab.as<unsigned>(), (unsigned long long)V, vcls.as<unsigned>(), d_ctr);
+    HIP_TRY(hipMemcpyAsync(midx.p, ix->idx.p, S * 4, hipMemcpyDeviceToDevice, s));
+    LAUNCH(remap_kernel, nb_s, BLOCK, s, midx.as<unsigned>(), (unsigned long long)S, vcls.as<unsigned>());
+    d_idx = midx.as<unsigned>();
+  }
+  HIP_TRY(hipEventRecord(ev_m.b, s));
+  // 2. the face table: per cell the representative (4 bytes), the two orientations' smallest faces (8) and counts (8); cells from
+  // 2 F (at most F sets). Then the rule. (The new handle's stream is made before the events: it is host work.)
+  IndexedPtr nx;
+  if (!dry)
+    if (int rc = indexed_new(dev, ix->num_cu, &nx)) return rc;
+  if (!dry && (!keep.take(dev, F) || !total.take(dev, 8) || !first.take(dev, V * 4) || !vnum.take(dev, V * 4))) return fail(GSDF_ERR_HIP, nomem);
+  auto tab_min = [&](uint64_t cells) { return (unsigned*)((uint8_t*)ftab.p + cells * 4); };
+  auto tab_cnt = [&](uint64_t cells) { return (unsigned*)((uint8_t*)ftab.p + cells * 12); };
+  HIP_TRY(hipEventRecord(ev_f.a, s));
+  if (faces) {
+    if (!fcell.take(dev, F * 4)) return fail(GSDF_ERR_HIP, nomem);
+    if (int rc = table_build("clean", floor_env, 2 * F, 20, dev, s, ftab, &d_ctr->ftab, [&](uint64_t cells) -> int {
+          HIP_TRY(hipMemsetAsync(ftab.p, 0xff, cells * 12, s));
+          HIP_TRY(hipMemsetAsync(tab_cnt(cells), 0, cells * 8, s));
+          HIP_TRY(hipMemsetAsync(&d_ctr->ftab, 0, sizeof(TableCounters), s));
+          LAUNCH(clean_face_insert_kernel, nb_f, BLOCK, s, d_idx, (unsigned long long)F, ftab.as<unsigned>(), tab_min(cells), tab_cnt(cells), (unsigned)(cells - 1),
+                 fcell.as<unsigned>(), &d_ctr->ftab);
+          return GSDF_OK;
+        }, &frun))
+      return rc;
+    if (frun.cells > ((uint64_t)1 << 31)) return fail(GSDF_ERR_CAPACITY, "clean: hash table capacity exceeded");
+  }
+  HIP_TRY(hipMemsetAsync(named.p, 0, V * 4, s));
+  LAUNCH(clean_decide_kernel, nb_f, BLOCK, s, d_idx, (unsigned long long)F, faces ? ftab.as<unsigned>() : nullptr, faces ? tab_min(frun.cells) : nullptr,
+         faces ? tab_cnt(frun.cells) : nullptr, faces ? fcell.as<unsigned>() : nullptr, named.as<unsigned>(), dry ? nullptr : keep.as<unsigned char>(),
+         blk_cnt.as<unsigned>(), d_ctr);
+  LAUNCH(block_scan_kernel, 1, 1024, s, blk_cnt.as<unsigned>(), nb_f, blk_base.as<unsigned>(), &d_ctr->kept);
+  LAUNCH(clean_named_kernel, grid_for(V, ix->num_cu, 8), BLOCK, s, named.as<unsigned>(), (unsigned long long)V, d_ctr);
+  HIP_TRY(hipEventRecord(ev_f.b, s));
+  CleanCounters hc{};
+  HIP_TRY(hipMemcpyAsync(&hc, d_ctr, sizeof hc, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  const uint64_t F2 = hc.kept;
+  if (hc.degenerate + hc.duplicate + hc.opposite + F2 != F || (faces && hc.face_sets != hc.ftab.distinct) || (merge && hc.merged >= V))
+    return fail(GSDF_ERR_HIP, "clean: internal error (the counts do not add up)");
+  // 3. extract's kernels over the classes: kept faces in order, classes by their smallest kept slot, the smallest member's data
+  uint64_t V2 = 0;
+  if (!dry) {
+    if (F2 == 0) return fail(GSDF_ERR_EMPTY_BUFFERS, "clean: nothing kept (every face is degenerate or cancels against an opposite one)");
+    const uint64_t S2 = 3 * F2;
+    const unsigned nb_s2 = blocks_of(S2);
+    if (!nx->idx.take(dev, S2 * 4)) return fail(GSDF_ERR_HIP, nomem);
+    HIP_TRY(hipEventRecord(ev_r.a, s));
+    HIP_TRY(hipMemsetAsync(first.p, 0xff, V * 4, s));
+    LAUNCH(topo_compact_kernel, nb_f, BLOCK, s, d_idx, keep.as<unsigned char>(), (unsigned long long)F, blk_base.as<unsigned>(), nx->idx.as<unsigned>(),
+           first.as<unsigned>());
+    LAUNCH(topo_owner_kernel, nb_s2, BLOCK, s, nx->idx.as<unsigned>(), (unsigned long long)S2, first.as<unsigned>(), blk_cnt.as<unsigned>());
+    if (int rc = scan_blocks(s, blk_cnt, nb_s2, blk_base, total, &V2)) return rc;
+    if (V2 != hc.named) return fail(GSDF_ERR_HIP, "clean: internal error (kept vertices)");
+    if (!nx->verts.take(dev, V2 * 12) || !nx->vkeys.take(dev, V2 * 8) || (ix->has_normals && !nx->normals.take(dev, V2 * 12))) return fail(GSDF_ERR_HIP, nomem);
+    LAUNCH(topo_renumber_kernel, nb_s2, BLOCK, s, nx->idx.as<unsigned>(), (unsigned long long)S2, first.as<unsigned>(), blk_base.as<unsigned>(), vnum.as<unsigned>(),
+           ix->verts.as<unsigned>(), ix->vkeys.as<unsigned long long>(), ix->has_normals ? ix->normals.as<unsigned>() : nullptr, nx->verts.as<unsigned>(),
+           nx->vkeys.as<unsigned long long>(), ix->has_normals ? nx->normals.as<unsigned>() : nullptr);
+    LAUNCH(remap_kernel, nb_s2, BLOCK, s, nx->idx.as<unsigned>(), (unsigned long long)S2, vnum.as<unsigned>());
+    HIP_TRY(hipEventRecord(ev_r.b, s));
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  gsdf_clean_stats r{};
+  r.n_verts_in = V; r.n_tris_in = F; r.merged_verts = hc.merged; r.degenerate = hc.degenerate; r.face_sets = hc.face_sets; r.cancelled_sets = hc.cancelled_sets;
+  r.duplicate_faces = hc.duplicate; r.opposite_faces = hc.opposite; r.largest_set = hc.largest; r.n_verts = hc.named; r.n_tris = F2;
+  r.ms_merge = ev_m.ms(); r.ms_faces = ev_f.ms(); r.ms_result = dry ? 0.0 : ev_r.ms();
+  r.vert_probes = merge ? vrun.head.probes : 0; r.vert_table_cells = vrun.cells; r.vert_attempts = vrun.attempts;
+  r.face_probes = faces ? frun.head.probes : 0; r.face_table_cells = frun.cells; r.face_attempts = frun.attempts;
+  if (st) *st = r;
+  if (!dry) {
+    nx->n_verts = V2;
+    nx->n_tris = F2;
+    nx->has_normals = ix->has_normals;
+    nx->ms_device = r.ms_merge + r.ms_faces + r.ms_result;
     *out = nx.release();
   }
   return GSDF_OK;

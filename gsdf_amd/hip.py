@@ -29,7 +29,7 @@ SYMBOLS = ["gsdf_hip_last_error", "gsdf_hip_init", "gsdf_hip_program_create", "g
            "gsdf_hip_mesh_read_records", "gsdf_hip_mesh_weld", "gsdf_hip_indexed_counts", "gsdf_hip_indexed_stats_get", "gsdf_hip_indexed_read",
            "gsdf_hip_indexed_normals", "gsdf_hip_indexed_read_normals", "gsdf_hip_indexed_ply", "gsdf_hip_indexed_host_ply", "gsdf_hip_indexed_destroy",
            "gsdf_hip_indexed_create", "gsdf_hip_indexed_report", "gsdf_hip_indexed_shells", "gsdf_hip_indexed_read_shell_of", "gsdf_hip_indexed_extract",
-           "gsdf_hip_indexed_simplify", "gsdf_hip_indexed_simplify_adaptive", "gsdf_hip_indexed_project", "gsdf_hip_indexed_read_fit", "gsdf_hip_mesh_dualcontour_indexed",
+           "gsdf_hip_indexed_simplify", "gsdf_hip_indexed_simplify_adaptive", "gsdf_hip_indexed_clean", "gsdf_hip_indexed_project", "gsdf_hip_indexed_read_fit", "gsdf_hip_mesh_dualcontour_indexed",
            "gsdf_hip_raycast3", "gsdf_hip_indexed_thickness",
            "gsdf_hip_contour2", "gsdf_hip_slice3", "gsdf_hip_contour_counts", "gsdf_hip_contour_read", "gsdf_hip_contour_stats_get", "gsdf_hip_contour_destroy",
            "gsdf_hip_contour_create", "gsdf_hip_contour_simplify", "gsdf_hip_contour_measures", "gsdf_hip_contour_measures_ms"]
@@ -134,6 +134,29 @@ class AdaptiveStats(C.Structure):
                 ("ms_cells", C.c_double), ("ms_error", C.c_double), ("ms_faces", C.c_double), ("probes", C.c_uint64), ("table_cells", C.c_uint64),
                 ("attempts", C.c_int32), ("reserved2", C.c_int32)]
     RESULT_BYTES = 224
+
+    def result_bytes(self):
+        return bytes(self)[:self.RESULT_BYTES]
+
+
+CLEAN_MERGE_POSITIONS, CLEAN_FACES = 1, 2  # gsdf_hip.h: GSDF_CLEAN_*
+
+
+class CleanOpts(C.Structure):
+    """gsdf_clean_opts (gsdf_hip.h): which of the two cleaning steps to run."""
+    _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class CleanStats(C.Structure):
+    """gsdf_clean_stats (gsdf_hip.h): what a clean merged and dropped; bytes 0 .. 87 (RESULT_BYTES) are a function of the mesh and the
+    flags alone, the rest says what the run cost."""
+    _fields_ = [("n_verts_in", C.c_uint64), ("n_tris_in", C.c_uint64), ("merged_verts", C.c_uint64), ("degenerate", C.c_uint64),
+                ("face_sets", C.c_uint64), ("cancelled_sets", C.c_uint64), ("duplicate_faces", C.c_uint64), ("opposite_faces", C.c_uint64),
+                ("largest_set", C.c_uint64), ("n_verts", C.c_uint64), ("n_tris", C.c_uint64),
+                ("ms_merge", C.c_double), ("ms_faces", C.c_double), ("ms_result", C.c_double),
+                ("vert_probes", C.c_uint64), ("vert_table_cells", C.c_uint64), ("face_probes", C.c_uint64), ("face_table_cells", C.c_uint64),
+                ("vert_attempts", C.c_int32), ("face_attempts", C.c_int32)]
+    RESULT_BYTES = 88
 
     def result_bytes(self):
         return bytes(self)[:self.RESULT_BYTES]
@@ -347,6 +370,7 @@ def lib():
         L.gsdf_hip_indexed_extract.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
         L.gsdf_hip_indexed_simplify.argtypes = [C.c_void_p, C.POINTER(SimplifyOpts), C.POINTER(C.c_void_p), C.POINTER(SimplifyStats)]
         L.gsdf_hip_indexed_simplify_adaptive.argtypes = [C.c_void_p, C.POINTER(AdaptiveOpts), C.POINTER(C.c_void_p), C.POINTER(AdaptiveStats)]
+        L.gsdf_hip_indexed_clean.argtypes = [C.c_void_p, C.POINTER(CleanOpts), C.POINTER(C.c_void_p), C.POINTER(CleanStats)]
         L.gsdf_hip_indexed_project.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(ProjectOpts), C.POINTER(C.c_void_p), C.POINTER(ProjectStats)]
         L.gsdf_hip_indexed_read_fit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.gsdf_hip_raycast3.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayOpts), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -942,6 +966,32 @@ class IndexedHIP:
         st, h = SimplifyStats(), C.c_void_p()
         _check(lib().gsdf_hip_indexed_simplify(self._h, C.byref(o), None if dry else C.byref(h), C.byref(st)))
         return (None if dry else IndexedHIP(h)), st
+
+    def clean(self, merge=False, faces=True, dry=False):
+        """gsdf_hip_indexed_clean: the mesh with vertices of equal position merged (merge), degenerate faces dropped, and of the faces
+        over one set of three vertices at most one kept (faces): (a new IndexedHIP, CleanStats). dry: (None, CleanStats)."""
+        o = CleanOpts(flags=(CLEAN_MERGE_POSITIONS if merge else 0) | (CLEAN_FACES if faces else 0))
+        st, h = CleanStats(), C.c_void_p()
+        _check(lib().gsdf_hip_indexed_clean(self._h, C.byref(o), None if dry else C.byref(h), C.byref(st)))
+        return (None if dry else IndexedHIP(h)), st
+
+    @classmethod
+    def from_soup(cls, tris):
+        """A triangle soup (F, 3, 3) float32 -- an STL read back, OctreeHIP.read()'s triangles -- as an indexed mesh: uploaded as 3 F
+        vertices with idx = arange, then clean(merge=True, faces=False), which joins the corners with equal positions:
+        (IndexedHIP, CleanStats). Corners that are merely close stay apart (gsdf_hip.h, "indexed meshes: clean")."""
+        t = np.ascontiguousarray(tris, np.float32).reshape(-1, 3, 3)
+        soup = cls.from_arrays(t.reshape(-1, 3), np.arange(3 * len(t), dtype=np.uint32).reshape(-1, 3))
+        try:
+            return soup.clean(merge=True, faces=False)
+        finally:
+            soup.close()
+
+    def read_normals(self):
+        """The normals the handle holds (V, 3) float32 -- computed by normals(), or carried by extract / clean; HipError if it has none."""
+        n = np.empty((self.n_verts, 3), np.float32)
+        _check(lib().gsdf_hip_indexed_read_normals(self._h, n.ctypes.data))
+        return n
 
     def simplify_to(self, max_tris, cell0, origin=(0, 0, 0)):
         """The first of cell0, 2 cell0, 4 cell0, ... (float32 doubling: exact) whose simplification has at most max_tris faces, found by

@@ -693,7 +693,8 @@ int gsdf_hip_indexed_extract(gsdf_indexed* ix, const uint8_t* keep_shell, int dr
  * gsdf_simplify_stats. Bytes 0 .. 79 (n_verts_in .. reserved) are a function of the mesh and the options alone; the rest says what
  *   this run cost. GSDF_HIP_SIMPLIFY_CELLS_MIN (environment) lowers the cluster table's first size so that tests can drive the
  *   grow-and-repeat path, as GSDF_HIP_TOPO_CELLS_MIN does.
- * Not done here: quadric edge-collapse, QEF placement of the representative, removing duplicate or opposite faces. (Adaptive
+ * Not done here: quadric edge-collapse, QEF placement of the representative. (Removing duplicate or opposite faces:
+ *   "indexed meshes: clean", below. Adaptive
  *   simplification, by error-bounded clustering over nested cells: "indexed meshes: adaptive simplify", below. Projecting the
  *   representatives back onto the field: gsdf_hip_indexed_project, below.) */
 typedef struct gsdf_simplify_opts {
@@ -781,7 +782,8 @@ int gsdf_hip_indexed_simplify(gsdf_indexed* ix, const gsdf_simplify_opts* o, gsd
  * Run to run. A welded mesh's last bits vary with the mesher's record order (see "simplify"), and here they can also flip an
  *   err <= tol decision, so two welds of one part may differ in a few clusters. A handle from gsdf_hip_mesh_dualcontour_indexed
  *   does not vary, so its adaptive result is reproducible byte for byte.
- * Not done here: edge-collapse, QEF placement, removing duplicate or opposite faces, un-flipping folded faces. */
+ * Not done here: edge-collapse, QEF placement, un-flipping folded faces. (Removing duplicate or opposite faces: "indexed meshes:
+ *   clean", below.) */
 typedef struct gsdf_adaptive_opts {
   float cell;        /* the finest cell's edge, > 0 and finite */
   float origin[3];   /* where cell (0, 0, 0) of every level starts; finite */
@@ -819,6 +821,99 @@ GSDF_ABI_ASSERT(offsetof(gsdf_adaptive_stats, cells) == 32 && offsetof(gsdf_adap
 GSDF_ABI_ASSERT(offsetof(gsdf_adaptive_stats, n_verts) == 184 && offsetof(gsdf_adaptive_stats, max_err) == 208 && offsetof(gsdf_adaptive_stats, exponent) == 216 &&
                 offsetof(gsdf_adaptive_stats, ms_cells) == 224, "gsdf_adaptive_stats result and cost");
 int gsdf_hip_indexed_simplify_adaptive(gsdf_indexed* ix, const gsdf_adaptive_opts* o, gsdf_indexed** out, gsdf_adaptive_stats* st);
+
+/* ---- indexed meshes: clean (no reference counterpart) ------------------------------------------------------------------------------
+ *
+ * Vertices with EQUAL positions merged, degenerate faces dropped, and of the faces over one set of three vertices at most one kept:
+ * what joins a triangle soup uploaded with gsdf_hip_indexed_create (an STL read back, any triangle list whose shared corners are
+ * the same floats) into an indexed mesh, and what removes the equal and opposite faces that clustering leaves where a wall is thinner
+ * than a cell ("simplify", "adaptive simplify"). All of it is integer work: the result is a function of the mesh and the flags
+ * alone, to the byte, under any order of arrival. Kernels: gsdf_amd/csrc/kernels_clean.h (abi_indexed.hip); a numpy restatement:
+ * tests/cleanref.py.
+ *
+ * Input. Any gsdf_indexed handle and gsdf_clean_opts: flags a non-empty subset of GSDF_CLEAN_MERGE_POSITIONS | GSDF_CLEAN_FACES, the
+ *   reserved words 0 -- anything else (flags == 0, an unknown bit, a non-zero reserved word) is GSDF_ERR_BAD_ARGUMENT, checked before
+ *   the handle is looked at.
+ * 1. Merge (only with GSDF_CLEAN_MERGE_POSITIONS). A vertex's POSITION KEY is its three float32 bit patterns, with 0x80000000 (-0)
+ *   replaced by 0. A vertex with a NaN or infinite coordinate is never merged: it is a class of its own. ALL vertices take part, used
+ *   or not. The vertices with one key form a CLASS, and every index that names a member is replaced by the class's SMALLEST vertex
+ *   number. merged_verts = the sum of (members - 1) over the classes. Without the flag every vertex is its own class, merged_verts 0.
+ * 2. Degenerate faces. After step 1 a face with two equal indices is DEGENERATE (the report's definition), counted in `degenerate`
+ *   -- the faces that were degenerate on input included -- and dropped.
+ * 3. Face sets (only with GSDF_CLEAN_FACES). Of a non-degenerate face (a, b, c), after step 1: its SET is the sorted triple
+ *   lo < mid < hi; its ORIENTATION is + if (a, b, c) is a rotation of (lo, mid, hi) and - if it is a rotation of (lo, hi, mid). Per
+ *   set, f = the number of its + faces and r = the number of its - faces. The rule, the whole of it:
+ *     f == r: every face of the set is dropped. The set is CANCELLED, and all f + r faces count as opposite_faces.
+ *     f != r: exactly ONE face is kept, the smallest-numbered face of the majority orientation, its corners in the order it has them
+ *             (not rotated). Of the dropped ones 2 min(f, r) count as opposite_faces and the other |f - r| - 1 as duplicate_faces.
+ *   face_sets = the distinct sets, cancelled_sets = those with f == r, largest_set = the largest f + r (0 where there is no set).
+ *   Without the flag every non-degenerate face is kept, and face_sets, cancelled_sets, duplicate_faces, opposite_faces and
+ *   largest_set are 0.
+ * 4. Result. The kept faces in their original order. Its vertices are the classes a kept face names, numbered by the smallest slot
+ *   3 g + c (g: the face's position among the kept faces) that names them, in increasing order -- the weld's, extract's and
+ *   simplify's rule. Position, key and normal (has_normals carries over as in extract: positions do not change) are those of the
+ *   class's smallest-numbered member, bit for bit: the -0 of the position key is for grouping only, the stored bits are the
+ *   member's own. n_verts, n_tris: of the result. Nothing kept: GSDF_ERR_EMPTY_BUFFERS.
+ * 5. Derived guarantees (tests/test_clean_ref.py holds the restatement to them by brute force).
+ *   (i)   Idempotent: cleaning the result with the same flags drops nothing and returns the same bytes. (Smallest members have
+ *         distinct keys; a kept face is alone in its set.)
+ *   (ii)  After GSDF_CLEAN_FACES no two faces of the result have one set.
+ *   (iii) Removing one + and one - face of a set removes each of its three vertex pairs once in each direction. So where
+ *         duplicate_faces == 0, every pair {p, q} of vertices has the same f - r (the report's uses as (p, q) minus its uses as
+ *         (q, p)) before and after, over the classes of step 1. In particular a mesh in which every pair has f == r (no boundary,
+ *         no misoriented edge; non-manifold edges allowed) keeps that property, and its non-manifold edges at cancelled sheets fall
+ *         from 2 + 2 uses to 1 + 1.
+ *   (iv)  With duplicate_faces > 0 signed volume and edge balance may change: the stats say so, and gsdf_hip_indexed_report of the
+ *         result tells the truth, as everywhere else.
+ *   NOT promised: that the result is closed; hole filling; re-orienting shells; merging vertices that are merely CLOSE -- the
+ *   copies of a corner that neighbouring cubes of a mesher emit differ in their last bits (see "indexed meshes", the weld; the
+ *   minecraft mesher's faces too: a corner is origin + res i + res in one cube and origin + res (i + 1) in the next): weld
+ *   marching-cubes meshes from records, or cluster with "simplify".
+ * Limits. 3 F < 2^32 and V < 2^32, as gsdf_hip_indexed_create enforces.
+ *
+ * gsdf_hip_indexed_clean(ix, o, out, st): as gsdf_hip_indexed_simplify. *out = a new, independent handle; st (optional) = the stats.
+ *   out == NULL with st != NULL is a DRY RUN: the same stats, no handle built, GSDF_OK with n_tris == 0 where nothing would be kept.
+ *   Both NULL: GSDF_ERR_BAD_ARGUMENT. On an error *out is NULL and *st is not written.
+ * gsdf_clean_stats. Bytes 0 .. 87 (n_verts_in .. n_tris) are a function of the mesh and the flags alone, and
+ *   n_tris == n_tris_in - degenerate - duplicate_faces - opposite_faces; the rest says what this run cost, per table (0 for a table
+ *   the flags do not ask for). GSDF_HIP_CLEAN_CELLS_MIN (environment) lowers both tables' first size so that tests can drive the
+ *   grow-and-repeat path, as GSDF_HIP_SIMPLIFY_CELLS_MIN does. */
+#define GSDF_CLEAN_MERGE_POSITIONS 1u
+#define GSDF_CLEAN_FACES 2u
+typedef struct gsdf_clean_opts {
+  uint32_t flags;    /* GSDF_CLEAN_MERGE_POSITIONS | GSDF_CLEAN_FACES, not 0; others refused */
+  uint32_t reserved[3];
+} gsdf_clean_opts;
+GSDF_ABI_ASSERT(sizeof(gsdf_clean_opts) == 16, "gsdf_clean_opts is 16 bytes");
+GSDF_ABI_ASSERT(offsetof(gsdf_clean_opts, flags) == 0 && offsetof(gsdf_clean_opts, reserved) == 4, "gsdf_clean_opts fields");
+typedef struct gsdf_clean_stats {
+  uint64_t n_verts_in, n_tris_in;
+  uint64_t merged_verts;      /* sum over the classes of (members - 1) */
+  uint64_t degenerate;        /* faces with two equal indices after the merge */
+  uint64_t face_sets;         /* distinct sets of the non-degenerate faces */
+  uint64_t cancelled_sets;    /* sets with f == r */
+  uint64_t duplicate_faces;   /* dropped faces of a kept face's own orientation beyond the opposite pairs */
+  uint64_t opposite_faces;    /* dropped faces that pair up, one + with one -: even */
+  uint64_t largest_set;       /* the largest f + r */
+  uint64_t n_verts, n_tris;   /* of the result */
+  double ms_merge;            /* device time, HIP events: vertex table (all attempts), classes, the merged faces */
+  double ms_faces;            /* face table (all attempts), the rule, the named classes */
+  double ms_result;           /* compaction, numbering, remap (0 in a dry run) */
+  uint64_t vert_probes;       /* vertex table: cells inspected by the inserting pass that succeeded */
+  uint64_t vert_table_cells;  /* its capacity (a power of two, >= 2 classes of finite vertices) */
+  uint64_t face_probes;       /* face table: the same */
+  uint64_t face_table_cells;  /* its capacity (a power of two, >= 2 face_sets) */
+  int32_t vert_attempts;      /* inserting passes run, per table */
+  int32_t face_attempts;
+} gsdf_clean_stats;
+GSDF_ABI_ASSERT(sizeof(gsdf_clean_stats) == 152, "gsdf_clean_stats is 152 bytes");
+GSDF_ABI_ASSERT(offsetof(gsdf_clean_stats, merged_verts) == 16 && offsetof(gsdf_clean_stats, face_sets) == 32 && offsetof(gsdf_clean_stats, duplicate_faces) == 48,
+                "gsdf_clean_stats counts");
+GSDF_ABI_ASSERT(offsetof(gsdf_clean_stats, largest_set) == 64 && offsetof(gsdf_clean_stats, n_verts) == 72 && offsetof(gsdf_clean_stats, n_tris) == 80,
+                "gsdf_clean_stats result");
+GSDF_ABI_ASSERT(offsetof(gsdf_clean_stats, ms_merge) == 88 && offsetof(gsdf_clean_stats, vert_probes) == 112 && offsetof(gsdf_clean_stats, vert_attempts) == 144,
+                "gsdf_clean_stats cost");
+int gsdf_hip_indexed_clean(gsdf_indexed* ix, const gsdf_clean_opts* o, gsdf_indexed** out, gsdf_clean_stats* st);
 
 /* ---- indexed meshes: project onto the field (no reference counterpart) -------------------------------------------------------------
  *

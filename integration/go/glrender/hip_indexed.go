@@ -290,6 +290,59 @@ func (ix *IndexedHIP) SimplifyAdaptive(cell, tol float32, levels int, origin ms3
 	return nx, stats, nil
 }
 
+// CleanOpts chooses the steps of Clean (gsdf_clean_opts.flags): MergePositions joins the vertices with equal positions (a triangle
+// soup uploaded as an indexed mesh), Faces keeps at most one face per set of three vertices and cancels opposite pairs.
+type CleanOpts struct {
+	MergePositions, Faces bool
+}
+
+// CleanStats is gsdf_clean_stats: what a clean merged and dropped, and its device time per stage.
+type CleanStats struct {
+	VIn, FIn, MergedV, Degenerate             uint64
+	FaceSets, CancelledSets                   uint64
+	DuplicateFaces, OppositeFaces, LargestSet uint64
+	V, F                                      uint64
+	MergeMillis, FacesMillis, ResultMillis    float64
+}
+
+// Clean returns a new, independent mesh without degenerate faces and, as `what` asks, with the vertices of equal position merged and
+// with at most one face over every set of three vertices: equal faces are dropped, opposite faces cancel in pairs (gsdf_hip.h,
+// "indexed meshes: clean", states every term). With dry set nothing is built: the mesh returned is nil and the stats say what the
+// result would be.
+func (ix *IndexedHIP) Clean(what CleanOpts, dry bool) (*IndexedHIP, CleanStats, error) {
+	var co C.gsdf_clean_opts
+	if what.MergePositions {
+		co.flags |= C.GSDF_CLEAN_MERGE_POSITIONS
+	}
+	if what.Faces {
+		co.flags |= C.GSDF_CLEAN_FACES
+	}
+	var cs C.gsdf_clean_stats
+	var h *C.gsdf_indexed
+	out := &h
+	if dry {
+		out = nil
+	}
+	if rc := C.gsdf_hip_indexed_clean(ix.h, &co, out, &cs); rc != 0 {
+		return nil, CleanStats{}, hipErr(rc)
+	}
+	stats := CleanStats{
+		VIn: uint64(cs.n_verts_in), FIn: uint64(cs.n_tris_in), MergedV: uint64(cs.merged_verts), Degenerate: uint64(cs.degenerate),
+		FaceSets: uint64(cs.face_sets), CancelledSets: uint64(cs.cancelled_sets), DuplicateFaces: uint64(cs.duplicate_faces),
+		OppositeFaces: uint64(cs.opposite_faces), LargestSet: uint64(cs.largest_set), V: uint64(cs.n_verts), F: uint64(cs.n_tris),
+		MergeMillis: float64(cs.ms_merge), FacesMillis: float64(cs.ms_faces), ResultMillis: float64(cs.ms_result),
+	}
+	if dry {
+		return nil, stats, nil
+	}
+	nx := &IndexedHIP{h: h}
+	var nv, nf C.uint64_t
+	var ms C.double
+	C.gsdf_hip_indexed_counts(h, &nv, &nf, &ms)
+	nx.V, nx.F, nx.WeldMillis = uint64(nv), uint64(nf), float64(ms)
+	return nx, stats, nil
+}
+
 // ProjectStats is gsdf_project_stats: what a projection of the vertices onto a field did, and its device time. Count is indexed by
 // the status byte: skipped, on, converged, iters, flat, clamped, nonfinite, reverted.
 type ProjectStats struct {
