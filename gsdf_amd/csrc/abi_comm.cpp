@@ -590,8 +590,7 @@ extern "C" int gsdf_hip_comm_create(const uint8_t id[GSDF_COMM_ID_BYTES], int ra
   c->rank = rank; c->world = world;
   auto bail = [&](int code) { gsdf_hip_comm_destroy(c); return code; };
   if (hipGetDevice(&c->device) != hipSuccess) return bail(fail(GSDF_ERR_HIP, "hipGetDevice failed"));
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, c->device) == hipSuccess) c->num_cu = prop.multiProcessorCount;
+  c->num_cu = grid_cus(c->device);
   if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) return bail(fail(GSDF_ERR_HIP, "hipStreamCreate failed"));
   const size_t words = (size_t)(world + 1) * gsdf_comm::kCountWords;
   if (hipMalloc((void**)&c->d_counts, sizeof(unsigned long long) * words) != hipSuccess) return bail(fail(GSDF_ERR_HIP, "hipMalloc(counts) failed"));

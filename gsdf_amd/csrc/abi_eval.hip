@@ -31,6 +31,14 @@ extern "C" int gsdf_hip_init(int device) {
   return GSDF_OK;
 }
 
+extern "C" int gsdf_hip_grid_cus(int device, int* real_cus) {
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess || n == 0) { (void)hipGetLastError(); return 0; }
+  if (device < 0 && hipGetDevice(&device) != hipSuccess) return 0;
+  if (device >= n) return 0;
+  return grid_cus(device, real_cus);
+}
+
 extern "C" int gsdf_hip_program_create(const gsdf_tree* tree, gsdf_program** out) {
   if (!tree || !out) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
   *out = nullptr;
@@ -50,8 +58,7 @@ extern "C" int gsdf_hip_program_create(const gsdf_tree* tree, gsdf_program** out
   }
   auto cleanup = [&](int code) { gsdf_hip_program_destroy(p); return code; };
   if (hipGetDevice(&p->device) != hipSuccess) return cleanup(fail(GSDF_ERR_HIP, "hipGetDevice failed"));
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, p->device) == hipSuccess) p->num_cu = prop.multiProcessorCount;
+  p->num_cu = grid_cus(p->device);
   if (p->lds_bytes(p->batch_k()) + gsdf_program::kCreateExtra > gsdf_program::kLdsPerCu) return cleanup(fail(GSDF_ERR_BAD_TREE, "tree needs more LDS scratch than one CU has"));
   if (p->stream.ensure() != hipSuccess) return cleanup(fail(GSDF_ERR_HIP, "hipStreamCreate failed"));
   size_t bytes = p->prog.code.size() * sizeof(uint32_t);

@@ -47,6 +47,18 @@ inline bool env_flag(const char* name) { const char* e = getenv(name); return e 
 inline bool env_flag_on(const char* name) { const char* e = getenv(name); return !e || atoi(e) != 0; }  // on unless set to 0
 inline bool env_set(const char* name) { return getenv(name) != nullptr; }
 
+// The CU count a handle sizes its capped grids from (grid_for, num_cu * workgroups per CU): the device's, or GSDF_HIP_GRID_CUS where
+// that is 1 .. the device's (read whenever a handle learns its count; handles made from a handle inherit). A developer knob:
+// with few CUs every grid-stride loop takes several trips at sizes a test can afford. *real_out: the device's own count.
+inline int grid_cus(int device, int* real_out = nullptr) {
+  int real = 256;
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) real = prop.multiProcessorCount;
+  if (real_out) *real_out = real;
+  const int n = env_int("GSDF_HIP_GRID_CUS", 0);
+  return n >= 1 && n < real ? n : real;
+}
+
 inline bool finite_all(const float* v, int n) {
   for (int i = 0; i < n; i++) if (!std::isfinite(v[i])) return false;
   return true;

@@ -445,10 +445,9 @@ extern "C" int gsdf_hip_indexed_create(const float* verts, uint64_t n_verts, con
     if (idx[s] >= n_verts)
       return fail(GSDF_ERR_BAD_ARGUMENT, "indexed mesh: face " + std::to_string(s / 3) + " names vertex index " + std::to_string(idx[s]) + ", the mesh has " +
                                              std::to_string(n_verts) + " vertices");
-  int device = 0, num_cu = 256;
+  int device = 0;
   HIP_TRY(hipGetDevice(&device));
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device) == hipSuccess) num_cu = prop.multiProcessorCount;
+  const int num_cu = grid_cus(device);
   IndexedPtr ix;
   if (int rc = indexed_new(device, num_cu, &ix)) return rc;
   if (!ix->verts.take(device, n_verts * 12) || !ix->idx.take(device, n_tris * 12) || !ix->vkeys.take(device, n_verts * 8))

@@ -692,7 +692,7 @@ static int dc_mesh(gsdf_program* p, float res, int chiseled, int shard_rank, int
 
   gsdf_mesh* m = new (std::nothrow) gsdf_mesh();
   if (!m) return fail(GSDF_ERR_BAD_ARGUMENT, "out of memory");
-  m->device = p->device; m->stream = s;
+  m->device = p->device; m->stream = s; m->num_cu = p->num_cu;
   m->st.levels = levels; m->st.res = res;
   m->st.origin[0] = ox; m->st.origin[1] = oy; m->st.origin[2] = oz;
   auto bail = [&](int code) {
@@ -977,7 +977,7 @@ extern "C" int gsdf_hip_mesh_minecraft(gsdf_program* p, float res, void* stream,
   const uint64_t n_cubes = (uint64_t)1 << (3 * nshift);
   gsdf_mesh* m = new (std::nothrow) gsdf_mesh();
   if (!m) return fail(GSDF_ERR_BAD_ARGUMENT, "out of memory");
-  m->device = p->device; m->stream = s;
+  m->device = p->device; m->stream = s; m->num_cu = p->num_cu;
   m->st.levels = levels; m->st.res = res;
   m->st.origin[0] = bb[0]; m->st.origin[1] = bb[1]; m->st.origin[2] = bb[2];
   float* d_pos = nullptr;
@@ -1049,7 +1049,7 @@ extern "C" int gsdf_hip_mesh_flat(gsdf_program* p, float res, int shard_rank, in
 
   gsdf_mesh* m = new (std::nothrow) gsdf_mesh();
   if (!m) return fail(GSDF_ERR_BAD_ARGUMENT, "out of memory");
-  m->device = p->device; m->stream = s;
+  m->device = p->device; m->stream = s; m->num_cu = p->num_cu;
   m->st.levels = 0; m->st.res = res;
   m->st.origin[0] = ox; m->st.origin[1] = oy; m->st.origin[2] = oz;
   auto bail = [&](int code) { gsdf_hip_mesh_destroy(m); return code; };
@@ -1268,7 +1268,7 @@ extern "C" int gsdf_hip_mesh_host_stl(gsdf_mesh* m, const uint8_t** stl, size_t*
     hipStream_t rs = mesh_stream(m);
     hipError_t e = hipMemcpyAsync(d_out, hdr, 84, hipMemcpyHostToDevice, rs);
     if (e == hipSuccess) {
-      hipLaunchKernelGGL(stl_kernel, dim3(grid_for(n, 256, 8)), dim3(BLOCK), 0, rs, m->d_tris, n, (uint8_t*)d_out);
+      hipLaunchKernelGGL(stl_kernel, dim3(grid_for(n, m->num_cu, 8)), dim3(BLOCK), 0, rs, m->d_tris, n, (uint8_t*)d_out);
       e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(m->h_stl, d_out, bytes, hipMemcpyDeviceToHost, rs);

@@ -125,6 +125,11 @@ int gsdf_hip_selftest_cossin(uint64_t* mismatches, uint64_t* fast_path_arguments
  * else term by term), 19 the same term by term always, 20 / 21 likewise for three terms, the third being divisor. Each pair agrees
  * bit for bit. y may be null for one-operand functions. */
 int gsdf_hip_selftest_math(int fn, const float* x, const float* y, float* out, uint64_t n, float divisor);
+/* Test hook (needs a GPU): the CU count that a handle created now on `device` (< 0: the current one) would size its grids from: the
+ * device's own, or GSDF_HIP_GRID_CUS (environment, read at every handle creation) where that is a number from 1 to the device's
+ * count. With few CUs every grid-stride loop takes several trips at sizes a test can afford; results never depend on it.
+ * real_cus (may be null) receives the device's own count. 0: no such device. */
+int gsdf_hip_grid_cus(int device, int* real_cus);
 /* Run-time specialisation (no reference counterpart; the reference's GPU path compiles GLSL per tree at
  * gleval/gpu.go:35-54, this is the same step for the HIP backend): builds, with hiprtc, eval / prune / leaf kernels in
  * which this program's instructions are laid out straight-line with literal parameters, and makes the handle launch
