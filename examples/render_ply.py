@@ -9,7 +9,10 @@ the device and arrives in pinned host memory by one DMA (gsdf_hip_indexed_host_p
 binary STL's of the same mesh, and the weld's device time.
 
     --report             also print what gsdf_hip_indexed_report says of the mesh (watertight and oriented? shells, volume, area,
-                         centre of mass; its device time per stage) and the shell table
+                         centre of mass; its device time per stage) and the shell table, and of the mesh that is written its mass
+                         properties (gsdf_hip_indexed_mass, on device): mass, centre of mass, the inertia tensor about it, the
+                         principal moments and axes; per shell where there are several
+    --density RHO        with --report: the density the mass and the inertia are printed for (default 1: volume and unit-density tensor)
     --min-shell-tris N   write the mesh without the shells of fewer than N faces (specks)
     --drop-cavities      ... and without the shells of negative volume (enclosed cavities)
     --simplify K         then merge the vertices of every cell of K x res into one at their mean and drop the faces that collapse
@@ -66,6 +69,22 @@ def print_report(name, ix):
               f"misoriented {s['misoriented_edges']}")
 
 
+def print_mass(name, ix, density):
+    """Mass properties of the mesh that goes to the file, and of its shells where it has more than one."""
+    total, shells = ix.mass(density)
+
+    def line(what, m):
+        t, c = m["inertia"], m["centroid"]
+        axes = "; ".join("(" + ", ".join(f"{x:.6g}" for x in row) + ")" for row in m["axes"])
+        return (f"{what}: mass {m['mass']:.9g} (volume {m['volume']:.9g} at density {density:g}), centre ({c[0]:.6g}, {c[1]:.6g}, {c[2]:.6g}); inertia about it "
+                f"xx {t[0, 0]:.9g} yy {t[1, 1]:.9g} zz {t[2, 2]:.9g} xy {t[0, 1]:.9g} xz {t[0, 2]:.9g} yz {t[1, 2]:.9g}; principal moments "
+                f"{m['moments'][0]:.9g} {m['moments'][1]:.9g} {m['moments'][2]:.9g} about {axes}")
+    print(line(f"{name} mass", total) + f"; device {type(ix).mass_ms():.3f} ms")
+    if len(shells) > 1:
+        for k, m in enumerate(shells):
+            print(line(f"  shell {k} (label {m['label']})", m))
+
+
 def parse_args(argv=None):
     """The command line, checked: needs no device."""
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -75,6 +94,7 @@ def parse_args(argv=None):
     ap.add_argument("-o", "--output", default=None)
     ap.add_argument("--interpreter", action="store_true", help="skip the per-tree kernel build")
     ap.add_argument("--report", action="store_true", help="print the mesh's report and its shell table")
+    ap.add_argument("--density", type=float, default=1.0, metavar="RHO", help="with --report: the density of the printed mass and inertia")
     ap.add_argument("--min-shell-tris", type=int, default=0, help="drop the shells with fewer faces than this")
     ap.add_argument("--drop-cavities", action="store_true", help="drop the shells of negative volume")
     ap.add_argument("--simplify", type=float, default=0.0, metavar="K", help="cluster the vertices in cells of K x res")
@@ -99,6 +119,8 @@ def parse_args(argv=None):
         ap.error("--adaptive with --max-tris needs a tolerance > 0 to double")
     if args.thickness is not None and not args.thickness >= 0:
         ap.error("--thickness needs a THIN >= 0")
+    if not (args.density > 0 and args.density < float("inf")):
+        ap.error("--density needs a finite RHO > 0")
     return args
 
 
@@ -194,6 +216,8 @@ def main(argv=None):
                   f"{ps.max_abs_after / float(res):.4g} res); vertices further than res / 1024 from the surface {ps.over_tol_before} -> {ps.over_tol_after} "
                   f"of {ps.n_verts}")
             print_report(args.scene + " projected", ix)
+    if args.report:
+        print_mass(args.scene, ix, args.density)
     out = args.output or f"{args.scene}.ply"
     data = ix.ply_view()
     if args.thickness is not None:

@@ -12,7 +12,8 @@ outer boundaries counter-clockwise, holes clockwise. --report prints loops, vert
 layer, and the device time of the two stages (evaluation, tracing). --simplify TOL drops the vertices that lie within TOL x res of a
 dyadic chord of their loop (gsdf_hip_contour_simplify; --levels, --passes as there), --max-verts N doubles that tolerance until at
 most N vertices are left; the report then adds the vertices before and after, the largest deviation and the layers' areas and lengths
-summed on the device. The SVG is written with the standard library only."""
+summed on the device. The report ends with the section properties of every layer that is written (gsdf_hip_contour_sections, on
+device): the centroid and the second moments of area about it. The SVG is written with the standard library only."""
 import argparse
 import importlib.util
 import math
@@ -76,6 +77,14 @@ def simplify_report(before, c, st, tol):
     return "\n".join(lines)
 
 
+def section_report(c):
+    """Centroid and central second moments of area of the written layers, from the device."""
+    _, layers = c.sections()
+    return "\n".join(f"layer {k} section: area {s['area']:.9g}, centroid ({s['centroid'][0]:.6g}, {s['centroid'][1]:.6g}), second moments about it "
+                     f"xx {s['central'][0]:.9g} yy {s['central'][1]:.9g} xy {s['central'][2]:.9g} (sections: {type(c).sections_ms():.3f} ms)"
+                     for k, s in enumerate(layers))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("scene", choices=SCENES_2D + SCENES_3D)
@@ -132,6 +141,7 @@ def main(argv=None):
         print(report(traced, z))
         if simplified:
             print(simplify_report(traced.n_verts, c, *simplified))
+        print(section_report(c))
     return 0
 
 

@@ -3,7 +3,8 @@
 // Kernels: kernels_contour.h. The distances come from the program's own Evaluate (gsdf_hip_eval2_dev / gsdf_hip_eval3_dev:
 // interpreter or per-tree kernels, whichever the handle has); no interpreter kernel is compiled here.
 // Behind the tracer (section "contours: simplify and measures", kernels_contour_simplify.h): gsdf_hip_contour_create uploads loops,
-// gsdf_hip_contour_simplify drops vertices within a tolerance of dyadic chords, gsdf_hip_contour_measures sums areas and lengths.
+// gsdf_hip_contour_simplify drops vertices within a tolerance of dyadic chords, gsdf_hip_contour_measures sums areas and lengths,
+// gsdf_hip_contour_sections (kernels_mass.h) first and second moments of area.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -16,6 +17,9 @@
 #include "kernels_common.h"
 #include "kernels_contour.h"
 #include "kernels_contour_simplify.h"
+#define KERNELS_MASS_LOOPS
+#include "kernels_mass.h"
+#include "mass_host.h"
 #include "abi_program.h"
 
 struct gsdf_contour {
@@ -434,17 +438,23 @@ extern "C" int gsdf_hip_contour_simplify(const gsdf_contour* c, const gsdf_conto
 
 namespace {
 thread_local double g_measures_ms = 0;
-}
-extern "C" double gsdf_hip_contour_measures_ms(void) { return g_measures_ms; }
+thread_local double g_sections_ms = 0;
 
-extern "C" int gsdf_hip_contour_measures(const gsdf_contour* c, gsdf_loop_measure* loops, gsdf_layer_measure* layers) {
-  if (!c) return fail(GSDF_ERR_BAD_ARGUMENT, "null contour");
-  g_measures_ms = 0;
+// What one pass over the loops leaves on the host: the measures' sums, with `sections` the section sums (kernels_mass.h) behind
+// them, the loops' extents and layers, the exponent, the device time of all of it.
+struct MeasureRun {
+  std::vector<CmeasAcc> acc;
+  std::vector<CsectAcc> sect;
+  std::vector<unsigned> start, layer;
+  int e = -125;
+  double ms = 0;
+};
+int measure_run(const gsdf_contour* c, bool sections, MeasureRun* r) {
   const uint64_t V = c->n_verts, NL = c->n_loops;
-  const uint32_t L = c->st.n_layers;
-  const float inf = std::numeric_limits<float>::infinity();
-  std::vector<CmeasAcc> h_acc(NL);
-  std::vector<unsigned> h_start(NL + 1), h_layer(NL);
+  r->acc.resize(NL);
+  r->sect.resize(sections ? NL : 0);
+  r->start.resize(NL + 1);
+  r->layer.resize(NL);
   unsigned long long h_maxbits = 0;
   if (V > 0 && NL > 0) {
     HIP_TRY(hipSetDevice(c->device));
@@ -453,9 +463,11 @@ extern "C" int gsdf_hip_contour_measures(const gsdf_contour* c, gsdf_loop_measur
     hipStream_t s = stream.s;
     DevPtr<unsigned> loop_of;
     DevPtr<CmeasAcc> acc;
+    DevPtr<CsectAcc> sect;
     DevPtr<unsigned long long> maxbits;
     EventSet<2> ev;
-    if (!dev_alloc(loop_of, V) || !dev_alloc(acc, NL) || !dev_alloc(maxbits, 1)) return fail(GSDF_ERR_HIP, "contour measures: no device memory for the workspace");
+    if (!dev_alloc(loop_of, V) || !dev_alloc(acc, NL) || !dev_alloc(maxbits, 1) || (sections && !dev_alloc(sect, NL)))
+      return fail(GSDF_ERR_HIP, "contour measures: no device memory for the workspace");
     if (ev.ensure() != hipSuccess) return fail(GSDF_ERR_HIP, "hipEventCreate failed");
     struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{s};
     const unsigned nb = blocks_of(V), nb_max = blocks_of(2 * V) < 1024u ? blocks_of(2 * V) : 1024u;
@@ -465,18 +477,41 @@ extern "C" int gsdf_hip_contour_measures(const gsdf_contour* c, gsdf_loop_measur
     LAUNCH(cmeas_init_kernel, blocks_of(NL), s, acc.p, (unsigned)NL);
     LAUNCH(cloop_of_kernel, nb, s, (const unsigned*)c->loop_start.p, (unsigned)NL, (unsigned)V, loop_of.p);
     LAUNCH(cmeas_kernel, nb, s, (const float*)c->xy.p, (const unsigned*)c->loop_start.p, (const unsigned*)loop_of.p, (unsigned)V, (const unsigned long long*)maxbits.p, acc.p);
+    if (sections) {
+      HIP_TRY(hipMemsetAsync(sect.p, 0, (size_t)NL * sizeof(CsectAcc), s));
+      LAUNCH(csect_kernel, nb, s, (const float*)c->xy.p, (const unsigned*)c->loop_start.p, (const unsigned*)loop_of.p, (unsigned)V, (const unsigned long long*)maxbits.p, sect.p);
+    }
     HIP_TRY(hipEventRecord(ev[1], s));
-    HIP_TRY(hipMemcpyAsync(h_acc.data(), acc.p, (size_t)NL * sizeof(CmeasAcc), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(h_start.data(), c->loop_start.p, (size_t)(NL + 1) * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(h_layer.data(), c->loop_layer.p, (size_t)NL * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(r->acc.data(), acc.p, (size_t)NL * sizeof(CmeasAcc), hipMemcpyDeviceToHost, s));
+    if (sections) HIP_TRY(hipMemcpyAsync(r->sect.data(), sect.p, (size_t)NL * sizeof(CsectAcc), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(r->start.data(), c->loop_start.p, (size_t)(NL + 1) * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(r->layer.data(), c->loop_layer.p, (size_t)NL * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(&h_maxbits, maxbits.p, 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     float t = 0;
-    if (hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess) g_measures_ms = t;
+    if (hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess) r->ms = t;
   }
-  // integers -> float64 with one rounding each, times the inverse power of two (exact); area = sum / 2
   const unsigned biased = (unsigned)(h_maxbits >> 23);
-  const int e = (int)(biased > 1u ? biased : 1u) - 126;
+  r->e = (int)(biased > 1u ? biased : 1u) - 126;
+  return GSDF_OK;
+}
+}  // namespace
+extern "C" double gsdf_hip_contour_measures_ms(void) { return g_measures_ms; }
+extern "C" double gsdf_hip_contour_sections_ms(void) { return g_sections_ms; }
+
+extern "C" int gsdf_hip_contour_measures(const gsdf_contour* c, gsdf_loop_measure* loops, gsdf_layer_measure* layers) {
+  if (!c) return fail(GSDF_ERR_BAD_ARGUMENT, "null contour");
+  g_measures_ms = 0;
+  const uint64_t NL = c->n_loops;
+  const uint32_t L = c->st.n_layers;
+  const float inf = std::numeric_limits<float>::infinity();
+  MeasureRun run;
+  if (int rc = measure_run(c, false, &run)) return rc;
+  g_measures_ms = run.ms;
+  const std::vector<CmeasAcc>& h_acc = run.acc;
+  const std::vector<unsigned>&h_start = run.start, &h_layer = run.layer;
+  // integers -> float64 with one rounding each, times the inverse power of two (exact); area = sum / 2
+  const int e = run.e;
   auto whole = [](unsigned long long lo, unsigned long long hi) { return (__int128)(long long)hi * ((__int128)1 << 32) + (__int128)lo; };
   auto unordered = [](unsigned o) { const unsigned b = o ^ ((o >> 31) ? 0x80000000u : 0xffffffffu); float f; std::memcpy(&f, &b, 4); return f; };
   struct LayerAcc { __int128 area = 0, length = 0; unsigned bb[4] = {CMEAS_BB_MIN_INIT, CMEAS_BB_MIN_INIT, CMEAS_BB_MAX_INIT, CMEAS_BB_MAX_INIT}; uint32_t n_loops = 0, n_verts = 0; };
@@ -513,5 +548,34 @@ extern "C" int gsdf_hip_contour_measures(const gsdf_contour* c, gsdf_loop_measur
       m.n_loops = la[l].n_loops;
       m.n_verts = la[l].n_verts;
     }
+  return GSDF_OK;
+}
+
+// ---- section properties (gsdf_hip.h, "contours: section properties"; kernels_mass.h, mass_host.h) -----------------------------------
+extern "C" int gsdf_hip_contour_sections(const gsdf_contour* c, gsdf_section* loops, gsdf_section* layers) {
+  g_sections_ms = 0;
+  if (!c) return fail(GSDF_ERR_BAD_ARGUMENT, "null contour");
+  const uint64_t NL = c->n_loops;
+  const uint32_t L = c->st.n_layers;
+  MeasureRun run;
+  if (int rc = measure_run(c, true, &run)) return rc;
+  g_sections_ms = run.ms;
+  struct LayerAcc { __int128 sums[6] = {0, 0, 0, 0, 0, 0}; uint32_t n_loops = 0, n_verts = 0; };
+  std::vector<LayerAcc> la(layers ? L : 0);
+  for (uint64_t q = 0; q < NL; q++) {
+    __int128 sums[6];
+    sums[0] = mass::whole(run.acc[q].sum[0], run.acc[q].sum[1]);
+    for (int k = 0; k < 5; k++) sums[1 + k] = mass::whole(run.sect[q].sum[2 * k], run.sect[q].sum[2 * k + 1]);
+    const uint32_t nv = run.start[q + 1] - run.start[q];
+    if (loops) mass::fill_section(&loops[q], sums, run.e, nv, run.layer[q]);
+    if (layers && run.layer[q] < L) {
+      LayerAcc& l = la[run.layer[q]];
+      for (int k = 0; k < 6; k++) l.sums[k] += sums[k];
+      l.n_loops++;
+      l.n_verts += nv;
+    }
+  }
+  if (layers)
+    for (uint32_t l = 0; l < L; l++) mass::fill_section(&layers[l], la[l].sums, run.e, la[l].n_verts, la[l].n_loops);
   return GSDF_OK;
 }

@@ -9,6 +9,7 @@
 //   abi_mesh.hip  octree / flat / dual-contouring meshers and the mesh accessors
 //   abi_indexed.hip  indexed meshes: the gsdf_indexed handle, weld, PLY, report and extract
 //   abi_contour.hip  2-D outlines and z-slices traced into ordered closed loops
+//   abi_mass.cpp  principal axes of an inertia tensor (host only; without a HIP header, so that a plain C++ program can link it)
 //   abi_comm.cpp  multi-GPU: communicator (RCCL or the in-process loopback transport), gather plan, gatherv
 // (the list the library is built from: UNITS in __graft_entry__.py)
 #pragma once

@@ -3,7 +3,7 @@
 // projection of the vertices onto a program's field (its kernel is abi_eval.hip's: project_dev), and the numbering of dual
 // contouring's quads into a handle (indexed_from_cube_slots: abi_mesh.hip orders them and owns the evaluating stages).
 // Kernels: kernels_weld.h (weld, PLY, and the table / scan / remap every pass shares), kernels_topo.h (report, extract),
-// kernels_simplify.h (simplify), kernels_simplify_adaptive.h (adaptive simplify), kernels_clean.h (clean). No
+// kernels_mass.h (mass properties), kernels_simplify.h (simplify), kernels_simplify_adaptive.h (adaptive simplify), kernels_clean.h (clean). No
 // interpreter kernel is compiled here: of the meshers this unit needs mesh_march_dense alone, and abi_mesh.hip owns that.
 #include <algorithm>
 #include <cmath>
@@ -17,6 +17,9 @@
 #include "kernels_common.h"
 #include "kernels_weld.h"
 #include "kernels_topo.h"
+#define KERNELS_MASS_MESH
+#include "kernels_mass.h"
+#include "mass_host.h"
 #include "kernels_simplify.h"
 #include "kernels_simplify_adaptive.h"
 #include "kernels_clean.h"
@@ -71,6 +74,14 @@ struct gsdf_indexed {
   gsdf_indexed_report rep{};
   std::vector<gsdf_shell> shells;
   PoolBuf shell_of_vertex, shell_of_face;
+  // ... and the shells' integers behind its volume and centroid (volume, moment x / y / z), which gsdf_hip_indexed_mass carries on
+  struct ShellInts { __int128 v[4]; };
+  std::vector<ShellInts> shell_ints;
+  // gsdf_hip_indexed_mass's result, computed once: the mesh's record, the shells' records, the device time of the pass
+  bool mass_valid = false;
+  gsdf_mass mass_total{};
+  std::vector<gsdf_mass> mass_shells;
+  double mass_ms = 0;
   // gsdf_hip_indexed_project's per-vertex record of the handle it made: d_before, d_after (V floats each), status (V bytes)
   bool has_fit = false;
   PoolBuf fit_before, fit_after, fit_status;
@@ -529,6 +540,7 @@ static int topo_ensure(gsdf_indexed* ix) {
   // the shells' records; the mesh's sums are the sums of the shells' integers
   gsdf_indexed_report r{};
   std::vector<gsdf_shell> shells(n_shells);
+  std::vector<gsdf_indexed::ShellInts> ints(n_shells);
   __int128 tot[5] = {0, 0, 0, 0, 0};
   unsigned bb[6] = {TOPO_BB_MIN_INIT, TOPO_BB_MIN_INIT, TOPO_BB_MIN_INIT, TOPO_BB_MAX_INIT, TOPO_BB_MAX_INIT, TOPO_BB_MAX_INIT};
   const int shift[5] = {sh_area, sh_vol, sh_mom, sh_mom, sh_mom};
@@ -544,6 +556,7 @@ static int topo_ensure(gsdf_indexed* ix) {
       const __int128 t = topo_int(a.sum + 2 * q);
       tot[q] += t;
       val[q] = topo_value(t, shift[q]);
+      if (q > 0) ints[k].v[q - 1] = t;
     }
     o.area = val[0]; o.volume = val[1];
     for (int q = 0; q < 3; q++) o.centroid[q] = topo_quotient(val[2 + q], val[1]);
@@ -566,6 +579,7 @@ static int topo_ensure(gsdf_indexed* ix) {
   r.probes = hc.tab.probes; r.table_cells = cells; r.attempts = run.attempts;
   ix->rep = r;
   ix->shells.swap(shells);
+  ix->shell_ints.swap(ints);
   ix->topo_valid = true;
   return GSDF_OK;
 }
@@ -593,6 +607,67 @@ extern "C" int gsdf_hip_indexed_read_shell_of(gsdf_indexed* ix, uint32_t* shell_
   HIP_TRY(hipSetDevice(ix->device));
   if (shell_of_vertex) HIP_TRY(hipMemcpy(shell_of_vertex, ix->shell_of_vertex.p, ix->n_verts * 4, hipMemcpyDeviceToHost));
   if (shell_of_face) HIP_TRY(hipMemcpy(shell_of_face, ix->shell_of_face.p, ix->n_tris * 4, hipMemcpyDeviceToHost));
+  return GSDF_OK;
+}
+
+// ---- mass properties (kernels_mass.h, mass_host.h; gsdf_hip.h: "indexed meshes: mass properties") ---------------------------------
+namespace {
+thread_local double g_mass_ms = 0;
+}
+extern "C" double gsdf_hip_indexed_mass_ms(void) { return g_mass_ms; }
+
+// The second moments of the shells, once per handle, behind the report (whose exponent, shell numbering and first-degree integers
+// it takes over).
+static int mass_ensure(gsdf_indexed* ix) {
+  if (ix->mass_valid) return GSDF_OK;
+  if (int rc = topo_ensure(ix)) return rc;
+  HIP_TRY(hipSetDevice(ix->device));
+  const int dev = ix->device;
+  hipStream_t s = ix->stream;
+  const uint64_t F = ix->n_tris, n_shells = ix->shells.size();
+  const int e = ix->rep.exponent;
+  PoolBuf acc;
+  if (!acc.take(dev, (n_shells + 1) * sizeof(MassShellAcc))) return fail(GSDF_ERR_HIP, "mass: no device memory for the workspace");
+  MassShellAcc* d_acc = acc.as<MassShellAcc>();
+  EventPair ev;
+  if (!ev.make()) return fail(GSDF_ERR_HIP, "hipEventCreate failed");
+  std::vector<MassShellAcc> ha(n_shells);
+  HIP_TRY(hipEventRecord(ev.a, s));
+  HIP_TRY(hipMemsetAsync(d_acc, 0, (n_shells + 1) * sizeof(MassShellAcc), s));
+  LAUNCH(mass_second_kernel, blocks_of(F), BLOCK, s, ix->verts.p, ix->idx.as<unsigned>(), (unsigned long long)F, ix->shell_of_face.as<unsigned>(), d_acc,
+         std::ldexp(1.0, 62 - 5 * e));
+  HIP_TRY(hipEventRecord(ev.b, s));
+  if (n_shells) HIP_TRY(hipMemcpyAsync(ha.data(), d_acc, n_shells * sizeof(MassShellAcc), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  // the shells' records; the mesh's integers are the sums of the shells'
+  std::vector<gsdf_mass> shells(n_shells);
+  __int128 tot[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (uint64_t k = 0; k < n_shells; k++) {
+    __int128 sums[10];
+    for (int q = 0; q < 4; q++) sums[q] = ix->shell_ints[k].v[q];
+    for (int q = 0; q < 6; q++) sums[4 + q] = mass::whole(ha[k].sum[2 * q], ha[k].sum[2 * q + 1]);
+    for (int q = 0; q < 10; q++) tot[q] += sums[q];
+    mass::fill_mass(&shells[k], sums, e, ix->shells[k].label);
+  }
+  mass::fill_mass(&ix->mass_total, tot, e, 0xffffffffu);
+  ix->mass_shells.swap(shells);
+  ix->mass_ms = ev.ms();
+  ix->mass_valid = true;
+  return GSDF_OK;
+}
+
+extern "C" int gsdf_hip_indexed_mass(gsdf_indexed* ix, gsdf_mass* total, gsdf_mass* shells, uint64_t cap, uint64_t* n) {
+  g_mass_ms = 0;
+  if (!ix) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  if (!total && !shells && !n) return fail(GSDF_ERR_BAD_ARGUMENT, "mass: nothing asked for (total, shells and n are all null)");
+  if (shells && !n) return fail(GSDF_ERR_BAD_ARGUMENT, "mass: shells needs n (a short buffer is reported through it)");
+  if (int rc = mass_ensure(ix)) return rc;
+  g_mass_ms = ix->mass_ms;
+  if (total) *total = ix->mass_total;
+  if (n) *n = ix->mass_shells.size();
+  if (!shells) return GSDF_OK;
+  if (cap < *n) return fail(GSDF_ERR_SHORT_BUFFER, "short buffer");
+  if (*n) std::memcpy(shells, ix->mass_shells.data(), *n * sizeof(gsdf_mass));
   return GSDF_OK;
 }
 

@@ -32,7 +32,8 @@ SYMBOLS = ["gsdf_hip_last_error", "gsdf_hip_init", "gsdf_hip_program_create", "g
            "gsdf_hip_indexed_simplify", "gsdf_hip_indexed_simplify_adaptive", "gsdf_hip_indexed_clean", "gsdf_hip_indexed_project", "gsdf_hip_indexed_read_fit", "gsdf_hip_mesh_dualcontour_indexed",
            "gsdf_hip_raycast3", "gsdf_hip_indexed_thickness",
            "gsdf_hip_contour2", "gsdf_hip_slice3", "gsdf_hip_contour_counts", "gsdf_hip_contour_read", "gsdf_hip_contour_stats_get", "gsdf_hip_contour_destroy",
-           "gsdf_hip_contour_create", "gsdf_hip_contour_simplify", "gsdf_hip_contour_measures", "gsdf_hip_contour_measures_ms"]
+           "gsdf_hip_contour_create", "gsdf_hip_contour_simplify", "gsdf_hip_contour_measures", "gsdf_hip_contour_measures_ms",
+           "gsdf_hip_indexed_mass", "gsdf_hip_indexed_mass_ms", "gsdf_hip_inertia_principal", "gsdf_hip_contour_sections", "gsdf_hip_contour_sections_ms"]
 
 
 PRUNE_ASSUME_SDF = 1 << 30  # gsdf_hip.h: GSDF_PRUNE_ASSUME_SDF
@@ -247,6 +248,28 @@ LOOP_MEASURE_DTYPE = np.dtype([("area", "<f8"), ("length", "<f8"), ("bbox", "<f4
 LAYER_MEASURE_DTYPE = np.dtype([("area", "<f8"), ("length", "<f8"), ("bbox", "<f4", (4,)), ("n_loops", "<u4"), ("n_verts", "<u4")])
 
 
+class Mass(C.Structure):
+    """gsdf_mass (gsdf_hip.h, "indexed meshes: mass properties"): volume, first and second moments about the origin (second and
+    inertia in the order xx yy zz xy xz yz), centroid and the unit-density inertia tensor about it, of one shell or of the mesh."""
+    _fields_ = [("volume", C.c_double), ("first", C.c_double * 3), ("second", C.c_double * 6), ("centroid", C.c_double * 3),
+                ("inertia", C.c_double * 6), ("exponent", C.c_int32), ("label", C.c_uint32)]
+
+
+class Section(C.Structure):
+    """gsdf_section (gsdf_hip.h, "contours: section properties"): area, first moments (x, y) and second moments (xx, yy, xy) about
+    the origin, centroid and the second moments about it, of one loop or of one layer."""
+    _fields_ = [("area", C.c_double), ("first", C.c_double * 2), ("second", C.c_double * 3), ("centroid", C.c_double * 2),
+                ("central", C.c_double * 3), ("n_verts", C.c_uint32), ("layer_or_n_loops", C.c_uint32)]
+
+
+# the same two as numpy records (arrays of shells, of loops, of layers)
+MASS_DTYPE = np.dtype([("volume", "<f8"), ("first", "<f8", (3,)), ("second", "<f8", (6,)), ("centroid", "<f8", (3,)), ("inertia", "<f8", (6,)),
+                       ("exponent", "<i4"), ("label", "<u4")])
+SECTION_DTYPE = np.dtype([("area", "<f8"), ("first", "<f8", (2,)), ("second", "<f8", (3,)), ("centroid", "<f8", (2,)), ("central", "<f8", (3,)),
+                          ("n_verts", "<u4"), ("layer_or_n_loops", "<u4")])
+MASS_TOTAL = 0xffffffff  # Mass.label of a whole mesh
+
+
 # gsdf_shell (gsdf_hip.h) as a numpy record: one per shell, in increasing order of the label (the shell's smallest vertex number)
 SHELL_DTYPE = np.dtype([("n_verts", "<u8"), ("n_tris", "<u8"), ("nonfinite", "<u8"), ("edges", "<u8"), ("boundary_edges", "<u8"),
                         ("nonmanifold_edges", "<u8"), ("misoriented_edges", "<u8"), ("euler", "<i8"), ("area", "<f8"), ("volume", "<f8"),
@@ -390,6 +413,13 @@ def lib():
         L.gsdf_hip_contour_measures.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.gsdf_hip_contour_measures_ms.argtypes = []
         L.gsdf_hip_contour_measures_ms.restype = C.c_double
+        L.gsdf_hip_indexed_mass.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.gsdf_hip_indexed_mass_ms.argtypes = []
+        L.gsdf_hip_indexed_mass_ms.restype = C.c_double
+        L.gsdf_hip_inertia_principal.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.gsdf_hip_contour_sections.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.gsdf_hip_contour_sections_ms.argtypes = []
+        L.gsdf_hip_contour_sections_ms.restype = C.c_double
         L.gsdf_hip_brick_owner.restype = C.c_uint32
         L.gsdf_hip_brick_owner.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         L.gsdf_hip_slab_range.restype = None
@@ -869,6 +899,29 @@ class OctreeHIP:
         return self._view(p.value, ln.value, np.uint8)
 
 
+def inertia_principal(inertia):
+    """gsdf_hip_inertia_principal (host only): (moments (3,) ascending, axes (3, 3), one unit vector per row, right-handed) of a
+    symmetric tensor given as six values xx yy zz xy xz yz or as a (3, 3) array (its upper triangle is read)."""
+    a = np.asarray(inertia, np.float64)
+    if a.shape == (3, 3):
+        a = np.array([a[0, 0], a[1, 1], a[2, 2], a[0, 1], a[0, 2], a[1, 2]])
+    a = np.ascontiguousarray(a.reshape(6))
+    m, ax = np.empty(3, np.float64), np.empty((3, 3), np.float64)
+    _check(lib().gsdf_hip_inertia_principal(a.ctypes.data, m.ctypes.data, ax.ctypes.data))
+    return m, ax
+
+
+def _mass_dict(rec, density):
+    i = np.asarray(rec["inertia"], np.float64) * float(density)
+    tensor = np.array([[i[0], i[3], i[4]], [i[3], i[1], i[5]], [i[4], i[5], i[2]]])
+    if np.isfinite(i).all():
+        moments, axes = inertia_principal(i)
+    else:
+        moments, axes = np.full(3, np.nan), np.full((3, 3), np.nan)
+    return {"label": int(rec["label"]), "volume": float(rec["volume"]), "mass": float(density) * float(rec["volume"]),
+            "centroid": np.array(rec["centroid"], np.float64), "inertia": tensor, "moments": moments, "axes": axes}
+
+
 class IndexedHIP:
     """An indexed triangle mesh resident on the device (gsdf_indexed): vertices, faces, the vertices' lattice keys, optional
     normals, and its binary PLY. Independent of the mesh it was welded from."""
@@ -950,6 +1003,29 @@ class IndexedHIP:
         if n.value:
             _check(lib().gsdf_hip_indexed_shells(self._h, out.ctypes.data, n.value, C.byref(n)))
         return out
+
+    def mass_records(self):
+        """gsdf_hip_indexed_mass as it is: (a MASS_DTYPE record of the mesh, a MASS_DTYPE array with one record per shell in shell
+        order), unit density; computed on the device once per handle."""
+        total, n = np.zeros(1, MASS_DTYPE), C.c_uint64()
+        _check(lib().gsdf_hip_indexed_mass(self._h, total.ctypes.data, None, 0, C.byref(n)))
+        shells = np.zeros(n.value, MASS_DTYPE)
+        if n.value:
+            _check(lib().gsdf_hip_indexed_mass(self._h, None, shells.ctypes.data, n.value, C.byref(n)))
+        return total[0], shells
+
+    def mass(self, density=1.0):
+        """Mass properties of the solid the mesh bounds: (total, shells), each a dict (shells: a list in shell order) with label
+        (MASS_TOTAL for the mesh), volume, mass = density * volume, centroid (3,), inertia (3, 3) about the centroid = density * the
+        unit-density tensor, and its principal moments (3,) ascending with their axes (3, 3), one unit vector per row
+        (inertia_principal). A record with volume 0 has NaN centroid, inertia, moments and axes."""
+        total, shells = self.mass_records()
+        return _mass_dict(total, density), [_mass_dict(s, density) for s in shells]
+
+    @staticmethod
+    def mass_ms():
+        """Device milliseconds (HIP events) of the pass behind this thread's last mass() / mass_records()."""
+        return float(lib().gsdf_hip_indexed_mass_ms())
 
     def shell_of(self):
         """(shell number of every vertex (V,), of every face (F,)) uint32; SHELL_NONE for an unused vertex / a degenerate face."""
@@ -1232,6 +1308,19 @@ class ContourHIP:
     def measures_ms():
         """Device milliseconds (HIP events) of this thread's last measures()."""
         return float(lib().gsdf_hip_contour_measures_ms())
+
+    def sections(self):
+        """gsdf_hip_contour_sections: (loops, layers) as numpy records (SECTION_DTYPE per loop and per layer): area, first and second
+        moments of area about the origin, centroid and the second moments about it, summed on the device as integers."""
+        loops = np.zeros(self.n_loops, SECTION_DTYPE)
+        layers = np.zeros(self.n_layers, SECTION_DTYPE)
+        _check(lib().gsdf_hip_contour_sections(self._h, loops.ctypes.data if self.n_loops else None, layers.ctypes.data if self.n_layers else None))
+        return loops, layers
+
+    @staticmethod
+    def sections_ms():
+        """Device milliseconds (HIP events) of this thread's last sections()."""
+        return float(lib().gsdf_hip_contour_sections_ms())
 
     def loops(self, layer=None):
         """The loops (of one layer, or of all) as (n, 2) float32 arrays, in the handle's order."""

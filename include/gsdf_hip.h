@@ -649,6 +649,75 @@ int gsdf_hip_indexed_shells(gsdf_indexed* ix, gsdf_shell* dst, uint64_t cap, uin
 int gsdf_hip_indexed_read_shell_of(gsdf_indexed* ix, uint32_t* shell_of_vertex, uint32_t* shell_of_face);
 int gsdf_hip_indexed_extract(gsdf_indexed* ix, const uint8_t* keep_shell, int drop_degenerate, gsdf_indexed** out);
 
+/* ---- indexed meshes: mass properties (no reference counterpart) -------------------------------------------------------------------
+ *
+ * One polynomial degree above the report: the second moments of the solid a mesh bounds, per shell and for the mesh, and from them
+ * the inertia tensor about the centre of mass and its principal axes. Computed on the device by the scheme of "report and extract"
+ * above, with its exponent e, its shells and its faces (degenerate and NONFINITE faces are absent), so order-independent to the bit.
+ * Kernel: gsdf_amd/csrc/kernels_mass.h (abi_indexed.hip); host arithmetic: gsdf_amd/csrc/mass_host.h; a numpy / Python-integer
+ * restatement: tests/massref.py.
+ *
+ * Terms, per FINITE non-degenerate face with corners a, b, c as (double)float32 and the report's det (the same operations in the
+ *   same order: the volume and first-moment integers of a shell ARE the report's). Let s_k = (a_k + b_k) + c_k. For the six pairs
+ *   (i, j) = xx, yy, zz, xy, xz, yz, in this order everywhere below:
+ *     second term ij = (det * ((((a_i a_j) + (b_i b_j)) + (c_i c_j)) + (s_i s_j))) / 120
+ *   every operation one IEEE float64 operation, none contracted: the integral of x_i x_j over the tetrahedron (0, a, b, c), signed
+ *   as its volume is.
+ * Bound (derived, not measured). |det| < 6 2^(3e) (six products of three coordinates), the bracket < 12 2^(2e) (|s_k| < 3 2^e), so
+ *   |term| < 72 / 120 2^(5e) = 0.6 2^(5e). The term is multiplied by the power of two 2^(62-5e) (exact; for e = -125 .. 128 a normal
+ *   double between 2^-578 and 2^687), rounded to the nearest integer, ties to even: |q| < 2^62. The q are summed as the report's are
+ *   (low 32 bits and arithmetic-shifted rest in separate 64-bit words). second_ij = that integer converted to float64 with ONE
+ *   rounding, times 2^(5e-62) (exact: never subnormal). Error of the quantisation: at most n_tris / 2 units of 2^(5e-62), i.e.
+ *   n_tris 2^-68 of 2^(5e+5), the second moment of the cube [-2^e, 2^e]^3 that holds the mesh about its own centre being 2^(5e+3) / 3.
+ * The record. volume and first[k] (the report's moment sums: first_k = the integral of x_k, so that the report's centroid_k =
+ *   first_k / volume) come from the report's integers, second[6] from the sums above. Derived, on the host, one float64 operation
+ *   each, in this order:
+ *     centroid_k = first_k / volume                                              (the report's bytes)
+ *     C_ij       = second_ij - ((first_i * first_j) / volume)                    (central second moments)
+ *     inertia    = (C_yy + C_zz, C_xx + C_zz, C_xx + C_yy, -C_xy, -C_xz, -C_yz)  (xx, yy, zz, xy, xz, yz; unit density)
+ *   With volume == 0 every centroid and inertia entry is the quiet NaN 0x7ff8000000000000. A mesh's integers are the sums of its
+ *   shells' integers (label 0xffffffff); a cavity's shell has negative volume and moments, so that the sums are the material's.
+ *   C cancels for a part far from the origin: the raw sums stay exact to the quantisation above whatever the position, while
+ *   centroid and inertia of a part of size d at distance D lose about 2 log2(D / d) bits -- on top of what float32 positions
+ *   carry (2^-24 of D per coordinate). Translate the part to the origin first if that matters. The derived values are what IEEE
+ *   arithmetic gives in the order stated: first_i * first_j is formed before the division, so at the very ends of the range of
+ *   e it can overflow to infinity (first moments near 2^512: an off-centre part at e = 128) or lose bits to a subnormal
+ *   product (below 2^-511: a small part at e near -125) where the raw sums are still exact. exponent = e.
+ * gsdf_hip_indexed_mass: total, shells and n are each optional, but shells needs n (a short buffer is reported through it) and
+ *   at least one of the three must be given: otherwise GSDF_ERR_BAD_ARGUMENT, before the device is touched. shells NULL: *n =
+ *   n_shells; cap < n_shells: GSDF_ERR_SHORT_BUFFER with *n set (total, if given, is filled). Runs the report if the handle has
+ *   none; computed once per handle, later calls return the same bytes. gsdf_hip_indexed_mass_ms: the device time (HIP events) of
+ *   the pass that made the records the calling thread's last successful gsdf_hip_indexed_mass returned; 0 before the first, and
+ *   after a call that failed.
+ * gsdf_hip_inertia_principal (host only, no GPU): the eigenvalues of the symmetric tensor I (inertia[6] in the order above:
+ *   A00 A11 A22 A01 A02 A12) in ascending order, and a right-handed frame of unit row vectors (axes[3 k + i] = component i of axis
+ *   k; unit to rounding), by the cyclic Jacobi iteration, float64, one operation at a time:
+ *     A = I, V = identity. Up to 32 sweeps; a sweep begins by the stop rule: A01 == 0 and A02 == 0 and A12 == 0 ends the iteration
+ *     (after 32 sweeps A is taken as it is). A sweep visits the pairs (p, q) = (0, 1), (0, 2), (1, 2), r the third index:
+ *       g = A_pq; g == 0: next pair.  |A_pp| + |g| == |A_pp| and |A_qq| + |g| == |A_qq|: A_pq = A_qp = 0, next pair.
+ *       theta = (A_qq - A_pp) / (2 g);  t = sgn / (|theta| + sqrt((theta theta) + 1)), sgn = 1 if theta >= 0 else -1
+ *       c = 1 / sqrt((t t) + 1);  s = t c;  h = t g;  A_pp = A_pp - h;  A_qq = A_qq + h;  A_pq = A_qp = 0
+ *       (x, y) = (A_rp, A_rq):  A_rp = A_pr = (c x) - (s y);  A_rq = A_qr = (s x) + (c y)
+ *       for i = 0, 1, 2, (x, y) = (V_ip, V_iq):  V_ip = (c x) - (s y);  V_iq = (s x) + (c y)
+ *     Order: positions (0, 1, 2) of the diagonal are sorted by compare-and-swap of positions (0, 1), (1, 2), (0, 1), swapping
+ *     when the first is GREATER (equal moments keep their order). moments[k] = the k-th diagonal entry, axis k = that column of V.
+ *     Sign: of axes 0 and 1, the component of largest magnitude (ties: the lowest index) is made positive by negating the axis;
+ *     axis 2 = axis 0 x axis 1 = ((x1 y2) - (x2 y1), (x2 y0) - (x0 y2), (x0 y1) - (x1 y0)).
+ *   An entry dropped by the second rule is below 2^-53 of both diagonal entries beside it. GSDF_ERR_BAD_ARGUMENT: a NULL pointer,
+ *   a NaN or infinite entry. */
+typedef struct gsdf_mass {
+  double volume, first[3], second[6]; /* second: xx yy zz xy xz yz, about the origin */
+  double centroid[3], inertia[6];     /* inertia: xx yy zz xy xz yz, about the centroid, unit density */
+  int32_t exponent;                   /* e of the contract */
+  uint32_t label;                     /* the shell's label; 0xffffffff: the whole mesh */
+} gsdf_mass;
+GSDF_ABI_ASSERT(sizeof(gsdf_mass) == 160, "gsdf_mass is 160 bytes");
+GSDF_ABI_ASSERT(offsetof(gsdf_mass, first) == 8 && offsetof(gsdf_mass, second) == 32 && offsetof(gsdf_mass, centroid) == 80, "gsdf_mass sums");
+GSDF_ABI_ASSERT(offsetof(gsdf_mass, inertia) == 104 && offsetof(gsdf_mass, exponent) == 152 && offsetof(gsdf_mass, label) == 156, "gsdf_mass derived values");
+int gsdf_hip_indexed_mass(gsdf_indexed* ix, gsdf_mass* total, gsdf_mass* shells, uint64_t cap, uint64_t* n);
+double gsdf_hip_indexed_mass_ms(void);
+int gsdf_hip_inertia_principal(const double inertia[6], double moments[3], double axes[9]);
+
 /* ---- indexed meshes: simplify (no reference counterpart) --------------------------------------------------------------------------
  *
  * A smaller mesh by VERTEX CLUSTERING: the used vertices fall into the cells of a cubic grid, the vertices of one cell become one
@@ -1303,6 +1372,46 @@ int gsdf_hip_contour_simplify(const gsdf_contour* c, const gsdf_contour_simplify
                               gsdf_contour_simplify_stats* st /* optional */);
 int gsdf_hip_contour_measures(const gsdf_contour* c, gsdf_loop_measure* loops /* n_loops or NULL */, gsdf_layer_measure* layers /* n_layers or NULL */);
 double gsdf_hip_contour_measures_ms(void);
+
+/* ---- contours: section properties (no reference counterpart) -----------------------------------------------------------------------
+ *
+ * What a beam calculation asks of a cross-section: its centroid and its second moments of area, per loop and per layer, by the
+ * scheme of gsdf_hip_contour_measures above and with its exponent e. Kernel: gsdf_amd/csrc/kernels_mass.h (abi_contour.hip); host
+ * arithmetic: gsdf_amd/csrc/mass_host.h; restated in tests/massref.py.
+ *
+ * Terms, per vertex j of a loop with its successor j+1 (the leader behind the last), coordinates as (double)float32, one IEEE
+ *   float64 operation each, none contracted; cross = x_j y_(j+1) - x_(j+1) y_j is the measures' area term:
+ *     first_x term = (cross * (x_j + x_(j+1))) / 6                                  and first_y likewise with y
+ *     xx term      = (cross * (((x_j x_j) + (x_j x_(j+1))) + (x_(j+1) x_(j+1)))) / 12     and yy likewise with y
+ *     xy term      = (cross * ((((x_j y_(j+1)) + (x_(j+1) y_j)) + 2 (x_j y_j)) + 2 (x_(j+1) y_(j+1)))) / 24
+ *   (2 (u v): the product, then doubled; every product of two coordinates is exact.) first_x is the integral of x over the part on
+ *   the left of the loop, xx of x^2, yy of y^2, xy of x y. The signs follow the area's: a hole's sums are negative, so a layer's
+ *   sums are those of the material.
+ * Bounds (derived). |cross| < 2^(2e+1); |x_j + x_(j+1)| < 2^(e+1): |first term| < 2^(3e+2) / 6 < 2^(3e), scale 2^(62-3e). The
+ *   brackets of xx and yy are < 3 2^(2e), that of xy < 6 2^(2e): |second term| < 2^(4e-1), scale 2^(62-4e). Scaled (exact), rounded
+ *   to the nearest integer, ties to even, |q| < 2^62, summed as integers as the measures' terms are, converted with ONE rounding,
+ *   times the inverse power of two (exact). A layer's integers are the sums of its loops' integers. Error of the quantisation: at
+ *   most n / 2 units of 2^(3e-62) resp. 2^(4e-62) for n vertices.
+ * The record. area has the bytes of gsdf_hip_contour_measures' area; first = (x, y); second = (xx, yy, xy), about the origin. Derived
+ *   on the host, one float64 operation each, in this order:
+ *     centroid_k = first_k / area
+ *     central    = (xx - ((first_x * first_x) / area), yy - ((first_y * first_y) / area), xy - ((first_x * first_y) / area))
+ *   With area == 0 (a layer without a loop among them) centroid and central are the quiet NaN 0x7ff8000000000000. central cancels
+ *   for a section far from the origin, as the inertia of a mesh does. n_verts: the loop's, or the layer's; layer_or_n_loops: the
+ *   loop's layer in a loop record, the number of loops in a layer record.
+ * gsdf_hip_contour_sections: loops (n_loops records, loop order) and layers (n_layers records), either may be NULL.
+ *   gsdf_hip_contour_sections_ms: the device time (HIP events) of the calling thread's last gsdf_hip_contour_sections, 0 before the
+ *   first. */
+typedef struct gsdf_section {
+  double area, first[2], second[3];  /* second: xx yy xy, about the origin */
+  double centroid[2], central[3];    /* central: xx yy xy, about the centroid */
+  uint32_t n_verts, layer_or_n_loops;
+} gsdf_section;
+GSDF_ABI_ASSERT(sizeof(gsdf_section) == 96, "gsdf_section is 96 bytes");
+GSDF_ABI_ASSERT(offsetof(gsdf_section, first) == 8 && offsetof(gsdf_section, second) == 24 && offsetof(gsdf_section, centroid) == 48, "gsdf_section sums");
+GSDF_ABI_ASSERT(offsetof(gsdf_section, central) == 64 && offsetof(gsdf_section, n_verts) == 88 && offsetof(gsdf_section, layer_or_n_loops) == 92, "gsdf_section derived values");
+int gsdf_hip_contour_sections(const gsdf_contour* c, gsdf_section* loops /* n_loops or NULL */, gsdf_section* layers /* n_layers or NULL */);
+double gsdf_hip_contour_sections_ms(void);
 
 /* ---- multi-GPU (one process per GPU). The meshers shard with NO data-path collective (shard_rank / shard_count above); the
  * one exchange is the final variable-length gather of the ranks' results, over xGMI, inside this library: a Go caller needs no

@@ -170,6 +170,81 @@ func (ix *IndexedHIP) Shells() ([]Shell, error) {
 	return out, nil
 }
 
+// Mass is gsdf_mass: the mass properties of the solid a shell (or the whole mesh: Label 0xffffffff) bounds, at unit density. Second
+// and Inertia are in the order xx yy zz xy xz yz; Second is about the origin, Inertia about Centroid. With Volume == 0 Centroid and
+// Inertia are NaN. Multiply Volume and Inertia by a density for a mass and its tensor.
+type Mass struct {
+	Label    uint32
+	Volume   float64
+	First    [3]float64
+	Second   [6]float64
+	Centroid [3]float64
+	Inertia  [6]float64
+}
+
+func massOf(raw *C.gsdf_mass) Mass {
+	var gm C.gsdf_mass = *raw
+	out := Mass{Label: uint32(gm.label), Volume: float64(gm.volume)}
+	for k := 0; k < 3; k++ {
+		out.First[k], out.Centroid[k] = float64(gm.first[k]), float64(gm.centroid[k])
+	}
+	for k := 0; k < 6; k++ {
+		out.Second[k], out.Inertia[k] = float64(gm.second[k]), float64(gm.inertia[k])
+	}
+	return out
+}
+
+// Mass computes (once per handle, on the device) the volume, the first and second moments, the centre of mass and the inertia
+// tensor about it of the whole mesh: order-independent to the bit (gsdf_hip.h, "indexed meshes: mass properties").
+func (ix *IndexedHIP) Mass() (Mass, error) {
+	var total C.gsdf_mass
+	if rc := C.gsdf_hip_indexed_mass(ix.h, &total, nil, 0, nil); rc != 0 {
+		return Mass{}, hipErr(rc)
+	}
+	return massOf(&total), nil
+}
+
+// MassShells returns the same per shell, in the order of Shells(). A cavity's shell has a negative Volume and negative moments.
+func (ix *IndexedHIP) MassShells() ([]Mass, error) {
+	var n C.uint64_t
+	if rc := C.gsdf_hip_indexed_mass(ix.h, nil, nil, 0, &n); rc != 0 {
+		return nil, hipErr(rc)
+	}
+	if n == 0 {
+		return nil, nil
+	}
+	raw := make([]C.gsdf_mass, int(n))
+	if rc := C.gsdf_hip_indexed_mass(ix.h, nil, &raw[0], n, &n); rc != 0 {
+		return nil, hipErr(rc)
+	}
+	out := make([]Mass, len(raw))
+	for i := range raw {
+		out[i] = massOf(&raw[i])
+	}
+	return out, nil
+}
+
+// InertiaPrincipal returns the principal moments of a symmetric tensor (xx yy zz xy xz yz, as Mass.Inertia) in ascending order and
+// their axes, one unit vector per row, right-handed (gsdf_hip_inertia_principal: a Jacobi iteration on the host, no GPU).
+func InertiaPrincipal(inertia [6]float64) (moments [3]float64, axes [3][3]float64, err error) {
+	var in [6]C.double
+	var m [3]C.double
+	var ax [9]C.double
+	for k := range in {
+		in[k] = C.double(inertia[k])
+	}
+	if rc := C.gsdf_hip_inertia_principal(&in[0], &m[0], &ax[0]); rc != 0 {
+		return moments, axes, hipErr(rc)
+	}
+	for k := 0; k < 3; k++ {
+		moments[k] = float64(m[k])
+		for i := 0; i < 3; i++ {
+			axes[k][i] = float64(ax[3*k+i])
+		}
+	}
+	return moments, axes, nil
+}
+
 // Extract returns a new, independent mesh with the faces of the kept shells (keep: one entry per shell of Shells(); nil keeps
 // all), vertices renumbered by first appearance. Degenerate faces stay only with keep == nil and dropDegenerate == false.
 func (ix *IndexedHIP) Extract(keep []bool, dropDegenerate bool) (*IndexedHIP, error) {

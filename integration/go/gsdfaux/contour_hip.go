@@ -215,3 +215,59 @@ func (c *ContoursHIP) Measures() (loops, layers []LoopMeasureHIP, err error) {
 	}
 	return loops, layers, nil
 }
+
+// SectionHIP is gsdf_section: the section properties of one loop (one layer). First is the integral of (x, y) over the part on the
+// left of the loop, Second of (x x, y y, x y), both about the origin; Central is Second about Centroid. Holes are negative, so a
+// layer's record is the material's. With Area == 0 Centroid and Central are NaN.
+type SectionHIP struct {
+	Area     float64
+	First    [2]float64
+	Second   [3]float64
+	Centroid [2]float64
+	Central  [3]float64
+	Verts    int
+	Layer    int // of a loop; of a layer: its number of loops
+}
+
+func sectionOf(raw *C.gsdf_section) SectionHIP {
+	var gs C.gsdf_section = *raw
+	out := SectionHIP{Area: float64(gs.area), Verts: int(gs.n_verts), Layer: int(gs.layer_or_n_loops)}
+	for k := 0; k < 2; k++ {
+		out.First[k], out.Centroid[k] = float64(gs.first[k]), float64(gs.centroid[k])
+	}
+	for k := 0; k < 3; k++ {
+		out.Second[k], out.Central[k] = float64(gs.second[k]), float64(gs.central[k])
+	}
+	return out
+}
+
+// Sections sums, on the device, the first and second moments of area of every loop and of every layer (gsdf_hip_contour_sections):
+// integer sums, the same bits whatever the order of the threads. A layer without loops has Area 0 and NaN Centroid and Central.
+func (c *ContoursHIP) Sections() (loops, layers []SectionHIP, err error) {
+	layers = make([]SectionHIP, c.Layers)
+	for k := range layers {
+		layers[k].Centroid = [2]float64{math.NaN(), math.NaN()}
+		layers[k].Central = [3]float64{math.NaN(), math.NaN(), math.NaN()}
+	}
+	if len(c.LoopStart) < 2 || c.Layers == 0 {
+		return nil, layers, nil
+	}
+	h, err := c.upload()
+	if err != nil {
+		return nil, nil, err
+	}
+	defer C.gsdf_hip_contour_destroy(h)
+	ls := make([]C.gsdf_section, len(c.LoopStart)-1)
+	ys := make([]C.gsdf_section, c.Layers)
+	if rc := C.gsdf_hip_contour_sections(h, &ls[0], &ys[0]); rc != 0 {
+		return nil, nil, errors.New("gsdf_hip: " + C.GoString(C.gsdf_hip_last_error()))
+	}
+	loops = make([]SectionHIP, len(ls))
+	for q := range ls {
+		loops[q] = sectionOf(&ls[q])
+	}
+	for k := range ys {
+		layers[k] = sectionOf(&ys[k])
+	}
+	return loops, layers, nil
+}
