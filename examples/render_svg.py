@@ -6,6 +6,7 @@ slicer wants of a 3-D part at each layer height:
     python examples/render_svg.py npt-flange --slice 5 -o flange.svg           # one contour of a 3-D scene (npt-flange, bolt) at z = 5
     python examples/render_svg.py bolt --layer-height 2 --report -o bolt.svg   # every layer of thickness 2, with a report
     python examples/render_svg.py text --simplify 0.125 --report -o text.svg   # vertices within res / 8 of a chord dropped on the GPU
+    python examples/render_svg.py bolt --layer-height 2 --hatch 4 --report -o bolt.svg   # hatch lines 4 res apart, 45 / 135 degrees by layer
 
 The lattice spacing is the diagonal of the part's bounds / --resdiv (default 400), or --res. Every layer is one even-odd <path>:
 outer boundaries counter-clockwise, holes clockwise. --report prints loops, vertices, outer and hole counts and the area of every
@@ -13,7 +14,10 @@ layer, and the device time of the two stages (evaluation, tracing). --simplify T
 dyadic chord of their loop (gsdf_hip_contour_simplify; --levels, --passes as there), --max-verts N doubles that tolerance until at
 most N vertices are left; the report then adds the vertices before and after, the largest deviation and the layers' areas and lengths
 summed on the device. The report ends with the section properties of every layer that is written (gsdf_hip_contour_sections, on
-device): the centroid and the second moments of area about it. The SVG is written with the standard library only."""
+device): the centroid and the second moments of area about it. --hatch SPACING fills every layer with the segments of parallel lines
+SPACING x res apart that lie inside the material (gsdf_hip_contour_hatch, on device; on the simplified loops when --simplify is
+given), at the angles of --hatch-angle in turn by layer; they are drawn as <line> elements, and the report adds the segments and the
+hatch length of every layer, the most crossings on one line and the device time. The SVG is written with the standard library only."""
 import argparse
 import importlib.util
 import math
@@ -85,6 +89,15 @@ def section_report(c):
                      for k, s in enumerate(layers))
 
 
+def hatch_report(h, c):
+    """What --hatch made: per layer the segments and their length, then the cost."""
+    st = h.stats
+    lines = [f"layer {k} hatch: {int(m['n_segments'])} segments, length {m['length']:.9g}, lines {int(m['k_min'])} .. {int(m['k_max'])}" for k, m in enumerate(h.layers)]
+    lines.append(f"hatch: {st.n_segments} segments on {st.n_lines} lines, length {st.length:.9g}, {st.zero_length} of zero length, max_line_crossings "
+                 f"{st.max_line_crossings}, device time {st.ms_device:.3f} ms (rank pass {type(c).hatch_rank_ms():.3f} ms)")
+    return "\n".join(lines)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("scene", choices=SCENES_2D + SCENES_3D)
@@ -96,6 +109,8 @@ def main(argv=None):
     ap.add_argument("--levels", type=int, default=8, help="--simplify: dyadic levels, 1 .. 16")
     ap.add_argument("--passes", type=int, default=1, help="--simplify: passes, 1 .. 8 (the deviations add)")
     ap.add_argument("--max-verts", type=int, default=None, metavar="N", help="--simplify: double the tolerance until at most N vertices are left")
+    ap.add_argument("--hatch", type=float, default=None, metavar="SPACING", help="fill the layers with parallel lines SPACING x res apart")
+    ap.add_argument("--hatch-angle", type=float, nargs="+", default=[45.0, 135.0], metavar="DEG", help="--hatch: the lines' angles, in turn by layer (1 .. 4)")
     ap.add_argument("--report", action="store_true")
     ap.add_argument("--interpreter", action="store_true", help="skip the per-tree kernel build")
     ap.add_argument("-o", "--output", default=None)
@@ -134,7 +149,10 @@ def main(argv=None):
     elif args.max_verts is not None:
         ap.error("--max-verts goes with --simplify TOL, the tolerance the doubling starts from")
     out = args.output or f"{args.scene}.svg"
-    svg.write_svg(out, [c.loops(k) for k in range(c.n_layers)], z=z)
+    hatch = None
+    if args.hatch is not None:
+        hatch = c.hatch(np.float32(np.float32(args.hatch) * res), args.hatch_angle)
+    svg.write_svg(out, [c.loops(k) for k in range(c.n_layers)], z=z, hatch=None if hatch is None else [hatch.segments(k) for k in range(hatch.n_layers)])
     print(f"{args.scene} res {float(res):.6g}: setup {t1 - t0:.2f} s, contours {(t2 - t1) * 1e3:.1f} ms (the first call includes the kernels' build); "
           f"{c.n_loops} loops, {c.n_verts} vertices in {c.n_layers} layer(s); written to {out}")
     if args.report:
@@ -142,6 +160,8 @@ def main(argv=None):
         if simplified:
             print(simplify_report(traced.n_verts, c, *simplified))
         print(section_report(c))
+        if hatch is not None:
+            print(hatch_report(hatch, c))
     return 0
 
 

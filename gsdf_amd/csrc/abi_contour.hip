@@ -4,7 +4,8 @@
 // interpreter or per-tree kernels, whichever the handle has); no interpreter kernel is compiled here.
 // Behind the tracer (section "contours: simplify and measures", kernels_contour_simplify.h): gsdf_hip_contour_create uploads loops,
 // gsdf_hip_contour_simplify drops vertices within a tolerance of dyadic chords, gsdf_hip_contour_measures sums areas and lengths,
-// gsdf_hip_contour_sections (kernels_mass.h) first and second moments of area.
+// gsdf_hip_contour_sections (kernels_mass.h) first and second moments of area, gsdf_hip_contour_hatch (kernels_hatch.h) the segments
+// of parallel lines inside the loops, as a gsdf_hatch handle of its own.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -20,6 +21,7 @@
 #define KERNELS_MASS_LOOPS
 #include "kernels_mass.h"
 #include "mass_host.h"
+#include "kernels_hatch.h"
 #include "abi_program.h"
 
 struct gsdf_contour {
@@ -577,5 +579,220 @@ extern "C" int gsdf_hip_contour_sections(const gsdf_contour* c, gsdf_section* lo
   }
   if (layers)
     for (uint32_t l = 0; l < L; l++) mass::fill_section(&layers[l], la[l].sums, run.e, la[l].n_verts, la[l].n_loops);
+  return GSDF_OK;
+}
+
+// ---- hatch fill (gsdf_hip.h, "contours: hatch fill"; kernels_hatch.h) ---------------------------------------------------------------
+struct gsdf_hatch {
+  int device = 0;
+  uint32_t n_layers = 0;
+  uint64_t n_segments = 0;
+  DevPtr<float> seg;  // 4 n_segments
+  DevPtr<int> line;   // n_segments
+  std::vector<uint32_t> layer_start;  // n_layers + 1
+  std::vector<gsdf_hatch_layer> layers;
+};
+
+extern "C" void gsdf_hip_hatch_destroy(gsdf_hatch* h) {
+  if (!h) return;
+  (void)hipSetDevice(h->device);
+  delete h;
+}
+
+namespace {
+struct HatchDelete { void operator()(gsdf_hatch* h) const { gsdf_hip_hatch_destroy(h); } };
+using HatchPtr = std::unique_ptr<gsdf_hatch, HatchDelete>;
+
+struct HatchWs {
+  DevPtr<unsigned long long> maxbits, total;
+  DevPtr<unsigned> loop_of, cnt, edge_off, blk_cnt, blk_base;
+  DevPtr<int> k_first, layer_kmin, rec_k;
+  DevPtr<HatchLayerAcc> acc;
+  DevPtr<HatchCounters> ctr;
+  DevPtr<unsigned> slot_base, line_cnt, line_start, cursor, cross_edge, cross_slot, rec_j, rec_slot, layer_start;
+  DevPtr<double> rec_u, u_sorted;
+  DevPtr<float> rec_xy;
+  EventSet<6> ev;
+};
+thread_local double g_hatch_rank_ms = 0;
+}  // namespace
+extern "C" double gsdf_hip_hatch_rank_ms(void) { return g_hatch_rank_ms; }
+
+extern "C" int gsdf_hip_contour_hatch(const gsdf_contour* c, const gsdf_hatch_opts* o, gsdf_hatch** out, gsdf_hatch_stats* st_out) {
+  if (out) *out = nullptr;
+  g_hatch_rank_ms = 0;
+  if (!c || !o) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  if (!std::isfinite(o->spacing) || !(o->spacing > 0.f)) return fail(GSDF_ERR_BAD_ARGUMENT, "hatch: spacing must be finite and positive");
+  if (!std::isfinite(o->offset)) return fail(GSDF_ERR_BAD_ARGUMENT, "hatch: offset must be finite");
+  if (o->n_dirs == 0 || o->n_dirs > 4) return fail(GSDF_ERR_BAD_ARGUMENT, "hatch: n_dirs must be 1 .. 4");
+  for (uint32_t d = 0; d < o->n_dirs; d++) {
+    const float dx = o->dir[d][0], dy = o->dir[d][1];
+    if (!std::isfinite(dx) || !std::isfinite(dy) || !(std::fabs(dx) <= 1.f) || !(std::fabs(dy) <= 1.f) || (dx == 0.f && dy == 0.f))
+      return fail(GSDF_ERR_BAD_ARGUMENT, "hatch: dir " + std::to_string(d) + " must be finite, within [-1, 1] and not (0, 0)");
+  }
+  const bool dry = o->dry != 0;
+  if (!out && !dry) return fail(GSDF_ERR_BAD_ARGUMENT, "hatch: out may be null in a dry run only");
+  const uint64_t V = c->n_verts, NL = c->n_loops;
+  const uint32_t L = c->st.n_layers;
+  HatchParams P{};
+  P.offset = (double)o->offset;
+  P.spacing = (double)o->spacing;
+  const float(*dir)[2] = o->dir;
+  P.dx0 = dir[0][0]; P.dy0 = dir[0][1];
+  P.dx1 = dir[1 % o->n_dirs][0]; P.dy1 = dir[1 % o->n_dirs][1];
+  P.dx2 = dir[2 % o->n_dirs][0]; P.dy2 = dir[2 % o->n_dirs][1];
+  P.dx3 = dir[3 % o->n_dirs][0]; P.dy3 = dir[3 % o->n_dirs][1];
+  P.n_dirs = o->n_dirs;
+  gsdf_hatch_stats st{};
+  st.n_layers = L;
+  HatchPtr h(new (std::nothrow) gsdf_hatch());
+  if (!h) return fail(GSDF_ERR_BAD_ARGUMENT, "out of memory");
+  h->device = c->device;
+  h->n_layers = L;
+  h->layer_start.assign((size_t)L + 1, 0u);
+  h->layers.assign(L, gsdf_hatch_layer{0.0, 0, 0, -1});
+  auto too_small = [&](int e) { return (std::ldexp(1.0, e + 1) + std::fabs(P.offset)) / P.spacing >= 536870912.0; };
+  const char* small_text = "hatch: spacing is too small for these coordinates ((2^(e+1) + |offset|) / spacing must stay below 2^29)";
+
+  HIP_TRY(hipSetDevice(c->device));
+  if (V == 0 || NL == 0) {
+    if (too_small(-125)) return fail(GSDF_ERR_BAD_ARGUMENT, small_text);
+  } else {
+    Stream stream;  // (ahead of the workspace: the work on it is over before the buffers go, and it goes last)
+    HIP_TRY(stream.ensure());
+    hipStream_t s = stream.s;
+    HatchWs w;
+    const char* nomem = "hatch: no device memory for the workspace";
+    if (!dev_alloc(w.maxbits, 1)) return fail(GSDF_ERR_HIP, nomem);
+    if (w.ev.ensure() != hipSuccess) return fail(GSDF_ERR_HIP, "hipEventCreate failed");
+    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{s};
+    auto interval_ms = [&](int a, int b) { float t = 0; return hipEventElapsedTime(&t, w.ev[a], w.ev[b]) == hipSuccess ? (double)t : 0.0; };
+    // 0. the exponent; the one argument check that needs it
+    const unsigned nb = blocks_of(V), nb_max = blocks_of(2 * V) < 1024u ? blocks_of(2 * V) : 1024u;
+    unsigned long long h_maxbits = 0;
+    HIP_TRY(hipEventRecord(w.ev[0], s));
+    HIP_TRY(hipMemsetAsync(w.maxbits.p, 0, 8, s));
+    LAUNCH(cmeas_maxbits_kernel, nb_max, s, (const float*)c->xy.p, (unsigned long long)(2 * V), w.maxbits.p);
+    HIP_TRY(hipEventRecord(w.ev[1], s));
+    HIP_TRY(hipMemcpyAsync(&h_maxbits, w.maxbits.p, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    st.ms_device += interval_ms(0, 1);
+    const unsigned biased = (unsigned)(h_maxbits >> 23);
+    const int e = (int)(biased > 1u ? biased : 1u) - 126;
+    if (too_small(e)) return fail(GSDF_ERR_BAD_ARGUMENT, small_text);
+    // 1. every edge's lines, the layers' line ranges, the edges' offsets
+    if (!dev_alloc(w.loop_of, V) || !dev_alloc(w.k_first, V) || !dev_alloc(w.cnt, V) || !dev_alloc(w.edge_off, V + 1) || !dev_alloc(w.blk_cnt, nb) ||
+        !dev_alloc(w.blk_base, nb) || !dev_alloc(w.total, 1) || !dev_alloc(w.acc, L) || !dev_alloc(w.ctr, 1) || !dev_alloc(w.slot_base, (uint64_t)L + 1) ||
+        !dev_alloc(w.layer_kmin, L) || !dev_alloc(w.layer_start, (uint64_t)L + 1))
+      return fail(GSDF_ERR_HIP, nomem);
+    std::vector<HatchLayerAcc> h_acc(L);
+    HatchCounters h_ctr{};
+    HIP_TRY(hipEventRecord(w.ev[0], s));
+    HIP_TRY(hipMemsetAsync(w.ctr.p, 0, sizeof(HatchCounters), s));
+    LAUNCH(hatch_init_kernel, blocks_of(L), s, w.acc.p, (unsigned)L);
+    LAUNCH(cloop_of_kernel, nb, s, (const unsigned*)c->loop_start.p, (unsigned)NL, (unsigned)V, w.loop_of.p);
+    LAUNCH(hatch_range_kernel, nb, s, (const float*)c->xy.p, (const unsigned*)c->loop_start.p, (const unsigned*)w.loop_of.p, (const unsigned*)c->loop_layer.p, (unsigned)V, (unsigned)L,
+           P, w.k_first.p, w.cnt.p, w.blk_cnt.p, w.acc.p, w.ctr.p);
+    if (int rc = launch_block_scan(w.blk_cnt.p, nb, w.blk_base.p, w.total.p, s)) return rc;
+    LAUNCH(hatch_scan_kernel, nb, s, (const unsigned*)w.cnt.p, (unsigned)V, (const unsigned*)w.blk_base.p, w.edge_off.p);
+    HIP_TRY(hipEventRecord(w.ev[1], s));
+    HIP_TRY(hipMemcpyAsync(&h_ctr, w.ctr.p, sizeof h_ctr, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h_acc.data(), w.acc.p, (size_t)L * sizeof(HatchLayerAcc), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    st.ms_device += interval_ms(0, 1);
+    if (h_ctr.bad) return fail(GSDF_ERR_HIP, "hatch: internal error (a loop names a layer the handle does not have)");
+    const uint64_t N = h_ctr.n_crossings;
+    if (N >= ((uint64_t)1 << 32)) return fail(GSDF_ERR_CAPACITY, "hatch: 2^32 crossings or more");
+    // the layers' line slots behind one another
+    std::vector<unsigned> h_slot_base((size_t)L + 1, 0u);
+    std::vector<int> h_kmin(L, 0);
+    uint64_t S = 0;
+    for (uint32_t l = 0; l < L; l++) {
+      h_slot_base[l] = (unsigned)S;
+      if (h_acc[l].k_min <= h_acc[l].k_max) {
+        h_kmin[l] = h_acc[l].k_min;
+        h->layers[l].k_min = h_acc[l].k_min;
+        h->layers[l].k_max = h_acc[l].k_max;
+        S += (uint64_t)((int64_t)h_acc[l].k_max - (int64_t)h_acc[l].k_min + 1);
+      }
+      if (S >= ((uint64_t)1 << 31)) return fail(GSDF_ERR_CAPACITY, "hatch: 2^31 line slots or more");
+    }
+    h_slot_base[L] = (unsigned)S;
+    if (N > 0) {
+      if ((N & 1) || S == 0) return fail(GSDF_ERR_HIP, "hatch: internal error (an odd number of crossings)");
+      const uint64_t NS = N / 2;
+      // 2. crossings per line slot, the buckets' starts
+      const unsigned nb_x = blocks_of(N), nb_s = blocks_of(S);
+      if (!dev_alloc(w.line_cnt, S) || !dev_alloc(w.line_start, S + 1) || !dev_alloc(w.cursor, S) || !dev_alloc(w.cross_edge, N) || !dev_alloc(w.cross_slot, N) ||
+          !dev_alloc(w.blk_cnt, nb_s) || !dev_alloc(w.blk_base, nb_s) || !dev_alloc(w.rec_u, N) || !dev_alloc(w.rec_j, N) || !dev_alloc(w.rec_xy, 2 * N) ||
+          !dev_alloc(w.rec_slot, N) || !dev_alloc(w.rec_k, N) || !dev_alloc(w.u_sorted, N))
+        return fail(GSDF_ERR_HIP, nomem);
+      if (!dev_alloc(h->seg, 4 * NS) || !dev_alloc(h->line, NS)) return fail(GSDF_ERR_HIP, "hatch: no device memory for the result");
+      HIP_TRY(hipMemcpyAsync(w.slot_base.p, h_slot_base.data(), ((size_t)L + 1) * 4, hipMemcpyHostToDevice, s));
+      HIP_TRY(hipMemcpyAsync(w.layer_kmin.p, h_kmin.data(), (size_t)L * 4, hipMemcpyHostToDevice, s));
+      HIP_TRY(hipEventRecord(w.ev[2], s));
+      HIP_TRY(hipMemsetAsync(w.line_cnt.p, 0, (size_t)S * 4, s));
+      HIP_TRY(hipMemsetAsync(w.cursor.p, 0, (size_t)S * 4, s));
+      HIP_TRY(hipMemsetAsync(w.rec_slot.p, 0xff, (size_t)N * 4, s));
+      LAUNCH(hatch_count_kernel, nb_x, s, (const unsigned*)w.edge_off.p, (unsigned)V, (const int*)w.k_first.p, (const unsigned*)w.loop_of.p, (const unsigned*)c->loop_layer.p,
+             (const unsigned*)w.slot_base.p, (const int*)w.layer_kmin.p, (unsigned)L, (unsigned)S, (unsigned)N, w.cross_edge.p, w.cross_slot.p, w.line_cnt.p, w.ctr.p);
+      LAUNCH(hatch_lines_kernel, nb_s, s, (const unsigned*)w.line_cnt.p, (unsigned)S, w.blk_cnt.p, w.ctr.p);
+      if (int rc = launch_block_scan(w.blk_cnt.p, nb_s, w.blk_base.p, w.total.p, s)) return rc;
+      LAUNCH(hatch_scan_kernel, nb_s, s, (const unsigned*)w.line_cnt.p, (unsigned)S, (const unsigned*)w.blk_base.p, w.line_start.p);
+      // 3. records into their buckets, 4. each to its rank; the layers' starts and lengths
+      LAUNCH(hatch_emit_kernel, nb_x, s, (const float*)c->xy.p, (const unsigned*)c->loop_start.p, (const unsigned*)w.loop_of.p, (const unsigned*)c->loop_layer.p, P,
+             (const unsigned*)w.edge_off.p, (const int*)w.k_first.p, (const unsigned*)w.cross_edge.p, (const unsigned*)w.cross_slot.p, (const unsigned*)w.line_start.p, (unsigned)S,
+             (unsigned)N, w.cursor.p, w.rec_u.p, w.rec_j.p, w.rec_xy.p, w.rec_slot.p, w.rec_k.p, w.ctr.p);
+      HIP_TRY(hipEventRecord(w.ev[3], s));
+      LAUNCH(hatch_rank_kernel, nb_x, s, (const double*)w.rec_u.p, (const unsigned*)w.rec_j.p, (const float*)w.rec_xy.p, (const unsigned*)w.rec_slot.p, (const int*)w.rec_k.p,
+             (const unsigned*)w.line_start.p, (unsigned)S, (unsigned)N, h->seg.p, h->line.p, w.u_sorted.p, w.ctr.p);
+      HIP_TRY(hipEventRecord(w.ev[4], s));
+      LAUNCH(hatch_layer_start_kernel, blocks_of((uint64_t)L + 1), s, (const unsigned*)w.line_start.p, (const unsigned*)w.slot_base.p, (unsigned)L, w.layer_start.p);
+      LAUNCH(hatch_length_kernel, blocks_of(NS), s, (const double*)w.u_sorted.p, (const unsigned*)h->seg.p, (const unsigned*)w.layer_start.p, (unsigned)L, (unsigned)NS,
+             (const unsigned long long*)w.maxbits.p, w.acc.p, w.ctr.p);
+      HIP_TRY(hipEventRecord(w.ev[5], s));
+      HIP_TRY(hipMemcpyAsync(&h_ctr, w.ctr.p, sizeof h_ctr, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(h_acc.data(), w.acc.p, (size_t)L * sizeof(HatchLayerAcc), hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(h->layer_start.data(), w.layer_start.p, ((size_t)L + 1) * 4, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+      st.ms_device += interval_ms(2, 3) + interval_ms(3, 4) + interval_ms(4, 5);
+      g_hatch_rank_ms = interval_ms(3, 4);
+      if (h_ctr.bad || h->layer_start[L] != NS) return fail(GSDF_ERR_HIP, "hatch: internal error (a line with an odd number of crossings, or a record out of range)");
+      h->n_segments = NS;
+      st.n_segments = NS;
+      st.n_crossings = N;
+      st.n_lines = h_ctr.n_lines;
+      st.max_line_crossings = h_ctr.max_line;
+      st.zero_length = h_ctr.zero_length;
+      // integers -> float64 with one rounding each, times the inverse power of two (exact)
+      __int128 all = 0;
+      for (uint32_t l = 0; l < L; l++) {
+        const __int128 sum = (__int128)(long long)h_acc[l].sum[1] * ((__int128)1 << 32) + (__int128)h_acc[l].sum[0];
+        all += sum;
+        h->layers[l].length = std::ldexp((double)sum, e - 58);
+        h->layers[l].n_segments = h->layer_start[l + 1] - h->layer_start[l];
+      }
+      st.length = std::ldexp((double)all, e - 58);
+    }
+  }
+  if (st_out) *st_out = st;
+  if (!dry) *out = h.release();
+  return GSDF_OK;
+}
+
+extern "C" int gsdf_hip_hatch_counts(const gsdf_hatch* h, uint32_t* n_layers, uint64_t* n_segments) {
+  if (!h) return fail(GSDF_ERR_BAD_ARGUMENT, "null hatch");
+  if (n_layers) *n_layers = h->n_layers;
+  if (n_segments) *n_segments = h->n_segments;
+  return GSDF_OK;
+}
+
+extern "C" int gsdf_hip_hatch_read(const gsdf_hatch* h, float* seg, int32_t* line, uint32_t* layer_start, gsdf_hatch_layer* layers) {
+  if (!h) return fail(GSDF_ERR_BAD_ARGUMENT, "null hatch");
+  HIP_TRY(hipSetDevice(h->device));
+  if (seg && h->n_segments) HIP_TRY(hipMemcpy(seg, h->seg.p, (size_t)h->n_segments * 16, hipMemcpyDeviceToHost));
+  if (line && h->n_segments) HIP_TRY(hipMemcpy(line, h->line.p, (size_t)h->n_segments * 4, hipMemcpyDeviceToHost));
+  if (layer_start) std::memcpy(layer_start, h->layer_start.data(), h->layer_start.size() * 4);
+  if (layers && h->n_layers) std::memcpy(layers, h->layers.data(), (size_t)h->n_layers * sizeof(gsdf_hatch_layer));
   return GSDF_OK;
 }

@@ -33,7 +33,8 @@ SYMBOLS = ["gsdf_hip_last_error", "gsdf_hip_init", "gsdf_hip_program_create", "g
            "gsdf_hip_raycast3", "gsdf_hip_indexed_thickness",
            "gsdf_hip_contour2", "gsdf_hip_slice3", "gsdf_hip_contour_counts", "gsdf_hip_contour_read", "gsdf_hip_contour_stats_get", "gsdf_hip_contour_destroy",
            "gsdf_hip_contour_create", "gsdf_hip_contour_simplify", "gsdf_hip_contour_measures", "gsdf_hip_contour_measures_ms",
-           "gsdf_hip_indexed_mass", "gsdf_hip_indexed_mass_ms", "gsdf_hip_inertia_principal", "gsdf_hip_contour_sections", "gsdf_hip_contour_sections_ms"]
+           "gsdf_hip_indexed_mass", "gsdf_hip_indexed_mass_ms", "gsdf_hip_inertia_principal", "gsdf_hip_contour_sections", "gsdf_hip_contour_sections_ms",
+           "gsdf_hip_contour_hatch", "gsdf_hip_hatch_counts", "gsdf_hip_hatch_read", "gsdf_hip_hatch_rank_ms", "gsdf_hip_hatch_destroy"]
 
 
 PRUNE_ASSUME_SDF = 1 << 30  # gsdf_hip.h: GSDF_PRUNE_ASSUME_SDF
@@ -262,6 +263,31 @@ class Section(C.Structure):
                 ("central", C.c_double * 3), ("n_verts", C.c_uint32), ("layer_or_n_loops", C.c_uint32)]
 
 
+class HatchOpts(C.Structure):
+    """gsdf_hatch_opts (gsdf_hip.h, "contours: hatch fill"): the lines' spacing and offset, the directions the layers take in turn, dry."""
+    _fields_ = [("spacing", C.c_float), ("offset", C.c_float), ("n_dirs", C.c_uint32), ("dry", C.c_uint32), ("dir", (C.c_float * 2) * 4)]
+
+
+class HatchLayer(C.Structure):
+    """gsdf_hatch_layer (gsdf_hip.h): a layer's hatch length (in units of |dir|), its segments, the smallest and largest line number
+    with a crossing (0, -1: none)."""
+    _fields_ = [("length", C.c_double), ("n_segments", C.c_uint64), ("k_min", C.c_int32), ("k_max", C.c_int32)]
+
+
+class HatchStats(C.Structure):
+    """gsdf_hatch_stats (gsdf_hip.h): what a hatch produced; bytes 0 .. 55 (RESULT_BYTES) are a function of the loops and the options
+    alone, ms_device says what the run cost."""
+    _fields_ = [("n_segments", C.c_uint64), ("n_crossings", C.c_uint64), ("n_lines", C.c_uint64), ("max_line_crossings", C.c_uint64),
+                ("zero_length", C.c_uint64), ("n_layers", C.c_uint32), ("reserved", C.c_uint32), ("length", C.c_double), ("ms_device", C.c_double)]
+    RESULT_BYTES = 56
+
+    def result_bytes(self):
+        return bytes(self)[:self.RESULT_BYTES]
+
+
+HATCH_LAYER_DTYPE = np.dtype([("length", "<f8"), ("n_segments", "<u8"), ("k_min", "<i4"), ("k_max", "<i4")])
+
+
 # the same two as numpy records (arrays of shells, of loops, of layers)
 MASS_DTYPE = np.dtype([("volume", "<f8"), ("first", "<f8", (3,)), ("second", "<f8", (6,)), ("centroid", "<f8", (3,)), ("inertia", "<f8", (6,)),
                        ("exponent", "<i4"), ("label", "<u4")])
@@ -420,6 +446,13 @@ def lib():
         L.gsdf_hip_contour_sections.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.gsdf_hip_contour_sections_ms.argtypes = []
         L.gsdf_hip_contour_sections_ms.restype = C.c_double
+        L.gsdf_hip_contour_hatch.argtypes = [C.c_void_p, C.POINTER(HatchOpts), C.POINTER(C.c_void_p), C.POINTER(HatchStats)]
+        L.gsdf_hip_hatch_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+        L.gsdf_hip_hatch_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.gsdf_hip_hatch_rank_ms.argtypes = []
+        L.gsdf_hip_hatch_rank_ms.restype = C.c_double
+        L.gsdf_hip_hatch_destroy.argtypes = [C.c_void_p]
+        L.gsdf_hip_hatch_destroy.restype = None
         L.gsdf_hip_brick_owner.restype = C.c_uint32
         L.gsdf_hip_brick_owner.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         L.gsdf_hip_slab_range.restype = None
@@ -1322,6 +1355,29 @@ class ContourHIP:
         """Device milliseconds (HIP events) of this thread's last sections()."""
         return float(lib().gsdf_hip_contour_sections_ms())
 
+    def hatch_dirs(self, spacing, dirs, offset=0.0, dry=False):
+        """gsdf_hip_contour_hatch with raw float32 directions (1 .. 4 pairs (dx, dy); layer l takes dirs[l % len(dirs)]): a HatchHIP;
+        dry: (None, HatchStats)."""
+        dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 2)
+        o = HatchOpts(np.float32(spacing), np.float32(offset), len(dirs), int(bool(dry)))
+        for k, (dx, dy) in enumerate(dirs[:4]):
+            o.dir[k][0], o.dir[k][1] = float(dx), float(dy)
+        st, h = HatchStats(), C.c_void_p()
+        _check(lib().gsdf_hip_contour_hatch(self._h, C.byref(o), None if dry else C.byref(h), C.byref(st)))
+        return (None, st) if dry else HatchHIP(h, st)
+
+    def hatch(self, spacing, angles_deg=(45.0,), offset=0.0, dry=False):
+        """The segments of parallel lines `spacing` apart inside the loops of every layer (gsdf_hip.h, "contours: hatch fill"); layer l
+        takes the direction float32(cos), float32(sin) of angles_deg[l % len(angles_deg)], computed in float64. A HatchHIP; dry: (None,
+        HatchStats)."""
+        a = np.radians(np.asarray(angles_deg, np.float64).reshape(-1))
+        return self.hatch_dirs(spacing, np.stack([np.cos(a), np.sin(a)], axis=1).astype(np.float32), offset, dry)
+
+    @staticmethod
+    def hatch_rank_ms():
+        """Device milliseconds (HIP events) of the rank pass of this thread's last hatch."""
+        return float(lib().gsdf_hip_hatch_rank_ms())
+
     def loops(self, layer=None):
         """The loops (of one layer, or of all) as (n, 2) float32 arrays, in the handle's order."""
         return [self.xy[self.loop_start[q]:self.loop_start[q + 1]] for q in range(self.n_loops) if layer is None or self.loop_layer[q] == layer]
@@ -1329,6 +1385,38 @@ class ContourHIP:
     def areas(self):
         """Signed area of every loop: the float64 shoelace sum over the handle's order, on the host (outer boundaries > 0, holes < 0)."""
         return np.array([loop_area(l) for l in self.loops()], np.float64)
+
+
+class HatchHIP:
+    """The hatch segments of a ContourHIP (gsdf_hatch): seg (n, 4) float32 (x0 y0 x1 y1), line n int32 (the line number k of each),
+    layer_start n_layers + 1, layers (HATCH_LAYER_DTYPE records), stats (HatchStats). Independent of the loops it was made from."""
+
+    def __init__(self, handle, stats):
+        self._h = handle
+        self.stats = stats
+        nl, ns = C.c_uint32(), C.c_uint64()
+        _check(lib().gsdf_hip_hatch_counts(handle, C.byref(nl), C.byref(ns)))
+        self.n_layers, self.n_segments = int(nl.value), int(ns.value)
+        self.seg = np.empty((self.n_segments, 4), np.float32)
+        self.line = np.empty(self.n_segments, np.int32)
+        self.layer_start = np.empty(self.n_layers + 1, np.uint32)
+        self.layers = np.zeros(self.n_layers, HATCH_LAYER_DTYPE)
+        _check(lib().gsdf_hip_hatch_read(handle, self.seg.ctypes.data, self.line.ctypes.data, self.layer_start.ctypes.data, self.layers.ctypes.data))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().gsdf_hip_hatch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def segments(self, layer):
+        """The segments of one layer, (n, 4) float32, in (k, position) order."""
+        return self.seg[self.layer_start[layer]:self.layer_start[layer + 1]]
 
 
 def loop_area(xy):

@@ -1,5 +1,5 @@
-"""SVG outlines with the standard library only (struct, re): the loops of a ContourHIP as one even-odd <path> per layer, and their
-reader. Coordinates are written as the shortest decimal that reads back as the same float32, so write followed by read is bit-exact;
+"""SVG outlines with the standard library only (struct, re): the loops of a ContourHIP as one even-odd <path> per layer, their hatch
+segments (a HatchHIP's) as <line> elements in a group of their own, and the loops' reader. Coordinates are written as the shortest decimal that reads back as the same float32, so write followed by read is bit-exact;
 the y axis points up in the part and down in SVG, and is turned by one transform around the paths, not by changing coordinates."""
 import re
 import struct
@@ -23,10 +23,11 @@ def fmt(v):
     raise AssertionError("nine digits always identify a float32")
 
 
-def write_svg(path, layers, z=None, stroke_width=None):
+def write_svg(path, layers, z=None, stroke_width=None, hatch=None):
     """layers: a list (one entry per layer) of lists of loops, each loop (n, 2) float32 in order of travel. One
     <path fill-rule="evenodd"> per layer (an empty layer: an empty path), each loop `M x y L x y ... Z`. z (optional): the layers'
-    heights, kept as data-z."""
+    heights, kept as data-z. hatch (optional): per layer an (n, 4) float32 array of segments x0 y0 x1 y1 (HatchHIP.segments(k)),
+    drawn as <line> elements in one <g id="hatchK"> per layer after the paths: never as <path>, which read_svg takes for a layer."""
     lo, hi = [None, None], [None, None]
     for loops in layers:
         for l in loops:
@@ -54,6 +55,14 @@ def write_svg(path, layers, z=None, stroke_width=None):
             d.append("M " + " L ".join(pts) + " Z")
         zattr = "" if z is None else ' data-z="%s"' % fmt(np.float32(z[k]))
         out.append('<path id="layer%d"%s fill-rule="evenodd" d="%s"/>\n' % (k, zattr, " ".join(d)))
+    if hatch is not None:
+        out.append('<g id="hatch" fill="none" stroke="#a04020" stroke-width="%.9g">\n' % (0.5 * sw))
+        for k, segs in enumerate(hatch):
+            out.append('<g id="hatch%d">\n' % k)
+            for x0, y0, x1, y1 in np.asarray(segs, np.float32).reshape(-1, 4):
+                out.append('<line x1="%s" y1="%s" x2="%s" y2="%s"/>\n' % (fmt(x0), fmt(y0), fmt(x1), fmt(y1)))
+            out.append("</g>\n")
+        out.append("</g>\n")
     out.append("</g>\n</svg>\n")
     with open(path, "w", encoding="utf-8") as f:
         f.write("".join(out))
@@ -62,6 +71,16 @@ def write_svg(path, layers, z=None, stroke_width=None):
 _PATH = re.compile(r'<path\b[^>]*?\bd="([^"]*)"[^>]*/>')
 _NUM = r"[-+]?(?:\d+\.?\d*|\.\d+)(?:[eE][-+]?\d+)?"
 _LOOP = re.compile(r"M\s*((?:%s[\s,]*|L\s*)+)Z" % _NUM)
+
+
+_LINE = re.compile(r'<line x1="(%s)" y1="(%s)" x2="(%s)" y2="(%s)"/>' % ((_NUM,) * 4))
+
+
+def read_svg_hatch(path):
+    """The hatch segments of a file written by write_svg(..., hatch=...): per <g id="hatchK"> an (n, 4) float32 array."""
+    text = open(path, encoding="utf-8").read()
+    return [np.array([[float(v) for v in m.groups()] for m in _LINE.finditer(g)], np.float64).astype(np.float32).reshape(-1, 4)
+            for g in re.findall(r'<g id="hatch\d+">(.*?)</g>', text, flags=re.S)]
 
 
 def read_svg(path):

@@ -1243,8 +1243,9 @@ int gsdf_hip_mesh_dualcontour_indexed(gsdf_program* p, float res, int chiseled, 
  *   are left out), ms_device = their sum. Bytes 0 .. 63 of the record are a function of the inputs alone.
  * Errors. GSDF_ERR_DIMENSION: gsdf_hip_contour2 on a 3-D program, gsdf_hip_slice3 on a 2-D one. GSDF_ERR_BAD_ARGUMENT: the lattice
  *   rules above, n_z == 0, a null z. GSDF_ERR_CAPACITY: 2^32 vertices or more. Blocking; the handle is independent of the program
- *   afterwards. Out of scope: DXF / G-code, arc fitting, tool offsets (Offset2D in the tree is exact), infill, sharded or gathered
- *   contours, a fused lattice kernel, asymptotic-decider saddles. (Simplification and the loops' areas on the device: the next section.)
+ *   afterwards. Out of scope: DXF / G-code, arc fitting, tool offsets (Offset2D in the tree is exact), sharded or gathered
+ *   contours, a fused lattice kernel, asymptotic-decider saddles. (Simplification and the loops' areas on the device: the next section; infill: "contours: hatch
+ *   fill" below.)
  * Kernels: gsdf_amd/csrc/kernels_contour.h (abi_contour.hip); a numpy restatement over the oracle: tests/contourref.py. */
 typedef struct gsdf_contour gsdf_contour; /* loops, resident in HBM */
 #define GSDF_CONTOUR_DEFAULT_MAX_NODES 16777216 /* 2^24 nodes: 0.4 GB of workspace */
@@ -1412,6 +1413,89 @@ GSDF_ABI_ASSERT(offsetof(gsdf_section, first) == 8 && offsetof(gsdf_section, sec
 GSDF_ABI_ASSERT(offsetof(gsdf_section, central) == 64 && offsetof(gsdf_section, n_verts) == 88 && offsetof(gsdf_section, layer_or_n_loops) == 92, "gsdf_section derived values");
 int gsdf_hip_contour_sections(const gsdf_contour* c, gsdf_section* loops /* n_loops or NULL */, gsdf_section* layers /* n_layers or NULL */);
 double gsdf_hip_contour_sections_ms(void);
+
+/* ---- contours: hatch fill (no reference counterpart) ---------------------------------------------------------------------------------
+ *
+ * The step between closed loops and something a printer, a laser or a plotter can follow: for every layer of a gsdf_contour handle
+ * (traced, uploaded or simplified), the segments of a family of parallel lines that lie inside the material. All of it runs on the
+ * device and is a function of the handle's arrays and the options alone, to the byte: NOT of the order in which threads arrive.
+ * Kernels: gsdf_amd/csrc/kernels_hatch.h (abi_contour.hip); a numpy restatement: tests/hatchref.py.
+ *
+ * Coordinates are taken as (double)float32 (exact), so are spacing, offset and dir. Every operation below is one IEEE float64
+ *   operation, in the order written, none contracted (the library is built with -ffp-contract=off).
+ * Vertex values. (dx, dy) = dir[l % n_dirs] is the direction of the vertex's layer l.
+ *     s = ((-dy) x) + (dx y)        u = (dx x) + (dy y)
+ *   All four products are exact (24 x 24 bits): one rounded addition each. s is the coordinate across the lines, u along them.
+ * Lines. Line k (an integer) of a layer is the set s = c_k, c_k = offset + ((double)k spacing). The product is exact while
+ *   |k| < 2^29; the addition's rounding is monotone, so c_k is non-decreasing in k. With a unit dir neighbouring lines are spacing apart.
+ * Crossings. The edge from vertex j to its successor in the loop (the leader follows the last vertex), a and b, crosses line k iff
+ *     (s_a < c_k) != (s_b < c_k)
+ *   A vertex exactly on a line counts as above it; an edge lying on a line does not cross it; every closed loop crosses every line an
+ *   even number of times (the predicate is a function of the vertex alone, and a closed walk changes sides an even number of times).
+ *     t   = (c_k - s_a) / (s_b - s_a)      (the divisor is not 0 at a crossing; 0 <= t <= 1; -0.0 occurs and is allowed)
+ *     u_c = u_a + (t (u_b - u_a))
+ *     x_c = (float)(x_a + (t (x_b - x_a)))   and y_c likewise: float64 arithmetic, rounded once to float32
+ *   How the candidate k of an edge are found is the implementation's business (here: floor((s - offset) / spacing), corrected with
+ *   the predicate); the predicate alone is the contract.
+ * Segments. The crossings of one (layer, k) are ordered by (u_c, j), increasing: u_c compared as doubles (-0 == +0), j, the global
+ *   vertex number of the edge's tail, breaks ties (an edge crosses a line once: the order is total). Consecutive pairs (0, 1),
+ *   (2, 3), ... are the segments: the even-odd rule, which is the material for the tracer's loops (outer boundaries counter-clockwise,
+ *   holes clockwise, properly nested). A segment runs from the lower to the higher u_c (x0 y0, then x1 y1). Segments are ordered by
+ *   (layer, k, position); layer_start[l] is the first segment of layer l, layer_start[n_layers] = n_segments. Nothing is dropped:
+ *   zero_length counts the segments whose two float32 end points are equal bit for bit.
+ * Lengths. A segment's term is u_c1 - u_c0, in units of |dir|. Bound (derived): with e the handle's exponent as in
+ *   gsdf_hip_contour_measures, |x|, |y| <= 2^e (1 - 2^-24) and |dx|, |dy| <= 1, so |s|, |u| <= 2^(e+1) (1 - 2^-24) before and after
+ *   their one rounding; t lies in [0, 1], so |u_c| < 2^(e+1) (1 + 2^-50) and |term| < 2^(e+2) (1 + 2^-50). Scaled by 2^(58-e)
+ *   (exact) the term is below 2^60 (1 + 2^-50): inside the |q| <= 2^62 the measures' scheme needs, with room to spare, so the
+ *   exponent stays 58 - e. Rounded to the nearest integer, ties to even, summed as INTEGERS (on the device: the low 32 bits and the
+ *   arithmetic-shifted rest in separate 64-bit words, which 2^31 segments cannot overflow), converted to float64 with ONE rounding,
+ *   times 2^(e-58) (exact). Error of the quantisation: at most n / 2 units of 2^(e-58) for n segments.
+ *   gsdf_hatch_layer: the layer's length, its n_segments, k_min and k_max = the smallest and the largest k with a crossing; a layer
+ *   without one has k_min = 0, k_max = -1, length 0. The statistics' length is the sum of the layers' integers, converted likewise.
+ * Statistics. Everything before ms_device is a function of the inputs alone. n_crossings = 2 n_segments; n_lines = the (layer, k)
+ *   with a crossing; max_line_crossings = the most crossings on one of them: the rank pass compares every crossing of a line with
+ *   every other one, so its cost grows with the square of this number. ms_device: HIP events around the kernels (the host's waits
+ *   between them left out). gsdf_hip_hatch_rank_ms: of that, the rank pass of the calling thread's last gsdf_hip_contour_hatch.
+ * dry != 0 fills the statistics and builds no handle: out may be NULL, and is set to NULL if it is not.
+ * Errors. GSDF_ERR_BAD_ARGUMENT: spacing not finite or <= 0; offset not finite; n_dirs 0 or > 4; a dir (of the first n_dirs) with a
+ *   non-finite component, |dx| or |dy| > 1, or both 0; out NULL without dry; (2^(e+1) + |offset|) / spacing >= 2^29, decided on the
+ *   host in float64 before any workspace but the exponent's one word is allocated: the text says that spacing is too small for these
+ *   coordinates. (|s| < 2^(e+1): every k that can cross has |k| < 2^29 + 2, and its product with spacing is exact.) GSDF_ERR_CAPACITY:
+ *   2^32 crossings or more, or 2^31 line slots (the sum over the layers of k_max - k_min + 1) or more. A handle without loops gives
+ *   a handle without segments and no error. Blocking; the result is independent of c afterwards.
+ * Out of scope: joining segments into zig-zag paths, travel ordering, concentric or gyroid patterns, dropping short segments,
+ *   clipping against anything but the handle's own loops, a segmented sort for lines with thousands of crossings. */
+typedef struct gsdf_hatch gsdf_hatch; /* segments, resident in HBM */
+typedef struct gsdf_hatch_opts {
+  float spacing;   /* > 0, finite */
+  float offset;    /* finite */
+  uint32_t n_dirs; /* 1 .. 4; layer l uses dir[l % n_dirs] */
+  uint32_t dry;    /* non-zero: statistics only */
+  float dir[4][2]; /* (dx, dy); both finite, |dx|, |dy| <= 1, not both 0. The caller's unit vector: float32(cos), float32(sin) */
+} gsdf_hatch_opts;
+GSDF_ABI_ASSERT(sizeof(gsdf_hatch_opts) == 48, "gsdf_hatch_opts is 48 bytes");
+GSDF_ABI_ASSERT(offsetof(gsdf_hatch_opts, offset) == 4 && offsetof(gsdf_hatch_opts, n_dirs) == 8 && offsetof(gsdf_hatch_opts, dry) == 12 && offsetof(gsdf_hatch_opts, dir) == 16, "gsdf_hatch_opts fields");
+typedef struct gsdf_hatch_layer {
+  double length;
+  uint64_t n_segments;
+  int32_t k_min, k_max;
+} gsdf_hatch_layer;
+GSDF_ABI_ASSERT(sizeof(gsdf_hatch_layer) == 24, "gsdf_hatch_layer is 24 bytes");
+GSDF_ABI_ASSERT(offsetof(gsdf_hatch_layer, n_segments) == 8 && offsetof(gsdf_hatch_layer, k_min) == 16 && offsetof(gsdf_hatch_layer, k_max) == 20, "gsdf_hatch_layer fields");
+typedef struct gsdf_hatch_stats {
+  uint64_t n_segments, n_crossings, n_lines /* (layer, k) pairs with a crossing */, max_line_crossings, zero_length;
+  uint32_t n_layers, reserved;
+  double length;    /* all layers */
+  double ms_device; /* last: everything before it is a function of the inputs alone */
+} gsdf_hatch_stats;
+GSDF_ABI_ASSERT(sizeof(gsdf_hatch_stats) == 64, "gsdf_hatch_stats is 64 bytes");
+GSDF_ABI_ASSERT(offsetof(gsdf_hatch_stats, zero_length) == 32 && offsetof(gsdf_hatch_stats, n_layers) == 40 && offsetof(gsdf_hatch_stats, length) == 48 && offsetof(gsdf_hatch_stats, ms_device) == 56, "gsdf_hatch_stats fields");
+int gsdf_hip_contour_hatch(const gsdf_contour* c, const gsdf_hatch_opts* o, gsdf_hatch** out /* NULL allowed iff dry */, gsdf_hatch_stats* st /* optional */);
+int gsdf_hip_hatch_counts(const gsdf_hatch* h, uint32_t* n_layers, uint64_t* n_segments); /* each optional */
+/* seg 4 n_segments floats (x0 y0 x1 y1), line n_segments (k), layer_start n_layers + 1, layers n_layers; any pointer may be NULL */
+int gsdf_hip_hatch_read(const gsdf_hatch* h, float* seg, int32_t* line, uint32_t* layer_start, gsdf_hatch_layer* layers);
+double gsdf_hip_hatch_rank_ms(void);
+void gsdf_hip_hatch_destroy(gsdf_hatch* h);
 
 /* ---- multi-GPU (one process per GPU). The meshers shard with NO data-path collective (shard_rank / shard_count above); the
  * one exchange is the final variable-length gather of the ranks' results, over xGMI, inside this library: a Go caller needs no
