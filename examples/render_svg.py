@@ -7,6 +7,7 @@ slicer wants of a 3-D part at each layer height:
     python examples/render_svg.py bolt --layer-height 2 --report -o bolt.svg   # every layer of thickness 2, with a report
     python examples/render_svg.py text --simplify 0.125 --report -o text.svg   # vertices within res / 8 of a chord dropped on the GPU
     python examples/render_svg.py bolt --layer-height 2 --hatch 4 --report -o bolt.svg   # hatch lines 4 res apart, 45 / 135 degrees by layer
+    python examples/render_svg.py bolt --layer-height 2 --hatch 4 --skin 1 1 --report    # the hatch classed as inner, bottom, top skin
 
 The lattice spacing is the diagonal of the part's bounds / --resdiv (default 400), or --res. Every layer is one even-odd <path>:
 outer boundaries counter-clockwise, holes clockwise. --report prints loops, vertices, outer and hole counts and the area of every
@@ -17,7 +18,11 @@ summed on the device. The report ends with the section properties of every layer
 device): the centroid and the second moments of area about it. --hatch SPACING fills every layer with the segments of parallel lines
 SPACING x res apart that lie inside the material (gsdf_hip_contour_hatch, on device; on the simplified loops when --simplify is
 given), at the angles of --hatch-angle in turn by layer; they are drawn as <line> elements, and the report adds the segments and the
-hatch length of every layer, the most crossings on one line and the device time. The SVG is written with the standard library only."""
+hatch length of every layer, the most crossings on one line and the device time. --skin BELOW ABOVE (with --hatch) cuts every hatch
+line against the loops of the BELOW layers under and the ABOVE layers over its layer (gsdf_hip_contour_hatch_skin, on device) and
+draws the pieces in one stroke per class: inner, bottom skin, top skin, both; the report then gives length x spacing of every class,
+per layer and in total (an estimate of its area), and the layers above the first BELOW that still have bottom skin: the overhangs.
+The SVG is written with the standard library only."""
 import argparse
 import importlib.util
 import math
@@ -98,6 +103,21 @@ def hatch_report(h, c):
     return "\n".join(lines)
 
 
+def skin_report(h, c, spacing, below):
+    """What --skin made: per layer and in total the area estimate length x spacing of every class, the overhanging layers, the cost."""
+    from gsdf_amd.hip import SKIN_CLASSES
+    st = h.stats
+    by_class = lambda length, n: ", ".join(f"{name} {float(length[q]) * spacing:.9g} ({int(n[q])})" for q, name in enumerate(SKIN_CLASSES))  # noqa: E731
+    lines = [f"layer {k} skin area (pieces): {by_class(m['length'], m['n_segments'])}" for k, m in enumerate(h.skin_layers)]
+    lines.append(f"skin area (pieces) in all: {by_class(st.length, st.n_class)}")
+    over = [f"layer {k} {float(m['length'][1] + m['length'][3]) * spacing:.9g}" for k, m in enumerate(h.skin_layers)
+            if k >= below and (m["n_segments"][1] or m["n_segments"][3])]
+    lines.append(f"overhangs (bottom skin above layer {below - 1}): " + (", ".join(over) or "none"))
+    lines.append(f"skin: window {st.below} below, {st.above} above; {st.n_segments} pieces on {st.n_lines} lines from {st.n_crossings} crossings ({st.n_own_crossings} own), "
+                 f"{st.zero_length} of zero length, max_line_crossings {st.max_line_crossings}, device time {st.ms_device:.3f} ms (rank pass {type(c).skin_rank_ms():.3f} ms)")
+    return "\n".join(lines)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("scene", choices=SCENES_2D + SCENES_3D)
@@ -111,10 +131,13 @@ def main(argv=None):
     ap.add_argument("--max-verts", type=int, default=None, metavar="N", help="--simplify: double the tolerance until at most N vertices are left")
     ap.add_argument("--hatch", type=float, default=None, metavar="SPACING", help="fill the layers with parallel lines SPACING x res apart")
     ap.add_argument("--hatch-angle", type=float, nargs="+", default=[45.0, 135.0], metavar="DEG", help="--hatch: the lines' angles, in turn by layer (1 .. 4)")
+    ap.add_argument("--skin", type=int, nargs=2, default=None, metavar=("BELOW", "ABOVE"), help="--hatch: class the hatch by the layers under and over (0 .. 8 each)")
     ap.add_argument("--report", action="store_true")
     ap.add_argument("--interpreter", action="store_true", help="skip the per-tree kernel build")
     ap.add_argument("-o", "--output", default=None)
     args = ap.parse_args(argv)
+    if args.skin is not None and args.hatch is None:
+        ap.error("--skin classes the hatch: it goes with --hatch SPACING")
 
     import numpy as np
     from gsdf_amd import hip, svg
@@ -149,10 +172,14 @@ def main(argv=None):
     elif args.max_verts is not None:
         ap.error("--max-verts goes with --simplify TOL, the tolerance the doubling starts from")
     out = args.output or f"{args.scene}.svg"
-    hatch = None
+    hatch = hatch_class = None
     if args.hatch is not None:
-        hatch = c.hatch(np.float32(np.float32(args.hatch) * res), args.hatch_angle)
-    svg.write_svg(out, [c.loops(k) for k in range(c.n_layers)], z=z, hatch=None if hatch is None else [hatch.segments(k) for k in range(hatch.n_layers)])
+        hatch_spacing = np.float32(np.float32(args.hatch) * res)
+        hatch = c.hatch(hatch_spacing, args.hatch_angle) if args.skin is None else c.skin(hatch_spacing, args.hatch_angle, *args.skin)
+        if args.skin is not None:
+            hatch_class = [hatch.cls[hatch.layer_start[k]:hatch.layer_start[k + 1]] for k in range(hatch.n_layers)]
+    svg.write_svg(out, [c.loops(k) for k in range(c.n_layers)], z=z, hatch=None if hatch is None else [hatch.segments(k) for k in range(hatch.n_layers)],
+                  hatch_class=hatch_class)
     print(f"{args.scene} res {float(res):.6g}: setup {t1 - t0:.2f} s, contours {(t2 - t1) * 1e3:.1f} ms (the first call includes the kernels' build); "
           f"{c.n_loops} loops, {c.n_verts} vertices in {c.n_layers} layer(s); written to {out}")
     if args.report:
@@ -161,7 +188,7 @@ def main(argv=None):
             print(simplify_report(traced.n_verts, c, *simplified))
         print(section_report(c))
         if hatch is not None:
-            print(hatch_report(hatch, c))
+            print(hatch_report(hatch, c) if args.skin is None else skin_report(hatch, c, float(hatch_spacing), args.skin[0]))
     return 0
 
 

@@ -5,7 +5,8 @@
 // Behind the tracer (section "contours: simplify and measures", kernels_contour_simplify.h): gsdf_hip_contour_create uploads loops,
 // gsdf_hip_contour_simplify drops vertices within a tolerance of dyadic chords, gsdf_hip_contour_measures sums areas and lengths,
 // gsdf_hip_contour_sections (kernels_mass.h) first and second moments of area, gsdf_hip_contour_hatch (kernels_hatch.h) the segments
-// of parallel lines inside the loops, as a gsdf_hatch handle of its own.
+// of parallel lines inside the loops, as a gsdf_hatch handle of its own, gsdf_hip_contour_hatch_skin (kernels_skin.h) those segments cut
+// against the layers under and over each layer and classed as inner, bottom or top skin.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -22,6 +23,7 @@
 #include "kernels_mass.h"
 #include "mass_host.h"
 #include "kernels_hatch.h"
+#include "kernels_skin.h"
 #include "abi_program.h"
 
 struct gsdf_contour {
@@ -591,6 +593,10 @@ struct gsdf_hatch {
   DevPtr<int> line;   // n_segments
   std::vector<uint32_t> layer_start;  // n_layers + 1
   std::vector<gsdf_hatch_layer> layers;
+  // a skin handle (gsdf_hip_contour_hatch_skin) only: every segment's class, the layers' records by class
+  bool has_classes = false;
+  DevPtr<unsigned char> cls;  // n_segments
+  std::vector<gsdf_skin_layer> skin_layers;
 };
 
 extern "C" void gsdf_hip_hatch_destroy(gsdf_hatch* h) {
@@ -615,13 +621,9 @@ struct HatchWs {
   EventSet<6> ev;
 };
 thread_local double g_hatch_rank_ms = 0;
-}  // namespace
-extern "C" double gsdf_hip_hatch_rank_ms(void) { return g_hatch_rank_ms; }
 
-extern "C" int gsdf_hip_contour_hatch(const gsdf_contour* c, const gsdf_hatch_opts* o, gsdf_hatch** out, gsdf_hatch_stats* st_out) {
-  if (out) *out = nullptr;
-  g_hatch_rank_ms = 0;
-  if (!c || !o) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+// ---- what gsdf_hip_contour_hatch and gsdf_hip_contour_hatch_skin share: the options' checks, the exponent, the layers' own lines
+int hatch_params(const gsdf_hatch_opts* o, const void* out, HatchParams* P_out) {
   if (!std::isfinite(o->spacing) || !(o->spacing > 0.f)) return fail(GSDF_ERR_BAD_ARGUMENT, "hatch: spacing must be finite and positive");
   if (!std::isfinite(o->offset)) return fail(GSDF_ERR_BAD_ARGUMENT, "hatch: offset must be finite");
   if (o->n_dirs == 0 || o->n_dirs > 4) return fail(GSDF_ERR_BAD_ARGUMENT, "hatch: n_dirs must be 1 .. 4");
@@ -630,10 +632,7 @@ extern "C" int gsdf_hip_contour_hatch(const gsdf_contour* c, const gsdf_hatch_op
     if (!std::isfinite(dx) || !std::isfinite(dy) || !(std::fabs(dx) <= 1.f) || !(std::fabs(dy) <= 1.f) || (dx == 0.f && dy == 0.f))
       return fail(GSDF_ERR_BAD_ARGUMENT, "hatch: dir " + std::to_string(d) + " must be finite, within [-1, 1] and not (0, 0)");
   }
-  const bool dry = o->dry != 0;
-  if (!out && !dry) return fail(GSDF_ERR_BAD_ARGUMENT, "hatch: out may be null in a dry run only");
-  const uint64_t V = c->n_verts, NL = c->n_loops;
-  const uint32_t L = c->st.n_layers;
+  if (!out && o->dry == 0) return fail(GSDF_ERR_BAD_ARGUMENT, "hatch: out may be null in a dry run only");
   HatchParams P{};
   P.offset = (double)o->offset;
   P.spacing = (double)o->spacing;
@@ -643,6 +642,94 @@ extern "C" int gsdf_hip_contour_hatch(const gsdf_contour* c, const gsdf_hatch_op
   P.dx2 = dir[2 % o->n_dirs][0]; P.dy2 = dir[2 % o->n_dirs][1];
   P.dx3 = dir[3 % o->n_dirs][0]; P.dy3 = dir[3 % o->n_dirs][1];
   P.n_dirs = o->n_dirs;
+  *P_out = P;
+  return GSDF_OK;
+}
+
+bool hatch_too_small(const HatchParams& P, int e) { return (std::ldexp(1.0, e + 1) + std::fabs(P.offset)) / P.spacing >= 536870912.0; }
+const char* const kHatchSmallText = "hatch: spacing is too small for these coordinates ((2^(e+1) + |offset|) / spacing must stay below 2^29)";
+const char* const kHatchNoMem = "hatch: no device memory for the workspace";
+
+// a stream that is waited for before the buffers declared ahead of it go
+struct StreamDrain { hipStream_t s; ~StreamDrain() { (void)hipStreamSynchronize(s); } };
+
+double event_ms(hipEvent_t a, hipEvent_t b) { float t = 0; return hipEventElapsedTime(&t, a, b) == hipSuccess ? (double)t : 0.0; }
+
+// Steps 0 and 1 of a hatch on s (w.ev[0], w.ev[1]; w.maxbits and w.ev are the caller's): the exponent and the one argument check that
+// needs it; every edge's lines (k_first, cnt, edge_off), the layers' line ranges, the crossings of the call. Waits for s.
+int hatch_ranges(const gsdf_contour* c, const HatchParams& P, hipStream_t s, HatchWs& w, int* e_out, std::vector<HatchLayerAcc>& h_acc, uint64_t* n_crossings, double* ms) {
+  const uint64_t V = c->n_verts, NL = c->n_loops;
+  const uint32_t L = c->st.n_layers;
+  // 0. the exponent; the one argument check that needs it
+  const unsigned nb = blocks_of(V), nb_max = blocks_of(2 * V) < 1024u ? blocks_of(2 * V) : 1024u;
+  unsigned long long h_maxbits = 0;
+  HIP_TRY(hipEventRecord(w.ev[0], s));
+  HIP_TRY(hipMemsetAsync(w.maxbits.p, 0, 8, s));
+  LAUNCH(cmeas_maxbits_kernel, nb_max, s, (const float*)c->xy.p, (unsigned long long)(2 * V), w.maxbits.p);
+  HIP_TRY(hipEventRecord(w.ev[1], s));
+  HIP_TRY(hipMemcpyAsync(&h_maxbits, w.maxbits.p, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  *ms += event_ms(w.ev[0], w.ev[1]);
+  const unsigned biased = (unsigned)(h_maxbits >> 23);
+  const int e = (int)(biased > 1u ? biased : 1u) - 126;
+  *e_out = e;
+  if (hatch_too_small(P, e)) return fail(GSDF_ERR_BAD_ARGUMENT, kHatchSmallText);
+  // 1. every edge's lines, the layers' line ranges, the edges' offsets
+  if (!dev_alloc(w.loop_of, V) || !dev_alloc(w.k_first, V) || !dev_alloc(w.cnt, V) || !dev_alloc(w.edge_off, V + 1) || !dev_alloc(w.blk_cnt, nb) ||
+      !dev_alloc(w.blk_base, nb) || !dev_alloc(w.total, 1) || !dev_alloc(w.acc, L) || !dev_alloc(w.ctr, 1) || !dev_alloc(w.slot_base, (uint64_t)L + 1) ||
+      !dev_alloc(w.layer_kmin, L) || !dev_alloc(w.layer_start, (uint64_t)L + 1))
+    return fail(GSDF_ERR_HIP, kHatchNoMem);
+  h_acc.assign(L, HatchLayerAcc{});
+  HatchCounters h_ctr{};
+  HIP_TRY(hipEventRecord(w.ev[0], s));
+  HIP_TRY(hipMemsetAsync(w.ctr.p, 0, sizeof(HatchCounters), s));
+  LAUNCH(hatch_init_kernel, blocks_of(L), s, w.acc.p, (unsigned)L);
+  LAUNCH(cloop_of_kernel, nb, s, (const unsigned*)c->loop_start.p, (unsigned)NL, (unsigned)V, w.loop_of.p);
+  LAUNCH(hatch_range_kernel, nb, s, (const float*)c->xy.p, (const unsigned*)c->loop_start.p, (const unsigned*)w.loop_of.p, (const unsigned*)c->loop_layer.p, (unsigned)V, (unsigned)L,
+         P, w.k_first.p, w.cnt.p, w.blk_cnt.p, w.acc.p, w.ctr.p);
+  if (int rc = launch_block_scan(w.blk_cnt.p, nb, w.blk_base.p, w.total.p, s)) return rc;
+  LAUNCH(hatch_scan_kernel, nb, s, (const unsigned*)w.cnt.p, (unsigned)V, (const unsigned*)w.blk_base.p, w.edge_off.p);
+  HIP_TRY(hipEventRecord(w.ev[1], s));
+  HIP_TRY(hipMemcpyAsync(&h_ctr, w.ctr.p, sizeof h_ctr, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(h_acc.data(), w.acc.p, (size_t)L * sizeof(HatchLayerAcc), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  *ms += event_ms(w.ev[0], w.ev[1]);
+  if (h_ctr.bad) return fail(GSDF_ERR_HIP, "hatch: internal error (a loop names a layer the handle does not have)");
+  *n_crossings = h_ctr.n_crossings;
+  if (h_ctr.n_crossings >= ((uint64_t)1 << 32)) return fail(GSDF_ERR_CAPACITY, "hatch: 2^32 crossings or more");
+  return GSDF_OK;
+}
+
+// the layers' line slots (layer, k - k_min) behind one another
+int hatch_slots(const std::vector<HatchLayerAcc>& h_acc, std::vector<unsigned>& slot_base, std::vector<int>& k_min, uint64_t* n_slots) {
+  const size_t L = h_acc.size();
+  slot_base.assign(L + 1, 0u);
+  k_min.assign(L, 0);
+  uint64_t S = 0;
+  for (size_t l = 0; l < L; l++) {
+    slot_base[l] = (unsigned)S;
+    if (h_acc[l].k_min <= h_acc[l].k_max) {
+      k_min[l] = h_acc[l].k_min;
+      S += (uint64_t)((int64_t)h_acc[l].k_max - (int64_t)h_acc[l].k_min + 1);
+    }
+    if (S >= ((uint64_t)1 << 31)) return fail(GSDF_ERR_CAPACITY, "hatch: 2^31 line slots or more");
+  }
+  slot_base[L] = (unsigned)S;
+  *n_slots = S;
+  return GSDF_OK;
+}
+}  // namespace
+extern "C" double gsdf_hip_hatch_rank_ms(void) { return g_hatch_rank_ms; }
+
+extern "C" int gsdf_hip_contour_hatch(const gsdf_contour* c, const gsdf_hatch_opts* o, gsdf_hatch** out, gsdf_hatch_stats* st_out) {
+  if (out) *out = nullptr;
+  g_hatch_rank_ms = 0;
+  if (!c || !o) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  HatchParams P{};
+  if (int rc = hatch_params(o, out, &P)) return rc;
+  const bool dry = o->dry != 0;
+  const uint64_t V = c->n_verts, NL = c->n_loops;
+  const uint32_t L = c->st.n_layers;
   gsdf_hatch_stats st{};
   st.n_layers = L;
   HatchPtr h(new (std::nothrow) gsdf_hatch());
@@ -651,73 +738,34 @@ extern "C" int gsdf_hip_contour_hatch(const gsdf_contour* c, const gsdf_hatch_op
   h->n_layers = L;
   h->layer_start.assign((size_t)L + 1, 0u);
   h->layers.assign(L, gsdf_hatch_layer{0.0, 0, 0, -1});
-  auto too_small = [&](int e) { return (std::ldexp(1.0, e + 1) + std::fabs(P.offset)) / P.spacing >= 536870912.0; };
-  const char* small_text = "hatch: spacing is too small for these coordinates ((2^(e+1) + |offset|) / spacing must stay below 2^29)";
 
   HIP_TRY(hipSetDevice(c->device));
   if (V == 0 || NL == 0) {
-    if (too_small(-125)) return fail(GSDF_ERR_BAD_ARGUMENT, small_text);
+    if (hatch_too_small(P, -125)) return fail(GSDF_ERR_BAD_ARGUMENT, kHatchSmallText);
   } else {
     Stream stream;  // (ahead of the workspace: the work on it is over before the buffers go, and it goes last)
     HIP_TRY(stream.ensure());
     hipStream_t s = stream.s;
     HatchWs w;
-    const char* nomem = "hatch: no device memory for the workspace";
+    const char* nomem = kHatchNoMem;
     if (!dev_alloc(w.maxbits, 1)) return fail(GSDF_ERR_HIP, nomem);
     if (w.ev.ensure() != hipSuccess) return fail(GSDF_ERR_HIP, "hipEventCreate failed");
-    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{s};
-    auto interval_ms = [&](int a, int b) { float t = 0; return hipEventElapsedTime(&t, w.ev[a], w.ev[b]) == hipSuccess ? (double)t : 0.0; };
-    // 0. the exponent; the one argument check that needs it
-    const unsigned nb = blocks_of(V), nb_max = blocks_of(2 * V) < 1024u ? blocks_of(2 * V) : 1024u;
-    unsigned long long h_maxbits = 0;
-    HIP_TRY(hipEventRecord(w.ev[0], s));
-    HIP_TRY(hipMemsetAsync(w.maxbits.p, 0, 8, s));
-    LAUNCH(cmeas_maxbits_kernel, nb_max, s, (const float*)c->xy.p, (unsigned long long)(2 * V), w.maxbits.p);
-    HIP_TRY(hipEventRecord(w.ev[1], s));
-    HIP_TRY(hipMemcpyAsync(&h_maxbits, w.maxbits.p, 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    st.ms_device += interval_ms(0, 1);
-    const unsigned biased = (unsigned)(h_maxbits >> 23);
-    const int e = (int)(biased > 1u ? biased : 1u) - 126;
-    if (too_small(e)) return fail(GSDF_ERR_BAD_ARGUMENT, small_text);
-    // 1. every edge's lines, the layers' line ranges, the edges' offsets
-    if (!dev_alloc(w.loop_of, V) || !dev_alloc(w.k_first, V) || !dev_alloc(w.cnt, V) || !dev_alloc(w.edge_off, V + 1) || !dev_alloc(w.blk_cnt, nb) ||
-        !dev_alloc(w.blk_base, nb) || !dev_alloc(w.total, 1) || !dev_alloc(w.acc, L) || !dev_alloc(w.ctr, 1) || !dev_alloc(w.slot_base, (uint64_t)L + 1) ||
-        !dev_alloc(w.layer_kmin, L) || !dev_alloc(w.layer_start, (uint64_t)L + 1))
-      return fail(GSDF_ERR_HIP, nomem);
-    std::vector<HatchLayerAcc> h_acc(L);
+    StreamDrain drain{s};
+    auto interval_ms = [&](int a, int b) { return event_ms(w.ev[a], w.ev[b]); };
+    int e = 0;
+    uint64_t N = 0;
+    std::vector<HatchLayerAcc> h_acc;
     HatchCounters h_ctr{};
-    HIP_TRY(hipEventRecord(w.ev[0], s));
-    HIP_TRY(hipMemsetAsync(w.ctr.p, 0, sizeof(HatchCounters), s));
-    LAUNCH(hatch_init_kernel, blocks_of(L), s, w.acc.p, (unsigned)L);
-    LAUNCH(cloop_of_kernel, nb, s, (const unsigned*)c->loop_start.p, (unsigned)NL, (unsigned)V, w.loop_of.p);
-    LAUNCH(hatch_range_kernel, nb, s, (const float*)c->xy.p, (const unsigned*)c->loop_start.p, (const unsigned*)w.loop_of.p, (const unsigned*)c->loop_layer.p, (unsigned)V, (unsigned)L,
-           P, w.k_first.p, w.cnt.p, w.blk_cnt.p, w.acc.p, w.ctr.p);
-    if (int rc = launch_block_scan(w.blk_cnt.p, nb, w.blk_base.p, w.total.p, s)) return rc;
-    LAUNCH(hatch_scan_kernel, nb, s, (const unsigned*)w.cnt.p, (unsigned)V, (const unsigned*)w.blk_base.p, w.edge_off.p);
-    HIP_TRY(hipEventRecord(w.ev[1], s));
-    HIP_TRY(hipMemcpyAsync(&h_ctr, w.ctr.p, sizeof h_ctr, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(h_acc.data(), w.acc.p, (size_t)L * sizeof(HatchLayerAcc), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    st.ms_device += interval_ms(0, 1);
-    if (h_ctr.bad) return fail(GSDF_ERR_HIP, "hatch: internal error (a loop names a layer the handle does not have)");
-    const uint64_t N = h_ctr.n_crossings;
-    if (N >= ((uint64_t)1 << 32)) return fail(GSDF_ERR_CAPACITY, "hatch: 2^32 crossings or more");
-    // the layers' line slots behind one another
-    std::vector<unsigned> h_slot_base((size_t)L + 1, 0u);
-    std::vector<int> h_kmin(L, 0);
+    if (int rc = hatch_ranges(c, P, s, w, &e, h_acc, &N, &st.ms_device)) return rc;
+    std::vector<unsigned> h_slot_base;
+    std::vector<int> h_kmin;
     uint64_t S = 0;
-    for (uint32_t l = 0; l < L; l++) {
-      h_slot_base[l] = (unsigned)S;
+    if (int rc = hatch_slots(h_acc, h_slot_base, h_kmin, &S)) return rc;
+    for (uint32_t l = 0; l < L; l++)
       if (h_acc[l].k_min <= h_acc[l].k_max) {
-        h_kmin[l] = h_acc[l].k_min;
         h->layers[l].k_min = h_acc[l].k_min;
         h->layers[l].k_max = h_acc[l].k_max;
-        S += (uint64_t)((int64_t)h_acc[l].k_max - (int64_t)h_acc[l].k_min + 1);
       }
-      if (S >= ((uint64_t)1 << 31)) return fail(GSDF_ERR_CAPACITY, "hatch: 2^31 line slots or more");
-    }
-    h_slot_base[L] = (unsigned)S;
     if (N > 0) {
       if ((N & 1) || S == 0) return fail(GSDF_ERR_HIP, "hatch: internal error (an odd number of crossings)");
       const uint64_t NS = N / 2;
@@ -777,6 +825,209 @@ extern "C" int gsdf_hip_contour_hatch(const gsdf_contour* c, const gsdf_hatch_op
   }
   if (st_out) *st_out = st;
   if (!dry) *out = h.release();
+  return GSDF_OK;
+}
+
+// ---- skin classification of the hatch (gsdf_hip.h, "contours: skin classification of the hatch"; kernels_skin.h) --------------------
+namespace {
+struct SkinWs {
+  HatchWs own;  // the hatch's range pass: the exponent, loop_of, the layers' own line ranges
+  DevPtr<int> layer_kmax, k_first, rec_k;
+  DevPtr<unsigned> cnt, pair_off, blk_cnt, blk_base, blk_cnt2, blk_base2;
+  DevPtr<unsigned> line_cnt, own_cnt, line_start, cursor, cross_pair, cross_slot, rec_slot, bnd_off, piece_off, bnd_pos;
+  DevPtr<SkinLayerAcc> acc;
+  DevPtr<SkinCounters> ctr;
+  DevPtr<SkinRec> rec;
+  DevPtr<float> rec_xy, xy_sorted;
+  DevPtr<double> u_sorted;
+  DevPtr<unsigned char> flag;
+  EventSet<8> ev;
+};
+thread_local double g_skin_rank_ms = 0;
+}  // namespace
+extern "C" double gsdf_hip_skin_rank_ms(void) { return g_skin_rank_ms; }
+
+extern "C" int gsdf_hip_contour_hatch_skin(const gsdf_contour* c, const gsdf_hatch_opts* o, const gsdf_skin_opts* k, gsdf_hatch** out, gsdf_skin_stats* st_out) {
+  if (out) *out = nullptr;
+  g_skin_rank_ms = 0;
+  if (!c || !o || !k) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  HatchParams P{};
+  if (int rc = hatch_params(o, out, &P)) return rc;
+  if (k->below > SKIN_MAX_WINDOW || k->above > SKIN_MAX_WINDOW) return fail(GSDF_ERR_BAD_ARGUMENT, "skin: below and above must be 0 .. 8");
+  SkinParams K{};
+  K.below = k->below;
+  K.above = k->above;
+  K.n_src = 1u + k->below + k->above;
+  K.need_below = ((1u << k->below) - 1u) << 1;
+  K.need_above = ((1u << k->above) - 1u) << (1u + k->below);
+  const bool dry = o->dry != 0;
+  const uint64_t V = c->n_verts, NL = c->n_loops;
+  const uint32_t L = c->st.n_layers;
+  gsdf_skin_stats st{};
+  st.n_layers = L;
+  st.below = k->below;
+  st.above = k->above;
+  HatchPtr h(new (std::nothrow) gsdf_hatch());
+  if (!h) return fail(GSDF_ERR_BAD_ARGUMENT, "out of memory");
+  h->device = c->device;
+  h->n_layers = L;
+  h->layer_start.assign((size_t)L + 1, 0u);
+  h->layers.assign(L, gsdf_hatch_layer{0.0, 0, 0, -1});
+  h->has_classes = true;
+  h->skin_layers.assign(L, gsdf_skin_layer{});
+
+  HIP_TRY(hipSetDevice(c->device));
+  if (V == 0 || NL == 0) {
+    if (hatch_too_small(P, -125)) return fail(GSDF_ERR_BAD_ARGUMENT, kHatchSmallText);
+  } else {
+    Stream stream;  // (ahead of the workspace: the work on it is over before the buffers go, and it goes last)
+    HIP_TRY(stream.ensure());
+    hipStream_t s = stream.s;
+    SkinWs w;
+    const char* nomem = "skin: no device memory for the workspace";
+    if (!dev_alloc(w.own.maxbits, 1)) return fail(GSDF_ERR_HIP, nomem);
+    if (w.own.ev.ensure() != hipSuccess || w.ev.ensure() != hipSuccess) return fail(GSDF_ERR_HIP, "hipEventCreate failed");
+    StreamDrain drain{s};
+    auto interval_ms = [&](int a, int b) { return event_ms(w.ev[a], w.ev[b]); };
+    // 0, 1. the exponent and the layers' own line ranges: the hatch's range pass
+    int e = 0;
+    uint64_t n_own = 0, S = 0;
+    std::vector<HatchLayerAcc> own_acc;
+    if (int rc = hatch_ranges(c, P, s, w.own, &e, own_acc, &n_own, &st.ms_device)) return rc;
+    std::vector<unsigned> h_slot_base;
+    std::vector<int> h_kmin, h_kmax(L, -1);
+    if (int rc = hatch_slots(own_acc, h_slot_base, h_kmin, &S)) return rc;
+    for (uint32_t l = 0; l < L; l++)
+      if (own_acc[l].k_min <= own_acc[l].k_max) h_kmax[l] = own_acc[l].k_max;
+    const uint64_t n_pairs = V * K.n_src;
+    if (n_pairs >= ((uint64_t)1 << 32)) return fail(GSDF_ERR_CAPACITY, "skin: 2^32 (edge, source layer) pairs or more");
+    if (n_own > 0) {
+      if ((n_own & 1) || S == 0) return fail(GSDF_ERR_HIP, "skin: internal error (an odd number of crossings)");
+      // 2. every (edge, source number)'s lines inside the target's own range, their offsets
+      const unsigned nb_p = blocks_of(n_pairs), nb_s = blocks_of(S);
+      if (!dev_alloc(w.layer_kmax, L) || !dev_alloc(w.k_first, n_pairs) || !dev_alloc(w.cnt, n_pairs) || !dev_alloc(w.pair_off, n_pairs + 1) || !dev_alloc(w.blk_cnt, nb_p) ||
+          !dev_alloc(w.blk_base, nb_p) || !dev_alloc(w.acc, L) || !dev_alloc(w.ctr, 1))
+        return fail(GSDF_ERR_HIP, nomem);
+      SkinCounters h_ctr{};
+      HIP_TRY(hipMemcpyAsync(w.own.slot_base.p, h_slot_base.data(), ((size_t)L + 1) * 4, hipMemcpyHostToDevice, s));
+      HIP_TRY(hipMemcpyAsync(w.own.layer_kmin.p, h_kmin.data(), (size_t)L * 4, hipMemcpyHostToDevice, s));
+      HIP_TRY(hipMemcpyAsync(w.layer_kmax.p, h_kmax.data(), (size_t)L * 4, hipMemcpyHostToDevice, s));
+      HIP_TRY(hipEventRecord(w.ev[0], s));
+      HIP_TRY(hipMemsetAsync(w.ctr.p, 0, sizeof(SkinCounters), s));
+      LAUNCH(skin_init_kernel, blocks_of(L), s, w.acc.p, (unsigned)L);
+      LAUNCH(skin_range_kernel, nb_p, s, (const float*)c->xy.p, (const unsigned*)c->loop_start.p, (const unsigned*)w.own.loop_of.p, (const unsigned*)c->loop_layer.p, (unsigned)V,
+             (unsigned)L, P, K, (const int*)w.own.layer_kmin.p, (const int*)w.layer_kmax.p, w.k_first.p, w.cnt.p, w.blk_cnt.p, w.ctr.p);
+      if (int rc = launch_block_scan(w.blk_cnt.p, nb_p, w.blk_base.p, w.own.total.p, s)) return rc;
+      LAUNCH(hatch_scan_kernel, nb_p, s, (const unsigned*)w.cnt.p, (unsigned)n_pairs, (const unsigned*)w.blk_base.p, w.pair_off.p);
+      HIP_TRY(hipEventRecord(w.ev[1], s));
+      HIP_TRY(hipMemcpyAsync(&h_ctr, w.ctr.p, sizeof h_ctr, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+      st.ms_device += interval_ms(0, 1);
+      if (h_ctr.bad) return fail(GSDF_ERR_HIP, "skin: internal error (a loop names a layer the handle does not have)");
+      const uint64_t N = h_ctr.n_cand;
+      if (N >= ((uint64_t)1 << 32)) return fail(GSDF_ERR_CAPACITY, "skin: 2^32 crossings or more");
+      if (N < n_own) return fail(GSDF_ERR_HIP, "skin: internal error (fewer crossings than the layers' own)");
+      // 3. crossings per line slot (slots without an own crossing emptied), the buckets' starts; 4. records into their buckets
+      const unsigned nb_x = blocks_of(N);
+      if (!dev_alloc(w.line_cnt, S) || !dev_alloc(w.own_cnt, S) || !dev_alloc(w.line_start, S + 1) || !dev_alloc(w.cursor, S) || !dev_alloc(w.cross_pair, N) ||
+          !dev_alloc(w.cross_slot, N) || !dev_alloc(w.blk_cnt, nb_s > nb_x ? nb_s : nb_x) || !dev_alloc(w.blk_base, nb_s > nb_x ? nb_s : nb_x) || !dev_alloc(w.blk_cnt2, nb_x) ||
+          !dev_alloc(w.blk_base2, nb_x) || !dev_alloc(w.rec, N) || !dev_alloc(w.rec_xy, 2 * N) || !dev_alloc(w.rec_slot, N) || !dev_alloc(w.rec_k, N) ||
+          !dev_alloc(w.u_sorted, N) || !dev_alloc(w.xy_sorted, 2 * N) || !dev_alloc(w.flag, N) || !dev_alloc(w.bnd_off, N) || !dev_alloc(w.piece_off, N + 1) ||
+          !dev_alloc(w.bnd_pos, N))
+        return fail(GSDF_ERR_HIP, nomem);
+      HIP_TRY(hipEventRecord(w.ev[2], s));
+      HIP_TRY(hipMemsetAsync(w.line_cnt.p, 0, (size_t)S * 4, s));
+      HIP_TRY(hipMemsetAsync(w.own_cnt.p, 0, (size_t)S * 4, s));
+      HIP_TRY(hipMemsetAsync(w.cursor.p, 0, (size_t)S * 4, s));
+      HIP_TRY(hipMemsetAsync(w.rec_slot.p, 0xff, (size_t)N * 4, s));
+      HIP_TRY(hipMemsetAsync(w.flag.p, 0, (size_t)N, s));
+      HIP_TRY(hipMemsetAsync(w.piece_off.p, 0, ((size_t)N + 1) * 4, s));
+      LAUNCH(skin_count_kernel, nb_x, s, (const unsigned*)w.pair_off.p, (unsigned)n_pairs, (unsigned)V, (const int*)w.k_first.p, (const unsigned*)w.own.loop_of.p,
+             (const unsigned*)c->loop_layer.p, K, (const unsigned*)w.own.slot_base.p, (const int*)w.own.layer_kmin.p, (unsigned)L, (unsigned)S, (unsigned)N, w.cross_pair.p,
+             w.cross_slot.p, w.line_cnt.p, w.own_cnt.p, w.ctr.p);
+      LAUNCH(skin_lines_kernel, nb_s, s, w.line_cnt.p, (const unsigned*)w.own_cnt.p, (unsigned)S, w.blk_cnt.p, w.ctr.p);
+      if (int rc = launch_block_scan(w.blk_cnt.p, nb_s, w.blk_base.p, w.own.total.p, s)) return rc;
+      LAUNCH(hatch_scan_kernel, nb_s, s, (const unsigned*)w.line_cnt.p, (unsigned)S, (const unsigned*)w.blk_base.p, w.line_start.p);
+      LAUNCH(skin_emit_kernel, nb_x, s, (const float*)c->xy.p, (const unsigned*)c->loop_start.p, (const unsigned*)w.own.loop_of.p, (const unsigned*)c->loop_layer.p, P, K,
+             (unsigned)V, (unsigned)L, (const unsigned*)w.pair_off.p, (const int*)w.k_first.p, (const unsigned*)w.cross_pair.p, (const unsigned*)w.cross_slot.p,
+             (const unsigned*)w.line_start.p, (unsigned)S, (unsigned)N, w.cursor.p, w.rec.p, w.rec_xy.p, w.rec_slot.p, w.rec_k.p, w.ctr.p);
+      // 5. each record to its rank, the sources' parity around it; 6. boundaries and pieces numbered
+      HIP_TRY(hipEventRecord(w.ev[3], s));
+      LAUNCH(skin_rank_kernel, nb_x, s, (const SkinRec*)w.rec.p, (const float*)w.rec_xy.p, (const unsigned*)w.rec_slot.p, (const unsigned*)w.line_start.p, (unsigned)S, (unsigned)N, K,
+             w.u_sorted.p, w.xy_sorted.p, w.flag.p, w.ctr.p);
+      HIP_TRY(hipEventRecord(w.ev[4], s));
+      LAUNCH(skin_flags_kernel, nb_x, s, (const unsigned char*)w.flag.p, (const unsigned*)w.line_start.p, (unsigned)S, (unsigned)N, w.blk_cnt.p, w.blk_cnt2.p, w.ctr.p);
+      if (int rc = launch_block_scan(w.blk_cnt.p, nb_x, w.blk_base.p, w.own.total.p, s)) return rc;
+      if (int rc = launch_block_scan(w.blk_cnt2.p, nb_x, w.blk_base2.p, w.own.total.p, s)) return rc;
+      LAUNCH(skin_compact_kernel, nb_x, s, (const unsigned char*)w.flag.p, (const unsigned*)w.line_start.p, (unsigned)S, (unsigned)N, (const unsigned*)w.blk_base.p,
+             (const unsigned*)w.blk_base2.p, w.bnd_off.p, w.piece_off.p, w.bnd_pos.p, w.ctr.p);
+      LAUNCH(skin_layer_start_kernel, blocks_of((uint64_t)L + 1), s, (const unsigned*)w.line_start.p, (const unsigned*)w.own.slot_base.p, (const unsigned*)w.piece_off.p, (unsigned)L,
+             (unsigned)S, (unsigned)N, w.own.layer_start.p);
+      HIP_TRY(hipEventRecord(w.ev[5], s));
+      HIP_TRY(hipMemcpyAsync(&h_ctr, w.ctr.p, sizeof h_ctr, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(h->layer_start.data(), w.own.layer_start.p, ((size_t)L + 1) * 4, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+      st.ms_device += interval_ms(2, 3) + interval_ms(3, 4) + interval_ms(4, 5);
+      g_skin_rank_ms = interval_ms(3, 4);
+      const uint64_t NB = h_ctr.n_bnd, NS = h_ctr.n_pieces;
+      if (h_ctr.bad || h_ctr.n_own != n_own || NB > N || NS > NB || h->layer_start[L] != NS)
+        return fail(GSDF_ERR_HIP, "skin: internal error (a line with an odd number of crossings, or a record out of range)");
+      // 7. the pieces: end points, classes, lengths by (layer, class)
+      if (!dev_alloc(h->seg, 4 * NS) || !dev_alloc(h->line, NS) || !dev_alloc(h->cls, NS)) return fail(GSDF_ERR_HIP, "skin: no device memory for the result");
+      std::vector<SkinLayerAcc> h_acc(L);
+      HIP_TRY(hipEventRecord(w.ev[6], s));
+      LAUNCH(skin_piece_kernel, nb_x, s, (const unsigned char*)w.flag.p, (const double*)w.u_sorted.p, (const unsigned*)w.xy_sorted.p, (const unsigned*)w.rec_slot.p, (const int*)w.rec_k.p,
+             (const unsigned*)w.line_start.p, (const unsigned*)w.own.slot_base.p, (unsigned)L, (unsigned)S, (unsigned)N, (const unsigned*)w.bnd_off.p, (const unsigned*)w.piece_off.p,
+             (const unsigned*)w.bnd_pos.p, (unsigned)NB, (unsigned)NS, (const unsigned long long*)w.own.maxbits.p, (unsigned*)h->seg.p, h->line.p, h->cls.p, w.acc.p, w.ctr.p);
+      HIP_TRY(hipEventRecord(w.ev[7], s));
+      HIP_TRY(hipMemcpyAsync(&h_ctr, w.ctr.p, sizeof h_ctr, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(h_acc.data(), w.acc.p, (size_t)L * sizeof(SkinLayerAcc), hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+      st.ms_device += interval_ms(6, 7);
+      if (h_ctr.bad) return fail(GSDF_ERR_HIP, "skin: internal error (a line that does not end outside, or a piece out of range)");
+      h->n_segments = NS;
+      st.n_segments = NS;
+      st.n_crossings = h_ctr.n_crossings;
+      st.n_own_crossings = h_ctr.n_own;
+      st.n_lines = h_ctr.n_lines;
+      st.max_line_crossings = h_ctr.max_line;
+      st.zero_length = h_ctr.zero_length;
+      // integers -> float64 with one rounding each, times the inverse power of two (exact)
+      __int128 all[4] = {0, 0, 0, 0};
+      for (uint32_t l = 0; l < L; l++) {
+        __int128 layer_sum = 0;
+        uint64_t layer_n = 0;
+        for (int q = 0; q < 4; q++) {
+          const __int128 sum = (__int128)(long long)h_acc[l].sum[q][1] * ((__int128)1 << 32) + (__int128)h_acc[l].sum[q][0];
+          all[q] += sum;
+          layer_sum += sum;
+          layer_n += h_acc[l].n[q];
+          st.n_class[q] += h_acc[l].n[q];
+          h->skin_layers[l].length[q] = std::ldexp((double)sum, e - 58);
+          h->skin_layers[l].n_segments[q] = h_acc[l].n[q];
+        }
+        if (layer_n != (uint64_t)h->layer_start[l + 1] - h->layer_start[l]) return fail(GSDF_ERR_HIP, "skin: internal error (a layer's pieces and its classes' counts differ)");
+        h->layers[l].length = std::ldexp((double)layer_sum, e - 58);
+        h->layers[l].n_segments = layer_n;
+        if (h_acc[l].k_min <= h_acc[l].k_max) {
+          h->layers[l].k_min = h_acc[l].k_min;
+          h->layers[l].k_max = h_acc[l].k_max;
+        }
+      }
+      for (int q = 0; q < 4; q++) st.length[q] = std::ldexp((double)all[q], e - 58);
+    }
+  }
+  if (st_out) *st_out = st;
+  if (!dry) *out = h.release();
+  return GSDF_OK;
+}
+
+extern "C" int gsdf_hip_hatch_read_skin(const gsdf_hatch* h, uint8_t* cls, gsdf_skin_layer* layers) {
+  if (!h) return fail(GSDF_ERR_BAD_ARGUMENT, "null hatch");
+  if (!h->has_classes) return fail(GSDF_ERR_BAD_ARGUMENT, "this handle has no classes (it was made by gsdf_hip_contour_hatch)");
+  HIP_TRY(hipSetDevice(h->device));
+  if (cls && h->n_segments) HIP_TRY(hipMemcpy(cls, h->cls.p, (size_t)h->n_segments, hipMemcpyDeviceToHost));
+  if (layers && h->n_layers) std::memcpy(layers, h->skin_layers.data(), (size_t)h->n_layers * sizeof(gsdf_skin_layer));
   return GSDF_OK;
 }
 

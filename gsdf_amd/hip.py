@@ -34,7 +34,8 @@ SYMBOLS = ["gsdf_hip_last_error", "gsdf_hip_init", "gsdf_hip_program_create", "g
            "gsdf_hip_contour2", "gsdf_hip_slice3", "gsdf_hip_contour_counts", "gsdf_hip_contour_read", "gsdf_hip_contour_stats_get", "gsdf_hip_contour_destroy",
            "gsdf_hip_contour_create", "gsdf_hip_contour_simplify", "gsdf_hip_contour_measures", "gsdf_hip_contour_measures_ms",
            "gsdf_hip_indexed_mass", "gsdf_hip_indexed_mass_ms", "gsdf_hip_inertia_principal", "gsdf_hip_contour_sections", "gsdf_hip_contour_sections_ms",
-           "gsdf_hip_contour_hatch", "gsdf_hip_hatch_counts", "gsdf_hip_hatch_read", "gsdf_hip_hatch_rank_ms", "gsdf_hip_hatch_destroy"]
+           "gsdf_hip_contour_hatch", "gsdf_hip_hatch_counts", "gsdf_hip_hatch_read", "gsdf_hip_hatch_rank_ms", "gsdf_hip_hatch_destroy",
+           "gsdf_hip_contour_hatch_skin", "gsdf_hip_hatch_read_skin", "gsdf_hip_skin_rank_ms"]
 
 
 PRUNE_ASSUME_SDF = 1 << 30  # gsdf_hip.h: GSDF_PRUNE_ASSUME_SDF
@@ -288,6 +289,32 @@ class HatchStats(C.Structure):
 HATCH_LAYER_DTYPE = np.dtype([("length", "<f8"), ("n_segments", "<u8"), ("k_min", "<i4"), ("k_max", "<i4")])
 
 
+class SkinOpts(C.Structure):
+    """gsdf_skin_opts (gsdf_hip.h, "contours: skin classification of the hatch"): the layers under and over a layer that must cover it."""
+    _fields_ = [("below", C.c_uint32), ("above", C.c_uint32)]
+
+
+class SkinLayer(C.Structure):
+    """gsdf_skin_layer (gsdf_hip.h): a layer's hatch length and pieces by class (0 inner, 1 bottom, 2 top, 3 both)."""
+    _fields_ = [("length", C.c_double * 4), ("n_segments", C.c_uint64 * 4)]
+
+
+class SkinStats(C.Structure):
+    """gsdf_skin_stats (gsdf_hip.h): what a classified hatch produced; bytes 0 .. 127 (RESULT_BYTES) are a function of the loops and
+    the options alone, ms_device says what the run cost."""
+    _fields_ = [("n_segments", C.c_uint64), ("n_crossings", C.c_uint64), ("n_own_crossings", C.c_uint64), ("n_lines", C.c_uint64),
+                ("max_line_crossings", C.c_uint64), ("zero_length", C.c_uint64), ("n_class", C.c_uint64 * 4), ("length", C.c_double * 4),
+                ("n_layers", C.c_uint32), ("below", C.c_uint32), ("above", C.c_uint32), ("reserved", C.c_uint32), ("ms_device", C.c_double)]
+    RESULT_BYTES = 128
+
+    def result_bytes(self):
+        return bytes(self)[:self.RESULT_BYTES]
+
+
+SKIN_LAYER_DTYPE = np.dtype([("length", "<f8", (4,)), ("n_segments", "<u8", (4,))])
+SKIN_CLASSES = ("inner", "bottom", "top", "both")
+
+
 # the same two as numpy records (arrays of shells, of loops, of layers)
 MASS_DTYPE = np.dtype([("volume", "<f8"), ("first", "<f8", (3,)), ("second", "<f8", (6,)), ("centroid", "<f8", (3,)), ("inertia", "<f8", (6,)),
                        ("exponent", "<i4"), ("label", "<u4")])
@@ -453,6 +480,10 @@ def lib():
         L.gsdf_hip_hatch_rank_ms.restype = C.c_double
         L.gsdf_hip_hatch_destroy.argtypes = [C.c_void_p]
         L.gsdf_hip_hatch_destroy.restype = None
+        L.gsdf_hip_contour_hatch_skin.argtypes = [C.c_void_p, C.POINTER(HatchOpts), C.POINTER(SkinOpts), C.POINTER(C.c_void_p), C.POINTER(SkinStats)]
+        L.gsdf_hip_hatch_read_skin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.gsdf_hip_skin_rank_ms.argtypes = []
+        L.gsdf_hip_skin_rank_ms.restype = C.c_double
         L.gsdf_hip_brick_owner.restype = C.c_uint32
         L.gsdf_hip_brick_owner.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         L.gsdf_hip_slab_range.restype = None
@@ -1355,13 +1386,18 @@ class ContourHIP:
         """Device milliseconds (HIP events) of this thread's last sections()."""
         return float(lib().gsdf_hip_contour_sections_ms())
 
-    def hatch_dirs(self, spacing, dirs, offset=0.0, dry=False):
-        """gsdf_hip_contour_hatch with raw float32 directions (1 .. 4 pairs (dx, dy); layer l takes dirs[l % len(dirs)]): a HatchHIP;
-        dry: (None, HatchStats)."""
+    @staticmethod
+    def _hatch_opts(spacing, dirs, offset, dry):
         dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 2)
         o = HatchOpts(np.float32(spacing), np.float32(offset), len(dirs), int(bool(dry)))
         for k, (dx, dy) in enumerate(dirs[:4]):
             o.dir[k][0], o.dir[k][1] = float(dx), float(dy)
+        return o
+
+    def hatch_dirs(self, spacing, dirs, offset=0.0, dry=False):
+        """gsdf_hip_contour_hatch with raw float32 directions (1 .. 4 pairs (dx, dy); layer l takes dirs[l % len(dirs)]): a HatchHIP;
+        dry: (None, HatchStats)."""
+        o = self._hatch_opts(spacing, dirs, offset, dry)
         st, h = HatchStats(), C.c_void_p()
         _check(lib().gsdf_hip_contour_hatch(self._h, C.byref(o), None if dry else C.byref(h), C.byref(st)))
         return (None, st) if dry else HatchHIP(h, st)
@@ -1378,6 +1414,26 @@ class ContourHIP:
         """Device milliseconds (HIP events) of the rank pass of this thread's last hatch."""
         return float(lib().gsdf_hip_hatch_rank_ms())
 
+    def skin_dirs(self, spacing, dirs, below, above, offset=0.0, dry=False):
+        """gsdf_hip_contour_hatch_skin with raw float32 directions: the hatch of hatch_dirs cut against the loops of the `below` layers
+        under and the `above` layers over each layer, a HatchHIP whose cls gives every piece's class (0 inner, 1 bottom, 2 top, 3 both)
+        and whose skin_layers the layers' lengths by class; dry: (None, SkinStats)."""
+        o = self._hatch_opts(spacing, dirs, offset, dry)
+        k = SkinOpts(int(below), int(above))
+        st, h = SkinStats(), C.c_void_p()
+        _check(lib().gsdf_hip_contour_hatch_skin(self._h, C.byref(o), C.byref(k), None if dry else C.byref(h), C.byref(st)))
+        return (None, st) if dry else HatchHIP(h, st, skin=True)
+
+    def skin(self, spacing, angles_deg, below, above, offset=0.0, dry=False):
+        """skin_dirs with the directions float32(cos), float32(sin) of angles_deg, as hatch() makes them."""
+        a = np.radians(np.asarray(angles_deg, np.float64).reshape(-1))
+        return self.skin_dirs(spacing, np.stack([np.cos(a), np.sin(a)], axis=1).astype(np.float32), below, above, offset, dry)
+
+    @staticmethod
+    def skin_rank_ms():
+        """Device milliseconds (HIP events) of the rank and parity pass of this thread's last skin()."""
+        return float(lib().gsdf_hip_skin_rank_ms())
+
     def loops(self, layer=None):
         """The loops (of one layer, or of all) as (n, 2) float32 arrays, in the handle's order."""
         return [self.xy[self.loop_start[q]:self.loop_start[q + 1]] for q in range(self.n_loops) if layer is None or self.loop_layer[q] == layer]
@@ -1389,9 +1445,11 @@ class ContourHIP:
 
 class HatchHIP:
     """The hatch segments of a ContourHIP (gsdf_hatch): seg (n, 4) float32 (x0 y0 x1 y1), line n int32 (the line number k of each),
-    layer_start n_layers + 1, layers (HATCH_LAYER_DTYPE records), stats (HatchStats). Independent of the loops it was made from."""
+    layer_start n_layers + 1, layers (HATCH_LAYER_DTYPE records), stats (HatchStats). Independent of the loops it was made from.
+    Made by ContourHIP.skin: also cls n uint8 (every segment's class) and skin_layers (SKIN_LAYER_DTYPE records), stats a SkinStats;
+    both are None for a plain hatch."""
 
-    def __init__(self, handle, stats):
+    def __init__(self, handle, stats, skin=False):
         self._h = handle
         self.stats = stats
         nl, ns = C.c_uint32(), C.c_uint64()
@@ -1402,6 +1460,11 @@ class HatchHIP:
         self.layer_start = np.empty(self.n_layers + 1, np.uint32)
         self.layers = np.zeros(self.n_layers, HATCH_LAYER_DTYPE)
         _check(lib().gsdf_hip_hatch_read(handle, self.seg.ctypes.data, self.line.ctypes.data, self.layer_start.ctypes.data, self.layers.ctypes.data))
+        self.cls = self.skin_layers = None
+        if skin:
+            self.cls = np.empty(self.n_segments, np.uint8)
+            self.skin_layers = np.zeros(self.n_layers, SKIN_LAYER_DTYPE)
+            _check(lib().gsdf_hip_hatch_read_skin(handle, self.cls.ctypes.data, self.skin_layers.ctypes.data))
 
     def close(self):
         if getattr(self, "_h", None):

@@ -1,5 +1,5 @@
 """SVG outlines with the standard library only (struct, re): the loops of a ContourHIP as one even-odd <path> per layer, their hatch
-segments (a HatchHIP's) as <line> elements in a group of their own, and the loops' reader. Coordinates are written as the shortest decimal that reads back as the same float32, so write followed by read is bit-exact;
+segments (a HatchHIP's) as <line> elements in a group of their own (a skin hatch's in one stroke per class), and the readers. Coordinates are written as the shortest decimal that reads back as the same float32, so write followed by read is bit-exact;
 the y axis points up in the part and down in SVG, and is turned by one transform around the paths, not by changing coordinates."""
 import re
 import struct
@@ -23,11 +23,16 @@ def fmt(v):
     raise AssertionError("nine digits always identify a float32")
 
 
-def write_svg(path, layers, z=None, stroke_width=None, hatch=None):
+SKIN_STROKES = ("#a04020", "#2060c0", "#20a040", "#a020a0")  # by class: inner (the plain hatch's stroke), bottom, top, both
+
+
+def write_svg(path, layers, z=None, stroke_width=None, hatch=None, hatch_class=None):
     """layers: a list (one entry per layer) of lists of loops, each loop (n, 2) float32 in order of travel. One
     <path fill-rule="evenodd"> per layer (an empty layer: an empty path), each loop `M x y L x y ... Z`. z (optional): the layers'
     heights, kept as data-z. hatch (optional): per layer an (n, 4) float32 array of segments x0 y0 x1 y1 (HatchHIP.segments(k)),
-    drawn as <line> elements in one <g id="hatchK"> per layer after the paths: never as <path>, which read_svg takes for a layer."""
+    drawn as <line> elements in one <g id="hatchK"> per layer after the paths: never as <path>, which read_svg takes for a layer.
+    hatch_class (optional, with hatch): per layer the n classes 0 .. 3 of its segments (HatchHIP.cls of a skin hatch); every line
+    then carries data-class and its class's stroke (SKIN_STROKES). Without it the file is what it was before classes existed."""
     lo, hi = [None, None], [None, None]
     for loops in layers:
         for l in loops:
@@ -59,8 +64,13 @@ def write_svg(path, layers, z=None, stroke_width=None, hatch=None):
         out.append('<g id="hatch" fill="none" stroke="#a04020" stroke-width="%.9g">\n' % (0.5 * sw))
         for k, segs in enumerate(hatch):
             out.append('<g id="hatch%d">\n' % k)
-            for x0, y0, x1, y1 in np.asarray(segs, np.float32).reshape(-1, 4):
-                out.append('<line x1="%s" y1="%s" x2="%s" y2="%s"/>\n' % (fmt(x0), fmt(y0), fmt(x1), fmt(y1)))
+            segs = np.asarray(segs, np.float32).reshape(-1, 4)
+            cls = None if hatch_class is None else np.asarray(hatch_class[k], np.uint8).reshape(-1)
+            if cls is not None and (len(cls) != len(segs) or (cls > 3).any()):
+                raise ValueError("hatch_class must give every segment of a layer a class 0 .. 3")
+            for i, (x0, y0, x1, y1) in enumerate(segs):
+                extra = "" if cls is None else ' data-class="%d" stroke="%s"' % (cls[i], SKIN_STROKES[cls[i]])
+                out.append('<line x1="%s" y1="%s" x2="%s" y2="%s"%s/>\n' % (fmt(x0), fmt(y0), fmt(x1), fmt(y1), extra))
             out.append("</g>\n")
         out.append("</g>\n")
     out.append("</g>\n</svg>\n")
@@ -73,14 +83,27 @@ _NUM = r"[-+]?(?:\d+\.?\d*|\.\d+)(?:[eE][-+]?\d+)?"
 _LOOP = re.compile(r"M\s*((?:%s[\s,]*|L\s*)+)Z" % _NUM)
 
 
-_LINE = re.compile(r'<line x1="(%s)" y1="(%s)" x2="(%s)" y2="(%s)"/>' % ((_NUM,) * 4))
+_LINE = re.compile(r'<line x1="(%s)" y1="(%s)" x2="(%s)" y2="(%s)"(?: data-class="([0-3])" stroke="#[0-9a-f]{6}")?/>' % ((_NUM,) * 4))
 
 
 def read_svg_hatch(path):
     """The hatch segments of a file written by write_svg(..., hatch=...): per <g id="hatchK"> an (n, 4) float32 array."""
     text = open(path, encoding="utf-8").read()
-    return [np.array([[float(v) for v in m.groups()] for m in _LINE.finditer(g)], np.float64).astype(np.float32).reshape(-1, 4)
+    return [np.array([[float(v) for v in m.groups()[:4]] for m in _LINE.finditer(g)], np.float64).astype(np.float32).reshape(-1, 4)
             for g in re.findall(r'<g id="hatch\d+">(.*?)</g>', text, flags=re.S)]
+
+
+def read_svg_hatch_class(path):
+    """The classes of the hatch segments of a file written by write_svg(..., hatch_class=...): per <g id="hatchK"> n uint8; a
+    file without classes raises ValueError."""
+    text = open(path, encoding="utf-8").read()
+    out = []
+    for g in re.findall(r'<g id="hatch\d+">(.*?)</g>', text, flags=re.S):
+        cls = [m.group(5) for m in _LINE.finditer(g)]
+        if None in cls:
+            raise ValueError("a hatch segment without a class")
+        out.append(np.array([int(c) for c in cls], np.uint8))
+    return out
 
 
 def read_svg(path):

@@ -1464,7 +1464,8 @@ double gsdf_hip_contour_sections_ms(void);
  *   2^32 crossings or more, or 2^31 line slots (the sum over the layers of k_max - k_min + 1) or more. A handle without loops gives
  *   a handle without segments and no error. Blocking; the result is independent of c afterwards.
  * Out of scope: joining segments into zig-zag paths, travel ordering, concentric or gyroid patterns, dropping short segments,
- *   clipping against anything but the handle's own loops, a segmented sort for lines with thousands of crossings. */
+ *   clipping against anything but the handle's own loops (against the neighbouring layers: the next section), a segmented sort for
+ *   lines with thousands of crossings. */
 typedef struct gsdf_hatch gsdf_hatch; /* segments, resident in HBM */
 typedef struct gsdf_hatch_opts {
   float spacing;   /* > 0, finite */
@@ -1496,6 +1497,80 @@ int gsdf_hip_hatch_counts(const gsdf_hatch* h, uint32_t* n_layers, uint64_t* n_s
 int gsdf_hip_hatch_read(const gsdf_hatch* h, float* seg, int32_t* line, uint32_t* layer_start, gsdf_hatch_layer* layers);
 double gsdf_hip_hatch_rank_ms(void);
 void gsdf_hip_hatch_destroy(gsdf_hatch* h);
+
+/* ---- contours: skin classification of the hatch (no reference counterpart) -----------------------------------------------------------
+ *
+ * What a layer's fill must be depends on its neighbours: where the layer above lacks material the surface is exposed (top skin),
+ * where the layer below lacks it the fill hangs in the air (bottom skin: an overhang or a bridge), the rest may be filled sparsely.
+ * gsdf_hip_contour_hatch_skin hatches every layer as the section above does and cuts each hatch line against the loops of the
+ * `below` layers under and the `above` layers over it: the pieces carry a class, 0 inner, 1 bottom, 2 top, 3 both. On the device, a
+ * function of the handle's arrays and the options alone, to the byte. Kernels: gsdf_amd/csrc/kernels_skin.h (abi_contour.hip); a
+ * numpy restatement: tests/skinref.py. Every operation is one IEEE float64 operation, uncontracted; s, u, c_k, the crossing predicate,
+ * t, u_c, x_c, y_c, the exponent e and the quantisation are the hatch section's, by name.
+ *
+ * Lines and sources. Target layer l of L uses the direction D_l = dir[l % n_dirs] and the hatch's lines c_k. Its sources are numbered
+ *   r: r = 0 is layer l itself, r = i is layer l - i (i = 1 .. below), r = below + i is layer l + i (i = 1 .. above). A source whose
+ *   layer index falls outside 0 .. L-1 is MISSING.
+ * Crossings. Every edge of every present source layer is crossed with the lines of D_l -- s and u of its ends under the TARGET's
+ *   direction, not the source layer's own -- with exactly the hatch's predicate and its formulas for t, u_c, x_c and y_c. A crossing is
+ *   (l, k, r, j), j the global vertex number of the edge's tail.
+ * Lines that count. Only lines (l, k) that carry at least one crossing of source 0 exist; crossings on other lines are counted
+ *   nowhere. Each closed loop crosses a line an even number of times, so every source's count on a line is even.
+ * Values and gaps. The distinct u_c on a line, v_0 < v_1 < ... (compared as doubles, -0 == +0). On the open gap (v_i, v_i+1) source r
+ *   is PRESENT iff the number of its crossings with u_c <= v_i is odd.
+ * Class of a gap. OUTSIDE if source 0 is not present. Otherwise bit 0 (value 1, bottom) is set iff below > 0 and some source
+ *   1 .. below is missing or not present; bit 1 (value 2, top) iff above > 0 and some source below+1 .. below+above is missing or not
+ *   present. Missing layers count as empty: the first `below` layers are bottom skin and the last `above` layers top skin throughout,
+ *   as a slicer's "N solid layers" means.
+ * Pieces. A maximal run of consecutive gaps of one line with the same class, not OUTSIDE, is one segment from the run's first value
+ *   to its last. The float32 end points are the (x_c, y_c) of the first crossing at that value under the order (r, j): a tie between
+ *   layers makes no sliver, and where an own-layer crossing has the value it decides the coordinates. Segments are ordered by (layer,
+ *   k, start value); layer_start and line are the hatch's; cls[i] is 0 .. 3. Nothing is dropped: zero_length counts the pieces whose
+ *   two float32 end points are equal bit for bit. (An own-layer pair of crossings with ONE value encloses no gap and makes no piece,
+ *   where the hatch makes a segment of length 0; on other inputs below = above = 0 gives the hatch's segments.)
+ * Lengths. A piece's term is (end value - start value), quantised with the hatch's scale 2^(58-e) -- u_c under any of the
+ *   directions obeys the hatch's bound, which applies unchanged -- and summed as split integers per (layer, class).
+ *   gsdf_skin_layer: the layer's length and pieces by class. The gsdf_hatch_layer of such a handle is the layer's total: the sum of
+ *   the four class INTEGERS converted once, n_segments summed, k_min and k_max over the pieces (0, -1: none). stats.length[c] is the
+ *   sum of the layers' integers of class c, converted likewise.
+ * Statistics. Bytes 0 .. 127 are a function of the inputs alone. n_own_crossings: the crossings of source 0 (the hatch's
+ *   n_crossings); n_crossings: all crossings on existing lines; n_lines: the existing lines; max_line_crossings: the most crossings,
+ *   of all sources, on one of them. The rank pass compares every crossing of a line with every other one: its cost grows with the
+ *   square of max_line_crossings, that is with about (1 + below + above)^2. ms_device as in the hatch; gsdf_hip_skin_rank_ms: of
+ *   that, the rank and parity pass of the calling thread's last gsdf_hip_contour_hatch_skin.
+ * The result is a gsdf_hatch: gsdf_hip_hatch_counts, _read and _destroy work on it unchanged. gsdf_hip_hatch_read_skin on a handle
+ *   made by gsdf_hip_contour_hatch fails with GSDF_ERR_BAD_ARGUMENT (this handle has no classes). dry as in the hatch.
+ * Errors. The hatch's checks of o, with its codes; a null k, below or above > 8: GSDF_ERR_BAD_ARGUMENT. GSDF_ERR_CAPACITY: 2^32
+ *   crossings or more -- of source 0, or of all sources inside the layers' own line ranges k_min .. k_max (counted before the lines
+ *   without an own crossing are left out) -- 2^32 (edge, source) pairs n_verts (1 + below + above) or more, or 2^31 line slots or more
+ *   (the hatch's sum); all refused from counts, before anything of that size is allocated. A handle without loops gives a handle
+ *   without segments and no error. Blocking; the result is independent of c afterwards.
+ * Out of scope: dropping short pieces, widening skin by an overhang angle, joining pieces into paths, support generation, a
+ *   segmented sort for lines with thousands of crossings. */
+typedef struct gsdf_skin_opts {
+  uint32_t below, above; /* 0 .. 8 each: the layers under and over a layer that must cover it */
+} gsdf_skin_opts;
+GSDF_ABI_ASSERT(sizeof(gsdf_skin_opts) == 8, "gsdf_skin_opts is 8 bytes");
+typedef struct gsdf_skin_layer {
+  double length[4];       /* by class: 0 inner, 1 bottom, 2 top, 3 both */
+  uint64_t n_segments[4];
+} gsdf_skin_layer;
+GSDF_ABI_ASSERT(sizeof(gsdf_skin_layer) == 64, "gsdf_skin_layer is 64 bytes");
+GSDF_ABI_ASSERT(offsetof(gsdf_skin_layer, n_segments) == 32, "gsdf_skin_layer fields");
+typedef struct gsdf_skin_stats {
+  uint64_t n_segments, n_crossings, n_own_crossings, n_lines, max_line_crossings, zero_length;
+  uint64_t n_class[4]; /* pieces by class */
+  double length[4];    /* all layers, by class */
+  uint32_t n_layers, below, above, reserved;
+  double ms_device;    /* last: bytes 0 .. 127 are a function of the inputs alone */
+} gsdf_skin_stats;
+GSDF_ABI_ASSERT(sizeof(gsdf_skin_stats) == 136, "gsdf_skin_stats is 136 bytes");
+GSDF_ABI_ASSERT(offsetof(gsdf_skin_stats, zero_length) == 40 && offsetof(gsdf_skin_stats, n_class) == 48 && offsetof(gsdf_skin_stats, length) == 80, "gsdf_skin_stats sums");
+GSDF_ABI_ASSERT(offsetof(gsdf_skin_stats, n_layers) == 112 && offsetof(gsdf_skin_stats, above) == 120 && offsetof(gsdf_skin_stats, ms_device) == 128, "gsdf_skin_stats fields");
+int gsdf_hip_contour_hatch_skin(const gsdf_contour* c, const gsdf_hatch_opts* o, const gsdf_skin_opts* k, gsdf_hatch** out /* NULL allowed iff o->dry */, gsdf_skin_stats* st /* optional */);
+/* cls n_segments bytes (0 .. 3), layers n_layers records; either may be NULL */
+int gsdf_hip_hatch_read_skin(const gsdf_hatch* h, uint8_t* cls, gsdf_skin_layer* layers);
+double gsdf_hip_skin_rank_ms(void);
 
 /* ---- multi-GPU (one process per GPU). The meshers shard with NO data-path collective (shard_rank / shard_count above); the
  * one exchange is the final variable-length gather of the ranks' results, over xGMI, inside this library: a Go caller needs no
