@@ -8,6 +8,7 @@ slicer wants of a 3-D part at each layer height:
     python examples/render_svg.py text --simplify 0.125 --report -o text.svg   # vertices within res / 8 of a chord dropped on the GPU
     python examples/render_svg.py bolt --layer-height 2 --hatch 4 --report -o bolt.svg   # hatch lines 4 res apart, 45 / 135 degrees by layer
     python examples/render_svg.py bolt --layer-height 2 --hatch 4 --skin 1 1 --report    # the hatch classed as inner, bottom, top skin
+    python examples/render_svg.py bolt --layer-height 2 --walls 3 --wall-width 4 --hatch 4 --report   # three walls 4 res wide, the fill inside them
 
 The lattice spacing is the diagonal of the part's bounds / --resdiv (default 400), or --res. Every layer is one even-odd <path>:
 outer boundaries counter-clockwise, holes clockwise. --report prints loops, vertices, outer and hole counts and the area of every
@@ -22,7 +23,11 @@ hatch length of every layer, the most crossings on one line and the device time.
 line against the loops of the BELOW layers under and the ABOVE layers over its layer (gsdf_hip_contour_hatch_skin, on device) and
 draws the pieces in one stroke per class: inner, bottom skin, top skin, both; the report then gives length x spacing of every class,
 per layer and in total (an estimate of its area), and the layers above the first BELOW that still have bottom skin: the overhangs.
-The SVG is written with the standard library only."""
+--walls N --wall-width W draws N perimeters inside every layer's outline, at the in-plane distances (i + 0.5) W x res (the middle of
+bead i; gsdf_hip_contour_offset, on device, from the loops themselves), as unfilled paths of their own class; --hatch and --skin then
+fill the loops of a second, single-inset offset at N W x res, the inner edge of the wall stack, instead of the raw outline, and the
+report adds the walls' lengths per layer (gsdf_hip_contour_measures on the offset handle) and the device time of the distance field
+and of the tracing. The SVG is written with the standard library only."""
 import argparse
 import importlib.util
 import math
@@ -118,6 +123,21 @@ def skin_report(h, c, spacing, below):
     return "\n".join(lines)
 
 
+def walls_report(walls, n, width, fill):
+    """What --walls made: per layer the length of every wall (measures on the offset handle), then the cost of the two offsets."""
+    _, layers = walls.measures()
+    lines = []
+    for k in range(walls.n_layers // n):
+        each = [float(layers[k * n + i]["length"]) for i in range(n)]
+        lines.append(f"layer {k} walls: length " + " + ".join(f"{v:.9g}" for v in each) + f" = {sum(each):.9g} ({sum(int(layers[k * n + i]['n_loops']) for i in range(n))} loops)")
+    for name, c in (("walls", walls), ("fill boundary", fill)):
+        st = c.offset_stats
+        lines.append(f"{name}: {st.n_insets} inset(s) of width {width:.6g} on a lattice {st.nx} x {st.ny} x {st.n_layers_in} layers, band {st.band:.6g}: {st.n_loops} loops, "
+                     f"{st.n_verts} vertices, {st.inside_nodes} nodes inside, {st.band_nodes} in the band, {st.saddle_cells} saddle cells; device time {st.ms_device:.6g} ms = "
+                     f"distance field {st.ms_field:.6g} + tracing {st.ms_trace:.6g}")
+    return "\n".join(lines)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("scene", choices=SCENES_2D + SCENES_3D)
@@ -132,12 +152,18 @@ def main(argv=None):
     ap.add_argument("--hatch", type=float, default=None, metavar="SPACING", help="fill the layers with parallel lines SPACING x res apart")
     ap.add_argument("--hatch-angle", type=float, nargs="+", default=[45.0, 135.0], metavar="DEG", help="--hatch: the lines' angles, in turn by layer (1 .. 4)")
     ap.add_argument("--skin", type=int, nargs=2, default=None, metavar=("BELOW", "ABOVE"), help="--hatch: class the hatch by the layers under and over (0 .. 8 each)")
+    ap.add_argument("--walls", type=int, default=None, metavar="N", help="N perimeters inside the outline (1 .. 8), the fill inside them")
+    ap.add_argument("--wall-width", type=float, default=None, metavar="W", help="--walls: the width of one wall, W x res")
     ap.add_argument("--report", action="store_true")
     ap.add_argument("--interpreter", action="store_true", help="skip the per-tree kernel build")
     ap.add_argument("-o", "--output", default=None)
     args = ap.parse_args(argv)
     if args.skin is not None and args.hatch is None:
         ap.error("--skin classes the hatch: it goes with --hatch SPACING")
+    if (args.walls is None) != (args.wall_width is None):
+        ap.error("--walls N and --wall-width W go together")
+    if args.walls is not None and not (1 <= args.walls <= 8 and args.wall_width > 0):
+        ap.error("--walls takes 1 .. 8 walls of a positive width")
 
     import numpy as np
     from gsdf_amd import hip, svg
@@ -172,14 +198,19 @@ def main(argv=None):
     elif args.max_verts is not None:
         ap.error("--max-verts goes with --simplify TOL, the tolerance the doubling starts from")
     out = args.output or f"{args.scene}.svg"
-    hatch = hatch_class = None
+    hatch = hatch_class = walls = None
+    fill = c  # the loops the hatch fills: the outline, or with --walls the inner edge of the wall stack
+    if args.walls is not None:
+        wall_width = np.float32(np.float32(args.wall_width) * res)
+        walls = c.offset(res, [np.float32(np.float32(i + 0.5) * wall_width) for i in range(args.walls)])
+        fill = c.offset(res, [np.float32(np.float32(args.walls) * wall_width)])
     if args.hatch is not None:
         hatch_spacing = np.float32(np.float32(args.hatch) * res)
-        hatch = c.hatch(hatch_spacing, args.hatch_angle) if args.skin is None else c.skin(hatch_spacing, args.hatch_angle, *args.skin)
+        hatch = fill.hatch(hatch_spacing, args.hatch_angle) if args.skin is None else fill.skin(hatch_spacing, args.hatch_angle, *args.skin)
         if args.skin is not None:
             hatch_class = [hatch.cls[hatch.layer_start[k]:hatch.layer_start[k + 1]] for k in range(hatch.n_layers)]
     svg.write_svg(out, [c.loops(k) for k in range(c.n_layers)], z=z, hatch=None if hatch is None else [hatch.segments(k) for k in range(hatch.n_layers)],
-                  hatch_class=hatch_class)
+                  hatch_class=hatch_class, walls=None if walls is None else [[walls.loops(k * args.walls + i) for i in range(args.walls)] for k in range(c.n_layers)])
     print(f"{args.scene} res {float(res):.6g}: setup {t1 - t0:.2f} s, contours {(t2 - t1) * 1e3:.1f} ms (the first call includes the kernels' build); "
           f"{c.n_loops} loops, {c.n_verts} vertices in {c.n_layers} layer(s); written to {out}")
     if args.report:
@@ -187,6 +218,8 @@ def main(argv=None):
         if simplified:
             print(simplify_report(traced.n_verts, c, *simplified))
         print(section_report(c))
+        if walls is not None:
+            print(walls_report(walls, args.walls, float(wall_width), fill))
         if hatch is not None:
             print(hatch_report(hatch, c) if args.skin is None else skin_report(hatch, c, float(hatch_spacing), args.skin[0]))
     return 0

@@ -6,7 +6,9 @@
 // gsdf_hip_contour_simplify drops vertices within a tolerance of dyadic chords, gsdf_hip_contour_measures sums areas and lengths,
 // gsdf_hip_contour_sections (kernels_mass.h) first and second moments of area, gsdf_hip_contour_hatch (kernels_hatch.h) the segments
 // of parallel lines inside the loops, as a gsdf_hatch handle of its own, gsdf_hip_contour_hatch_skin (kernels_skin.h) those segments cut
-// against the layers under and over each layer and classed as inner, bottom or top skin.
+// against the layers under and over each layer and classed as inner, bottom or top skin, gsdf_hip_contour_offset /
+// gsdf_hip_contour_distance (kernels_offset.h) the loops moved sideways by in-plane distances: the signed distance of a lattice to the
+// layer's own edges, traced by the tracer's steps 2 .. 5 (trace_chunk below, which gsdf_hip_contour2 / gsdf_hip_slice3 run too).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -24,6 +26,7 @@
 #include "mass_host.h"
 #include "kernels_hatch.h"
 #include "kernels_skin.h"
+#include "kernels_offset.h"
 #include "abi_program.h"
 
 struct gsdf_contour {
@@ -92,6 +95,122 @@ struct Workspace {
   EventSet<7> ev;
 };
 
+// Steps 2 .. 5 of one chunk of Lc whole layers whose distances stand in w.dist (the caller recorded w.ev[0] ahead of its field pass
+// and has just queued it): cells -> succ, vertex numbers, leaders and ranks, the loops -> a Part (none for a chunk without a cut
+// edge; with emit false the counts alone). l0: the chunk's first layer. Adds to st's counts and times; waits for s.
+int trace_chunk(Workspace& w, hipStream_t s, const ContourLattice& lat, uint64_t Lc, uint64_t l0, bool emit, gsdf_contour_stats& st, std::deque<Part>& parts,
+                std::vector<unsigned>& h_base, uint64_t* largest_layer) {
+  const char* nomem = "contour: no device memory for the workspace";
+  const uint64_t N = (uint64_t)lat.nx * lat.ny, E = 2 * N;
+  const uint64_t nodes = Lc * N, slots = Lc * E;
+  const unsigned nb_slots = blocks_of(slots);
+  auto interval_ms = [&](int a, int b) { float t = 0; return hipEventElapsedTime(&t, w.ev[a], w.ev[b]) == hipSuccess ? (double)t : 0.0; };
+  HIP_TRY(hipEventRecord(w.ev[1], s));
+  // 2. cells -> succ over the edge slots; cut edges per block, per layer
+  HIP_TRY(hipMemsetAsync(w.succ.p, 0xff, (size_t)slots * 4, s));
+  LAUNCH(contour_cells_kernel, blocks_of(nodes), s, lat, (const float*)w.dist.p, (unsigned long long)nodes, w.succ.p, w.ctr.p);
+  LAUNCH(contour_count_kernel, nb_slots, s, (const unsigned*)w.succ.p, (unsigned long long)slots, w.blk_cnt.p);
+  if (int rc = launch_block_scan(w.blk_cnt.p, nb_slots, w.blk_base.p, w.totals.p, s)) return rc;
+  LAUNCH(contour_layer_base_kernel, blocks_of(Lc + 1), s, (const unsigned*)w.succ.p, (const unsigned*)w.blk_base.p, (const unsigned long long*)w.totals.p, (unsigned)E,
+         (unsigned)Lc, w.layer_base.p);
+  HIP_TRY(hipEventRecord(w.ev[2], s));
+  HIP_TRY(hipMemcpyAsync(h_base.data(), w.layer_base.p, (size_t)(Lc + 1) * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  st.ms_eval += interval_ms(0, 1);
+  st.ms_trace += interval_ms(1, 2);
+  const uint64_t V = h_base[Lc];
+  uint64_t chunk_largest = 0;
+  for (uint64_t l = 0; l < Lc; l++) chunk_largest = std::max<uint64_t>(chunk_largest, h_base[l + 1] - h_base[l]);
+  *largest_layer = std::max(*largest_layer, chunk_largest);
+  if (V == 0) return GSDF_OK;
+  if (st.n_verts + V >= ((uint64_t)1 << 32)) return fail(GSDF_ERR_CAPACITY, "contour: 2^32 vertices or more");
+  // 3. vertex numbers, links, the leaders by pointer jumping, the ranks by list ranking: rounds for the chunk's largest layer
+  const unsigned nb_v = blocks_of(V);
+  if (w.verts.ensure((size_t)V * 9 * 4) != hipSuccess || w.blk.ensure((size_t)nb_v * 4 * 4) != hipSuccess) return fail(GSDF_ERR_HIP, nomem);
+  unsigned* va = (unsigned*)w.verts.p;
+  unsigned *slot_of = va, *pred = va + V, *mn[2] = {va + 2 * V, va + 3 * V}, *lk[2] = {va + 4 * V, va + 5 * V}, *rk[2] = {va + 6 * V, va + 7 * V}, *start_of = va + 8 * V;
+  unsigned* ba = (unsigned*)w.blk.p;
+  unsigned *blk_loops = ba, *blk_len = ba + nb_v, *base_loops = ba + 2 * (size_t)nb_v, *base_len = ba + 3 * (size_t)nb_v;
+  unsigned* vnum = (unsigned*)w.pos.p;
+  const unsigned rounds = ceil_log2(chunk_largest);
+  HIP_TRY(hipEventRecord(w.ev[3], s));
+  LAUNCH(contour_number_kernel, nb_slots, s, (const unsigned*)w.succ.p, (unsigned long long)slots, (const unsigned*)w.blk_base.p, (unsigned)V, vnum, slot_of, w.ctr.p);
+  LAUNCH(contour_link_kernel, nb_v, s, (const unsigned*)w.succ.p, (unsigned long long)slots, (const unsigned*)vnum, (const unsigned*)slot_of, (unsigned)V, pred, mn[0], lk[0],
+         w.ctr.p);
+  int cur = 0;
+  for (unsigned r = 0; r < rounds; r++, cur ^= 1)
+    LAUNCH(contour_min_kernel, nb_v, s, (const unsigned*)mn[cur], (const unsigned*)lk[cur], (unsigned)V, mn[cur ^ 1], lk[cur ^ 1]);
+  const unsigned* leader = mn[cur];
+  LAUNCH(contour_rank_init_kernel, nb_v, s, leader, (const unsigned*)pred, (unsigned)V, rk[0], lk[0]);
+  int rc_ = 0;
+  for (unsigned r = 0; r < rounds; r++, rc_ ^= 1)
+    LAUNCH(contour_rank_kernel, nb_v, s, (const unsigned*)rk[rc_], (const unsigned*)lk[rc_], (unsigned)V, rk[rc_ ^ 1], lk[rc_ ^ 1]);
+  const unsigned* rank = rk[rc_];
+  // 4. leaders -> loops
+  LAUNCH(contour_leader_count_kernel, nb_v, s, leader, (const unsigned*)pred, rank, (unsigned)V, blk_loops, blk_len);
+  if (int rc = launch_block_scan(blk_loops, nb_v, base_loops, w.totals.p + 1, s)) return rc;
+  if (int rc = launch_block_scan(blk_len, nb_v, base_len, w.totals.p + 2, s)) return rc;
+  HIP_TRY(hipEventRecord(w.ev[4], s));
+  unsigned long long h_tot[3] = {0, 0, 0};
+  ContourCounters h_ctr;
+  HIP_TRY(hipMemcpyAsync(h_tot, w.totals.p, sizeof h_tot, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(&h_ctr, w.ctr.p, sizeof h_ctr, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  st.ms_trace += interval_ms(3, 4);
+  const uint64_t nl = h_tot[1];
+  if (h_ctr.bad || nl == 0 || nl > V || h_tot[2] != V) return fail(GSDF_ERR_HIP, "contour: internal error (succ is not a permutation of the cut edges)");
+  if (emit) {
+    // 5. emit
+    parts.emplace_back();
+    Part& part = parts.back();
+    part.n_verts = V;
+    part.n_loops = nl;
+    if (!dev_alloc(part.xy, 2 * V) || !dev_alloc(part.keys, V) || !dev_alloc(part.loop_start, nl) || !dev_alloc(part.loop_layer, nl)) return fail(GSDF_ERR_HIP, nomem);
+    HIP_TRY(hipEventRecord(w.ev[5], s));
+    LAUNCH(contour_leader_number_kernel, nb_v, s, leader, (const unsigned*)pred, rank, (const unsigned*)slot_of, (unsigned)V, (const unsigned*)base_loops, (const unsigned*)base_len,
+           (unsigned)nl, (unsigned)E, (unsigned)l0, (unsigned)st.n_verts, start_of, part.loop_start.p, part.loop_layer.p, w.ctr.p);
+    LAUNCH(contour_emit_kernel, nb_v, s, lat, (const float*)w.dist.p, (const unsigned*)slot_of, leader, rank, (const unsigned*)start_of, (unsigned)V, (unsigned)E, part.xy.p,
+           part.keys.p, w.ctr.p);
+    HIP_TRY(hipEventRecord(w.ev[6], s));
+    HIP_TRY(hipStreamSynchronize(s));
+    st.ms_trace += interval_ms(5, 6);
+  }
+  st.n_verts += V;
+  st.n_loops += nl;
+  return GSDF_OK;
+}
+
+// Behind the last chunk: the counters of the whole call into st; with a handle, the chunks' loops behind one another in it.
+int trace_finish(Workspace& w, hipStream_t s, gsdf_contour_stats& st, uint64_t largest_layer, const std::deque<Part>& parts, gsdf_contour* c) {
+  ContourCounters h_ctr;
+  HIP_TRY(hipMemcpyAsync(&h_ctr, w.ctr.p, sizeof h_ctr, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (h_ctr.bad) return fail(GSDF_ERR_HIP, "contour: internal error (a vertex out of range)");
+  st.border_inside = h_ctr.border_inside;
+  st.nonfinite_nodes = h_ctr.nonfinite_nodes;
+  st.saddle_cells = h_ctr.saddle_cells;
+  st.rank_rounds = ceil_log2(largest_layer);
+  st.ms_device = st.ms_eval + st.ms_trace;
+  if (!c) return GSDF_OK;
+  c->n_verts = st.n_verts;
+  c->n_loops = st.n_loops;
+  if (!dev_alloc(c->xy, 2 * c->n_verts) || !dev_alloc(c->keys, c->n_verts) || !dev_alloc(c->loop_start, c->n_loops + 1) || !dev_alloc(c->loop_layer, c->n_loops))
+    return fail(GSDF_ERR_HIP, "contour: no device memory for the result");
+  uint64_t v0 = 0, q0 = 0;
+  for (const Part& part : parts) {
+    HIP_TRY(hipMemcpyAsync(c->xy.p + 2 * v0, part.xy.p, (size_t)part.n_verts * 8, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(c->keys.p + v0, part.keys.p, (size_t)part.n_verts * 4, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(c->loop_start.p + q0, part.loop_start.p, (size_t)part.n_loops * 4, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(c->loop_layer.p + q0, part.loop_layer.p, (size_t)part.n_loops * 4, hipMemcpyDeviceToDevice, s));
+    v0 += part.n_verts;
+    q0 += part.n_loops;
+  }
+  const unsigned end = (unsigned)c->n_verts;
+  HIP_TRY(hipMemcpyAsync(c->loop_start.p + c->n_loops, &end, 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return GSDF_OK;
+}
+
 int contour_run(gsdf_program* p, int dim, float res, const float* z, uint32_t n_z, const gsdf_contour_opts* o, gsdf_contour** out) {
   if (!p || !out) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
   *out = nullptr;
@@ -139,115 +258,20 @@ int contour_run(gsdf_program* p, int dim, float res, const float* z, uint32_t n_
   st.n_layers = (uint32_t)L;
   std::vector<unsigned> h_base(per_chunk + 1);
   uint64_t largest_layer = 0;
-  auto interval_ms = [&](int a, int b) { float t = 0; return hipEventElapsedTime(&t, w.ev[a], w.ev[b]) == hipSuccess ? (double)t : 0.0; };
 
   for (uint64_t l0 = 0; l0 < L; l0 += per_chunk) {
     const uint64_t Lc = L - l0 < per_chunk ? L - l0 : per_chunk;
-    const uint64_t nodes = Lc * N, slots = Lc * E;
-    const unsigned nb_slots = blocks_of(slots);
+    const uint64_t nodes = Lc * N;
     // 1. evaluate: positions, then the program's Evaluate over them
     HIP_TRY(hipEventRecord(w.ev[0], s));
     if (dim == 2) LAUNCH(contour_pos_kernel<2>, blocks_of(nodes), s, lat, (const float*)nullptr, (unsigned long long)nodes, w.pos.p);
     else LAUNCH(contour_pos_kernel<3>, blocks_of(nodes), s, lat, (const float*)(w.z.p + l0), (unsigned long long)nodes, w.pos.p);
     if (int rc = dim == 2 ? gsdf_hip_eval2_dev(p, w.pos.p, 8, w.dist.p, (size_t)nodes, (void*)s) : gsdf_hip_eval3_dev(p, w.pos.p, 12, w.dist.p, (size_t)nodes, (void*)s)) return rc;
-    HIP_TRY(hipEventRecord(w.ev[1], s));
-    // 2. cells -> succ over the edge slots; cut edges per block, per layer
-    HIP_TRY(hipMemsetAsync(w.succ.p, 0xff, (size_t)slots * 4, s));
-    LAUNCH(contour_cells_kernel, blocks_of(nodes), s, lat, (const float*)w.dist.p, (unsigned long long)nodes, w.succ.p, w.ctr.p);
-    LAUNCH(contour_count_kernel, nb_slots, s, (const unsigned*)w.succ.p, (unsigned long long)slots, w.blk_cnt.p);
-    if (int rc = launch_block_scan(w.blk_cnt.p, nb_slots, w.blk_base.p, w.totals.p, s)) return rc;
-    LAUNCH(contour_layer_base_kernel, blocks_of(Lc + 1), s, (const unsigned*)w.succ.p, (const unsigned*)w.blk_base.p, (const unsigned long long*)w.totals.p, (unsigned)E,
-           (unsigned)Lc, w.layer_base.p);
-    HIP_TRY(hipEventRecord(w.ev[2], s));
-    HIP_TRY(hipMemcpyAsync(h_base.data(), w.layer_base.p, (size_t)(Lc + 1) * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    st.ms_eval += interval_ms(0, 1);
-    st.ms_trace += interval_ms(1, 2);
-    const uint64_t V = h_base[Lc];
-    uint64_t chunk_largest = 0;
-    for (uint64_t l = 0; l < Lc; l++) chunk_largest = std::max<uint64_t>(chunk_largest, h_base[l + 1] - h_base[l]);
-    largest_layer = std::max(largest_layer, chunk_largest);
-    if (V == 0) continue;
-    if (st.n_verts + V >= ((uint64_t)1 << 32)) return fail(GSDF_ERR_CAPACITY, "contour: 2^32 vertices or more");
-    // 3. vertex numbers, links, the leaders by pointer jumping, the ranks by list ranking: rounds for the chunk's largest layer
-    const unsigned nb_v = blocks_of(V);
-    if (w.verts.ensure((size_t)V * 9 * 4) != hipSuccess || w.blk.ensure((size_t)nb_v * 4 * 4) != hipSuccess) return fail(GSDF_ERR_HIP, nomem);
-    unsigned* va = (unsigned*)w.verts.p;
-    unsigned *slot_of = va, *pred = va + V, *mn[2] = {va + 2 * V, va + 3 * V}, *lk[2] = {va + 4 * V, va + 5 * V}, *rk[2] = {va + 6 * V, va + 7 * V}, *start_of = va + 8 * V;
-    unsigned* ba = (unsigned*)w.blk.p;
-    unsigned *blk_loops = ba, *blk_len = ba + nb_v, *base_loops = ba + 2 * (size_t)nb_v, *base_len = ba + 3 * (size_t)nb_v;
-    unsigned* vnum = (unsigned*)w.pos.p;
-    const unsigned rounds = ceil_log2(chunk_largest);
-    HIP_TRY(hipEventRecord(w.ev[3], s));
-    LAUNCH(contour_number_kernel, nb_slots, s, (const unsigned*)w.succ.p, (unsigned long long)slots, (const unsigned*)w.blk_base.p, (unsigned)V, vnum, slot_of, w.ctr.p);
-    LAUNCH(contour_link_kernel, nb_v, s, (const unsigned*)w.succ.p, (unsigned long long)slots, (const unsigned*)vnum, (const unsigned*)slot_of, (unsigned)V, pred, mn[0], lk[0],
-           w.ctr.p);
-    int cur = 0;
-    for (unsigned r = 0; r < rounds; r++, cur ^= 1)
-      LAUNCH(contour_min_kernel, nb_v, s, (const unsigned*)mn[cur], (const unsigned*)lk[cur], (unsigned)V, mn[cur ^ 1], lk[cur ^ 1]);
-    const unsigned* leader = mn[cur];
-    LAUNCH(contour_rank_init_kernel, nb_v, s, leader, (const unsigned*)pred, (unsigned)V, rk[0], lk[0]);
-    int rc_ = 0;
-    for (unsigned r = 0; r < rounds; r++, rc_ ^= 1)
-      LAUNCH(contour_rank_kernel, nb_v, s, (const unsigned*)rk[rc_], (const unsigned*)lk[rc_], (unsigned)V, rk[rc_ ^ 1], lk[rc_ ^ 1]);
-    const unsigned* rank = rk[rc_];
-    // 4. leaders -> loops
-    LAUNCH(contour_leader_count_kernel, nb_v, s, leader, (const unsigned*)pred, rank, (unsigned)V, blk_loops, blk_len);
-    if (int rc = launch_block_scan(blk_loops, nb_v, base_loops, w.totals.p + 1, s)) return rc;
-    if (int rc = launch_block_scan(blk_len, nb_v, base_len, w.totals.p + 2, s)) return rc;
-    HIP_TRY(hipEventRecord(w.ev[4], s));
-    unsigned long long h_tot[3] = {0, 0, 0};
-    ContourCounters h_ctr;
-    HIP_TRY(hipMemcpyAsync(h_tot, w.totals.p, sizeof h_tot, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(&h_ctr, w.ctr.p, sizeof h_ctr, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    st.ms_trace += interval_ms(3, 4);
-    const uint64_t nl = h_tot[1];
-    if (h_ctr.bad || nl == 0 || nl > V || h_tot[2] != V) return fail(GSDF_ERR_HIP, "contour: internal error (succ is not a permutation of the cut edges)");
-    // 5. emit
-    parts.emplace_back();
-    Part& part = parts.back();
-    part.n_verts = V;
-    part.n_loops = nl;
-    if (!dev_alloc(part.xy, 2 * V) || !dev_alloc(part.keys, V) || !dev_alloc(part.loop_start, nl) || !dev_alloc(part.loop_layer, nl)) return fail(GSDF_ERR_HIP, nomem);
-    HIP_TRY(hipEventRecord(w.ev[5], s));
-    LAUNCH(contour_leader_number_kernel, nb_v, s, leader, (const unsigned*)pred, rank, (const unsigned*)slot_of, (unsigned)V, (const unsigned*)base_loops, (const unsigned*)base_len,
-           (unsigned)nl, (unsigned)E, (unsigned)l0, (unsigned)st.n_verts, start_of, part.loop_start.p, part.loop_layer.p, w.ctr.p);
-    LAUNCH(contour_emit_kernel, nb_v, s, lat, (const float*)w.dist.p, (const unsigned*)slot_of, leader, rank, (const unsigned*)start_of, (unsigned)V, (unsigned)E, part.xy.p,
-           part.keys.p, w.ctr.p);
-    HIP_TRY(hipEventRecord(w.ev[6], s));
-    HIP_TRY(hipStreamSynchronize(s));
-    st.ms_trace += interval_ms(5, 6);
-    st.n_verts += V;
-    st.n_loops += nl;
+    // 2 .. 5. trace
+    if (int rc = trace_chunk(w, s, lat, Lc, l0, true, st, parts, h_base, &largest_layer)) return rc;
   }
-  // the counters of the whole call; the chunks' loops behind one another
-  ContourCounters h_ctr;
-  HIP_TRY(hipMemcpyAsync(&h_ctr, w.ctr.p, sizeof h_ctr, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (h_ctr.bad) return fail(GSDF_ERR_HIP, "contour: internal error (a vertex out of range)");
-  st.border_inside = h_ctr.border_inside;
-  st.nonfinite_nodes = h_ctr.nonfinite_nodes;
-  st.saddle_cells = h_ctr.saddle_cells;
-  st.rank_rounds = ceil_log2(largest_layer);
   st.evals = N * L;
-  st.ms_device = st.ms_eval + st.ms_trace;
-  c->n_verts = st.n_verts;
-  c->n_loops = st.n_loops;
-  if (!dev_alloc(c->xy, 2 * c->n_verts) || !dev_alloc(c->keys, c->n_verts) || !dev_alloc(c->loop_start, c->n_loops + 1) || !dev_alloc(c->loop_layer, c->n_loops))
-    return fail(GSDF_ERR_HIP, "contour: no device memory for the result");
-  uint64_t v0 = 0, q0 = 0;
-  for (const Part& part : parts) {
-    HIP_TRY(hipMemcpyAsync(c->xy.p + 2 * v0, part.xy.p, (size_t)part.n_verts * 8, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemcpyAsync(c->keys.p + v0, part.keys.p, (size_t)part.n_verts * 4, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemcpyAsync(c->loop_start.p + q0, part.loop_start.p, (size_t)part.n_loops * 4, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemcpyAsync(c->loop_layer.p + q0, part.loop_layer.p, (size_t)part.n_loops * 4, hipMemcpyDeviceToDevice, s));
-    v0 += part.n_verts;
-    q0 += part.n_loops;
-  }
-  const unsigned end = (unsigned)c->n_verts;
-  HIP_TRY(hipMemcpyAsync(c->loop_start.p + c->n_loops, &end, 4, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipStreamSynchronize(s));
+  if (int rc = trace_finish(w, s, st, largest_layer, parts, c.get())) return rc;
   *out = c.release();
   return GSDF_OK;
 }
@@ -1045,5 +1069,218 @@ extern "C" int gsdf_hip_hatch_read(const gsdf_hatch* h, float* seg, int32_t* lin
   if (line && h->n_segments) HIP_TRY(hipMemcpy(line, h->line.p, (size_t)h->n_segments * 4, hipMemcpyDeviceToHost));
   if (layer_start) std::memcpy(layer_start, h->layer_start.data(), h->layer_start.size() * 4);
   if (layers && h->n_layers) std::memcpy(layers, h->layers.data(), (size_t)h->n_layers * sizeof(gsdf_hatch_layer));
+  return GSDF_OK;
+}
+
+// ---- offset (gsdf_hip.h, "contours: offset"; kernels_offset.h) ----------------------------------------------------------------------
+namespace {
+struct OffsetWs {
+  DevPtr<unsigned> loop_of, bb, layer_edge;
+  DevPtr<float4> edges;
+  DevPtr<float> D;
+  DevPtr<OffsetCounters> ctr;
+};
+
+// what gsdf_hip_contour_offset and gsdf_hip_contour_distance share: the options' checks, the one lattice of the call, the band
+struct OffsetPlan {
+  ContourLattice lat{};
+  uint64_t N = 0;
+  float band = 0.f;
+  unsigned tiles_x = 0, tiles_y = 0;
+  OffsetInsets insets{};
+};
+
+int offset_check(const gsdf_offset_opts* o) {
+  if (!std::isfinite(o->res) || !(o->res > 0.f)) return fail(GSDF_ERR_BAD_ARGUMENT, "offset: res must be finite and positive");
+  if (o->n_insets == 0 || o->n_insets > OFFSET_MAX_INSETS) return fail(GSDF_ERR_BAD_ARGUMENT, "offset: n_insets must be 1 .. 8");
+  for (uint32_t i = 0; i < o->n_insets; i++)
+    if (!std::isfinite(o->inset[i])) return fail(GSDF_ERR_BAD_ARGUMENT, "offset: inset " + std::to_string(i) + " is not finite");
+  if (o->reserved != 0) return fail(GSDF_ERR_BAD_ARGUMENT, "offset: reserved must be 0");
+  return GSDF_OK;
+}
+
+// The lattice (the handle's exact box grown for the negative insets, then the tracer's rules) and the handle's edges on s: ws.edges in
+// vertex order, ws.layer_edge the first edge of every layer. Waits for s.
+int offset_prepare(const gsdf_contour* c, const gsdf_offset_opts* o, hipStream_t s, OffsetWs& ws, OffsetPlan* plan) {
+  const uint64_t V = c->n_verts, NL = c->n_loops;
+  const uint32_t L = c->st.n_layers;
+  float box[4] = {0.f, 0.f, 0.f, 0.f};  // (a handle without vertices: the origin)
+  if (V > 0) {
+    const unsigned init[4] = {0xffffffffu, 0xffffffffu, 0u, 0u};
+    unsigned h_bb[4];
+    if (!dev_alloc(ws.bb, 4)) return fail(GSDF_ERR_HIP, "offset: no device memory for the workspace");
+    HIP_TRY(hipMemcpyAsync(ws.bb.p, init, sizeof init, hipMemcpyHostToDevice, s));
+    LAUNCH(offset_bbox_kernel, blocks_of(V), s, (const float*)c->xy.p, (unsigned)V, ws.bb.p);
+    HIP_TRY(hipMemcpyAsync(h_bb, ws.bb.p, sizeof h_bb, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int k = 0; k < 4; k++) {
+      const unsigned b = h_bb[k] ^ ((h_bb[k] >> 31) ? 0x80000000u : 0xffffffffu);
+      std::memcpy(&box[k], &b, 4);
+    }
+  }
+  float grow = 0.f, reach = 0.f;
+  for (uint32_t i = 0; i < o->n_insets; i++) {
+    grow = std::max(grow, -o->inset[i]);
+    reach = std::max(reach, std::fabs(o->inset[i]));
+    plan->insets.v[i] = o->inset[i];
+  }
+  const float res = o->res;
+  const float lo_x = box[0] - grow, lo_y = box[1] - grow, hi_x = box[2] + grow, hi_y = box[3] + grow;
+  if (!std::isfinite(lo_x) || !std::isfinite(lo_y) || !std::isfinite(hi_x) || !std::isfinite(hi_y)) return fail(GSDF_ERR_BAD_ARGUMENT, "offset: the grown bounds are not finite");
+  const uint64_t nx = axis_nodes(lo_x, hi_x, res), ny = axis_nodes(lo_y, hi_y, res);
+  if (nx == 0 || ny == 0 || nx * ny >= ((uint64_t)1 << 31)) return fail(GSDF_ERR_BAD_ARGUMENT, "offset: the lattice needs 2^31 nodes or more at this res");
+  if (nx * ny * o->n_insets >= ((uint64_t)1 << 31)) return fail(GSDF_ERR_BAD_ARGUMENT, "offset: the lattices of one layer's insets need 2^31 nodes or more at this res");
+  plan->lat = ContourLattice{(unsigned)nx, (unsigned)ny, lo_x - res, lo_y - res, res};
+  plan->N = nx * ny;
+  const float two_res = 2.f * res;
+  plan->band = reach + two_res;
+  plan->tiles_x = (unsigned)((nx + OFFSET_TILE - 1) / OFFSET_TILE);
+  plan->tiles_y = (unsigned)((ny + OFFSET_TILE - 1) / OFFSET_TILE);
+  // the layers' edges: a layer's loops, and with them its vertices, are contiguous (loop_layer is non-decreasing)
+  std::vector<unsigned> h_start(NL + 1, 0u), h_layer(NL, 0u), h_edge((size_t)L + 1, (unsigned)V);
+  if (!dev_alloc(ws.layer_edge, (uint64_t)L + 1) || !dev_alloc(ws.loop_of, V) || !dev_alloc(ws.edges, V)) return fail(GSDF_ERR_HIP, "offset: no device memory for the workspace");
+  if (V > 0 && NL > 0) {
+    HIP_TRY(hipMemcpyAsync(h_start.data(), c->loop_start.p, (size_t)(NL + 1) * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h_layer.data(), c->loop_layer.p, (size_t)NL * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    uint64_t q = 0;
+    for (uint32_t l = 0; l <= L; l++) {
+      while (q < NL && h_layer[q] < l) q++;
+      h_edge[l] = q < NL ? h_start[q] : (unsigned)V;
+    }
+    h_edge[L] = (unsigned)V;
+    LAUNCH(cloop_of_kernel, blocks_of(V), s, (const unsigned*)c->loop_start.p, (unsigned)NL, (unsigned)V, ws.loop_of.p);
+    LAUNCH(offset_edges_kernel, blocks_of(V), s, (const float*)c->xy.p, (const unsigned*)c->loop_start.p, (const unsigned*)ws.loop_of.p, (unsigned)V, ws.edges.p);
+  }
+  HIP_TRY(hipMemcpyAsync(ws.layer_edge.p, h_edge.data(), ((size_t)L + 1) * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return GSDF_OK;
+}
+
+void offset_stats_of(const OffsetPlan& plan, const gsdf_offset_opts* o, uint32_t n_layers_in, gsdf_offset_stats* st) {
+  st->nx = plan.lat.nx;
+  st->ny = plan.lat.ny;
+  st->n_layers_in = n_layers_in;
+  st->n_insets = o->n_insets;
+  st->x0 = plan.lat.x0;
+  st->y0 = plan.lat.y0;
+  st->band = plan.band;
+  st->res = o->res;
+}
+}  // namespace
+
+extern "C" int gsdf_hip_contour_offset(const gsdf_contour* c, const gsdf_offset_opts* o, gsdf_contour** out, gsdf_offset_stats* st_out) {
+  if (out) *out = nullptr;
+  if (!c || !o) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  if (int rc = offset_check(o)) return rc;
+  const bool dry = o->dry != 0;
+  if (!out && !dry) return fail(GSDF_ERR_BAD_ARGUMENT, "offset: out may be null in a dry run only");
+  const uint64_t L_in = c->st.n_layers, K = o->n_insets, L_out = L_in * K;
+  if (L_out >= ((uint64_t)1 << 32)) return fail(GSDF_ERR_CAPACITY, "offset: 2^32 output layers or more");
+
+  HIP_TRY(hipSetDevice(c->device));
+  Stream stream;  // (ahead of the workspaces: the work on it is over before the buffers go, and it goes last)
+  HIP_TRY(stream.ensure());
+  hipStream_t s = stream.s;
+  std::deque<Part> parts;
+  Workspace w;
+  OffsetWs ws;
+  ContourPtr r(new (std::nothrow) gsdf_contour());
+  if (!r) return fail(GSDF_ERR_BAD_ARGUMENT, "out of memory");
+  r->device = c->device;
+  StreamDrain drain{s};
+  OffsetPlan plan;
+  if (int rc = offset_prepare(c, o, s, ws, &plan)) return rc;
+  const ContourLattice& lat = plan.lat;
+  const uint64_t N = plan.N, tiles = (uint64_t)plan.tiles_x * plan.tiles_y;
+  // input layers per chunk, each with all its insets: max_nodes nodes, at least one, and the chunk's slots below 2^32
+  const uint64_t max_nodes = o->max_nodes ? o->max_nodes : (uint64_t)GSDF_CONTOUR_DEFAULT_MAX_NODES;
+  uint64_t per_chunk = max_nodes / (N * K);
+  if (per_chunk < 1) per_chunk = 1;
+  if (per_chunk > (((uint64_t)1 << 31) - 1) / (N * K)) per_chunk = (((uint64_t)1 << 31) - 1) / (N * K);
+  if (per_chunk > L_in) per_chunk = L_in;
+  const char* nomem = "offset: no device memory for the workspace";
+  const uint64_t chunk_nodes = per_chunk * K * N, chunk_slots = 2 * chunk_nodes;
+  const unsigned slot_blocks = blocks_of(chunk_slots);
+  if (!dev_alloc(w.pos, chunk_slots) || !dev_alloc(w.dist, chunk_nodes) || !dev_alloc(w.succ, chunk_slots) || !dev_alloc(w.blk_cnt, slot_blocks) ||
+      !dev_alloc(w.blk_base, slot_blocks) || !dev_alloc(w.layer_base, per_chunk * K + 1) || !dev_alloc(w.totals, 3) || !dev_alloc(w.ctr, 1) || !dev_alloc(ws.D, per_chunk * N) ||
+      !dev_alloc(ws.ctr, 1))
+    return fail(GSDF_ERR_HIP, nomem);
+  if (w.ev.ensure() != hipSuccess) return fail(GSDF_ERR_HIP, "hipEventCreate failed");
+  HIP_TRY(hipMemsetAsync(w.ctr.p, 0, sizeof(ContourCounters), s));
+  HIP_TRY(hipMemsetAsync(ws.ctr.p, 0, sizeof(OffsetCounters), s));
+
+  gsdf_contour_stats& st = r->st;
+  st.nx = lat.nx;
+  st.ny = lat.ny;
+  st.n_layers = (uint32_t)L_out;
+  std::vector<unsigned> h_base(per_chunk * K + 1);
+  uint64_t largest_layer = 0;
+  for (uint64_t l0 = 0; l0 < L_in; l0 += per_chunk) {
+    const uint64_t Lc = L_in - l0 < per_chunk ? L_in - l0 : per_chunk;
+    const uint64_t nodes = Lc * K * N;
+    // 1. the field: D of the chunk's input layers, then every inset's lattice where the tracer reads its distances
+    HIP_TRY(hipEventRecord(w.ev[0], s));
+    const unsigned tile_blocks = (unsigned)(tiles * Lc);  // (tiles <= N: below 2^31 with the chunk's nodes)
+    LAUNCH(offset_tile_kernel, tile_blocks, s, lat, (const float4*)ws.edges.p, (const unsigned*)ws.layer_edge.p, (unsigned)l0, plan.tiles_x, plan.tiles_y, plan.band, ws.D.p,
+           ws.ctr.p);
+    LAUNCH(offset_field_kernel, blocks_of(nodes), s, (const float*)ws.D.p, (unsigned)N, (unsigned)K, plan.insets, (unsigned long long)nodes, w.dist.p);
+    // 2 .. 5. trace
+    if (int rc = trace_chunk(w, s, lat, Lc * K, l0 * K, !dry, st, parts, h_base, &largest_layer)) return rc;
+  }
+  if (int rc = trace_finish(w, s, st, largest_layer, parts, dry ? nullptr : r.get())) return rc;
+  OffsetCounters h_ctr{};
+  HIP_TRY(hipMemcpyAsync(&h_ctr, ws.ctr.p, sizeof h_ctr, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (st_out) {
+    gsdf_offset_stats os{};
+    offset_stats_of(plan, o, (uint32_t)L_in, &os);
+    os.n_verts = st.n_verts;
+    os.n_loops = st.n_loops;
+    os.border_inside = st.border_inside;
+    os.saddle_cells = st.saddle_cells;
+    os.inside_nodes = h_ctr.inside_nodes;
+    os.band_nodes = h_ctr.band_nodes;
+    os.ms_field = st.ms_eval;
+    os.ms_trace = st.ms_trace;
+    os.ms_device = st.ms_device;
+    *st_out = os;
+  }
+  if (!dry) *out = r.release();
+  return GSDF_OK;
+}
+
+extern "C" int gsdf_hip_contour_distance(const gsdf_contour* c, const gsdf_offset_opts* o, uint32_t layer, float* d_out, gsdf_offset_stats* st_out) {
+  if (!c || !o || !d_out) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
+  if (int rc = offset_check(o)) return rc;
+  if (layer >= c->st.n_layers) return fail(GSDF_ERR_BAD_ARGUMENT, "offset: layer " + std::to_string(layer) + " of a handle with " + std::to_string(c->st.n_layers) + " layers");
+  HIP_TRY(hipSetDevice(c->device));
+  Stream stream;
+  HIP_TRY(stream.ensure());
+  hipStream_t s = stream.s;
+  OffsetWs ws;
+  EventSet<2> ev;
+  StreamDrain drain{s};
+  OffsetPlan plan;
+  if (int rc = offset_prepare(c, o, s, ws, &plan)) return rc;
+  if (!dev_alloc(ws.D, plan.N) || !dev_alloc(ws.ctr, 1)) return fail(GSDF_ERR_HIP, "offset: no device memory for the workspace");
+  if (ev.ensure() != hipSuccess) return fail(GSDF_ERR_HIP, "hipEventCreate failed");
+  OffsetCounters h_ctr{};
+  HIP_TRY(hipMemsetAsync(ws.ctr.p, 0, sizeof(OffsetCounters), s));
+  HIP_TRY(hipEventRecord(ev[0], s));
+  LAUNCH(offset_tile_kernel, plan.tiles_x * plan.tiles_y, s, plan.lat, (const float4*)ws.edges.p, (const unsigned*)ws.layer_edge.p, (unsigned)layer, plan.tiles_x, plan.tiles_y,
+         plan.band, ws.D.p, ws.ctr.p);
+  HIP_TRY(hipEventRecord(ev[1], s));
+  HIP_TRY(hipMemcpyAsync(d_out, ws.D.p, (size_t)plan.N * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(&h_ctr, ws.ctr.p, sizeof h_ctr, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (st_out) {
+    gsdf_offset_stats os{};
+    offset_stats_of(plan, o, c->st.n_layers, &os);
+    os.inside_nodes = h_ctr.inside_nodes;
+    os.band_nodes = h_ctr.band_nodes;
+    os.ms_field = os.ms_device = event_ms(ev[0], ev[1]);
+    *st_out = os;
+  }
   return GSDF_OK;
 }

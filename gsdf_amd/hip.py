@@ -35,7 +35,7 @@ SYMBOLS = ["gsdf_hip_last_error", "gsdf_hip_init", "gsdf_hip_program_create", "g
            "gsdf_hip_contour_create", "gsdf_hip_contour_simplify", "gsdf_hip_contour_measures", "gsdf_hip_contour_measures_ms",
            "gsdf_hip_indexed_mass", "gsdf_hip_indexed_mass_ms", "gsdf_hip_inertia_principal", "gsdf_hip_contour_sections", "gsdf_hip_contour_sections_ms",
            "gsdf_hip_contour_hatch", "gsdf_hip_hatch_counts", "gsdf_hip_hatch_read", "gsdf_hip_hatch_rank_ms", "gsdf_hip_hatch_destroy",
-           "gsdf_hip_contour_hatch_skin", "gsdf_hip_hatch_read_skin", "gsdf_hip_skin_rank_ms"]
+           "gsdf_hip_contour_hatch_skin", "gsdf_hip_hatch_read_skin", "gsdf_hip_skin_rank_ms", "gsdf_hip_contour_offset", "gsdf_hip_contour_distance"]
 
 
 PRUNE_ASSUME_SDF = 1 << 30  # gsdf_hip.h: GSDF_PRUNE_ASSUME_SDF
@@ -315,6 +315,24 @@ SKIN_LAYER_DTYPE = np.dtype([("length", "<f8", (4,)), ("n_segments", "<u8", (4,)
 SKIN_CLASSES = ("inner", "bottom", "top", "both")
 
 
+class OffsetOpts(C.Structure):
+    """gsdf_offset_opts (gsdf_hip.h, "contours: offset"): the lattice spacing, 1 .. 8 insets (> 0 into the material, < 0 outwards), dry,
+    lattice nodes per chunk of whole input layers (0: the library's default)."""
+    _fields_ = [("res", C.c_float), ("n_insets", C.c_uint32), ("dry", C.c_uint32), ("reserved", C.c_uint32), ("max_nodes", C.c_uint64), ("inset", C.c_float * 8)]
+
+
+class OffsetStats(C.Structure):
+    """gsdf_offset_stats (gsdf_hip.h): what an offset produced and the lattice it used; bytes 0 .. 79 (RESULT_BYTES) are a function of
+    the loops and the options alone, the three times say what the run cost (distance field, tracing, their sum)."""
+    _fields_ = [("n_verts", C.c_uint64), ("n_loops", C.c_uint64), ("border_inside", C.c_uint64), ("saddle_cells", C.c_uint64), ("inside_nodes", C.c_uint64),
+                ("band_nodes", C.c_uint64), ("nx", C.c_uint32), ("ny", C.c_uint32), ("n_layers_in", C.c_uint32), ("n_insets", C.c_uint32), ("x0", C.c_float),
+                ("y0", C.c_float), ("band", C.c_float), ("res", C.c_float), ("ms_field", C.c_double), ("ms_trace", C.c_double), ("ms_device", C.c_double)]
+    RESULT_BYTES = 80
+
+    def result_bytes(self):
+        return bytes(self)[:self.RESULT_BYTES]
+
+
 # the same two as numpy records (arrays of shells, of loops, of layers)
 MASS_DTYPE = np.dtype([("volume", "<f8"), ("first", "<f8", (3,)), ("second", "<f8", (6,)), ("centroid", "<f8", (3,)), ("inertia", "<f8", (6,)),
                        ("exponent", "<i4"), ("label", "<u4")])
@@ -484,6 +502,8 @@ def lib():
         L.gsdf_hip_hatch_read_skin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.gsdf_hip_skin_rank_ms.argtypes = []
         L.gsdf_hip_skin_rank_ms.restype = C.c_double
+        L.gsdf_hip_contour_offset.argtypes = [C.c_void_p, C.POINTER(OffsetOpts), C.POINTER(C.c_void_p), C.POINTER(OffsetStats)]
+        L.gsdf_hip_contour_distance.argtypes = [C.c_void_p, C.POINTER(OffsetOpts), C.c_uint32, C.c_void_p, C.POINTER(OffsetStats)]
         L.gsdf_hip_brick_owner.restype = C.c_uint32
         L.gsdf_hip_brick_owner.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         L.gsdf_hip_slab_range.restype = None
@@ -1433,6 +1453,39 @@ class ContourHIP:
     def skin_rank_ms():
         """Device milliseconds (HIP events) of the rank and parity pass of this thread's last skin()."""
         return float(lib().gsdf_hip_skin_rank_ms())
+
+    @staticmethod
+    def _offset_opts(res, insets, max_nodes, dry):
+        insets = np.ascontiguousarray(insets, np.float32).reshape(-1)
+        o = OffsetOpts(np.float32(res), len(insets), int(bool(dry)), 0, int(max_nodes))
+        for k, v in enumerate(insets[:8]):
+            o.inset[k] = float(v)
+        return o
+
+    def offset(self, res, insets, max_nodes=0, dry=False):
+        """gsdf_hip_contour_offset: the loops moved sideways by the in-plane distances `insets` (1 .. 8 floats; > 0 into the material,
+        < 0 outwards, 0 re-traces), traced on a lattice of spacing res from the signed distance to the layer's own edges (gsdf_hip.h,
+        "contours: offset"). A new ContourHIP with n_layers x len(insets) layers -- input layer l with inset i is layer
+        l len(insets) + i -- and the call's OffsetStats as .offset_stats; dry: (None, OffsetStats)."""
+        o = self._offset_opts(res, insets, max_nodes, dry)
+        st, h = OffsetStats(), C.c_void_p()
+        _check(lib().gsdf_hip_contour_offset(self._h, C.byref(o), None if dry else C.byref(h), C.byref(st)))
+        if dry:
+            return None, st
+        c = ContourHIP(h)
+        c.offset_stats = st
+        return c
+
+    def distance(self, res, insets, layer):
+        """gsdf_hip_contour_distance: the signed in-plane distance of input layer `layer` to its own loops (negative inside, clamped to
+        the band of these insets) on exactly the lattice offset(res, insets) uses: an (ny, nx) float32 array. The lattice's origin and
+        spacing are in .offset_stats of an offset, or in the OffsetStats of a dry one. Two device passes run: a dry offset (the field
+        of every layer and its trace) for nx and ny, as the header has it, then this layer's field again."""
+        _, st = self.offset(res, insets, dry=True)
+        d = np.empty((int(st.ny), int(st.nx)), np.float32)
+        o = self._offset_opts(res, insets, 0, False)
+        _check(lib().gsdf_hip_contour_distance(self._h, C.byref(o), int(layer), d.ctypes.data, None))
+        return d
 
     def loops(self, layer=None):
         """The loops (of one layer, or of all) as (n, 2) float32 arrays, in the handle's order."""

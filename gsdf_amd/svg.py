@@ -1,5 +1,6 @@
 """SVG outlines with the standard library only (struct, re): the loops of a ContourHIP as one even-odd <path> per layer, their hatch
-segments (a HatchHIP's) as <line> elements in a group of their own (a skin hatch's in one stroke per class), and the readers. Coordinates are written as the shortest decimal that reads back as the same float32, so write followed by read is bit-exact;
+segments (a HatchHIP's) as <line> elements in a group of their own (a skin hatch's in one stroke per class), the walls of a
+ContourHIP.offset as unfilled paths of their own class, and the readers. Coordinates are written as the shortest decimal that reads back as the same float32, so write followed by read is bit-exact;
 the y axis points up in the part and down in SVG, and is turned by one transform around the paths, not by changing coordinates."""
 import re
 import struct
@@ -24,15 +25,29 @@ def fmt(v):
 
 
 SKIN_STROKES = ("#a04020", "#2060c0", "#20a040", "#a020a0")  # by class: inner (the plain hatch's stroke), bottom, top, both
+WALL_STROKE = "#206040"
 
 
-def write_svg(path, layers, z=None, stroke_width=None, hatch=None, hatch_class=None):
+def _path_data(loops):
+    d = []
+    for l in loops:
+        a = np.asarray(l, np.float32).reshape(-1, 2)
+        if len(a) == 0:
+            continue
+        d.append("M " + " L ".join("%s %s" % (fmt(x), fmt(y)) for x, y in a) + " Z")
+    return " ".join(d)
+
+
+def write_svg(path, layers, z=None, stroke_width=None, hatch=None, hatch_class=None, walls=None):
     """layers: a list (one entry per layer) of lists of loops, each loop (n, 2) float32 in order of travel. One
     <path fill-rule="evenodd"> per layer (an empty layer: an empty path), each loop `M x y L x y ... Z`. z (optional): the layers'
     heights, kept as data-z. hatch (optional): per layer an (n, 4) float32 array of segments x0 y0 x1 y1 (HatchHIP.segments(k)),
     drawn as <line> elements in one <g id="hatchK"> per layer after the paths: never as <path>, which read_svg takes for a layer.
     hatch_class (optional, with hatch): per layer the n classes 0 .. 3 of its segments (HatchHIP.cls of a skin hatch); every line
-    then carries data-class and its class's stroke (SKIN_STROKES). Without it the file is what it was before classes existed."""
+    then carries data-class and its class's stroke (SKIN_STROKES). Without it the file is what it was before classes existed.
+    walls (optional): per layer a list (one entry per wall, outermost first) of lists of loops (the layers of a ContourHIP.offset):
+    one unfilled <path class="wall" id="wallK_I"> each, in one <g id="wallsK"> per layer between the layers' paths and the hatch;
+    read_svg leaves them out and read_svg_walls returns them. Without it the file is what it was before walls existed."""
     lo, hi = [None, None], [None, None]
     for loops in layers:
         for l in loops:
@@ -51,15 +66,16 @@ def write_svg(path, layers, z=None, stroke_width=None, hatch=None, hatch_class=N
            '<svg xmlns="http://www.w3.org/2000/svg" viewBox="%.9g %.9g %.9g %.9g">\n' % (lo[0] - pad, -(hi[1] + pad), w + 2 * pad, h + 2 * pad),
            '<g transform="scale(1,-1)" fill="#c8d4e4" stroke="#203040" stroke-width="%.9g">\n' % sw]
     for k, loops in enumerate(layers):
-        d = []
-        for l in loops:
-            a = np.asarray(l, np.float32).reshape(-1, 2)
-            if len(a) == 0:
-                continue
-            pts = ["%s %s" % (fmt(x), fmt(y)) for x, y in a]
-            d.append("M " + " L ".join(pts) + " Z")
         zattr = "" if z is None else ' data-z="%s"' % fmt(np.float32(z[k]))
-        out.append('<path id="layer%d"%s fill-rule="evenodd" d="%s"/>\n' % (k, zattr, " ".join(d)))
+        out.append('<path id="layer%d"%s fill-rule="evenodd" d="%s"/>\n' % (k, zattr, _path_data(loops)))
+    if walls is not None:
+        out.append('<g id="walls" fill="none" stroke="%s" stroke-width="%.9g">\n' % (WALL_STROKE, 0.75 * sw))
+        for k, per_wall in enumerate(walls):
+            out.append('<g id="walls%d">\n' % k)
+            for i, loops in enumerate(per_wall):
+                out.append('<path class="wall" id="wall%d_%d" fill-rule="evenodd" d="%s"/>\n' % (k, i, _path_data(loops)))
+            out.append("</g>\n")
+        out.append("</g>\n")
     if hatch is not None:
         out.append('<g id="hatch" fill="none" stroke="#a04020" stroke-width="%.9g">\n' % (0.5 * sw))
         for k, segs in enumerate(hatch):
@@ -106,16 +122,24 @@ def read_svg_hatch_class(path):
     return out
 
 
+def _loops_of(d):
+    loops = []
+    for lm in _LOOP.finditer(d):
+        vals = [float(s) for s in re.findall(_NUM, lm.group(1))]
+        if len(vals) % 2:
+            raise ValueError("odd number of coordinates in a loop")
+        loops.append(np.array(vals, np.float64).astype(np.float32).reshape(-1, 2))
+    return loops
+
+
 def read_svg(path):
-    """The loops of a file written by write_svg: a list per layer (per <path>) of (n, 2) float32 arrays."""
+    """The loops of a file written by write_svg: a list per layer (per <path> that is no wall) of (n, 2) float32 arrays."""
     text = open(path, encoding="utf-8").read()
-    layers = []
-    for m in _PATH.finditer(text):
-        loops = []
-        for lm in _LOOP.finditer(m.group(1)):
-            vals = [float(s) for s in re.findall(_NUM, lm.group(1))]
-            if len(vals) % 2:
-                raise ValueError("odd number of coordinates in a loop")
-            loops.append(np.array(vals, np.float64).astype(np.float32).reshape(-1, 2))
-        layers.append(loops)
-    return layers
+    return [_loops_of(m.group(1)) for m in _PATH.finditer(text) if ' class="wall"' not in m.group(0)]
+
+
+def read_svg_walls(path):
+    """The walls of a file written by write_svg(..., walls=...): per <g id="wallsK"> a list (one entry per wall) of lists of (n, 2)
+    float32 loops."""
+    text = open(path, encoding="utf-8").read()
+    return [[_loops_of(m.group(1)) for m in _PATH.finditer(g)] for g in re.findall(r'<g id="walls\d+">(.*?)</g>', text, flags=re.S)]

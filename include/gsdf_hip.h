@@ -1243,8 +1243,9 @@ int gsdf_hip_mesh_dualcontour_indexed(gsdf_program* p, float res, int chiseled, 
  *   are left out), ms_device = their sum. Bytes 0 .. 63 of the record are a function of the inputs alone.
  * Errors. GSDF_ERR_DIMENSION: gsdf_hip_contour2 on a 3-D program, gsdf_hip_slice3 on a 2-D one. GSDF_ERR_BAD_ARGUMENT: the lattice
  *   rules above, n_z == 0, a null z. GSDF_ERR_CAPACITY: 2^32 vertices or more. Blocking; the handle is independent of the program
- *   afterwards. Out of scope: DXF / G-code, arc fitting, tool offsets (Offset2D in the tree is exact), sharded or gathered
- *   contours, a fused lattice kernel, asymptotic-decider saddles. (Simplification and the loops' areas on the device: the next section; infill: "contours: hatch
+ *   afterwards. Out of scope: DXF / G-code, arc fitting, tool offsets inside the tracer (Offset2D in the tree is exact for a 2-D
+ *   program; in-plane offsets of any handle: "contours: offset" below), sharded or gathered contours, a fused lattice kernel,
+ *   asymptotic-decider saddles. (Simplification and the loops' areas on the device: the next section; infill: "contours: hatch
  *   fill" below.)
  * Kernels: gsdf_amd/csrc/kernels_contour.h (abi_contour.hip); a numpy restatement over the oracle: tests/contourref.py. */
 typedef struct gsdf_contour gsdf_contour; /* loops, resident in HBM */
@@ -1571,6 +1572,88 @@ int gsdf_hip_contour_hatch_skin(const gsdf_contour* c, const gsdf_hatch_opts* o,
 /* cls n_segments bytes (0 .. 3), layers n_layers records; either may be NULL */
 int gsdf_hip_hatch_read_skin(const gsdf_hatch* h, uint8_t* cls, gsdf_skin_layer* layers);
 double gsdf_hip_skin_rank_ms(void);
+
+/* ---- contours: offset (no reference counterpart) ---------------------------------------------------------------------------------------
+ *
+ * The step every consumer of loops takes first: move a boundary sideways by a stated in-plane distance -- a printer's walls at half a
+ * bead, one and a half beads, ... inside the outline, the fill stopped a wall-stack short of it, a laser's kerf or a mill's radius in
+ * either direction. Offset2D in a 2-D program is exact, but offsetting a 3-D field and slicing it is NOT an in-plane offset (the 3-D
+ * distance is the shorter wherever the surface leans), and an uploaded or simplified handle has no field at all: the only correct
+ * source is the stack of loops itself. gsdf_hip_contour_offset computes, for every layer of a gsdf_contour handle (traced, uploaded,
+ * simplified, or itself an offset), the signed in-plane distance D of a lattice to the layer's own edges and traces the zero sets of
+ * D + inset[i] with the tracer of the section "contours". The result is an ordinary gsdf_contour: simplify, measures, sections, hatch,
+ * skin, read, counts and destroy work on it unchanged. Input layer l with inset i is output layer l n_insets + i (n_layers out =
+ * n_layers in x n_insets): with n_insets = 1 the layers keep their numbers, and the hatch's direction l % n_dirs and the skin's
+ * neighbours mean what they meant. gsdf_hip_contour_distance copies out D of ONE input layer (nx ny floats, row j behind row j - 1; nx
+ * and ny from a dry offset call with the same options): an in-plane distance map of a slice, on exactly the lattice the offset call
+ * uses. On the device, a function of the handle's arrays and the options alone, to the byte -- not of thread order, of the chunking,
+ * or of which edges the kernel culls. Kernels: gsdf_amd/csrc/kernels_offset.h (abi_contour.hip); a numpy restatement over every edge:
+ * tests/offsetref.py.
+ *
+ * Coordinates are taken as (double)float32 (exact). Every operation below is one IEEE float64 operation, in the order written, none
+ *   contracted, unless marked fl: float32, rounded once.
+ * Lattice. One lattice serves every layer and every inset of the call. xmin, ymin, xmax, ymax are the exact minima and maxima of
+ *   the handle's vertices (all layers; a handle without vertices: all four 0). g = max(0, max_i(-inset[i])) (float32, exact). The box
+ *   is fl(xmin - g), fl(ymin - g), fl(xmax + g), fl(ymax + g), and the paragraph "Lattice" of the section "contours" is applied to that
+ *   box with res, by name: the same x0, nx, x_i and the same refusals (a box that is not finite among them), and one more:
+ *   nx ny n_insets >= 2^31.
+ * Edges. An edge runs from a vertex to its successor in the loop; the leader follows the last vertex: the hatch's edges.
+ * Distance of node p = (x_i, y_j) to the edge a -> b.
+ *     ex = bx - ax    ey = by - ay    wx = px - ax    wy = py - ay    ee = (ex ex) + (ey ey)
+ *     h  = ee > 0 ? min(max(((wx ex) + (wy ey)) / ee, 0), 1) : 0
+ *     qx = wx - (h ex)    qy = wy - (h ey)    d2 = (qx qx) + (qy qy)
+ *   m2 = the minimum of d2 over the edges of the node's layer; +inf for a layer without loops. (A minimum does not depend on order.)
+ * Band. band = fl(fl(max_i |inset[i]|) + fl(2 res)); a = min(sqrt(m2), (double)band), the square root correctly rounded. The clamp is
+ *   what makes culling legal: an edge no nearer than band to a node cannot change that node's value.
+ * Sign. The node is INSIDE iff an odd number of its layer's edges satisfy (ay < py) != (by < py) and x_c > px, with
+ *     t = (py - ay) / (by - ay)    x_c = ax + (t (bx - ax))
+ *   the hatch's crossing predicate and formula for the direction (1, 0): the even-odd rule. A count: it does not depend on order.
+ * Field. D = fl(INSIDE ? -a : a) (float64 to float32, once); f_i = fl(D + inset[i]). inset > 0 moves the boundary INTO the material,
+ *   < 0 grows the part, 0 re-traces it on the lattice. The lattice f_i of input layer l is traced as output layer l n_insets + i by the
+ *   tracer's paragraphs "Inside", "Vertices", "Segments" and "Order", verbatim: zero is outside, a border node with f < 0 is forced
+ *   outside and counted, keys and loop order as there.
+ * Derived. |a| is 1-Lipschitz up to rounding, so a cut edge has both ends within |inset| + res of the loops: the clamp (band is 2 res
+ *   beyond the largest |inset|) never touches a node that decides a vertex, and the loops are those of the unclamped distance. Every
+ *   output vertex v has | dist(v, source loops) - |inset| | <= res plus rounding (the linear interpolation of a 1-Lipschitz function
+ *   over one lattice edge). A distance offset ROUNDS outward corners. A remainder thinner than res fragments into small loops or
+ *   vanishes (n_loops and saddle_cells show it); not an error. Where the field is exactly 0 (the medial line of a strip of width
+ *   2 inset) the node is outside.
+ * Chunks. Like the tracer's: a chunk holds whole input layers, each with all its insets, of at most max_nodes lattice nodes (always
+ *   at least one input layer). The result and the integer statistics do not depend on it. On the HOST the call holds one word per
+ *   input layer (the layers' edge ranges) and per output layer of a chunk, as the hatch holds its layer_start: a handle uploaded
+ *   with 2^29 declared layers costs 2 GB there before the device sees any work. The layers are the caller's to keep sensible.
+ * Statistics. inside_nodes and band_nodes count, over the input layers, the nodes that are INSIDE and the nodes with a < band;
+ *   border_inside, saddle_cells, n_verts and n_loops cover the output (the tracer's counts). x0, y0, band, res: the lattice's. ms_field:
+ *   device time of the distance and field kernels, ms_trace: of the tracer's steps, ms_device their sum. Bytes 0 .. 79 are a function of
+ *   the inputs alone. gsdf_hip_contour_distance fills the lattice's fields, n_layers_in, n_insets and the two node counts of its one
+ *   layer; the output's counts are 0. The result handle's own gsdf_contour_stats carries the tracer's fields with evals = 0 and
+ *   ms_eval = ms_field.
+ * dry != 0 fills the statistics and builds no handle: out may be NULL, and is set to NULL if it is not.
+ * Errors. The lattice's refusals above; GSDF_ERR_BAD_ARGUMENT: n_insets 0 or > 8, a non-finite inset (of the first n_insets),
+ *   reserved != 0, out NULL without dry, a NULL d_out, layer >= n_layers (the distance call). GSDF_ERR_CAPACITY: 2^32 output layers or
+ *   vertices or more. A handle without loops gives a handle without loops. Blocking; the result is independent of c afterwards.
+ * Out of scope: mitred or sharp outward corners (a distance offset rounds them), medial-axis gap fill, variable bead width, joining
+ *   walls into one path, travel order. */
+typedef struct gsdf_offset_opts {
+  float res;          /* lattice spacing, finite, > 0 */
+  uint32_t n_insets;  /* 1 .. 8 */
+  uint32_t dry;       /* non-zero: statistics only */
+  uint32_t reserved;  /* 0 */
+  uint64_t max_nodes; /* lattice nodes per chunk; 0 = GSDF_CONTOUR_DEFAULT_MAX_NODES */
+  float inset[8];     /* finite; > 0 moves the boundary INTO the material, < 0 grows the part, 0 re-traces it */
+} gsdf_offset_opts;
+GSDF_ABI_ASSERT(sizeof(gsdf_offset_opts) == 56, "gsdf_offset_opts is 56 bytes");
+GSDF_ABI_ASSERT(offsetof(gsdf_offset_opts, n_insets) == 4 && offsetof(gsdf_offset_opts, dry) == 8 && offsetof(gsdf_offset_opts, reserved) == 12 && offsetof(gsdf_offset_opts, max_nodes) == 16 && offsetof(gsdf_offset_opts, inset) == 24, "gsdf_offset_opts fields");
+typedef struct gsdf_offset_stats {
+  uint64_t n_verts, n_loops, border_inside, saddle_cells, inside_nodes, band_nodes;
+  uint32_t nx, ny, n_layers_in, n_insets;
+  float x0, y0, band, res;
+  double ms_field, ms_trace, ms_device; /* last: bytes 0 .. 79 are a function of the inputs alone */
+} gsdf_offset_stats;
+GSDF_ABI_ASSERT(sizeof(gsdf_offset_stats) == 104, "gsdf_offset_stats is 104 bytes");
+GSDF_ABI_ASSERT(offsetof(gsdf_offset_stats, band_nodes) == 40 && offsetof(gsdf_offset_stats, nx) == 48 && offsetof(gsdf_offset_stats, n_insets) == 60 && offsetof(gsdf_offset_stats, x0) == 64 && offsetof(gsdf_offset_stats, res) == 76 && offsetof(gsdf_offset_stats, ms_field) == 80, "gsdf_offset_stats fields");
+int gsdf_hip_contour_offset(const gsdf_contour* c, const gsdf_offset_opts* o, gsdf_contour** out /* NULL allowed iff dry */, gsdf_offset_stats* st /* optional */);
+int gsdf_hip_contour_distance(const gsdf_contour* c, const gsdf_offset_opts* o, uint32_t layer, float* d_out /* nx ny floats, host */, gsdf_offset_stats* st /* optional */);
 
 /* ---- multi-GPU (one process per GPU). The meshers shard with NO data-path collective (shard_rank / shard_count above); the
  * one exchange is the final variable-length gather of the ranks' results, over xGMI, inside this library: a Go caller needs no
