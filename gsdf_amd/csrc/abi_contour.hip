@@ -8,7 +8,10 @@
 // of parallel lines inside the loops, as a gsdf_hatch handle of its own, gsdf_hip_contour_hatch_skin (kernels_skin.h) those segments cut
 // against the layers under and over each layer and classed as inner, bottom or top skin, gsdf_hip_contour_offset /
 // gsdf_hip_contour_distance (kernels_offset.h) the loops moved sideways by in-plane distances: the signed distance of a lattice to the
-// layer's own edges, traced by the tracer's steps 2 .. 5 (trace_chunk below, which gsdf_hip_contour2 / gsdf_hip_slice3 run too).
+// layer's own edges, traced by the tracer's steps 2 .. 5 (Tracer below, which gsdf_hip_contour2 / gsdf_hip_slice3 run too).
+// What the entry points share stands once, ahead of them: Job (a call's stream, events and final wait), contour_new / hatch_new (the
+// handles' buffers), the fixed-point helpers (exponent_of, unordered, maxbits_enqueue; mass::whole and mass::value from mass_host.h),
+// scan_offsets (counts -> offsets), Tracer (steps 2 .. 5), hatch_open / length_of (the opening and the tail of hatch and skin).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -47,6 +50,8 @@ namespace {
 struct ContourDelete { void operator()(gsdf_contour* c) const { gsdf_hip_contour_destroy(c); } };
 using ContourPtr = std::unique_ptr<gsdf_contour, ContourDelete>;
 
+// (kernel parameters convert implicitly: a T* buffer goes to a const T* parameter as it is. The casts left at the launches below
+// reinterpret -- float data read or written as words, w.pos reused as vertex numbers -- or narrow a count that a capacity check bounds.)
 #define LAUNCH(KERNEL, GRID, STREAM, ...)                                          \
   do {                                                                             \
     hipLaunchKernelGGL(KERNEL, dim3(GRID), dim3(BLOCK), 0, STREAM, __VA_ARGS__);   \
@@ -60,6 +65,68 @@ bool dev_alloc(DevPtr<T>& b, uint64_t n) {
   b.reset();
   if (hipMalloc((void**)&b.p, (n ? n : 1) * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); b.p = nullptr; return false; }
   return true;
+}
+
+// One call's stream, events and final wait. `stream` is the call's own Stream or the program's, borrowed; the caller declares it
+// first, then its workspaces and unfinished handles, then the Job: on every way out the Job goes first and waits for the stream, then
+// the buffers go, and an owned stream is destroyed last.
+struct Job : NoCopy {
+  Stream& stream;
+  hipStream_t s = nullptr;
+  EventSet<8> ev;
+  explicit Job(Stream& st) : stream(st) {}
+  ~Job() { if (s) (void)hipStreamSynchronize(s); }
+  int open() {
+    HIP_TRY(stream.ensure());
+    if (ev.ensure() != hipSuccess) return fail(GSDF_ERR_HIP, "hipEventCreate failed");
+    s = stream.s;
+    return GSDF_OK;
+  }
+  double ms(int a, int b) const { float t = 0; return hipEventElapsedTime(&t, ev[a], ev[b]) == hipSuccess ? (double)t : 0.0; }
+};
+
+// a handle for n_verts vertices in n_loops loops: buffers only, the stats' three counts set
+int contour_new(int device, uint64_t n_verts, uint64_t n_loops, uint32_t n_layers, ContourPtr* out) {
+  ContourPtr c(new (std::nothrow) gsdf_contour());
+  if (!c) return fail(GSDF_ERR_BAD_ARGUMENT, "out of memory");
+  c->device = device;
+  c->n_verts = n_verts;
+  c->n_loops = n_loops;
+  c->st.n_verts = n_verts;
+  c->st.n_loops = n_loops;
+  c->st.n_layers = n_layers;
+  if (!dev_alloc(c->xy, 2 * n_verts) || !dev_alloc(c->keys, n_verts) || !dev_alloc(c->loop_start, n_loops + 1) || !dev_alloc(c->loop_layer, n_loops))
+    return fail(GSDF_ERR_HIP, "contour: no device memory for the result");
+  *out = std::move(c);
+  return GSDF_OK;
+}
+
+// ---- fixed point: the sums are integers at a power of two that the largest |coordinate| decides (gsdf_hip.h states the arithmetic) ----
+// memset and cmeas_maxbits_kernel on s: *d_maxbits = the largest bits of |x|, |y| over the handle's vertices. Queues, does not wait.
+int maxbits_enqueue(const gsdf_contour* c, unsigned long long* d_maxbits, hipStream_t s) {
+  const uint64_t V = c->n_verts;
+  const unsigned nb_max = blocks_of(2 * V) < 1024u ? blocks_of(2 * V) : 1024u;
+  HIP_TRY(hipMemsetAsync(d_maxbits, 0, 8, s));
+  LAUNCH(cmeas_maxbits_kernel, nb_max, s, c->xy.p, (unsigned long long)(2 * V), d_maxbits);
+  return GSDF_OK;
+}
+// the exponent e of that word: coordinates are below 2^e (0, the word of a handle without vertices: -125)
+int exponent_of(unsigned long long maxbits) { return (int)std::max(1u, (unsigned)(maxbits >> 23)) - 126; }
+// the float whose order-preserving word (cmeas_kernel's and offset_bbox_kernel's boxes) is o
+float unordered(unsigned o) {
+  const unsigned b = o ^ ((o >> 31) ? 0x80000000u : 0xffffffffu);
+  float f;
+  std::memcpy(&f, &b, 4);
+  return f;
+}
+// (integers -> float64: mass::whole puts the two words of a sum together, mass::value rounds it once and scales by a power of two)
+
+// cnt[n], whose per-block sums the kernel that counted left in blk_cnt -> off[n + 1], exclusive; *total = their sum. On s.
+int scan_offsets(const unsigned* cnt, uint64_t n, const unsigned* blk_cnt, unsigned* blk_base, unsigned long long* total, unsigned* off, hipStream_t s) {
+  const unsigned nb = blocks_of(n);
+  if (int rc = launch_block_scan(blk_cnt, nb, blk_base, total, s)) return rc;
+  LAUNCH(hatch_scan_kernel, nb, s, cnt, (unsigned)n, blk_base, off);
+  return GSDF_OK;
 }
 
 // nodes along one axis (gsdf_hip.h, "Lattice"): floor(fl(fl(hi - lo) / res)) + 4; 0 for a count that cannot be a lattice's
@@ -92,124 +159,159 @@ struct Workspace {
   DevPtr<ContourCounters> ctr;
   Arena verts;  // nine arrays of V words
   Arena blk;    // four arrays of blocks_of(V) words
-  EventSet<7> ev;
 };
 
-// Steps 2 .. 5 of one chunk of Lc whole layers whose distances stand in w.dist (the caller recorded w.ev[0] ahead of its field pass
-// and has just queued it): cells -> succ, vertex numbers, leaders and ranks, the loops -> a Part (none for a chunk without a cut
-// edge; with emit false the counts alone). l0: the chunk's first layer. Adds to st's counts and times; waits for s.
-int trace_chunk(Workspace& w, hipStream_t s, const ContourLattice& lat, uint64_t Lc, uint64_t l0, bool emit, gsdf_contour_stats& st, std::deque<Part>& parts,
-                std::vector<unsigned>& h_base, uint64_t* largest_layer) {
-  const char* nomem = "contour: no device memory for the workspace";
-  const uint64_t N = (uint64_t)lat.nx * lat.ny, E = 2 * N;
-  const uint64_t nodes = Lc * N, slots = Lc * E;
-  const unsigned nb_slots = blocks_of(slots);
-  auto interval_ms = [&](int a, int b) { float t = 0; return hipEventElapsedTime(&t, w.ev[a], w.ev[b]) == hipSuccess ? (double)t : 0.0; };
-  HIP_TRY(hipEventRecord(w.ev[1], s));
-  // 2. cells -> succ over the edge slots; cut edges per block, per layer
-  HIP_TRY(hipMemsetAsync(w.succ.p, 0xff, (size_t)slots * 4, s));
-  LAUNCH(contour_cells_kernel, blocks_of(nodes), s, lat, (const float*)w.dist.p, (unsigned long long)nodes, w.succ.p, w.ctr.p);
-  LAUNCH(contour_count_kernel, nb_slots, s, (const unsigned*)w.succ.p, (unsigned long long)slots, w.blk_cnt.p);
-  if (int rc = launch_block_scan(w.blk_cnt.p, nb_slots, w.blk_base.p, w.totals.p, s)) return rc;
-  LAUNCH(contour_layer_base_kernel, blocks_of(Lc + 1), s, (const unsigned*)w.succ.p, (const unsigned*)w.blk_base.p, (const unsigned long long*)w.totals.p, (unsigned)E,
-         (unsigned)Lc, w.layer_base.p);
-  HIP_TRY(hipEventRecord(w.ev[2], s));
-  HIP_TRY(hipMemcpyAsync(h_base.data(), w.layer_base.p, (size_t)(Lc + 1) * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  st.ms_eval += interval_ms(0, 1);
-  st.ms_trace += interval_ms(1, 2);
-  const uint64_t V = h_base[Lc];
-  uint64_t chunk_largest = 0;
-  for (uint64_t l = 0; l < Lc; l++) chunk_largest = std::max<uint64_t>(chunk_largest, h_base[l + 1] - h_base[l]);
-  *largest_layer = std::max(*largest_layer, chunk_largest);
-  if (V == 0) return GSDF_OK;
-  if (st.n_verts + V >= ((uint64_t)1 << 32)) return fail(GSDF_ERR_CAPACITY, "contour: 2^32 vertices or more");
-  // 3. vertex numbers, links, the leaders by pointer jumping, the ranks by list ranking: rounds for the chunk's largest layer
-  const unsigned nb_v = blocks_of(V);
-  if (w.verts.ensure((size_t)V * 9 * 4) != hipSuccess || w.blk.ensure((size_t)nb_v * 4 * 4) != hipSuccess) return fail(GSDF_ERR_HIP, nomem);
-  unsigned* va = (unsigned*)w.verts.p;
-  unsigned *slot_of = va, *pred = va + V, *mn[2] = {va + 2 * V, va + 3 * V}, *lk[2] = {va + 4 * V, va + 5 * V}, *rk[2] = {va + 6 * V, va + 7 * V}, *start_of = va + 8 * V;
-  unsigned* ba = (unsigned*)w.blk.p;
-  unsigned *blk_loops = ba, *blk_len = ba + nb_v, *base_loops = ba + 2 * (size_t)nb_v, *base_len = ba + 3 * (size_t)nb_v;
-  unsigned* vnum = (unsigned*)w.pos.p;
-  const unsigned rounds = ceil_log2(chunk_largest);
-  HIP_TRY(hipEventRecord(w.ev[3], s));
-  LAUNCH(contour_number_kernel, nb_slots, s, (const unsigned*)w.succ.p, (unsigned long long)slots, (const unsigned*)w.blk_base.p, (unsigned)V, vnum, slot_of, w.ctr.p);
-  LAUNCH(contour_link_kernel, nb_v, s, (const unsigned*)w.succ.p, (unsigned long long)slots, (const unsigned*)vnum, (const unsigned*)slot_of, (unsigned)V, pred, mn[0], lk[0],
-         w.ctr.p);
-  int cur = 0;
-  for (unsigned r = 0; r < rounds; r++, cur ^= 1)
-    LAUNCH(contour_min_kernel, nb_v, s, (const unsigned*)mn[cur], (const unsigned*)lk[cur], (unsigned)V, mn[cur ^ 1], lk[cur ^ 1]);
-  const unsigned* leader = mn[cur];
-  LAUNCH(contour_rank_init_kernel, nb_v, s, leader, (const unsigned*)pred, (unsigned)V, rk[0], lk[0]);
-  int rc_ = 0;
-  for (unsigned r = 0; r < rounds; r++, rc_ ^= 1)
-    LAUNCH(contour_rank_kernel, nb_v, s, (const unsigned*)rk[rc_], (const unsigned*)lk[rc_], (unsigned)V, rk[rc_ ^ 1], lk[rc_ ^ 1]);
-  const unsigned* rank = rk[rc_];
-  // 4. leaders -> loops
-  LAUNCH(contour_leader_count_kernel, nb_v, s, leader, (const unsigned*)pred, rank, (unsigned)V, blk_loops, blk_len);
-  if (int rc = launch_block_scan(blk_loops, nb_v, base_loops, w.totals.p + 1, s)) return rc;
-  if (int rc = launch_block_scan(blk_len, nb_v, base_len, w.totals.p + 2, s)) return rc;
-  HIP_TRY(hipEventRecord(w.ev[4], s));
-  unsigned long long h_tot[3] = {0, 0, 0};
-  ContourCounters h_ctr;
-  HIP_TRY(hipMemcpyAsync(h_tot, w.totals.p, sizeof h_tot, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(&h_ctr, w.ctr.p, sizeof h_ctr, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  st.ms_trace += interval_ms(3, 4);
-  const uint64_t nl = h_tot[1];
-  if (h_ctr.bad || nl == 0 || nl > V || h_tot[2] != V) return fail(GSDF_ERR_HIP, "contour: internal error (succ is not a permutation of the cut edges)");
-  if (emit) {
-    // 5. emit
-    parts.emplace_back();
-    Part& part = parts.back();
-    part.n_verts = V;
-    part.n_loops = nl;
-    if (!dev_alloc(part.xy, 2 * V) || !dev_alloc(part.keys, V) || !dev_alloc(part.loop_start, nl) || !dev_alloc(part.loop_layer, nl)) return fail(GSDF_ERR_HIP, nomem);
-    HIP_TRY(hipEventRecord(w.ev[5], s));
-    LAUNCH(contour_leader_number_kernel, nb_v, s, leader, (const unsigned*)pred, rank, (const unsigned*)slot_of, (unsigned)V, (const unsigned*)base_loops, (const unsigned*)base_len,
-           (unsigned)nl, (unsigned)E, (unsigned)l0, (unsigned)st.n_verts, start_of, part.loop_start.p, part.loop_layer.p, w.ctr.p);
-    LAUNCH(contour_emit_kernel, nb_v, s, lat, (const float*)w.dist.p, (const unsigned*)slot_of, leader, rank, (const unsigned*)start_of, (unsigned)V, (unsigned)E, part.xy.p,
-           part.keys.p, w.ctr.p);
-    HIP_TRY(hipEventRecord(w.ev[6], s));
-    HIP_TRY(hipStreamSynchronize(s));
-    st.ms_trace += interval_ms(5, 6);
-  }
-  st.n_verts += V;
-  st.n_loops += nl;
-  return GSDF_OK;
-}
+// The tracer's steps 2 .. 5 over a call's chunks, and what the call carries from chunk to chunk. The caller plans, allocates, queues
+// its field pass into w.dist chunk by chunk (job.ev[0] recorded ahead of it) with chunk() behind each, and finishes. A unit is what
+// the caller's chunks are whole numbers of: a layer (contour2 / slice3), an input layer with all its insets (offset).
+struct Tracer {
+  gsdf_contour_stats& st;
+  std::deque<Part> parts;  // (ahead of the workspace: it goes first)
+  Workspace w;
+  std::vector<unsigned> h_base;
+  uint64_t largest_layer = 0;
+  ContourLattice lat{};
+  uint64_t per_chunk = 0;                     // units per chunk
+  uint64_t chunk_nodes = 0, chunk_layers = 0;  // of a full chunk
 
-// Behind the last chunk: the counters of the whole call into st; with a handle, the chunks' loops behind one another in it.
-int trace_finish(Workspace& w, hipStream_t s, gsdf_contour_stats& st, uint64_t largest_layer, const std::deque<Part>& parts, gsdf_contour* c) {
-  ContourCounters h_ctr;
-  HIP_TRY(hipMemcpyAsync(&h_ctr, w.ctr.p, sizeof h_ctr, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (h_ctr.bad) return fail(GSDF_ERR_HIP, "contour: internal error (a vertex out of range)");
-  st.border_inside = h_ctr.border_inside;
-  st.nonfinite_nodes = h_ctr.nonfinite_nodes;
-  st.saddle_cells = h_ctr.saddle_cells;
-  st.rank_rounds = ceil_log2(largest_layer);
-  st.ms_device = st.ms_eval + st.ms_trace;
-  if (!c) return GSDF_OK;
-  c->n_verts = st.n_verts;
-  c->n_loops = st.n_loops;
-  if (!dev_alloc(c->xy, 2 * c->n_verts) || !dev_alloc(c->keys, c->n_verts) || !dev_alloc(c->loop_start, c->n_loops + 1) || !dev_alloc(c->loop_layer, c->n_loops))
-    return fail(GSDF_ERR_HIP, "contour: no device memory for the result");
-  uint64_t v0 = 0, q0 = 0;
-  for (const Part& part : parts) {
-    HIP_TRY(hipMemcpyAsync(c->xy.p + 2 * v0, part.xy.p, (size_t)part.n_verts * 8, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemcpyAsync(c->keys.p + v0, part.keys.p, (size_t)part.n_verts * 4, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemcpyAsync(c->loop_start.p + q0, part.loop_start.p, (size_t)part.n_loops * 4, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemcpyAsync(c->loop_layer.p + q0, part.loop_layer.p, (size_t)part.n_loops * 4, hipMemcpyDeviceToDevice, s));
-    v0 += part.n_verts;
-    q0 += part.n_loops;
+  // The one lattice of the call and its layers into st. Units per chunk: max_nodes nodes, at least one unit, the chunk's slots
+  // (layer * 2 N + key) below 2^32, no more than there are.
+  void plan(const ContourLattice& lattice, uint64_t max_nodes, uint64_t layers_per_unit, uint64_t n_units) {
+    lat = lattice;
+    st.nx = lat.nx;
+    st.ny = lat.ny;
+    st.n_layers = (uint32_t)(n_units * layers_per_unit);
+    const uint64_t unit_nodes = (uint64_t)lat.nx * lat.ny * layers_per_unit;
+    per_chunk = std::min({std::max<uint64_t>(max_nodes / unit_nodes, 1), (((uint64_t)1 << 31) - 1) / unit_nodes, n_units});
+    chunk_nodes = per_chunk * unit_nodes;
+    chunk_layers = per_chunk * layers_per_unit;
   }
-  const unsigned end = (unsigned)c->n_verts;
-  HIP_TRY(hipMemcpyAsync(c->loop_start.p + c->n_loops, &end, 4, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return GSDF_OK;
-}
+
+  // The buffers of a full chunk, the counters cleared on the job's stream. pos_words: words of w.pos per node (the field pass's
+  // positions; the slots' vertex numbers live there afterwards: 8 bytes per node at least). z: n_z planes for w.z, or null.
+  int alloc(Job& job, unsigned pos_words, const float* z, uint64_t n_z, const char* nomem) {
+    const uint64_t chunk_slots = 2 * chunk_nodes;
+    const unsigned slot_blocks = blocks_of(chunk_slots);
+    if (!dev_alloc(w.pos, chunk_nodes * pos_words) || !dev_alloc(w.dist, chunk_nodes) || !dev_alloc(w.succ, chunk_slots) || !dev_alloc(w.blk_cnt, slot_blocks) ||
+        !dev_alloc(w.blk_base, slot_blocks) || !dev_alloc(w.layer_base, chunk_layers + 1) || !dev_alloc(w.totals, 3) || !dev_alloc(w.ctr, 1) || (n_z && !dev_alloc(w.z, n_z)))
+      return fail(GSDF_ERR_HIP, nomem);
+    h_base.resize(chunk_layers + 1);
+    if (z) HIP_TRY(hipMemcpyAsync(w.z.p, z, (size_t)n_z * 4, hipMemcpyHostToDevice, job.s));
+    HIP_TRY(hipMemsetAsync(w.ctr.p, 0, sizeof(ContourCounters), job.s));
+    return GSDF_OK;
+  }
+
+  // Steps 2 .. 5 of one chunk of Lc whole layers whose distances stand in w.dist: cells -> succ, vertex numbers, leaders and ranks,
+  // the loops -> a Part (none for a chunk without a cut edge; with emit false the counts alone). l0: the chunk's first layer. Adds to
+  // st's counts and times; waits for the stream.
+  int chunk(Job& job, uint64_t Lc, uint64_t l0, bool emit) {
+    const char* nomem = "contour: no device memory for the workspace";
+    hipStream_t s = job.s;
+    const uint64_t N = (uint64_t)lat.nx * lat.ny, E = 2 * N;
+    const uint64_t nodes = Lc * N, slots = Lc * E;
+    const unsigned nb_slots = blocks_of(slots);
+    HIP_TRY(hipEventRecord(job.ev[1], s));
+    // 2. cells -> succ over the edge slots; cut edges per block, per layer
+    HIP_TRY(hipMemsetAsync(w.succ.p, 0xff, (size_t)slots * 4, s));
+    LAUNCH(contour_cells_kernel, blocks_of(nodes), s, lat, w.dist.p, (unsigned long long)nodes, w.succ.p, w.ctr.p);
+    LAUNCH(contour_count_kernel, nb_slots, s, w.succ.p, (unsigned long long)slots, w.blk_cnt.p);
+    if (int rc = launch_block_scan(w.blk_cnt.p, nb_slots, w.blk_base.p, w.totals.p, s)) return rc;
+    LAUNCH(contour_layer_base_kernel, blocks_of(Lc + 1), s, w.succ.p, w.blk_base.p, w.totals.p, (unsigned)E, (unsigned)Lc, w.layer_base.p);
+    HIP_TRY(hipEventRecord(job.ev[2], s));
+    HIP_TRY(hipMemcpyAsync(h_base.data(), w.layer_base.p, (size_t)(Lc + 1) * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    st.ms_eval += job.ms(0, 1);
+    st.ms_trace += job.ms(1, 2);
+    const uint64_t V = h_base[Lc];
+    uint64_t chunk_largest = 0;
+    for (uint64_t l = 0; l < Lc; l++) chunk_largest = std::max<uint64_t>(chunk_largest, h_base[l + 1] - h_base[l]);
+    largest_layer = std::max(largest_layer, chunk_largest);
+    if (V == 0) return GSDF_OK;
+    if (st.n_verts + V >= ((uint64_t)1 << 32)) return fail(GSDF_ERR_CAPACITY, "contour: 2^32 vertices or more");
+    // 3. vertex numbers, links, the leaders by pointer jumping, the ranks by list ranking: rounds for the chunk's largest layer
+    const unsigned nb_v = blocks_of(V);
+    if (w.verts.ensure((size_t)V * 9 * 4) != hipSuccess || w.blk.ensure((size_t)nb_v * 4 * 4) != hipSuccess) return fail(GSDF_ERR_HIP, nomem);
+    unsigned* va = (unsigned*)w.verts.p;
+    unsigned *slot_of = va, *pred = va + V, *mn[2] = {va + 2 * V, va + 3 * V}, *lk[2] = {va + 4 * V, va + 5 * V}, *rk[2] = {va + 6 * V, va + 7 * V}, *start_of = va + 8 * V;
+    unsigned* ba = (unsigned*)w.blk.p;
+    unsigned *blk_loops = ba, *blk_len = ba + nb_v, *base_loops = ba + 2 * (size_t)nb_v, *base_len = ba + 3 * (size_t)nb_v;
+    unsigned* vnum = (unsigned*)w.pos.p;
+    const unsigned rounds = ceil_log2(chunk_largest);
+    HIP_TRY(hipEventRecord(job.ev[3], s));
+    LAUNCH(contour_number_kernel, nb_slots, s, w.succ.p, (unsigned long long)slots, w.blk_base.p, (unsigned)V, vnum, slot_of, w.ctr.p);
+    LAUNCH(contour_link_kernel, nb_v, s, w.succ.p, (unsigned long long)slots, vnum, slot_of, (unsigned)V, pred, mn[0], lk[0], w.ctr.p);
+    int cur = 0;
+    for (unsigned r = 0; r < rounds; r++, cur ^= 1) LAUNCH(contour_min_kernel, nb_v, s, mn[cur], lk[cur], (unsigned)V, mn[cur ^ 1], lk[cur ^ 1]);
+    const unsigned* leader = mn[cur];
+    LAUNCH(contour_rank_init_kernel, nb_v, s, leader, pred, (unsigned)V, rk[0], lk[0]);
+    int rc_ = 0;
+    for (unsigned r = 0; r < rounds; r++, rc_ ^= 1) LAUNCH(contour_rank_kernel, nb_v, s, rk[rc_], lk[rc_], (unsigned)V, rk[rc_ ^ 1], lk[rc_ ^ 1]);
+    const unsigned* rank = rk[rc_];
+    // 4. leaders -> loops
+    LAUNCH(contour_leader_count_kernel, nb_v, s, leader, pred, rank, (unsigned)V, blk_loops, blk_len);
+    if (int rc = launch_block_scan(blk_loops, nb_v, base_loops, w.totals.p + 1, s)) return rc;
+    if (int rc = launch_block_scan(blk_len, nb_v, base_len, w.totals.p + 2, s)) return rc;
+    HIP_TRY(hipEventRecord(job.ev[4], s));
+    unsigned long long h_tot[3] = {0, 0, 0};
+    ContourCounters h_ctr;
+    HIP_TRY(hipMemcpyAsync(h_tot, w.totals.p, sizeof h_tot, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&h_ctr, w.ctr.p, sizeof h_ctr, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    st.ms_trace += job.ms(3, 4);
+    const uint64_t nl = h_tot[1];
+    if (h_ctr.bad || nl == 0 || nl > V || h_tot[2] != V) return fail(GSDF_ERR_HIP, "contour: internal error (succ is not a permutation of the cut edges)");
+    if (emit) {
+      // 5. emit
+      parts.emplace_back();
+      Part& part = parts.back();
+      part.n_verts = V;
+      part.n_loops = nl;
+      if (!dev_alloc(part.xy, 2 * V) || !dev_alloc(part.keys, V) || !dev_alloc(part.loop_start, nl) || !dev_alloc(part.loop_layer, nl)) return fail(GSDF_ERR_HIP, nomem);
+      HIP_TRY(hipEventRecord(job.ev[5], s));
+      LAUNCH(contour_leader_number_kernel, nb_v, s, leader, pred, rank, slot_of, (unsigned)V, base_loops, base_len, (unsigned)nl, (unsigned)E, (unsigned)l0, (unsigned)st.n_verts,
+             start_of, part.loop_start.p, part.loop_layer.p, w.ctr.p);
+      LAUNCH(contour_emit_kernel, nb_v, s, lat, w.dist.p, slot_of, leader, rank, start_of, (unsigned)V, (unsigned)E, part.xy.p, part.keys.p, w.ctr.p);
+      HIP_TRY(hipEventRecord(job.ev[6], s));
+      HIP_TRY(hipStreamSynchronize(s));
+      st.ms_trace += job.ms(5, 6);
+    }
+    st.n_verts += V;
+    st.n_loops += nl;
+    return GSDF_OK;
+  }
+
+  // Behind the last chunk: the counters of the whole call into st; with `out`, a handle with st and the chunks' loops behind one another.
+  int finish(Job& job, int device, ContourPtr* out) {
+    hipStream_t s = job.s;
+    ContourCounters h_ctr;
+    HIP_TRY(hipMemcpyAsync(&h_ctr, w.ctr.p, sizeof h_ctr, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (h_ctr.bad) return fail(GSDF_ERR_HIP, "contour: internal error (a vertex out of range)");
+    st.border_inside = h_ctr.border_inside;
+    st.nonfinite_nodes = h_ctr.nonfinite_nodes;
+    st.saddle_cells = h_ctr.saddle_cells;
+    st.rank_rounds = ceil_log2(largest_layer);
+    st.ms_device = st.ms_eval + st.ms_trace;
+    if (!out) return GSDF_OK;
+    ContourPtr c;
+    if (int rc = contour_new(device, st.n_verts, st.n_loops, st.n_layers, &c)) return rc;
+    c->st = st;
+    uint64_t v0 = 0, q0 = 0;
+    for (const Part& part : parts) {
+      HIP_TRY(hipMemcpyAsync(c->xy.p + 2 * v0, part.xy.p, (size_t)part.n_verts * 8, hipMemcpyDeviceToDevice, s));
+      HIP_TRY(hipMemcpyAsync(c->keys.p + v0, part.keys.p, (size_t)part.n_verts * 4, hipMemcpyDeviceToDevice, s));
+      HIP_TRY(hipMemcpyAsync(c->loop_start.p + q0, part.loop_start.p, (size_t)part.n_loops * 4, hipMemcpyDeviceToDevice, s));
+      HIP_TRY(hipMemcpyAsync(c->loop_layer.p + q0, part.loop_layer.p, (size_t)part.n_loops * 4, hipMemcpyDeviceToDevice, s));
+      v0 += part.n_verts;
+      q0 += part.n_loops;
+    }
+    const unsigned end = (unsigned)c->n_verts;
+    HIP_TRY(hipMemcpyAsync(c->loop_start.p + c->n_loops, &end, 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *out = std::move(c);
+    return GSDF_OK;
+  }
+};
 
 int contour_run(gsdf_program* p, int dim, float res, const float* z, uint32_t n_z, const gsdf_contour_opts* o, gsdf_contour** out) {
   if (!p || !out) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
@@ -222,56 +324,33 @@ int contour_run(gsdf_program* p, int dim, float res, const float* z, uint32_t n_
     if (a % 3 != 2 && !std::isfinite(bb[a])) return fail(GSDF_ERR_BAD_ARGUMENT, "contour: the program's bounds are not finite");
   const uint64_t nx = axis_nodes(bb[0], bb[3], res), ny = axis_nodes(bb[1], bb[4], res);
   if (nx == 0 || ny == 0 || nx * ny >= ((uint64_t)1 << 31)) return fail(GSDF_ERR_BAD_ARGUMENT, "contour: the lattice needs 2^31 nodes or more at this res");
-  const uint64_t N = nx * ny, E = 2 * N, L = dim == 2 ? 1 : n_z;
+  const uint64_t N = nx * ny, L = dim == 2 ? 1 : n_z;
   ContourLattice lat{(unsigned)nx, (unsigned)ny, bb[0] - res, bb[1] - res, res};
-  // layers per chunk: max_nodes nodes, at least one layer, and slots (layer * E + key) below 2^32
-  uint64_t max_nodes = o && o->max_nodes ? o->max_nodes : (uint64_t)GSDF_CONTOUR_DEFAULT_MAX_NODES;
-  uint64_t per_chunk = max_nodes / N;
-  if (per_chunk < 1) per_chunk = 1;
-  if (per_chunk > (((uint64_t)1 << 31) - 1) / N) per_chunk = (((uint64_t)1 << 31) - 1) / N;
-  if (per_chunk > L) per_chunk = L;
 
   HIP_TRY(hipSetDevice(p->device));
   spec_adopt(p);
-  hipStream_t s = p->stream.s;
-  std::deque<Part> parts;  // (ahead of the handle and the workspace; all of them outlive the work on s: every way out below has waited for it)
-  Workspace w;
-  ContourPtr c(new (std::nothrow) gsdf_contour());
-  if (!c) return fail(GSDF_ERR_BAD_ARGUMENT, "out of memory");
-  c->device = p->device;
-  const char* nomem = "contour: no device memory for the workspace";
-  const uint64_t chunk_nodes = per_chunk * N, chunk_slots = per_chunk * E;
-  const unsigned slot_blocks = blocks_of(chunk_slots);
-  // (the vertex numbers of the slots live where the positions were: 8 bytes per node either way)
-  if (!dev_alloc(w.pos, chunk_nodes * (dim == 2 ? 2 : 3)) || !dev_alloc(w.dist, chunk_nodes) || !dev_alloc(w.succ, chunk_slots) || !dev_alloc(w.blk_cnt, slot_blocks) ||
-      !dev_alloc(w.blk_base, slot_blocks) || !dev_alloc(w.layer_base, per_chunk + 1) || !dev_alloc(w.totals, 3) || !dev_alloc(w.ctr, 1) || !dev_alloc(w.z, L))
-    return fail(GSDF_ERR_HIP, nomem);
-  if (w.ev.ensure() != hipSuccess) return fail(GSDF_ERR_HIP, "hipEventCreate failed");
-  // on every way out from here the stream is drained before the buffers above go
-  struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{s};
-  if (dim == 3) HIP_TRY(hipMemcpyAsync(w.z.p, z, (size_t)L * 4, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemsetAsync(w.ctr.p, 0, sizeof(ContourCounters), s));
-
-  gsdf_contour_stats& st = c->st;
-  st.nx = (uint32_t)nx;
-  st.ny = (uint32_t)ny;
-  st.n_layers = (uint32_t)L;
-  std::vector<unsigned> h_base(per_chunk + 1);
-  uint64_t largest_layer = 0;
-
-  for (uint64_t l0 = 0; l0 < L; l0 += per_chunk) {
-    const uint64_t Lc = L - l0 < per_chunk ? L - l0 : per_chunk;
+  gsdf_contour_stats st{};
+  Tracer t{st};
+  ContourPtr c;
+  Job job(p->stream);  // (the program's stream, borrowed)
+  if (int rc = job.open()) return rc;
+  hipStream_t s = job.s;
+  t.plan(lat, o && o->max_nodes ? o->max_nodes : (uint64_t)GSDF_CONTOUR_DEFAULT_MAX_NODES, 1, L);
+  if (int rc = t.alloc(job, dim == 2 ? 2 : 3, dim == 3 ? z : nullptr, L, "contour: no device memory for the workspace")) return rc;
+  Workspace& w = t.w;
+  for (uint64_t l0 = 0; l0 < L; l0 += t.per_chunk) {
+    const uint64_t Lc = L - l0 < t.per_chunk ? L - l0 : t.per_chunk;
     const uint64_t nodes = Lc * N;
     // 1. evaluate: positions, then the program's Evaluate over them
-    HIP_TRY(hipEventRecord(w.ev[0], s));
-    if (dim == 2) LAUNCH(contour_pos_kernel<2>, blocks_of(nodes), s, lat, (const float*)nullptr, (unsigned long long)nodes, w.pos.p);
-    else LAUNCH(contour_pos_kernel<3>, blocks_of(nodes), s, lat, (const float*)(w.z.p + l0), (unsigned long long)nodes, w.pos.p);
+    HIP_TRY(hipEventRecord(job.ev[0], s));
+    if (dim == 2) LAUNCH(contour_pos_kernel<2>, blocks_of(nodes), s, lat, nullptr, (unsigned long long)nodes, w.pos.p);
+    else LAUNCH(contour_pos_kernel<3>, blocks_of(nodes), s, lat, w.z.p + l0, (unsigned long long)nodes, w.pos.p);
     if (int rc = dim == 2 ? gsdf_hip_eval2_dev(p, w.pos.p, 8, w.dist.p, (size_t)nodes, (void*)s) : gsdf_hip_eval3_dev(p, w.pos.p, 12, w.dist.p, (size_t)nodes, (void*)s)) return rc;
     // 2 .. 5. trace
-    if (int rc = trace_chunk(w, s, lat, Lc, l0, true, st, parts, h_base, &largest_layer)) return rc;
+    if (int rc = t.chunk(job, Lc, l0, true)) return rc;
   }
   st.evals = N * L;
-  if (int rc = trace_finish(w, s, st, largest_layer, parts, c.get())) return rc;
+  if (int rc = t.finish(job, p->device, &c)) return rc;
   *out = c.release();
   return GSDF_OK;
 }
@@ -308,36 +387,11 @@ extern "C" int gsdf_hip_contour_stats_get(const gsdf_contour* c, gsdf_contour_st
 
 // ---- loops after tracing: upload, simplify, measures (gsdf_hip.h, "contours: simplify and measures") -------------------------------
 namespace {
-// a handle for n_verts vertices in n_loops loops: buffers only, the stats' three counts set
-int contour_new(int device, uint64_t n_verts, uint64_t n_loops, uint32_t n_layers, ContourPtr* out) {
-  ContourPtr c(new (std::nothrow) gsdf_contour());
-  if (!c) return fail(GSDF_ERR_BAD_ARGUMENT, "out of memory");
-  c->device = device;
-  c->n_verts = n_verts;
-  c->n_loops = n_loops;
-  c->st.n_verts = n_verts;
-  c->st.n_loops = n_loops;
-  c->st.n_layers = n_layers;
-  if (!dev_alloc(c->xy, 2 * n_verts) || !dev_alloc(c->keys, n_verts) || !dev_alloc(c->loop_start, n_loops + 1) || !dev_alloc(c->loop_layer, n_loops))
-    return fail(GSDF_ERR_HIP, "contour: no device memory for the result");
-  *out = std::move(c);
-  return GSDF_OK;
-}
-
-// the loops one pass reads or writes (device pointers; the owner is a handle)
-struct LoopsView {
-  uint64_t n_verts, n_loops;
-  float* xy;
-  unsigned *keys, *loop_start;
-};
-LoopsView view_of(const gsdf_contour* c) { return LoopsView{c->n_verts, c->n_loops, c->xy.p, c->keys.p, c->loop_start.p}; }
-
 struct SimplifyWs {
   DevPtr<unsigned> loop_of, rej, changed, blk_cnt, blk_base;
   DevPtr<unsigned char> keep;
   DevPtr<unsigned long long> total;
   DevPtr<CsimpCounters> ctr;
-  EventSet<4> ev;
 };
 }  // namespace
 
@@ -397,48 +451,45 @@ extern "C" int gsdf_hip_contour_simplify(const gsdf_contour* c, const gsdf_conto
   ContourPtr cur;  // the previous pass's result; null: the caller's handle
   if (c->n_verts > 0 && c->n_loops > 0) {
     const uint64_t V0 = c->n_verts, NL = c->n_loops;
-    Stream stream;  // (ahead of the workspace: the work on it is over before the buffers go, and it goes last)
-    HIP_TRY(stream.ensure());
-    hipStream_t s = stream.s;
+    Stream stream;
     SimplifyWs w;
+    Job job(stream);
+    if (int rc = job.open()) return rc;
+    hipStream_t s = job.s;
     const unsigned nb0 = blocks_of(V0);
     if (!dev_alloc(w.loop_of, V0) || !dev_alloc(w.rej, V0) || !dev_alloc(w.changed, NL) || !dev_alloc(w.blk_cnt, nb0) || !dev_alloc(w.blk_base, nb0) || !dev_alloc(w.keep, V0) ||
         !dev_alloc(w.total, 1) || !dev_alloc(w.ctr, 1))
       return fail(GSDF_ERR_HIP, "contour simplify: no device memory for the workspace");
-    if (w.ev.ensure() != hipSuccess) return fail(GSDF_ERR_HIP, "hipEventCreate failed");
-    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{s};
     HIP_TRY(hipMemsetAsync(w.ctr.p, 0, sizeof(CsimpCounters), s));
-    auto interval_ms = [&](int a, int b) { float t = 0; return hipEventElapsedTime(&t, w.ev[a], w.ev[b]) == hipSuccess ? (double)t : 0.0; };
     for (unsigned pass = 0; pass < passes; pass++) {
-      const LoopsView in = view_of(cur ? cur.get() : c);
-      const uint64_t V = in.n_verts;
+      const gsdf_contour* in = cur ? cur.get() : c;
+      const uint64_t V = in->n_verts;
       const unsigned nb = blocks_of(V);
       const bool last = pass + 1 == passes;
-      HIP_TRY(hipEventRecord(w.ev[0], s));
+      HIP_TRY(hipEventRecord(job.ev[0], s));
       HIP_TRY(hipMemsetAsync(w.rej.p, 0, (size_t)V * 4, s));
       HIP_TRY(hipMemsetAsync(w.changed.p, 0, (size_t)NL * 4, s));
-      LAUNCH(cloop_of_kernel, nb, s, (const unsigned*)in.loop_start, (unsigned)NL, (unsigned)V, w.loop_of.p);
-      LAUNCH(csimp_reject_kernel, nb, s, (const float*)in.xy, (const unsigned*)in.loop_start, (const unsigned*)w.loop_of.p, (unsigned)V, levels, tol2, w.rej.p);
-      LAUNCH(csimp_mark_kernel, nb, s, (const float*)in.xy, (const unsigned*)in.loop_start, (const unsigned*)w.loop_of.p, (unsigned)V, levels, (const unsigned*)w.rej.p, w.keep.p,
-             w.changed.p, w.blk_cnt.p, w.ctr.p);
+      LAUNCH(cloop_of_kernel, nb, s, in->loop_start.p, (unsigned)NL, (unsigned)V, w.loop_of.p);
+      LAUNCH(csimp_reject_kernel, nb, s, in->xy.p, in->loop_start.p, w.loop_of.p, (unsigned)V, levels, tol2, w.rej.p);
+      LAUNCH(csimp_mark_kernel, nb, s, in->xy.p, in->loop_start.p, w.loop_of.p, (unsigned)V, levels, w.rej.p, w.keep.p, w.changed.p, w.blk_cnt.p, w.ctr.p);
       if (int rc = launch_block_scan(w.blk_cnt.p, nb, w.blk_base.p, w.total.p, s)) return rc;
-      HIP_TRY(hipEventRecord(w.ev[1], s));
+      HIP_TRY(hipEventRecord(job.ev[1], s));
       unsigned long long h_total = 0;
       HIP_TRY(hipMemcpyAsync(&h_total, w.total.p, 8, hipMemcpyDeviceToHost, s));
       HIP_TRY(hipStreamSynchronize(s));
-      st.ms_device += interval_ms(0, 1);
+      st.ms_device += job.ms(0, 1);
       if (h_total < 3 * NL || h_total > V) return fail(GSDF_ERR_HIP, "contour simplify: internal error (a loop kept fewer than 3 vertices)");
       st.n_verts_out = h_total;
       if (last && dry) break;
       ContourPtr next;
       if (int rc = contour_new(c->device, h_total, NL, c->st.n_layers, &next)) return rc;
-      HIP_TRY(hipEventRecord(w.ev[2], s));
-      LAUNCH(csimp_emit_kernel, nb, s, (const unsigned*)in.xy, (const unsigned*)in.keys, (const unsigned*)in.loop_start, (const unsigned*)w.loop_of.p, (unsigned)V, (unsigned)NL,
-             (const unsigned char*)w.keep.p, (const unsigned*)w.blk_base.p, (unsigned)h_total, (unsigned*)next->xy.p, next->keys.p, next->loop_start.p, w.ctr.p);
+      HIP_TRY(hipEventRecord(job.ev[2], s));
+      LAUNCH(csimp_emit_kernel, nb, s, (const unsigned*)in->xy.p, in->keys.p, in->loop_start.p, w.loop_of.p, (unsigned)V, (unsigned)NL, w.keep.p, w.blk_base.p, (unsigned)h_total,
+             (unsigned*)next->xy.p, next->keys.p, next->loop_start.p, w.ctr.p);
       HIP_TRY(hipMemcpyAsync(next->loop_layer.p, c->loop_layer.p, (size_t)NL * 4, hipMemcpyDeviceToDevice, s));
-      HIP_TRY(hipEventRecord(w.ev[3], s));
+      HIP_TRY(hipEventRecord(job.ev[3], s));
       HIP_TRY(hipStreamSynchronize(s));
-      st.ms_device += interval_ms(2, 3);
+      st.ms_device += job.ms(2, 3);
       cur = std::move(next);
     }
     CsimpCounters h_ctr;
@@ -487,40 +538,35 @@ int measure_run(const gsdf_contour* c, bool sections, MeasureRun* r) {
   if (V > 0 && NL > 0) {
     HIP_TRY(hipSetDevice(c->device));
     Stream stream;
-    HIP_TRY(stream.ensure());
-    hipStream_t s = stream.s;
     DevPtr<unsigned> loop_of;
     DevPtr<CmeasAcc> acc;
     DevPtr<CsectAcc> sect;
     DevPtr<unsigned long long> maxbits;
-    EventSet<2> ev;
+    Job job(stream);
+    if (int rc = job.open()) return rc;
+    hipStream_t s = job.s;
     if (!dev_alloc(loop_of, V) || !dev_alloc(acc, NL) || !dev_alloc(maxbits, 1) || (sections && !dev_alloc(sect, NL)))
       return fail(GSDF_ERR_HIP, "contour measures: no device memory for the workspace");
-    if (ev.ensure() != hipSuccess) return fail(GSDF_ERR_HIP, "hipEventCreate failed");
-    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{s};
-    const unsigned nb = blocks_of(V), nb_max = blocks_of(2 * V) < 1024u ? blocks_of(2 * V) : 1024u;
-    HIP_TRY(hipEventRecord(ev[0], s));
-    HIP_TRY(hipMemsetAsync(maxbits.p, 0, 8, s));
-    LAUNCH(cmeas_maxbits_kernel, nb_max, s, (const float*)c->xy.p, (unsigned long long)(2 * V), maxbits.p);
+    const unsigned nb = blocks_of(V);
+    HIP_TRY(hipEventRecord(job.ev[0], s));
+    if (int rc = maxbits_enqueue(c, maxbits.p, s)) return rc;
     LAUNCH(cmeas_init_kernel, blocks_of(NL), s, acc.p, (unsigned)NL);
-    LAUNCH(cloop_of_kernel, nb, s, (const unsigned*)c->loop_start.p, (unsigned)NL, (unsigned)V, loop_of.p);
-    LAUNCH(cmeas_kernel, nb, s, (const float*)c->xy.p, (const unsigned*)c->loop_start.p, (const unsigned*)loop_of.p, (unsigned)V, (const unsigned long long*)maxbits.p, acc.p);
+    LAUNCH(cloop_of_kernel, nb, s, c->loop_start.p, (unsigned)NL, (unsigned)V, loop_of.p);
+    LAUNCH(cmeas_kernel, nb, s, c->xy.p, c->loop_start.p, loop_of.p, (unsigned)V, maxbits.p, acc.p);
     if (sections) {
       HIP_TRY(hipMemsetAsync(sect.p, 0, (size_t)NL * sizeof(CsectAcc), s));
-      LAUNCH(csect_kernel, nb, s, (const float*)c->xy.p, (const unsigned*)c->loop_start.p, (const unsigned*)loop_of.p, (unsigned)V, (const unsigned long long*)maxbits.p, sect.p);
+      LAUNCH(csect_kernel, nb, s, c->xy.p, c->loop_start.p, loop_of.p, (unsigned)V, maxbits.p, sect.p);
     }
-    HIP_TRY(hipEventRecord(ev[1], s));
+    HIP_TRY(hipEventRecord(job.ev[1], s));
     HIP_TRY(hipMemcpyAsync(r->acc.data(), acc.p, (size_t)NL * sizeof(CmeasAcc), hipMemcpyDeviceToHost, s));
     if (sections) HIP_TRY(hipMemcpyAsync(r->sect.data(), sect.p, (size_t)NL * sizeof(CsectAcc), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(r->start.data(), c->loop_start.p, (size_t)(NL + 1) * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(r->layer.data(), c->loop_layer.p, (size_t)NL * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(&h_maxbits, maxbits.p, 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    float t = 0;
-    if (hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess) r->ms = t;
+    r->ms = job.ms(0, 1);
   }
-  const unsigned biased = (unsigned)(h_maxbits >> 23);
-  r->e = (int)(biased > 1u ? biased : 1u) - 126;
+  r->e = exponent_of(h_maxbits);
   return GSDF_OK;
 }
 }  // namespace
@@ -536,21 +582,18 @@ extern "C" int gsdf_hip_contour_measures(const gsdf_contour* c, gsdf_loop_measur
   MeasureRun run;
   if (int rc = measure_run(c, false, &run)) return rc;
   g_measures_ms = run.ms;
-  const std::vector<CmeasAcc>& h_acc = run.acc;
-  const std::vector<unsigned>&h_start = run.start, &h_layer = run.layer;
   // integers -> float64 with one rounding each, times the inverse power of two (exact); area = sum / 2
   const int e = run.e;
-  auto whole = [](unsigned long long lo, unsigned long long hi) { return (__int128)(long long)hi * ((__int128)1 << 32) + (__int128)lo; };
-  auto unordered = [](unsigned o) { const unsigned b = o ^ ((o >> 31) ? 0x80000000u : 0xffffffffu); float f; std::memcpy(&f, &b, 4); return f; };
+  const std::vector<unsigned>&h_start = run.start, &h_layer = run.layer;
   struct LayerAcc { __int128 area = 0, length = 0; unsigned bb[4] = {CMEAS_BB_MIN_INIT, CMEAS_BB_MIN_INIT, CMEAS_BB_MAX_INIT, CMEAS_BB_MAX_INIT}; uint32_t n_loops = 0, n_verts = 0; };
   std::vector<LayerAcc> la(layers ? L : 0);
   for (uint64_t q = 0; q < NL; q++) {
-    const CmeasAcc& a = h_acc[q];
-    const __int128 area = whole(a.sum[0], a.sum[1]), length = whole(a.sum[2], a.sum[3]);
+    const CmeasAcc& a = run.acc[q];
+    const __int128 area = mass::whole(a.sum[0], a.sum[1]), length = mass::whole(a.sum[2], a.sum[3]);
     if (loops) {
       gsdf_loop_measure& m = loops[q];
-      m.area = std::ldexp((double)area, 2 * e - 62);
-      m.length = std::ldexp((double)length, e - 60);
+      m.area = mass::value(area, 62 - 2 * e);
+      m.length = mass::value(length, 60 - e);
       for (int k = 0; k < 4; k++) m.bbox[k] = unordered(a.bb[k]);
       m.n_verts = h_start[q + 1] - h_start[q];
       m.layer = h_layer[q];
@@ -570,8 +613,8 @@ extern "C" int gsdf_hip_contour_measures(const gsdf_contour* c, gsdf_loop_measur
   if (layers)
     for (uint32_t l = 0; l < L; l++) {
       gsdf_layer_measure& m = layers[l];
-      m.area = std::ldexp((double)la[l].area, 2 * e - 62);
-      m.length = std::ldexp((double)la[l].length, e - 60);
+      m.area = mass::value(la[l].area, 62 - 2 * e);
+      m.length = mass::value(la[l].length, 60 - e);
       for (int k = 0; k < 4; k++) m.bbox[k] = la[l].n_loops ? unordered(la[l].bb[k]) : (k < 2 ? inf : -inf);
       m.n_loops = la[l].n_loops;
       m.n_verts = la[l].n_verts;
@@ -633,6 +676,20 @@ namespace {
 struct HatchDelete { void operator()(gsdf_hatch* h) const { gsdf_hip_hatch_destroy(h); } };
 using HatchPtr = std::unique_ptr<gsdf_hatch, HatchDelete>;
 
+// a handle of n_layers layers without a segment: host records only, the segments' buffers come with their count
+int hatch_new(int device, uint32_t n_layers, bool with_classes, HatchPtr* out) {
+  HatchPtr h(new (std::nothrow) gsdf_hatch());
+  if (!h) return fail(GSDF_ERR_BAD_ARGUMENT, "out of memory");
+  h->device = device;
+  h->n_layers = n_layers;
+  h->layer_start.assign((size_t)n_layers + 1, 0u);
+  h->layers.assign(n_layers, gsdf_hatch_layer{0.0, 0, 0, -1});
+  h->has_classes = with_classes;
+  if (with_classes) h->skin_layers.assign(n_layers, gsdf_skin_layer{});
+  *out = std::move(h);
+  return GSDF_OK;
+}
+
 struct HatchWs {
   DevPtr<unsigned long long> maxbits, total;
   DevPtr<unsigned> loop_of, cnt, edge_off, blk_cnt, blk_base;
@@ -642,7 +699,6 @@ struct HatchWs {
   DevPtr<unsigned> slot_base, line_cnt, line_start, cursor, cross_edge, cross_slot, rec_j, rec_slot, layer_start;
   DevPtr<double> rec_u, u_sorted;
   DevPtr<float> rec_xy;
-  EventSet<6> ev;
 };
 thread_local double g_hatch_rank_ms = 0;
 
@@ -673,75 +729,100 @@ int hatch_params(const gsdf_hatch_opts* o, const void* out, HatchParams* P_out) 
 bool hatch_too_small(const HatchParams& P, int e) { return (std::ldexp(1.0, e + 1) + std::fabs(P.offset)) / P.spacing >= 536870912.0; }
 const char* const kHatchSmallText = "hatch: spacing is too small for these coordinates ((2^(e+1) + |offset|) / spacing must stay below 2^29)";
 const char* const kHatchNoMem = "hatch: no device memory for the workspace";
+const char* const kSkinNoMem = "skin: no device memory for the workspace";
 
-// a stream that is waited for before the buffers declared ahead of it go
-struct StreamDrain { hipStream_t s; ~StreamDrain() { (void)hipStreamSynchronize(s); } };
+// What both entry points open with. The caller declares it first: an unfinished handle goes behind the call's workspace and stream.
+struct HatchOpening {
+  HatchParams P{};
+  HatchPtr h;          // n_layers empty layers
+  bool loops = false;  // the handle has loops: the job is open and what follows is set
+  int e = 0;
+  std::vector<HatchLayerAcc> own;   // the layers' own line ranges (k_min > k_max: none)
+  std::vector<unsigned> slot_base;  // the layers' line slots (layer, k - k_min) behind one another
+  std::vector<int> k_min;
+  uint64_t n_slots = 0, n_own = 0;  // line slots, own crossings
+};
 
-double event_ms(hipEvent_t a, hipEvent_t b) { float t = 0; return hipEventElapsedTime(&t, a, b) == hipSuccess ? (double)t : 0.0; }
-
-// Steps 0 and 1 of a hatch on s (w.ev[0], w.ev[1]; w.maxbits and w.ev are the caller's): the exponent and the one argument check that
-// needs it; every edge's lines (k_first, cnt, edge_off), the layers' line ranges, the crossings of the call. Waits for s.
-int hatch_ranges(const gsdf_contour* c, const HatchParams& P, hipStream_t s, HatchWs& w, int* e_out, std::vector<HatchLayerAcc>& h_acc, uint64_t* n_crossings, double* ms) {
+// Steps 0 and 1 of a hatch on the job's stream (events 0 and 1; w.maxbits is the caller's): the exponent and the one argument check that
+// needs it; every edge's lines (k_first, cnt, edge_off), the layers' line ranges, the crossings of the call. Waits for the stream.
+int hatch_ranges(const gsdf_contour* c, Job& job, HatchWs& w, HatchOpening* a, double* ms) {
   const uint64_t V = c->n_verts, NL = c->n_loops;
   const uint32_t L = c->st.n_layers;
+  hipStream_t s = job.s;
   // 0. the exponent; the one argument check that needs it
-  const unsigned nb = blocks_of(V), nb_max = blocks_of(2 * V) < 1024u ? blocks_of(2 * V) : 1024u;
+  const unsigned nb = blocks_of(V);
   unsigned long long h_maxbits = 0;
-  HIP_TRY(hipEventRecord(w.ev[0], s));
-  HIP_TRY(hipMemsetAsync(w.maxbits.p, 0, 8, s));
-  LAUNCH(cmeas_maxbits_kernel, nb_max, s, (const float*)c->xy.p, (unsigned long long)(2 * V), w.maxbits.p);
-  HIP_TRY(hipEventRecord(w.ev[1], s));
+  HIP_TRY(hipEventRecord(job.ev[0], s));
+  if (int rc = maxbits_enqueue(c, w.maxbits.p, s)) return rc;
+  HIP_TRY(hipEventRecord(job.ev[1], s));
   HIP_TRY(hipMemcpyAsync(&h_maxbits, w.maxbits.p, 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  *ms += event_ms(w.ev[0], w.ev[1]);
-  const unsigned biased = (unsigned)(h_maxbits >> 23);
-  const int e = (int)(biased > 1u ? biased : 1u) - 126;
-  *e_out = e;
-  if (hatch_too_small(P, e)) return fail(GSDF_ERR_BAD_ARGUMENT, kHatchSmallText);
+  *ms += job.ms(0, 1);
+  a->e = exponent_of(h_maxbits);
+  if (hatch_too_small(a->P, a->e)) return fail(GSDF_ERR_BAD_ARGUMENT, kHatchSmallText);
   // 1. every edge's lines, the layers' line ranges, the edges' offsets
   if (!dev_alloc(w.loop_of, V) || !dev_alloc(w.k_first, V) || !dev_alloc(w.cnt, V) || !dev_alloc(w.edge_off, V + 1) || !dev_alloc(w.blk_cnt, nb) ||
       !dev_alloc(w.blk_base, nb) || !dev_alloc(w.total, 1) || !dev_alloc(w.acc, L) || !dev_alloc(w.ctr, 1) || !dev_alloc(w.slot_base, (uint64_t)L + 1) ||
       !dev_alloc(w.layer_kmin, L) || !dev_alloc(w.layer_start, (uint64_t)L + 1))
     return fail(GSDF_ERR_HIP, kHatchNoMem);
-  h_acc.assign(L, HatchLayerAcc{});
+  a->own.assign(L, HatchLayerAcc{});
   HatchCounters h_ctr{};
-  HIP_TRY(hipEventRecord(w.ev[0], s));
+  HIP_TRY(hipEventRecord(job.ev[0], s));
   HIP_TRY(hipMemsetAsync(w.ctr.p, 0, sizeof(HatchCounters), s));
   LAUNCH(hatch_init_kernel, blocks_of(L), s, w.acc.p, (unsigned)L);
-  LAUNCH(cloop_of_kernel, nb, s, (const unsigned*)c->loop_start.p, (unsigned)NL, (unsigned)V, w.loop_of.p);
-  LAUNCH(hatch_range_kernel, nb, s, (const float*)c->xy.p, (const unsigned*)c->loop_start.p, (const unsigned*)w.loop_of.p, (const unsigned*)c->loop_layer.p, (unsigned)V, (unsigned)L,
-         P, w.k_first.p, w.cnt.p, w.blk_cnt.p, w.acc.p, w.ctr.p);
-  if (int rc = launch_block_scan(w.blk_cnt.p, nb, w.blk_base.p, w.total.p, s)) return rc;
-  LAUNCH(hatch_scan_kernel, nb, s, (const unsigned*)w.cnt.p, (unsigned)V, (const unsigned*)w.blk_base.p, w.edge_off.p);
-  HIP_TRY(hipEventRecord(w.ev[1], s));
+  LAUNCH(cloop_of_kernel, nb, s, c->loop_start.p, (unsigned)NL, (unsigned)V, w.loop_of.p);
+  LAUNCH(hatch_range_kernel, nb, s, c->xy.p, c->loop_start.p, w.loop_of.p, c->loop_layer.p, (unsigned)V, (unsigned)L, a->P, w.k_first.p, w.cnt.p, w.blk_cnt.p, w.acc.p, w.ctr.p);
+  if (int rc = scan_offsets(w.cnt.p, V, w.blk_cnt.p, w.blk_base.p, w.total.p, w.edge_off.p, s)) return rc;
+  HIP_TRY(hipEventRecord(job.ev[1], s));
   HIP_TRY(hipMemcpyAsync(&h_ctr, w.ctr.p, sizeof h_ctr, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(h_acc.data(), w.acc.p, (size_t)L * sizeof(HatchLayerAcc), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(a->own.data(), w.acc.p, (size_t)L * sizeof(HatchLayerAcc), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  *ms += event_ms(w.ev[0], w.ev[1]);
+  *ms += job.ms(0, 1);
   if (h_ctr.bad) return fail(GSDF_ERR_HIP, "hatch: internal error (a loop names a layer the handle does not have)");
-  *n_crossings = h_ctr.n_crossings;
+  a->n_own = h_ctr.n_crossings;
   if (h_ctr.n_crossings >= ((uint64_t)1 << 32)) return fail(GSDF_ERR_CAPACITY, "hatch: 2^32 crossings or more");
   return GSDF_OK;
 }
 
-// the layers' line slots (layer, k - k_min) behind one another
-int hatch_slots(const std::vector<HatchLayerAcc>& h_acc, std::vector<unsigned>& slot_base, std::vector<int>& k_min, uint64_t* n_slots) {
-  const size_t L = h_acc.size();
-  slot_base.assign(L + 1, 0u);
-  k_min.assign(L, 0);
+// In this order: the options' checks (k: the skin's, or null), the handle, the device; a handle without loops is held to the smallest
+// exponent, otherwise the job opens, w.maxbits comes, hatch_ranges runs (device time added to *ms) and the layers get their slots. A
+// plain hatch's layers take their own line range here (a skin's take the range of their pieces, later).
+int hatch_open(const gsdf_contour* c, const gsdf_hatch_opts* o, const gsdf_skin_opts* k, const void* out, Job& job, HatchWs& w, HatchOpening* a, double* ms) {
+  if (int rc = hatch_params(o, out, &a->P)) return rc;
+  if (k && (k->below > SKIN_MAX_WINDOW || k->above > SKIN_MAX_WINDOW)) return fail(GSDF_ERR_BAD_ARGUMENT, "skin: below and above must be 0 .. 8");
+  const uint32_t L = c->st.n_layers;
+  if (int rc = hatch_new(c->device, L, k != nullptr, &a->h)) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  if (c->n_verts == 0 || c->n_loops == 0) return hatch_too_small(a->P, -125) ? fail(GSDF_ERR_BAD_ARGUMENT, kHatchSmallText) : GSDF_OK;
+  a->loops = true;
+  if (int rc = job.open()) return rc;
+  if (!dev_alloc(w.maxbits, 1)) return fail(GSDF_ERR_HIP, k ? kSkinNoMem : kHatchNoMem);
+  if (int rc = hatch_ranges(c, job, w, a, ms)) return rc;
+  a->slot_base.assign((size_t)L + 1, 0u);
+  a->k_min.assign(L, 0);
   uint64_t S = 0;
-  for (size_t l = 0; l < L; l++) {
-    slot_base[l] = (unsigned)S;
-    if (h_acc[l].k_min <= h_acc[l].k_max) {
-      k_min[l] = h_acc[l].k_min;
-      S += (uint64_t)((int64_t)h_acc[l].k_max - (int64_t)h_acc[l].k_min + 1);
+  for (uint32_t l = 0; l < L; l++) {
+    const HatchLayerAcc& r = a->own[l];
+    a->slot_base[l] = (unsigned)S;
+    if (r.k_min <= r.k_max) {
+      a->k_min[l] = r.k_min;
+      S += (uint64_t)((int64_t)r.k_max - (int64_t)r.k_min + 1);
+      if (!k) a->h->layers[l].k_min = r.k_min, a->h->layers[l].k_max = r.k_max;
     }
     if (S >= ((uint64_t)1 << 31)) return fail(GSDF_ERR_CAPACITY, "hatch: 2^31 line slots or more");
   }
-  slot_base[L] = (unsigned)S;
-  *n_slots = S;
+  a->slot_base[L] = (unsigned)S;
+  a->n_slots = S;
   return GSDF_OK;
 }
+
+// The tail of both: fixed-point sums of segment lengths (two words each: low 32 bits summed, the signed rest summed) added up as
+// integers, then float64 at exponent e with one rounding, times the inverse power of two (exact).
+struct LengthSum {
+  __int128 t = 0;
+  LengthSum& add(const unsigned long long sum[2]) { t += mass::whole(sum[0], sum[1]); return *this; }
+  double at(int e) const { return mass::value(t, 58 - e); }
+};
 }  // namespace
 extern "C" double gsdf_hip_hatch_rank_ms(void) { return g_hatch_rank_ms; }
 
@@ -749,106 +830,74 @@ extern "C" int gsdf_hip_contour_hatch(const gsdf_contour* c, const gsdf_hatch_op
   if (out) *out = nullptr;
   g_hatch_rank_ms = 0;
   if (!c || !o) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
-  HatchParams P{};
-  if (int rc = hatch_params(o, out, &P)) return rc;
-  const bool dry = o->dry != 0;
-  const uint64_t V = c->n_verts, NL = c->n_loops;
+  const uint64_t V = c->n_verts;
   const uint32_t L = c->st.n_layers;
   gsdf_hatch_stats st{};
   st.n_layers = L;
-  HatchPtr h(new (std::nothrow) gsdf_hatch());
-  if (!h) return fail(GSDF_ERR_BAD_ARGUMENT, "out of memory");
-  h->device = c->device;
-  h->n_layers = L;
-  h->layer_start.assign((size_t)L + 1, 0u);
-  h->layers.assign(L, gsdf_hatch_layer{0.0, 0, 0, -1});
-
-  HIP_TRY(hipSetDevice(c->device));
-  if (V == 0 || NL == 0) {
-    if (hatch_too_small(P, -125)) return fail(GSDF_ERR_BAD_ARGUMENT, kHatchSmallText);
-  } else {
-    Stream stream;  // (ahead of the workspace: the work on it is over before the buffers go, and it goes last)
-    HIP_TRY(stream.ensure());
-    hipStream_t s = stream.s;
-    HatchWs w;
-    const char* nomem = kHatchNoMem;
-    if (!dev_alloc(w.maxbits, 1)) return fail(GSDF_ERR_HIP, nomem);
-    if (w.ev.ensure() != hipSuccess) return fail(GSDF_ERR_HIP, "hipEventCreate failed");
-    StreamDrain drain{s};
-    auto interval_ms = [&](int a, int b) { return event_ms(w.ev[a], w.ev[b]); };
-    int e = 0;
-    uint64_t N = 0;
-    std::vector<HatchLayerAcc> h_acc;
+  HatchOpening a;
+  Stream stream;
+  HatchWs w;
+  Job job(stream);
+  if (int rc = hatch_open(c, o, nullptr, out, job, w, &a, &st.ms_device)) return rc;
+  gsdf_hatch* h = a.h.get();
+  const HatchParams& P = a.P;
+  const uint64_t N = a.n_own, S = a.n_slots;
+  if (N > 0) {
+    hipStream_t s = job.s;
+    std::vector<HatchLayerAcc>& h_acc = a.own;  // (the ranges are used up: the layers' sums come into it)
     HatchCounters h_ctr{};
-    if (int rc = hatch_ranges(c, P, s, w, &e, h_acc, &N, &st.ms_device)) return rc;
-    std::vector<unsigned> h_slot_base;
-    std::vector<int> h_kmin;
-    uint64_t S = 0;
-    if (int rc = hatch_slots(h_acc, h_slot_base, h_kmin, &S)) return rc;
-    for (uint32_t l = 0; l < L; l++)
-      if (h_acc[l].k_min <= h_acc[l].k_max) {
-        h->layers[l].k_min = h_acc[l].k_min;
-        h->layers[l].k_max = h_acc[l].k_max;
-      }
-    if (N > 0) {
-      if ((N & 1) || S == 0) return fail(GSDF_ERR_HIP, "hatch: internal error (an odd number of crossings)");
-      const uint64_t NS = N / 2;
-      // 2. crossings per line slot, the buckets' starts
-      const unsigned nb_x = blocks_of(N), nb_s = blocks_of(S);
-      if (!dev_alloc(w.line_cnt, S) || !dev_alloc(w.line_start, S + 1) || !dev_alloc(w.cursor, S) || !dev_alloc(w.cross_edge, N) || !dev_alloc(w.cross_slot, N) ||
-          !dev_alloc(w.blk_cnt, nb_s) || !dev_alloc(w.blk_base, nb_s) || !dev_alloc(w.rec_u, N) || !dev_alloc(w.rec_j, N) || !dev_alloc(w.rec_xy, 2 * N) ||
-          !dev_alloc(w.rec_slot, N) || !dev_alloc(w.rec_k, N) || !dev_alloc(w.u_sorted, N))
-        return fail(GSDF_ERR_HIP, nomem);
-      if (!dev_alloc(h->seg, 4 * NS) || !dev_alloc(h->line, NS)) return fail(GSDF_ERR_HIP, "hatch: no device memory for the result");
-      HIP_TRY(hipMemcpyAsync(w.slot_base.p, h_slot_base.data(), ((size_t)L + 1) * 4, hipMemcpyHostToDevice, s));
-      HIP_TRY(hipMemcpyAsync(w.layer_kmin.p, h_kmin.data(), (size_t)L * 4, hipMemcpyHostToDevice, s));
-      HIP_TRY(hipEventRecord(w.ev[2], s));
-      HIP_TRY(hipMemsetAsync(w.line_cnt.p, 0, (size_t)S * 4, s));
-      HIP_TRY(hipMemsetAsync(w.cursor.p, 0, (size_t)S * 4, s));
-      HIP_TRY(hipMemsetAsync(w.rec_slot.p, 0xff, (size_t)N * 4, s));
-      LAUNCH(hatch_count_kernel, nb_x, s, (const unsigned*)w.edge_off.p, (unsigned)V, (const int*)w.k_first.p, (const unsigned*)w.loop_of.p, (const unsigned*)c->loop_layer.p,
-             (const unsigned*)w.slot_base.p, (const int*)w.layer_kmin.p, (unsigned)L, (unsigned)S, (unsigned)N, w.cross_edge.p, w.cross_slot.p, w.line_cnt.p, w.ctr.p);
-      LAUNCH(hatch_lines_kernel, nb_s, s, (const unsigned*)w.line_cnt.p, (unsigned)S, w.blk_cnt.p, w.ctr.p);
-      if (int rc = launch_block_scan(w.blk_cnt.p, nb_s, w.blk_base.p, w.total.p, s)) return rc;
-      LAUNCH(hatch_scan_kernel, nb_s, s, (const unsigned*)w.line_cnt.p, (unsigned)S, (const unsigned*)w.blk_base.p, w.line_start.p);
-      // 3. records into their buckets, 4. each to its rank; the layers' starts and lengths
-      LAUNCH(hatch_emit_kernel, nb_x, s, (const float*)c->xy.p, (const unsigned*)c->loop_start.p, (const unsigned*)w.loop_of.p, (const unsigned*)c->loop_layer.p, P,
-             (const unsigned*)w.edge_off.p, (const int*)w.k_first.p, (const unsigned*)w.cross_edge.p, (const unsigned*)w.cross_slot.p, (const unsigned*)w.line_start.p, (unsigned)S,
-             (unsigned)N, w.cursor.p, w.rec_u.p, w.rec_j.p, w.rec_xy.p, w.rec_slot.p, w.rec_k.p, w.ctr.p);
-      HIP_TRY(hipEventRecord(w.ev[3], s));
-      LAUNCH(hatch_rank_kernel, nb_x, s, (const double*)w.rec_u.p, (const unsigned*)w.rec_j.p, (const float*)w.rec_xy.p, (const unsigned*)w.rec_slot.p, (const int*)w.rec_k.p,
-             (const unsigned*)w.line_start.p, (unsigned)S, (unsigned)N, h->seg.p, h->line.p, w.u_sorted.p, w.ctr.p);
-      HIP_TRY(hipEventRecord(w.ev[4], s));
-      LAUNCH(hatch_layer_start_kernel, blocks_of((uint64_t)L + 1), s, (const unsigned*)w.line_start.p, (const unsigned*)w.slot_base.p, (unsigned)L, w.layer_start.p);
-      LAUNCH(hatch_length_kernel, blocks_of(NS), s, (const double*)w.u_sorted.p, (const unsigned*)h->seg.p, (const unsigned*)w.layer_start.p, (unsigned)L, (unsigned)NS,
-             (const unsigned long long*)w.maxbits.p, w.acc.p, w.ctr.p);
-      HIP_TRY(hipEventRecord(w.ev[5], s));
-      HIP_TRY(hipMemcpyAsync(&h_ctr, w.ctr.p, sizeof h_ctr, hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipMemcpyAsync(h_acc.data(), w.acc.p, (size_t)L * sizeof(HatchLayerAcc), hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipMemcpyAsync(h->layer_start.data(), w.layer_start.p, ((size_t)L + 1) * 4, hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipStreamSynchronize(s));
-      st.ms_device += interval_ms(2, 3) + interval_ms(3, 4) + interval_ms(4, 5);
-      g_hatch_rank_ms = interval_ms(3, 4);
-      if (h_ctr.bad || h->layer_start[L] != NS) return fail(GSDF_ERR_HIP, "hatch: internal error (a line with an odd number of crossings, or a record out of range)");
-      h->n_segments = NS;
-      st.n_segments = NS;
-      st.n_crossings = N;
-      st.n_lines = h_ctr.n_lines;
-      st.max_line_crossings = h_ctr.max_line;
-      st.zero_length = h_ctr.zero_length;
-      // integers -> float64 with one rounding each, times the inverse power of two (exact)
-      __int128 all = 0;
-      for (uint32_t l = 0; l < L; l++) {
-        const __int128 sum = (__int128)(long long)h_acc[l].sum[1] * ((__int128)1 << 32) + (__int128)h_acc[l].sum[0];
-        all += sum;
-        h->layers[l].length = std::ldexp((double)sum, e - 58);
-        h->layers[l].n_segments = h->layer_start[l + 1] - h->layer_start[l];
-      }
-      st.length = std::ldexp((double)all, e - 58);
+    if ((N & 1) || S == 0) return fail(GSDF_ERR_HIP, "hatch: internal error (an odd number of crossings)");
+    const uint64_t NS = N / 2;
+    // 2. crossings per line slot, the buckets' starts
+    const unsigned nb_x = blocks_of(N), nb_s = blocks_of(S);
+    if (!dev_alloc(w.line_cnt, S) || !dev_alloc(w.line_start, S + 1) || !dev_alloc(w.cursor, S) || !dev_alloc(w.cross_edge, N) || !dev_alloc(w.cross_slot, N) ||
+        !dev_alloc(w.blk_cnt, nb_s) || !dev_alloc(w.blk_base, nb_s) || !dev_alloc(w.rec_u, N) || !dev_alloc(w.rec_j, N) || !dev_alloc(w.rec_xy, 2 * N) ||
+        !dev_alloc(w.rec_slot, N) || !dev_alloc(w.rec_k, N) || !dev_alloc(w.u_sorted, N))
+      return fail(GSDF_ERR_HIP, kHatchNoMem);
+    if (!dev_alloc(h->seg, 4 * NS) || !dev_alloc(h->line, NS)) return fail(GSDF_ERR_HIP, "hatch: no device memory for the result");
+    HIP_TRY(hipMemcpyAsync(w.slot_base.p, a.slot_base.data(), ((size_t)L + 1) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(w.layer_kmin.p, a.k_min.data(), (size_t)L * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(job.ev[2], s));
+    HIP_TRY(hipMemsetAsync(w.line_cnt.p, 0, (size_t)S * 4, s));
+    HIP_TRY(hipMemsetAsync(w.cursor.p, 0, (size_t)S * 4, s));
+    HIP_TRY(hipMemsetAsync(w.rec_slot.p, 0xff, (size_t)N * 4, s));
+    LAUNCH(hatch_count_kernel, nb_x, s, w.edge_off.p, (unsigned)V, w.k_first.p, w.loop_of.p, c->loop_layer.p, w.slot_base.p, w.layer_kmin.p, (unsigned)L, (unsigned)S, (unsigned)N,
+           w.cross_edge.p, w.cross_slot.p, w.line_cnt.p, w.ctr.p);
+    LAUNCH(hatch_lines_kernel, nb_s, s, w.line_cnt.p, (unsigned)S, w.blk_cnt.p, w.ctr.p);
+    if (int rc = scan_offsets(w.line_cnt.p, S, w.blk_cnt.p, w.blk_base.p, w.total.p, w.line_start.p, s)) return rc;
+    // 3. records into their buckets, 4. each to its rank; the layers' starts and lengths
+    LAUNCH(hatch_emit_kernel, nb_x, s, c->xy.p, c->loop_start.p, w.loop_of.p, c->loop_layer.p, P, w.edge_off.p, w.k_first.p, w.cross_edge.p, w.cross_slot.p, w.line_start.p,
+           (unsigned)S, (unsigned)N, w.cursor.p, w.rec_u.p, w.rec_j.p, w.rec_xy.p, w.rec_slot.p, w.rec_k.p, w.ctr.p);
+    HIP_TRY(hipEventRecord(job.ev[3], s));
+    LAUNCH(hatch_rank_kernel, nb_x, s, w.rec_u.p, w.rec_j.p, w.rec_xy.p, w.rec_slot.p, w.rec_k.p, w.line_start.p, (unsigned)S, (unsigned)N, h->seg.p, h->line.p, w.u_sorted.p,
+           w.ctr.p);
+    HIP_TRY(hipEventRecord(job.ev[4], s));
+    LAUNCH(hatch_layer_start_kernel, blocks_of((uint64_t)L + 1), s, w.line_start.p, w.slot_base.p, (unsigned)L, w.layer_start.p);
+    LAUNCH(hatch_length_kernel, blocks_of(NS), s, w.u_sorted.p, (const unsigned*)h->seg.p, w.layer_start.p, (unsigned)L, (unsigned)NS, w.maxbits.p, w.acc.p, w.ctr.p);
+    HIP_TRY(hipEventRecord(job.ev[5], s));
+    HIP_TRY(hipMemcpyAsync(&h_ctr, w.ctr.p, sizeof h_ctr, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h_acc.data(), w.acc.p, (size_t)L * sizeof(HatchLayerAcc), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h->layer_start.data(), w.layer_start.p, ((size_t)L + 1) * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    st.ms_device += job.ms(2, 3) + job.ms(3, 4) + job.ms(4, 5);
+    g_hatch_rank_ms = job.ms(3, 4);
+    if (h_ctr.bad || h->layer_start[L] != NS) return fail(GSDF_ERR_HIP, "hatch: internal error (a line with an odd number of crossings, or a record out of range)");
+    h->n_segments = NS;
+    st.n_segments = NS;
+    st.n_crossings = N;
+    st.n_lines = h_ctr.n_lines;
+    st.max_line_crossings = h_ctr.max_line;
+    st.zero_length = h_ctr.zero_length;
+    LengthSum all;
+    for (uint32_t l = 0; l < L; l++) {
+      all.add(h_acc[l].sum);
+      h->layers[l].length = LengthSum().add(h_acc[l].sum).at(a.e);
+      h->layers[l].n_segments = h->layer_start[l + 1] - h->layer_start[l];
     }
+    st.length = all.at(a.e);
   }
   if (st_out) *st_out = st;
-  if (!dry) *out = h.release();
+  if (o->dry == 0) *out = a.h.release();
   return GSDF_OK;
 }
 
@@ -865,7 +914,6 @@ struct SkinWs {
   DevPtr<float> rec_xy, xy_sorted;
   DevPtr<double> u_sorted;
   DevPtr<unsigned char> flag;
-  EventSet<8> ev;
 };
 thread_local double g_skin_rank_ms = 0;
 }  // namespace
@@ -875,174 +923,141 @@ extern "C" int gsdf_hip_contour_hatch_skin(const gsdf_contour* c, const gsdf_hat
   if (out) *out = nullptr;
   g_skin_rank_ms = 0;
   if (!c || !o || !k) return fail(GSDF_ERR_BAD_ARGUMENT, "null argument");
-  HatchParams P{};
-  if (int rc = hatch_params(o, out, &P)) return rc;
-  if (k->below > SKIN_MAX_WINDOW || k->above > SKIN_MAX_WINDOW) return fail(GSDF_ERR_BAD_ARGUMENT, "skin: below and above must be 0 .. 8");
+  const uint64_t V = c->n_verts;
+  const uint32_t L = c->st.n_layers;
+  gsdf_skin_stats st{};
+  st.n_layers = L;
+  st.below = k->below;
+  st.above = k->above;
+  HatchOpening a;
+  Stream stream;
+  SkinWs w;
+  Job job(stream);
+  // 0, 1. the exponent and the layers' own line ranges: the hatch's range pass
+  if (int rc = hatch_open(c, o, k, out, job, w.own, &a, &st.ms_device)) return rc;
+  gsdf_hatch* h = a.h.get();
+  const HatchParams& P = a.P;
   SkinParams K{};
   K.below = k->below;
   K.above = k->above;
   K.n_src = 1u + k->below + k->above;
   K.need_below = ((1u << k->below) - 1u) << 1;
   K.need_above = ((1u << k->above) - 1u) << (1u + k->below);
-  const bool dry = o->dry != 0;
-  const uint64_t V = c->n_verts, NL = c->n_loops;
-  const uint32_t L = c->st.n_layers;
-  gsdf_skin_stats st{};
-  st.n_layers = L;
-  st.below = k->below;
-  st.above = k->above;
-  HatchPtr h(new (std::nothrow) gsdf_hatch());
-  if (!h) return fail(GSDF_ERR_BAD_ARGUMENT, "out of memory");
-  h->device = c->device;
-  h->n_layers = L;
-  h->layer_start.assign((size_t)L + 1, 0u);
-  h->layers.assign(L, gsdf_hatch_layer{0.0, 0, 0, -1});
-  h->has_classes = true;
-  h->skin_layers.assign(L, gsdf_skin_layer{});
-
-  HIP_TRY(hipSetDevice(c->device));
-  if (V == 0 || NL == 0) {
-    if (hatch_too_small(P, -125)) return fail(GSDF_ERR_BAD_ARGUMENT, kHatchSmallText);
-  } else {
-    Stream stream;  // (ahead of the workspace: the work on it is over before the buffers go, and it goes last)
-    HIP_TRY(stream.ensure());
-    hipStream_t s = stream.s;
-    SkinWs w;
-    const char* nomem = "skin: no device memory for the workspace";
-    if (!dev_alloc(w.own.maxbits, 1)) return fail(GSDF_ERR_HIP, nomem);
-    if (w.own.ev.ensure() != hipSuccess || w.ev.ensure() != hipSuccess) return fail(GSDF_ERR_HIP, "hipEventCreate failed");
-    StreamDrain drain{s};
-    auto interval_ms = [&](int a, int b) { return event_ms(w.ev[a], w.ev[b]); };
-    // 0, 1. the exponent and the layers' own line ranges: the hatch's range pass
-    int e = 0;
-    uint64_t n_own = 0, S = 0;
-    std::vector<HatchLayerAcc> own_acc;
-    if (int rc = hatch_ranges(c, P, s, w.own, &e, own_acc, &n_own, &st.ms_device)) return rc;
-    std::vector<unsigned> h_slot_base;
-    std::vector<int> h_kmin, h_kmax(L, -1);
-    if (int rc = hatch_slots(own_acc, h_slot_base, h_kmin, &S)) return rc;
+  const uint64_t n_own = a.n_own, S = a.n_slots, n_pairs = V * K.n_src;
+  if (a.loops && n_pairs >= ((uint64_t)1 << 32)) return fail(GSDF_ERR_CAPACITY, "skin: 2^32 (edge, source layer) pairs or more");
+  if (n_own > 0) {
+    hipStream_t s = job.s;
+    const int e = a.e;
+    const char* nomem = kSkinNoMem;
+    std::vector<int> h_kmax(L, -1);
     for (uint32_t l = 0; l < L; l++)
-      if (own_acc[l].k_min <= own_acc[l].k_max) h_kmax[l] = own_acc[l].k_max;
-    const uint64_t n_pairs = V * K.n_src;
-    if (n_pairs >= ((uint64_t)1 << 32)) return fail(GSDF_ERR_CAPACITY, "skin: 2^32 (edge, source layer) pairs or more");
-    if (n_own > 0) {
-      if ((n_own & 1) || S == 0) return fail(GSDF_ERR_HIP, "skin: internal error (an odd number of crossings)");
-      // 2. every (edge, source number)'s lines inside the target's own range, their offsets
-      const unsigned nb_p = blocks_of(n_pairs), nb_s = blocks_of(S);
-      if (!dev_alloc(w.layer_kmax, L) || !dev_alloc(w.k_first, n_pairs) || !dev_alloc(w.cnt, n_pairs) || !dev_alloc(w.pair_off, n_pairs + 1) || !dev_alloc(w.blk_cnt, nb_p) ||
-          !dev_alloc(w.blk_base, nb_p) || !dev_alloc(w.acc, L) || !dev_alloc(w.ctr, 1))
-        return fail(GSDF_ERR_HIP, nomem);
-      SkinCounters h_ctr{};
-      HIP_TRY(hipMemcpyAsync(w.own.slot_base.p, h_slot_base.data(), ((size_t)L + 1) * 4, hipMemcpyHostToDevice, s));
-      HIP_TRY(hipMemcpyAsync(w.own.layer_kmin.p, h_kmin.data(), (size_t)L * 4, hipMemcpyHostToDevice, s));
-      HIP_TRY(hipMemcpyAsync(w.layer_kmax.p, h_kmax.data(), (size_t)L * 4, hipMemcpyHostToDevice, s));
-      HIP_TRY(hipEventRecord(w.ev[0], s));
-      HIP_TRY(hipMemsetAsync(w.ctr.p, 0, sizeof(SkinCounters), s));
-      LAUNCH(skin_init_kernel, blocks_of(L), s, w.acc.p, (unsigned)L);
-      LAUNCH(skin_range_kernel, nb_p, s, (const float*)c->xy.p, (const unsigned*)c->loop_start.p, (const unsigned*)w.own.loop_of.p, (const unsigned*)c->loop_layer.p, (unsigned)V,
-             (unsigned)L, P, K, (const int*)w.own.layer_kmin.p, (const int*)w.layer_kmax.p, w.k_first.p, w.cnt.p, w.blk_cnt.p, w.ctr.p);
-      if (int rc = launch_block_scan(w.blk_cnt.p, nb_p, w.blk_base.p, w.own.total.p, s)) return rc;
-      LAUNCH(hatch_scan_kernel, nb_p, s, (const unsigned*)w.cnt.p, (unsigned)n_pairs, (const unsigned*)w.blk_base.p, w.pair_off.p);
-      HIP_TRY(hipEventRecord(w.ev[1], s));
-      HIP_TRY(hipMemcpyAsync(&h_ctr, w.ctr.p, sizeof h_ctr, hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipStreamSynchronize(s));
-      st.ms_device += interval_ms(0, 1);
-      if (h_ctr.bad) return fail(GSDF_ERR_HIP, "skin: internal error (a loop names a layer the handle does not have)");
-      const uint64_t N = h_ctr.n_cand;
-      if (N >= ((uint64_t)1 << 32)) return fail(GSDF_ERR_CAPACITY, "skin: 2^32 crossings or more");
-      if (N < n_own) return fail(GSDF_ERR_HIP, "skin: internal error (fewer crossings than the layers' own)");
-      // 3. crossings per line slot (slots without an own crossing emptied), the buckets' starts; 4. records into their buckets
-      const unsigned nb_x = blocks_of(N);
-      if (!dev_alloc(w.line_cnt, S) || !dev_alloc(w.own_cnt, S) || !dev_alloc(w.line_start, S + 1) || !dev_alloc(w.cursor, S) || !dev_alloc(w.cross_pair, N) ||
-          !dev_alloc(w.cross_slot, N) || !dev_alloc(w.blk_cnt, nb_s > nb_x ? nb_s : nb_x) || !dev_alloc(w.blk_base, nb_s > nb_x ? nb_s : nb_x) || !dev_alloc(w.blk_cnt2, nb_x) ||
-          !dev_alloc(w.blk_base2, nb_x) || !dev_alloc(w.rec, N) || !dev_alloc(w.rec_xy, 2 * N) || !dev_alloc(w.rec_slot, N) || !dev_alloc(w.rec_k, N) ||
-          !dev_alloc(w.u_sorted, N) || !dev_alloc(w.xy_sorted, 2 * N) || !dev_alloc(w.flag, N) || !dev_alloc(w.bnd_off, N) || !dev_alloc(w.piece_off, N + 1) ||
-          !dev_alloc(w.bnd_pos, N))
-        return fail(GSDF_ERR_HIP, nomem);
-      HIP_TRY(hipEventRecord(w.ev[2], s));
-      HIP_TRY(hipMemsetAsync(w.line_cnt.p, 0, (size_t)S * 4, s));
-      HIP_TRY(hipMemsetAsync(w.own_cnt.p, 0, (size_t)S * 4, s));
-      HIP_TRY(hipMemsetAsync(w.cursor.p, 0, (size_t)S * 4, s));
-      HIP_TRY(hipMemsetAsync(w.rec_slot.p, 0xff, (size_t)N * 4, s));
-      HIP_TRY(hipMemsetAsync(w.flag.p, 0, (size_t)N, s));
-      HIP_TRY(hipMemsetAsync(w.piece_off.p, 0, ((size_t)N + 1) * 4, s));
-      LAUNCH(skin_count_kernel, nb_x, s, (const unsigned*)w.pair_off.p, (unsigned)n_pairs, (unsigned)V, (const int*)w.k_first.p, (const unsigned*)w.own.loop_of.p,
-             (const unsigned*)c->loop_layer.p, K, (const unsigned*)w.own.slot_base.p, (const int*)w.own.layer_kmin.p, (unsigned)L, (unsigned)S, (unsigned)N, w.cross_pair.p,
-             w.cross_slot.p, w.line_cnt.p, w.own_cnt.p, w.ctr.p);
-      LAUNCH(skin_lines_kernel, nb_s, s, w.line_cnt.p, (const unsigned*)w.own_cnt.p, (unsigned)S, w.blk_cnt.p, w.ctr.p);
-      if (int rc = launch_block_scan(w.blk_cnt.p, nb_s, w.blk_base.p, w.own.total.p, s)) return rc;
-      LAUNCH(hatch_scan_kernel, nb_s, s, (const unsigned*)w.line_cnt.p, (unsigned)S, (const unsigned*)w.blk_base.p, w.line_start.p);
-      LAUNCH(skin_emit_kernel, nb_x, s, (const float*)c->xy.p, (const unsigned*)c->loop_start.p, (const unsigned*)w.own.loop_of.p, (const unsigned*)c->loop_layer.p, P, K,
-             (unsigned)V, (unsigned)L, (const unsigned*)w.pair_off.p, (const int*)w.k_first.p, (const unsigned*)w.cross_pair.p, (const unsigned*)w.cross_slot.p,
-             (const unsigned*)w.line_start.p, (unsigned)S, (unsigned)N, w.cursor.p, w.rec.p, w.rec_xy.p, w.rec_slot.p, w.rec_k.p, w.ctr.p);
-      // 5. each record to its rank, the sources' parity around it; 6. boundaries and pieces numbered
-      HIP_TRY(hipEventRecord(w.ev[3], s));
-      LAUNCH(skin_rank_kernel, nb_x, s, (const SkinRec*)w.rec.p, (const float*)w.rec_xy.p, (const unsigned*)w.rec_slot.p, (const unsigned*)w.line_start.p, (unsigned)S, (unsigned)N, K,
-             w.u_sorted.p, w.xy_sorted.p, w.flag.p, w.ctr.p);
-      HIP_TRY(hipEventRecord(w.ev[4], s));
-      LAUNCH(skin_flags_kernel, nb_x, s, (const unsigned char*)w.flag.p, (const unsigned*)w.line_start.p, (unsigned)S, (unsigned)N, w.blk_cnt.p, w.blk_cnt2.p, w.ctr.p);
-      if (int rc = launch_block_scan(w.blk_cnt.p, nb_x, w.blk_base.p, w.own.total.p, s)) return rc;
-      if (int rc = launch_block_scan(w.blk_cnt2.p, nb_x, w.blk_base2.p, w.own.total.p, s)) return rc;
-      LAUNCH(skin_compact_kernel, nb_x, s, (const unsigned char*)w.flag.p, (const unsigned*)w.line_start.p, (unsigned)S, (unsigned)N, (const unsigned*)w.blk_base.p,
-             (const unsigned*)w.blk_base2.p, w.bnd_off.p, w.piece_off.p, w.bnd_pos.p, w.ctr.p);
-      LAUNCH(skin_layer_start_kernel, blocks_of((uint64_t)L + 1), s, (const unsigned*)w.line_start.p, (const unsigned*)w.own.slot_base.p, (const unsigned*)w.piece_off.p, (unsigned)L,
-             (unsigned)S, (unsigned)N, w.own.layer_start.p);
-      HIP_TRY(hipEventRecord(w.ev[5], s));
-      HIP_TRY(hipMemcpyAsync(&h_ctr, w.ctr.p, sizeof h_ctr, hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipMemcpyAsync(h->layer_start.data(), w.own.layer_start.p, ((size_t)L + 1) * 4, hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipStreamSynchronize(s));
-      st.ms_device += interval_ms(2, 3) + interval_ms(3, 4) + interval_ms(4, 5);
-      g_skin_rank_ms = interval_ms(3, 4);
-      const uint64_t NB = h_ctr.n_bnd, NS = h_ctr.n_pieces;
-      if (h_ctr.bad || h_ctr.n_own != n_own || NB > N || NS > NB || h->layer_start[L] != NS)
-        return fail(GSDF_ERR_HIP, "skin: internal error (a line with an odd number of crossings, or a record out of range)");
-      // 7. the pieces: end points, classes, lengths by (layer, class)
-      if (!dev_alloc(h->seg, 4 * NS) || !dev_alloc(h->line, NS) || !dev_alloc(h->cls, NS)) return fail(GSDF_ERR_HIP, "skin: no device memory for the result");
-      std::vector<SkinLayerAcc> h_acc(L);
-      HIP_TRY(hipEventRecord(w.ev[6], s));
-      LAUNCH(skin_piece_kernel, nb_x, s, (const unsigned char*)w.flag.p, (const double*)w.u_sorted.p, (const unsigned*)w.xy_sorted.p, (const unsigned*)w.rec_slot.p, (const int*)w.rec_k.p,
-             (const unsigned*)w.line_start.p, (const unsigned*)w.own.slot_base.p, (unsigned)L, (unsigned)S, (unsigned)N, (const unsigned*)w.bnd_off.p, (const unsigned*)w.piece_off.p,
-             (const unsigned*)w.bnd_pos.p, (unsigned)NB, (unsigned)NS, (const unsigned long long*)w.own.maxbits.p, (unsigned*)h->seg.p, h->line.p, h->cls.p, w.acc.p, w.ctr.p);
-      HIP_TRY(hipEventRecord(w.ev[7], s));
-      HIP_TRY(hipMemcpyAsync(&h_ctr, w.ctr.p, sizeof h_ctr, hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipMemcpyAsync(h_acc.data(), w.acc.p, (size_t)L * sizeof(SkinLayerAcc), hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipStreamSynchronize(s));
-      st.ms_device += interval_ms(6, 7);
-      if (h_ctr.bad) return fail(GSDF_ERR_HIP, "skin: internal error (a line that does not end outside, or a piece out of range)");
-      h->n_segments = NS;
-      st.n_segments = NS;
-      st.n_crossings = h_ctr.n_crossings;
-      st.n_own_crossings = h_ctr.n_own;
-      st.n_lines = h_ctr.n_lines;
-      st.max_line_crossings = h_ctr.max_line;
-      st.zero_length = h_ctr.zero_length;
-      // integers -> float64 with one rounding each, times the inverse power of two (exact)
-      __int128 all[4] = {0, 0, 0, 0};
-      for (uint32_t l = 0; l < L; l++) {
-        __int128 layer_sum = 0;
-        uint64_t layer_n = 0;
-        for (int q = 0; q < 4; q++) {
-          const __int128 sum = (__int128)(long long)h_acc[l].sum[q][1] * ((__int128)1 << 32) + (__int128)h_acc[l].sum[q][0];
-          all[q] += sum;
-          layer_sum += sum;
-          layer_n += h_acc[l].n[q];
-          st.n_class[q] += h_acc[l].n[q];
-          h->skin_layers[l].length[q] = std::ldexp((double)sum, e - 58);
-          h->skin_layers[l].n_segments[q] = h_acc[l].n[q];
-        }
-        if (layer_n != (uint64_t)h->layer_start[l + 1] - h->layer_start[l]) return fail(GSDF_ERR_HIP, "skin: internal error (a layer's pieces and its classes' counts differ)");
-        h->layers[l].length = std::ldexp((double)layer_sum, e - 58);
-        h->layers[l].n_segments = layer_n;
-        if (h_acc[l].k_min <= h_acc[l].k_max) {
-          h->layers[l].k_min = h_acc[l].k_min;
-          h->layers[l].k_max = h_acc[l].k_max;
-        }
+      if (a.own[l].k_min <= a.own[l].k_max) h_kmax[l] = a.own[l].k_max;
+    if ((n_own & 1) || S == 0) return fail(GSDF_ERR_HIP, "skin: internal error (an odd number of crossings)");
+    // 2. every (edge, source number)'s lines inside the target's own range, their offsets
+    const unsigned nb_p = blocks_of(n_pairs), nb_s = blocks_of(S);
+    if (!dev_alloc(w.layer_kmax, L) || !dev_alloc(w.k_first, n_pairs) || !dev_alloc(w.cnt, n_pairs) || !dev_alloc(w.pair_off, n_pairs + 1) || !dev_alloc(w.blk_cnt, nb_p) ||
+        !dev_alloc(w.blk_base, nb_p) || !dev_alloc(w.acc, L) || !dev_alloc(w.ctr, 1))
+      return fail(GSDF_ERR_HIP, nomem);
+    SkinCounters h_ctr{};
+    HIP_TRY(hipMemcpyAsync(w.own.slot_base.p, a.slot_base.data(), ((size_t)L + 1) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(w.own.layer_kmin.p, a.k_min.data(), (size_t)L * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(w.layer_kmax.p, h_kmax.data(), (size_t)L * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(job.ev[0], s));
+    HIP_TRY(hipMemsetAsync(w.ctr.p, 0, sizeof(SkinCounters), s));
+    LAUNCH(skin_init_kernel, blocks_of(L), s, w.acc.p, (unsigned)L);
+    LAUNCH(skin_range_kernel, nb_p, s, c->xy.p, c->loop_start.p, w.own.loop_of.p, c->loop_layer.p, (unsigned)V, (unsigned)L, P, K, w.own.layer_kmin.p, w.layer_kmax.p, w.k_first.p,
+           w.cnt.p, w.blk_cnt.p, w.ctr.p);
+    if (int rc = scan_offsets(w.cnt.p, n_pairs, w.blk_cnt.p, w.blk_base.p, w.own.total.p, w.pair_off.p, s)) return rc;
+    HIP_TRY(hipEventRecord(job.ev[1], s));
+    HIP_TRY(hipMemcpyAsync(&h_ctr, w.ctr.p, sizeof h_ctr, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    st.ms_device += job.ms(0, 1);
+    if (h_ctr.bad) return fail(GSDF_ERR_HIP, "skin: internal error (a loop names a layer the handle does not have)");
+    const uint64_t N = h_ctr.n_cand;
+    if (N >= ((uint64_t)1 << 32)) return fail(GSDF_ERR_CAPACITY, "skin: 2^32 crossings or more");
+    if (N < n_own) return fail(GSDF_ERR_HIP, "skin: internal error (fewer crossings than the layers' own)");
+    // 3. crossings per line slot (slots without an own crossing emptied), the buckets' starts; 4. records into their buckets
+    const unsigned nb_x = blocks_of(N);
+    if (!dev_alloc(w.line_cnt, S) || !dev_alloc(w.own_cnt, S) || !dev_alloc(w.line_start, S + 1) || !dev_alloc(w.cursor, S) || !dev_alloc(w.cross_pair, N) ||
+        !dev_alloc(w.cross_slot, N) || !dev_alloc(w.blk_cnt, nb_s > nb_x ? nb_s : nb_x) || !dev_alloc(w.blk_base, nb_s > nb_x ? nb_s : nb_x) || !dev_alloc(w.blk_cnt2, nb_x) ||
+        !dev_alloc(w.blk_base2, nb_x) || !dev_alloc(w.rec, N) || !dev_alloc(w.rec_xy, 2 * N) || !dev_alloc(w.rec_slot, N) || !dev_alloc(w.rec_k, N) ||
+        !dev_alloc(w.u_sorted, N) || !dev_alloc(w.xy_sorted, 2 * N) || !dev_alloc(w.flag, N) || !dev_alloc(w.bnd_off, N) || !dev_alloc(w.piece_off, N + 1) ||
+        !dev_alloc(w.bnd_pos, N))
+      return fail(GSDF_ERR_HIP, nomem);
+    HIP_TRY(hipEventRecord(job.ev[2], s));
+    HIP_TRY(hipMemsetAsync(w.line_cnt.p, 0, (size_t)S * 4, s));
+    HIP_TRY(hipMemsetAsync(w.own_cnt.p, 0, (size_t)S * 4, s));
+    HIP_TRY(hipMemsetAsync(w.cursor.p, 0, (size_t)S * 4, s));
+    HIP_TRY(hipMemsetAsync(w.rec_slot.p, 0xff, (size_t)N * 4, s));
+    HIP_TRY(hipMemsetAsync(w.flag.p, 0, (size_t)N, s));
+    HIP_TRY(hipMemsetAsync(w.piece_off.p, 0, ((size_t)N + 1) * 4, s));
+    LAUNCH(skin_count_kernel, nb_x, s, w.pair_off.p, (unsigned)n_pairs, (unsigned)V, w.k_first.p, w.own.loop_of.p, c->loop_layer.p, K, w.own.slot_base.p, w.own.layer_kmin.p,
+           (unsigned)L, (unsigned)S, (unsigned)N, w.cross_pair.p, w.cross_slot.p, w.line_cnt.p, w.own_cnt.p, w.ctr.p);
+    LAUNCH(skin_lines_kernel, nb_s, s, w.line_cnt.p, w.own_cnt.p, (unsigned)S, w.blk_cnt.p, w.ctr.p);
+    if (int rc = scan_offsets(w.line_cnt.p, S, w.blk_cnt.p, w.blk_base.p, w.own.total.p, w.line_start.p, s)) return rc;
+    LAUNCH(skin_emit_kernel, nb_x, s, c->xy.p, c->loop_start.p, w.own.loop_of.p, c->loop_layer.p, P, K, (unsigned)V, (unsigned)L, w.pair_off.p, w.k_first.p, w.cross_pair.p,
+           w.cross_slot.p, w.line_start.p, (unsigned)S, (unsigned)N, w.cursor.p, w.rec.p, w.rec_xy.p, w.rec_slot.p, w.rec_k.p, w.ctr.p);
+    // 5. each record to its rank, the sources' parity around it; 6. boundaries and pieces numbered
+    HIP_TRY(hipEventRecord(job.ev[3], s));
+    LAUNCH(skin_rank_kernel, nb_x, s, w.rec.p, w.rec_xy.p, w.rec_slot.p, w.line_start.p, (unsigned)S, (unsigned)N, K, w.u_sorted.p, w.xy_sorted.p, w.flag.p, w.ctr.p);
+    HIP_TRY(hipEventRecord(job.ev[4], s));
+    LAUNCH(skin_flags_kernel, nb_x, s, w.flag.p, w.line_start.p, (unsigned)S, (unsigned)N, w.blk_cnt.p, w.blk_cnt2.p, w.ctr.p);
+    if (int rc = launch_block_scan(w.blk_cnt.p, nb_x, w.blk_base.p, w.own.total.p, s)) return rc;
+    if (int rc = launch_block_scan(w.blk_cnt2.p, nb_x, w.blk_base2.p, w.own.total.p, s)) return rc;
+    LAUNCH(skin_compact_kernel, nb_x, s, w.flag.p, w.line_start.p, (unsigned)S, (unsigned)N, w.blk_base.p, w.blk_base2.p, w.bnd_off.p, w.piece_off.p, w.bnd_pos.p, w.ctr.p);
+    LAUNCH(skin_layer_start_kernel, blocks_of((uint64_t)L + 1), s, w.line_start.p, w.own.slot_base.p, w.piece_off.p, (unsigned)L, (unsigned)S, (unsigned)N, w.own.layer_start.p);
+    HIP_TRY(hipEventRecord(job.ev[5], s));
+    HIP_TRY(hipMemcpyAsync(&h_ctr, w.ctr.p, sizeof h_ctr, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h->layer_start.data(), w.own.layer_start.p, ((size_t)L + 1) * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    st.ms_device += job.ms(2, 3) + job.ms(3, 4) + job.ms(4, 5);
+    g_skin_rank_ms = job.ms(3, 4);
+    const uint64_t NB = h_ctr.n_bnd, NS = h_ctr.n_pieces;
+    if (h_ctr.bad || h_ctr.n_own != n_own || NB > N || NS > NB || h->layer_start[L] != NS)
+      return fail(GSDF_ERR_HIP, "skin: internal error (a line with an odd number of crossings, or a record out of range)");
+    // 7. the pieces: end points, classes, lengths by (layer, class)
+    if (!dev_alloc(h->seg, 4 * NS) || !dev_alloc(h->line, NS) || !dev_alloc(h->cls, NS)) return fail(GSDF_ERR_HIP, "skin: no device memory for the result");
+    std::vector<SkinLayerAcc> h_acc(L);
+    HIP_TRY(hipEventRecord(job.ev[6], s));
+    LAUNCH(skin_piece_kernel, nb_x, s, w.flag.p, w.u_sorted.p, (const unsigned*)w.xy_sorted.p, w.rec_slot.p, w.rec_k.p, w.line_start.p, w.own.slot_base.p, (unsigned)L, (unsigned)S,
+           (unsigned)N, w.bnd_off.p, w.piece_off.p, w.bnd_pos.p, (unsigned)NB, (unsigned)NS, w.own.maxbits.p, (unsigned*)h->seg.p, h->line.p, h->cls.p, w.acc.p, w.ctr.p);
+    HIP_TRY(hipEventRecord(job.ev[7], s));
+    HIP_TRY(hipMemcpyAsync(&h_ctr, w.ctr.p, sizeof h_ctr, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h_acc.data(), w.acc.p, (size_t)L * sizeof(SkinLayerAcc), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    st.ms_device += job.ms(6, 7);
+    if (h_ctr.bad) return fail(GSDF_ERR_HIP, "skin: internal error (a line that does not end outside, or a piece out of range)");
+    h->n_segments = NS;
+    st.n_segments = NS;
+    st.n_crossings = h_ctr.n_crossings;
+    st.n_own_crossings = h_ctr.n_own;
+    st.n_lines = h_ctr.n_lines;
+    st.max_line_crossings = h_ctr.max_line;
+    st.zero_length = h_ctr.zero_length;
+    LengthSum all[4];
+    for (uint32_t l = 0; l < L; l++) {
+      LengthSum layer;
+      uint64_t layer_n = 0;
+      for (int q = 0; q < 4; q++) {
+        all[q].add(h_acc[l].sum[q]);
+        layer.add(h_acc[l].sum[q]);
+        layer_n += h_acc[l].n[q];
+        st.n_class[q] += h_acc[l].n[q];
+        h->skin_layers[l].length[q] = LengthSum().add(h_acc[l].sum[q]).at(e);
+        h->skin_layers[l].n_segments[q] = h_acc[l].n[q];
       }
-      for (int q = 0; q < 4; q++) st.length[q] = std::ldexp((double)all[q], e - 58);
+      if (layer_n != (uint64_t)h->layer_start[l + 1] - h->layer_start[l]) return fail(GSDF_ERR_HIP, "skin: internal error (a layer's pieces and its classes' counts differ)");
+      h->layers[l].length = layer.at(e);
+      h->layers[l].n_segments = layer_n;
+      if (h_acc[l].k_min <= h_acc[l].k_max) {
+        h->layers[l].k_min = h_acc[l].k_min;
+        h->layers[l].k_max = h_acc[l].k_max;
+      }
     }
+    for (int q = 0; q < 4; q++) st.length[q] = all[q].at(e);
   }
   if (st_out) *st_out = st;
-  if (!dry) *out = h.release();
+  if (o->dry == 0) *out = a.h.release();
   return GSDF_OK;
 }
 
@@ -1089,6 +1104,7 @@ struct OffsetPlan {
   unsigned tiles_x = 0, tiles_y = 0;
   OffsetInsets insets{};
 };
+const char* const kOffsetNoMem = "offset: no device memory for the workspace";
 
 int offset_check(const gsdf_offset_opts* o) {
   if (!std::isfinite(o->res) || !(o->res > 0.f)) return fail(GSDF_ERR_BAD_ARGUMENT, "offset: res must be finite and positive");
@@ -1108,15 +1124,12 @@ int offset_prepare(const gsdf_contour* c, const gsdf_offset_opts* o, hipStream_t
   if (V > 0) {
     const unsigned init[4] = {0xffffffffu, 0xffffffffu, 0u, 0u};
     unsigned h_bb[4];
-    if (!dev_alloc(ws.bb, 4)) return fail(GSDF_ERR_HIP, "offset: no device memory for the workspace");
+    if (!dev_alloc(ws.bb, 4)) return fail(GSDF_ERR_HIP, kOffsetNoMem);
     HIP_TRY(hipMemcpyAsync(ws.bb.p, init, sizeof init, hipMemcpyHostToDevice, s));
-    LAUNCH(offset_bbox_kernel, blocks_of(V), s, (const float*)c->xy.p, (unsigned)V, ws.bb.p);
+    LAUNCH(offset_bbox_kernel, blocks_of(V), s, c->xy.p, (unsigned)V, ws.bb.p);
     HIP_TRY(hipMemcpyAsync(h_bb, ws.bb.p, sizeof h_bb, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    for (int k = 0; k < 4; k++) {
-      const unsigned b = h_bb[k] ^ ((h_bb[k] >> 31) ? 0x80000000u : 0xffffffffu);
-      std::memcpy(&box[k], &b, 4);
-    }
+    for (int k = 0; k < 4; k++) box[k] = unordered(h_bb[k]);
   }
   float grow = 0.f, reach = 0.f;
   for (uint32_t i = 0; i < o->n_insets; i++) {
@@ -1138,7 +1151,7 @@ int offset_prepare(const gsdf_contour* c, const gsdf_offset_opts* o, hipStream_t
   plan->tiles_y = (unsigned)((ny + OFFSET_TILE - 1) / OFFSET_TILE);
   // the layers' edges: a layer's loops, and with them its vertices, are contiguous (loop_layer is non-decreasing)
   std::vector<unsigned> h_start(NL + 1, 0u), h_layer(NL, 0u), h_edge((size_t)L + 1, (unsigned)V);
-  if (!dev_alloc(ws.layer_edge, (uint64_t)L + 1) || !dev_alloc(ws.loop_of, V) || !dev_alloc(ws.edges, V)) return fail(GSDF_ERR_HIP, "offset: no device memory for the workspace");
+  if (!dev_alloc(ws.layer_edge, (uint64_t)L + 1) || !dev_alloc(ws.loop_of, V) || !dev_alloc(ws.edges, V)) return fail(GSDF_ERR_HIP, kOffsetNoMem);
   if (V > 0 && NL > 0) {
     HIP_TRY(hipMemcpyAsync(h_start.data(), c->loop_start.p, (size_t)(NL + 1) * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(h_layer.data(), c->loop_layer.p, (size_t)NL * 4, hipMemcpyDeviceToHost, s));
@@ -1149,8 +1162,8 @@ int offset_prepare(const gsdf_contour* c, const gsdf_offset_opts* o, hipStream_t
       h_edge[l] = q < NL ? h_start[q] : (unsigned)V;
     }
     h_edge[L] = (unsigned)V;
-    LAUNCH(cloop_of_kernel, blocks_of(V), s, (const unsigned*)c->loop_start.p, (unsigned)NL, (unsigned)V, ws.loop_of.p);
-    LAUNCH(offset_edges_kernel, blocks_of(V), s, (const float*)c->xy.p, (const unsigned*)c->loop_start.p, (const unsigned*)ws.loop_of.p, (unsigned)V, ws.edges.p);
+    LAUNCH(cloop_of_kernel, blocks_of(V), s, c->loop_start.p, (unsigned)NL, (unsigned)V, ws.loop_of.p);
+    LAUNCH(offset_edges_kernel, blocks_of(V), s, c->xy.p, c->loop_start.p, ws.loop_of.p, (unsigned)V, ws.edges.p);
   }
   HIP_TRY(hipMemcpyAsync(ws.layer_edge.p, h_edge.data(), ((size_t)L + 1) * 4, hipMemcpyHostToDevice, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -1179,56 +1192,36 @@ extern "C" int gsdf_hip_contour_offset(const gsdf_contour* c, const gsdf_offset_
   if (L_out >= ((uint64_t)1 << 32)) return fail(GSDF_ERR_CAPACITY, "offset: 2^32 output layers or more");
 
   HIP_TRY(hipSetDevice(c->device));
-  Stream stream;  // (ahead of the workspaces: the work on it is over before the buffers go, and it goes last)
-  HIP_TRY(stream.ensure());
-  hipStream_t s = stream.s;
-  std::deque<Part> parts;
-  Workspace w;
+  gsdf_contour_stats st{};
+  Stream stream;
+  Tracer t{st};
   OffsetWs ws;
-  ContourPtr r(new (std::nothrow) gsdf_contour());
-  if (!r) return fail(GSDF_ERR_BAD_ARGUMENT, "out of memory");
-  r->device = c->device;
-  StreamDrain drain{s};
+  ContourPtr r;
+  Job job(stream);
+  if (int rc = job.open()) return rc;
+  hipStream_t s = job.s;
   OffsetPlan plan;
   if (int rc = offset_prepare(c, o, s, ws, &plan)) return rc;
   const ContourLattice& lat = plan.lat;
   const uint64_t N = plan.N, tiles = (uint64_t)plan.tiles_x * plan.tiles_y;
-  // input layers per chunk, each with all its insets: max_nodes nodes, at least one, and the chunk's slots below 2^32
-  const uint64_t max_nodes = o->max_nodes ? o->max_nodes : (uint64_t)GSDF_CONTOUR_DEFAULT_MAX_NODES;
-  uint64_t per_chunk = max_nodes / (N * K);
-  if (per_chunk < 1) per_chunk = 1;
-  if (per_chunk > (((uint64_t)1 << 31) - 1) / (N * K)) per_chunk = (((uint64_t)1 << 31) - 1) / (N * K);
-  if (per_chunk > L_in) per_chunk = L_in;
-  const char* nomem = "offset: no device memory for the workspace";
-  const uint64_t chunk_nodes = per_chunk * K * N, chunk_slots = 2 * chunk_nodes;
-  const unsigned slot_blocks = blocks_of(chunk_slots);
-  if (!dev_alloc(w.pos, chunk_slots) || !dev_alloc(w.dist, chunk_nodes) || !dev_alloc(w.succ, chunk_slots) || !dev_alloc(w.blk_cnt, slot_blocks) ||
-      !dev_alloc(w.blk_base, slot_blocks) || !dev_alloc(w.layer_base, per_chunk * K + 1) || !dev_alloc(w.totals, 3) || !dev_alloc(w.ctr, 1) || !dev_alloc(ws.D, per_chunk * N) ||
-      !dev_alloc(ws.ctr, 1))
-    return fail(GSDF_ERR_HIP, nomem);
-  if (w.ev.ensure() != hipSuccess) return fail(GSDF_ERR_HIP, "hipEventCreate failed");
-  HIP_TRY(hipMemsetAsync(w.ctr.p, 0, sizeof(ContourCounters), s));
+  // a chunk is whole input layers, each with all its insets
+  t.plan(lat, o->max_nodes ? o->max_nodes : (uint64_t)GSDF_CONTOUR_DEFAULT_MAX_NODES, K, L_in);
+  if (!dev_alloc(ws.D, t.per_chunk * N) || !dev_alloc(ws.ctr, 1)) return fail(GSDF_ERR_HIP, kOffsetNoMem);
+  if (int rc = t.alloc(job, 2, nullptr, 0, kOffsetNoMem)) return rc;
   HIP_TRY(hipMemsetAsync(ws.ctr.p, 0, sizeof(OffsetCounters), s));
 
-  gsdf_contour_stats& st = r->st;
-  st.nx = lat.nx;
-  st.ny = lat.ny;
-  st.n_layers = (uint32_t)L_out;
-  std::vector<unsigned> h_base(per_chunk * K + 1);
-  uint64_t largest_layer = 0;
-  for (uint64_t l0 = 0; l0 < L_in; l0 += per_chunk) {
-    const uint64_t Lc = L_in - l0 < per_chunk ? L_in - l0 : per_chunk;
+  for (uint64_t l0 = 0; l0 < L_in; l0 += t.per_chunk) {
+    const uint64_t Lc = L_in - l0 < t.per_chunk ? L_in - l0 : t.per_chunk;
     const uint64_t nodes = Lc * K * N;
     // 1. the field: D of the chunk's input layers, then every inset's lattice where the tracer reads its distances
-    HIP_TRY(hipEventRecord(w.ev[0], s));
+    HIP_TRY(hipEventRecord(job.ev[0], s));
     const unsigned tile_blocks = (unsigned)(tiles * Lc);  // (tiles <= N: below 2^31 with the chunk's nodes)
-    LAUNCH(offset_tile_kernel, tile_blocks, s, lat, (const float4*)ws.edges.p, (const unsigned*)ws.layer_edge.p, (unsigned)l0, plan.tiles_x, plan.tiles_y, plan.band, ws.D.p,
-           ws.ctr.p);
-    LAUNCH(offset_field_kernel, blocks_of(nodes), s, (const float*)ws.D.p, (unsigned)N, (unsigned)K, plan.insets, (unsigned long long)nodes, w.dist.p);
+    LAUNCH(offset_tile_kernel, tile_blocks, s, lat, ws.edges.p, ws.layer_edge.p, (unsigned)l0, plan.tiles_x, plan.tiles_y, plan.band, ws.D.p, ws.ctr.p);
+    LAUNCH(offset_field_kernel, blocks_of(nodes), s, ws.D.p, (unsigned)N, (unsigned)K, plan.insets, (unsigned long long)nodes, t.w.dist.p);
     // 2 .. 5. trace
-    if (int rc = trace_chunk(w, s, lat, Lc * K, l0 * K, !dry, st, parts, h_base, &largest_layer)) return rc;
+    if (int rc = t.chunk(job, Lc * K, l0 * K, !dry)) return rc;
   }
-  if (int rc = trace_finish(w, s, st, largest_layer, parts, dry ? nullptr : r.get())) return rc;
+  if (int rc = t.finish(job, c->device, dry ? nullptr : &r)) return rc;
   OffsetCounters h_ctr{};
   HIP_TRY(hipMemcpyAsync(&h_ctr, ws.ctr.p, sizeof h_ctr, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -1256,21 +1249,18 @@ extern "C" int gsdf_hip_contour_distance(const gsdf_contour* c, const gsdf_offse
   if (layer >= c->st.n_layers) return fail(GSDF_ERR_BAD_ARGUMENT, "offset: layer " + std::to_string(layer) + " of a handle with " + std::to_string(c->st.n_layers) + " layers");
   HIP_TRY(hipSetDevice(c->device));
   Stream stream;
-  HIP_TRY(stream.ensure());
-  hipStream_t s = stream.s;
   OffsetWs ws;
-  EventSet<2> ev;
-  StreamDrain drain{s};
+  Job job(stream);
+  if (int rc = job.open()) return rc;
+  hipStream_t s = job.s;
   OffsetPlan plan;
   if (int rc = offset_prepare(c, o, s, ws, &plan)) return rc;
-  if (!dev_alloc(ws.D, plan.N) || !dev_alloc(ws.ctr, 1)) return fail(GSDF_ERR_HIP, "offset: no device memory for the workspace");
-  if (ev.ensure() != hipSuccess) return fail(GSDF_ERR_HIP, "hipEventCreate failed");
+  if (!dev_alloc(ws.D, plan.N) || !dev_alloc(ws.ctr, 1)) return fail(GSDF_ERR_HIP, kOffsetNoMem);
   OffsetCounters h_ctr{};
   HIP_TRY(hipMemsetAsync(ws.ctr.p, 0, sizeof(OffsetCounters), s));
-  HIP_TRY(hipEventRecord(ev[0], s));
-  LAUNCH(offset_tile_kernel, plan.tiles_x * plan.tiles_y, s, plan.lat, (const float4*)ws.edges.p, (const unsigned*)ws.layer_edge.p, (unsigned)layer, plan.tiles_x, plan.tiles_y,
-         plan.band, ws.D.p, ws.ctr.p);
-  HIP_TRY(hipEventRecord(ev[1], s));
+  HIP_TRY(hipEventRecord(job.ev[0], s));
+  LAUNCH(offset_tile_kernel, plan.tiles_x * plan.tiles_y, s, plan.lat, ws.edges.p, ws.layer_edge.p, (unsigned)layer, plan.tiles_x, plan.tiles_y, plan.band, ws.D.p, ws.ctr.p);
+  HIP_TRY(hipEventRecord(job.ev[1], s));
   HIP_TRY(hipMemcpyAsync(d_out, ws.D.p, (size_t)plan.N * 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(&h_ctr, ws.ctr.p, sizeof h_ctr, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -1279,7 +1269,7 @@ extern "C" int gsdf_hip_contour_distance(const gsdf_contour* c, const gsdf_offse
     offset_stats_of(plan, o, c->st.n_layers, &os);
     os.inside_nodes = h_ctr.inside_nodes;
     os.band_nodes = h_ctr.band_nodes;
-    os.ms_field = os.ms_device = event_ms(ev[0], ev[1]);
+    os.ms_field = os.ms_device = job.ms(0, 1);
     *st_out = os;
   }
   return GSDF_OK;

@@ -8,7 +8,8 @@
 //                 first use (spec_ensure), the report of what a handle launches. Host code only: it owns no kernel
 //   abi_mesh.hip  octree / flat / dual-contouring meshers and the mesh accessors
 //   abi_indexed.hip  indexed meshes: the gsdf_indexed handle, weld, PLY, report and extract
-//   abi_contour.hip  2-D outlines and z-slices traced into ordered closed loops
+//   abi_contour.hip  2-D outlines and z-slices traced into ordered closed loops; the loops uploaded, simplified, measured, hatched,
+//                 skin-classified and offset. One Job (stream, events, final wait) per call, one Tracer for every traced call
 //   abi_mass.cpp  principal axes of an inertia tensor (host only; without a HIP header, so that a plain C++ program can link it)
 //   abi_comm.cpp  multi-GPU: communicator (RCCL or the in-process loopback transport), gather plan, gatherv
 // (the list the library is built from: UNITS in __graft_entry__.py)
