@@ -14,7 +14,7 @@ LAYER_DTYPE = np.dtype([("length", "<f8"), ("n_segments", "<u8"), ("k_min", "<i4
 class Hatch:
     """seg (n, 4) float32, line n int32, layer_start n_layers + 1 uint32, layers LAYER_DTYPE records, stats (a dict with the fields
     of gsdf_hatch_stats before ms_device); and what the tests of the twin itself look at: t of every crossing, the crossings per
-    (layer, k) as line_counts."""
+    (layer, k) as line_counts, the sorted crossings as records."""
 
     def segments(self, layer):
         return self.seg[self.layer_start[layer]:self.layer_start[layer + 1]]
@@ -100,6 +100,7 @@ def hatch(c, spacing, dirs, offset=0.0):
         out.line_counts = np.zeros(0, np.int64)
         out.line_ids = np.zeros((0, 2), np.int64)
     out.t = t
+    out.records = (lay, k, uc, j)                       # every crossing's layer, line, u_c and tail vertex, in sorted order
     assert (out.line_counts % 2 == 0).all(), "a line with an odd number of crossings"
     # even counts on every line: the pairs of the whole sorted list are the pairs of the lines
     out.seg = np.stack([xc[0::2], yc[0::2], xc[1::2], yc[1::2]], axis=1).astype(F).reshape(-1, 4)

@@ -16,7 +16,8 @@ STATS_FIELDS = ("n_segments", "n_crossings", "n_own_crossings", "n_lines", "max_
 
 class Skin(H.Hatch):
     """A Hatch (seg, line, layer_start, layers: the layers' totals) with cls n uint8, skin_layers SKIN_LAYER_DTYPE records and the
-    stats of gsdf_skin_stats before ms_device; start_u / end_u: every piece's two values (what the tests of the twin look at)."""
+    stats of gsdf_skin_stats before ms_device; start_u / end_u: every piece's two values, records: the sorted crossings (what the tests
+    of the twin look at)."""
 
 
 def classes_of(mask, below, above):
@@ -92,6 +93,7 @@ def skin(c, spacing, dirs, below, above, offset=0.0):
     lay, k, r, j, uc, xc, yc, line_key = (a[order] for a in (lay, k, r, j, uc, xc, yc, line_key))
     out = Skin()
     out.exponent = e
+    out.records = (line_key, uc, r, j, xc, yc)          # every crossing's line, u_c, source, tail vertex and point, in sorted order
     if n:
         new_line = np.concatenate([[True], line_key[1:] != line_key[:-1]])
         new_value = new_line | np.concatenate([[True], uc[1:] != uc[:-1]])
